@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X-native RoI/mask inference hot path.
 
-`python bench.py --gpus N --steps K --warmup W`
+`python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]`
+  A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, `step_ms`); everything else
+  described below -- `value_resident` / `value_incl_h2d_f32` / `value_e2e`, `roofline` / `roofline_hbm`, `bs1`, `stage_ms_*`, `cpu_baseline`
+  and the parity check against the oracle, the embedded Mask R-CNN blocks, `stream_layout`, `box` and the RCCL record check -- runs with --full.
+  --dump-outputs DIR: after the timed steps, what the timed path computed in its last step, as a caller of that path receives it, goes to
+  DIR/<name>.npy (float32 / float64): the detections cut at each image's count, the prototypes, and the mask planes as per-detection areas
+  plus a fixed seeded sample of their pixels.  The inputs are seeded, so two builds can be compared output for output.
   N = 1: runs in this process.  N > 1 without a rank environment: this process only starts N child ranks (`python -m isegmi.launch
   --nproc N bench.py ...`, before any HIP call), relays rank 0's JSON line and exits with the children's code.  N > 1 inside a rank
   environment (RANK / WORLD_SIZE set, by isegmi.launch or by the driver's launcher): one rank per GPU.
@@ -13,12 +19,12 @@ to_image_list run on the device), image decode / resize is outside.  `value_resi
 record block per step back in pinned host memory (N = 1) or all-gathered over RCCL (N > 1).
 Default workload = BASELINE.json configs[1]: Yolact R50-FPN 550x550, bs=8 per GPU: backbone -> FPN -> protonet +
 prediction heads -> Detect (softmax, decode, fast-NMS) -> postprocess (mask assembly at 550x550, uint8)
-[-> RCCL all-gather of detection records when N>1].  At N=1 the default run ALSO measures BASELINE configs[2] /
+[-> RCCL all-gather of detection records when N>1].  At N=1 a --full run ALSO measures BASELINE configs[2] /
 north_star's own target (Mask R-CNN R50-FPN 1333x800: bs=2 throughput, bs=1 latency, conv roofline fraction, parity
 against the CPU oracle on the bench batch) and reports it under the "maskrcnn" key of the same JSON line.
 `--model maskrcnn [--depth 101] [--fp16] [--c4]` makes Mask R-CNN the measured workload itself.
 
-Prints ONE JSON line on rank 0 (contract in the task brief) with `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0; with --full it carries `roofline` and `cpu_baseline` too.
 """
 import argparse
 import ctypes as C
@@ -80,7 +86,16 @@ def parse():
     ap.add_argument("--param", action="append", default=[], metavar="NAME=VALUE", help="engine parameter for A/B runs (isegmi_engine_set_param), repeatable")
     ap.add_argument("--single-stream", action="store_true", help="profiling aid: run the timed region on one stream too, so that "
                     "rocprofv3 per-kernel durations are not inflated by overlapping launches (throughput drops ~20 %%)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run every measurement and check beyond the headline: the extra timed loops, "
+                    "rooflines, bs=1 latency, stage timings, CPU baseline + oracle parity, the embedded Mask R-CNN blocks, stream layout, box calibration "
+                    "(the --no-* switches above select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last step to DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not a.full:  # a plain run: set up, warm up, time the K steps, print the headline line
+        a.no_box = a.no_h2d = a.no_e2e = a.no_latency = a.no_cpu_baseline = a.no_maskrcnn = True
+    return a
 
 
 _JSON_FD = None
@@ -382,6 +397,52 @@ def roofline_dict(kernel, flops, ms, launches, steps, peak, traffic_file):
             "launches_per_step": launches // max(steps, 1), "avg_launch_us": round(ms * 1e3 / max(launches, 1), 2)}
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6  # --dump-outputs: at most 64 MB in all
+DUMP_WHOLE_ELEMENTS = 6 << 20  # an output with more elements than this is dumped as a fixed seeded sample ...
+DUMP_SAMPLE_ELEMENTS = 4 << 20  # ... of this many elements
+
+
+def caller_outputs(net, batch, per_detection, whole=(), masks="det.masks"):
+    """What a caller of the timed path receives for the batch of its last step (call right after the timed region): the per-detection
+    arrays with every image's rows past its detection count zeroed, the per-image arrays `whole`, and the uint8 mask planes as each
+    detection's area (every pixel counted) next to a fixed seeded sample of their pixels."""
+    count = net.fetch("det.count", batch)
+    out = {"det.count": count}
+    for k in tuple(per_detection) + (masks,):
+        v = net.fetch(k, batch)
+        for i in range(batch):
+            v[i, int(count[i]):] = 0
+        out[k] = v
+    m = out.pop(masks)
+    out[masks + ".area"] = m.reshape(m.shape[0], m.shape[1], -1).sum(-1, dtype=np.int64)
+    out[masks] = m
+    for k in whole:
+        out[k] = net.fetch(k, batch)
+    return out
+
+
+def write_outputs(path, arrays):
+    """DIR/<name>.npy per output: floating types as float32 (float64 kept), integers as float64 (exact) or float32 (bytes); an output
+    larger than DUMP_WHOLE_ELEMENTS as DUMP_SAMPLE_ELEMENTS elements at fixed seeded flat positions (`<name>.sample.npy`)."""
+    os.makedirs(path, exist_ok=True)
+    files, total = {}, 0
+    for name, v in arrays.items():
+        v = np.asarray(v)
+        if v.size > DUMP_WHOLE_ELEMENTS:
+            idx = np.sort(np.random.default_rng(20261016).integers(0, v.size, DUMP_SAMPLE_ELEMENTS))
+            v, name = v.reshape(-1)[idx], name + ".sample"
+        if v.dtype.kind == "f":
+            v = v.astype(np.float64 if v.dtype == np.float64 else np.float32)
+        else:
+            v = v.astype(np.float32 if v.dtype.itemsize == 1 else np.float64)
+        files[name] = v
+        total += v.nbytes
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %.1f MB (limit %d MB)" % (total / 1e6, DUMP_LIMIT_BYTES // 10**6))
+    for name, v in files.items():
+        np.save(os.path.join(path, name + ".npy"), v)
+
+
 # ------------------------------------------------------------------------------------------------------------------ Yolact
 def bench_yolact(a, dist):
     from isegmi import _ffi
@@ -444,12 +505,16 @@ def bench_yolact(a, dist):
     full_sync()
     upload_u8(0)
     elapsed, step_ms = timed_region(net, step, full_sync, dist, a.steps)
-    # what the GPU produced for the bench batch through the timed path (device front end + forward + postprocess); compared with the oracle below
-    net.upload(imgs)
-    conv_flops, conv_ms, conv_launches, ops = roofline_pass(net, step_resident, full_sync, a.steps, a.single_stream)
-    gpu = {k: net.fetch(k, a.batch) for k in ("det.count", "det.prior", "det.class", "det.score", "det.box", "det.coeff", "det.masks", "det.box_int")}
+    dump = caller_outputs(net, a.batch, ("det.class", "det.score", "det.box", "det.coeff", "det.prior", "det.box_int") +
+                          (("det.mask_score",) if net.has_maskiou else ()), whole=("proto",)) if a.dump_outputs and rank == 0 else None
+    counts = net.fetch("det.count", a.batch)
+    if a.full:
+        # what the GPU produced for the bench batch through the timed path (device front end + forward + postprocess); compared with the oracle below
+        net.upload(imgs)
+        conv_flops, conv_ms, conv_launches, ops = roofline_pass(net, step_resident, full_sync, a.steps, a.single_stream)
+        gpu = {k: net.fetch(k, a.batch) for k in ("det.count", "det.prior", "det.class", "det.score", "det.box", "det.coeff", "det.masks", "det.box_int")}
     rccl = None
-    if gather is not None:
+    if gather is not None and a.full:
         from isegmi.dist import unpack_records
         blocks = gather.fetch()
         rccl = {"rccl_ranks": int(gather.world), "ranks_with_records": int(sum(1 for r in range(world) if unpack_records(blocks[r], a.batch)["count"].any()))}
@@ -494,10 +559,11 @@ def bench_yolact(a, dist):
     net.upload(imgs)
     full_sync()
     pin8.free()
-    counts = gpu["det.count"]
     value = a.batch * world * a.steps / elapsed
     if rank != 0:
         return None, net, gather
+    if dump is not None:
+        write_outputs(a.dump_outputs, dump)
     fp16_note = "fp16 storage / f16 MFMA, fp32 accumulate (optional mode, not configs[1])" if a.fp16 else "fp32"
     out = {
         "metric": "images/sec (%s %dx%d, bs=%d per GPU, %s)" % (yname, size, size, a.batch, fp16_note),
@@ -509,9 +575,6 @@ def bench_yolact(a, dist):
                    "global_batch": a.batch * world, "parallelism": "batch-sharded x%d, RCCL all-gather of detections" % world,
                    "detections_per_image_rank0": [int(c) for c in counts]},
         "value_note": "SURVEY 8(d): the H2D of every batch is inside the step (%.1f MB of uint8 images per batch through pinned memory on a copy stream, double-buffered; the transform runs on the engine's stream); results stay on the device (value_e2e ships them)" % (raw_u8.nbytes / 1e6),
-        "roofline": roofline_dict(("conv_f16_glds / conv3x3_f16_strip kernels (all conv launches of a step, v_mfma_f32_32x32x16_f16)" if a.fp16 else
-                                   "conv_mfma_v2_kernel + conv_mfma16_kernel + conv_mfma_kernel (all conv launches of a step; v_mfma_f32_32x32x2_f32 on 64x64 tiles, v_mfma_f32_16x16x4_f32 on the 32x32 / 32x64 blocks of small grids)"),
-                                  conv_flops, conv_ms, conv_launches, a.steps, ypeak, None if (a.fp16 or a.yolact_config != "resnet50") else "pmc_yolact.json"),
         "step_ms": {"mean": round(elapsed / a.steps * 1e3, 3), "p50": round(pct(step_ms, 0.5), 3), "p90": round(pct(step_ms, 0.9), 3),
                     "note": "intervals between consecutive per-step completion events on the results stream (pipelined multi-stream run)" +
                             ("; the RCCL all-gather of the step runs on that stream in front of its mark, so it is inside these intervals" if gather is not None else "")},
@@ -532,14 +595,18 @@ def bench_yolact(a, dist):
                                   " / all-gathered over RCCL" if gather is not None else "", int(a.batch * 100 * size * size / 1e6))}
     if rccl:
         out.update(rccl)
-    traffic = hbm_traffic("hbm_stage_traffic_yolact.json") if (a.yolact_config == "resnet50" and not a.fp16 and a.batch == 8) else None
-    hbm = hbm_rooflines(ops, a.steps, traffic)
-    if rle_op:
-        hbm += hbm_rooflines(rle_op, 5, traffic)   # (the front end's counter bytes are per launch, as its algorithmic bytes are)
-    out["roofline_hbm"] = hbm
-    out["roofline_hbm_note"] = ("SURVEY 8(d) HBM-bound stages, per step of %d images, in the single-stream pass of `roofline`: achieved = ALGORITHMIC bytes (each "
-                                "stage's compulsory reads + writes, SURVEY 8d) / HIP-event time on the launching stream; peak 8 TB/s (spec); frac well under 1 on a "
-                                "latency-bound selection stage says its grid is small, not that it moves many bytes" % a.batch)
+    if a.full:
+        out["roofline"] = roofline_dict(("conv_f16_glds / conv3x3_f16_strip kernels (all conv launches of a step, v_mfma_f32_32x32x16_f16)" if a.fp16 else
+                                         "conv_mfma_v2_kernel + conv_mfma16_kernel + conv_mfma_kernel (all conv launches of a step; v_mfma_f32_32x32x2_f32 on 64x64 tiles, v_mfma_f32_16x16x4_f32 on the 32x32 / 32x64 blocks of small grids)"),
+                                        conv_flops, conv_ms, conv_launches, a.steps, ypeak, None if (a.fp16 or a.yolact_config != "resnet50") else "pmc_yolact.json")
+        traffic = hbm_traffic("hbm_stage_traffic_yolact.json") if (a.yolact_config == "resnet50" and not a.fp16 and a.batch == 8) else None
+        hbm = hbm_rooflines(ops, a.steps, traffic)
+        if rle_op:
+            hbm += hbm_rooflines(rle_op, 5, traffic)   # (the front end's counter bytes are per launch, as its algorithmic bytes are)
+        out["roofline_hbm"] = hbm
+        out["roofline_hbm_note"] = ("SURVEY 8(d) HBM-bound stages, per step of %d images, in the single-stream pass of `roofline`: achieved = ALGORITHMIC bytes (each "
+                                    "stage's compulsory reads + writes, SURVEY 8d) / HIP-event time on the launching stream; peak 8 TB/s (spec); frac well under 1 on a "
+                                    "latency-bound selection stage says its grid is small, not that it moves many bytes" % a.batch)
     if not a.no_latency:
         out["bs1"] = latency_pass(net, lambda: (net.forward_device(1), net.postprocess_device(size, size)))
         f1, m1, l1, _ = roofline_pass(net, lambda i: (net.forward_device(1), net.postprocess_device(size, size)), full_sync, 10, a.single_stream)
@@ -668,12 +735,15 @@ def bench_maskrcnn(a, dist, summary=None):
     full_sync()
     upload_u8(0)
     elapsed, step_ms = timed_region(model, step, full_sync, dist, steps)
-    model.upload(x, hw)
-    flops, ms, launches, ops = roofline_pass(model, step_resident, full_sync, steps, a.single_stream)
-    names = ("det.count", "det.score", "det.label", "det.box", "det.mask14" if c4 else "det.mask28", "det.masks", "proposal_count", "proposals")
-    gpu = {k: model.fetch(k, batch) for k in names}
+    dump = caller_outputs(model, batch, ("det.score", "det.label", "det.box", "det.mask14" if c4 else "det.mask28")) if a.dump_outputs and rank == 0 and not summary else None
+    gpu = {k: model.fetch(k, batch) for k in ("det.count", "proposal_count")}
+    if a.full:
+        model.upload(x, hw)
+        flops, ms, launches, ops = roofline_pass(model, step_resident, full_sync, steps, a.single_stream)
+        names = ("det.count", "det.score", "det.label", "det.box", "det.mask14" if c4 else "det.mask28", "det.masks", "proposal_count", "proposals")
+        gpu = {k: model.fetch(k, batch) for k in names}
     rccl = None
-    if gather is not None:
+    if gather is not None and a.full:
         from isegmi.dist import unpack_maskrcnn_records
         blocks = gather.fetch()
         rccl = {"rccl_ranks": int(gather.world), "ranks_with_records": int(sum(1 for r in range(world) if unpack_maskrcnn_records(blocks[r], batch, M=14 if c4 else 28)["count"].any()))}
@@ -719,10 +789,9 @@ def bench_maskrcnn(a, dist, summary=None):
     pin8.free()
     if rank != 0:
         return None, model, gather
+    if dump is not None:
+        write_outputs(a.dump_outputs, dump)
     value = batch * world * steps / elapsed
-    traffic_file = "pmc_r101f16.json" if (fp16 and depth == 101 and batch == 8 and not c4) else None if (fp16 or c4 or depth != 50 or batch != 2) else "pmc_maskrcnn.json"
-    roof = roofline_dict("conv_f16_glds / conv3x3_f16_strip kernels (all conv launches of a step)" if fp16 else "conv_mfma_v2_kernel + conv_mfma16_kernel + conv_mfma_kernel (all conv launches of a step)",
-                         flops, ms, launches, steps, peak, traffic_file)
     workload = ("Mask R-CNN %s 1333x800 (padded 800x1344) bs=%d/GPU random weights, %s: uint8 upload + conv1-4 + single-map RPN (6000 -> 1000) + RoIAlign + conv5 head + NMS + shared-extractor mask branch + paste (the README.md:263-273 config; not a BASELINE config)" % (tag, batch, prec)) if c4 else \
         "Mask R-CNN %s 1333x800 (padded 800x1344) bs=%d/GPU random weights, %s: uint8 upload + mean/pad on the device + backbone+FPN+RPN+RoIAlign+box head+NMS+mask head+paste (BASELINE configs[%d])" % (tag, batch, prec, 4 if fp16 else 2)
     out = {"metric": "images/sec (Mask R-CNN %s 1333x800, bs=%d per GPU, %s)" % (tag, batch, prec),
@@ -731,7 +800,6 @@ def bench_maskrcnn(a, dist, summary=None):
            "dtype": "f16" if fp16 else "f32", "data": "synthetic",
            "config": {"workload": workload, "global_batch": batch * world, "parallelism": "batch-sharded x%d, RCCL all-gather of detection records" % world,
                       "proposals_per_image": [int(c) for c in gpu["proposal_count"]], "detections_per_image": [int(c) for c in gpu["det.count"]]},
-           "roofline": roof,
            "step_ms": {"mean": round(elapsed / steps * 1e3, 3), "p50": round(pct(step_ms, 0.5), 3), "p90": round(pct(step_ms, 0.9), 3),
                        "note": "intervals between consecutive per-step completion events on the results stream (pipelined multi-stream run)" +
                                ("; the RCCL all-gather of the step runs on that stream in front of its mark, so it is inside these intervals" if gather is not None else "")},
@@ -749,17 +817,22 @@ def bench_maskrcnn(a, dist, summary=None):
                           " / all-gathered over RCCL" if gather is not None else "", int(batch * 100 * 800 * 1333 / 1e6))}
     if rccl:
         out.update(rccl)
-    traffic = None
-    if not c4 and not fp16 and depth == 50 and batch == 2:
-        traffic = hbm_traffic("hbm_stage_traffic_maskrcnn.json")
-    elif not c4 and fp16 and depth == 101 and batch == 8:
-        traffic = hbm_traffic("hbm_stage_traffic_r101f16.json")
-    hbm = hbm_rooflines(ops, steps, traffic)
-    if rle_op:
-        hbm += hbm_rooflines(rle_op, 5, traffic)   # (the front end's counter bytes are per launch, as its algorithmic bytes are)
-    out["roofline_hbm"] = hbm
-    out["roofline_hbm_note"] = ("SURVEY 8(d) HBM-bound stages, per step of %d images, in the single-stream pass of `roofline`: achieved = ALGORITHMIC bytes / "
-                                "HIP-event time on the launching stream; peak 8 TB/s (spec)" % batch)
+    if a.full:
+        traffic_file = "pmc_r101f16.json" if (fp16 and depth == 101 and batch == 8 and not c4) else None if (fp16 or c4 or depth != 50 or batch != 2) else "pmc_maskrcnn.json"
+        roof = roofline_dict("conv_f16_glds / conv3x3_f16_strip kernels (all conv launches of a step)" if fp16 else "conv_mfma_v2_kernel + conv_mfma16_kernel + conv_mfma_kernel (all conv launches of a step)",
+                             flops, ms, launches, steps, peak, traffic_file)
+        out["roofline"] = roof
+        traffic = None
+        if not c4 and not fp16 and depth == 50 and batch == 2:
+            traffic = hbm_traffic("hbm_stage_traffic_maskrcnn.json")
+        elif not c4 and fp16 and depth == 101 and batch == 8:
+            traffic = hbm_traffic("hbm_stage_traffic_r101f16.json")
+        hbm = hbm_rooflines(ops, steps, traffic)
+        if rle_op:
+            hbm += hbm_rooflines(rle_op, 5, traffic)   # (the front end's counter bytes are per launch, as its algorithmic bytes are)
+        out["roofline_hbm"] = hbm
+        out["roofline_hbm_note"] = ("SURVEY 8(d) HBM-bound stages, per step of %d images, in the single-stream pass of `roofline`: achieved = ALGORITHMIC bytes / "
+                                    "HIP-event time on the launching stream; peak 8 TB/s (spec)" % batch)
     if not a.no_latency:
         model.upload(x[:1], hw[:1])
         out["bs1"] = latency_pass(model, lambda: (model.forward_device(1), model.paste_device(800, 1333)), iters=11, drop=3)
@@ -807,7 +880,8 @@ def bench_maskrcnn(a, dist, summary=None):
             ok &= np.array_equal(gpu["det.masks"][i, :c], pasted[i])
         out["parity_vs_oracle_on_bench_batch"] = bool(ok)
         out["parity_note"] = "%d images: proposals, detection count, score, label, box, 28x28 masks and the masks pasted at 800x1333 all bit-equal" % batch
-    out["stream_layout"] = stream_layout(model)
+    if a.full:
+        out["stream_layout"] = stream_layout(model)
     if summary:
         keep = {"workload": out["config"]["workload"], "img_per_s": out["value"], "batch": batch, "ms_per_step": out["ms_per_step"], "steps": steps, "warmup": warmup,
                 "dtype": out["dtype"], "step_ms": out["step_ms"], "bs1": out.get("bs1"), "roofline_hbm": out.get("roofline_hbm"),
@@ -848,7 +922,7 @@ def main():
         out, net, gather = bench_maskrcnn(a, dist)
     else:
         out, net, gather = bench_yolact(a, dist)
-    if out is not None and a.model == "yolact":
+    if out is not None and a.model == "yolact" and a.full:
         out["stream_layout"] = stream_layout(net)
     net.close()
     if out is not None and a.model == "yolact" and dist.world == 1 and not dist.on and not a.no_maskrcnn and a.yolact_config == "resnet50" and not a.fp16:

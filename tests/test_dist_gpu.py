@@ -182,7 +182,7 @@ def test_bench_multi_rank_code_path_on_one_gpu(ffi, model_args, launcher):
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
-    args = [os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-latency"] + model_args
+    args = [os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-latency"] + model_args
     env = dict(os.environ, ISEGMI_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0", PYTHONPATH=os.path.join(root, "instancesegmentation-jittor_amd"))
     if launcher == "isegmi.launch":
         cmd = [sys.executable, "-m", "isegmi.launch", "--nproc", "1", "--timeout", "500", "--init-timeout", "200"] + args

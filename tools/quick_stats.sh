@@ -4,7 +4,7 @@ set -e -o pipefail
 tag=$1; shift
 root=$(pwd); out=$root/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/qs_${tag} -o run -- python3 $root/bench.py $* --steps 10 --warmup 2 --no-cpu-baseline --no-latency --no-maskrcnn --no-h2d --single-stream > $out/qs_${tag}.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/qs_${tag} -o run -- python3 $root/bench.py $* --steps 10 --warmup 2 --full --no-cpu-baseline --no-latency --no-maskrcnn --no-h2d --single-stream > $out/qs_${tag}.log 2>&1
 cd $root
 rm -f $out/qs_${tag}/run_kernel_trace.csv
 python3 - <<EOF

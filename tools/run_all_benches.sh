@@ -5,7 +5,7 @@
 set -o pipefail
 out=gpurun_out
 mkdir -p $out
-run() { name=$1; shift; python bench.py "$@" > $out/all_$name.json 2> $out/all_$name.err; python - "$out/all_$name.json" <<'PY'
+run() { name=$1; shift; python bench.py --full "$@" > $out/all_$name.json 2> $out/all_$name.err; python - "$out/all_$name.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read())
 print("%-28s value %8.1f img/s (resident %8.1f, e2e %8.1f)  %7.3f ms/step  conv %6.1f TF/s (%.3f of peak)  bs1 %.2f ms  rle==host %s" % (
