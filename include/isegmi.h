@@ -381,13 +381,47 @@ int isegmi_rle_workspace(int N, int K, int plane_h, int plane_w, int cap_runs, i
                          int64_t* nruns_bytes, int64_t* tile_bytes, int64_t* len_bytes, int64_t* starts_bytes);
 int isegmi_op_rle_encode(const isegmi_rle_args* a, void* stream);
 
+/* ---- Pose2Seg pose-guided stages (csrc/pose2seg_ops.hip) ----
+ * Sizes are the model's: a 512 x 512 input, P2 = 128 x 128, 64 x 64 RoIs.  Keypoints are COCO's 17 (x, y, v) per person; instance r
+ * belongs to image d_roi_img[r].  All warps share one bilinear helper (zero padding, taps
+ * ((v00 wx0 + v01 wx1) wy0) + ((v10 wx0 + v11 wx1) wy1)); results are bit-identical to tests/pose2seg_ref.py. */
+typedef struct isegmi_p2s_image {
+    int64_t offset;                  /* byte offset of the image's [h][w][3] uint8 pixels in d_u8 */
+    int32_t h, w;
+    float minv[6];                   /* m1^-1 (input plane -> image pixels), row-major 2 x 3 */
+    int32_t reserved[2];
+} isegmi_p2s_image;
+/* input letterbox (m1): d_out [N][S][S][4] = ((warp(v) / 255 - mean3[c]) / std3[c], ..., 0), v of channel swap_rb ? 2 - c : c; round_u8:
+ * the warped value is rounded to u8 first (floor(v + 0.5) clamped to [0, 255]).  d_table [N] is a DEVICE array. */
+int isegmi_op_pose2seg_letterbox(const uint8_t* d_u8, const isegmi_p2s_image* d_table, int N, int S, const float* mean3, const float* std3,
+                                 int swap_rb, int round_u8, float* d_out, void* stream);
+/* pose template fit, fp64: d_kpts [R][17][3] image pixels, d_m1 [N][6] the images' letterbox matrices, d_templates [T][17][3] (x, y, weight)
+ * in align-frame pixels, T <= 64.  Outputs: d_m3 / d_G / d_mmask [R][6] fp32 (feature -> align, the pixel-space Affine-Align sampler matrix,
+ * image -> output), d_kalign [R][17][3] (keypoints in the align frame, v copied), d_fit [R][8] fp64 = (m3, error, template index or -1 for
+ * the fallback). */
+int isegmi_op_pose2seg_fit(const float* d_kpts, const int32_t* d_roi_img, int R, const double* d_m1, const float* d_templates, int T,
+                           int align_corners, float* d_m3, float* d_G, float* d_mmask, float* d_kalign, double* d_fit, void* stream);
+/* Affine-Align: d_feat [N][Hf][Wf][C] -> channels [0, C) of d_out [R][64][64][out_c]; C % 4 == 0 */
+int isegmi_op_pose2seg_align(const float* d_feat, int Hf, int Wf, int C, const int32_t* d_roi_img, const float* d_G, int R, float* d_out,
+                             int out_c, void* stream);
+/* skeleton features of d_kalign: channels [c0, c0 + 55) of d_out [R][64][64][out_c] (17 heatmaps, 19 limb vectors), zeros in
+ * [c0 + 55, c0 + 64); out_c == c0 + 64 */
+int isegmi_op_pose2seg_skeleton(const float* d_kalign, int R, float* d_out, int out_c, int c0, void* stream);
+/* softmax of d_logits [R][64][64][2] and the reverse warp of channel 1 at d_mmask: d_masks [N][K][Hmax][Wmax] u8 = p > 0.5 for slot (n, k),
+ * k < d_counts[n] (instance d_roi_off[n] + k), inside the image's own d_image_hw[n]; zeros elsewhere.  d_boxes [N][K][4] the tight xyxy box
+ * (right / bottom exclusive; an empty mask: zeros), d_scores = 1, d_labels = 1 on valid slots (0 elsewhere), d_count_out = d_counts.
+ * d_ws_box: [N][K][4] int32 workspace. */
+int isegmi_op_pose2seg_masks(const float* d_logits, const float* d_mmask, const int32_t* d_counts, const int32_t* d_roi_off,
+                             const int32_t* d_image_hw, int N, int K, int Hmax, int Wmax, int32_t* d_ws_box, uint8_t* d_masks, float* d_boxes,
+                             float* d_scores, int32_t* d_labels, int32_t* d_count_out, void* stream);
+
 /* ---- model engine ----
  * Replaces the model object the reference builds inside COCODemo(cfg, ...) (README.md:320-324)
  * and Yolact eval.py (README.md:243): weights are pushed per layer under their upstream
  * state-dict names with BN already folded to (scale, shift) by the Python host; activations,
  * workspaces and outputs live in named device buffers owned by the engine. */
 typedef struct isegmi_engine isegmi_engine;
-/* model_kind: 1 = Yolact R50-FPN, 2 = Mask R-CNN R50/R101-FPN.  H, W = network input size. */
+/* model_kind: 1 = Yolact R50-FPN, 2 = Mask R-CNN R50/R101-FPN, 3 = Pose2Seg (H = W = 512).  H, W = network input size. */
 int isegmi_engine_create(int model_kind, int max_batch, int H, int W, isegmi_engine** out);
 int isegmi_engine_destroy(isegmi_engine* e);
 int isegmi_engine_set_param(isegmi_engine* e, const char* name, float value);
@@ -416,6 +450,15 @@ int isegmi_maskrcnn_forward_canvas(isegmi_engine* e, const float* d_images_nhwc3
 /* Masker paste of the last forward into (out_h,out_w) planes; boxes first scaled by h_ratios_wh [N][2] =
  * (out_w/w_i, out_h/h_i) like BoxList.resize -> det.masks u8 [N][cap][out_h][out_w], det.box_resized */
 int isegmi_maskrcnn_paste(isegmi_engine* e, const float* h_ratios_wh, int out_h, int out_w);
+/* Pose2Seg test.py's model([img], [kpts]) (kind 3): d_u8_staging = the N images' [h][w][3] uint8 pixels back to back
+ * (h_sizes_hw [N][2]), d_kpts = their persons' COCO keypoints [R][17][3] fp32, image by image (h_counts [N], each <= param "max_instances",
+ * default 32, else ISEGMI_ERR_ARG); both may be the destinations of isegmi_engine_upload_async.  Letterbox, ResNet-FPN to P2, template fit,
+ * Affine-Align, skeleton features, SegModule, then det.masks u8 [N][K][Hmax][Wmax] (each image at its own size), det.box_resized (tight xyxy,
+ * right / bottom exclusive), det.score = 1, det.label = 1, det.count: isegmi_engine_rle and isegmi_engine_pack_coco_records work as for
+ * Mask R-CNN.  Intermediates: p2s.p2, p2s.roi, p2s.logits, p2s.fit.  Params: cat_skeleton, align_corners, warp_round_u8, swap_rb,
+ * fpn_bilinear; fp16 and graph are refused (ISEGMI_ERR_ARG). */
+int isegmi_pose2seg_forward(isegmi_engine* e, const uint8_t* d_u8_staging, const int32_t* h_sizes_hw, const float* d_kpts,
+                            const int32_t* h_counts, int N);
 /* postprocess (Y7): masks of the last forward at (out_h,out_w) -> det.masks u8, det.box_int i64 */
 int isegmi_yolact_postprocess(isegmi_engine* e, int out_h, int out_w);
 /* the same with image n assembled at ITS (h, w) = h_image_hw[n] inside a common plane of the batch's maximum size (a batch of images of

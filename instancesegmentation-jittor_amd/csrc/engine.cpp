@@ -1100,7 +1100,8 @@ extern "C" int isegmi_engine_stream_layout(isegmi_engine* h, int32_t* queue_clas
 
 extern "C" int isegmi_engine_create(int model_kind, int max_batch, int H, int W, isegmi_engine** out) {
     ARG_CHECK(out, "null out");
-    ARG_CHECK(model_kind == 1 || model_kind == 2, "model_kind: 1 yolact, 2 maskrcnn");
+    ARG_CHECK(model_kind == 1 || model_kind == 2 || model_kind == 3, "model_kind: 1 yolact, 2 maskrcnn, 3 pose2seg");
+    ARG_CHECK(model_kind != 3 || (H == 512 && W == 512), "pose2seg: the input plane is 512 x 512");
     ARG_CHECK(max_batch > 0 && H > 0 && W > 0, "sizes");
     isegmi_engine* h = new isegmi_engine();
     h->e.kind = model_kind; h->e.max_batch = max_batch; h->e.H = H; h->e.W = W;

@@ -39,7 +39,7 @@ struct StageTime {
 };
 
 struct Engine {
-    int kind = 0;  // 1 yolact, 2 maskrcnn
+    int kind = 0;  // 1 yolact, 2 maskrcnn, 3 pose2seg
     int max_batch = 0, H = 0, W = 0;       // H, W: the LARGEST network input (padded canvas) this engine serves
     int cur_H = 0, cur_W = 0;              // Mask R-CNN: padded canvas of the current forward (<= H, W; to_image_list pads each batch to its own size)
     int anchor_H = -1, anchor_W = -1;      // canvas the anchors.* buffers were generated for

@@ -5,10 +5,10 @@
 //
 // Record block of a batch of N images, K = detection capacity per image (byte offsets are multiples of 8):
 //   [status  i32 x 4]            total runs, total characters, overflow bits (1 runs, 2 characters: raise the "rle_cap_*" params), 0
-//   [box     N*K*4]              Mask R-CNN: f32 xyxy in ORIGINAL image coordinates (det.box_resized); Yolact: i64 xyxy (det.box_int)
+//   [box     N*K*4]              Mask R-CNN, Pose2Seg: f32 xyxy in ORIGINAL image coordinates (det.box_resized); Yolact: i64 xyxy (det.box_int)
 //   [count   i32 x N]
 //   [score   f32 x N*K]
-//   [label   i32 x N*K]          Mask R-CNN: 1..80; Yolact: class 0..79
+//   [label   i32 x N*K]          Mask R-CNN: 1..80; Yolact: class 0..79; Pose2Seg: 1
 //   [mscore  f32 x N*K]          YOLACT++ only (mask re-scoring)
 //   [str_off i32 x (N*K + 1)]    characters of slot (n, k): chars[str_off[n*K+k] .. str_off[n*K+k+1])
 //   [pad to 8]
@@ -27,7 +27,11 @@ int rle_encode_launch(const isegmi_rle_args* a, hipStream_t st);
     } while (0)
 
 int maskrcnn_det_cap(Engine& e);
-static int det_cap(Engine& e) { return e.kind == 1 ? (int)e.param("max_num_detections", 100) : maskrcnn_det_cap(e); }
+int pose2seg_det_cap(Engine& e);
+// Pose2Seg (kind 3) takes the Mask R-CNN record form (f32 boxes, i32 labels) with K = its max_instances
+static int det_cap(Engine& e) {
+    return e.kind == 1 ? (int)e.param("max_num_detections", 100) : e.kind == 3 ? pose2seg_det_cap(e) : maskrcnn_det_cap(e);
+}
 // Default RLE capacities per image: a blob mask costs ~2 runs per column it spans and ~1.7 characters per run, so K masks as wide as the
 // network canvas need ~4 K W runs; the fixed 256 Ki of round 3 was marginal at 640 px and short at 1500 px with K = 100.  An
 // overflow is not fatal any more (isegmi.pipeline.run_record_loop raises these parameters and redoes the step), this only makes it rare.
@@ -81,11 +85,11 @@ int eng_rle(Engine& e, const int32_t* h_image_hw) {
     a.N = N; a.K = K; a.plane_h = ph; a.plane_w = pw; a.cap_runs = rle_cap_runs(e); a.cap_chars = rle_cap_chars(e);
     a.d_masks = (const uint8_t*)mit->second.d;
     a.d_count = (const int32_t*)e.bufs["det.count"].d;
-    {   // the windows the paste / mask assembly kernel wrote next to the planes: only they are read
+    {   // the windows the paste / mask assembly kernel wrote next to the planes: only they are read (Pose2Seg writes whole planes and leaves none)
         auto wit = e.bufs.find("det.mask_window");
         if (wit != e.bufs.end() && wit->second.d != nullptr && wit->second.shape.size() == 3 && wit->second.shape[0] == N && wit->second.shape[1] == K)
             a.d_windows = (const int32_t*)wit->second.d;
-        else if (e.param("sparse_masks", 0.0f) != 0.0f) { set_error("rle: sparse_masks is set but the last postprocess / paste left no windows"); return ISEGMI_ERR_STATE; }
+        else if (e.kind != 3 && e.param("sparse_masks", 0.0f) != 0.0f) { set_error("rle: sparse_masks is set but the last postprocess / paste left no windows"); return ISEGMI_ERR_STATE; }
     }
     void* q;
     if (h_image_hw) {

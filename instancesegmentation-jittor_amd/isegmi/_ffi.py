@@ -680,3 +680,55 @@ def rle_encode(masks, count=None, image_hw=None, cap_runs=None, cap_chars=None, 
     check(lib().isegmi_op_rle_encode(C.byref(a), None))
     sync()
     return ro.numpy(), cn.numpy(), so.numpy(), ch.numpy().tobytes(), stt.numpy()
+
+
+# ---------------------------------------------------------------- Pose2Seg pose-guided stages (csrc/pose2seg_ops.hip)
+class P2sImage(C.Structure):
+    """isegmi_p2s_image: one image of a letterbox batch."""
+    _fields_ = [("offset", C.c_int64), ("h", C.c_int32), ("w", C.c_int32), ("minv", C.c_float * 6), ("reserved", C.c_int32 * 2)]
+
+
+_VP, _I32 = C.c_void_p, C.c_int
+_P2S_SIGS = {
+    "isegmi_op_pose2seg_letterbox": [_VP, _VP, _I32, _I32, C.POINTER(C.c_float), C.POINTER(C.c_float), _I32, _I32, _VP, _VP],
+    "isegmi_op_pose2seg_fit": [_VP, _VP, _I32, _VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP],
+    "isegmi_op_pose2seg_align": [_VP, _I32, _I32, _I32, _VP, _VP, _I32, _VP, _I32, _VP],
+    "isegmi_op_pose2seg_skeleton": [_VP, _I32, _VP, _I32, _I32, _VP],
+    "isegmi_op_pose2seg_masks": [_VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+}
+
+
+def p2s_fn(name):
+    """The Pose2Seg entry point `name` with its argtypes / restype declared: an ABI change raises instead of shifting arguments."""
+    f = getattr(lib(), name)
+    if f.argtypes is None:
+        f.argtypes = _P2S_SIGS[name]
+        f.restype = C.c_int
+    return f
+
+
+def p2s_letterbox(d_u8, d_table, N, S, mean3, std3, swap_rb, round_u8, d_out, stream=None):
+    m = (C.c_float * 3)(*[float(v) for v in mean3]); sd = (C.c_float * 3)(*[float(v) for v in std3])
+    check(p2s_fn("isegmi_op_pose2seg_letterbox")(_ptr(d_u8), _ptr(d_table), int(N), int(S), m, sd, int(bool(swap_rb)), int(bool(round_u8)),
+                                                 _ptr(d_out), stream))
+
+
+def p2s_fit(d_kpts, d_roi_img, R, d_m1, d_templates, T, align_corners, d_m3, d_G, d_mmask, d_kalign, d_fit, stream=None):
+    check(p2s_fn("isegmi_op_pose2seg_fit")(_ptr(d_kpts), _ptr(d_roi_img), int(R), _ptr(d_m1), _ptr(d_templates), int(T), int(bool(align_corners)),
+                                           _ptr(d_m3), _ptr(d_G), _ptr(d_mmask), _ptr(d_kalign), _ptr(d_fit), stream))
+
+
+def p2s_align(d_feat, Hf, Wf, Cc, d_roi_img, d_G, R, d_out, out_c, stream=None):
+    check(p2s_fn("isegmi_op_pose2seg_align")(_ptr(d_feat), int(Hf), int(Wf), int(Cc), _ptr(d_roi_img), _ptr(d_G), int(R), _ptr(d_out), int(out_c),
+                                             stream))
+
+
+def p2s_skeleton(d_kalign, R, d_out, out_c, c0, stream=None):
+    check(p2s_fn("isegmi_op_pose2seg_skeleton")(_ptr(d_kalign), int(R), _ptr(d_out), int(out_c), int(c0), stream))
+
+
+def p2s_masks(d_logits, d_mmask, d_counts, d_roi_off, d_image_hw, N, K, Hmax, Wmax, d_ws_box, d_masks, d_boxes, d_scores, d_labels, d_count_out,
+              stream=None):
+    check(p2s_fn("isegmi_op_pose2seg_masks")(_ptr(d_logits), _ptr(d_mmask), _ptr(d_counts), _ptr(d_roi_off), _ptr(d_image_hw), int(N), int(K),
+                                             int(Hmax), int(Wmax), _ptr(d_ws_box), _ptr(d_masks), _ptr(d_boxes), _ptr(d_scores), _ptr(d_labels),
+                                             _ptr(d_count_out), stream))

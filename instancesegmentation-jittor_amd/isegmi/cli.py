@@ -3,6 +3,7 @@
   python -m isegmi.cli eval --trained_model=weights.npz --score_threshold=0.15 --top_k=15 --image=in.png[:out.png]
   python -m isegmi.cli eval --trained_model=weights.npz --images=in_dir:out_dir [--output_coco_json=dets.json]
   python -m isegmi.cli test_net --config-file cfg.yaml [--images dir] [--output results.json]
+  python -m isegmi.cli pose2seg_test --weights random --anno person_keypoints.json --image-root DIR [--output segm.json] [--batch-size 8]
 
 `--trained_model` / `MODEL.WEIGHT` take the .npz written by tools/import_pth.py; the literal value `random` uses the
 seeded synthetic weights (there is no network to fetch the reference's .pth files).  Images are read with PIL.
@@ -137,7 +138,30 @@ def cmd_test_net(a):
     return results
 
 
-def main(argv=None):
+def cmd_pose2seg_test(a):
+    """Pose2Seg test.py (README section 2.2): images + COCO person keypoints -> COCO segmentation json (category 1, score 1.0)."""
+    from .pose2seg import Pose2Seg, Pose2SegConfig, read_person_keypoints, test
+    from .weights import pose2seg_state_dict
+    if a.weights in ("", "random", None):
+        sd = pose2seg_state_dict(1234)
+    elif a.weights.endswith(".npz"):
+        sd = dict(np.load(a.weights))
+    else:
+        raise SystemExit("%s: Pose2Seg takes .npz weights in this engine's names (importing last.pkl is out of scope)" % a.weights)
+    images, kps = read_person_keypoints(a.anno)
+    images = [im for im in images if im["id"] in kps]
+    _, _, local = _rank_world()
+    net = Pose2Seg(sd, Pose2SegConfig(), max_batch=a.batch_size, max_instances=a.max_instances, device=local)
+    results = test(net, lambda i: _load_image_bgr(os.path.join(a.image_root, images[i]["file_name"])), [kps[im["id"]] for im in images],
+                   [im["id"] for im in images], batch_size=a.batch_size)
+    net.close()
+    with open(a.output, "w") as f:
+        json.dump(results, f)
+    print("wrote %d person masks for %d images to %s" % (len(results), len(images), a.output))
+    return results
+
+
+def build_parser():
     ap = argparse.ArgumentParser(prog="isegmi.cli")
     sub = ap.add_subparsers(dest="cmd", required=True)
     e = sub.add_parser("eval", help="Yolact eval.py-style image evaluation")
@@ -157,8 +181,19 @@ def main(argv=None):
     t.add_argument("--group", default="canvas", choices=["canvas", "aspect"],
                    help="canvas: batch only images with the same padded canvas (every result equals the single-image result); aspect: upstream's ASPECT_RATIO_GROUPING")
     t.add_argument("opts", nargs=argparse.REMAINDER, default=[])
-    a = ap.parse_args(argv)
-    return cmd_eval(a) if a.cmd == "eval" else cmd_test_net(a)
+    p = sub.add_parser("pose2seg_test", help="Pose2Seg test.py-style evaluation: images + COCO person keypoints -> COCO segmentation json")
+    p.add_argument("--weights", default="random", help="random (seeded synthetic weights) or an .npz in this engine's names")
+    p.add_argument("--anno", required=True, help="COCO person_keypoints json")
+    p.add_argument("--image-root", dest="image_root", required=True)
+    p.add_argument("--output", default="segm.json")
+    p.add_argument("--batch-size", dest="batch_size", type=int, default=8)
+    p.add_argument("--max-instances", dest="max_instances", type=int, default=32)
+    return ap
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
+    return {"eval": cmd_eval, "test_net": cmd_test_net, "pose2seg_test": cmd_pose2seg_test}[a.cmd](a)
 
 
 if __name__ == "__main__":

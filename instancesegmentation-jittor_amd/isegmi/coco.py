@@ -126,7 +126,8 @@ def results_from_records(rec, image_ids, image_hw, kind, K=100, score_threshold=
     """One rank's unpacked record block (isegmi.dist.unpack_coco_records: the device-side output of a step) -> COCO result dicts, the
     same records maskrcnn_results / yolact_results build from host arrays: bbox conversion and category map here, `segmentation.counts`
     straight from the device-made strings.  image_ids / image_hw: per image slot of the batch (None id = an empty padding slot).
-    score_threshold / top_k (Yolact eval.py --score_threshold / --top_k): keep score > threshold, then the first top_k (score order)."""
+    score_threshold / top_k (Yolact eval.py --score_threshold / --top_k): keep score > threshold, then the first top_k (score order).
+    kind: 1 Yolact, 2 Mask R-CNN, 3 Pose2Seg (category 1, score 1.0, bbox = the mask's tight box)."""
     out = []
     count, box, score, label, so, chars = rec["count"], rec["box"], rec["score"], rec["label"], rec["str_off"], rec["chars"]
     ms = rec.get("mscore")
@@ -136,7 +137,10 @@ def results_from_records(rec, image_ids, image_hw, kind, K=100, score_threshold=
             continue
         h, w = int(image_hw[n][0]), int(image_hw[n][1])
         b = np.asarray(box[n, :c], np.float64)
-        if kind == 2:   # prepare_for_coco_detection: xyxy -> xywh with the legacy +1
+        if kind == 3:   # Pose2Seg test.py: every person is category 1; the tight mask box (right / bottom exclusive) as xywh
+            bb = np.stack([b[:, 0], b[:, 1], b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]], 1).tolist()
+            cats = [1] * c
+        elif kind == 2:   # prepare_for_coco_detection: xyxy -> xywh with the legacy +1
             bb = np.stack([b[:, 0], b[:, 1], b[:, 2] - b[:, 0] + 1.0, b[:, 3] - b[:, 1] + 1.0], 1).tolist()
             cats = [COCO_CATEGORY_IDS[int(l) - 1] for l in label[n, :c]]
         else:           # Detections.add_bbox: [x1, y1, w, h] rounded to 0.1

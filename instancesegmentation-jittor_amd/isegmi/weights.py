@@ -242,3 +242,61 @@ def maskrcnn_c4_state_dict(seed=1234):
     sd["roi_heads.mask.predictor.conv5_mask.bias"] = (rng.standard_normal(256) * 0.01).astype(np.float32)
     _conv_bias(rng, sd, "roi_heads.mask.predictor.mask_fcn_logits", 81, 256, 1, gain=C4_MASK_LOGIT_GAIN)
     return sd
+
+
+# Synthetic pose templates in the 64 x 64 align frame, COCO keypoint order (nose, eyes, ears, shoulders, elbows, wrists, hips, knees,
+# ankles; left before right).  NOT upstream's templates.json: an upright pose with the left arm raised, its mirror with left and right
+# swapped, and a crouch.  Weight 1 on every joint.
+_POSE_UPRIGHT = [(32, 8), (34, 6), (30, 6), (36, 7), (28, 7), (40, 16), (24, 16), (45, 22), (21, 26), (46, 14), (20, 35), (37, 36), (27, 36),
+                 (38, 47), (26, 47), (38, 58), (26, 58)]
+_POSE_CROUCH = [(32, 16), (34, 14), (30, 14), (36, 15), (28, 15), (40, 24), (24, 24), (43, 32), (21, 32), (40, 38), (24, 38), (37, 40), (27, 40),
+                (43, 48), (21, 48), (38, 58), (26, 58)]
+_COCO_FLIP = [0, 2, 1, 4, 3, 6, 5, 8, 7, 10, 9, 12, 11, 14, 13, 16, 15]
+
+
+def pose_templates():
+    up = np.array([(x, y, 1.0) for x, y in _POSE_UPRIGHT], np.float32)
+    mirror = up[_COCO_FLIP].copy()
+    mirror[:, 0] = 64.0 - mirror[:, 0]
+    crouch = np.array([(x, y, 1.0) for x, y in _POSE_CROUCH], np.float32)
+    return np.stack([up, mirror, crouch])
+
+
+def pose2seg_state_dict(seed=1234, cat_skeleton=True, width=64, blocks=(3, 4, 6, 3), fpn_channels=256, seg_width=64, seg_blocks=(10, 1)):
+    """Seeded synthetic Pose2Seg weights: a torchvision-form ResNet (backbone.conv1 / bn1 / layers.L.B.*), the FPN laterals and P2 output
+    conv (fpn.lateral2..5, fpn.output2..5), the SegModule (segnet.conv1 / bn1, segnet.stage1.B.* ten bottlenecks, segnet.stage2.0.* one,
+    segnet.conv_out 1x1 -> 2) and `pose_templates` [3][17][3] -- SYNTHETIC templates (pose_templates()), not upstream's templates.json.
+    The defaults are the paper's widths; the tests use narrower ones (the engine reads every width from the weight shapes)."""
+    rng = np.random.default_rng(seed)
+    sd = {}
+
+    def bneck(nm, cin, planes, proj):
+        sd[nm + ".conv1.weight"] = _conv(rng, planes, cin, 1); _bn(rng, sd, nm + ".bn1", planes)
+        sd[nm + ".conv2.weight"] = _conv(rng, planes, planes, 3); _bn(rng, sd, nm + ".bn2", planes)
+        sd[nm + ".conv3.weight"] = _conv(rng, planes * 4, planes, 1); _bn(rng, sd, nm + ".bn3", planes * 4, 0.25)
+        if proj:
+            sd[nm + ".downsample.0.weight"] = _conv(rng, planes * 4, cin, 1)
+            _bn(rng, sd, nm + ".downsample.1", planes * 4)
+
+    sd["backbone.conv1.weight"] = _conv(rng, width, 3, 7)
+    _bn(rng, sd, "backbone.bn1", width)
+    cin = width
+    for li, nb in enumerate(blocks):
+        planes = width << li
+        for b in range(nb):
+            bneck("backbone.layers.%d.%d" % (li, b), cin, planes, b == 0)
+            cin = planes * 4
+    for l in range(4):
+        _conv_bias(rng, sd, "fpn.lateral%d" % (l + 2), fpn_channels, (width * 4) << l, 1)
+        _conv_bias(rng, sd, "fpn.output%d" % (l + 2), fpn_channels, fpn_channels, 3)
+    cin = fpn_channels + (55 if cat_skeleton else 0)
+    sd["segnet.conv1.weight"] = _conv(rng, seg_width, cin, 7)
+    _bn(rng, sd, "segnet.bn1", seg_width)
+    cin = seg_width
+    for si, nb in enumerate(seg_blocks):
+        for b in range(nb):
+            bneck("segnet.stage%d.%d" % (si + 1, b), cin, seg_width, cin != seg_width * 4)
+            cin = seg_width * 4
+    _conv_bias(rng, sd, "segnet.conv_out", 2, cin, 1, bias_std=0.1)
+    sd["pose_templates"] = pose_templates()
+    return sd
