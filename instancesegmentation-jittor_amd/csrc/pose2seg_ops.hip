@@ -116,7 +116,7 @@ __global__ void __launch_bounds__(64) p2s_fit_kernel(const float* __restrict__ k
         const double x = (double)k[0], y = (double)k[1];
         s_kx[t] = (s_m21[0] * x + s_m21[1] * y) + s_m21[2];
         s_ky[t] = (s_m21[3] * x + s_m21[4] * y) + s_m21[5];
-        s_v[t] = k[2];
+        s_v[t] = isfinite(k[0]) && isfinite(k[1]) ? k[2] : 0.0f;   // a non-finite coordinate counts as not visible
     }
     __syncthreads();
     if (t < T) {

@@ -101,7 +101,7 @@ def fit(kpts, m1, templates, align_corners=0):
     m21 = mat3_mul(m2, mat3(m1))
     kx = [(m21[0] * float(p[0]) + m21[1] * float(p[1])) + m21[2] for p in kpts]
     ky = [(m21[3] * float(p[0]) + m21[4] * float(p[1])) + m21[5] for p in kpts]
-    v = [F32(p[2]) for p in kpts]
+    v = [F32(p[2]) if np.isfinite(p[0]) and np.isfinite(p[1]) else F32(0) for p in kpts]   # a non-finite coordinate counts as not visible
     tp = np.asarray(templates, F32)
     best, best_err, best_A = -1, 0.0, None
     for t in range(tp.shape[0]):

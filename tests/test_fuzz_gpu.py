@@ -137,3 +137,54 @@ def test_roi_align_fuzz_table_plain_oracle(ffi, K, seed, aligned, f16, PH, nonfi
         k = int(counts[n])
         assert np.array_equal(plain.reshape(ref.shape)[n, :k].astype(np.float32), ref[n, :k].astype(np.float32), equal_nan=True)
         assert np.array_equal(tabbed[n, :k].astype(np.float32), ref[n, :k].astype(np.float32), equal_nan=True)
+
+
+@settings(**SET)
+@given(seed=st.integers(0, 2 ** 31), n_img=st.integers(1, 3), T=st.integers(1, 64), align_corners=st.integers(0, 1),
+       kind=st.sampled_from(["plain", "invisible", "offframe", "duplicate", "nonfinite"]))
+def test_pose2seg_fuzz(ffi, seed, n_img, T, align_corners, kind):
+    """Pose2Seg fit -> align -> skeleton -> masks through the op entries, bit-exact against tests/pose2seg_ref.py: random image sizes and
+    person counts, invisible / off-frame / duplicated / non-finite keypoints, 1..64 templates, both align_corners"""
+    import pose2seg_fp64 as f64
+    import pose2seg_ref as ref
+    import pose2seg_run as run
+    from isegmi.weights import pose_templates
+    rng = np.random.default_rng(seed)
+    hws = [(int(rng.integers(1, 900)), int(rng.integers(1, 900))) for _ in range(n_img)]
+    counts = rng.integers(0, 6, n_img).astype(np.int32)
+    counts[0] = max(counts[0], 1)
+    k = np.concatenate([f64.persons(rng, c, h, w, invisible=0.6 if kind == "invisible" else 0.2) for c, (h, w) in zip(counts, hws)])
+    R = len(k)
+    if kind == "offframe":
+        k[..., :2] += rng.choice([-2.0, 0.0, 2.0], (R, 17, 2)).astype(np.float32) * max(max(hws))
+    elif kind == "duplicate" and R > 1:
+        k[1:] = k[0]
+    elif kind == "nonfinite":
+        bad = rng.uniform(size=(R, 17, 2)) < 0.15
+        k[..., :2][bad] = rng.choice(np.float32([np.nan, np.inf, -np.inf]), int(bad.sum()))
+    tp = pose_templates() if T == 3 else f64.random_templates(rng, T)
+    roi_img = np.repeat(np.arange(n_img), counts).astype(np.int32)
+    m3, G, mm, kal, fit = run.fit(ffi, k, roi_img, hws, tp, align_corners)
+    fits = [ref.fit(k[r], list(f64.m1_matrix(*hws[roi_img[r]])[:2].ravel()), tp, align_corners) for r in range(R)]
+    for r, f in enumerate(fits):
+        assert np.array_equal(fit[r, :6], f["m3"]) and fit[r, 6] == f["err"] and fit[r, 7] == f["t"], r
+        assert np.array_equal(G[r], f["G"]) and np.array_equal(mm[r], f["mmask"]) and np.array_equal(kal[r], f["kalign"], equal_nan=True), r
+    C = 8
+    feat = rng.standard_normal((n_img, 128, 128, C)).astype(np.float32)
+    got = run.align_skeleton(ffi, feat, roi_img, G, kal, C + 64)
+    for r in range(R):
+        assert np.array_equal(got[r, ..., :C], ref.affine_align(feat[roi_img[r]], G[r])), r
+        assert np.array_equal(got[r, ..., C:C + 55], ref.skeleton(kal[r])) and not got[r, ..., C + 55:].any(), r
+    logits = (rng.standard_normal((R, 64, 64, 2)) * 2).astype(np.float32)
+    K = int(counts.max())
+    M, B, S, L, cnt = run.masks(ffi, logits, mm, counts, hws, K)
+    r = 0
+    for n, (h, w) in enumerate(hws):
+        for j in range(K):
+            if j < counts[n]:
+                m, b = ref.reverse_warp(logits[r], mm[r], h, w)
+                assert np.array_equal(M[n, j, :h, :w], m) and np.array_equal(B[n, j], b), (n, j)
+                r += 1
+            else:
+                assert not M[n, j].any() and not B[n, j].any()
+    assert list(cnt) == list(counts)

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import pose2seg_ref as ref
+from isegmi.weights import pose_templates
 
 pytestmark = pytest.mark.gpu
 
@@ -267,4 +268,188 @@ def test_engine_records_kind3(ffi):
             assert np.array_equal(rec["box"][n, k], want["boxes"][n][k]) and rec["label"][n, k] == 1 and rec["score"][n, k] == 1.0
     res = results_from_records(rec, [5, 6, 7, None], hw + [(1, 1)], 3, K)
     assert [(d["image_id"], d["segmentation"]) for d in res] == [(i, rle_encode(m)) for i, ms in zip((5, 6, 7), want["masks"]) for m in ms]
+    net.close()
+
+
+# ---------------------------------------------------------------------------------------------------- paper widths, edges, capacity
+def test_paper_widths_end_to_end_bitexact(ffi):
+    """the default widths (ResNet-50 3-4-6-3, FPN 256, SegModule 10-1, a 320-channel RoI tensor); the test's own copy of the seeded
+    weights moves segnet.conv_out.bias[1] so the masks are neither empty nor full"""
+    from isegmi.pose2seg import Pose2Seg, Pose2SegConfig
+    from isegmi.weights import pose2seg_state_dict
+    import pose2seg_fp64 as f64
+    sd = dict(pose2seg_state_dict(11))
+    rng = np.random.default_rng(29)
+    imgs = [rng.integers(0, 256, hw + (3,), np.uint8) for hw in ((480, 640), (640, 427), (300, 301))]
+    K = 8
+    tp = pose_templates()
+    kps = [f64.posed_persons(rng, 5, 480, 640, tp), f64.posed_persons(rng, K, 640, 427, tp), f64.posed_persons(rng, 6, 300, 301, tp)]
+    cfg = Pose2SegConfig()
+    net = Pose2Seg(sd, cfg, max_batch=3, max_instances=K)
+    net.forward(imgs, kps)
+    lg = net.read("logits", (19, 64, 64, 2))
+    net.close()
+    sd["segnet.conv_out.bias"] = sd["segnet.conv_out.bias"].copy()
+    sd["segnet.conv_out.bias"][1] += np.float32(-np.median(lg[..., 1] - lg[..., 0]))
+    net = Pose2Seg(sd, cfg, max_batch=3, max_instances=K)
+    masks = net(imgs, kps)
+    _, boxes = net.collect()
+    want = ref.forward(sd, imgs, kps, cfg)
+    for name in ("p2", "roi", "logits"):
+        assert np.array_equal(net.read(name, want[name].shape), want[name]), name
+    fg = (want["logits"][..., 1] > want["logits"][..., 0]).mean()
+    assert 0.1 < fg < 0.9, fg
+    for n in range(3):
+        for k in range(len(kps[n])):
+            assert np.array_equal(masks[n][k], want["masks"][n][k]) and np.array_equal(boxes[n][k], want["boxes"][n][k]), (n, k)
+    assert all(m.any() and not m.all() for ms in masks for m in ms)
+    net.close()
+
+
+@pytest.mark.parametrize("T,align_corners", [(1, 0), (64, 1), (3, 0)])
+def test_fit_edges_bitexact(ffi, T, align_corners):
+    """T = 1 / 64 (random templates, some zero-weight joints, a duplicate), v in {-1, 1, 2}, +-1e5, duplicated persons, off-frame and
+    non-finite keypoints, R = 256"""
+    import pose2seg_fp64 as f64
+    import pose2seg_run as run
+    rng = np.random.default_rng(200 + T)
+    hws = [(480, 640), (333, 200), (1, 1)]
+    e = f64.edge_persons(rng, *hws[0])
+    k = np.concatenate([e, f64.persons(rng, 256 - len(e), *hws[1], invisible=0.3)])
+    k[-15:-10] = k[-20:-15]                                       # duplicated persons (one image)
+    roi_img = np.array([0] * len(e) + [1] * (256 - len(e) - 3) + [2] * 3, np.int32)
+    tp = pose_templates() if T == 3 else f64.random_templates(rng, T)
+    m3, G, mm, kal, fit = run.fit(ffi, k, roi_img, hws, tp, align_corners)
+    ts = []
+    for r in range(len(k)):
+        f = ref.fit(k[r], list(f64.m1_matrix(*hws[roi_img[r]])[:2].ravel()), tp, align_corners)
+        assert np.array_equal(fit[r, :6], f["m3"]) and fit[r, 6] == f["err"] and fit[r, 7] == f["t"], r
+        assert np.array_equal(G[r], f["G"]) and np.array_equal(mm[r], f["mmask"]) and np.array_equal(kal[r], f["kalign"], equal_nan=True), r
+        ts.append(f["t"])
+    assert -1 in ts and max(ts) >= 0
+    assert np.array_equal(fit[-15:-10], fit[-20:-15])
+
+
+def test_nonfinite_keypoints_fit_bitexact(ffi):
+    """a NaN / inf coordinate counts as not visible on the GPU as in the restatement: the fallback box of [NaN, one finite point] is the
+    8 px box of the finite point, not NaN and not a box stretched by the NaN"""
+    import pose2seg_run as run
+    k = np.zeros((3, 17, 3), np.float32)
+    k[0, 0] = (np.nan, 100, 2); k[0, 1] = (200, 120, 2)
+    k[1, 0] = (np.inf, 100, 2); k[1, 1] = (200, 120, 2); k[1, 2] = (210, -np.inf, 2)
+    k[2, :, :2] = np.random.default_rng(1).uniform(50, 400, (17, 2)); k[2, :, 2] = 2; k[2, 4, 0] = np.nan
+    hws = [(480, 640)]
+    tp = pose_templates()
+    m3, G, mm, kal, fit = run.fit(ffi, k, np.zeros(3, np.int32), hws, tp, 0)
+    for r in range(3):
+        f = ref.fit(k[r], ref.m1_of(*hws[0]), tp, 0)
+        assert np.array_equal(fit[r, :6], f["m3"]) and fit[r, 7] == f["t"] and np.array_equal(G[r], f["G"]), r
+        assert np.all(np.isfinite(fit[r, :6])) and np.all(np.isfinite(mm[r])), r
+        assert np.array_equal(kal[r], f["kalign"], equal_nan=True)
+    assert fit[0, 7] == fit[1, 7] == -1 and fit[0, 0] == fit[1, 0] == 8.0 and fit[2, 7] >= 0
+    assert kal[0, 0, 2] == 0 and kal[1, 2, 2] == 0 and kal[2, 4, 2] == 0 and kal[0, 1, 2] == 2
+
+
+def test_align_edges_bitexact(ffi):
+    """C = 4 and C = 256 into a wider row (out_c > C, no skeleton: channels past C untouched); samples exactly on -1, 0, W - 1 and W;
+    a NaN matrix samples nothing"""
+    import pose2seg_run as run
+    rng = np.random.default_rng(210)
+    G = np.float32([[1, 0, -1, 0, 1, 64], [1, 0, 65, 0, 1, -1], [0.5, 0, 0, 0, 0.5, 0], [np.nan] * 6, [1, 0, 64.5, 0, 1, 63.5]])
+    roi_img = np.array([0, 1, 0, 1, 0], np.int32)
+    for C, out_c in ((4, 4), (256, 320), (8, 12)):
+        feat = rng.standard_normal((2, 128, 128, C)).astype(np.float32)
+        got = run.align_skeleton(ffi, feat, roi_img, G, None, out_c, skeleton=False, fill=-7.0)
+        for r in range(len(G)):
+            assert np.array_equal(got[r, ..., :C], ref.affine_align(feat[roi_img[r]], G[r])), (C, r)
+        assert np.all(got[..., C:] == -7.0)
+        assert not got[3, ..., :C].any()
+
+
+def test_skeleton_edges_bitexact(ffi):
+    """zero-length and axis-aligned limbs, joints outside [0, 64), pixels at |perp| = 1 exactly and at e = 4.6052"""
+    import pose2seg_run as run
+    kal = np.zeros((4, 17, 3), np.float32)
+    kal[..., 2] = 2
+    kal[0, :, :2] = np.random.default_rng(3).uniform(-30, 94, (17, 2))            # many joints off the frame
+    kal[1, :, :2] = (30.0, 30.0)                                                      # every limb zero-length
+    kal[2, 5, :2] = (30.0, 10.0); kal[2, 6, :2] = (30.0, 50.0)                       # vertical: columns 29 / 31 at |perp| = 1
+    kal[2, 11, :2] = (10.0, 40.0); kal[2, 12, :2] = (55.0, 40.0)                     # horizontal
+    kal[2, 0, :2] = (np.float32(32.0) + np.float32(np.sqrt(2 * 9 * 4.6052)), 5.0)      # a pixel at the heatmap cut
+    kal[3, :, :2] = (-5.0, 70.0); kal[3, 0, :2] = (-0.5, 64.5)
+    got = run.align_skeleton(ffi, np.zeros((1, 128, 128, 4), np.float32), np.zeros(4, np.int32), np.zeros((4, 6), np.float32), kal, 68)
+    for r in range(4):
+        assert np.array_equal(got[r, ..., 4:59], ref.skeleton(kal[r])), r
+        assert not got[r, ..., 59:].any()
+    l = ref.LIMBS.index([6, 7])
+    assert got[2, 10:50, 30, 4 + 18 + 2 * l].all() and not got[2, :, 29, 4 + 17 + 2 * l:4 + 19 + 2 * l].any()
+
+
+def test_masks_edges_bitexact(ffi):
+    """N K = 65535 accepted and 65536 refused (tiny planes); Hmax and Wmax from different images, not multiples of 64; a 1 x 1 and a
+    3000 x 4000 image; logits of +-inf, NaN, equal pairs (p = 0.5 gives 0) and +-1e30"""
+    import pose2seg_run as run
+    from isegmi import _ffi
+    rng = np.random.default_rng(220)
+    lg = rng.standard_normal((3, 64, 64, 2)).astype(np.float32) * 3
+    mm = np.float32([[0.6, 0, 1, 0, 0.6, 2]] * 3)
+    M, B, S, L, cnt = run.masks(ffi, lg, mm, [1, 0, 2], [(1, 1), (2, 1), (1, 2)], 21845)
+    assert M.shape == (3, 21845, 2, 2) and list(cnt) == [1, 0, 2] and S[0, 0] == 1 and S[0, 1] == 0 and not M[0, 1:].any()
+    with pytest.raises(_ffi.IsegmiError, match="65535"):
+        run.masks(ffi, lg, mm, [1, 0], [(1, 1), (1, 1)], 32768)
+    special = rng.standard_normal((64, 64, 2)).astype(np.float32) * 1e30
+    special[:8] = np.inf; special[8:16, :, 0] = -np.inf; special[16:24, :32] = np.nan; special[24:40] = special[24:40, :, :1]   # equal pairs
+    special[40:48, :, 1] = -np.inf
+    lg = np.stack([special, lg[0], lg[1], lg[2]])
+    hw = np.array([[70, 30], [20, 130], [1, 1]], np.int32)
+    mm = np.float32([[0.9, 0.1, -2, -0.1, 0.9, 3], [1.5, 0, -10, 0, 1.5, 5], [0.5, 0, 0, 0, 0.5, 0], [64, 0, 0, 0, 64, 0]])
+    counts = np.array([2, 1, 1], np.int32)
+    M, B, S, L, cnt = run.masks(ffi, lg, mm, counts, hw, 3)
+    assert M.shape == (3, 3, 70, 130)
+    r = 0
+    for n in range(3):
+        h, w = hw[n]
+        for k in range(3):
+            if k < counts[n]:
+                m, b = ref.reverse_warp(lg[r], mm[r], h, w)
+                assert np.array_equal(M[n, k, :h, :w], m) and np.array_equal(B[n, k], b), (n, k)
+                r += 1
+            assert not M[n, k, h:].any() and not M[n, k, :, w:].any()
+    eq = np.full((1, 64, 64, 2), -2.5, np.float32)
+    M, B, *_ = run.masks(ffi, eq, np.float32([[1, 0, 0, 0, 1, 0]]), [1], [(64, 64)], 1)
+    assert not M.any() and not B.any()
+    big = np.zeros((1, 64, 64, 2), np.float32); big[0, 20:40, 10:50, 1] = 4
+    h, w = 3000, 4000
+    M, B, *_ = run.masks(ffi, big, np.float32([[64 / 4000, 0, 0, 0, 64 / 4000, 0]]), [1], [(h, w)], 2)
+    m, b = ref.reverse_warp(big[0], np.float32([64 / 4000, 0, 0, 0, 64 / 4000, 0]), h, w)
+    assert np.array_equal(M[0, 0], m) and np.array_equal(B[0, 0], b) and m.any() and not M[0, 1].any()
+
+
+def test_engine_back_to_back_changing_R(ffi):
+    """one engine, forwards with R = 7, 1, 0, max_batch * K (full capacity), 3: each equal to the restatement (stale or under-sized
+    reused buffers would show)"""
+    from isegmi.pose2seg import Pose2Seg, Pose2SegConfig
+    from isegmi.weights import pose2seg_state_dict
+    import pose2seg_fp64 as f64
+    sd = pose2seg_state_dict(41, **SMALL)
+    cfg = Pose2SegConfig()
+    K = 4
+    net = Pose2Seg(sd, cfg, max_batch=2, max_instances=K)
+    rng = np.random.default_rng(43)
+    for counts in ((4, 3), (1, 0), (0, 0), (K, K), (2, 1)):
+        imgs = [rng.integers(0, 256, (int(rng.integers(20, 200)), int(rng.integers(20, 200)), 3), np.uint8) for _ in counts]
+        kps = [f64.persons(rng, c, *im.shape[:2]) for c, im in zip(counts, imgs)]
+        masks = net(imgs, kps)
+        _, boxes = net.collect()
+        want = ref.forward(sd, imgs, kps, cfg)
+        assert net.last["R"] == sum(counts)
+        assert np.array_equal(net.read("p2", want["p2"].shape), want["p2"])
+        if sum(counts):
+            assert np.array_equal(net.read("roi", want["roi"].shape), want["roi"])
+            assert np.array_equal(net.read("logits", want["logits"].shape), want["logits"])
+        for n in range(2):
+            assert len(masks[n]) == counts[n]
+            for k in range(counts[n]):
+                assert np.array_equal(masks[n][k], want["masks"][n][k]) and np.array_equal(boxes[n][k], want["boxes"][n][k]), (counts, n, k)
+        assert list(net.read("count", (2,), np.int32)) == list(counts)
     net.close()
