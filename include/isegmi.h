@@ -525,6 +525,56 @@ int isegmi_engine_op_stats(isegmi_engine* e, char* names, int names_cap, double*
 /* per-layer text report (label, GFLOP, ms, TFLOP/s per line) accumulated under conv_timing; clears it */
 int isegmi_engine_conv_report(isegmi_engine* e, char* buf, int cap);
 
+/* ---- COCO evaluation on the device (csrc/cocoeval.hip) ----
+ * What of pycocotools' maskApi.c / cocoeval.py these restate (rleArea, rleToBbox, rleIou, bbIou, COCOeval.evaluateImg) is
+ * [UPSTREAM-RECALL -- unverified].  An RLE is its run counts as isegmi.coco.rle_from_string yields them: column-major, zeros first.
+ * M RLEs lie back to back in d_counts; d_off [M + 1] (int64) are their first runs; d_hw [M][2] = (h, w), h * w < 2^32.
+ *
+ * isegmi_op_rle_prefix: d_bounds[i] = end position of run i, d_cum[i] = set pixels in runs 0 .. i (both per RLE, same indexing as d_counts);
+ *   d_area [M] = set pixels; d_bbox [M][4] = tight box (x0, y0, x1, y1) INCLUSIVE, (0, 0, -1, -1) for an empty mask.
+ * isegmi_op_rle_iou: d_pairs [P][3] = (det RLE, gt RLE, crowd); d_out[p] = inter / union, inter / area(det) when crowd, exactly 0.0 when
+ *   inter == 0.  inter and the areas are integers; the only floating operation is one double division.  -1.0 marks a pair that is not
+ *   evaluable (an index outside [0, M), or two RLEs of different size).
+ * isegmi_op_bbox_iou: the same pair list over d_boxes [B][4] double xywh, in bbIou's operation order:
+ *   da = dw*dh; ga = gw*gh; w = min(dx+dw, gx+gw) - max(dx, gx), w <= 0 -> 0; h likewise; i = w*h; u = crowd ? da : (da + ga) - i; o = i / u. */
+int isegmi_coco_rle_prefix_bytes(int64_t total_runs, int M, int64_t* bounds_bytes, int64_t* cum_bytes, int64_t* area_bytes, int64_t* bbox_bytes);
+int isegmi_op_rle_prefix(const uint32_t* d_counts, const int64_t* d_off, const int32_t* d_hw, int M, uint32_t* d_bounds, uint32_t* d_cum,
+                         int64_t* d_area, int32_t* d_bbox, void* stream);
+int isegmi_op_rle_iou(const uint32_t* d_bounds, const uint32_t* d_cum, const int64_t* d_off, const int32_t* d_hw, const int64_t* d_area,
+                      const int32_t* d_bbox, int M, const int32_t* d_pairs, int64_t P, double* d_out, void* stream);
+int isegmi_op_bbox_iou(const double* d_boxes, int B, const int32_t* d_pairs, int64_t P, double* d_out, void* stream);
+/* isegmi_op_coco_match: evaluateImg's greedy matching, one sequential scan per (group, area range, IoU threshold).  A group is one
+ * (image, category) -- or one image with useCats = 0.  Group g owns detections [d_det_off[g], d_det_off[g + 1]) (already sorted by score, best
+ * first, and cut to maxDets[-1]), gts [d_gt_off[g], d_gt_off[g + 1]) and the row-major [D][G] IoU block at d_ious + d_iou_off[g].
+ * Rule per area range a = (lo, hi) and threshold t: gtIg = ignore | iscrowd | area < lo | area > hi; gts are visited non-ignored first, each
+ * part in input order; every det in turn starts with best = min(t, 1 - 1e-10), skips a gt matched at this t unless it is crowd, stops at the
+ * first ignored gt once it holds a non-ignored match, skips iou < best, else takes the gt and raises best.  A matched det inherits the gt's
+ * ignore flag; an unmatched det whose own area lies outside a is ignored.
+ * Outputs (sizes: isegmi_coco_match_bytes): d_dt_match [A][T][n_dets] = 1 + the gt's index inside its group (input order), 0 = unmatched
+ * (upstream stores the annotation id, so that a gt with id 0 looks unmatched: a deliberate deviation); d_dt_ignore [A][T][n_dets];
+ * d_gt_match [A][T][n_gts] = 1 + the det's index inside its group, 0 = unmatched; d_gt_ignore_out [A][n_gts]. */
+typedef struct isegmi_coco_match_args {
+    int32_t n_groups, A, T, reserved;
+    int64_t n_dets, n_gts, n_ious;
+    const int64_t* d_det_off;      /* [n_groups + 1] */
+    const int64_t* d_gt_off;       /* [n_groups + 1] */
+    const int64_t* d_iou_off;      /* [n_groups] */
+    const double* d_ious;          /* [n_ious] */
+    const double* d_det_area;      /* [n_dets] */
+    const double* d_gt_area;       /* [n_gts] */
+    const uint8_t* d_gt_crowd;     /* [n_gts] */
+    const uint8_t* d_gt_ignore;    /* [n_gts] */
+    const double* d_area_rng;      /* [A][2] */
+    const double* d_iou_thrs;      /* [T] */
+    int32_t* d_dt_match;
+    uint8_t* d_dt_ignore;
+    int32_t* d_gt_match;
+    uint8_t* d_gt_ignore_out;
+} isegmi_coco_match_args;
+int isegmi_coco_match_bytes(int64_t n_dets, int64_t n_gts, int A, int T, int64_t* dt_match_bytes, int64_t* dt_ignore_bytes,
+                            int64_t* gt_match_bytes, int64_t* gt_ignore_bytes);
+int isegmi_op_coco_match(const isegmi_coco_match_args* a, void* stream);
+
 /* ---- multi-GPU: images shard by batch, one process per GPU; the only exchange is one
  * RCCL all-gather of fixed-size records per batch (upstream analogue: the pickle all_gather of
  * {image_id: BoxList} in maskrcnn-benchmark engine/inference.py, reached from README.md:344-347). */

@@ -732,3 +732,162 @@ def p2s_masks(d_logits, d_mmask, d_counts, d_roi_off, d_image_hw, N, K, Hmax, Wm
     check(p2s_fn("isegmi_op_pose2seg_masks")(_ptr(d_logits), _ptr(d_mmask), _ptr(d_counts), _ptr(d_roi_off), _ptr(d_image_hw), int(N), int(K),
                                              int(Hmax), int(Wmax), _ptr(d_ws_box), _ptr(d_masks), _ptr(d_boxes), _ptr(d_scores), _ptr(d_labels),
                                              _ptr(d_count_out), stream))
+
+
+# ---------------------------------------------------------------- COCO evaluation on the device (csrc/cocoeval.hip)
+class CocoMatchArgs(C.Structure):
+    """isegmi_coco_match_args."""
+    _fields_ = [("n_groups", C.c_int32), ("A", C.c_int32), ("T", C.c_int32), ("reserved", C.c_int32),
+                ("n_dets", C.c_int64), ("n_gts", C.c_int64), ("n_ious", C.c_int64)] + \
+               [(n, C.c_void_p) for n in ("d_det_off", "d_gt_off", "d_iou_off", "d_ious", "d_det_area", "d_gt_area", "d_gt_crowd", "d_gt_ignore",
+                                          "d_area_rng", "d_iou_thrs", "d_dt_match", "d_dt_ignore", "d_gt_match", "d_gt_ignore_out")]
+
+
+_I64, _PI64 = C.c_int64, C.POINTER(C.c_int64)
+_COCO_SIGS = {
+    "isegmi_coco_rle_prefix_bytes": [_I64, _I32, _PI64, _PI64, _PI64, _PI64],
+    "isegmi_op_rle_prefix": [_VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP],
+    "isegmi_op_rle_iou": [_VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _I64, _VP, _VP],
+    "isegmi_op_bbox_iou": [_VP, _I32, _VP, _I64, _VP, _VP],
+    "isegmi_coco_match_bytes": [_I64, _I64, _I32, _I32, _PI64, _PI64, _PI64, _PI64],
+    "isegmi_op_coco_match": [C.POINTER(CocoMatchArgs), _VP],
+}
+
+
+def coco_fn(name):
+    """The COCO-evaluation entry point `name` with its argtypes / restype declared: an ABI change raises instead of shifting arguments."""
+    f = getattr(lib(), name)
+    if f.argtypes is None:
+        f.argtypes = _COCO_SIGS[name]
+        f.restype = C.c_int
+    return f
+
+
+class RleSet:
+    """M run-length encodings on the device, prefix-summed once (isegmi_op_rle_prefix): the operand of rle_iou.
+    counts_list: per RLE its run counts (column-major, zeros first, as isegmi.coco.rle_from_string yields them); hw [M][2] = (h, w).
+    .area [M] int64 and .bbox [M][4] int32 (x0, y0, x1, y1 inclusive; (0, 0, -1, -1) when empty) are downloaded on first use."""
+
+    def __init__(self, counts_list, hw, stream=None):
+        self.M = len(counts_list)
+        hw = np.ascontiguousarray(hw, np.int32).reshape(self.M, 2)
+        lens = np.fromiter((len(c) for c in counts_list), np.int64, self.M)
+        off = np.zeros(self.M + 1, np.int64)
+        np.cumsum(lens, out=off[1:])
+        total = int(off[-1])
+        flat = np.concatenate([np.asarray(c, np.int64).ravel() for c in counts_list]) if total else np.zeros(0, np.int64)
+        if total and (flat.min() < 0 or flat.max() >= 1 << 32):
+            raise IsegmiError("RLE run counts must fit uint32")
+        sz = [C.c_int64() for _ in range(4)]
+        check(coco_fn("isegmi_coco_rle_prefix_bytes")(total, self.M, *[C.byref(s) for s in sz]))
+        self.d_counts = DeviceBuffer.from_numpy(flat.astype(np.uint32))
+        self.d_off = DeviceBuffer.from_numpy(off)
+        self.d_hw = DeviceBuffer.from_numpy(hw)
+        self.d_bounds = DeviceBuffer((sz[0].value // 4,), np.uint32)
+        self.d_cum = DeviceBuffer((sz[1].value // 4,), np.uint32)
+        self.d_area = DeviceBuffer((sz[2].value // 8,), np.int64)
+        self.d_bbox = DeviceBuffer((sz[3].value // 16, 4), np.int32)
+        self.off, self.hw, self.total_runs = off, hw, total
+        self._area = self._bbox = None
+        import time
+        sync()
+        t0 = time.perf_counter()
+        self.prefix(stream)
+        sync()
+        self.prefix_seconds = time.perf_counter() - t0      # the prefix kernel alone, uploads excluded (tools/cocoeval_bench.py)
+
+    def prefix(self, stream=None):
+        check(coco_fn("isegmi_op_rle_prefix")(self.d_counts.ptr, self.d_off.ptr, self.d_hw.ptr, self.M, self.d_bounds.ptr, self.d_cum.ptr,
+                                              self.d_area.ptr, self.d_bbox.ptr, stream))
+
+    @property
+    def area(self):
+        if self._area is None:
+            sync()
+            self._area = self.d_area.numpy()
+        return self._area
+
+    @property
+    def bbox(self):
+        if self._bbox is None:
+            sync()
+            self._bbox = self.d_bbox.numpy()
+        return self._bbox
+
+    def free(self):
+        for b in (self.d_counts, self.d_off, self.d_hw, self.d_bounds, self.d_cum, self.d_area, self.d_bbox):
+            b.free()
+
+
+def rle_iou_device(rles, d_pairs, P, d_out, stream=None):
+    """isegmi_op_rle_iou over device buffers: d_pairs [P][3] int32 (det, gt, crowd) -> d_out [P] float64."""
+    check(coco_fn("isegmi_op_rle_iou")(rles.d_bounds.ptr, rles.d_cum.ptr, rles.d_off.ptr, rles.d_hw.ptr, rles.d_area.ptr, rles.d_bbox.ptr,
+                                       rles.M, _ptr(d_pairs), int(P), _ptr(d_out), stream))
+
+
+def rle_iou(rles, pairs):
+    """Host convenience: pairs [P][3] (det RLE, gt RLE, crowd) of an RleSet -> float64 [P]."""
+    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 3)
+    dp = DeviceBuffer.from_numpy(pairs); do = DeviceBuffer((len(pairs),), np.float64)
+    rle_iou_device(rles, dp, len(pairs), do)
+    sync()
+    out = do.numpy()
+    dp.free(); do.free()
+    return out
+
+
+def bbox_iou_device(d_boxes, B, d_pairs, P, d_out, stream=None):
+    check(coco_fn("isegmi_op_bbox_iou")(_ptr(d_boxes), int(B), _ptr(d_pairs), int(P), _ptr(d_out), stream))
+
+
+def bbox_iou(boxes, pairs):
+    """Host convenience: boxes [B][4] float64 xywh, pairs [P][3] (det box, gt box, crowd) -> float64 [P] in bbIou's operation order."""
+    boxes = np.ascontiguousarray(boxes, np.float64).reshape(-1, 4)
+    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 3)
+    db = DeviceBuffer.from_numpy(boxes); dp = DeviceBuffer.from_numpy(pairs); do = DeviceBuffer((len(pairs),), np.float64)
+    bbox_iou_device(db, len(boxes), dp, len(pairs), do)
+    sync()
+    out = do.numpy()
+    for b in (db, dp, do):
+        b.free()
+    return out
+
+
+def coco_match(det_off, gt_off, iou_off, ious, det_area, gt_area, gt_crowd, gt_ignore, area_rng, iou_thrs, d_ious=None, stream=None):
+    """isegmi_op_coco_match: -> (dt_match [A,T,n_dets] int32, dt_ignore [A,T,n_dets] uint8, gt_match [A,T,n_gts] int32, gt_ignore [A,n_gts] uint8).
+    ious: host float64 array, or None with d_ious = a DeviceBuffer that already holds the blocks (the output of rle_iou_device)."""
+    det_off = np.ascontiguousarray(det_off, np.int64); gt_off = np.ascontiguousarray(gt_off, np.int64)
+    iou_off = np.ascontiguousarray(iou_off, np.int64)
+    n_groups = len(iou_off)
+    assert len(det_off) == n_groups + 1 and len(gt_off) == n_groups + 1
+    area_rng = np.ascontiguousarray(area_rng, np.float64).reshape(-1, 2); iou_thrs = np.ascontiguousarray(iou_thrs, np.float64).ravel()
+    A, T = len(area_rng), len(iou_thrs)
+    n_dets, n_gts = int(det_off[-1]) if n_groups else 0, int(gt_off[-1]) if n_groups else 0
+    own = []
+
+    def up(a, dt):
+        b = DeviceBuffer.from_numpy(np.ascontiguousarray(a, dt))
+        own.append(b)
+        return b
+    if d_ious is None:
+        d_ious = up(np.asarray(ious, np.float64).ravel(), np.float64)
+    n_ious = d_ious.nbytes // 8
+    sz = [C.c_int64() for _ in range(4)]
+    check(coco_fn("isegmi_coco_match_bytes")(n_dets, n_gts, A, T, *[C.byref(s) for s in sz]))
+    o_dtm = DeviceBuffer((A, T, n_dets), np.int32); o_dti = DeviceBuffer((A, T, n_dets), np.uint8)
+    o_gtm = DeviceBuffer((A, T, n_gts), np.int32); o_gti = DeviceBuffer((A, n_gts), np.uint8)
+    own += [o_dtm, o_dti, o_gtm, o_gti]
+    assert [o_dtm.nbytes, o_dti.nbytes, o_gtm.nbytes, o_gti.nbytes] == [s.value for s in sz]
+    for b in (o_dtm, o_dti, o_gtm, o_gti):
+        if b.nbytes:
+            b.zero()
+    a = CocoMatchArgs(n_groups, A, T, 0, n_dets, n_gts, n_ious, up(det_off, np.int64).ptr, up(gt_off, np.int64).ptr, up(iou_off, np.int64).ptr,
+                      d_ious.ptr, up(det_area, np.float64).ptr, up(gt_area, np.float64).ptr, up(gt_crowd, np.uint8).ptr,
+                      up(gt_ignore, np.uint8).ptr, up(area_rng, np.float64).ptr, up(iou_thrs, np.float64).ptr,
+                      o_dtm.ptr, o_dti.ptr, o_gtm.ptr, o_gti.ptr)
+    check(coco_fn("isegmi_op_coco_match")(C.byref(a), stream))
+    sync()
+    out = (o_dtm.numpy(), o_dti.numpy(), o_gtm.numpy(), o_gti.numpy())
+    for b in own:
+        b.free()
+    return out

@@ -4,6 +4,9 @@
   python -m isegmi.cli eval --trained_model=weights.npz --images=in_dir:out_dir [--output_coco_json=dets.json]
   python -m isegmi.cli test_net --config-file cfg.yaml [--images dir] [--output results.json]
   python -m isegmi.cli pose2seg_test --weights random --anno person_keypoints.json --image-root DIR [--output segm.json] [--batch-size 8]
+  python -m isegmi.cli coco_eval --gt instances.json --dt results.json --iou-type segm|bbox [--cat-ids ...] [--max-dets ...] [--out stats.json]
+
+eval, test_net and pose2seg_test take an optional `--gt instances.json`: after writing their json they print the COCO AP / AR summary.
 
 `--trained_model` / `MODEL.WEIGHT` take the .npz written by tools/import_pth.py; the literal value `random` uses the
 seeded synthetic weights (there is no network to fetch the reference's .pth files).  Images are read with PIL.
@@ -110,6 +113,8 @@ def cmd_eval(a):
                 _save_image_bgr(dst, _load_image_bgr(src))
         if a.output_coco_json:
             dump(results, a.output_coco_json)
+        if a.gt:
+            _print_coco_summary(a.gt, results, ("bbox", "segm"))
     return results
 
 
@@ -135,6 +140,8 @@ def cmd_test_net(a):
             json.dump(results, f)
         print("wrote %d results for %d images to %s (%d steps of %d images on %d rank(s))" % (
             len(results), len(files), a.output, stats.get("steps", 0), a.batch_size, world))
+        if a.gt:
+            _print_coco_summary(a.gt, results, ("bbox", "segm"))
     return results
 
 
@@ -158,7 +165,26 @@ def cmd_pose2seg_test(a):
     with open(a.output, "w") as f:
         json.dump(results, f)
     print("wrote %d person masks for %d images to %s" % (len(results), len(images), a.output))
+    if a.gt:
+        _print_coco_summary(a.gt, results, ("segm",))
     return results
+
+
+def _print_coco_summary(gt_path, results, iou_types, cat_ids=None, max_dets=None):
+    """The COCO summary of a result list against an annotation file, as the reference's test commands print it."""
+    from .cocoeval import evaluate_results
+    if not results:
+        print("no results to evaluate")
+        return {}
+    return evaluate_results(gt_path, results, iou_types, cat_ids=cat_ids, max_dets=max_dets, verbose=True)
+
+
+def cmd_coco_eval(a):
+    stats = _print_coco_summary(a.gt, a.dt, (a.iou_type,), a.cat_ids, a.max_dets)
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump({k: [float(x) for x in v] for k, v in stats.items()}, f)
+    return stats
 
 
 def build_parser():
@@ -188,12 +214,21 @@ def build_parser():
     p.add_argument("--output", default="segm.json")
     p.add_argument("--batch-size", dest="batch_size", type=int, default=8)
     p.add_argument("--max-instances", dest="max_instances", type=int, default=32)
+    for q in (e, t, p):
+        q.add_argument("--gt", default=None, help="COCO annotation json: print the COCO AP / AR summary of the written results (isegmi.cocoeval)")
+    c = sub.add_parser("coco_eval", help="COCO AP / AR of a result json against an annotation json (pycocotools COCOeval restated)")
+    c.add_argument("--gt", required=True, help="COCO annotation json")
+    c.add_argument("--dt", required=True, help="COCO result json")
+    c.add_argument("--iou-type", dest="iou_type", default="segm", choices=["segm", "bbox"])
+    c.add_argument("--cat-ids", dest="cat_ids", type=int, nargs="+", default=None)
+    c.add_argument("--max-dets", dest="max_dets", type=int, nargs="+", default=None)
+    c.add_argument("--out", default=None, help="also write the twelve stats as json")
     return ap
 
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
-    return {"eval": cmd_eval, "test_net": cmd_test_net, "pose2seg_test": cmd_pose2seg_test}[a.cmd](a)
+    return {"eval": cmd_eval, "test_net": cmd_test_net, "pose2seg_test": cmd_pose2seg_test, "coco_eval": cmd_coco_eval}[a.cmd](a)
 
 
 if __name__ == "__main__":

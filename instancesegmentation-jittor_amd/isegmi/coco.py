@@ -90,6 +90,120 @@ def rle_decode(rle):
     return flat.reshape((h, w), order="F")
 
 
+def rle_from_polygon(xy, h, w):
+    """Run counts (column-major, zeros first) of one polygon [x0, y0, x1, y1, ...] in an h x w image.
+    [UPSTREAM-RECALL -- unverified] pycocotools maskApi.c rleFrPoly: vertices scaled by 5 and rounded with +0.5 truncation; every edge walked one
+    step along its longer axis with the other coordinate rounded; the points where x changes mapped back with (x + 0.5) / 5 - 0.5, kept where
+    that is an integer column inside the image, y clamped to [0, h] and rounded up; the flat positions x * h + y sorted, h * w appended,
+    differenced, and zero-length runs folded into their neighbours."""
+    xy = np.asarray(xy, np.float64).ravel()
+    k = xy.size // 2
+    h, w = int(h), int(w)
+    if k == 0:
+        return [h * w]
+    scale = 5.0
+    x = np.trunc(scale * xy[0:2 * k:2] + 0.5).astype(np.int64)
+    y = np.trunc(scale * xy[1:2 * k:2] + 0.5).astype(np.int64)
+    x = np.append(x, x[0]); y = np.append(y, y[0])
+    us, vs = [], []
+    for j in range(k):
+        xs, xe, ys, ye = int(x[j]), int(x[j + 1]), int(y[j]), int(y[j + 1])
+        dx, dy = abs(xe - xs), abs(ys - ye)
+        flip = (dx >= dy and xs > xe) or (dx < dy and ys > ye)
+        if flip:
+            xs, xe, ys, ye = xe, xs, ye, ys
+        if dx >= dy:
+            s = (ye - ys) / dx if dx else 0.0     # a degenerate edge (dx = dy = 0) is 0 / 0 upstream; it contributes its single point
+            t = np.arange(dx, -1, -1) if flip else np.arange(dx + 1)
+            us.append(t + xs)
+            vs.append(np.trunc(ys + s * t + 0.5).astype(np.int64))
+        else:
+            s = (xe - xs) / dy
+            t = np.arange(dy, -1, -1) if flip else np.arange(dy + 1)
+            vs.append(t + ys)
+            us.append(np.trunc(xs + s * t + 0.5).astype(np.int64))
+    u = np.concatenate(us); v = np.concatenate(vs)
+    # the points where x changes: the y-boundary crossings, mapped back to pixel columns
+    u0, u1, v0, v1 = u[:-1], u[1:], v[:-1], v[1:]
+    ch = u1 != u0
+    u0, u1, v0, v1 = u0[ch], u1[ch], v0[ch], v1[ch]
+    xd = np.where(u1 < u0, u1, u1 - 1).astype(np.float64)
+    xd = (xd + 0.5) / scale - 0.5
+    keep = (np.floor(xd) == xd) & (xd >= 0) & (xd <= w - 1)
+    yd = np.where(v1 < v0, v1, v0).astype(np.float64)
+    yd = (yd + 0.5) / scale - 0.5
+    yd = np.ceil(np.clip(yd, 0.0, float(h)))
+    a = (xd[keep].astype(np.int64) * h + yd[keep].astype(np.int64))
+    a = np.sort(np.append(a, h * w))
+    d = np.diff(np.concatenate([[0], a])).tolist()
+    # fold zero-length runs: a zero count joins its two neighbours into one run
+    b = [d[0]]
+    j = 1
+    while j < len(d):
+        if d[j] > 0:
+            b.append(d[j]); j += 1
+        else:
+            j += 1
+            if j < len(d):
+                b[-1] += d[j]; j += 1
+    return b
+
+
+def _rle_intervals(counts):
+    """[start, end) of the 1-runs of a count list, empty ones dropped."""
+    c = np.asarray(counts, np.int64).ravel()
+    e = np.cumsum(c)
+    s = e - c
+    s, e = s[1::2], e[1::2]
+    nz = e > s
+    return s[nz], e[nz]
+
+
+def rle_merge(counts_list, hw_pixels):
+    """Union of several RLEs of one image size (hw_pixels = h * w) as canonical run counts.
+    [UPSTREAM-RECALL -- unverified] the result of pycocotools rleMerge(intersect=0): the parts of one annotation joined into one mask."""
+    parts = [_rle_intervals(c) for c in counts_list]
+    s = np.concatenate([p[0] for p in parts]) if parts else np.zeros(0, np.int64)
+    e = np.concatenate([p[1] for p in parts]) if parts else np.zeros(0, np.int64)
+    if s.size == 0:
+        return [int(hw_pixels)]
+    o = np.argsort(s, kind="stable")
+    s, e = s[o], e[o]
+    reach = np.maximum.accumulate(e)
+    first = np.ones(s.size, bool)
+    first[1:] = s[1:] > reach[:-1]          # touching or overlapping intervals are one run
+    starts = s[first]
+    ends = np.append(reach[:-1][first[1:]], reach[-1])
+    b = np.empty(2 * starts.size + 1, np.int64)
+    b[0:-1:2] = starts; b[1::2] = ends; b[-1] = int(hw_pixels)
+    out = np.diff(np.concatenate([[0], b])).tolist()
+    if out[-1] == 0:
+        out.pop()
+    return out
+
+
+def rle_area(counts):
+    """Set pixels of a count list (rleArea)."""
+    return int(np.asarray(counts, np.int64).ravel()[1::2].sum())
+
+
+def rle_to_bbox(counts, h):
+    """Tight box [x, y, w, h] of a count list (rleToBbox), [0, 0, 0, 0] for an empty mask.  Empty 1-runs are skipped."""
+    s, e = _rle_intervals(counts)
+    if s.size == 0:
+        return [0.0, 0.0, 0.0, 0.0]
+    h = int(h)
+    last = e - 1
+    xs, xe = s // h, last // h
+    wrap = xs < xe
+    if wrap.any():
+        y0, y1 = 0, h - 1
+    else:
+        y0, y1 = int((s - xs * h).min()), int((last - xe * h).max())
+    x0, x1 = int(xs.min()), int(xe.max())
+    return [float(x0), float(y0), float(x1 - x0 + 1), float(y1 - y0 + 1)]
+
+
 def maskrcnn_results(image_id, boxes_xyxy, scores, labels, masks=None):
     """maskrcnn-benchmark prepare_for_coco_detection/segmentation: bbox xywh with the legacy +1 widths,
     category_id via the contiguous->json id map, segmentation = RLE of the pasted HxW mask."""
