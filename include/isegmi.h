@@ -179,6 +179,13 @@ int isegmi_op_upsample_nearest2x_add(const float* d_coarse, int N, int Hc, int W
 int isegmi_op_pad_c3_to_c4(const float* d_in, int64_t npix, float* d_out, void* stream);
 /* fn: 0 exp 1 sigmoid 2 tanh 3 log2 -- exposes the deterministic math for parity tests */
 int isegmi_op_map_f32(const float* d_x, float* d_y, int64_t n, int fn, void* stream);
+/* fp16-storage twins of isegmi_op_maxpool / _resize_bilinear / _upsample_nearest2x_add (configs[4]) -- exposes the kernels of csrc/spatial_f16.hip
+ * for parity tests.  Tensors are fp16 NHWC (d_in of the max-pool is fp32 when in_f16 == 0); all arithmetic is fp32 in the order of the fp32 ops, only
+ * loads and stores convert: out = fp16(op(fp32(in))).  C % 4 == 0; the max-pool's output (H + 2p - k) / s + 1 must not be empty. */
+int isegmi_op_maxpool_f16(const void* d_in, int in_f16, int N, int H, int W, int C, int k, int s, int p, void* d_out, void* stream);
+int isegmi_op_resize_bilinear_f16(const void* d_in, int N, int H, int W, int C, int Ho, int Wo, const void* d_add, int relu, void* d_out, void* stream);
+int isegmi_op_upsample_nearest2x_add_f16(const void* d_coarse, int N, int Hc, int Wc, int C, const void* d_lateral, int H, int W, void* d_out,
+                                         void* stream);
 
 /* ---- selection: torch.topk / sort stand-in (M6, M9, Y6) ----
  * rows independent problems; row r = d_keys + r*row_stride, n elements; output sorted by
@@ -324,6 +331,11 @@ int isegmi_op_box_postprocess(const isegmi_box_post_args* a, void* stream);
 /* mask predictor tail (A.8): out[r,p] = sigmoid(<feat[r,p,:], w[label_r,:]> + b[label_r]); label 0 -> zeros */
 int isegmi_op_mask_logits_select(const float* d_feat, int R, int HW, int C, const float* d_w,
                                  const float* d_b, const int32_t* d_labels, float* d_out, void* stream);
+/* the same tail on fp16 features (configs[4]; d_w, d_b and d_out stay fp32) -- exposes mask_logits_select_f16_launch for parity tests.  C % 4 == 0.
+ * C == 256 with 16-byte aligned features takes the coalesced form, whose dot product is 8 chained FMAs per lane and a 32-lane butterfly (parity
+ * with the fp32 op by tolerance); every other C sums in the fp32 op's order (same bits).  label <= 0 -> zeros. */
+int isegmi_op_mask_logits_select_f16(const void* d_feat, int R, int HW, int C, const float* d_w, const float* d_b, const int32_t* d_labels,
+                                     float* d_out, void* stream);
 /* Masker(threshold, padding=1) paste (A.8): masks [N][K][M][M], boxes [N][K][4] -> u8 [N][K][im_h][im_w] */
 int isegmi_op_paste_masks(const float* d_masks, const float* d_boxes, const int32_t* d_counts, int N,
                           int K, int M, int im_h, int im_w, float thr, uint8_t* d_out, void* stream);

@@ -588,3 +588,24 @@ extern "C" int isegmi_op_roi_align_f16_ordered(const void* const* d_feats, const
     return isegmi::roi_align_f16_launch(d_feats, Hs, Ws, scales, nlevels, d_rois, d_counts, N, K, C, PH, PW, 2, k_min, d_out, (hipStream_t)stream,
                                         d_order, d_table);
 }
+// the fp16 spatial ops and the fp16 mask tail for parity tests (the engines call the launchers)
+extern "C" int isegmi_op_maxpool_f16(const void* d_in, int in_f16, int N, int H, int W, int C, int k, int s, int p, void* d_out, void* stream) {
+    ARG_CHECK(d_in && d_out && N > 0 && H > 0 && W > 0 && C > 0 && k > 0 && s > 0 && p >= 0, "args");
+    ARG_CHECK(H + 2 * p >= k && W + 2 * p >= k, "maxpool_f16: empty output");
+    return isegmi::maxpool_to_f16_launch(d_in, in_f16, N, H, W, C, k, s, p, d_out, (hipStream_t)stream);
+}
+extern "C" int isegmi_op_resize_bilinear_f16(const void* d_in, int N, int H, int W, int C, int Ho, int Wo, const void* d_add, int relu, void* d_out,
+                                             void* stream) {
+    ARG_CHECK(d_in && d_out && N > 0 && H > 0 && W > 0 && C > 0 && Ho > 0 && Wo > 0, "args");
+    return isegmi::resize_bilinear_f16_launch(d_in, N, H, W, C, Ho, Wo, d_add, relu, d_out, (hipStream_t)stream);
+}
+extern "C" int isegmi_op_upsample_nearest2x_add_f16(const void* d_coarse, int N, int Hc, int Wc, int C, const void* d_lateral, int H, int W,
+                                                    void* d_out, void* stream) {
+    ARG_CHECK(d_coarse && d_lateral && d_out && N > 0 && Hc > 0 && Wc > 0 && C > 0 && H > 0 && W > 0, "args");
+    return isegmi::nearest2x_add_f16_launch(d_coarse, N, Hc, Wc, C, d_lateral, H, W, d_out, (hipStream_t)stream);
+}
+extern "C" int isegmi_op_mask_logits_select_f16(const void* d_feat, int R, int HW, int C, const float* d_w, const float* d_b,
+                                                const int32_t* d_labels, float* d_out, void* stream) {
+    ARG_CHECK(d_feat && d_w && d_b && d_labels && d_out && R > 0 && HW > 0 && C > 0, "args");
+    return isegmi::mask_logits_select_f16_launch(d_feat, R, HW, C, d_w, d_b, d_labels, d_out, (hipStream_t)stream);
+}

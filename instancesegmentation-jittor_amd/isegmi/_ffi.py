@@ -111,6 +111,12 @@ class DeviceBuffer:
     def zero(self):
         check(lib().isegmi_memset(self.ptr, C.c_int(0), C.c_int64(self.nbytes)))
 
+    def poison(self):
+        """0xFF in every byte (NaN as fp16 / fp32, -1 as an integer): an element a kernel never wrote cannot pass as a zero."""
+        if self.nbytes:
+            check(lib().isegmi_memset(self.ptr, C.c_int(0xFF), C.c_int64(self.nbytes)))
+        return self
+
     def free(self):
         if self.ptr is not None and self.ptr.value:
             lib().isegmi_free(self.ptr)
@@ -226,17 +232,38 @@ def maxpool(x, k, s, p):
     x = np.ascontiguousarray(x, np.float32)
     N, H, W, Cc = x.shape
     ho, wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
-    dx = DeviceBuffer.from_numpy(x); do = DeviceBuffer((N, ho, wo, Cc))
+    dx = DeviceBuffer.from_numpy(x); do = DeviceBuffer((N, ho, wo, Cc)).poison()
     check(lib().isegmi_op_maxpool(dx.ptr, N, H, W, Cc, k, s, p, do.ptr, None))
+    return do.numpy()
+
+
+def maxpool_f16(x, k, s, p, in_f16=True):
+    """isegmi_op_maxpool_f16: x [N,H,W,C] cast to fp16 (fp32 when not in_f16) -> fp16 [N,Ho,Wo,C]."""
+    x = np.ascontiguousarray(x, np.float16 if in_f16 else np.float32)
+    N, H, W, Cc = x.shape
+    ho, wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+    dx = DeviceBuffer.from_numpy(x); do = DeviceBuffer((N, max(ho, 0), max(wo, 0), Cc), np.float16).poison()
+    check(lib().isegmi_op_maxpool_f16(dx.ptr, int(bool(in_f16)), N, H, W, Cc, k, s, p, do.ptr, None))
     return do.numpy()
 
 
 def resize_bilinear(x, Ho, Wo, add=None, relu=0):
     x = np.ascontiguousarray(x, np.float32)
     N, H, W, Cc = x.shape
-    dx = DeviceBuffer.from_numpy(x); do = DeviceBuffer((N, Ho, Wo, Cc))
+    dx = DeviceBuffer.from_numpy(x); do = DeviceBuffer((N, Ho, Wo, Cc)).poison()
     da = None if add is None else DeviceBuffer.from_numpy(np.asarray(add, np.float32))
     check(lib().isegmi_op_resize_bilinear(dx.ptr, N, H, W, Cc, Ho, Wo, _ptr(da), relu, do.ptr, None))
+    return do.numpy()
+
+
+def resize_bilinear_f16(x, Ho, Wo, add=None, relu=0):
+    """isegmi_op_resize_bilinear_f16: x [N,H,W,C] and add [N,Ho,Wo,C] cast to fp16 -> fp16 [N,Ho,Wo,C]."""
+    x = np.ascontiguousarray(x, np.float16)
+    N, H, W, Cc = x.shape
+    dx = DeviceBuffer.from_numpy(x); do = DeviceBuffer((N, Ho, Wo, Cc), np.float16).poison()
+    da = None if add is None else DeviceBuffer.from_numpy(np.ascontiguousarray(add, np.float16))
+    assert da is None or da.shape == do.shape, (da.shape, do.shape)
+    check(lib().isegmi_op_resize_bilinear_f16(dx.ptr, N, H, W, Cc, Ho, Wo, _ptr(da), int(relu), do.ptr, None))
     return do.numpy()
 
 
@@ -267,8 +294,29 @@ def upsample_nearest2x_add(coarse, lateral):
     coarse = np.ascontiguousarray(coarse, np.float32); lateral = np.ascontiguousarray(lateral, np.float32)
     N, Hc, Wc, Cc = coarse.shape
     _, H, W, _ = lateral.shape
-    dc = DeviceBuffer.from_numpy(coarse); dl = DeviceBuffer.from_numpy(lateral); do = DeviceBuffer(lateral.shape)
+    dc = DeviceBuffer.from_numpy(coarse); dl = DeviceBuffer.from_numpy(lateral); do = DeviceBuffer(lateral.shape).poison()
     check(lib().isegmi_op_upsample_nearest2x_add(dc.ptr, N, Hc, Wc, Cc, dl.ptr, H, W, do.ptr, None))
+    return do.numpy()
+
+
+def upsample_nearest2x_add_f16(coarse, lateral):
+    """isegmi_op_upsample_nearest2x_add_f16: coarse [N,Hc,Wc,C], lateral [N,H,W,C] cast to fp16 -> fp16 [N,H,W,C]."""
+    coarse = np.ascontiguousarray(coarse, np.float16); lateral = np.ascontiguousarray(lateral, np.float16)
+    N, Hc, Wc, Cc = coarse.shape
+    N2, H, W, C2 = lateral.shape
+    assert (N2, C2) == (N, Cc), (coarse.shape, lateral.shape)
+    dc = DeviceBuffer.from_numpy(coarse); dl = DeviceBuffer.from_numpy(lateral); do = DeviceBuffer(lateral.shape, np.float16).poison()
+    check(lib().isegmi_op_upsample_nearest2x_add_f16(dc.ptr, N, Hc, Wc, Cc, dl.ptr, H, W, do.ptr, None))
+    return do.numpy()
+
+
+def pad_c3_to_c4(x):
+    """isegmi_op_pad_c3_to_c4: [..., 3] fp32 pixels -> [..., 4] with a zero 4th channel."""
+    x = np.ascontiguousarray(x, np.float32)
+    assert x.shape[-1] == 3, x.shape
+    npix = x.size // 3
+    dx = DeviceBuffer.from_numpy(x); do = DeviceBuffer(x.shape[:-1] + (4,)).poison()
+    check(lib().isegmi_op_pad_c3_to_c4(dx.ptr, C.c_int64(npix), do.ptr, None))
     return do.numpy()
 
 
@@ -413,7 +461,7 @@ def avgpool_full(x):
     """[R,H,W,C] fp32 -> [R,C]: AvgPool2d over the whole window."""
     x = np.ascontiguousarray(x, np.float32)
     R_, H, W, Cc = x.shape
-    dx = DeviceBuffer.from_numpy(x); do = DeviceBuffer((R_, Cc))
+    dx = DeviceBuffer.from_numpy(x); do = DeviceBuffer((R_, Cc)).poison()
     check(lib().isegmi_op_avgpool_full(dx.ptr, C.c_int64(R_), H * W, Cc, do.ptr, None))
     return do.numpy()
 
@@ -471,8 +519,29 @@ def mask_logits_select(feat, w, b, labels):
     R, HW, Cc = feat.shape
     df = DeviceBuffer.from_numpy(feat); dw = DeviceBuffer.from_numpy(np.ascontiguousarray(w, np.float32))
     db = DeviceBuffer.from_numpy(np.ascontiguousarray(b, np.float32)); dl = DeviceBuffer.from_numpy(np.ascontiguousarray(labels, np.int32))
-    do = DeviceBuffer((R, HW))
+    do = DeviceBuffer((R, HW)).poison()
     check(lib().isegmi_op_mask_logits_select(df.ptr, R, HW, Cc, dw.ptr, db.ptr, dl.ptr, do.ptr, None))
+    return do.numpy()
+
+
+def mask_logits_select_f16(feat, w, b, labels):
+    """isegmi_op_mask_logits_select_f16: feat [R,HW,C] cast to fp16; w [ncls,C], b [ncls] fp32; labels [R] -> fp32 [R,HW]."""
+    feat = np.ascontiguousarray(feat, np.float16)
+    R, HW, Cc = feat.shape
+    df = DeviceBuffer.from_numpy(feat); dw = DeviceBuffer.from_numpy(np.ascontiguousarray(w, np.float32))
+    db = DeviceBuffer.from_numpy(np.ascontiguousarray(b, np.float32)); dl = DeviceBuffer.from_numpy(np.ascontiguousarray(labels, np.int32))
+    do = DeviceBuffer((R, HW)).poison()
+    check(lib().isegmi_op_mask_logits_select_f16(df.ptr, R, HW, Cc, dw.ptr, db.ptr, dl.ptr, do.ptr, None))
+    return do.numpy()
+
+
+def grid_anchors(base, stride, grid_h, grid_w):
+    """isegmi_op_grid_anchors: base [A,4] -> [grid_h*grid_w*A, 4], row (y*grid_w + x)*A + a = base[a] + (x, y, x, y) * stride."""
+    base = np.ascontiguousarray(base, np.float32)
+    A = base.shape[0]
+    assert base.shape == (A, 4), base.shape
+    db = DeviceBuffer.from_numpy(base); do = DeviceBuffer((grid_h * grid_w * A, 4)).poison()
+    check(lib().isegmi_op_grid_anchors(db.ptr, A, int(stride), int(grid_h), int(grid_w), do.ptr, None))
     return do.numpy()
 
 
