@@ -185,20 +185,30 @@ def op_conv2d(desc, d_in, d_wpacked, d_scale=None, d_shift=None, d_residual=None
                                  _ptr(d_residual), _ptr(d_out), None))
 
 
-def conv2d(x, w_krsc, stride=1, pad=0, scale=None, shift=None, residual=None, act=0, tile=0):
-    """Convenience host->device->host convolution (tests / small inputs)."""
+def _strided_out(shape, dtype, out_shape, out_offset):
+    """The output buffer of the conv wrappers, every byte 0xFF before the launch: the dense result, or (out_shape given) a larger array that the strided
+    output mode writes into from element out_offset on.  -> (buffer, address of the first element the kernel is given)."""
+    do = DeviceBuffer(shape if out_shape is None else out_shape, dtype).poison()
+    return do, C.c_void_p(do.ptr.value + int(out_offset) * do.dtype.itemsize)
+
+
+def conv2d(x, w_krsc, stride=1, pad=0, scale=None, shift=None, residual=None, act=0, tile=0, out_shape=None, out_div=0, out_img_stride=0,
+           out_pix_stride=0, out_offset=0):
+    """Convenience host->device->host convolution (tests / small inputs).  out_shape: the strided output mode of isegmi_conv_desc -- the whole array
+    of that shape is returned, 0xFF in every byte the kernel did not write; result element (m, co) lies at flat index
+    out_offset + (m / out_div) * out_img_stride + (m % out_div) * out_pix_stride + co."""
     x = np.ascontiguousarray(x, np.float32)
     N, H, W, Cin = x.shape
     Cout, R, S, _ = w_krsc.shape
-    d = make_conv_desc(N, H, W, Cin, Cout, R, S, stride, pad, act, tile)
+    d = make_conv_desc(N, H, W, Cin, Cout, R, S, stride, pad, act, tile, out_div, out_img_stride, out_pix_stride)
     ho, wo = conv_out_hw(d)
     dx = DeviceBuffer.from_numpy(x)
     dw = DeviceBuffer.from_numpy(pack_conv_weights(d, w_krsc))
     ds = None if scale is None else DeviceBuffer.from_numpy(np.asarray(scale, np.float32))
     dh = None if shift is None else DeviceBuffer.from_numpy(np.asarray(shift, np.float32))
     dr = None if residual is None else DeviceBuffer.from_numpy(np.asarray(residual, np.float32))
-    do = DeviceBuffer((N, ho, wo, Cout))
-    op_conv2d(d, dx, dw, ds, dh, dr, do)
+    do, first = _strided_out((N, ho, wo, Cout), np.float32, out_shape, out_offset)
+    check(lib().isegmi_op_conv2d(C.byref(d), dx.ptr, dw.ptr, _ptr(ds), _ptr(dh), _ptr(dr), first, None))
     return do.numpy()
 
 
@@ -663,19 +673,21 @@ def stem_pool_f16(x_nhwc3, w_krs4, scale, shift, flags=0):
     return do.numpy()
 
 
-def conv2d_f16(x, w_krsc, stride=1, pad=0, scale=None, shift=None, residual=None, act=0, tile=0, out_f32=False):
-    """x fp16-representable NHWC (any float dtype; cast to fp16), returns fp16 (or fp32 when out_f32) as numpy."""
+def conv2d_f16(x, w_krsc, stride=1, pad=0, scale=None, shift=None, residual=None, act=0, tile=0, out_f32=False, out_shape=None, out_div=0,
+               out_img_stride=0, out_pix_stride=0, out_offset=0):
+    """x fp16-representable NHWC (any float dtype; cast to fp16), returns fp16 (or fp32 when out_f32) as numpy.  out_shape / out_div / out_img_stride /
+    out_pix_stride / out_offset: the strided output mode, as conv2d (strides and offset in elements of the output type)."""
     x = np.ascontiguousarray(x, np.float16)
     N, H, W, Cin = x.shape
     Cout, R, S, _ = w_krsc.shape
-    d = make_conv_desc(N, H, W, Cin, Cout, R, S, stride, pad, act, tile)
+    d = make_conv_desc(N, H, W, Cin, Cout, R, S, stride, pad, act, tile, out_div, out_img_stride, out_pix_stride)
     ho, wo = (H + 2 * pad - R) // stride + 1, (W + 2 * pad - S) // stride + 1
     dx = DeviceBuffer.from_numpy(x); dw = DeviceBuffer.from_numpy(pack_conv_weights_f16(d, w_krsc))
     ds = None if scale is None else DeviceBuffer.from_numpy(np.asarray(scale, np.float32))
     dh = None if shift is None else DeviceBuffer.from_numpy(np.asarray(shift, np.float32))
     dr = None if residual is None else DeviceBuffer.from_numpy(np.ascontiguousarray(residual, np.float16))
-    do = DeviceBuffer((N, ho, wo, Cout), np.float32 if out_f32 else np.float16)
-    check(lib().isegmi_op_conv2d_f16(C.byref(d), dx.ptr, dw.ptr, _ptr(ds), _ptr(dh), _ptr(dr), do.ptr, int(out_f32), None))
+    do, first = _strided_out((N, ho, wo, Cout), np.float32 if out_f32 else np.float16, out_shape, out_offset)
+    check(lib().isegmi_op_conv2d_f16(C.byref(d), dx.ptr, dw.ptr, _ptr(ds), _ptr(dh), _ptr(dr), first, int(out_f32), None))
     return do.numpy()
 
 

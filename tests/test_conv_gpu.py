@@ -1,4 +1,5 @@
-"""HIP implicit-GEMM conv vs the CPU oracle: BIT-EXACT (k-ordered fmaf chain on both sides)."""
+"""HIP implicit-GEMM conv vs the CPU oracle: BIT-EXACT (k-ordered fmaf chain on both sides).  One exception, outside the contract (DESIGN.md
+section 2): the sign of a result that is exactly zero, in a layer without residual and without ReLU (tests/test_conv_edges_gpu.py::test_negative_zero_results)."""
 import numpy as np
 import pytest
 
