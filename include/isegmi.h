@@ -499,6 +499,13 @@ int isegmi_engine_memory(isegmi_engine* e, int64_t* weight_bytes, int64_t* buffe
  * runtime (equal class numbers = one queue; found by a spin-kernel probe, ~2 ms; call on an idle engine).  An engine's throughput depends on this
  * placement, which the runtime derives from the process's stream-creation history. */
 int isegmi_engine_stream_layout(isegmi_engine* e, int32_t* queue_class, int n);
+/* Backbone lanes of the Yolact fp32 engine (parameter "step_overlap": consecutive forwards alternate between two lanes -- a main stream with its side
+ * streams and its own backbone / FPN buffers -- so that step i + 1's backbone overlaps step i's; 0 = one lane, launch for launch as before).  n >= 18:
+ * out[0] lanes the next forward alternates over (2, or 1: off, forced off -- graph capture / "graph", multi_stream 0, fp16, timing modes, other models --
+ * or fallback); out[1] = 1: wanted, but the runtime gave lane 1's main stream no hardware queue apart from lane 0's main and the tail: the engine fell
+ * back to one lane; out[2..11] the ten roles' queue classes as isegmi_engine_stream_layout; out[12..15] lane 1's main / side0-2 in the same numbering
+ * (-1 not dealt); out[16] lanes the last forward alternated over; out[17] forwards run on lane 1 so far.  Call on an idle engine. */
+int isegmi_engine_lane_layout(isegmi_engine* e, int32_t* out, int n);
 /* per-stage hipEvent timings of the last synchronised forward (set_param "timing" 1 first) */
 int isegmi_engine_get_timings(isegmi_engine* e, char* names, int names_cap, float* ms, int ms_cap,
                               int* count);

@@ -1057,6 +1057,12 @@ static int conv_fill(const isegmi_conv_desc* d, const float* in, const float* w,
     return ISEGMI_OK;
 }
 
+static bool conv_hybrid_on() {
+    static int on = -1;
+    if (on < 0) { const char* e = getenv("ISEGMI_CONV_HYBRID"); on = (e && atoi(e) == 0) ? 0 : 1; }
+    return on != 0;
+}
+
 int conv2d_launch(const isegmi_conv_desc* d, const float* in, const float* w, const float* scale, const float* shift,
                   const float* res, float* out, hipStream_t st) {
     ConvK k;
@@ -1091,7 +1097,9 @@ int conv2d_launch(const isegmi_conv_desc* d, const float* in, const float* w, co
         // (profiles/r02_conv_tile_sweep_v4.txt), behind it once the tail passes ~15 % of the layer (616, 1228 tiles)
         // round 3 sweep over 355 layer shapes incl. the canvases COCODemo produces (profiles/r03_conv_tile_sweep.txt): no upper limit any more -- on
         // the 3400-9500-tile 3x3 layers (FPN / RPN at P2, proto_net.8) the hybrid launch is 0.5-2.6 % ahead of plain v2 as well
-        else if (t64 >= 513 && t64 % ncu != 0 && (t64 % ncu) * 100 <= t64 * 15) tile = 13;
+        // (ISEGMI_CONV_HYBRID=0, dev: the rule as it stood before the hybrid launch -- the same single k-ordered chain per output, so the same bits; the
+        // A/B of "does a second backbone lane fill the last round instead", profiles/step_overlap.md)
+        else if (t64 >= 513 && t64 % ncu != 0 && (t64 % ncu) * 100 <= t64 * 15 && conv_hybrid_on()) tile = 13;
         else if (t64 <= 512) tile = v2;
         else if (t64 <= 640) tile = nck >= 32 ? 6 : 4;
         else if (t64 <= 1024) tile = v2;

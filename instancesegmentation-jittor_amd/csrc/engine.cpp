@@ -33,7 +33,7 @@ int eng_buf(Engine& e, const std::string& name, int64_t bytes, void** out, int d
 
 int eng_act(Engine& e, const std::string& name, int N, int H, int W, int C, Tensor* t, int dt) {
     void* p = nullptr;
-    int rc = eng_buf(e, name, (int64_t)N * H * W * C * (dt ? 2 : 4), &p, dt ? 4 : 0, {N, H, W, C});
+    int rc = eng_buf(e, e.lane_tag.empty() ? name : name + e.lane_tag, (int64_t)N * H * W * C * (dt ? 2 : 4), &p, dt ? 4 : 0, {N, H, W, C});
     if (rc) return rc;
     t->d = (float*)p; t->N = N; t->H = H; t->W = W; t->C = C; t->dt = dt;
     return ISEGMI_OK;
@@ -398,10 +398,14 @@ int eng_tail_end(Engine& e) {
     return ISEGMI_OK;
 }
 
+// Input slot rule: a front-end write into an input slot (upload_async, and the preprocess kernel behind an upload_u8_async) must follow the LAST READ
+// of that slot by every forward enqueued so far.  The two lanes' forwards share no stream, so each lane records its own event right after the one
+// kernel of its forward that reads the caller's input, and isegmi_engine_upload_async makes the copy stream wait on every lane's pending event
+// before it writes (conservative: it does not track which slot a lane read; the event sits behind the first kernel of a forward, so the wait is short).
 int eng_input_consumed(Engine& e) {
-    if (e.capturing || e.in_done == nullptr) return ISEGMI_OK;
-    HIP_TRY(hipEventRecord(e.in_done, e.cur));
-    e.in_pending = true;
+    if (e.capturing || e.in_done[e.lane] == nullptr) return ISEGMI_OK;
+    HIP_TRY(hipEventRecord(e.in_done[e.lane], e.cur));
+    e.in_pending[e.lane] = true;
     return ISEGMI_OK;
 }
 
@@ -409,18 +413,20 @@ int eng_input_consumed(Engine& e) {
 // upload_async / front-end launches that filled [d_ptr, d_ptr + bytes) -- and only for those.
 int eng_wait_upload(Engine& e, const void* d_ptr, int64_t bytes, hipStream_t st) {
     const char* p = (const char*)d_ptr;
+    const unsigned bit = (st != nullptr && st == e.lane_stream[1]) ? 2u : 1u;   // the lane whose main stream waits
     for (auto& u : e.uploads)
-        if (!u.waited && p < u.dst + u.bytes && u.dst < p + bytes) { HIP_TRY(hipStreamWaitEvent(st, u.done, 0)); u.waited = true; }
+        if (!(u.waited & bit) && p < u.dst + u.bytes && u.dst < p + bytes) { HIP_TRY(hipStreamWaitEvent(st, u.done, 0)); u.waited |= bit; }
     return ISEGMI_OK;
 }
 
-// Registers "the copy stream has, up to here, written [d_dst, d_dst + bytes)": one completion event per destination.
-static int eng_note_upload(Engine& e, const void* d_dst, int64_t bytes) {
+// Registers "stream st (the copy stream; the main stream for a front-end launch there) has, up to here, written [d_dst, d_dst + bytes)": one completion
+// event per destination.  `ordered`: the lanes whose main stream is already behind the write (bits as in Upload::waited).
+static int eng_note_upload(Engine& e, const void* d_dst, int64_t bytes, hipStream_t st = nullptr, unsigned ordered = 0u) {
     Engine::Upload* u = nullptr;
     for (auto& x : e.uploads) if (x.dst == (const char*)d_dst) u = &x;
     if (!u) {
         if (e.uploads.size() >= 64) {  // destinations come and go (staging buffers are re-allocated when they grow): recycle a consumed entry
-            for (auto& x : e.uploads) if (x.waited) { u = &x; break; }
+            for (auto& x : e.uploads) if (e.consumed(x)) { u = &x; break; }
             if (u == nullptr) { set_error("more than 64 upload destinations with unconsumed uploads"); return ISEGMI_ERR_STATE; }
         } else {
             e.uploads.emplace_back();
@@ -430,8 +436,8 @@ static int eng_note_upload(Engine& e, const void* d_dst, int64_t bytes) {
         u->dst = (const char*)d_dst;
     }
     u->bytes = bytes;
-    HIP_TRY(hipEventRecord(u->done, e.copy));
-    u->waited = false;
+    HIP_TRY(hipEventRecord(u->done, st ? st : e.copy));
+    u->waited = ordered;
     return ISEGMI_OK;
 }
 
@@ -496,7 +502,7 @@ int eng_graph_run(Engine& e, const std::string& key, const std::function<int()>&
     ++e.graph_replays;
     // eng_input_consumed() is skipped under capture and never runs on a replay: the end of the graph is the (conservative) point
     // after which the next upload_async may overwrite the input / staging buffer
-    if (e.in_done) { HIP_TRY(hipEventRecord(e.in_done, e.stream)); e.in_pending = true; }
+    if (e.in_done[0]) { HIP_TRY(hipEventRecord(e.in_done[0], e.stream)); e.in_pending[0] = true; }
     return ISEGMI_OK;
 }
 
@@ -545,6 +551,18 @@ static void collect_times(Engine& e) {
     } while (0)
 
 // Redirects everything the rest of a forward launches (main stream, side streams, current stream) to the heads stream group.
+// Points the engine's main / side streams and the names of the buffers eng_act allocates at lane e.lane for the duration of a forward.
+struct LaneScope {
+    Engine& e;
+    explicit LaneScope(Engine& e_) : e(e_) { set(e.lane); if (e.lane) e.lane_tag = "@1"; }
+    ~LaneScope() { set(0); e.lane_tag.clear(); e.cur = e.stream; }
+    void set(int l) {
+        if (e.lane_stream[l] == nullptr) return;
+        e.stream = e.lane_stream[l];
+        for (int k = 0; k < 3; ++k) e.side[k] = e.lane_side[l][k];
+    }
+};
+
 struct HeadsScope {
     Engine& e;
     hipStream_t s, sd[3];
@@ -558,6 +576,8 @@ struct HeadsScope {
 
 int yolact_forward(Engine& e, const float* d_images, int N) {
     const int H = e.H, W = e.W;
+    LaneScope lscope(e);
+    const int lane = e.lane;
     e.cur = e.stream;
     // cross-step pipelining of the heads phase (eager multi-stream throughput mode only)
     const bool pipe = e.multi_stream && !e.capturing && !e.timing && !e.conv_timing && e.heads != nullptr &&
@@ -584,7 +604,7 @@ int yolact_forward(Engine& e, const float* d_images, int N) {
         for (int li = 0; li < 5; ++li) {
             const std::string ln = "backbone.layers." + std::to_string(li);
             // C3 (layer 2's output, then C4, C5) is about to be overwritten: the previous step's lateral convs must have read them
-            if (li == 2 && e.lat_pending) HIP_TRY(hipStreamWaitEvent(e.stream, e.lat_done, 0));
+            if (li == 2 && e.lat_pending[lane]) HIP_TRY(hipStreamWaitEvent(e.stream, e.lat_done[lane], 0));
             Tensor y;
             TRY(eng_conv(e, ln + ".0.0", x, 2, 1, 3, nullptr, ln + ".down", &y));
             x = y;
@@ -630,7 +650,7 @@ int yolact_forward(Engine& e, const float* d_images, int N) {
             const std::string sg = alias ? "res" + std::to_string(li + 2) : nm;
             const std::string out_name = !alias ? nm + ".out" : b == blocks[li] - 1 ? sg + ".C" : sg + (b & 1 ? ".outB" : ".outA");
             if (dt && (b > 0 || st == 1)) {  // fp16 identity blocks of res2 / res3 and res2's first block: one launch, t1 / t2 stay in LDS (csrc/bottleneck_f16.hip)
-                if (li == 1 && b == blocks[1] - 1 && e.lat_pending) HIP_TRY(hipStreamWaitEvent(e.stream, e.lat_done, 0));  // (see below)
+                if (li == 1 && b == blocks[1] - 1 && e.lat_pending[lane]) HIP_TRY(hipStreamWaitEvent(e.stream, e.lat_done[lane], 0));  // (see below)
                 bool fused = false;
                 TRY(eng_bottleneck_f16(e, nm, x, b == 0, out_name, &y, &fused));
                 if (fused) { x = y; continue; }
@@ -664,7 +684,7 @@ int yolact_forward(Engine& e, const float* d_images, int N) {
             if (b == 0 && !pair) TRY(eng_join(e, 0));
             // C3 (then C4, C5) is about to be overwritten: the previous step's lateral convs, running on the heads streams, must
             // have read them (they are the first thing of that phase, so this wait practically never blocks)
-            if (li == 1 && b == blocks[1] - 1 && e.lat_pending) HIP_TRY(hipStreamWaitEvent(e.stream, e.lat_done, 0));
+            if (li == 1 && b == blocks[1] - 1 && e.lat_pending[lane]) HIP_TRY(hipStreamWaitEvent(e.stream, e.lat_done[lane], 0));
             TRY(eng_conv(e, nm + ".conv3", t2, 1, 0, 1, &idt, out_name, &y, false, /*may_split=*/true));
             x = y;
         }
@@ -709,7 +729,7 @@ int yolact_forward(Engine& e, const float* d_images, int N) {
     TRY(eng_join(e, 0));
     TRY(eng_join(e, 1));
     }
-    if (pipe) { HIP_TRY(hipEventRecord(e.lat_done, e.stream)); e.lat_pending = true; }
+    if (pipe) { HIP_TRY(hipEventRecord(e.lat_done[lane], e.stream)); e.lat_pending[lane] = true; }
     TRY(eng_act(e, "fpn.x4", N, l4.H, l4.W, l4.C, &x4f, dt));
     if (dt) TRY(resize_bilinear_f16_launch(l5.d, N, l5.H, l5.W, l5.C, l4.H, l4.W, l4.d, 0, x4f.d, e.cur));
     else TRY(resize_bilinear_launch(l5.d, N, l5.H, l5.W, l5.C, l4.H, l4.W, l4.d, 0, x4f.d, e.cur));
@@ -740,6 +760,7 @@ int yolact_forward(Engine& e, const float* d_images, int N) {
     TRY(eng_join(e, 1));
     }
     eng_mark(e, "fpn");
+    e.lane_tag.clear();   // everything allocated from here on (protonet, heads, Detect) exists once: it runs in step order behind the WAR point below
     // shared prediction head geometry
     const int A = (int)e.param("num_priors", 3), ncls = 81, md = 32;  // 9 for YOLACT++ (3 scales x 3 aspect ratios per cell)
     int Ptot = 0, off[5];
@@ -778,6 +799,8 @@ int yolact_forward(Engine& e, const float* d_images, int N) {
     };
     // WAR: the previous forward's Detect / postprocess (tail stream) still reads loc/conf/mask/proto and the det.*
     // buffers; everything before this point touched only backbone/FPN buffers and was free to overlap with it.
+    // (Two lanes: this wait is also what orders this step's heads phase behind the previous step's when pipeline_heads is off and the two
+    // run on different lanes' main streams -- tail_done is recorded behind the previous step's Detect, which follows its heads.)
     if (e.multi_stream && e.tail_pending && !e.capturing) HIP_TRY(hipStreamWaitEvent(e.stream, e.tail_done, 0));
     // protonet (side 0) || heads on P3 (main) || heads on P4,P6 (side 1) || heads on P5,P7 (side 2)
     Tensor proto;
@@ -994,7 +1017,11 @@ int same_queue(hipStream_t a, hipStream_t b, bool* same) {
 // dealt by queue class to reproduce the layout a fresh process gets (classes A main / side0 / heads-side1, B side2 / tail / heads-side2,
 // C side1 / heads / copy, D heads-side0); candidates not needed stay idle in the set (destroying them would shift the next set's placement).
 namespace {
-struct StreamSet { int dev = 0; bool used = false; hipStream_t s[10] = {nullptr}; std::vector<hipStream_t> spare; int placed = 0; };
+struct StreamSet {
+    int dev = 0; bool used = false; hipStream_t s[10] = {nullptr}; std::vector<hipStream_t> spare; int placed = 0;
+    hipStream_t lane1[4] = {nullptr};   // the second backbone lane's main + three side streams (deal_lane_streams), dealt on first demand
+    int lane_state = 0;                 // as Engine::lane_state
+};
 std::mutex g_sets_mu;
 std::vector<StreamSet*> g_sets;
 
@@ -1068,9 +1095,82 @@ int acquire_streams(StreamSet** out) {
     return ISEGMI_OK;
 }
 
+// The second backbone lane ("step_overlap") needs a main stream whose hardware queue carries neither lane 0's main stream nor the tail (two backbones on
+// one in-order queue would simply run one after the other; behind the tail it would wait for every Detect chain), and preferably not the heads stream
+// either.  With four queues that is the fourth class of the partition above (D), which otherwise carries only heads-side streams that are idle at the
+// bench batch.  It is taken from the set's idle candidates -- their queues are probed against the three live roles -- and only if none qualifies are up
+// to eight further streams created and probed.  No such queue (a runtime that hands out fewer distinct queues than the partition needs): lane_state -1,
+// the engine stays on one lane and says so (isegmi_engine_lane_layout) rather than share a queue.  Lane 1's side streams: side0 on its own main's queue
+// or lane 0's main's, side1 / side2 on the queues of lane 0's side1 / side2 where a candidate is left, else any idle candidate, else a new stream.
+int deal_lane_streams(StreamSet* ss) {
+    if (ss->lane_state != 0) return ISEGMI_OK;
+    auto qualifies = [&](hipStream_t c, int* q) -> int {   // *q: 0 no, 1 shares the heads stream's queue, 2 free of all three
+        bool same = false;
+        *q = 0;
+        int rc = same_queue(ss->s[0], c, &same);
+        if (rc || same) return rc;
+        rc = same_queue(ss->s[4], c, &same);
+        if (rc || same) return rc;
+        rc = same_queue(ss->s[5], c, &same);
+        if (rc) return rc;
+        *q = same ? 1 : 2;
+        return ISEGMI_OK;
+    };
+    int pick = -1, second = -1;
+    for (size_t j = 0; j < ss->spare.size() && pick < 0; ++j) {
+        int q = 0;
+        int rc = qualifies(ss->spare[j], &q);
+        if (rc) return rc;
+        if (q == 2) pick = (int)j;
+        else if (q == 1 && second < 0) second = (int)j;
+    }
+    for (int extra = 0; extra < 8 && pick < 0; ++extra) {
+        hipStream_t st = nullptr;
+        if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); break; }
+        ss->spare.push_back(st);
+        int q = 0;
+        int rc = qualifies(st, &q);
+        if (rc) return rc;
+        if (q == 2) pick = (int)ss->spare.size() - 1;
+        else if (q == 1 && second < 0) second = (int)ss->spare.size() - 1;
+    }
+    if (pick < 0) pick = second;
+    if (pick < 0) { ss->lane_state = -1; return ISEGMI_OK; }
+    ss->lane1[0] = ss->spare[pick];
+    ss->spare.erase(ss->spare.begin() + pick);
+    for (int k = 0; k < 3; ++k) {
+        const hipStream_t want[2] = {k == 0 ? ss->lane1[0] : ss->s[1 + k], k == 0 ? ss->s[0] : nullptr};
+        int got = -1;
+        for (int w = 0; w < 2 && got < 0 && want[w]; ++w)
+            for (size_t j = 0; j < ss->spare.size() && got < 0; ++j) {
+                bool same = false;
+                int rc = same_queue(want[w], ss->spare[j], &same);
+                if (rc) return rc;
+                if (same) got = (int)j;
+            }
+        if (got < 0 && !ss->spare.empty()) got = 0;
+        if (got < 0) {
+            hipStream_t st = nullptr;
+            if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) {
+                (void)hipGetLastError();
+                for (int i = 0; i <= k; ++i) if (ss->lane1[i]) { ss->spare.push_back(ss->lane1[i]); ss->lane1[i] = nullptr; }
+                ss->lane_state = -1;
+                return ISEGMI_OK;
+            }
+            ss->lane1[1 + k] = st;
+            continue;
+        }
+        ss->lane1[1 + k] = ss->spare[got];
+        ss->spare.erase(ss->spare.begin() + got);
+    }
+    ss->lane_state = 1;
+    return ISEGMI_OK;
+}
+
 void release_streams(StreamSet* ss) {
     if (!ss) return;
     for (int i = 0; i < 10; ++i) (void)hipStreamSynchronize(ss->s[i]);
+    for (int i = 0; i < 4; ++i) if (ss->lane1[i]) (void)hipStreamSynchronize(ss->lane1[i]);
     std::lock_guard<std::mutex> lk(g_sets_mu);
     ss->used = false;
 }
@@ -1098,6 +1198,68 @@ extern "C" int isegmi_engine_stream_layout(isegmi_engine* h, int32_t* queue_clas
     return ISEGMI_OK;
 }
 
+// "step_overlap" in force for the next forward?  Yolact fp32, eager multi-stream throughput mode only: off under graph capture / the "graph" latency
+// mode (a captured graph keeps its one-lane shape), with multi_stream 0, and under the stage / conv timing modes, whose events must bracket one stream's
+// kernels.  The first call that finds it wanted deals lane 1's streams (probes queues: a few ms, once per process and stream set).
+static int lanes_active(Engine& e, bool* on) {
+    *on = false;
+    if (e.kind != 1 || e.fp16 || !e.multi_stream || e.capturing || e.timing || e.conv_timing || e.param("graph", 0.0f) != 0.0f ||
+        e.param("step_overlap", STEP_OVERLAP_DEFAULT) == 0.0f)
+        return ISEGMI_OK;
+    if (e.lane_state == 0) {
+        StreamSet* ss = (StreamSet*)e.stream_set;
+        {
+            std::lock_guard<std::mutex> lk(g_sets_mu);
+            int rc = deal_lane_streams(ss);
+            if (rc) return rc;
+        }
+        e.lane_state = ss->lane_state;
+        if (e.lane_state == 1) {
+            e.lane_stream[1] = ss->lane1[0];
+            for (int k = 0; k < 3; ++k) e.lane_side[1][k] = ss->lane1[1 + k];
+        }
+    }
+    *on = e.lane_state == 1;
+    return ISEGMI_OK;
+}
+
+// Read-out of the backbone lanes ("step_overlap"), n >= 18.  Call on an idle engine (it synchronises the streams, and deals lane 1's when wanted).
+//   out[0]     lanes the next forward would alternate over (2, or 1: parameter off / forced off / fallback)
+//   out[1]     1 = step_overlap is wanted but the runtime gave lane 1's main stream no queue of its own: the engine FELL BACK to one lane
+//   out[2..11] queue classes of the ten roles, as isegmi_engine_stream_layout numbers them
+//   out[12..15] queue classes of lane 1's main, side0, side1, side2 in the same numbering (-1: not dealt)
+//   out[16]    lanes the LAST forward alternated over; out[17] forwards that ran on lane 1 so far (saturating at INT32_MAX)
+extern "C" int isegmi_engine_lane_layout(isegmi_engine* h, int32_t* out, int n) {
+    ARG_CHECK(h && out && n >= 18, "lane_layout args");
+    Engine& e = h->e;
+    StreamSet* ss = (StreamSet*)e.stream_set;
+    ARG_CHECK(ss, "engine has no streams");
+    bool on = false;
+    int rc = lanes_active(e, &on);
+    if (rc) return rc;
+    out[0] = on ? 2 : 1;
+    out[1] = e.lane_state == -1 ? 1 : 0;
+    hipStream_t all[14];
+    for (int i = 0; i < 10; ++i) all[i] = ss->s[i];
+    for (int i = 0; i < 4; ++i) all[10 + i] = e.lane_state == 1 ? ss->lane1[i] : nullptr;
+    int reps[14], nrep = 0;
+    for (int i = 0; i < 14; ++i) {
+        int cls = -1;
+        if (all[i] == nullptr) { out[2 + i] = -1; continue; }
+        for (int r = 0; r < nrep && cls < 0; ++r) {
+            bool same = false;
+            rc = same_queue(all[reps[r]], all[i], &same);
+            if (rc) return rc;
+            if (same) cls = r;
+        }
+        if (cls < 0) { cls = nrep; reps[nrep++] = i; }
+        out[2 + i] = cls;
+    }
+    out[16] = e.last_lanes;
+    out[17] = (int32_t)(e.lane1_forwards > 0x7fffffff ? 0x7fffffff : e.lane1_forwards);
+    return ISEGMI_OK;
+}
+
 extern "C" int isegmi_engine_create(int model_kind, int max_batch, int H, int W, isegmi_engine** out) {
     ARG_CHECK(out, "null out");
     ARG_CHECK(model_kind == 1 || model_kind == 2 || model_kind == 3, "model_kind: 1 yolact, 2 maskrcnn, 3 pose2seg");
@@ -1114,10 +1276,14 @@ extern "C" int isegmi_engine_create(int model_kind, int max_batch, int H, int W,
     h->e.heads = ss->s[5];
     for (int i = 0; i < 3; ++i) h->e.hside[i] = ss->s[6 + i];
     h->e.copy = ss->s[9];
+    h->e.lane_stream[0] = h->e.stream;
+    for (int i = 0; i < 3; ++i) h->e.lane_side[0][i] = h->e.side[i];
     hipError_t er = hipEventCreateWithFlags(&h->e.tail_done, hipEventDisableTiming);
-    if (er == hipSuccess) er = hipEventCreateWithFlags(&h->e.lat_done, hipEventDisableTiming);
+    for (int l = 0; l < 2; ++l) {
+        if (er == hipSuccess) er = hipEventCreateWithFlags(&h->e.lat_done[l], hipEventDisableTiming);
+        if (er == hipSuccess) er = hipEventCreateWithFlags(&h->e.in_done[l], hipEventDisableTiming);
+    }
     if (er == hipSuccess) er = hipEventCreateWithFlags(&h->e.heads_done, hipEventDisableTiming);
-    if (er == hipSuccess) er = hipEventCreateWithFlags(&h->e.in_done, hipEventDisableTiming);
     if (er != hipSuccess) { set_error(std::string("engine events: ") + hipGetErrorString(er)); release_streams(ss); delete h; return ISEGMI_ERR_HIP; }
     h->e.cur = h->e.stream;
     *out = h;
@@ -1128,14 +1294,15 @@ extern "C" int isegmi_engine_destroy(isegmi_engine* h) {
     if (!h) return ISEGMI_OK;
     Engine& e = h->e;
     if (e.stream_set) for (int i = 0; i < 10; ++i) (void)hipStreamSynchronize(((StreamSet*)e.stream_set)->s[i]);  // nothing of this engine is in flight any more
+    for (int i = 0; i < 4; ++i) if (e.stream_set && ((StreamSet*)e.stream_set)->lane1[i]) (void)hipStreamSynchronize(((StreamSet*)e.stream_set)->lane1[i]);
     eng_graph_reset(e);
     if (e.heads) { (void)hipStreamSynchronize(e.heads); }
     if (e.tail) (void)hipStreamSynchronize(e.tail);
     if (e.tail_done) (void)hipEventDestroy(e.tail_done);
-    if (e.lat_done) (void)hipEventDestroy(e.lat_done);
+    for (int l = 0; l < 2; ++l) if (e.lat_done[l]) (void)hipEventDestroy(e.lat_done[l]);
     if (e.heads_done) (void)hipEventDestroy(e.heads_done);
     if (e.copy) (void)hipStreamSynchronize(e.copy);
-    if (e.in_done) (void)hipEventDestroy(e.in_done);
+    for (int l = 0; l < 2; ++l) if (e.in_done[l]) (void)hipEventDestroy(e.in_done[l]);
     for (auto& u : e.uploads) if (u.done) (void)hipEventDestroy(u.done);
     for (int i = 0; i < 2; ++i) if (e.dl_done[i]) (void)hipEventDestroy(e.dl_done[i]);
     for (int i = 0; i < Engine::PIN_SLOTS; ++i) if (e.pin_ev[i]) (void)hipEventDestroy(e.pin_ev[i]);
@@ -1220,10 +1387,27 @@ extern "C" int isegmi_yolact_forward(isegmi_engine* h, const float* d_images_nhw
     ARG_CHECK(h->e.kind == 1, "engine is not a yolact engine");
     ARG_CHECK(N > 0 && N <= h->e.max_batch, "batch size");
     Engine& e = h->e;
-    TRY(eng_wait_upload(e, d_images_nhwc3, (int64_t)N * e.H * e.W * 3 * 4, e.stream));
-    char key[96];
-    snprintf(key, sizeof(key), "yolact:%d:%p", N, (const void*)d_images_nhwc3);
-    const int rc = eng_graph_run(e, key, [&]() { return yolact_forward(e, d_images_nhwc3, N); });
+    // backbone lane of this forward: consecutive forwards alternate while step_overlap is in force (an engine-side counter, whatever input slot
+    // the caller reads: a resident batch is read by both lanes)
+    bool two = false;
+    TRY(lanes_active(e, &two));
+    e.lane = two ? (e.lane_next++ & 1) : 0;
+    e.last_lanes = two ? 2 : 1;
+    if (e.lane == 1) { e.lane1_busy = true; ++e.lane1_forwards; }
+    else if (!two && e.lane1_busy) {  // back to one lane with lane 1 still in flight (a parameter or mode switch without a sync): lane 0 follows it
+        hipEvent_t ev;
+        TRY(eng_next_event(e, &ev));
+        HIP_TRY(hipEventRecord(ev, e.lane_stream[1]));
+        HIP_TRY(hipStreamWaitEvent(e.lane_stream[0], ev, 0));
+        e.lane1_busy = false;
+    }
+    int rc = eng_wait_upload(e, d_images_nhwc3, (int64_t)N * e.H * e.W * 3 * 4, e.lane_stream[e.lane]);
+    if (rc == ISEGMI_OK) {
+        char key[96];
+        snprintf(key, sizeof(key), "yolact:%d:%p", N, (const void*)d_images_nhwc3);
+        rc = eng_graph_run(e, key, [&]() { return yolact_forward(e, d_images_nhwc3, N); });
+    }
+    e.lane = 0;
     if (rc == ISEGMI_OK) e.last_N = N;
     return rc;
 }
@@ -1249,13 +1433,14 @@ extern "C" int isegmi_engine_sync(isegmi_engine* h) {
     ARG_CHECK(h, "null");
     if (h->e.copy) HIP_TRY(hipStreamSynchronize(h->e.copy));  // an upload_async without a consumer yet: the host may reuse its pinned source after sync()
     HIP_TRY(hipStreamSynchronize(h->e.stream));
+    if (h->e.lane_stream[1]) HIP_TRY(hipStreamSynchronize(h->e.lane_stream[1]));
     if (h->e.heads) HIP_TRY(hipStreamSynchronize(h->e.heads));
     if (h->e.tail) HIP_TRY(hipStreamSynchronize(h->e.tail));
-    h->e.in_pending = false;
+    for (int l = 0; l < 2; ++l) h->e.in_pending[l] = h->e.lat_pending[l] = false;
+    h->e.lane1_busy = false;
     h->e.tail_pending = false;
-    h->e.lat_pending = false;
     h->e.heads_pending = false;
-    for (auto& u : h->e.uploads) u.waited = true;  // the copy stream has drained: nothing is left to wait for
+    for (auto& u : h->e.uploads) u.waited = ~0u;  // the copy stream has drained: nothing is left to wait for
     collect_times(h->e);
     return ISEGMI_OK;
 }
@@ -1269,7 +1454,8 @@ extern "C" int isegmi_engine_sync(isegmi_engine* h) {
 extern "C" int isegmi_engine_upload_async(isegmi_engine* h, void* d_dst, const void* h_src, int64_t bytes) {
     ARG_CHECK(h && d_dst && h_src && bytes > 0, "upload args");
     Engine& e = h->e;
-    if (e.in_pending) { HIP_TRY(hipStreamWaitEvent(e.copy, e.in_done, 0)); e.in_pending = false; }
+    for (int l = 0; l < 2; ++l)   // every lane's last read of its input (the rule: eng_input_consumed)
+        if (e.in_pending[l]) { HIP_TRY(hipStreamWaitEvent(e.copy, e.in_done[l], 0)); e.in_pending[l] = false; }
     HIP_TRY(hipMemcpyAsync(d_dst, h_src, (size_t)bytes, hipMemcpyHostToDevice, e.copy));
     return eng_note_upload(e, d_dst, bytes);
 }
@@ -1286,7 +1472,7 @@ extern "C" int isegmi_engine_preprocess_u8(isegmi_engine* h, const uint8_t* d_u8
     bool on_copy = false;  // the source holds an upload the main stream has not been ordered behind: stay on the copy stream, behind it
     for (auto& u : e.uploads) {
         const char* p = (const char*)d_u8;
-        if (!u.waited && p < u.dst + u.bytes && u.dst < p + src_bytes) on_copy = true;
+        if (!(u.waited & 1u) && p < u.dst + u.bytes && u.dst < p + src_bytes) on_copy = true;
     }
     if (on_copy) {
         // d_out's previous reader is fenced by upload_async's wait on in_done, which precedes the copy in this stream
@@ -1300,8 +1486,13 @@ extern "C" int isegmi_engine_preprocess_u8(isegmi_engine* h, const uint8_t* d_u8
         return eng_note_upload(e, d_out, dst_bytes);
     }
     TRY(eng_wait_upload(e, d_u8, src_bytes, e.stream));
-    OpScope op(e, e.stream, "front end (uint8 -> resize / normalise / pad -> fp32 input)", (double)src_bytes + (double)dst_bytes);
-    return preprocess_u8_launch(d_u8, N, Hin, Win, d_out, Hout, Wout, Hpad, Wpad, out_img_stride, mean3, std3, swap_rb, e.stream);
+    {
+        OpScope op(e, e.stream, "front end (uint8 -> resize / normalise / pad -> fp32 input)", (double)src_bytes + (double)dst_bytes);
+        TRY(preprocess_u8_launch(d_u8, N, Hin, Win, d_out, Hout, Wout, Hpad, Wpad, out_img_stride, mean3, std3, swap_rb, e.stream));
+    }
+    // two lanes: the forward that reads d_out may run on lane 1, which is not behind this (lane 0) main-stream launch -- it waits as for an upload
+    if (e.lane_state == 1) return eng_note_upload(e, d_out, dst_bytes, e.stream, 1u);
+    return ISEGMI_OK;
 }
 
 // Records a completion mark for the step just enqueued on the stream its results finish on; isegmi_engine_step_times returns

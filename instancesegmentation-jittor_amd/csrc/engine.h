@@ -38,6 +38,9 @@ struct StageTime {
     hipEvent_t ev;
 };
 
+// default of the "step_overlap" engine parameter (Yolact fp32 only; profiles/step_overlap.md has the measurement behind it)
+constexpr float STEP_OVERLAP_DEFAULT = 1.0f;
+
 struct Engine {
     int kind = 0;  // 1 yolact, 2 maskrcnn, 3 pose2seg
     int max_batch = 0, H = 0, W = 0;       // H, W: the LARGEST network input (padded canvas) this engine serves
@@ -54,11 +57,25 @@ struct Engine {
     // layers fill).  lat_done fences the only backbone buffers the heads phase reads (C3-C5, by the lateral convs).
     hipStream_t heads = nullptr;
     hipStream_t hside[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t lat_done = nullptr;
-    bool lat_pending = false;
+    hipEvent_t lat_done[2] = {nullptr, nullptr};   // one per backbone lane (see below): the laterals that read THAT lane's C3-C5
+    bool lat_pending[2] = {false, false};
     hipEvent_t heads_done = nullptr;       // end of the last pipelined heads phase (a non-pipelined forward's heads phase waits on it)
     bool heads_pending = false;
     bool multi_stream = true;
+    // Yolact fp32 "step_overlap": two backbone LANES.  A lane is a main stream with its three side streams plus its own copy of every buffer a
+    // forward writes before the tail WAR point (padded input, stem, pooled map, the res<l>.* activations, laterals, P3-P7; lane 1's carry the
+    // suffix "@1").  Consecutive forwards alternate lanes, so step i + 1's backbone overlaps step i's backbone, heads and tail; everything
+    // behind the WAR point (heads, protonet, Detect, postprocess) has one set of buffers and keeps running in step order.  `stream` / `side`
+    // are the CURRENT lane's streams while a forward is enqueued and lane 0's otherwise.
+    hipStream_t lane_stream[2] = {nullptr, nullptr};
+    hipStream_t lane_side[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
+    int lane_state = 0;                    // 0: lane 1's streams not asked for yet; 1: dealt; -1: the runtime gave no free queue -- one lane (reported)
+    int lane = 0;                          // lane of the forward being enqueued
+    int lane_next = 0;                     // engine-side counter: forwards alternate lanes while step_overlap is active
+    int last_lanes = 1;                    // lanes the last forward could choose from (1: step_overlap inactive)
+    bool lane1_busy = false;               // lane 1 has run a forward since the last sync
+    int64_t lane1_forwards = 0;
+    std::string lane_tag;                  // appended to the names eng_act allocates: "" or "@1" before the WAR point, "" behind it
     // hipGraph replay of a forward ("graph" param): the ~130-150 launches of one forward are captured once per
     // (entry, batch, input pointer) and replayed with one hipGraphLaunch -- removes the per-launch gaps that bound bs=1
     // latency.  A replay ends joined on the main stream (no cross-step tail overlap), so it is a latency mode.
@@ -69,11 +86,14 @@ struct Engine {
     // asynchronous input upload (isegmi_engine_upload_async): pinned host -> device on a copy stream; in_done marks the point
     // where the last forward has consumed its input buffer (WAR for the next upload; recorded at the end of a hipGraph replay)
     hipStream_t copy = nullptr;
-    hipEvent_t in_done = nullptr;
-    bool in_pending = false;
+    hipEvent_t in_done[2] = {nullptr, nullptr};   // per lane: the two lanes' forwards are not ordered against each other
+    bool in_pending[2] = {false, false};
     // one completion event per upload destination (input slot / uint8 staging buffer): the consumer of a buffer waits for ITS upload
     // only, so the copy of batch i+1 really overlaps forward i
-    struct Upload { const char* dst = nullptr; int64_t bytes = 0; hipEvent_t done = nullptr; bool waited = true; };
+    // (waited: bit l = lane l's main stream has been ordered behind it; two lanes may read one input slot, each needs its own wait)
+    struct Upload { const char* dst = nullptr; int64_t bytes = 0; hipEvent_t done = nullptr; unsigned waited = ~0u; };
+    unsigned lane_mask() const { return lane_state == 1 ? 3u : 1u; }
+    bool consumed(const Upload& u) const { return (u.waited & lane_mask()) == lane_mask(); }
     std::vector<Upload> uploads;
     // per-step completion marks on the results stream (isegmi_engine_mark_step / _step_times): true per-step latency samples
     std::vector<hipEvent_t> step_marks;
