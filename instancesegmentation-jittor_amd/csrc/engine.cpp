@@ -1,9 +1,5 @@
-// engine.cpp -- engine object behind the C ABI: weights, buffers, timings, and the Yolact graph.
-//
-// Yolact graph = SURVEY.md 8a Y2..Y7 (App. A.9): ResNet-50 (stride on the 3x3) -> FPN (bilinear
-// top-down, relu'd 3x3 preds, two stride-2 downsamples) -> protonet on P3 -> shared prediction head
-// on P3..P7 -> Detect -> postprocess.  BN is folded into the conv epilogue (scale, shift) by the
-// Python host (isegmi/yolact.py) exactly once, in fp32.
+// engine.cpp -- engine object behind the C ABI: weights, buffers, conv launches, streams and lanes, uploads, timings.  The models' forward graphs
+// are in yolact.cpp, maskrcnn.cpp and pose2seg.cpp, over the ResNet trunk of resnet.cpp.
 #include <mutex>
 #include "engine.h"
 
@@ -48,31 +44,15 @@ static int find_conv(Engine& e, const std::string& layer, const ConvLayer** out)
 
 static int timed_conv(Engine& e, const std::string& label, const isegmi_conv_desc* d, const float* in, const ConvLayer* L, const float* res, void* out,
                       bool out_f32 = false) {
-    hipEvent_t a = nullptr, b = nullptr;
-    if (e.conv_timing) {
-        HIP_TRY(hipEventCreate(&a));
-        HIP_TRY(hipEventCreate(&b));
-        HIP_TRY(hipEventRecord(a, e.cur));
-    }
-    if (e.conv_trace) {  // dev tools (tools/conv_traffic.py): the launch order, to join per-dispatch counters with layers
-        const int Ho = (d->H + 2 * d->pad - d->R) / d->stride + 1, Wo = (d->W + 2 * d->pad - d->S) / d->stride + 1;
-        fprintf(stderr, "convlaunch\t%s\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\n", label.c_str(), d->N, d->H, d->W, d->Cin, d->Cout, d->R, d->stride, Ho * Wo * d->N,
-                res ? 1 : 0);
-    }
-    int rc = L->f16 ? conv2d_f16_launch(d, in, L->d_w, L->d_scale, L->d_shift, res, out, out_f32 ? 1 : 0, e.cur)
-                    : conv2d_launch(d, in, L->d_w, L->d_scale, L->d_shift, res, (float*)out, e.cur);
-    if (e.conv_timing) {
-        HIP_TRY(hipEventRecord(b, e.cur));
-        e.conv_evs.push_back({a, b});
-        const int Ho = (d->H + 2 * d->pad - d->R) / d->stride + 1, Wo = (d->W + 2 * d->pad - d->S) / d->stride + 1;
-        const int cin_true = (d->Cin == 4 && d->R == 7) ? 3 : d->Cin;
-        const double fl = 2.0 * d->N * Ho * Wo * (double)d->Cout * d->R * d->S * cin_true;
-        e.conv_flops_pending += fl;
-        char geo[160];
-        snprintf(geo, sizeof(geo), "%s [M=%d K=%d Cout=%d %dx%d/%d]", label.c_str(), d->N * Ho * Wo, d->R * d->S * d->Cin, d->Cout, d->R, d->S, d->stride);
-        e.conv_ev_info.push_back({geo, fl});
-    }
-    return rc;
+    const int Ho = (d->H + 2 * d->pad - d->R) / d->stride + 1, Wo = (d->W + 2 * d->pad - d->S) / d->stride + 1;
+    ConvScope cs(e);
+    cs.trace(label, "", d->N, d->H, d->W, d->Cin, d->Cout, d->R, d->stride, Ho * Wo * d->N, res != nullptr);
+    TRY(L->f16 ? conv2d_f16_launch(d, in, L->d_w, L->d_scale, L->d_shift, res, out, out_f32 ? 1 : 0, e.cur)
+               : conv2d_launch(d, in, L->d_w, L->d_scale, L->d_shift, res, (float*)out, e.cur));
+    const int cin_true = (d->Cin == 4 && d->R == 7) ? 3 : d->Cin;   // the stem's fourth input channel is padding
+    cs.done(2.0 * d->N * Ho * Wo * (double)d->Cout * d->R * d->S * cin_true, "%s [M=%d K=%d Cout=%d %dx%d/%d]", label.c_str(), d->N * Ho * Wo,
+            d->R * d->S * d->Cin, d->Cout, d->R, d->S, d->stride);
+    return ISEGMI_OK;
 }
 
 int eng_conv_into(Engine& e, const std::string& layer, const Tensor& in, int stride, int pad, int act, void* dst, int out_div,
@@ -134,6 +114,7 @@ int eng_conv_group(Engine& e, std::vector<ConvGroupItem>& items) {
     std::vector<const isegmi_conv_desc*> dp(n);
     std::vector<const float*> in(n), w(n), sc(n), sh(n), rs(n);
     std::vector<float*> out(n);
+    std::vector<int> M(n);
     double fl = 0;
     std::string label = "group[";
     for (int i = 0; i < n; ++i) {
@@ -155,25 +136,15 @@ int eng_conv_group(Engine& e, std::vector<ConvGroupItem>& items) {
         }
         dp[i] = &d; in[i] = it.in.d; w[i] = (const float*)L->d_w; sc[i] = L->d_scale; sh[i] = L->d_shift; rs[i] = it.residual ? it.residual->d : nullptr;
         fl += 2.0 * d.N * Ho * Wo * (double)d.Cout * d.R * d.S * d.Cin;
-        if (e.conv_trace) fprintf(stderr, "convlaunch\t%s\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\n", (it.layer + (i == 0 ? ".group" : ".grouped")).c_str(), d.N, d.H, d.W, d.Cin,
-                                  d.Cout, d.R, d.stride, Ho * Wo * d.N, rs[i] ? 1 : 0);
+        M[i] = Ho * Wo * d.N;
         if (i < 3) label += (i ? " " : "") + it.layer;
     }
     label += n > 3 ? " ... x" + std::to_string(n) + "]" : "]";
-    hipEvent_t a = nullptr, b = nullptr;
-    if (e.conv_timing) {
-        HIP_TRY(hipEventCreate(&a));
-        HIP_TRY(hipEventCreate(&b));
-        HIP_TRY(hipEventRecord(a, e.cur));
-    }
-    int rc = conv2d_group_launch(n, dp.data(), in.data(), w.data(), sc.data(), sh.data(), rs.data(), out.data(), e.cur);
-    if (rc) return rc;
-    if (e.conv_timing) {
-        HIP_TRY(hipEventRecord(b, e.cur));
-        e.conv_evs.push_back({a, b});
-        e.conv_flops_pending += fl;
-        e.conv_ev_info.push_back({label + " [" + std::to_string(n) + " convolutions, one launch]", fl});
-    }
+    ConvScope cs(e);
+    for (int i = 0; i < n; ++i)
+        cs.trace(items[i].layer, i == 0 ? ".group" : ".grouped", ds[i].N, ds[i].H, ds[i].W, ds[i].Cin, ds[i].Cout, ds[i].R, ds[i].stride, M[i], rs[i] != nullptr);
+    TRY(conv2d_group_launch(n, dp.data(), in.data(), w.data(), sc.data(), sh.data(), rs.data(), out.data(), e.cur));
+    cs.done(fl, "%s [%d convolutions, one launch]", label.c_str(), n);
     return ISEGMI_OK;
 }
 
@@ -202,27 +173,14 @@ int eng_bottleneck_f16(Engine& e, const std::string& block, const Tensor& x, boo
     isegmi_bottleneck_desc d;
     memset(&d, 0, sizeof(d));
     d.N = x.N; d.H = x.H; d.W = x.W; d.Cin = x.C; d.Cmid = Cmid;
-    hipEvent_t a = nullptr, b = nullptr;
-    if (e.conv_timing) {
-        HIP_TRY(hipEventCreate(&a));
-        HIP_TRY(hipEventCreate(&b));
-        HIP_TRY(hipEventRecord(a, e.cur));
-    }
+    ConvScope cs(e);
     const int M = x.N * x.H * x.W;
-    if (e.conv_trace) fprintf(stderr, "convlaunch\t%s.fused\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\n", block.c_str(), x.N, x.H, x.W, x.C, Cout, 3, 1, M, 1);
-    rc = bottleneck_f16_launch(&d, x.d, L1.d_w, L1.d_scale, L1.d_shift, L2.d_w, L2.d_scale, L2.d_shift, L3.d_w, L3.d_scale, L3.d_shift,
-                               first ? LD->d_w : nullptr, first ? LD->d_scale : nullptr, first ? LD->d_shift : nullptr, out->d, e.cur);
-    if (rc) return rc;
-    if (e.conv_timing) {
-        HIP_TRY(hipEventRecord(b, e.cur));
-        e.conv_evs.push_back({a, b});
-        // algorithmic FLOPs of the convolutions the launch stands for (the halo the fused kernel recomputes for conv1 is not counted)
-        const double fl = 2.0 * M * ((double)x.C * Cmid + 9.0 * Cmid * Cmid + (double)Cmid * Cout + (first ? (double)x.C * Cout : 0.0));
-        e.conv_flops_pending += fl;
-        char geo[160];
-        snprintf(geo, sizeof(geo), "%s.fused [M=%d Cin=%d Cmid=%d Cout=%d 1x1+3x3+1x1%s]", block.c_str(), M, x.C, Cmid, Cout, first ? "+proj" : "");
-        e.conv_ev_info.push_back({geo, fl});
-    }
+    cs.trace(block, ".fused", x.N, x.H, x.W, x.C, Cout, 3, 1, M, true);
+    TRY(bottleneck_f16_launch(&d, x.d, L1.d_w, L1.d_scale, L1.d_shift, L2.d_w, L2.d_scale, L2.d_shift, L3.d_w, L3.d_scale, L3.d_shift,
+                               first ? LD->d_w : nullptr, first ? LD->d_scale : nullptr, first ? LD->d_shift : nullptr, out->d, e.cur));
+    // algorithmic FLOPs of the convolutions the launch stands for (the halo the fused kernel recomputes for conv1 is not counted)
+    cs.done(2.0 * M * ((double)x.C * Cmid + 9.0 * Cmid * Cmid + (double)Cmid * Cout + (first ? (double)x.C * Cout : 0.0)),
+            "%s.fused [M=%d Cin=%d Cmid=%d Cout=%d 1x1+3x3+1x1%s]", block.c_str(), M, x.C, Cmid, Cout, first ? "+proj" : "");
     *fused = true;
     return ISEGMI_OK;
 }
@@ -241,25 +199,11 @@ int eng_conv_up2x_f16(Engine& e, const std::string& layer, const Tensor& x, cons
     isegmi_conv_desc d;
     memset(&d, 0, sizeof(d));
     d.N = x.N; d.H = x.H; d.W = x.W; d.Cin = x.C; d.Cout = L.Cout; d.R = 1; d.S = 1; d.stride = 1; d.pad = 0; d.act = 0;
-    hipEvent_t a = nullptr, b = nullptr;
-    if (e.conv_timing) {
-        HIP_TRY(hipEventCreate(&a));
-        HIP_TRY(hipEventCreate(&b));
-        HIP_TRY(hipEventRecord(a, e.cur));
-    }
+    ConvScope cs(e);
     const int M = x.N * x.H * x.W;
-    if (e.conv_trace) fprintf(stderr, "convlaunch\t%s.up2x\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\n", layer.c_str(), x.N, x.H, x.W, x.C, L.Cout, 1, 1, M, 1);
-    rc = conv2d_f16_up2x_launch(&d, x.d, L.d_w, L.d_scale, L.d_shift, coarse.d, coarse.H, coarse.W, out->d, e.cur);
-    if (rc) return rc;
-    if (e.conv_timing) {
-        HIP_TRY(hipEventRecord(b, e.cur));
-        e.conv_evs.push_back({a, b});
-        const double fl = 2.0 * M * (double)x.C * L.Cout;
-        e.conv_flops_pending += fl;
-        char geo[200];
-        snprintf(geo, sizeof(geo), "%s.up2x [M=%d K=%d Cout=%d 1x1/1 + nearest-2x top-down add]", layer.c_str(), M, x.C, L.Cout);
-        e.conv_ev_info.push_back({geo, fl});
-    }
+    cs.trace(layer, ".up2x", x.N, x.H, x.W, x.C, L.Cout, 1, 1, M, true);
+    TRY(conv2d_f16_up2x_launch(&d, x.d, L.d_w, L.d_scale, L.d_shift, coarse.d, coarse.H, coarse.W, out->d, e.cur));
+    cs.done(2.0 * M * (double)x.C * L.Cout, "%s.up2x [M=%d K=%d Cout=%d 1x1/1 + nearest-2x top-down add]", layer.c_str(), M, x.C, L.Cout);
     *merged = true;
     return ISEGMI_OK;
 }
@@ -278,29 +222,13 @@ int eng_rpn_head_f16(Engine& e, const std::string& conv, const std::string& head
     isegmi_conv_desc d;
     memset(&d, 0, sizeof(d));
     d.N = x.N; d.H = x.H; d.W = x.W; d.Cin = x.C; d.Cout = 256; d.R = 3; d.S = 3; d.stride = 1; d.pad = 1; d.act = 1;
-    hipEvent_t a = nullptr, b = nullptr;
-    if (e.conv_timing) {
-        HIP_TRY(hipEventCreate(&a));
-        HIP_TRY(hipEventCreate(&b));
-        HIP_TRY(hipEventRecord(a, e.cur));
-    }
-    rc = conv2d_f16_head_launch(&d, x.d, L.d_w, L.d_scale, L.d_shift, H.d_w, H.d_scale, H.d_shift, H.Cout, out->d, fused, e.cur);
-    if (rc) return rc;
-    if (!*fused) {
-        if (a) { HIP_TRY(hipEventDestroy(a)); HIP_TRY(hipEventDestroy(b)); }
-        return ISEGMI_OK;
-    }
+    ConvScope cs(e);
+    TRY(conv2d_f16_head_launch(&d, x.d, L.d_w, L.d_scale, L.d_shift, H.d_w, H.d_scale, H.d_shift, H.Cout, out->d, fused, e.cur));
+    if (!*fused) return ISEGMI_OK;
     const int M = x.N * x.H * x.W;
-    if (e.conv_trace) fprintf(stderr, "convlaunch\t%s+%s.fused\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\n", conv.c_str(), headl.c_str(), x.N, x.H, x.W, x.C, H.Cout, 3, 1, M, 0);
-    if (e.conv_timing) {
-        HIP_TRY(hipEventRecord(b, e.cur));
-        e.conv_evs.push_back({a, b});
-        const double fl = 2.0 * M * (9.0 * x.C * 256 + 256.0 * H.Cout);   // both convolutions' algorithmic FLOPs
-        e.conv_flops_pending += fl;
-        char geo[200];
-        snprintf(geo, sizeof(geo), "%s+%s.fused [M=%d K=%d Cout=256 3x3/1 + 1x1 -> %d]", conv.c_str(), headl.c_str(), M, 9 * x.C, H.Cout);
-        e.conv_ev_info.push_back({geo, fl});
-    }
+    cs.trace(conv + "+" + headl, ".fused", x.N, x.H, x.W, x.C, H.Cout, 3, 1, M, false);
+    // both convolutions' algorithmic FLOPs
+    cs.done(2.0 * M * (9.0 * x.C * 256 + 256.0 * H.Cout), "%s+%s.fused [M=%d K=%d Cout=256 3x3/1 + 1x1 -> %d]", conv.c_str(), headl.c_str(), M, 9 * x.C, H.Cout);
     return ISEGMI_OK;
 }
 
@@ -316,25 +244,12 @@ int eng_stem_pool_f16(Engine& e, const std::string& layer, const Tensor& halo, i
     const int Hc = (H + 6 - 7) / 2 + 1, Wc = (W + 6 - 7) / 2 + 1, Hp = (Hc + 2 - 3) / 2 + 1, Wp = (Wc + 2 - 3) / 2 + 1;
     int rc = eng_act(e, out_name, halo.N, Hp, Wp, L.Cout, out, 1);
     if (rc) return rc;
-    hipEvent_t a = nullptr, b = nullptr;
-    if (e.conv_timing) {
-        HIP_TRY(hipEventCreate(&a));
-        HIP_TRY(hipEventCreate(&b));
-        HIP_TRY(hipEventRecord(a, e.cur));
-    }
+    ConvScope cs(e);
     const int M = halo.N * Hc * Wc;
-    if (e.conv_trace) fprintf(stderr, "convlaunch\t%s.fused\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\n", layer.c_str(), halo.N, H, W, 4, L.Cout, 7, 2, M, 1);
-    rc = stem_pool_f16_launch(halo.N, H, W, halo.d, L.d_w, L.d_scale, L.d_shift, out->d, 0, e.cur);
-    if (rc) return rc;
-    if (e.conv_timing) {
-        HIP_TRY(hipEventRecord(b, e.cur));
-        e.conv_evs.push_back({a, b});
-        const double fl = 2.0 * M * 147.0 * L.Cout;   // the convolution's algorithmic FLOPs (7 x 7 x 3 taps), as the unfused layer counts them
-        e.conv_flops_pending += fl;
-        char geo[160];
-        snprintf(geo, sizeof(geo), "%s.fused [M=%d K=196 Cout=%d 7x7/2 + maxpool 3x3/2]", layer.c_str(), M, L.Cout);
-        e.conv_ev_info.push_back({geo, fl});
-    }
+    cs.trace(layer, ".fused", halo.N, H, W, 4, L.Cout, 7, 2, M, true);
+    TRY(stem_pool_f16_launch(halo.N, H, W, halo.d, L.d_w, L.d_scale, L.d_shift, out->d, 0, e.cur));
+    // the convolution's algorithmic FLOPs (7 x 7 x 3 taps), as the unfused layer counts them
+    cs.done(2.0 * M * 147.0 * L.Cout, "%s.fused [M=%d K=196 Cout=%d 7x7/2 + maxpool 3x3/2]", layer.c_str(), M, L.Cout);
     *fused = true;
     return ISEGMI_OK;
 }
@@ -542,416 +457,6 @@ static void collect_times(Engine& e) {
     }
     for (auto& m : e.marks) (void)hipEventDestroy(m.ev);
     e.marks.clear();
-}
-
-#define TRY(x)            \
-    do {                  \
-        int _rc = (x);    \
-        if (_rc) return _rc; \
-    } while (0)
-
-// Redirects everything the rest of a forward launches (main stream, side streams, current stream) to the heads stream group.
-// Points the engine's main / side streams and the names of the buffers eng_act allocates at lane e.lane for the duration of a forward.
-struct LaneScope {
-    Engine& e;
-    explicit LaneScope(Engine& e_) : e(e_) { set(e.lane); if (e.lane) e.lane_tag = "@1"; }
-    ~LaneScope() { set(0); e.lane_tag.clear(); e.cur = e.stream; }
-    void set(int l) {
-        if (e.lane_stream[l] == nullptr) return;
-        e.stream = e.lane_stream[l];
-        for (int k = 0; k < 3; ++k) e.side[k] = e.lane_side[l][k];
-    }
-};
-
-struct HeadsScope {
-    Engine& e;
-    hipStream_t s, sd[3];
-    bool on = false;
-    explicit HeadsScope(Engine& e_) : e(e_), s(e_.stream) { for (int k = 0; k < 3; ++k) sd[k] = e.side[k]; }
-    // wide = the group's branches (three laterals, protonet || prediction heads per level) on the group's own three side streams; otherwise they
-    // queue on the heads stream one after the other (see yolact_forward)
-    void enter(bool wide) { on = true; e.stream = e.heads; for (int k = 0; k < 3; ++k) e.side[k] = wide ? e.hside[k] : e.heads; e.cur = e.heads; }
-    ~HeadsScope() { if (on) { e.stream = s; for (int k = 0; k < 3; ++k) e.side[k] = sd[k]; e.cur = s; } }
-};
-
-int yolact_forward(Engine& e, const float* d_images, int N) {
-    const int H = e.H, W = e.W;
-    LaneScope lscope(e);
-    const int lane = e.lane;
-    e.cur = e.stream;
-    // cross-step pipelining of the heads phase (eager multi-stream throughput mode only)
-    const bool pipe = e.multi_stream && !e.capturing && !e.timing && !e.conv_timing && e.heads != nullptr &&
-                      e.param("graph", 0.0f) == 0.0f && e.param("pipeline_heads", 1.0f) != 0.0f;
-    HeadsScope hscope(e);
-    eng_mark(e, "start");
-    const int dt = e.fp16 ? 1 : 0;  // fp16 storage + f16 MFMA convolutions (optional mode; heads / prototypes / Detect stay fp32)
-    if (dt && e.convs.count("prediction_layers.0.head_cat") == 0) { set_error("fp16 Yolact needs the fused prediction head"); return ISEGMI_ERR_STATE; }
-    Tensor x4;
-    Tensor s, x;
-    bool stem_fused = false;
-    Tensor outs[5];
-    const bool darknet = e.param("darknet", 0.0f) != 0.0f;  // yolact_darknet53_config: DarkNetBackbone([1, 2, 8, 8, 4]), selected layers 2-4
-    if (darknet) {
-        if (dt) { set_error("the Darknet53 backbone runs in fp32 only"); return ISEGMI_ERR_STATE; }
-        // _preconv: 3x3 on the 3-channel image, via a zero-padded 32-channel copy; every conv is Conv + BN + LeakyReLU(0.1), a
-        // block is 1x1 (C -> C/2) then 3x3 (C/2 -> C) with the shortcut added AFTER the activation (act 4)
-        TRY(eng_act(e, "input32", N, H, W, 32, &x4));
-        TRY(pad_c3_c32_launch(d_images, (int64_t)N * H * W, x4.d, e.cur));
-        TRY(eng_input_consumed(e));
-        TRY(eng_conv(e, "backbone._preconv.0", x4, 1, 1, 3, nullptr, "stem", &x));
-        eng_mark(e, "stem");
-        const int nblk[5] = {1, 2, 8, 8, 4};
-        for (int li = 0; li < 5; ++li) {
-            const std::string ln = "backbone.layers." + std::to_string(li);
-            // C3 (layer 2's output, then C4, C5) is about to be overwritten: the previous step's lateral convs must have read them
-            if (li == 2 && e.lat_pending[lane]) HIP_TRY(hipStreamWaitEvent(e.stream, e.lat_done[lane], 0));
-            Tensor y;
-            TRY(eng_conv(e, ln + ".0.0", x, 2, 1, 3, nullptr, ln + ".down", &y));
-            x = y;
-            for (int b = 1; b <= nblk[li]; ++b) {
-                const std::string nm = ln + "." + std::to_string(b);
-                Tensor t1;
-                TRY(eng_conv(e, nm + ".conv1", x, 1, 0, 3, nullptr, nm + ".t1", &t1));
-                TRY(eng_conv(e, nm + ".conv2", t1, 1, 1, 4, &x, nm + ".out", &y));
-                x = y;
-            }
-            outs[li] = x;
-            if (li >= 1) eng_mark(e, li == 1 ? "layer1" : li == 2 ? "layer2" : li == 3 ? "layer3" : "layer4");
-        }
-    } else {
-    if (dt) {
-        TRY(eng_act(e, "input4h", N, H + 6, (W + 7) & ~1, 4, &x4, 1));
-        TRY(pad_c3_to_f16_halo_launch(d_images, N, H, W, x4.d, e.cur));
-        TRY(eng_input_consumed(e));
-        TRY(eng_stem_pool_f16(e, "backbone.conv1", x4, H, W, "pool", &x, &stem_fused));
-        if (!stem_fused) TRY(eng_conv_stem_f16(e, "backbone.conv1", x4, H, W, "stem", &s));
-    } else {
-        TRY(eng_act(e, "input4", N, H, W, 4, &x4));
-        TRY(pad_c3_c4_launch(d_images, (int64_t)N * H * W, x4.d, e.cur));
-        TRY(eng_input_consumed(e));
-        TRY(eng_conv(e, "backbone.conv1", x4, 2, 3, 1, nullptr, "stem", &s));
-    }
-    if (!stem_fused) {
-        const int Ho = (s.H + 2 - 3) / 2 + 1, Wo = (s.W + 2 - 3) / 2 + 1;
-        TRY(eng_act(e, "pool", N, Ho, Wo, s.C, &x, dt));
-        if (dt) TRY(maxpool_to_f16_launch(s.d, 1, N, s.H, s.W, s.C, 3, 2, 1, x.d, e.cur));
-        else TRY(maxpool_launch(s.d, N, s.H, s.W, s.C, 3, 2, 1, x.d, e.cur));
-    }
-    eng_mark(e, "stem");
-    const int blocks[4] = {3, 4, (int)e.param("resnet_depth", 50) == 101 ? 23 : 6, 3};
-    for (int li = 0; li < 4; ++li) {
-        for (int b = 0; b < blocks[li]; ++b) {
-            const std::string nm = "backbone.layers." + std::to_string(li) + "." + std::to_string(b);
-            const int st = (b == 0 && li > 0) ? 2 : 1;
-            Tensor idt = x, t1, t2, y;
-            // buffers by liveness (see maskrcnn.cpp): one t1 / t2 per stage, two alternating block outputs, the stage's final output on its own
-            // (C3-C5 are read by the lateral convs of the pipelined heads phase; the lat_done fence below guards exactly those)
-            const bool alias = e.param("alias_buffers", 1.0f) != 0.0f;  // 0: one buffer per layer output (rounds 1-2; kept for A/B)
-            const std::string sg = alias ? "res" + std::to_string(li + 2) : nm;
-            const std::string out_name = !alias ? nm + ".out" : b == blocks[li] - 1 ? sg + ".C" : sg + (b & 1 ? ".outB" : ".outA");
-            if (dt && (b > 0 || st == 1)) {  // fp16 identity blocks of res2 / res3 and res2's first block: one launch, t1 / t2 stay in LDS (csrc/bottleneck_f16.hip)
-                if (li == 1 && b == blocks[1] - 1 && e.lat_pending[lane]) HIP_TRY(hipStreamWaitEvent(e.stream, e.lat_done[lane], 0));  // (see below)
-                bool fused = false;
-                TRY(eng_bottleneck_f16(e, nm, x, b == 0, out_name, &y, &fused));
-                if (fused) { x = y; continue; }
-            }
-            const bool pair = b == 0 && !dt && e.param("conv_groups", 1.0f) != 0.0f && e.param("conv_tile", 0) == 0.0f;
-            if (pair) {  // fp32: the projection shortcut and conv1 read the same x: one grouped launch (round 5) instead of a side stream
-                std::vector<ConvGroupItem> g(2);
-                g[0].layer = nm + ".conv1"; g[0].in = x; g[0].act = 1; g[0].out_name = sg + ".t1"; g[0].out = &t1;
-                g[1].layer = nm + ".downsample.0"; g[1].in = x; g[1].stride = st; g[1].out_name = nm + ".ds"; g[1].out = &idt;
-                TRY(eng_conv_group(e, g));
-            } else {
-            if (b == 0) {  // the projection shortcut is independent of conv1 -> conv2: side stream
-                TRY(eng_fork(e, 0));
-                SideScope sc(e, 0);
-                TRY(eng_conv(e, nm + ".downsample.0", x, st, 0, 0, nullptr, nm + ".ds", &idt));
-            }
-            TRY(eng_conv(e, nm + ".conv1", x, 1, 0, 1, nullptr, sg + ".t1", &t1, false, /*may_split=*/b > 0));
-            }
-            if (e.convs.count(nm + ".conv2.conv_offset_mask")) {
-                // DCNv2 3x3 (YOLACT++ backbones): offsets + mask logits from a plain 3x3 -> the nine taps sampled into columns ->
-                // the deformable conv proper as a 1x1 over 9*C channels (weights handed over in KRSC order, bias folded into BN)
-                if (dt) { set_error("the DCNv2 backbones run in fp32 only"); return ISEGMI_ERR_STATE; }
-                Tensor om, col;
-                TRY(eng_conv(e, nm + ".conv2.conv_offset_mask", t1, st, 1, 0, nullptr, nm + ".om", &om));
-                TRY(eng_act(e, nm + ".col", N, om.H, om.W, 9 * t1.C, &col));
-                TRY(deform_im2col_launch((const float*)t1.d, N, t1.H, t1.W, t1.C, (const float*)om.d, 3, 3, st, 1, 1, (float*)col.d, e.cur));
-                TRY(eng_conv(e, nm + ".conv2", col, 1, 0, 1, nullptr, sg + ".t2", &t2));
-            } else {
-                TRY(eng_conv(e, nm + ".conv2", t1, st, 1, 1, nullptr, sg + ".t2", &t2, false, /*may_split=*/true));
-            }
-            if (b == 0 && !pair) TRY(eng_join(e, 0));
-            // C3 (then C4, C5) is about to be overwritten: the previous step's lateral convs, running on the heads streams, must
-            // have read them (they are the first thing of that phase, so this wait practically never blocks)
-            if (li == 1 && b == blocks[1] - 1 && e.lat_pending[lane]) HIP_TRY(hipStreamWaitEvent(e.stream, e.lat_done[lane], 0));
-            TRY(eng_conv(e, nm + ".conv3", t2, 1, 0, 1, &idt, out_name, &y, false, /*may_split=*/true));
-            x = y;
-        }
-        outs[li] = x;
-        eng_mark(e, li == 0 ? "layer1" : li == 1 ? "layer2" : li == 2 ? "layer3" : "layer4");
-    }
-    }
-    const Tensor C3 = outs[darknet ? 2 : 1], C4 = outs[darknet ? 3 : 2], C5 = outs[darknet ? 4 : 3];
-    if (pipe) {  // hand the rest of this forward to the heads stream group; the caller's next forward starts its backbone at once
-        hipEvent_t ev;
-        TRY(eng_next_event(e, &ev));
-        HIP_TRY(hipEventRecord(ev, e.stream));
-        HIP_TRY(hipStreamWaitEvent(e.heads, ev, 0));
-        // Side streams for the heads group only where a forward is latency-bound (small batches: bs=1 p50 1.98 vs 2.24 ms).  At the bench batch two
-        // concurrent streams of chip-filling convolutions (backbone i+1 || heads i) leave nothing for more streams to fill, and every extra stream
-        // is one more for the runtime to fold onto its four in-order hardware queues, where a branch then waits behind kernels of the other group
-        // it does not depend on: without them +1-4 % (Yolact fp32 / yolact_base / fp16 bs=8; profiles/r03_experiments.txt 3c).  Parameter
-        // "heads_side_streams": 1 always, 0 never, default by batch size.
-        const float hs = e.param("heads_side_streams", -1.0f);
-        hscope.enter(hs < 0.0f ? N <= 2 : hs != 0.0f);
-    } else if (e.heads_pending) {  // mode switch without a sync in between: an earlier pipelined heads phase writes the same buffers
-        HIP_TRY(hipStreamWaitEvent(e.stream, e.heads_done, 0));
-        e.heads_pending = false;
-    }
-    // FPN: the three laterals are independent; so are the three prediction convs.  fp32 (round 5): each trio is ONE grouped launch (eng_conv_group), and
-    // so are the five levels' upfeature and head_cat convs below: 16 launches become 4, and the small levels run inside the big level's launch instead of
-    // as 23-us launches of their own.  "conv_groups" 0 restores the per-layer launches (A/B; fp16 and the unfused head layout keep them anyway).
-    const bool grp = !dt && e.param("conv_groups", 1.0f) != 0.0f && e.param("conv_tile", 0) == 0.0f && e.convs.count("prediction_layers.0.head_cat") != 0;
-    Tensor l5, l4, l3, x4f, x3f, P[5];
-    if (grp) {
-        std::vector<ConvGroupItem> g(3);
-        g[0].layer = "fpn.lat_layers.2"; g[0].in = C3; g[0].out_name = "fpn.lat3"; g[0].out = &l3;
-        g[1].layer = "fpn.lat_layers.1"; g[1].in = C4; g[1].out_name = "fpn.lat4"; g[1].out = &l4;
-        g[2].layer = "fpn.lat_layers.0"; g[2].in = C5; g[2].out_name = "fpn.lat5"; g[2].out = &l5;
-        TRY(eng_conv_group(e, g));
-    } else {
-    TRY(eng_fork(e, 0));
-    TRY(eng_fork(e, 1));
-    { SideScope sc(e, 0); TRY(eng_conv(e, "fpn.lat_layers.1", C4, 1, 0, 0, nullptr, "fpn.lat4", &l4)); }
-    { SideScope sc(e, 1); TRY(eng_conv(e, "fpn.lat_layers.2", C3, 1, 0, 0, nullptr, "fpn.lat3", &l3)); }
-    TRY(eng_conv(e, "fpn.lat_layers.0", C5, 1, 0, 0, nullptr, "fpn.lat5", &l5));
-    TRY(eng_join(e, 0));
-    TRY(eng_join(e, 1));
-    }
-    if (pipe) { HIP_TRY(hipEventRecord(e.lat_done[lane], e.stream)); e.lat_pending[lane] = true; }
-    TRY(eng_act(e, "fpn.x4", N, l4.H, l4.W, l4.C, &x4f, dt));
-    if (dt) TRY(resize_bilinear_f16_launch(l5.d, N, l5.H, l5.W, l5.C, l4.H, l4.W, l4.d, 0, x4f.d, e.cur));
-    else TRY(resize_bilinear_launch(l5.d, N, l5.H, l5.W, l5.C, l4.H, l4.W, l4.d, 0, x4f.d, e.cur));
-    TRY(eng_act(e, "fpn.x3", N, l3.H, l3.W, l3.C, &x3f, dt));
-    if (dt) TRY(resize_bilinear_f16_launch(x4f.d, N, x4f.H, x4f.W, x4f.C, l3.H, l3.W, l3.d, 0, x3f.d, e.cur));
-    else TRY(resize_bilinear_launch(x4f.d, N, x4f.H, x4f.W, x4f.C, l3.H, l3.W, l3.d, 0, x3f.d, e.cur));
-    if (grp) {
-        std::vector<ConvGroupItem> g(3);
-        g[0].layer = "fpn.pred_layers.2"; g[0].in = x3f; g[0].out_name = "P3"; g[0].out = &P[0];
-        g[1].layer = "fpn.pred_layers.1"; g[1].in = x4f; g[1].out_name = "P4"; g[1].out = &P[1];
-        g[2].layer = "fpn.pred_layers.0"; g[2].in = l5; g[2].out_name = "P5"; g[2].out = &P[2];
-        for (auto& it : g) { it.pad = 1; it.act = 1; }
-        TRY(eng_conv_group(e, g));
-        TRY(eng_conv(e, "fpn.downsample_layers.0", P[2], 2, 1, 0, nullptr, "P6", &P[3]));
-        TRY(eng_conv(e, "fpn.downsample_layers.1", P[3], 2, 1, 0, nullptr, "P7", &P[4]));
-    } else {
-    TRY(eng_fork(e, 0));
-    TRY(eng_fork(e, 1));
-    {
-        SideScope sc(e, 0);  // P5 -> P6 -> P7 chain
-        TRY(eng_conv(e, "fpn.pred_layers.0", l5, 1, 1, 1, nullptr, "P5", &P[2]));
-        TRY(eng_conv(e, "fpn.downsample_layers.0", P[2], 2, 1, 0, nullptr, "P6", &P[3]));
-        TRY(eng_conv(e, "fpn.downsample_layers.1", P[3], 2, 1, 0, nullptr, "P7", &P[4]));
-    }
-    { SideScope sc(e, 1); TRY(eng_conv(e, "fpn.pred_layers.1", x4f, 1, 1, 1, nullptr, "P4", &P[1])); }
-    TRY(eng_conv(e, "fpn.pred_layers.2", x3f, 1, 1, 1, nullptr, "P3", &P[0]));
-    TRY(eng_join(e, 0));
-    TRY(eng_join(e, 1));
-    }
-    eng_mark(e, "fpn");
-    e.lane_tag.clear();   // everything allocated from here on (protonet, heads, Detect) exists once: it runs in step order behind the WAR point below
-    // shared prediction head geometry
-    const int A = (int)e.param("num_priors", 3), ncls = 81, md = 32;  // 9 for YOLACT++ (3 scales x 3 aspect ratios per cell)
-    int Ptot = 0, off[5];
-    for (int l = 0; l < 5; ++l) { off[l] = Ptot; Ptot += P[l].H * P[l].W * A; }
-    {
-        auto it = e.tensors.find("priors");
-        if (it == e.tensors.end() || it->second.bytes != (int64_t)Ptot * 16) { set_error("priors tensor missing or wrong size"); return ISEGMI_ERR_STATE; }
-    }
-    // The three prediction convs (bbox 12, conf 243, mask 96) run as ONE 351-wide convolution when the host supplied
-    // the fused layer: 6 instead of 1+4+2 64-wide column tiles per pixel tile, 5 launches instead of 15.  Its output
-    // row per pixel is [A x 4 loc | A x 81 conf | A x 32 mask(pre-tanh)]; Detect reads it in place (HeadLayout).
-    const bool fused = e.convs.count("prediction_layers.0.head_cat") != 0;
-    const int CH = A * (4 + ncls + md);
-    void *loc = nullptr, *conf = nullptr, *mask = nullptr, *headcat = nullptr;
-    if (fused) {
-        TRY(eng_buf(e, "headcat", (int64_t)N * (Ptot / A) * CH * 4, &headcat, 0, {N, Ptot / A, CH}));
-    } else {
-        TRY(eng_buf(e, "loc", (int64_t)N * Ptot * 4 * 4, &loc, 0, {N, Ptot, 4}));
-        TRY(eng_buf(e, "conf", (int64_t)N * Ptot * ncls * 4, &conf, 0, {N, Ptot, ncls}));
-        TRY(eng_buf(e, "mask", (int64_t)N * Ptot * md * 4, &mask, 0, {N, Ptot, md}));
-    }
-    auto head_level = [&](int l) -> int {
-        Tensor uf;
-        const std::string ln = "head.up" + std::to_string(l);
-        TRY(eng_conv(e, "prediction_layers.0.upfeature.0", P[l], 1, 1, 1, nullptr, ln, &uf));
-        const int hw = uf.H * uf.W;
-        if (fused) {
-            TRY(eng_conv_into(e, "prediction_layers.0.head_cat", uf, 1, 1, 0, (float*)headcat + (int64_t)(off[l] / A) * CH, hw,
-                              (int64_t)(Ptot / A) * CH, CH, /*out_f32=*/true));
-            return ISEGMI_OK;
-        }
-        TRY(eng_conv_into(e, "prediction_layers.0.bbox_layer", uf, 1, 1, 0, (float*)loc + (int64_t)off[l] * 4, hw, (int64_t)Ptot * 4, A * 4));
-        TRY(eng_conv_into(e, "prediction_layers.0.conf_layer", uf, 1, 1, 0, (float*)conf + (int64_t)off[l] * ncls, hw, (int64_t)Ptot * ncls, A * ncls));
-        TRY(eng_conv_into(e, "prediction_layers.0.mask_layer", uf, 1, 1, 2, (float*)mask + (int64_t)off[l] * md, hw, (int64_t)Ptot * md, A * md));
-        return ISEGMI_OK;
-    };
-    // WAR: the previous forward's Detect / postprocess (tail stream) still reads loc/conf/mask/proto and the det.*
-    // buffers; everything before this point touched only backbone/FPN buffers and was free to overlap with it.
-    // (Two lanes: this wait is also what orders this step's heads phase behind the previous step's when pipeline_heads is off and the two
-    // run on different lanes' main streams -- tail_done is recorded behind the previous step's Detect, which follows its heads.)
-    if (e.multi_stream && e.tail_pending && !e.capturing) HIP_TRY(hipStreamWaitEvent(e.stream, e.tail_done, 0));
-    // protonet (side 0) || heads on P3 (main) || heads on P4,P6 (side 1) || heads on P5,P7 (side 2)
-    Tensor proto;
-    TRY(eng_fork(e, 0));
-    TRY(eng_fork(e, 1));
-    TRY(eng_fork(e, 2));
-    {
-        SideScope sc(e, 0);
-        Tensor t, u;
-        TRY(eng_conv(e, "proto_net.0", P[0], 1, 1, 1, nullptr, "proto.t0", &t));
-        TRY(eng_conv(e, "proto_net.2", t, 1, 1, 1, nullptr, "proto.t1", &u));
-        TRY(eng_conv(e, "proto_net.4", u, 1, 1, 1, nullptr, "proto.t2", &t));
-        TRY(eng_act(e, "proto.up", N, t.H * 2, t.W * 2, t.C, &u, dt));
-        if (dt) TRY(resize_bilinear_f16_launch(t.d, N, t.H, t.W, t.C, t.H * 2, t.W * 2, nullptr, 1, u.d, e.cur));
-        else TRY(resize_bilinear_launch(t.d, N, t.H, t.W, t.C, t.H * 2, t.W * 2, nullptr, 1, u.d, e.cur));
-        TRY(eng_conv(e, "proto_net.8", u, 1, 1, 1, nullptr, "proto.t3", &t));
-        TRY(eng_conv(e, "proto_net.10", t, 1, 0, 1, nullptr, "proto", &proto, /*out_f32=*/true));
-    }
-    if (grp) {   // the shared head over all five levels: upfeature x 5 as one launch, head_cat x 5 as one launch (main stream; the protonet on side 0)
-        Tensor uf[5];
-        std::vector<ConvGroupItem> gu(5), gh(5);
-        for (int l = 0; l < 5; ++l) {
-            gu[l].layer = "prediction_layers.0.upfeature.0"; gu[l].in = P[l]; gu[l].pad = 1; gu[l].act = 1; gu[l].out_name = "head.up" + std::to_string(l); gu[l].out = &uf[l];
-        }
-        TRY(eng_conv_group(e, gu));
-        for (int l = 0; l < 5; ++l) {
-            gh[l].layer = "prediction_layers.0.head_cat"; gh[l].in = uf[l]; gh[l].pad = 1; gh[l].act = 0;
-            gh[l].dst = (float*)headcat + (int64_t)(off[l] / A) * CH; gh[l].out_div = uf[l].H * uf[l].W;
-            gh[l].out_img_stride = (int64_t)(Ptot / A) * CH; gh[l].out_pix_stride = CH; gh[l].out_f32 = true;
-        }
-        TRY(eng_conv_group(e, gh));
-    } else {
-    { SideScope sc(e, 1); TRY(head_level(1)); TRY(head_level(3)); }
-    { SideScope sc(e, 2); TRY(head_level(2)); TRY(head_level(4)); }
-    TRY(head_level(0));
-    }
-    TRY(eng_join(e, 0));
-    TRY(eng_join(e, 1));
-    TRY(eng_join(e, 2));
-    eng_mark(e, "proto+heads");
-    // Detect
-    const int top_k = (int)e.param("nms_top_k", 200), max_det = (int)e.param("max_num_detections", 100);
-    const int nc = ncls - 1;
-    isegmi_yolact_detect_args a;
-    memset(&a, 0, sizeof(a));
-    a.N = N; a.P = Ptot; a.ncls = ncls; a.mask_dim = md; a.top_k = top_k; a.max_det = max_det;
-    a.conf_thresh = e.param("nms_conf_thresh", 0.05f);
-    a.nms_thresh = e.param("nms_thresh", 0.5f);
-    a.second_threshold = (int)e.param("nms_second_threshold", 0) ? 1 : 0;   // App. A.6 fork (fast_nms(second_threshold=...)): default off
-    if (fused) {
-        a.d_conf = a.d_loc = a.d_mask = (const float*)headcat;
-        a.A = A; a.pix_stride = CH; a.off_loc = 0; a.off_conf = A * 4; a.off_mask = A * 4 + A * ncls; a.mask_tanh = 1;
-    } else {
-        a.d_conf = (const float*)conf; a.d_loc = (const float*)loc; a.d_mask = (const float*)mask;
-    }
-    a.d_priors = (const float*)e.tensors["priors"].d;
-    void* p;
-    TRY(eng_buf(e, "ws.scoresT", (int64_t)N * nc * Ptot * 4, &p)); a.d_ws_scoresT = (float*)p;
-    TRY(eng_buf(e, "boxes_all", (int64_t)N * Ptot * 16, &p, 0, {N, Ptot, 4})); a.d_ws_boxes = (float*)p;
-    TRY(eng_buf(e, "ws.counts", (int64_t)2 * N * 4, &p, 1)); a.d_ws_counts = (int32_t*)p;
-    TRY(eng_buf(e, "ws.tk_vals", (int64_t)N * nc * top_k * 4, &p)); a.d_ws_tk_vals = (float*)p;
-    TRY(eng_buf(e, "ws.tk_idx", (int64_t)N * nc * top_k * 4, &p, 1)); a.d_ws_tk_idx = (int32_t*)p;
-    TRY(eng_buf(e, "ws.tk_cnt", (int64_t)N * nc * 4, &p, 1)); a.d_ws_tk_cnt = (int32_t*)p;
-    TRY(eng_buf(e, "ws.cand", (int64_t)N * nc * top_k * 4, &p)); a.d_ws_cand = (float*)p;
-    TRY(eng_buf(e, "ws.fin_vals", (int64_t)N * max_det * 4, &p)); a.d_ws_fin_vals = (float*)p;
-    TRY(eng_buf(e, "ws.fin_idx", (int64_t)N * max_det * 4, &p, 1)); a.d_ws_fin_idx = (int32_t*)p;
-    TRY(eng_buf(e, "ws.fin_cnt", (int64_t)N * 4, &p, 1)); a.d_ws_fin_cnt = (int32_t*)p;
-    TRY(eng_buf(e, "det.count", (int64_t)N * 4, &p, 1, {N})); a.d_out_count = (int32_t*)p;
-    TRY(eng_buf(e, "det.box", (int64_t)N * max_det * 16, &p, 0, {N, max_det, 4})); a.d_out_boxes = (float*)p;
-    TRY(eng_buf(e, "det.score", (int64_t)N * max_det * 4, &p, 0, {N, max_det})); a.d_out_scores = (float*)p;
-    TRY(eng_buf(e, "det.class", (int64_t)N * max_det * 4, &p, 1, {N, max_det})); a.d_out_classes = (int32_t*)p;
-    TRY(eng_buf(e, "det.coeff", (int64_t)N * max_det * md * 4, &p, 0, {N, max_det, md})); a.d_out_coeffs = (float*)p;
-    TRY(eng_buf(e, "det.prior", (int64_t)N * max_det * 4, &p, 1, {N, max_det})); a.d_out_prior = (int32_t*)p;
-    // Detect is a chain of small latency-bound grids: run it (and postprocess) on the tail stream so the NEXT
-    // forward's MFMA-bound backbone can start underneath it.
-    hipStream_t ds = e.stream;
-    if (e.multi_stream) {
-        hipEvent_t ev;
-        TRY(eng_next_event(e, &ev));
-        HIP_TRY(hipEventRecord(ev, e.stream));
-        HIP_TRY(hipStreamWaitEvent(e.tail, ev, 0));
-        ds = e.tail;
-    }
-    {
-        // confidences, box regressions and mask coefficients of every prior once (the fused head's [N][P][4 + 81 + 32] rows) + priors
-        OpScope op(e, ds, "yolact_detect (softmax + decode + per-class top-k + fast-NMS + gather)", (double)N * Ptot * ((double)(4 + nc + md) * 4) + (double)Ptot * 16);
-        TRY(yolact_detect_launch(&a, ds));
-    }
-    if (pipe) { HIP_TRY(hipEventRecord(e.heads_done, e.stream)); e.heads_pending = true; }
-    TRY(eng_tail_end(e));
-    eng_mark(e, "detect");
-    return ISEGMI_OK;
-}
-
-// h_image_hw (optional, [N][2]): image n is assembled at its own (h_n, w_n) inside the common (h, w) plane
-int yolact_postprocess(Engine& e, int h, int w, const int32_t* h_image_hw) {
-    const int N = e.last_N;
-    if (N <= 0) { set_error("postprocess before forward"); return ISEGMI_ERR_STATE; }
-    const int K = (int)e.param("max_num_detections", 100);
-    RawBuf& proto = e.bufs["proto"];
-    const int PH = (int)proto.shape[1], PW = (int)proto.shape[2], md = (int)proto.shape[3];
-    void *lo, *masks, *ib;
-    hipStream_t rs = (e.multi_stream && e.tail_pending) ? e.tail : e.stream;  // results stream of the last forward
-    int* d_ihw = nullptr;
-    if (h_image_hw) {
-        for (int i = 0; i < N; ++i)
-            if (h_image_hw[2 * i] <= 0 || h_image_hw[2 * i] > h || h_image_hw[2 * i + 1] <= 0 || h_image_hw[2 * i + 1] > w) { set_error("postprocess: image size outside the plane"); return ISEGMI_ERR_ARG; }
-        void* q;
-        TRY(eng_buf(e, "pp.image_hw", (int64_t)e.max_batch * 8, &q, 1, {N, 2}));
-        d_ihw = (int*)q;
-        TRY(eng_stage_small(e, h_image_hw, (size_t)N * 8, d_ihw, rs));
-    }
-    TRY(eng_buf(e, "ws.lo", (int64_t)N * K * PH * PW * 4, &lo));
-    TRY(eng_buf(e, "det.masks", (int64_t)N * K * h * w, &masks, 2, {N, K, h, w}));
-    TRY(eng_buf(e, "det.box_int", (int64_t)N * K * 4 * 8, &ib, 3, {N, K, 4}));
-    void* wq;
-    TRY(eng_buf(e, "det.mask_window", (int64_t)e.max_batch * K * 16, &wq, 1, {N, K, 4}));
-    {
-        // SURVEY 8d "Yolact assembly: read the prototypes + coefficients, write n x h x w" (uint8 planes; whole unless sparse_masks)
-        const bool whole = e.param("sparse_masks", 0.0f) == 0.0f;
-        OpScope op(e, rs, whole ? "yolact_masks (proto @ coeff -> sigmoid -> crop -> upsample -> threshold, whole uint8 planes)" : "yolact_masks (sparse: box windows only)",
-                   (double)N * PH * PW * md * 4 + (double)N * K * md * 4 + (whole ? (double)N * K * h * w : 0.0));
-        TRY(yolact_masks_launch((const float*)proto.d, (const float*)e.bufs["det.coeff"].d, (const float*)e.bufs["det.box"].d,
-                                (const int*)e.bufs["det.count"].d, N, PH, PW, md, K, h, w, (float*)lo, (uint8_t*)masks, (int64_t*)ib,
-                                rs, d_ihw, (int*)wq, whole, /*dense_lo=*/e.convs.count("maskiou_net.2") != 0));
-    }
-    if (e.convs.count("maskiou_net.2")) {
-        // YOLACT++ fast mask re-scoring on the proto-resolution masks just written to ws.lo: first layer (1 input channel) and
-        // the global-max / class pick as small dedicated kernels, the rest on the MFMA conv kernels over all N*K slots
-        auto w0 = e.tensors.find("maskiou.w0"), b0 = e.tensors.find("maskiou.b0");
-        if (w0 == e.tensors.end() || b0 == e.tensors.end()) { set_error("maskiou_net.0 weights missing"); return ISEGMI_ERR_STATE; }
-        hipStream_t saved = e.cur;
-        e.cur = rs;
-        Tensor t, u;
-        TRY(eng_act(e, "maskiou.t0", N * K, (PH - 3) / 2 + 1, (PW - 3) / 2 + 1, 32, &t));
-        TRY(maskiou_conv1_launch((const float*)lo, N * K, PH, PW, (const float*)w0->second.d, (const float*)b0->second.d, t.d, rs));
-        for (int i = 2; i <= 8; i += 2) {
-            if (t.H < 3 || t.W < 3) { e.cur = saved; set_error("input too small for the mask-IoU net (five stride-2 3x3 convs)"); return ISEGMI_ERR_ARG; }
-            TRY(eng_conv(e, "maskiou_net." + std::to_string(i), t, 2, 0, 1, nullptr, "maskiou.t" + std::to_string(i), &u));
-            t = u;
-        }
-        TRY(eng_conv(e, "maskiou_net.10", t, 1, 0, 1, nullptr, "maskiou.cls", &u));
-        void* ms;
-        TRY(eng_buf(e, "det.mask_score", (int64_t)N * K * 4, &ms, 0, {N, K}));
-        TRY(maskiou_rescore_launch(u.d, N, K, u.H * u.W, u.C, (const int*)e.bufs["det.class"].d, (const float*)e.bufs["det.score"].d,
-                                   (const int*)e.bufs["det.count"].d, (float*)ms, rs));
-        e.cur = saved;
-    }
-    if (rs == e.tail) HIP_TRY(hipEventRecord(e.tail_done, e.tail));
-    eng_mark(e, "masks");
-    return ISEGMI_OK;
 }
 
 }  // namespace isegmi

@@ -1,6 +1,8 @@
-// engine.h -- model engine: packed-weight registry, named activation buffers, per-model forward graphs.
+// engine.h -- model engine: packed-weight registry, named activation buffers, per-model forward graphs (yolact.cpp, maskrcnn.cpp, pose2seg.cpp).
 #pragma once
 #include "rpn_levels.h"
+#include <stdarg.h>
+
 #include <functional>
 #include <map>
 #include <string>
@@ -8,6 +10,12 @@
 
 #include "../../include/isegmi.h"
 #include "common.h"
+
+#define TRY(x)               \
+    do {                     \
+        int _rc = (x);       \
+        if (_rc) return _rc; \
+    } while (0)
 
 namespace isegmi {
 
@@ -215,6 +223,63 @@ struct OpScope {
         else (void)hipEventDestroy(a);
     }
 };
+
+// RAII: one conv-type launch (or one grouped launch) on e.cur.  With "conv_timing" it brackets the launch with a HIP event pair, which done() hands
+// to conv_report / conv_stats with the launch's label and algorithmic FLOPs; with "conv_trace", trace() prints the launch's `convlaunch` line (one
+// per member of a grouped launch).  A scope left without done() -- an error, or nothing launched -- destroys its events: no half-recorded pair.
+struct ConvScope {
+    Engine& e;
+    hipEvent_t a = nullptr, b = nullptr;
+    explicit ConvScope(Engine& e_) : e(e_) {
+        if (!e.conv_timing) return;
+        if (hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess && hipEventRecord(a, e.cur) == hipSuccess) return;
+        drop();
+    }
+    ~ConvScope() { drop(); }
+    void drop() {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+        a = b = nullptr;
+    }
+    // dev tools (tools/conv_traffic.py): the launch order, to join per-dispatch counters with layers
+    void trace(const std::string& layer, const char* suffix, int N, int H, int W, int Cin, int Cout, int R, int stride, int M, bool res) const {
+        if (e.conv_trace) fprintf(stderr, "convlaunch\t%s%s\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\n", layer.c_str(), suffix, N, H, W, Cin, Cout, R, stride, M, res ? 1 : 0);
+    }
+    __attribute__((format(printf, 3, 4))) void done(double flops, const char* label_fmt, ...) {
+        if (!a) return;
+        char label[320];
+        va_list ap;
+        va_start(ap, label_fmt);
+        vsnprintf(label, sizeof(label), label_fmt, ap);
+        va_end(ap);
+        (void)hipEventRecord(b, e.cur);
+        e.conv_evs.push_back({a, b});
+        e.conv_ev_info.push_back({label, flops});
+        e.conv_flops_pending += flops;
+        a = b = nullptr;
+    }
+};
+
+// resnet.cpp: the ResNet trunk every model's backbone (and the C4 RoI head) is built from
+// Stem: d_images [N][H][W][3] fp32 -> padded 4-channel copy ("input4"; fp16: the zero-haloed "input4h") -> 7x7/2 conv `layer` + BN + ReLU ("stem") ->
+// 3x3/2 max-pool ("pool").  fp16: conv and pool as one launch where eng_stem_pool_f16 has the kernel ("stem" then never exists).
+int resnet_stem(Engine& e, const std::string& layer, const float* d_images, int N, int H, int W, Tensor* pool);
+// One stage of bottleneck blocks: block b's layers are <layers>.<b>.{conv1, conv2, conv3, downsample.0}.
+struct ResStage {
+    std::string layers;          // layer-name prefix
+    std::string bufs;            // buffer-name prefix of the per-block buffers <bufs>.<b>.{t1, t2, ds, out}: `layers`, unless one set of weights runs into two sets of buffers
+    int blocks = 0;
+    int stride = 1;              // of block 0
+    bool stride_in_1x1 = false;  // the stride sits on conv1 (maskrcnn-benchmark's STRIDE_IN_1X1) instead of on the 3x3 (torchvision, Yolact)
+    // full: the FPN backbones' form -- buffers by liveness under `stage`.{t1, t2, outA, outB, C} (unless "alias_buffers" is 0), block 0's projection
+    // grouped with conv1 (fp32) or on side stream 0, the fused fp16 bottleneck where it has a kernel, `conv_split_k` marks.  Otherwise the plain
+    // form: one launch per layer on the current stream, one buffer per layer.
+    bool full = false;
+    std::string stage;           // full: "res<l>"
+    bool proj_by_name = false;   // a block projects its shortcut where it has a downsample.0 (torchvision-form weights of any layout); otherwise block 0 does
+    hipEvent_t before_out = nullptr;  // the main stream waits on it before the launch that writes the stage's final output
+};
+int resnet_stage(Engine& e, const ResStage& s, const Tensor& in, Tensor* out);
 
 int yolact_forward(Engine& e, const float* d_images, int N);
 int yolact_postprocess(Engine& e, int h, int w, const int32_t* h_image_hw = nullptr);

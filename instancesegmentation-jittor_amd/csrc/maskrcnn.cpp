@@ -45,12 +45,6 @@ static int maskrcnn_nms_flags(Engine& e) {
            ((int)e.param("nms_index_order", 0) ? ISEGMI_NMS_INDEX_ORDER : 0);
 }
 
-#define TRY(x)               \
-    do {                     \
-        int _rc = (x);       \
-        if (_rc) return _rc; \
-    } while (0)
-
 static int need_tensor(Engine& e, const std::string& name, int64_t bytes, const RawBuf** out) {
     auto it = e.tensors.find(name);
     if (it == e.tensors.end()) { set_error("tensor not set: " + name); return ISEGMI_ERR_STATE; }
@@ -113,66 +107,21 @@ int maskrcnn_forward(Engine& e, const float* d_images, int N) {
     int* d_hw = (int*)e.last_hw_ptr;  // maskrcnn_set_image_hw
 
     const int dt = e.fp16 ? 1 : 0;  // storage type of everything after the stem
-    Tensor x4, s, x;
-    bool stem_fused = false;
-    if (dt) {  // fp16: images are rounded to fp16 into a zero-haloed 4-channel buffer the stem kernel reads without bounds tests
-        TRY(eng_act(e, "input4h", N, H + 6, (W + 7) & ~1, 4, &x4, 1));
-        TRY(pad_c3_to_f16_halo_launch(d_images, N, H, W, x4.d, st));
-        TRY(eng_input_consumed(e));
-        TRY(eng_stem_pool_f16(e, "backbone.body.stem.conv1", x4, H, W, "pool", &x, &stem_fused));   // conv + BN + ReLU + max-pool in one launch
-        if (!stem_fused) TRY(eng_conv_stem_f16(e, "backbone.body.stem.conv1", x4, H, W, "stem", &s));
-    } else {
-        TRY(eng_act(e, "input4", N, H, W, 4, &x4));
-        TRY(pad_c3_c4_launch(d_images, (int64_t)N * H * W, x4.d, st));
-        TRY(eng_input_consumed(e));
-        TRY(eng_conv(e, "backbone.body.stem.conv1", x4, 2, 3, 1, nullptr, "stem", &s));
-    }
-    if (!stem_fused) {
-        const int Ho = (s.H + 2 - 3) / 2 + 1, Wo = (s.W + 2 - 3) / 2 + 1;
-        TRY(eng_act(e, "pool", N, Ho, Wo, s.C, &x, dt));
-        if (dt) TRY(maxpool_to_f16_launch(s.d, 1, N, s.H, s.W, s.C, 3, 2, 1, x.d, st));
-        else TRY(maxpool_launch(s.d, N, s.H, s.W, s.C, 3, 2, 1, x.d, st));
-    }
+    Tensor x;
+    TRY(resnet_stem(e, "backbone.body.stem.conv1", d_images, N, H, W, &x));
     eng_mark(e, "stem");
     const int depth = (int)e.param("resnet_depth", 50);
     const int blocks[4] = {3, 4, depth == 101 ? 23 : 6, 3};
     Tensor C[4];
     for (int li = 0; li < 4; ++li) {
-        for (int b = 0; b < blocks[li]; ++b) {
-            const std::string nm = "backbone.body.layer" + std::to_string(li + 1) + "." + std::to_string(b);
-            const int sd = (b == 0 && li > 0) ? 2 : 1;
-            Tensor idt = x, t1, t2, y;
-            // Buffers by LIVENESS, not by layer (round 3): a stage owns one t1, one t2, two alternating block outputs and its final output
-            // C<l>.  Everything runs in order on the main stream (the shortcut of block 0 is joined before conv3), so a buffer's last reader
-            // is always enqueued before its next writer.  Besides the memory (R101 bs=8: 33 x 3 buffers -> 4 x 5), a dead activation is now
-            // overwritten while its lines still sit in the Infinity Cache instead of being written back to HBM behind the live traffic.
-            const bool alias = e.param("alias_buffers", 1.0f) != 0.0f;  // 0: one buffer per layer output (rounds 1-2; kept for A/B)
-            const std::string sg = alias ? "res" + std::to_string(li + 2) : nm;
-            const std::string out_name = !alias ? nm + ".out" : b == blocks[li] - 1 ? sg + ".C" : sg + (b & 1 ? ".outB" : ".outA");
-            bool fused = false;
-            // fp16: the identity blocks of res2 / res3 and res2's first block (projection included) are ONE launch each, t1 / t2 stay in LDS
-            if (b > 0 || sd == 1) TRY(eng_bottleneck_f16(e, nm, x, b == 0, out_name, &y, &fused));
-            if (!fused) {
-                const bool pair = b == 0 && !dt && e.param("conv_groups", 1.0f) != 0.0f && e.param("conv_tile", 0) == 0.0f;
-                if (pair) {  // fp32: the projection shortcut and conv1 read the same x: one grouped launch (round 5) instead of a side stream
-                    std::vector<ConvGroupItem> g(2);
-                    g[0].layer = nm + ".conv1"; g[0].in = x; g[0].stride = sd; g[0].act = 1; g[0].out_name = sg + ".t1"; g[0].out = &t1;
-                    g[1].layer = nm + ".downsample.0"; g[1].in = x; g[1].stride = sd; g[1].out_name = nm + ".ds"; g[1].out = &idt;
-                    TRY(eng_conv_group(e, g));
-                } else {
-                if (b == 0) {  // projection shortcut on a side stream, concurrent with conv1 -> conv2
-                    TRY(eng_fork(e, 0));
-                    SideScope sc(e, 0);
-                    TRY(eng_conv(e, nm + ".downsample.0", x, sd, 0, 0, nullptr, nm + ".ds", &idt));
-                }
-                TRY(eng_conv(e, nm + ".conv1", x, sd, 0, 1, nullptr, sg + ".t1", &t1, false, /*may_split=*/b > 0));  // STRIDE_IN_1X1
-                }
-                TRY(eng_conv(e, nm + ".conv2", t1, 1, 1, 1, nullptr, sg + ".t2", &t2, false, /*may_split=*/true));   // (`conv_split_k`: see eng_conv)
-                if (b == 0 && !pair) TRY(eng_join(e, 0));
-                TRY(eng_conv(e, nm + ".conv3", t2, 1, 0, 1, &idt, out_name, &y, false, /*may_split=*/true));
-            }
-            x = y;
-        }
+        ResStage rs;
+        rs.layers = rs.bufs = "backbone.body.layer" + std::to_string(li + 1);
+        rs.blocks = blocks[li];
+        rs.stride = li > 0 ? 2 : 1;
+        rs.stride_in_1x1 = true;
+        rs.full = true;
+        rs.stage = "res" + std::to_string(li + 2);
+        TRY(resnet_stage(e, rs, x, &x));
         C[li] = x;
         eng_mark(e, li == 0 ? "res2" : li == 1 ? "res3" : li == 2 ? "res4" : "res5");
     }
@@ -528,21 +477,15 @@ int maskrcnn_forward(Engine& e, const float* d_images, int N) {
 // box post-processing as in the FPN model -> the SAME extractor on the detections (SHARE_BOX_FEATURE_EXTRACTOR) ->
 // MaskRCNNC4Predictor: ConvTranspose 2x2/2 2048->256 + ReLU -> 1x1 -> 81 -> sigmoid, class-selected: 14x14 masks.
 // fp32 only; single stream (the RoI heads are ~1.5 TFLOP per image here and dominate).
+// (one set of weights, `prefix`, into the buffers of `tag`: the box and the mask branch each keep their own activations)
 static int res5_head(Engine& e, const std::string& prefix, const std::string& tag, const Tensor& in, Tensor* out) {
-    Tensor x = in;
-    for (int b = 0; b < 3; ++b) {
-        const std::string nm = prefix + "." + std::to_string(b);
-        const std::string bt = tag + "." + std::to_string(b);
-        const int sd = b == 0 ? 2 : 1;
-        Tensor idt = x, t1, t2, y;
-        if (b == 0) TRY(eng_conv(e, nm + ".downsample.0", x, sd, 0, 0, nullptr, bt + ".ds", &idt));
-        TRY(eng_conv(e, nm + ".conv1", x, sd, 0, 1, nullptr, bt + ".t1", &t1));  // STRIDE_IN_1X1
-        TRY(eng_conv(e, nm + ".conv2", t1, 1, 1, 1, nullptr, bt + ".t2", &t2));
-        TRY(eng_conv(e, nm + ".conv3", t2, 1, 0, 1, &idt, bt + ".out", &y));
-        x = y;
-    }
-    *out = x;
-    return ISEGMI_OK;
+    ResStage rs;
+    rs.layers = prefix;
+    rs.bufs = tag;
+    rs.blocks = 3;
+    rs.stride = 2;
+    rs.stride_in_1x1 = true;
+    return resnet_stage(e, rs, in, out);
 }
 
 static int maskrcnn_c4_forward(Engine& e, const float* d_images, int N) {
@@ -556,28 +499,17 @@ static int maskrcnn_c4_forward(Engine& e, const float* d_images, int N) {
     eng_mark(e, "start");
     void* p;
     int* d_hw = (int*)e.last_hw_ptr;  // maskrcnn_set_image_hw
-    Tensor x4, s, x;
-    TRY(eng_act(e, "input4", N, H, W, 4, &x4));
-    TRY(pad_c3_c4_launch(d_images, (int64_t)N * H * W, x4.d, st));
-    TRY(eng_input_consumed(e));
-    TRY(eng_conv(e, "backbone.body.stem.conv1", x4, 2, 3, 1, nullptr, "stem", &s));
-    {
-        const int Ho = (s.H + 2 - 3) / 2 + 1, Wo = (s.W + 2 - 3) / 2 + 1;
-        TRY(eng_act(e, "pool", N, Ho, Wo, s.C, &x));
-        TRY(maxpool_launch(s.d, N, s.H, s.W, s.C, 3, 2, 1, x.d, st));
-    }
+    Tensor x;
+    TRY(resnet_stem(e, "backbone.body.stem.conv1", d_images, N, H, W, &x));
     const int blocks[3] = {3, 4, 6};
-    for (int li = 0; li < 3; ++li)
-        for (int b = 0; b < blocks[li]; ++b) {
-            const std::string nm = "backbone.body.layer" + std::to_string(li + 1) + "." + std::to_string(b);
-            const int sd = (b == 0 && li > 0) ? 2 : 1;
-            Tensor idt = x, t1, t2, y;
-            if (b == 0) TRY(eng_conv(e, nm + ".downsample.0", x, sd, 0, 0, nullptr, nm + ".ds", &idt));
-            TRY(eng_conv(e, nm + ".conv1", x, sd, 0, 1, nullptr, nm + ".t1", &t1));
-            TRY(eng_conv(e, nm + ".conv2", t1, 1, 1, 1, nullptr, nm + ".t2", &t2));
-            TRY(eng_conv(e, nm + ".conv3", t2, 1, 0, 1, &idt, nm + ".out", &y));
-            x = y;
-        }
+    for (int li = 0; li < 3; ++li) {   // the plain form: one stream here, one buffer per layer
+        ResStage rs;
+        rs.layers = rs.bufs = "backbone.body.layer" + std::to_string(li + 1);
+        rs.blocks = blocks[li];
+        rs.stride = li > 0 ? 2 : 1;
+        rs.stride_in_1x1 = true;
+        TRY(resnet_stage(e, rs, x, &x));
+    }
     Tensor C4 = x;  // [N, H/16, W/16, 1024]
     {   // expose under a stable name for tests
         Tensor alias;

@@ -15,12 +15,6 @@
 
 namespace isegmi {
 
-#define TRY(x)               \
-    do {                     \
-        int _rc = (x);       \
-        if (_rc) return _rc; \
-    } while (0)
-
 static const float kP2sMean[3] = {0.485f, 0.456f, 0.406f};
 static const float kP2sStd[3] = {0.229f, 0.224f, 0.225f};
 
@@ -28,22 +22,19 @@ int pose2seg_det_cap(Engine& e) { return (int)e.param("max_instances", 32.0f); }
 
 static int p2s_blocks(Engine& e, const std::string& prefix) {
     int n = 0;
-    while (e.convs.count(prefix + std::to_string(n) + ".conv1")) ++n;
+    while (e.convs.count(prefix + "." + std::to_string(n) + ".conv1")) ++n;
     return n;
 }
 
-// torchvision bottleneck: relu(bn3(conv3(relu(bn2(conv2(relu(bn1(conv1(x)))))))) + shortcut), stride on conv2.  x is taken by value: callers
-// pass their running tensor as both x and y, and y is rewritten before conv3 reads the identity shortcut.
-static int p2s_bottleneck(Engine& e, const std::string& nm, const Tensor x, int stride, Tensor* y) {
-    Tensor t1, t2, sc;
-    TRY(eng_conv(e, nm + ".conv1", x, 1, 0, 1, nullptr, nm + ".t1", &t1));
-    TRY(eng_conv(e, nm + ".conv2", t1, stride, 1, 1, nullptr, nm + ".t2", &t2));
-    const Tensor* res = &x;
-    if (e.convs.count(nm + ".downsample.0")) {
-        TRY(eng_conv(e, nm + ".downsample.0", x, stride, 0, 0, nullptr, nm + ".sc", &sc));
-        res = &sc;
-    }
-    return eng_conv(e, nm + ".conv3", t2, 1, 0, 1, res, nm + ".out", y);
+// blocks <prefix>.0 .. of torchvision bottlenecks (relu(bn3(conv3(relu(bn2(conv2(relu(bn1(conv1(x)))))))) + shortcut), stride on conv2), as many as the
+// weights hold; a block projects its shortcut where it has a downsample.0
+static int p2s_res_stage(Engine& e, const std::string& prefix, int stride, Tensor* x) {
+    ResStage rs;
+    rs.layers = rs.bufs = prefix;
+    rs.blocks = p2s_blocks(e, prefix);
+    rs.stride = stride;
+    rs.proj_by_name = true;
+    return resnet_stage(e, rs, *x, x);
 }
 
 // a host array of any size through the pinned ring, slot by slot
@@ -99,10 +90,9 @@ static int pose2seg_forward(Engine& e, const uint8_t* d_u8, const int32_t* h_hw,
     TRY(maxpool_launch(s.d, N, s.H, s.W, s.C, 3, 2, 1, x.d, e.stream));
     Tensor feats[4];
     for (int l = 0; l < 4; ++l) {
-        const std::string pre = "backbone.layers." + std::to_string(l) + ".";
-        const int nb = p2s_blocks(e, pre);
-        if (nb == 0) { set_error("pose2seg: no blocks in " + pre); return ISEGMI_ERR_STATE; }
-        for (int b = 0; b < nb; ++b) TRY(p2s_bottleneck(e, pre + std::to_string(b), x, (l > 0 && b == 0) ? 2 : 1, &x));
+        const std::string pre = "backbone.layers." + std::to_string(l);
+        if (p2s_blocks(e, pre) == 0) { set_error("pose2seg: no blocks in " + pre + "."); return ISEGMI_ERR_STATE; }
+        TRY(p2s_res_stage(e, pre, l > 0 ? 2 : 1, &x));
         feats[l] = x;
     }
     // FPN top-down to P2
@@ -154,11 +144,11 @@ static int pose2seg_forward(Engine& e, const uint8_t* d_u8, const int32_t* h_hw,
         }
         Tensor t, up;
         TRY(eng_conv(e, "segnet.conv1", roi, 2, 3, 1, nullptr, "p2s.seg.c1", &t));
-        for (int b = 0, nb = p2s_blocks(e, "segnet.stage1."); b < nb; ++b) TRY(p2s_bottleneck(e, "segnet.stage1." + std::to_string(b), t, 1, &t));
+        TRY(p2s_res_stage(e, "segnet.stage1", 1, &t));
         TRY(eng_act(e, "p2s.seg.up", R, 2 * t.H, 2 * t.W, t.C, &up));
         TRY(resize_bilinear_launch(t.d, R, t.H, t.W, t.C, up.H, up.W, nullptr, 0, up.d, e.stream));
         t = up;
-        for (int b = 0, nb = p2s_blocks(e, "segnet.stage2."); b < nb; ++b) TRY(p2s_bottleneck(e, "segnet.stage2." + std::to_string(b), t, 1, &t));
+        TRY(p2s_res_stage(e, "segnet.stage2", 1, &t));
         if (t.H != 64 || t.W != 64) { set_error("pose2seg: SegModule output is not 64 x 64"); return ISEGMI_ERR_STATE; }
         TRY(eng_conv(e, "segnet.conv_out", t, 1, 0, 0, nullptr, "p2s.logits", &logits));
     }

@@ -1,0 +1,98 @@
+// resnet.cpp -- the ResNet trunk, once: the stem and one stage of bottleneck blocks, as the Yolact and Mask R-CNN backbones, the C4 RoI head
+// and Pose2Seg (backbone and SegModule) run them.  What differs between those is data (ResStage in engine.h), not code.
+#include "engine.h"
+
+namespace isegmi {
+
+int resnet_stem(Engine& e, const std::string& layer, const float* d_images, int N, int H, int W, Tensor* pool) {
+    const int dt = e.fp16 ? 1 : 0;
+    Tensor x4, s;
+    bool stem_fused = false;
+    if (dt) {  // fp16: images are rounded to fp16 into a zero-haloed 4-channel buffer the stem kernel reads without bounds tests
+        TRY(eng_act(e, "input4h", N, H + 6, (W + 7) & ~1, 4, &x4, 1));
+        TRY(pad_c3_to_f16_halo_launch(d_images, N, H, W, x4.d, e.cur));
+        TRY(eng_input_consumed(e));
+        TRY(eng_stem_pool_f16(e, layer, x4, H, W, "pool", pool, &stem_fused));   // conv + BN + ReLU + max-pool in one launch
+        if (!stem_fused) TRY(eng_conv_stem_f16(e, layer, x4, H, W, "stem", &s));
+    } else {
+        TRY(eng_act(e, "input4", N, H, W, 4, &x4));
+        TRY(pad_c3_c4_launch(d_images, (int64_t)N * H * W, x4.d, e.cur));
+        TRY(eng_input_consumed(e));
+        TRY(eng_conv(e, layer, x4, 2, 3, 1, nullptr, "stem", &s));
+    }
+    if (!stem_fused) {
+        const int Ho = (s.H + 2 - 3) / 2 + 1, Wo = (s.W + 2 - 3) / 2 + 1;
+        TRY(eng_act(e, "pool", N, Ho, Wo, s.C, pool, dt));
+        if (dt) TRY(maxpool_to_f16_launch(s.d, 1, N, s.H, s.W, s.C, 3, 2, 1, pool->d, e.cur));
+        else TRY(maxpool_launch(s.d, N, s.H, s.W, s.C, 3, 2, 1, pool->d, e.cur));
+    }
+    return ISEGMI_OK;
+}
+
+// conv2 of a block as DCNv2 (YOLACT++ backbones): offsets + mask logits from a plain 3x3 -> the nine taps sampled into columns ->
+// the deformable conv proper as a 1x1 over 9*C channels (weights handed over in KRSC order, bias folded into BN)
+static int dcn_conv2(Engine& e, const std::string& nm, const std::string& blk, const Tensor& t1, int stride, const std::string& out_name, Tensor* t2) {
+    if (t1.dt) { set_error("the DCNv2 backbones run in fp32 only"); return ISEGMI_ERR_STATE; }
+    Tensor om, col;
+    TRY(eng_conv(e, nm + ".conv2.conv_offset_mask", t1, stride, 1, 0, nullptr, blk + ".om", &om));
+    TRY(eng_act(e, blk + ".col", t1.N, om.H, om.W, 9 * t1.C, &col));
+    TRY(deform_im2col_launch((const float*)t1.d, t1.N, t1.H, t1.W, t1.C, (const float*)om.d, 3, 3, stride, 1, 1, (float*)col.d, e.cur));
+    return eng_conv(e, nm + ".conv2", col, 1, 0, 1, nullptr, out_name, t2);
+}
+
+int resnet_stage(Engine& e, const ResStage& s, const Tensor& in, Tensor* out) {
+    // Buffers by LIVENESS, not by layer (round 3): a full stage owns one t1, one t2, two alternating block outputs and its final output
+    // <stage>.C.  Everything runs in order on the main stream (the shortcut of block 0 is joined before conv3), so a buffer's last reader
+    // is always enqueued before its next writer.  Besides the memory (R101 bs=8: 33 x 3 buffers -> 4 x 5), a dead activation is now
+    // overwritten while its lines still sit in the Infinity Cache instead of being written back to HBM behind the live traffic.
+    // (The stage's final output is on its own: Yolact's C3-C5 are read by the lateral convs of the pipelined heads phase, and `before_out` guards
+    // exactly those.)
+    const bool alias = s.full && e.param("alias_buffers", 1.0f) != 0.0f;  // 0: one buffer per layer output (rounds 1-2; kept for A/B)
+    const bool groups = e.param("conv_groups", 1.0f) != 0.0f && e.param("conv_tile", 0) == 0.0f;
+    Tensor x = in;
+    for (int b = 0; b < s.blocks; ++b) {
+        const std::string nm = s.layers + "." + std::to_string(b), blk = s.bufs + "." + std::to_string(b);
+        const std::string sg = alias ? s.stage : blk;
+        const std::string out_name = !alias ? blk + ".out" : b == s.blocks - 1 ? sg + ".C" : sg + (b & 1 ? ".outB" : ".outA");
+        const int st = b == 0 ? s.stride : 1, st1 = s.stride_in_1x1 ? st : 1, st2 = s.stride_in_1x1 ? 1 : st;
+        const bool proj = s.proj_by_name ? e.convs.count(nm + ".downsample.0") != 0 : b == 0;
+        // the previous user of the stage's output buffer must have read it: one wait, ahead of whichever launch writes it (they are the first
+        // thing of the phase that reads it, so this wait practically never blocks)
+        bool fence = b == s.blocks - 1 && s.before_out != nullptr;
+        Tensor idt = x, t1, t2, y;
+        if (s.full && x.dt == 1 && (b > 0 || st == 1)) {
+            // fp16: the identity blocks of res2 / res3 and res2's first block (projection included) are ONE launch each, t1 / t2 stay in LDS
+            // (csrc/bottleneck_f16.hip); the alternating outA / outB are what keeps that launch from running in place
+            if (fence) { HIP_TRY(hipStreamWaitEvent(e.stream, s.before_out, 0)); fence = false; }
+            bool fused = false;
+            TRY(eng_bottleneck_f16(e, nm, x, b == 0, out_name, &y, &fused));
+            if (fused) { x = y; continue; }
+        }
+        const bool pair = s.full && proj && x.dt == 0 && groups;
+        if (pair) {  // fp32: the projection shortcut and conv1 read the same x: one grouped launch (round 5) instead of a side stream
+            std::vector<ConvGroupItem> g(2);
+            g[0].layer = nm + ".conv1"; g[0].in = x; g[0].stride = st1; g[0].act = 1; g[0].out_name = sg + ".t1"; g[0].out = &t1;
+            g[1].layer = nm + ".downsample.0"; g[1].in = x; g[1].stride = st; g[1].out_name = blk + ".ds"; g[1].out = &idt;
+            TRY(eng_conv_group(e, g));
+        } else {
+            if (proj && s.full) {  // the projection shortcut is independent of conv1 -> conv2: side stream
+                TRY(eng_fork(e, 0));
+                SideScope sc(e, 0);
+                TRY(eng_conv(e, nm + ".downsample.0", x, st, 0, 0, nullptr, blk + ".ds", &idt));
+            } else if (proj) {
+                TRY(eng_conv(e, nm + ".downsample.0", x, st, 0, 0, nullptr, blk + ".ds", &idt));
+            }
+            TRY(eng_conv(e, nm + ".conv1", x, st1, 0, 1, nullptr, sg + ".t1", &t1, false, /*may_split=*/s.full && b > 0));   // (`conv_split_k`: see eng_conv)
+        }
+        if (e.convs.count(nm + ".conv2.conv_offset_mask")) TRY(dcn_conv2(e, nm, blk, t1, st2, sg + ".t2", &t2));
+        else TRY(eng_conv(e, nm + ".conv2", t1, st2, 1, 1, nullptr, sg + ".t2", &t2, false, /*may_split=*/s.full));
+        if (proj && s.full && !pair) TRY(eng_join(e, 0));
+        if (fence) HIP_TRY(hipStreamWaitEvent(e.stream, s.before_out, 0));
+        TRY(eng_conv(e, nm + ".conv3", t2, 1, 0, 1, &idt, out_name, &y, false, /*may_split=*/s.full));
+        x = y;
+    }
+    *out = x;
+    return ISEGMI_OK;
+}
+
+}  // namespace isegmi

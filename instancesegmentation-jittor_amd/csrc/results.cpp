@@ -20,12 +20,6 @@
 namespace isegmi {
 int rle_encode_launch(const isegmi_rle_args* a, hipStream_t st);
 
-#define TRY(x)               \
-    do {                     \
-        int _rc = (x);       \
-        if (_rc) return _rc; \
-    } while (0)
-
 int maskrcnn_det_cap(Engine& e);
 int pose2seg_det_cap(Engine& e);
 // Pose2Seg (kind 3) takes the Mask R-CNN record form (f32 boxes, i32 labels) with K = its max_instances

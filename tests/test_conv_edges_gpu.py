@@ -297,7 +297,7 @@ def test_f16_strided_mask_head_scatter(ffi, tile, f32):
 @pytest.mark.parametrize("tile", STRIDED_TILES + [30, 40])
 @pytest.mark.parametrize("Cout", [3, 12, 15, 324])
 def test_f16_strided_head_concatenation(ffi, Cout, tile, f32):
-    """A level's slice of the concatenated [N][sum P][C] prediction buffer (engine.cpp: fp32 heads, Cout % 8 != 0 on the per-element epilogue)."""
+    """A level's slice of the concatenated [N][sum P][C] prediction buffer (yolact.cpp: fp32 heads, Cout % 8 != 0 on the per-element epilogue)."""
     case = (2, 9, 10, 64, Cout, 3, 1, 1)
     _strided(ffi, case, tile, f32, 90, 500 * Cout, Cout, 37 * Cout, 2 * 500 * Cout, act=0)
 

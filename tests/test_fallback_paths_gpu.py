@@ -1,7 +1,8 @@
 """The launch forms the defaults no longer take: per-layer launches instead of grouped convolutions (`conv_groups` 0), the per-level RPN
 selection on side streams instead of the (level, image)-batched one (`rpn_select_groups` 0; also what PRE_NMS_TOP_N_TEST outside 257..1024 falls back
 to), the two forced groupings (1 / 2), and the stream joins that go with them.  They stay selectable for A/B runs and for configurations the grouped
-forms do not cover, so they are tested: every tensor the heads produce must be BIT-IDENTICAL to the default path's, fp32 and fp16, one image and two."""
+forms do not cover, so they are tested: every tensor the heads produce must be BIT-IDENTICAL to the default path's, fp32 and fp16, one image and two.
+So does the ResNet trunk's buffer naming (`alias_buffers` 0: one buffer per layer output instead of the liveness-aliased res<l>.* set)."""
 import dataclasses
 
 import numpy as np
@@ -69,6 +70,8 @@ def test_maskrcnn_fallback_launch_forms_are_bit_identical_to_the_default(ffi, sd
                 dict(rpn_select_groups=0, rpn_select_on_tail=1), dict(multi_stream=0), dict(box_nms_chip_wide=0)]
     if not fp16:   # the fp16 engine has no grouped convolutions to switch off
         variants += [dict(conv_groups=0), dict(conv_groups=0, rpn_select_groups=0), dict(conv_groups=0, rpn_select_groups=2), dict(conv_groups=1, rpn_select_groups=0)]
+    if N == 2:   # fp16: the fused bottleneck writes its output buffer directly; res<l>.outA / .outB alternating is what keeps it from running in place
+        variants += [dict(alias_buffers=0)]
     for v in variants:
         try:
             _same(_maskrcnn_run(sd, x, hw, fp16, v), base)
@@ -131,6 +134,8 @@ def test_yolact_fallback_launch_forms_are_bit_identical_to_the_default(ffi, fp16
     variants = [dict(multi_stream=0)]
     if not fp16:
         variants += [dict(conv_groups=0), dict(conv_groups=0, multi_stream=0)]
+    if N == 2:
+        variants += [dict(alias_buffers=0)]
     for v in variants:
         try:
             same(run(v), base)
