@@ -175,6 +175,15 @@ int isegmi_op_deform_im2col(const float* d_x, int N, int H, int W, int C, const 
 int isegmi_op_upsample_nearest2x_add(const float* d_coarse, int N, int Hc, int Wc, int C,
                                      const float* d_lateral, int H, int W, float* d_out,
                                      void* stream);
+/* GroupNorm over NHWC fp32 ([UPSTREAM-RECALL] maskrcnn-benchmark group_norm(): torch.nn.GroupNorm(groups, C, eps, affine=True)):
+ *   out = (x - mu) * rsqrt(var + eps) * gamma + beta [+ residual] [ReLU], mu / biased var over (H, W, C / groups) of one image (or RoI) and one group.
+ * N images or RoI slabs (N == 0 launches nothing).  C % 4 == 0, groups divides C, and a 64-channel tile holds whole groups (C % 64 == 0 and
+ * 64 % (C / groups) == 0, or C < 64).  d_residual (x's shape) is optional; d_out may be d_x (in place).  Planes of H * W <= 196 run as one launch
+ * with the slab in registers; larger planes run statistics + apply passes and need d_workspace of isegmi_op_group_norm_workspace_bytes() bytes
+ * (0 for the small planes, where d_workspace may be NULL).  No atomics, fixed summation order (csrc/groupnorm.hip): same input, same bits. */
+int64_t isegmi_op_group_norm_workspace_bytes(int64_t N, int H, int W, int C, int groups);
+int isegmi_op_group_norm(const float* d_x, int64_t N, int H, int W, int C, int groups, const float* d_gamma, const float* d_beta, float eps,
+                         const float* d_residual, int relu, float* d_out, void* d_workspace, int64_t workspace_bytes, void* stream);
 /* NHWC3 -> NHWC4 zero pad (stem input) */
 int isegmi_op_pad_c3_to_c4(const float* d_in, int64_t npix, float* d_out, void* stream);
 /* fn: 0 exp 1 sigmoid 2 tanh 3 log2 -- exposes the deterministic math for parity tests */

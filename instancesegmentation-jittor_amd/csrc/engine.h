@@ -280,6 +280,12 @@ struct ResStage {
     hipEvent_t before_out = nullptr;  // the main stream waits on it before the launch that writes the stage's final output
 };
 int resnet_stage(Engine& e, const ResStage& s, const Tensor& in, Tensor* out);
+// GroupNorm layers.  The norm is data: a convolution `layer` whose GroupNorm affine was set as the tensors <layer>.gn.weight / .gn.bias
+// (the host sets them where the state dict's norm has a weight but no running statistics) is followed by eng_gn as its own launch, in place on the
+// convolution's output; the convolution itself then runs with scale 1, shift 0 and no activation.  Groups per layer: C / "gn_dim_per_gp" where that
+// parameter is positive, else "gn_num_groups" (32); eps "gn_epsilon" (1e-5).  fp32 only.
+bool eng_has_gn(Engine& e, const std::string& layer);
+int eng_gn(Engine& e, const std::string& layer, Tensor* x, const Tensor* residual, bool relu);
 
 int yolact_forward(Engine& e, const float* d_images, int N);
 int yolact_postprocess(Engine& e, int h, int w, const int32_t* h_image_hw = nullptr);
@@ -316,6 +322,10 @@ int roi_prep_launch(const float* rois, const int* counts, int N, int K, const in
 int mask_logits_select_f16_launch(const void* feat, int R, int HW, int C, const float* w, const float* b, const int* labels, float* out,
                                   hipStream_t st);
 int maxpool_launch(const float* in, int N, int H, int W, int C, int k, int s, int p, float* out, hipStream_t st);
+int64_t groupnorm_workspace_bytes(int64_t N, int H, int W, int C, int groups);
+bool groupnorm_is_slab(int H, int W);
+int groupnorm_launch(const float* x, int64_t N, int H, int W, int C, int groups, const float* gamma, const float* beta, float eps, const float* residual,
+                     int relu, float* out, void* ws, int64_t ws_bytes, hipStream_t st);
 int resize_bilinear_launch(const float* in, int N, int H, int W, int C, int Ho, int Wo, const float* add, int relu, float* out,
                            hipStream_t st);
 int nearest2x_add_launch(const float* coarse, int N, int Hc, int Wc, int C, const float* lat, int H, int W, float* out,

@@ -71,6 +71,11 @@ int maskrcnn_set_image_hw(Engine& e, const int32_t* h_image_hw, int N) {
 
 static int maskrcnn_c4_forward(Engine& e, const float* d_images, int N);
 
+// the GroupNorm behind a convolution, where the layer has one (gn_baselines: MODEL.FPN.USE_GN, ROI_BOX_HEAD.USE_GN, ROI_MASK_HEAD.USE_GN)
+static int gn_after(Engine& e, const std::string& layer, Tensor* x, bool relu) {
+    return eng_has_gn(e, layer) ? eng_gn(e, layer, x, nullptr, relu) : ISEGMI_OK;
+}
+
 // rows of every per-image detection buffer: DETECTIONS_PER_IMG, or more when "detections_cap" is set -- upstream's kth-value rule keeps every
 // detection whose score ties with the 100th, so an image can return more than DETECTIONS_PER_IMG; the extra rows hold those ties
 int maskrcnn_det_cap(Engine& e) {
@@ -118,7 +123,7 @@ int maskrcnn_forward(Engine& e, const float* d_images, int N) {
         rs.layers = rs.bufs = "backbone.body.layer" + std::to_string(li + 1);
         rs.blocks = blocks[li];
         rs.stride = li > 0 ? 2 : 1;
-        rs.stride_in_1x1 = true;
+        rs.stride_in_1x1 = e.param("stride_in_1x1", 1.0f) != 0.0f;   // MODEL.RESNETS.STRIDE_IN_1X1 (False in the GroupNorm yaml)
         rs.full = true;
         rs.stage = "res" + std::to_string(li + 2);
         TRY(resnet_stage(e, rs, x, &x));
@@ -142,12 +147,14 @@ int maskrcnn_forward(Engine& e, const float* d_images, int N) {
         g[2].layer = "backbone.fpn.fpn_inner3"; g[2].in = C[2]; g[2].out_name = "fpn.lat3"; g[2].out = &lats[2];
         g[3].layer = "backbone.fpn.fpn_inner4"; g[3].in = C[3]; g[3].out_name = "fpn.last4"; g[3].out = &last[3];
         TRY(eng_conv_group(e, g));
+        for (int l = 0; l < 4; ++l) TRY(gn_after(e, g[l].layer, l < 3 ? &lats[l] : &last[3], false));   // the top-down add consumes the normalised lateral
         for (int l = 2; l >= 0; --l) {
             TRY(eng_act(e, "fpn.last" + std::to_string(l + 1), N, lats[l].H, lats[l].W, lats[l].C, &last[l], 0));
             TRY(nearest2x_add_launch(last[l + 1].d, N, last[l + 1].H, last[l + 1].W, last[l + 1].C, lats[l].d, lats[l].H, lats[l].W, last[l].d, st));
         }
     } else {
     TRY(eng_conv(e, "backbone.fpn.fpn_inner4", C[3], 1, 0, 0, nullptr, "fpn.last4", &last[3]));
+    TRY(gn_after(e, "backbone.fpn.fpn_inner4", &last[3], false));
     for (int l = 2; l >= 0; --l) {
         const std::string ls = std::to_string(l + 1);
         if (dt) {  // fp16: the merge with the coarser level in the lateral conv's own epilogue (one launch, the lateral tensor never exists)
@@ -156,6 +163,7 @@ int maskrcnn_forward(Engine& e, const float* d_images, int N) {
             if (merged) continue;
         }
         TRY(eng_conv(e, "backbone.fpn.fpn_inner" + ls, C[l], 1, 0, 0, nullptr, "fpn.lat" + ls, &lat));
+        TRY(gn_after(e, "backbone.fpn.fpn_inner" + ls, &lat, false));
         TRY(eng_act(e, "fpn.last" + ls, N, lat.H, lat.W, lat.C, &last[l], dt));
         if (dt) TRY(nearest2x_add_f16_launch(last[l + 1].d, N, last[l + 1].H, last[l + 1].W, last[l + 1].C, lat.d, lat.H, lat.W, last[l].d, st));
         else TRY(nearest2x_add_launch(last[l + 1].d, N, last[l + 1].H, last[l + 1].W, last[l + 1].C, lat.d, lat.H, lat.W, last[l].d, st));
@@ -292,6 +300,7 @@ int maskrcnn_forward(Engine& e, const float* d_images, int N) {
             g[l].layer = "backbone.fpn.fpn_layer" + std::to_string(l + 1); g[l].in = last[l]; g[l].pad = 1; g[l].out_name = "P" + std::to_string(l + 2); g[l].out = &P[l];
         }
         TRY(eng_conv_group(e, g));
+        for (int l = 0; l < 4; ++l) TRY(gn_after(e, g[l].layer, &P[l], false));
         const int Ho = (P[3].H - 1) / 2 + 1, Wo = (P[3].W - 1) / 2 + 1;
         TRY(eng_act(e, "P6", N, Ho, Wo, P[3].C, &P[4], 0));
         TRY(maxpool_launch(P[3].d, N, P[3].H, P[3].W, P[3].C, 1, 2, 0, P[4].d, st));
@@ -312,6 +321,7 @@ int maskrcnn_forward(Engine& e, const float* d_images, int N) {
     } else {
     for (int l = 0; l < 4; ++l) {
         TRY(eng_conv(e, "backbone.fpn.fpn_layer" + std::to_string(l + 1), last[l], 1, 1, 0, nullptr, "P" + std::to_string(l + 2), &P[l]));
+        TRY(gn_after(e, "backbone.fpn.fpn_layer" + std::to_string(l + 1), &P[l], false));
         TRY(rpn_level(l));
     }
     {
@@ -383,8 +393,22 @@ int maskrcnn_forward(Engine& e, const float* d_images, int N) {
         if (dt) TRY(roi_align_f16_launch((const void* const*)feats, Hs, Ws, scales, 4, props, prop_cnt, N, R, 256, 7, 7, 2, 2, roi7.d, st, order, tab, roi_aligned));
         else TRY(roi_align_launch(feats, Hs, Ws, scales, 4, props, prop_cnt, N, R, 256, 7, 7, 2, 2, -1, roi7.d, nullptr, st, order, tab, roi_aligned));
     }
+    if (e.convs.count("roi_heads.box.feature_extractor.xconvs.0")) {
+        // FPNXconv1fcFeatureExtractor (gn_baselines): NUM_STACKED_CONVS x [3x3 conv (no bias) -> GN -> ReLU] on the 7x7 RoI features, then ReLU(fc6); no fc7
+        Tensor xc = roi7;
+        for (int i = 0; e.convs.count("roi_heads.box.feature_extractor.xconvs." + std::to_string(i)); ++i) {
+            const std::string nm = "roi_heads.box.feature_extractor.xconvs." + std::to_string(i);
+            const bool gn = eng_has_gn(e, nm);
+            Tensor o;
+            TRY(eng_conv(e, nm, xc, 1, 1, gn ? 0 : 1, nullptr, "box.xconv" + std::to_string(i), &o));
+            TRY(gn_after(e, nm, &o, true));
+            xc = o;
+        }
+        TRY(eng_conv(e, "roi_heads.box.feature_extractor.fc6", xc, 1, 0, 1, nullptr, "box.fc6", &f7));
+    } else {
     TRY(eng_conv(e, "roi_heads.box.feature_extractor.fc6", roi7, 1, 0, 1, nullptr, "box.fc6", &f6));
     TRY(eng_conv(e, "roi_heads.box.feature_extractor.fc7", f6, 1, 0, 1, nullptr, "box.fc7", &f7));
+    }
     TRY(eng_conv(e, "roi_heads.box.predictor.cls_bbox", f7, 1, 0, 0, nullptr, "box.cls_bbox", &cb, /*out_f32=*/true));
     const int ncls = 81, dpi = (int)e.param("detections_per_img", 100), cap = maskrcnn_det_cap(e);
     if (cb.C != ncls * 5) { set_error("cls_bbox layer must have 81+324 outputs"); return ISEGMI_ERR_STATE; }
@@ -436,7 +460,10 @@ int maskrcnn_forward(Engine& e, const float* d_images, int N) {
     }
     for (int i = 1; i <= 4; ++i) {
         Tensor o;
-        TRY(eng_conv(e, "roi_heads.mask.feature_extractor.mask_fcn" + std::to_string(i), m, 1, 1, 1, nullptr, "mask.fcn" + std::to_string(i), &o));
+        const std::string nm = "roi_heads.mask.feature_extractor.mask_fcn" + std::to_string(i);
+        const bool gn = eng_has_gn(e, nm);
+        TRY(eng_conv(e, nm, m, 1, 1, gn ? 0 : 1, nullptr, "mask.fcn" + std::to_string(i), &o));
+        TRY(gn_after(e, nm, &o, true));
         m = o;
     }
     Tensor up;

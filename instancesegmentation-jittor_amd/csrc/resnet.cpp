@@ -4,8 +4,40 @@
 
 namespace isegmi {
 
+bool eng_has_gn(Engine& e, const std::string& layer) { return e.tensors.count(layer + ".gn.weight") != 0; }
+
+int eng_gn(Engine& e, const std::string& layer, Tensor* x, const Tensor* residual, bool relu) {
+    if (e.fp16 || x->dt || (residual && residual->dt)) { set_error("GroupNorm layers run in fp32 only (" + layer + ")"); return ISEGMI_ERR_STATE; }
+    auto wi = e.tensors.find(layer + ".gn.weight"), bi = e.tensors.find(layer + ".gn.bias");
+    if (wi == e.tensors.end() || bi == e.tensors.end()) { set_error("GroupNorm affine not set: " + layer + ".gn.weight / .gn.bias"); return ISEGMI_ERR_STATE; }
+    if (wi->second.bytes != (int64_t)x->C * 4 || bi->second.bytes != (int64_t)x->C * 4) { set_error("GroupNorm affine of " + layer + " has the wrong size"); return ISEGMI_ERR_STATE; }
+    const int per = (int)e.param("gn_dim_per_gp", -1.0f);
+    const int groups = per > 0 ? x->C / per : (int)e.param("gn_num_groups", 32.0f);
+    if (groups <= 0 || x->C % groups || (per > 0 && x->C % per)) { set_error("GroupNorm of " + layer + ": the groups do not divide its channels"); return ISEGMI_ERR_ARG; }
+    if (residual && (residual->N != x->N || residual->H != x->H || residual->W != x->W || residual->C != x->C)) { set_error("GroupNorm of " + layer + ": residual shape"); return ISEGMI_ERR_ARG; }
+    void* ws = nullptr;
+    const int64_t ws_bytes = groupnorm_workspace_bytes(x->N, x->H, x->W, x->C, groups);
+    if (ws_bytes) TRY(eng_buf(e, "gn.ws:" + layer, ws_bytes, &ws, 2));   // one per layer: GroupNorm launches of independent branches run on different streams
+    // algorithmic bytes: x once (slabs) or twice (statistics pass + apply pass), the residual once, y once
+    OpScope op(e, e.cur, groupnorm_is_slab(x->H, x->W) ? "group_norm (slab: one pass)" : "group_norm (plane: statistics + apply)",
+               (double)x->numel() * 4 * ((groupnorm_is_slab(x->H, x->W) ? 2 : 3) + (residual ? 1 : 0)));
+    return groupnorm_launch(x->d, x->N, x->H, x->W, x->C, groups, (const float*)wi->second.d, (const float*)bi->second.d, e.param("gn_epsilon", 1e-5f),
+                            residual ? residual->d : nullptr, relu ? 1 : 0, x->d, ws, ws_bytes, e.cur);
+}
+
 int resnet_stem(Engine& e, const std::string& layer, const float* d_images, int N, int H, int W, Tensor* pool) {
     const int dt = e.fp16 ? 1 : 0;
+    if (eng_has_gn(e, layer)) {   // StemWithGN: conv -> GN -> ReLU -> max-pool
+        Tensor x4, s;
+        if (dt) { set_error("GroupNorm layers run in fp32 only (" + layer + ")"); return ISEGMI_ERR_STATE; }
+        TRY(eng_act(e, "input4", N, H, W, 4, &x4));
+        TRY(pad_c3_c4_launch(d_images, (int64_t)N * H * W, x4.d, e.cur));
+        TRY(eng_input_consumed(e));
+        TRY(eng_conv(e, layer, x4, 2, 3, 0, nullptr, "stem", &s));
+        TRY(eng_gn(e, layer, &s, nullptr, true));
+        TRY(eng_act(e, "pool", N, (s.H + 2 - 3) / 2 + 1, (s.W + 2 - 3) / 2 + 1, s.C, pool, 0));
+        return maxpool_launch(s.d, N, s.H, s.W, s.C, 3, 2, 1, pool->d, e.cur);
+    }
     Tensor x4, s;
     bool stem_fused = false;
     if (dt) {  // fp16: images are rounded to fp16 into a zero-haloed 4-channel buffer the stem kernel reads without bounds tests
@@ -56,6 +88,10 @@ int resnet_stage(Engine& e, const ResStage& s, const Tensor& in, Tensor* out) {
         const std::string out_name = !alias ? blk + ".out" : b == s.blocks - 1 ? sg + ".C" : sg + (b & 1 ? ".outB" : ".outA");
         const int st = b == 0 ? s.stride : 1, st1 = s.stride_in_1x1 ? st : 1, st2 = s.stride_in_1x1 ? 1 : st;
         const bool proj = s.proj_by_name ? e.convs.count(nm + ".downsample.0") != 0 : b == 0;
+        // BottleneckWithGN: conv1-GN-ReLU, conv2-GN-ReLU, conv3-GN + identity, ReLU (the projection is followed by its own GN).  Each convolution runs
+        // bare (no activation, no residual); the GroupNorm launch behind it carries the ReLU, and conv3's the residual add too.
+        const bool gn = eng_has_gn(e, nm + ".conv1");
+        const int act = gn ? 0 : 1;
         // the previous user of the stage's output buffer must have read it: one wait, ahead of whichever launch writes it (they are the first
         // thing of the phase that reads it, so this wait practically never blocks)
         bool fence = b == s.blocks - 1 && s.before_out != nullptr;
@@ -71,24 +107,33 @@ int resnet_stage(Engine& e, const ResStage& s, const Tensor& in, Tensor* out) {
         const bool pair = s.full && proj && x.dt == 0 && groups;
         if (pair) {  // fp32: the projection shortcut and conv1 read the same x: one grouped launch (round 5) instead of a side stream
             std::vector<ConvGroupItem> g(2);
-            g[0].layer = nm + ".conv1"; g[0].in = x; g[0].stride = st1; g[0].act = 1; g[0].out_name = sg + ".t1"; g[0].out = &t1;
+            g[0].layer = nm + ".conv1"; g[0].in = x; g[0].stride = st1; g[0].act = act; g[0].out_name = sg + ".t1"; g[0].out = &t1;
             g[1].layer = nm + ".downsample.0"; g[1].in = x; g[1].stride = st; g[1].out_name = blk + ".ds"; g[1].out = &idt;
             TRY(eng_conv_group(e, g));
+            if (gn) {
+                TRY(eng_gn(e, nm + ".conv1", &t1, nullptr, true));
+                TRY(eng_gn(e, nm + ".downsample.0", &idt, nullptr, false));
+            }
         } else {
             if (proj && s.full) {  // the projection shortcut is independent of conv1 -> conv2: side stream
                 TRY(eng_fork(e, 0));
                 SideScope sc(e, 0);
                 TRY(eng_conv(e, nm + ".downsample.0", x, st, 0, 0, nullptr, blk + ".ds", &idt));
+                if (gn) TRY(eng_gn(e, nm + ".downsample.0", &idt, nullptr, false));
             } else if (proj) {
                 TRY(eng_conv(e, nm + ".downsample.0", x, st, 0, 0, nullptr, blk + ".ds", &idt));
+                if (gn) TRY(eng_gn(e, nm + ".downsample.0", &idt, nullptr, false));
             }
-            TRY(eng_conv(e, nm + ".conv1", x, st1, 0, 1, nullptr, sg + ".t1", &t1, false, /*may_split=*/s.full && b > 0));   // (`conv_split_k`: see eng_conv)
+            TRY(eng_conv(e, nm + ".conv1", x, st1, 0, act, nullptr, sg + ".t1", &t1, false, /*may_split=*/s.full && b > 0));   // (`conv_split_k`: see eng_conv)
+            if (gn) TRY(eng_gn(e, nm + ".conv1", &t1, nullptr, true));
         }
         if (e.convs.count(nm + ".conv2.conv_offset_mask")) TRY(dcn_conv2(e, nm, blk, t1, st2, sg + ".t2", &t2));
-        else TRY(eng_conv(e, nm + ".conv2", t1, st2, 1, 1, nullptr, sg + ".t2", &t2, false, /*may_split=*/s.full));
+        else TRY(eng_conv(e, nm + ".conv2", t1, st2, 1, act, nullptr, sg + ".t2", &t2, false, /*may_split=*/s.full));
+        if (gn) TRY(eng_gn(e, nm + ".conv2", &t2, nullptr, true));
         if (proj && s.full && !pair) TRY(eng_join(e, 0));
         if (fence) HIP_TRY(hipStreamWaitEvent(e.stream, s.before_out, 0));
-        TRY(eng_conv(e, nm + ".conv3", t2, 1, 0, 1, &idt, out_name, &y, false, /*may_split=*/s.full));
+        TRY(eng_conv(e, nm + ".conv3", t2, 1, 0, act, gn ? nullptr : &idt, out_name, &y, false, /*may_split=*/s.full));
+        if (gn) TRY(eng_gn(e, nm + ".conv3", &y, &idt, true));
         x = y;
     }
     *out = x;

@@ -309,6 +309,45 @@ def upsample_nearest2x_add(coarse, lateral):
     return do.numpy()
 
 
+def _group_norm_fn():
+    """isegmi_op_group_norm with its argtypes declared: an ABI change raises instead of shifting arguments."""
+    f = lib().isegmi_op_group_norm
+    if f.argtypes is None:
+        V, I, L = C.c_void_p, C.c_int, C.c_int64
+        f.argtypes = [V, L, I, I, I, I, V, V, C.c_float, V, I, V, V, L, V]
+        f.restype = I
+        w = lib().isegmi_op_group_norm_workspace_bytes
+        w.argtypes = [L, I, I, I, I]
+        w.restype = L
+    return f
+
+
+def group_norm_device(d_x, N, H, W, Cc, groups, d_gamma, d_beta, eps=1e-5, d_residual=None, relu=False, d_out=None, d_ws=None):
+    """isegmi_op_group_norm on DeviceBuffers (d_out None: in place; d_ws None: allocated here when the shape needs one).  Returns the workspace."""
+    f = _group_norm_fn()
+    need = lib().isegmi_op_group_norm_workspace_bytes(N, H, W, Cc, groups)
+    if d_ws is None and need:
+        d_ws = DeviceBuffer((need,), np.uint8)
+    check(f(d_x.ptr, N, H, W, Cc, groups, d_gamma.ptr, d_beta.ptr, float(eps), _ptr(d_residual), int(bool(relu)), (d_out or d_x).ptr, _ptr(d_ws),
+            d_ws.nbytes if d_ws is not None else 0, None))
+    return d_ws
+
+
+def group_norm(x, groups, gamma, beta, eps=1e-5, residual=None, relu=False, inplace=False):
+    """GroupNorm of x [N,H,W,C] fp32 over (H, W, C / groups) per image and group, + residual, ReLU (isegmi_op_group_norm; N may be 0).
+    inplace: the kernel writes over its input (same result; the tests run both)."""
+    x = np.ascontiguousarray(x, np.float32)
+    N, H, W, Cc = x.shape
+    dx = DeviceBuffer.from_numpy(x)
+    dg = DeviceBuffer.from_numpy(np.ascontiguousarray(gamma, np.float32)); db = DeviceBuffer.from_numpy(np.ascontiguousarray(beta, np.float32))
+    assert dg.shape == (Cc,) and db.shape == (Cc,), (dg.shape, db.shape, Cc)
+    dr = None if residual is None else DeviceBuffer.from_numpy(np.ascontiguousarray(residual, np.float32))
+    assert dr is None or dr.shape == x.shape, (dr.shape, x.shape)
+    do = dx if inplace else DeviceBuffer(x.shape).poison()
+    group_norm_device(dx, N, H, W, Cc, int(groups), dg, db, eps, dr, relu, do)
+    return do.numpy()
+
+
 def upsample_nearest2x_add_f16(coarse, lateral):
     """isegmi_op_upsample_nearest2x_add_f16: coarse [N,Hc,Wc,C], lateral [N,H,W,C] cast to fp16 -> fp16 [N,H,W,C]."""
     coarse = np.ascontiguousarray(coarse, np.float16); lateral = np.ascontiguousarray(lateral, np.float16)

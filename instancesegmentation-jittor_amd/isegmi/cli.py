@@ -33,9 +33,11 @@ def _save_image_bgr(path, img):
     Image.fromarray(np.ascontiguousarray(img[:, :, ::-1])).save(path)
 
 
-def _weights(spec, kind, depth=50, ycfg=None):
+def _weights(spec, kind, depth=50, ycfg=None, gn=False):
     from .weights import maskrcnn_state_dict, yolact_state_dict
     if spec in ("", "random", None):
+        if kind == "maskrcnn" and gn:
+            return maskrcnn_state_dict(1234, depth, gn=True)
         if kind == "yolact" and ycfg is not None:
             return yolact_state_dict(1234, ycfg.depth, ycfg.num_priors, ycfg.dcn_layers, ycfg.dcn_interval, ycfg.use_maskiou, ycfg.backbone)
         return yolact_state_dict(1234, depth) if kind == "yolact" else maskrcnn_state_dict(1234, depth)
@@ -129,7 +131,7 @@ def cmd_test_net(a):
     mc = to_maskrcnn_config(c)
     rank, world, local = _rank_world()
     files = sorted(os.path.join(a.images, f) for f in os.listdir(a.images)) if a.images else []
-    demo = COCODemo(mc, min_image_size=mc.MIN_SIZE_TEST, confidence_threshold=0.0, state_dict=_weights(c.MODEL.WEIGHT, "maskrcnn", mc.depth),
+    demo = COCODemo(mc, min_image_size=mc.MIN_SIZE_TEST, confidence_threshold=0.0, state_dict=_weights(c.MODEL.WEIGHT, "maskrcnn", mc.depth, gn=mc.USE_GN),
                     max_image_size=mc.MAX_SIZE_TEST, device=local, max_batch=a.batch_size)
     stats = {}
     results = inference(demo, lambda i: _load_image_bgr(files[i]), batch_size=a.batch_size, group=a.group, rank=rank, world=world,

@@ -72,11 +72,18 @@ def _defaults():
         "DATALOADER": {"SIZE_DIVISIBILITY": 32},
         "MODEL": {"META_ARCHITECTURE": "GeneralizedRCNN", "WEIGHT": "", "MASK_ON": True,
                   "BACKBONE": {"CONV_BODY": "R-50-FPN"},
+                  # [UPSTREAM-RECALL] maskrcnn-benchmark defaults.py
+                  "GROUP_NORM": {"DIM_PER_GP": -1, "NUM_GROUPS": 32, "EPSILON": 1e-5},
+                  "RESNETS": {"TRANS_FUNC": "BottleneckWithFixedBatchNorm", "STEM_FUNC": "StemWithFixedBatchNorm", "STRIDE_IN_1X1": True,
+                              "RES5_DILATION": 1},
+                  "FPN": {"USE_GN": False, "USE_RELU": False},
+                  "ROI_BOX_HEAD": {"FEATURE_EXTRACTOR": "FPN2MLPFeatureExtractor", "USE_GN": False, "NUM_STACKED_CONVS": 4, "CONV_HEAD_DIM": 256,
+                                   "MLP_HEAD_DIM": 1024, "DILATION": 1},
                   "RPN": {"USE_FPN": True, "ANCHOR_SIZES": (32, 64, 128, 256, 512), "ANCHOR_STRIDE": (4, 8, 16, 32, 64),
                           "ASPECT_RATIOS": (0.5, 1.0, 2.0), "PRE_NMS_TOP_N_TEST": 1000, "POST_NMS_TOP_N_TEST": 1000,
                           "FPN_POST_NMS_TOP_N_TEST": 1000, "NMS_THRESH": 0.7, "MIN_SIZE": 0},
                   "ROI_HEADS": {"SCORE_THRESH": 0.05, "NMS": 0.5, "DETECTIONS_PER_IMG": 100},
-                  "ROI_MASK_HEAD": {"PREDICTOR": "MaskRCNNC4Predictor", "RESOLUTION": 28}},
+                  "ROI_MASK_HEAD": {"PREDICTOR": "MaskRCNNC4Predictor", "RESOLUTION": 28, "USE_GN": False, "DILATION": 1}},
     })
     return c
 
@@ -84,11 +91,73 @@ def _defaults():
 cfg = _defaults()
 
 
+def _bool(v):
+    return v if isinstance(v, bool) else str(v).strip().lower() in ("true", "1", "yes")
+
+
+def _norm_config(c, body):
+    """The norm / head keys (MODEL.GROUP_NORM, RESNETS, FPN, ROI_BOX_HEAD, ROI_MASK_HEAD) -> MaskRCNNConfig fields.  Built: FrozenBatchNorm everywhere
+    with the 2-MLP box head (today's models), or [UPSTREAM-RECALL] gn_baselines -- GroupNorm in backbone, FPN, Xconv1fc box head and mask head
+    together.  Everything else raises and names the key (none silently degrade)."""
+    m = c.MODEL
+    rn, fpn, bh, mh, g = m.RESNETS, m.FPN, m.ROI_BOX_HEAD, m.ROI_MASK_HEAD, m.GROUP_NORM
+    trans, stem = str(rn.TRANS_FUNC), str(rn.STEM_FUNC)
+    if trans not in ("BottleneckWithFixedBatchNorm", "BottleneckWithGN"):
+        raise ValueError("MODEL.RESNETS.TRANS_FUNC=%r: built are BottleneckWithFixedBatchNorm and BottleneckWithGN" % trans)
+    if stem not in ("StemWithFixedBatchNorm", "StemWithGN"):
+        raise ValueError("MODEL.RESNETS.STEM_FUNC=%r: built are StemWithFixedBatchNorm and StemWithGN" % stem)
+    for key, node in (("MODEL.RESNETS.RES5_DILATION", rn.RES5_DILATION), ("MODEL.ROI_BOX_HEAD.DILATION", bh.DILATION),
+                      ("MODEL.ROI_MASK_HEAD.DILATION", mh.DILATION)):
+        if int(node) != 1:
+            raise ValueError("%s=%s: dilated convolutions are not built" % (key, node))
+    if _bool(fpn.USE_RELU):
+        raise ValueError("MODEL.FPN.USE_RELU=True is not built")
+    fx = str(bh.FEATURE_EXTRACTOR)
+    if fx not in ("FPN2MLPFeatureExtractor", "FPNXconv1fcFeatureExtractor"):
+        raise ValueError("MODEL.ROI_BOX_HEAD.FEATURE_EXTRACTOR=%r: built are FPN2MLPFeatureExtractor and FPNXconv1fcFeatureExtractor" % fx)
+    flags = (("MODEL.RESNETS.TRANS_FUNC", trans == "BottleneckWithGN"), ("MODEL.RESNETS.STEM_FUNC", stem == "StemWithGN"),
+             ("MODEL.FPN.USE_GN", _bool(fpn.USE_GN)), ("MODEL.ROI_BOX_HEAD.USE_GN", _bool(bh.USE_GN)), ("MODEL.ROI_MASK_HEAD.USE_GN", _bool(mh.USE_GN)))
+    on = [k for k, v in flags if v]
+    stride_in_1x1 = _bool(rn.STRIDE_IN_1X1)
+    if not on:
+        if fx != "FPN2MLPFeatureExtractor":
+            raise ValueError("MODEL.ROI_BOX_HEAD.FEATURE_EXTRACTOR=%r is built with GroupNorm only (USE_GN: True)" % fx)
+        if not stride_in_1x1:
+            raise ValueError("MODEL.RESNETS.STRIDE_IN_1X1=False is built for the GroupNorm model only")
+        if int(bh.MLP_HEAD_DIM) != 1024:
+            raise ValueError("MODEL.ROI_BOX_HEAD.MLP_HEAD_DIM=%s: FPN2MLPFeatureExtractor is built at 1024" % bh.MLP_HEAD_DIM)
+        return {}
+    if body.endswith("-C4"):
+        raise ValueError("%s: GroupNorm is built for the FPN bodies only (MODEL.BACKBONE.CONV_BODY=%r)" % (on[0], body))
+    off = [k for k, v in flags if not v]
+    if off:
+        raise ValueError("%s asks for GroupNorm but %s does not: GroupNorm is built for backbone, FPN, box head and mask head together" % (on[0], off[0]))
+    if fx != "FPNXconv1fcFeatureExtractor":
+        raise ValueError("MODEL.ROI_BOX_HEAD.FEATURE_EXTRACTOR=%r with MODEL.ROI_BOX_HEAD.USE_GN: only FPNXconv1fcFeatureExtractor has GroupNorm" % fx)
+    groups, per = int(g.NUM_GROUPS), int(g.DIM_PER_GP)
+    if (groups > 0) == (per > 0):
+        raise ValueError("MODEL.GROUP_NORM: exactly one of DIM_PER_GP (%d) and NUM_GROUPS (%d) must be positive" % (per, groups))
+    conv_dim, mlp_dim, nconv = int(bh.CONV_HEAD_DIM), int(bh.MLP_HEAD_DIM), int(bh.NUM_STACKED_CONVS)
+    if nconv < 1:
+        raise ValueError("MODEL.ROI_BOX_HEAD.NUM_STACKED_CONVS=%d: at least one convolution" % nconv)
+    if conv_dim % 32 or mlp_dim % 32:
+        raise ValueError("MODEL.ROI_BOX_HEAD.CONV_HEAD_DIM / MLP_HEAD_DIM must be multiples of 32 (%d, %d)" % (conv_dim, mlp_dim))
+    for key, ch in [("MODEL.RESNETS (stage widths)", 64), ("MODEL.FPN (256 channels)", 256), ("MODEL.ROI_BOX_HEAD.CONV_HEAD_DIM", conv_dim)]:
+        if ch % (per if per > 0 else groups):
+            raise ValueError("MODEL.GROUP_NORM.%s=%d does not divide %s: %d channels" % ("DIM_PER_GP" if per > 0 else "NUM_GROUPS", per if per > 0 else groups, key, ch))
+        cpg = per if per > 0 else ch // groups
+        if 64 % cpg:
+            raise ValueError("MODEL.GROUP_NORM: %d channels per group (%s) -- the GroupNorm kernels take group widths that divide 64" % (cpg, key))
+    return dict(USE_GN=True, GN_NUM_GROUPS=groups if per <= 0 else 32, GN_DIM_PER_GP=per if per > 0 else -1, GN_EPSILON=float(g.EPSILON),
+                STRIDE_IN_1X1=stride_in_1x1, BOX_HEAD=fx, BOX_HEAD_STACKED_CONVS=nconv, BOX_HEAD_CONV_DIM=conv_dim, BOX_HEAD_MLP_DIM=mlp_dim)
+
+
 def to_maskrcnn_config(c):
     """Map the yaml-keyed node onto the frozen dataclass the engine consumes; rejects what the path does not build."""
     body = c.MODEL.BACKBONE.CONV_BODY
     r = c.MODEL.RPN
     h = c.MODEL.ROI_HEADS
+    norm = _norm_config(c, body)
     if body == "R-50-C4":
         # the yaml the reference prints (README.md:263-273): everything it does not set comes from maskrcnn-benchmark's
         # defaults.py -- one stride-16 map, no FPN merge, SIZE_DIVISIBILITY 0 (the engine pads to 16), 14x14 masks
@@ -112,4 +181,4 @@ def to_maskrcnn_config(c):
                           RPN_PRE_NMS_TOP_N_TEST=int(r.PRE_NMS_TOP_N_TEST), RPN_POST_NMS_TOP_N_TEST=int(r.POST_NMS_TOP_N_TEST),
                           RPN_FPN_POST_NMS_TOP_N_TEST=int(r.FPN_POST_NMS_TOP_N_TEST), RPN_NMS_THRESH=float(r.NMS_THRESH),
                           RPN_MIN_SIZE=float(r.MIN_SIZE), ROI_SCORE_THRESH=float(h.SCORE_THRESH), ROI_NMS=float(h.NMS),
-                          DETECTIONS_PER_IMG=int(h.DETECTIONS_PER_IMG))
+                          DETECTIONS_PER_IMG=int(h.DETECTIONS_PER_IMG), **norm)

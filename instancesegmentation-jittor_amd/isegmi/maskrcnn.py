@@ -50,6 +50,17 @@ class MaskRCNNConfig:
     # model run with conv_split_k=1, NOT against the default mode; results then depend on the batch size a layer is run at (the rule is by shape)
     CONV_SPLIT_K: int = 0
     CONV_BODY: str = "R-50-FPN"  # "R-50-FPN" / "R-101-FPN" (depth) or "R-50-C4" (the yaml README.md:263-273 prints)
+    # [UPSTREAM-RECALL] gn_baselines: GroupNorm in the backbone (StemWithGN / BottleneckWithGN), the FPN, the Xconv1fc box head and the
+    # mask head -- all of them or none (config.to_maskrcnn_config refuses the mixtures).  fp32 only.
+    USE_GN: bool = False
+    GN_NUM_GROUPS: int = 32      # MODEL.GROUP_NORM.NUM_GROUPS
+    GN_DIM_PER_GP: int = -1      # MODEL.GROUP_NORM.DIM_PER_GP: > 0 -> groups = C / DIM_PER_GP (then NUM_GROUPS is unused)
+    GN_EPSILON: float = 1e-5     # MODEL.GROUP_NORM.EPSILON
+    STRIDE_IN_1X1: bool = True   # MODEL.RESNETS.STRIDE_IN_1X1: a stage's stride on conv1 (True) or on the 3x3 (False: the GN yaml)
+    BOX_HEAD: str = "FPN2MLPFeatureExtractor"   # or "FPNXconv1fcFeatureExtractor" (with USE_GN)
+    BOX_HEAD_STACKED_CONVS: int = 4   # MODEL.ROI_BOX_HEAD.NUM_STACKED_CONVS
+    BOX_HEAD_CONV_DIM: int = 256      # MODEL.ROI_BOX_HEAD.CONV_HEAD_DIM
+    BOX_HEAD_MLP_DIM: int = 1024      # MODEL.ROI_BOX_HEAD.MLP_HEAD_DIM
 
     @staticmethod
     def c4():
@@ -198,6 +209,10 @@ class MaskRCNN:
     def __init__(self, state_dict, H, W, cfg=MaskRCNNConfig(), max_batch=2, device=0, fp16=False):
         assert H % cfg.SIZE_DIVISIBILITY == 0 and W % cfg.SIZE_DIVISIBILITY == 0
         assert not (cfg.is_c4 and fp16), "the C4 configuration is fp32 only"
+        if cfg.USE_GN and fp16:
+            raise ValueError("fp16=True with GroupNorm (USE_GN): the GroupNorm kernels are fp32 only")
+        if cfg.USE_GN and cfg.is_c4:
+            raise ValueError("USE_GN with the C4 body is not built")
         self.cfg, self.H, self.W, self.max_batch = cfg, H, W, max_batch
         self.mask_buf = "det.mask14" if cfg.is_c4 else "det.mask28"
         _ffi.lib()
@@ -210,8 +225,11 @@ class MaskRCNN:
         if cfg.is_c4:
             self.set_param("arch_c4", 1.0)
             self._load_c4(state_dict)
+        elif cfg.USE_GN:
+            self._load_gn(state_dict)
         else:
             self._load(state_dict)
+        self.set_param("stride_in_1x1", float(bool(cfg.STRIDE_IN_1X1)))
         for k, v in (("resnet_depth", cfg.depth), ("rpn_pre_nms_top_n", cfg.RPN_PRE_NMS_TOP_N_TEST),
                      ("rpn_post_nms_top_n", cfg.RPN_POST_NMS_TOP_N_TEST), ("rpn_fpn_post_nms_top_n", cfg.RPN_FPN_POST_NMS_TOP_N_TEST),
                      ("rpn_nms_thresh", cfg.RPN_NMS_THRESH), ("rpn_min_size", cfg.RPN_MIN_SIZE), ("roi_score_thresh", cfg.ROI_SCORE_THRESH),
@@ -292,6 +310,75 @@ class MaskRCNN:
         self._set_tensor("mask_logits.w", sd["roi_heads.mask.predictor.mask_fcn_logits.weight"].reshape(81, 256).astype(np.float32))
         self._set_tensor("mask_logits.b", sd["roi_heads.mask.predictor.mask_fcn_logits.bias"].astype(np.float32))
         # AnchorGenerator: the A base anchors per level go over; the engine lays the grid out for each batch's canvas (isegmi_op_grid_anchors)
+        for l, (stride, size) in enumerate(zip(cfg.ANCHOR_STRIDE, cfg.ANCHOR_SIZES)):
+            self._set_tensor("anchor_base.%d" % l, generate_anchors(stride, size, cfg.ASPECT_RATIOS))
+            self.set_param("anchor_stride%d" % l, float(stride))
+
+    def _set_gn_conv(self, sd, name, conv, norm, w=None):
+        """A convolution followed by GroupNorm: the conv goes over bare (scale 1, shift 0: no bias upstream), the norm's affine as the tensors
+        <name>.gn.weight / .gn.bias -- their presence is what makes the engine launch GroupNorm behind the layer."""
+        for k in (".running_mean", ".running_var"):
+            if norm + k in sd:
+                raise ValueError("%s has running statistics: a FrozenBatchNorm layer in a USE_GN model" % norm)
+        if conv + ".bias" in sd:
+            raise ValueError("%s.bias: a GroupNorm convolution has no bias" % conv)
+        w = to_krsc(sd[conv + ".weight"]) if w is None else w
+        if w.shape[0] != sd[norm + ".weight"].shape[0] or sd[norm + ".bias"].shape != sd[norm + ".weight"].shape:
+            raise ValueError("%s: affine shape %s does not match %d output channels" % (norm, sd[norm + ".weight"].shape, w.shape[0]))
+        cfg = self.cfg
+        if (w.shape[0] % cfg.GN_DIM_PER_GP if cfg.GN_DIM_PER_GP > 0 else w.shape[0] % cfg.GN_NUM_GROUPS):
+            raise ValueError("MODEL.GROUP_NORM: the groups do not divide the %d channels of %s" % (w.shape[0], norm))
+        self._set_conv_krsc(name, w)
+        self._set_tensor(name + ".gn.weight", np.asarray(sd[norm + ".weight"], np.float32))
+        self._set_tensor(name + ".gn.bias", np.asarray(sd[norm + ".bias"], np.float32))
+
+    def _load_gn(self, sd):
+        """[UPSTREAM-RECALL] gn_baselines state dict (weights.maskrcnn_gn_state_dict lists the names)."""
+        cfg = self.cfg
+        if cfg.BOX_HEAD != "FPNXconv1fcFeatureExtractor":
+            raise ValueError("USE_GN is built with BOX_HEAD FPNXconv1fcFeatureExtractor only")
+        for k, v in (("gn_num_groups", cfg.GN_NUM_GROUPS), ("gn_dim_per_gp", cfg.GN_DIM_PER_GP), ("gn_epsilon", cfg.GN_EPSILON)):
+            self.set_param(k, float(v))
+        w = to_krsc(sd["backbone.body.stem.conv1.weight"])
+        w = np.concatenate([w, np.zeros(w.shape[:3] + (1,), np.float32)], -1)
+        self._set_gn_conv(sd, "backbone.body.stem.conv1", "backbone.body.stem.conv1", "backbone.body.stem.bn1", w)
+        for li, nb in enumerate((3, 4, 23 if cfg.depth == 101 else 6, 3), 1):
+            for b in range(nb):
+                nm = "backbone.body.layer%d.%d" % (li, b)
+                for i in (1, 2, 3):
+                    self._set_gn_conv(sd, "%s.conv%d" % (nm, i), "%s.conv%d" % (nm, i), "%s.bn%d" % (nm, i))
+                if b == 0:
+                    self._set_gn_conv(sd, nm + ".downsample.0", nm + ".downsample.0", nm + ".downsample.1")
+        for i in range(1, 5):
+            for k in ("inner", "layer"):
+                nm = "backbone.fpn.fpn_%s%d" % (k, i)
+                self._set_gn_conv(sd, nm, nm + ".0", nm + ".1")
+        self._set_conv_krsc("rpn.head.conv", to_krsc(sd["rpn.head.conv.weight"]), None, sd["rpn.head.conv.bias"])
+        wcb = np.concatenate([to_krsc(sd["rpn.head.cls_logits.weight"]), to_krsc(sd["rpn.head.bbox_pred.weight"])], 0)
+        bcb = np.concatenate([sd["rpn.head.cls_logits.bias"], sd["rpn.head.bbox_pred.bias"]])
+        self._set_conv_krsc("rpn.head.cls_bbox", wcb, None, bcb)
+        fx = "roi_heads.box.feature_extractor"
+        for i in range(cfg.BOX_HEAD_STACKED_CONVS):
+            self._set_gn_conv(sd, "%s.xconvs.%d" % (fx, i), "%s.xconvs.%d" % (fx, 3 * i), "%s.xconvs.%d" % (fx, 3 * i + 1))
+        if "%s.xconvs.%d.weight" % (fx, 3 * cfg.BOX_HEAD_STACKED_CONVS) in sd or fx + ".fc7.weight" in sd:
+            raise ValueError("%s: more layers than NUM_STACKED_CONVS=%d convolutions and fc6" % (fx, cfg.BOX_HEAD_STACKED_CONVS))
+        cd, md = cfg.BOX_HEAD_CONV_DIM, cfg.BOX_HEAD_MLP_DIM
+        w6 = sd[fx + ".fc6.weight"]
+        if w6.shape != (md, cd * 49):
+            raise ValueError("%s.fc6.weight %s: expected (MLP_HEAD_DIM, CONV_HEAD_DIM * 7 * 7) = (%d, %d)" % (fx, w6.shape, md, cd * 49))
+        self._set_conv_krsc(fx + ".fc6", w6.reshape(md, cd, 7, 7).transpose(0, 2, 3, 1), None, sd[fx + ".fc6.bias"])
+        wp = np.concatenate([sd["roi_heads.box.predictor.cls_score.weight"], sd["roi_heads.box.predictor.bbox_pred.weight"]], 0)
+        bp = np.concatenate([sd["roi_heads.box.predictor.cls_score.bias"], sd["roi_heads.box.predictor.bbox_pred.bias"]])
+        self._set_conv_krsc("roi_heads.box.predictor.cls_bbox", wp.reshape(405, 1, 1, md), None, bp)
+        for i in range(1, 5):
+            nm = "roi_heads.mask.feature_extractor.mask_fcn%d" % i
+            self._set_gn_conv(sd, nm, nm + ".0", nm + ".1")
+        wd = sd["roi_heads.mask.predictor.conv5_mask.weight"]  # [Cin][Cout][2][2]
+        for ab in range(4):
+            wab = np.ascontiguousarray(wd[:, :, ab >> 1, ab & 1].T).reshape(256, 1, 1, 256)
+            self._set_conv_krsc("roi_heads.mask.predictor.conv5_mask.%d" % ab, wab, None, sd["roi_heads.mask.predictor.conv5_mask.bias"])
+        self._set_tensor("mask_logits.w", sd["roi_heads.mask.predictor.mask_fcn_logits.weight"].reshape(81, 256).astype(np.float32))
+        self._set_tensor("mask_logits.b", sd["roi_heads.mask.predictor.mask_fcn_logits.bias"].astype(np.float32))
         for l, (stride, size) in enumerate(zip(cfg.ANCHOR_STRIDE, cfg.ANCHOR_SIZES)):
             self._set_tensor("anchor_base.%d" % l, generate_anchors(stride, size, cfg.ASPECT_RATIOS))
             self.set_param("anchor_stride%d" % l, float(stride))

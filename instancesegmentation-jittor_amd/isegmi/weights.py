@@ -161,8 +161,72 @@ MRCNN_BBOX_GAIN = 0.0002
 MRCNN_MASK_LOGIT_GAIN = 0.0005
 
 
-def maskrcnn_state_dict(seed=1234, depth=50):
-    """maskrcnn-benchmark e2e_mask_rcnn_R_50/101_FPN state-dict names."""
+# Recorded calibration of the GroupNorm model's predictors (gn_baselines; found with the CPU reference tests/maskrcnn_gn_ref.py on the seeded 256 x 352
+# test canvas): every normalised feature is O(1) whatever the weights, so the gains differ from the FrozenBN model's.
+MRCNN_GN_RPN_CLS_GAIN = 0.05
+MRCNN_GN_RPN_BBOX_GAIN = 0.005
+MRCNN_GN_CLS_GAIN = 1.4
+MRCNN_GN_BG_BIAS = 4.0
+MRCNN_GN_BBOX_GAIN = 0.01
+MRCNN_GN_MASK_LOGIT_GAIN = 0.5
+
+
+def _gn(rng, sd, prefix, c, wscale=1.0):
+    """GroupNorm affine: weight U(0.5, 1.5), bias N(0, 0.1); no running statistics (that is what marks the layer as GroupNorm)."""
+    sd[prefix + ".weight"] = (rng.uniform(0.5, 1.5, c) * wscale).astype(np.float32)
+    sd[prefix + ".bias"] = (rng.standard_normal(c) * 0.1).astype(np.float32)
+
+
+def maskrcnn_gn_state_dict(seed=1234, depth=50, stacked_convs=4, conv_head_dim=256, mlp_head_dim=1024):
+    """[UPSTREAM-RECALL] maskrcnn-benchmark gn_baselines/e2e_mask_rcnn_R_50_FPN_1x_gn state-dict names: the norms sit where the FrozenBN sat
+    (stem.bn1, bn1/bn2/bn3, downsample.1) with weight and bias only; fpn_innerK / fpn_layerK / mask_fcnK are Sequential(conv, GN) -> `.0.weight`,
+    `.1.{weight,bias}`; box head xconvs.{0,3,6,9} (conv) and xconvs.{1,4,7,10} (GN), fc6, no fc7.  GN convolutions have no bias."""
+    rng = np.random.default_rng(seed)
+    sd = {}
+    tmp = {}
+    resnet_state_dict(rng, tmp, "", blocks=(3, 4, 23 if depth == 101 else 6, 3))
+    for k, v in tmp.items():
+        if k.endswith("running_mean") or k.endswith("running_var"):
+            continue
+        if k.endswith("bn3.weight"):   # the FrozenBN generator damps a block's last norm (x 0.25); GroupNorm renormalises every layer: undo it (exact)
+            v = v * np.float32(4.0)
+        if k.startswith("conv1.") or k.startswith("bn1."):
+            sd["backbone.body.stem." + k] = v
+        else:
+            parts = k.split(".")
+            sd["backbone.body.layer%d.%s" % (int(parts[1]) + 1, ".".join(parts[2:]))] = v
+    for i, cin in enumerate((256, 512, 1024, 2048), 1):
+        sd["backbone.fpn.fpn_inner%d.0.weight" % i] = _conv(rng, 256, cin, 1); _gn(rng, sd, "backbone.fpn.fpn_inner%d.1" % i, 256)
+        sd["backbone.fpn.fpn_layer%d.0.weight" % i] = _conv(rng, 256, 256, 3); _gn(rng, sd, "backbone.fpn.fpn_layer%d.1" % i, 256)
+    _conv_bias(rng, sd, "rpn.head.conv", 256, 256, 3)
+    _conv_bias(rng, sd, "rpn.head.cls_logits", 3, 256, 1, gain=MRCNN_GN_RPN_CLS_GAIN)
+    _conv_bias(rng, sd, "rpn.head.bbox_pred", 12, 256, 1, gain=MRCNN_GN_RPN_BBOX_GAIN)
+    cin = 256
+    for i in range(stacked_convs):
+        sd["roi_heads.box.feature_extractor.xconvs.%d.weight" % (3 * i)] = _conv(rng, conv_head_dim, cin, 3)
+        _gn(rng, sd, "roi_heads.box.feature_extractor.xconvs.%d" % (3 * i + 1), conv_head_dim)
+        cin = conv_head_dim
+
+    def fc(name, cout, cin, gain=1.0):
+        sd[name + ".weight"] = (rng.standard_normal((cout, cin)) * gain * np.sqrt(2.0 / cin)).astype(np.float32)
+        sd[name + ".bias"] = (rng.standard_normal(cout) * 0.01).astype(np.float32)
+    fc("roi_heads.box.feature_extractor.fc6", mlp_head_dim, conv_head_dim * 7 * 7)
+    fc("roi_heads.box.predictor.cls_score", 81, mlp_head_dim, MRCNN_GN_CLS_GAIN)
+    fc("roi_heads.box.predictor.bbox_pred", 324, mlp_head_dim, MRCNN_GN_BBOX_GAIN)
+    sd["roi_heads.box.predictor.cls_score.bias"][0] += MRCNN_GN_BG_BIAS
+    for i in range(1, 5):
+        sd["roi_heads.mask.feature_extractor.mask_fcn%d.0.weight" % i] = _conv(rng, 256, 256, 3)
+        _gn(rng, sd, "roi_heads.mask.feature_extractor.mask_fcn%d.1" % i, 256)
+    sd["roi_heads.mask.predictor.conv5_mask.weight"] = (rng.standard_normal((256, 256, 2, 2)) * np.sqrt(2.0 / 256)).astype(np.float32)
+    sd["roi_heads.mask.predictor.conv5_mask.bias"] = (rng.standard_normal(256) * 0.01).astype(np.float32)
+    _conv_bias(rng, sd, "roi_heads.mask.predictor.mask_fcn_logits", 81, 256, 1, gain=MRCNN_GN_MASK_LOGIT_GAIN)
+    return sd
+
+
+def maskrcnn_state_dict(seed=1234, depth=50, gn=False):
+    """maskrcnn-benchmark e2e_mask_rcnn_R_50/101_FPN state-dict names; gn=True: the GroupNorm model (maskrcnn_gn_state_dict)."""
+    if gn:
+        return maskrcnn_gn_state_dict(seed, depth)
     rng = np.random.default_rng(seed)
     sd = {}
     blocks = (3, 4, 23 if depth == 101 else 6, 3)

@@ -1,0 +1,217 @@
+"""GroupNorm on the CPU: the two references against each other and against torch, the derived bound (and that a naive fp32 variance misses it), the
+config mapping of the GroupNorm yaml, the importer's name mapping, and a torch nn.Module composition of one GN bottleneck and of the Xconv1fc box head
+against tests/maskrcnn_gn_ref.py (style of tests/test_composition_cpu.py)."""
+import os
+
+import numpy as np
+import pytest
+
+import groupnorm_ref as G
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GN_YAML = os.path.join(ROOT, "configs", "e2e_mask_rcnn_R_50_FPN_1x_gn.yaml")
+
+
+def _affine(rng, C):
+    return rng.uniform(0.5, 1.5, C).astype(np.float32), (rng.standard_normal(C) * 0.1).astype(np.float32)
+
+
+def _inputs(rng, shape):
+    n01 = rng.standard_normal(shape).astype(np.float32)
+    return {"normal": n01, "relu": np.maximum(n01, 0), "offset": (n01 * np.float32(0.5) + np.float32(500.0)).astype(np.float32)}
+
+
+SHAPES = [((2, 7, 7, 256), 32), ((2, 14, 14, 256), 32), ((1, 25, 42, 256), 32), ((2, 37, 53, 64), 32), ((2, 1, 1, 2048), 32), ((1, 37, 53, 256), 16)]
+
+
+@pytest.mark.parametrize("shape,groups", SHAPES)
+def test_restatement_inside_the_bound_and_naive_outside(shape, groups):
+    rng = np.random.default_rng(sum(shape))
+    ga, be = _affine(rng, shape[-1])
+    res = rng.standard_normal(shape).astype(np.float32)
+    for name, x in _inputs(rng, shape).items():
+        ref = G.gn_fp64(x, groups, ga, be)
+        err = np.abs(G.gn_kernel_order(x, groups, ga, be).astype(np.float64) - ref)
+        assert np.all(err <= G.gn_bound(x, groups, ga, be)), name
+        err = np.abs(G.gn_kernel_order(x, groups, ga, be, residual=res, relu=True).astype(np.float64) - G.gn_fp64(x, groups, ga, be, residual=res, relu=True))
+        assert np.all(err <= G.gn_bound(x, groups, ga, be, residual=res)), name
+        if name == "offset" and shape[1] * shape[2] > 1:   # |mu| / sigma = 1e3: plain fp32 E[x^2] - mu^2 cancels, the shifted sums do not
+            naive = np.abs(G.gn_naive_fp32(x, groups, ga, be).astype(np.float64) - ref)
+            assert np.any(naive > 100 * G.gn_bound(x, groups, ga, be))
+
+
+def test_constant_plane_and_single_pixel():
+    rng = np.random.default_rng(4)
+    ga, be = _affine(rng, 256)
+    for shape in ((2, 7, 7, 256), (1, 25, 42, 256)):
+        assert np.array_equal(G.gn_kernel_order(np.full(shape, 3.25, np.float32), 32, ga, be), np.broadcast_to(be, shape))
+    x = rng.standard_normal((3, 1, 1, 64)).astype(np.float32)
+    assert np.all(np.abs(G.gn_kernel_order(x, 32, ga[:64], be[:64]) - G.gn_fp64(x, 32, ga[:64], be[:64])) <= G.gn_bound(x, 32, ga[:64], be[:64]))
+
+
+def test_fp64_reference_against_torch():
+    torch = pytest.importorskip("torch")
+    rng = np.random.default_rng(7)
+    for shape, groups in SHAPES:
+        x = rng.standard_normal(shape); ga = rng.uniform(0.5, 1.5, shape[-1]); be = rng.standard_normal(shape[-1])
+        want = torch.nn.functional.group_norm(torch.from_numpy(x).permute(0, 3, 1, 2), groups, torch.from_numpy(ga), torch.from_numpy(be), 1e-5)
+        got = G.gn_fp64(x, groups, ga, be, eps=np.float64(np.float32(1e-5)))
+        assert np.allclose(got, want.permute(0, 2, 3, 1).numpy(), rtol=1e-9, atol=1e-9)   # (eps: float32(1e-5) against 1e-5, 3e-8 relative)
+
+
+# ------------------------------------------------------------------------------------------------------------------- config
+def _node(path=None, opts=()):
+    from isegmi.config import cfg
+    c = cfg.clone()
+    if path:
+        c.merge_from_file(path)
+    c.merge_from_list(list(opts))
+    return c
+
+
+def test_gn_yaml_maps_onto_the_gn_config():
+    from isegmi.config import to_maskrcnn_config
+    mc = to_maskrcnn_config(_node(GN_YAML))
+    assert mc.USE_GN and not mc.STRIDE_IN_1X1 and mc.BOX_HEAD == "FPNXconv1fcFeatureExtractor"
+    assert (mc.GN_NUM_GROUPS, mc.GN_DIM_PER_GP, mc.GN_EPSILON) == (32, -1, 1e-5)
+    assert (mc.BOX_HEAD_STACKED_CONVS, mc.BOX_HEAD_CONV_DIM, mc.BOX_HEAD_MLP_DIM) == (4, 256, 1024)
+    assert mc.depth == 50 and mc.CONV_BODY == "R-50-FPN" and not mc.is_c4
+    mc = to_maskrcnn_config(_node(GN_YAML, ("MODEL.GROUP_NORM.DIM_PER_GP", 16, "MODEL.GROUP_NORM.NUM_GROUPS", -1)))
+    assert mc.USE_GN and mc.GN_DIM_PER_GP == 16
+
+
+def test_old_yamls_map_as_before():
+    """Both existing yamls give exactly the objects the constructors without any GroupNorm field give."""
+    from isegmi.config import to_maskrcnn_config
+    from isegmi.maskrcnn import MaskRCNNConfig
+    assert to_maskrcnn_config(_node(os.path.join(ROOT, "configs", "e2e_mask_rcnn_R_50_FPN_1x.yaml"))) == MaskRCNNConfig()
+    assert to_maskrcnn_config(_node(os.path.join(ROOT, "configs", "e2e_mask_rcnn_R_50_C4_1x.yaml"))) == MaskRCNNConfig.c4()
+    assert to_maskrcnn_config(_node()) == MaskRCNNConfig()
+    assert not MaskRCNNConfig().USE_GN and MaskRCNNConfig().STRIDE_IN_1X1 and MaskRCNNConfig().BOX_HEAD == "FPN2MLPFeatureExtractor"
+
+
+@pytest.mark.parametrize("base,opts,key", [
+    (None, ("MODEL.RESNETS.TRANS_FUNC", "BottleneckWithGN", "MODEL.RESNETS.STEM_FUNC", "StemWithGN"), "MODEL.FPN.USE_GN"),          # GN in the backbone only
+    (None, ("MODEL.RESNETS.TRANS_FUNC", "BottleneckWithGN"), "MODEL.RESNETS.STEM_FUNC"),
+    (None, ("MODEL.FPN.USE_GN", True), "MODEL.FPN.USE_GN"),
+    (None, ("MODEL.ROI_MASK_HEAD.USE_GN", True), "MODEL.ROI_MASK_HEAD.USE_GN"),
+    (None, ("MODEL.ROI_BOX_HEAD.USE_GN", True), "MODEL.ROI_BOX_HEAD.USE_GN"),                                                  # FPN2MLP with USE_GN
+    (GN_YAML, ("MODEL.ROI_BOX_HEAD.FEATURE_EXTRACTOR", "FPN2MLPFeatureExtractor"), "MODEL.ROI_BOX_HEAD.FEATURE_EXTRACTOR"),
+    (None, ("MODEL.ROI_BOX_HEAD.FEATURE_EXTRACTOR", "FPNXconv1fcFeatureExtractor"), "MODEL.ROI_BOX_HEAD.FEATURE_EXTRACTOR"),
+    (None, ("MODEL.ROI_BOX_HEAD.FEATURE_EXTRACTOR", "ResNet50Conv5ROIFeatureExtractor"), "MODEL.ROI_BOX_HEAD.FEATURE_EXTRACTOR"),
+    (None, ("MODEL.RESNETS.STRIDE_IN_1X1", False), "MODEL.RESNETS.STRIDE_IN_1X1"),
+    (None, ("MODEL.RESNETS.TRANS_FUNC", "BottleneckWithBatchNorm"), "MODEL.RESNETS.TRANS_FUNC"),
+    (GN_YAML, ("MODEL.RESNETS.RES5_DILATION", 2), "MODEL.RESNETS.RES5_DILATION"),
+    (GN_YAML, ("MODEL.ROI_MASK_HEAD.DILATION", 2), "MODEL.ROI_MASK_HEAD.DILATION"),
+    (GN_YAML, ("MODEL.ROI_BOX_HEAD.DILATION", 2), "MODEL.ROI_BOX_HEAD.DILATION"),
+    (GN_YAML, ("MODEL.GROUP_NORM.DIM_PER_GP", 16), "MODEL.GROUP_NORM"),                                                         # both positive
+    (GN_YAML, ("MODEL.GROUP_NORM.NUM_GROUPS", 48), "MODEL.GROUP_NORM.NUM_GROUPS"),                                              # 48 does not divide 64
+    (GN_YAML, ("MODEL.BACKBONE.CONV_BODY", "R-50-C4"), "MODEL.BACKBONE.CONV_BODY"),
+    (GN_YAML, ("MODEL.FPN.USE_RELU", True), "MODEL.FPN.USE_RELU"),
+])
+def test_unsupported_combinations_raise_and_name_the_key(base, opts, key):
+    from isegmi.config import to_maskrcnn_config
+    with pytest.raises(ValueError) as ei:
+        to_maskrcnn_config(_node(base, opts))
+    assert key in str(ei.value), str(ei.value)
+
+
+# ------------------------------------------------------------------------------------------------------------------- weights / importer
+def test_gn_state_dict_and_importer_names():
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import import_pth
+    from isegmi.weights import maskrcnn_state_dict
+    sd = maskrcnn_state_dict(3, gn=True)
+    assert not any(k.endswith("running_mean") or k.endswith("running_var") for k in sd)
+    for k in ("backbone.body.stem.bn1.weight", "backbone.body.layer1.0.downsample.1.bias", "backbone.body.layer4.2.bn3.weight",
+              "backbone.fpn.fpn_inner1.0.weight", "backbone.fpn.fpn_inner1.1.bias", "backbone.fpn.fpn_layer4.1.weight",
+              "roi_heads.box.feature_extractor.xconvs.9.weight", "roi_heads.box.feature_extractor.xconvs.10.bias",
+              "roi_heads.box.feature_extractor.fc6.bias", "roi_heads.mask.feature_extractor.mask_fcn4.0.weight",
+              "roi_heads.mask.feature_extractor.mask_fcn4.1.weight", "rpn.head.conv.bias", "roi_heads.mask.predictor.conv5_mask.bias"):
+        assert k in sd, k
+    assert "roi_heads.box.feature_extractor.fc7.weight" not in sd and "backbone.fpn.fpn_inner1.bias" not in sd
+    g = sd["backbone.body.layer2.1.bn3.weight"]
+    assert 0.5 <= g.min() and g.max() <= 1.5
+    # an upstream checkpoint: {"model": {"module.<name>": tensor}} plus optimizer state and num_batches_tracked-style extras
+    ckpt = {"model": {"module." + k: v for k, v in sd.items()}, "optimizer": {"lr": 0.1}, "iteration": 90000}
+    out = import_pth.convert(ckpt, "maskrcnn_r50_fpn_gn")
+    assert set(out) == set(sd) and all(np.array_equal(out[k], sd[k]) for k in sd)
+    with pytest.raises(KeyError):   # a FrozenBN checkpoint is not a GroupNorm one
+        import_pth.convert({"model": maskrcnn_state_dict(3)}, "maskrcnn_r50_fpn_gn")
+    with pytest.raises(KeyError):
+        import_pth.convert(ckpt, "maskrcnn_r50_fpn")
+
+
+def test_seeded_gn_weights_give_detections_on_the_small_canvas():
+    """The condition of tests/test_maskrcnn_gn_gpu.py, checked with the reference alone: the seeded weights (their recorded predictor gains) yield at
+    least 8 detections on an image of the small canvas, so the mask head is exercised.  (One image: the reference forward is the slow part.)"""
+    from isegmi.maskrcnn import prepare_images
+    from isegmi.weights import maskrcnn_state_dict
+    from maskrcnn_gn_ref import MaskRCNNGNRef
+    rng = np.random.default_rng(20261003)
+    x, hw = prepare_images([rng.uniform(0, 255, (250, 340, 3)).astype(np.float32)])
+    rd = MaskRCNNGNRef(maskrcnn_state_dict(1234, gn=True)).forward(x, hw)
+    assert len(rd[0]["score"]) >= 8 and len(rd[0]["proposals"]) > 100
+    assert (rd[0]["mask28"] > 0.5).any() and (rd[0]["mask28"] < 0.5).any()
+
+
+# ------------------------------------------------------------------------------------------------------------------- composition (torch)
+def test_torch_composition_of_gn_bottleneck_and_xconv1fc_head():
+    """One BottleneckWithGN (projection, stride 2 on the 3x3) and the FPNXconv1fcFeatureExtractor as torch modules with upstream's names, loaded
+    strictly from the state dict, against maskrcnn_gn_ref.  Tolerance 1e-4 of the tensor's largest magnitude (different summation orders)."""
+    torch = pytest.importorskip("torch")
+    nn, F = torch.nn, torch.nn.functional
+    from isegmi.weights import maskrcnn_state_dict
+    from maskrcnn_gn_ref import MaskRCNNGNRef
+    sd = maskrcnn_state_dict(5, gn=True)
+    ref = MaskRCNNGNRef(sd)
+
+    def gn(c):
+        return nn.GroupNorm(32, c, 1e-5, affine=True)
+
+    class BottleneckWithGN(nn.Module):
+        def __init__(self, cin, mid, cout, stride):
+            super().__init__()
+            self.downsample = nn.Sequential(nn.Conv2d(cin, cout, 1, stride=stride, bias=False), gn(cout))
+            self.conv1 = nn.Conv2d(cin, mid, 1, bias=False); self.bn1 = gn(mid)
+            self.conv2 = nn.Conv2d(mid, mid, 3, stride=stride, padding=1, bias=False); self.bn2 = gn(mid)   # STRIDE_IN_1X1 False
+            self.conv3 = nn.Conv2d(mid, cout, 1, bias=False); self.bn3 = gn(cout)
+
+        def forward(self, x):
+            out = F.relu(self.bn1(self.conv1(x)))
+            out = F.relu(self.bn2(self.conv2(out)))
+            return F.relu(self.bn3(self.conv3(out)) + self.downsample(x))
+
+    class Xconv1fc(nn.Module):
+        def __init__(self):
+            super().__init__()
+            layers = []
+            for _ in range(4):
+                layers += [nn.Conv2d(256, 256, 3, padding=1, bias=False), gn(256), nn.ReLU()]
+            self.xconvs = nn.Sequential(*layers)
+            self.fc6 = nn.Linear(256 * 7 * 7, 1024)
+
+        def forward(self, x):
+            x = self.xconvs(x)
+            return x, F.relu(self.fc6(x.reshape(x.shape[0], -1)))
+
+    def load(mod, prefix):
+        mod.load_state_dict({k[len(prefix):]: torch.from_numpy(np.asarray(v)) for k, v in sd.items() if k.startswith(prefix)}, strict=True)
+        return mod.eval()
+
+    def close(got, want, name):
+        err = np.max(np.abs(got - want)) / max(1e-6, np.max(np.abs(want)))
+        assert got.shape == want.shape and err < 1e-4, (name, err)
+
+    rng = np.random.default_rng(6)
+    with torch.no_grad():
+        x = rng.standard_normal((2, 13, 17, 256)).astype(np.float32)
+        blk = load(BottleneckWithGN(256, 128, 512, 2), "backbone.body.layer2.0.")
+        close(blk(torch.from_numpy(x).permute(0, 3, 1, 2)).permute(0, 2, 3, 1).numpy(), ref.bottleneck(x, "backbone.body.layer2.0", 2, True), "bottleneck")
+        r = np.maximum(rng.standard_normal((5, 7, 7, 256)), 0).astype(np.float32)
+        head = load(Xconv1fc(), "roi_heads.box.feature_extractor.")
+        xt, f6 = head(torch.from_numpy(r).permute(0, 3, 1, 2))
+        xf, f6r = ref.xconv1fc(r)
+        close(xt.permute(0, 2, 3, 1).numpy(), xf, "xconvs")
+        close(f6.numpy(), f6r.reshape(5, -1), "fc6")

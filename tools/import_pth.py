@@ -1,7 +1,7 @@
 """Pretrained-weight importer: the checkpoints the reference README points at -> an .npz state dict in the
 upstream key names isegmi.yolact.Yolact / isegmi.maskrcnn.MaskRCNN consume.
 
-    python tools/import_pth.py IN OUT.npz [--family maskrcnn_r50_fpn|maskrcnn_r101_fpn|maskrcnn_r50_c4|yolact_resnet50|yolact_base|
+    python tools/import_pth.py IN OUT.npz [--family maskrcnn_r50_fpn|maskrcnn_r101_fpn|maskrcnn_r50_c4|maskrcnn_r50_fpn_gn|yolact_resnet50|yolact_base|
                                                     yolact_im700|yolact_darknet53|yolact_plus_resnet50|yolact_plus_base]
 
 Accepted inputs (torch is used HERE only to unpickle -- a tool, not the product):
@@ -30,7 +30,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "instancesegmentation-jittor_amd")]
 
-FAMILIES = ("maskrcnn_r50_fpn", "maskrcnn_r101_fpn", "maskrcnn_r50_c4", "yolact_resnet50", "yolact_base", "yolact_im700",
+FAMILIES = ("maskrcnn_r50_fpn", "maskrcnn_r101_fpn", "maskrcnn_r50_c4", "maskrcnn_r50_fpn_gn", "yolact_resnet50", "yolact_base", "yolact_im700",
             "yolact_darknet53", "yolact_plus_resnet50", "yolact_plus_base")
 
 
@@ -44,6 +44,10 @@ def expected_keys(family):
         sd = W.maskrcnn_state_dict(0, 101)
     elif family == "maskrcnn_r50_c4":
         sd = W.maskrcnn_c4_state_dict(0)
+    elif family == "maskrcnn_r50_fpn_gn":
+        # [UPSTREAM-RECALL] gn_baselines/e2e_mask_rcnn_R_50_FPN_1x_gn: GroupNorm where the FrozenBN sat (weight / bias only), Sequential(conv, GN)
+        # for fpn_innerK / fpn_layerK / mask_fcnK (`.0.weight`, `.1.weight`, `.1.bias`), box head xconvs.{0,3,6,9} / {1,4,7,10} + fc6
+        sd = W.maskrcnn_state_dict(0, 50, gn=True)
     else:
         cfg = {"yolact_resnet50": YolactConfig(), "yolact_base": YolactConfig.base(), "yolact_im700": YolactConfig.im700(),
                "yolact_darknet53": YolactConfig.darknet53(), "yolact_plus_resnet50": YolactConfig.plus_resnet50(),
