@@ -322,14 +322,23 @@ def _group_norm_fn():
     return f
 
 
-def group_norm_device(d_x, N, H, W, Cc, groups, d_gamma, d_beta, eps=1e-5, d_residual=None, relu=False, d_out=None, d_ws=None):
-    """isegmi_op_group_norm on DeviceBuffers (d_out None: in place; d_ws None: allocated here when the shape needs one).  Returns the workspace."""
+def group_norm_device(d_x, N, H, W, Cc, groups, d_gamma, d_beta, eps=1e-5, d_residual=None, relu=False, d_out=None, d_ws=None, ws_bytes=None,
+                      alloc_ws=True, offsets=None):
+    """isegmi_op_group_norm on DeviceBuffers (d_out None: in place; d_ws None: allocated here when the shape needs one).  Returns the workspace.
+    For the launcher's refusals: `ws_bytes` is the workspace size handed over (default: the buffer's), `alloc_ws` False passes a null workspace where
+    none is given, `offsets` {"x" | "out" | "gamma" | "beta" | "residual" | "ws": bytes} moves a pointer into its (over-allocated) buffer."""
     f = _group_norm_fn()
     need = lib().isegmi_op_group_norm_workspace_bytes(N, H, W, Cc, groups)
-    if d_ws is None and need:
+    if d_ws is None and need and alloc_ws:
         d_ws = DeviceBuffer((need,), np.uint8)
-    check(f(d_x.ptr, N, H, W, Cc, groups, d_gamma.ptr, d_beta.ptr, float(eps), _ptr(d_residual), int(bool(relu)), (d_out or d_x).ptr, _ptr(d_ws),
-            d_ws.nbytes if d_ws is not None else 0, None))
+    off = offsets or {}
+
+    def at(buf, key):
+        return C.c_void_p(buf.ptr.value + off[key]) if buf is not None and off.get(key) else _ptr(buf)
+    if ws_bytes is None:
+        ws_bytes = d_ws.nbytes if d_ws is not None else 0
+    check(f(at(d_x, "x"), N, H, W, Cc, groups, at(d_gamma, "gamma"), at(d_beta, "beta"), float(eps), at(d_residual, "residual"), int(bool(relu)),
+            at(d_out or d_x, "out"), at(d_ws, "ws"), ws_bytes, None))
     return d_ws
 
 

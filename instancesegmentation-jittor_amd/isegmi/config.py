@@ -13,7 +13,7 @@ import copy
 
 import yaml
 
-from .maskrcnn import MaskRCNNConfig
+from .maskrcnn import MaskRCNNConfig, gn_groups, gn_model_layers
 
 
 def _literal(v):
@@ -142,12 +142,8 @@ def _norm_config(c, body):
         raise ValueError("MODEL.ROI_BOX_HEAD.NUM_STACKED_CONVS=%d: at least one convolution" % nconv)
     if conv_dim % 32 or mlp_dim % 32:
         raise ValueError("MODEL.ROI_BOX_HEAD.CONV_HEAD_DIM / MLP_HEAD_DIM must be multiples of 32 (%d, %d)" % (conv_dim, mlp_dim))
-    for key, ch in [("MODEL.RESNETS (stage widths)", 64), ("MODEL.FPN (256 channels)", 256), ("MODEL.ROI_BOX_HEAD.CONV_HEAD_DIM", conv_dim)]:
-        if ch % (per if per > 0 else groups):
-            raise ValueError("MODEL.GROUP_NORM.%s=%d does not divide %s: %d channels" % ("DIM_PER_GP" if per > 0 else "NUM_GROUPS", per if per > 0 else groups, key, ch))
-        cpg = per if per > 0 else ch // groups
-        if 64 % cpg:
-            raise ValueError("MODEL.GROUP_NORM: %d channels per group (%s) -- the GroupNorm kernels take group widths that divide 64" % (cpg, key))
+    for layer, ch in gn_model_layers(box_head_conv_dim=conv_dim):   # every GroupNorm width of the model, res5's 2048 included
+        gn_groups(ch, groups, per, layer)
     return dict(USE_GN=True, GN_NUM_GROUPS=groups if per <= 0 else 32, GN_DIM_PER_GP=per if per > 0 else -1, GN_EPSILON=float(g.EPSILON),
                 STRIDE_IN_1X1=stride_in_1x1, BOX_HEAD=fx, BOX_HEAD_STACKED_CONVS=nconv, BOX_HEAD_CONV_DIM=conv_dim, BOX_HEAD_MLP_DIM=mlp_dim)
 

@@ -78,6 +78,32 @@ class MaskRCNNConfig:
         return max(self.DETECTIONS_PER_IMG, self.DETECTIONS_CAP)
 
 
+GN_TILE_CHANNELS = 64   # csrc/groupnorm.hip GN_TILE_C
+
+
+def gn_groups(channels, num_groups, dim_per_gp, layer):
+    """THE rule of which GroupNorm configurations are built, stated once (config.to_maskrcnn_config and MaskRCNN._set_gn_conv both ask here; the kernel's
+    own check, gn_geometry, is the backstop): the groups divide the layer's channels, and a layer of 64 channels or more has groups of 1, 2, 4 ... 64
+    channels, because the kernels cut the channels into tiles of 64 and a tile holds whole groups.  -> the layer's group count; raises ValueError that
+    names the yaml key, the layer and its channel count."""
+    key, val = ("DIM_PER_GP", dim_per_gp) if dim_per_gp > 0 else ("NUM_GROUPS", num_groups)
+    if val <= 0 or channels % val:
+        raise ValueError("MODEL.GROUP_NORM.%s=%d does not divide the %d channels of %s" % (key, val, channels, layer))
+    cpg = dim_per_gp if dim_per_gp > 0 else channels // num_groups
+    if channels % 4 or (channels >= GN_TILE_CHANNELS and (channels % GN_TILE_CHANNELS or GN_TILE_CHANNELS % cpg)):
+        raise ValueError("MODEL.GROUP_NORM.%s=%d gives groups of %d channels in %s (%d channels): the GroupNorm kernels take channel counts that are "
+                         "multiples of 4 and, from 64 channels on, multiples of 64 with group widths that divide 64" % (key, val, cpg, layer, channels))
+    return channels // cpg
+
+
+def gn_model_layers(box_head_conv_dim=256):
+    """(name, channels) of every distinct GroupNorm width of the gn_baselines model, for the checks that run before any weight is seen."""
+    out = [("backbone.body.stem", 64)]
+    for li in range(1, 5):
+        out += [("backbone.body.layer%d (conv1 / conv2)" % li, 64 << (li - 1)), ("backbone.body.layer%d (conv3 / downsample)" % li, 256 << (li - 1))]
+    return out + [("backbone.fpn", 256), ("MODEL.ROI_BOX_HEAD.CONV_HEAD_DIM", box_head_conv_dim), ("roi_heads.mask.feature_extractor", 256)]
+
+
 # ---------------------------------------------------------------------------------------- anchors (A.3)
 def _whctrs(a):
     w = a[2] - a[0] + 1
@@ -213,6 +239,9 @@ class MaskRCNN:
             raise ValueError("fp16=True with GroupNorm (USE_GN): the GroupNorm kernels are fp32 only")
         if cfg.USE_GN and cfg.is_c4:
             raise ValueError("USE_GN with the C4 body is not built")
+        if cfg.USE_GN:   # before the engine exists: a refused configuration costs nothing and needs no device
+            for layer, ch in gn_model_layers(cfg.BOX_HEAD_CONV_DIM):
+                gn_groups(ch, cfg.GN_NUM_GROUPS, cfg.GN_DIM_PER_GP, layer)
         self.cfg, self.H, self.W, self.max_batch = cfg, H, W, max_batch
         self.mask_buf = "det.mask14" if cfg.is_c4 else "det.mask28"
         _ffi.lib()
@@ -326,8 +355,7 @@ class MaskRCNN:
         if w.shape[0] != sd[norm + ".weight"].shape[0] or sd[norm + ".bias"].shape != sd[norm + ".weight"].shape:
             raise ValueError("%s: affine shape %s does not match %d output channels" % (norm, sd[norm + ".weight"].shape, w.shape[0]))
         cfg = self.cfg
-        if (w.shape[0] % cfg.GN_DIM_PER_GP if cfg.GN_DIM_PER_GP > 0 else w.shape[0] % cfg.GN_NUM_GROUPS):
-            raise ValueError("MODEL.GROUP_NORM: the groups do not divide the %d channels of %s" % (w.shape[0], norm))
+        gn_groups(w.shape[0], cfg.GN_NUM_GROUPS, cfg.GN_DIM_PER_GP, norm)   # refuses what the kernels do not take, here and not in the first forward
         self._set_conv_krsc(name, w)
         self._set_tensor(name + ".gn.weight", np.asarray(sd[norm + ".weight"], np.float32))
         self._set_tensor(name + ".gn.bias", np.asarray(sd[norm + ".bias"], np.float32))

@@ -102,12 +102,11 @@ def _stats_kernel_order(d, groups, slab):
     return out[0], out[1]
 
 
-def gn_kernel_order(x, groups, gamma, beta, eps=1e-5, residual=None, relu=False):
-    """(b) csrc/groupnorm.hip restated: shifted data, the documented summation order, fp64 moments, fp32 apply.  -> float32 [N, H, W, C]"""
+def gn_moments_kernel_order(x, groups, eps=1e-5):
+    """The statistics half of (b): -> (d [N, HW, C] fp32 shifted data, m [N, groups] fp32, rstd [N, groups] fp32).  gn_kernel_order takes the result as
+    `moments`, so a test that applies several epilogues to one input pays for the summation once."""
     x = np.ascontiguousarray(x, np.float32)
     N, H, W, C = x.shape
-    if N == 0:
-        return x.copy()
     HW, cpg = H * W, C // groups
     assert C % 4 == 0 and C % groups == 0 and C % min(C, TILE_C) == 0 and min(C, TILE_C) % cpg == 0, (C, groups)
     xr = x.reshape(N, HW, C)
@@ -122,6 +121,19 @@ def gn_kernel_order(x, groups, gamma, beta, eps=1e-5, residual=None, relu=False)
         var = np.where(var > 0.0, var, 0.0)
         m = md.astype(np.float32)
         rstd = (1.0 / np.sqrt(var + np.float64(np.float32(eps)))).astype(np.float32)
+    return d, m, rstd
+
+
+def gn_kernel_order(x, groups, gamma, beta, eps=1e-5, residual=None, relu=False, moments=None):
+    """(b) csrc/groupnorm.hip restated: shifted data, the documented summation order, fp64 moments, fp32 apply.  -> float32 [N, H, W, C]"""
+    x = np.ascontiguousarray(x, np.float32)
+    N, H, W, C = x.shape
+    if N == 0:
+        return x.copy()
+    HW = H * W
+    grp = np.arange(C) // (C // groups)
+    d, m, rstd = gn_moments_kernel_order(x, groups, eps) if moments is None else moments
+    with np.errstate(all="ignore"):
         y = (d - m[:, None, grp]) * rstd[:, None, grp] * np.asarray(gamma, np.float32) + np.asarray(beta, np.float32)
         if residual is not None:
             y = y + np.ascontiguousarray(residual, np.float32).reshape(N, HW, C)
@@ -129,6 +141,24 @@ def gn_kernel_order(x, groups, gamma, beta, eps=1e-5, residual=None, relu=False)
             y = np.where(y > 0.0, y, np.float32(0.0))
     assert y.dtype == np.float32
     return y.reshape(N, H, W, C)
+
+
+def affine(rng, C):
+    """gamma in [0.5, 1.5], beta ~ 0.1 N(0, 1): what a trained norm looks like."""
+    return rng.uniform(0.5, 1.5, C).astype(np.float32), (rng.standard_normal(C) * 0.1).astype(np.float32)
+
+
+def check_bits(ffi, x, groups, seed=0, eps=1e-5, gamma_beta=None):
+    """The kernel through ffi.group_norm against the restatement, bit for bit: plain, ReLU, residual, residual + ReLU, each out of place and in place."""
+    rng = np.random.default_rng(seed)
+    ga, be = affine(rng, x.shape[-1]) if gamma_beta is None else gamma_beta
+    res = rng.standard_normal(x.shape).astype(np.float32)
+    mom = gn_moments_kernel_order(x, groups, eps)
+    for kw in (dict(), dict(residual=res, relu=True), dict(relu=True), dict(residual=res)):
+        want = gn_kernel_order(x, groups, ga, be, eps, kw.get("residual"), kw.get("relu", False), moments=mom)
+        for inplace in (False, True):
+            got = ffi.group_norm(x, groups, ga, be, eps, inplace=inplace, **kw)
+            assert got.shape == x.shape and np.array_equal(got, want), (x.shape, groups, eps, sorted(kw), inplace)
 
 
 def gn_naive_fp32(x, groups, gamma, beta, eps=1e-5):

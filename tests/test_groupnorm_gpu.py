@@ -9,20 +9,7 @@ import groupnorm_ref as G
 pytestmark = pytest.mark.gpu
 
 
-def _affine(rng, C):
-    return rng.uniform(0.5, 1.5, C).astype(np.float32), (rng.standard_normal(C) * 0.1).astype(np.float32)
-
-
-def _check_bits(ffi, x, groups, seed=0):
-    """Plain, residual + ReLU, and in place (with residual + ReLU): each against the restatement."""
-    rng = np.random.default_rng(seed)
-    ga, be = _affine(rng, x.shape[-1])
-    res = rng.standard_normal(x.shape).astype(np.float32)
-    for kw in (dict(), dict(residual=res, relu=True), dict(relu=True), dict(residual=res)):
-        want = G.gn_kernel_order(x, groups, ga, be, 1e-5, kw.get("residual"), kw.get("relu", False))
-        for inplace in (False, True):
-            got = ffi.group_norm(x, groups, ga, be, 1e-5, inplace=inplace, **kw)
-            assert got.shape == x.shape and np.array_equal(got, want), (x.shape, groups, sorted(kw), inplace)
+_affine, _check_bits = G.affine, G.check_bits
 
 
 # channels per group 2, 8, 64 (C = 64, 256, 2048 with 32 groups) and DIM_PER_GP 16; planes of 1, 49, 196 (slabs) and 25x42, 37x53 (chunks of 512 pixels:

@@ -1,36 +1,12 @@
 """The GroupNorm Mask R-CNN (gn_baselines: GN backbone, FPN, Xconv1fc box head, GN mask head) end to end: the HIP engine against
 tests/maskrcnn_gn_ref.py -- the oracle's ops plus the GroupNorm restatement in the kernel's summation order -- bit for bit."""
-import dataclasses
-
 import numpy as np
 import pytest
 
 import groupnorm_ref as G
-from maskrcnn_gn_ref import MaskRCNNGNRef
+from maskrcnn_gn_common import MaskRCNNGNRef, gn_cfg as _cfg, sd, small  # noqa: F401  (sd, small: fixtures, shared with test_maskrcnn_gn_forms_gpu.py)
 
 pytestmark = pytest.mark.gpu
-
-
-def _cfg(**kw):
-    from isegmi.maskrcnn import MaskRCNNConfig
-    return dataclasses.replace(MaskRCNNConfig(), USE_GN=True, STRIDE_IN_1X1=False, BOX_HEAD="FPNXconv1fcFeatureExtractor", **kw)
-
-
-@pytest.fixture(scope="module")
-def sd():
-    from isegmi.weights import maskrcnn_state_dict
-    return maskrcnn_state_dict(1234, gn=True)
-
-
-@pytest.fixture(scope="module")
-def small(sd):
-    """The small canvas of tests/test_maskrcnn_e2e_gpu.py, bs = 2, and its reference forward (computed once, never modified)."""
-    from isegmi.maskrcnn import prepare_images
-    rng = np.random.default_rng(20261003)
-    x, hw = prepare_images([rng.uniform(0, 255, (250, 340, 3)).astype(np.float32), rng.uniform(0, 255, (256, 300, 3)).astype(np.float32)])
-    ref = MaskRCNNGNRef(sd)
-    rd = ref.forward(x, hw)
-    return x, hw, ref, rd
 
 
 def _same_detections(out, rd):
