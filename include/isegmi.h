@@ -199,7 +199,10 @@ int isegmi_op_upsample_nearest2x_add_f16(const void* d_coarse, int N, int Hc, in
 /* ---- selection: torch.topk / sort stand-in (M6, M9, Y6) ----
  * rows independent problems; row r = d_keys + r*row_stride, n elements; output sorted by
  * (score desc, index asc); k <= 8192.  k_eff = min(k, n, d_limit[r / rows_per_limit]) when
- * d_limit != NULL.  d_vals/d_idx are [rows][k]; d_cnt [rows] (optional) receives k_eff. */
+ * d_limit != NULL.  d_vals/d_idx are [rows][k]; d_cnt [rows] (optional) receives k_eff.
+ * Key order contract: keys compare as floats -- -0.0 and +0.0 are equal (the lower index first, as torch.topk / sort
+ * order them), +-inf and subnormals are ordinary keys.  d_vals holds the selected keys bit for bit, except that a
+ * selected -0.0 is returned as +0.0 (both zeros share one sort key).  NaN keys are outside the contract. */
 int isegmi_op_topk(const float* d_keys, int64_t row_stride, int rows, int n, int k,
                    const int32_t* d_limit, int rows_per_limit, float* d_vals, int32_t* d_idx,
                    int32_t* d_cnt, void* stream);
@@ -265,7 +268,8 @@ int isegmi_op_yolact_masks(const float* d_proto, const float* d_coeffs, const fl
                                      instead of score order; the RPN truncates a score-sorted list, where both orders keep the same boxes in the same order */
 /* greedy NMS (A.6): `problems` independent sets of n <= 6144 boxes; visiting order (score desc, index
  * asc); IoU with legacy +1 areas when plus_one; suppress on iou > thr (ge: >=).  d_keep [problems][n]
- * receives ORIGINAL indices in score order, d_cnt [problems] the count (<= max_keep when max_keep > 0). */
+ * receives ORIGINAL indices in score order, d_cnt [problems] the count (<= max_keep when max_keep > 0).
+ * Scores follow isegmi_op_topk's key order contract: -0.0 == +0.0 (index decides), no NaN. */
 int isegmi_op_nms(const float* d_boxes, const float* d_scores, int problems, int n, float thr,
                   int plus_one, int ge, int max_keep, int32_t* d_keep, int32_t* d_cnt, void* stream);
 /* LevelMapper + RoIAlign (A.7).  aligned 0: the legacy op (no half-pixel shift, RoI at least one pixel wide and high -- maskrcnn-benchmark); aligned 1:

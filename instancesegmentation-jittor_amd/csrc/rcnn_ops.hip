@@ -21,8 +21,10 @@
 
 namespace isegmi {
 
+// scores order as floats: -0.0 == +0.0 share one key and the index decides (ora_nms's comparator; csrc/select.hip has the contract).  NaN scores: outside it.
 __device__ __forceinline__ unsigned f2ord_(float f) {
     const unsigned u = __float_as_uint(f);
+    if (u == 0x80000000u) return 0x80000000u;
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ float ord2f_(unsigned o) {
@@ -1181,8 +1183,9 @@ __global__ __launch_bounds__(256) void paste_masks_kernel(const float* __restric
         for (int e = 0; e < 4; ++e) {
             const int64_t f = q + e;
             if (f >= total) break;
-            int y = yrow, x = (int)(f - (int64_t)yrow * im_w);   // the word may reach into the row above or below
-            if (x < 0) { x += im_w; --y; } else if (x >= im_w) { x -= im_w; ++y; }
+            int y = yrow, x = (int)(f - (int64_t)yrow * im_w);   // the word may reach into the row above or below -- two rows away in an image
+            while (x < 0) { x += im_w; --y; }                    // narrower than 3 pixels (x spans -3 .. im_w + 2): one step only when im_w >= 3
+            while (x >= im_w) { x -= im_w; ++y; }
             if (y < y_0 || y >= y_1 || x < x_0 || x >= x_1) continue;
             int sy0, sy1, sx0, sx1; float ly0, ly1, lx0, lx1;
             dm_bil_coef_s(y - y1, P, sy, sy0, sy1, ly0, ly1);

@@ -5,6 +5,12 @@
 // the box post-processor (M9).  Total order = (score descending, index ascending): exactly the
 // oracle's ora_topk, so indices are bit-identical.
 //
+// KEY ORDER CONTRACT.  Keys compare as floats, not as bit patterns: -0.0 and +0.0 are EQUAL (the lower
+// index wins, as in ora_topk, torch.topk and sort), -inf < every finite key < +inf, subnormals keep
+// their value.  f2ord() maps both zeros to one sort key; a returned value is rebuilt from that key, so
+// a selected -0.0 comes back as +0.0 (every other value comes back bit for bit).  NaN keys are outside
+// the contract: a comparator-based reference has no total order with them.
+//
 // One block per problem row:
 //   A. 3-pass radix select (12+12+8 bits, LDS histogram) of the threshold score T with
 //      count(score > T) < k <= count(score >= T);
@@ -22,6 +28,7 @@ namespace isegmi {
 
 __device__ __forceinline__ unsigned f2ord(float f) {
     const unsigned u = __float_as_uint(f);
+    if (u == 0x80000000u) return 0x80000000u;  // -0.0 == +0.0: one key for both, the index decides
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ float ord2f(unsigned o) {

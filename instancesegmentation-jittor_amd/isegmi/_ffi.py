@@ -385,15 +385,22 @@ def map_f32(x, fn):
     return dy.numpy()
 
 
-def topk(keys2d, k, limit=None, rows_per_limit=1):
-    """keys2d [rows][n] -> (vals [rows][k], idx [rows][k], cnt [rows])"""
+def topk(keys2d, k, limit=None, rows_per_limit=1, row_stride=None):
+    """keys2d [rows][n] -> (vals [rows][k], idx [rows][k], cnt [rows]).  row_stride > n: the rows lie row_stride keys apart on the device and the
+    row_stride - n keys between them hold +inf (selected first if the kernel ever read them)."""
     keys2d = np.ascontiguousarray(keys2d, np.float32)
     rows, n = keys2d.shape
+    row_stride = n if row_stride is None else int(row_stride)
+    assert row_stride >= n
+    if row_stride > n:
+        padded = np.full((rows, row_stride), np.inf, np.float32)
+        padded[:, :n] = keys2d
+        keys2d = padded
     dk = DeviceBuffer.from_numpy(keys2d)
     dv = DeviceBuffer((rows, k), np.float32); di = DeviceBuffer((rows, k), np.int32); dc = DeviceBuffer((rows,), np.int32)
     dv.zero(); di.zero()
     dl = None if limit is None else DeviceBuffer.from_numpy(np.asarray(limit, np.int32))
-    check(lib().isegmi_op_topk(dk.ptr, C.c_int64(n), rows, n, k, _ptr(dl), rows_per_limit, dv.ptr, di.ptr, dc.ptr, None))
+    check(lib().isegmi_op_topk(dk.ptr, C.c_int64(row_stride), rows, n, k, _ptr(dl), rows_per_limit, dv.ptr, di.ptr, dc.ptr, None))
     return dv.numpy(), di.numpy(), dc.numpy()
 
 
