@@ -373,6 +373,60 @@ int isegmi_op_rpn_levels(int nl, const float* const* d_heads, const float* const
                          int32_t* d_ws_cand_idx, float* d_ws_tk_vals, int32_t* d_ws_tk_idx, int32_t* d_ws_tk_cnt, void* d_ws_nms,
                          float* d_out_boxes, float* d_out_scores, int32_t* d_out_cnt, void* stream);
 
+/* ---- RetinaNet tail ([UPSTREAM-RECALL] maskrcnn-benchmark RetinaNetPostProcessor, reached from README.md:344-347 with the retinanet configs) ----
+ * isegmi_op_retina_select: forward_for_single_feature_map for nl <= 5 levels x N images in two launches.  Row (level l, image n) is d_logits[l] + n * HW[l]*A*C,
+ * the cls_logits output as the convolution wrote it: flat index ((y*W + x)*A + a)*C + c.  p = dm_sigmoid(logit) (isegmi_op_map_f32 fn 1); candidates are
+ * p > score_thresh (strict); the min(#candidates, top_n) best are kept, top_n <= 1024, ordered (p desc, flat index asc) -- isegmi_op_topk's key order contract on
+ * the SIGMOID values (two logits may share one).  Every logit is read once; no probability tensor is written; exact for any number of candidates; bitwise
+ * reproducible.  NaN logits are outside the contract.  d_sel_scores / d_sel_idx [N][nl][top_n] (-1 past the count), d_sel_cnt [N][nl].
+ * Decode (d_out_boxes != NULL; then d_deltas[l] [N][HW_l][A*4], d_anchors[l] [HW_l*A][4] and d_image_hw [N][2] (h, w) are read): anchor = idx / C, label =
+ * idx % C + 1, BoxCoder(10, 10, 5, 5) with the legacy +1 widths and the log(1000/16) clamp, clip to (w - 1, h - 1), boxes with a side (+1) under min_size
+ * dropped, selection order kept.  d_out_boxes [N][nl*top_n][4], d_out_scores / d_out_labels [N][nl*top_n] (level l's list starts at l*top_n; -1 / 0 past its
+ * count), d_out_cnt [N][nl].  d_ws: isegmi_op_retina_select_workspace bytes (one list of top_n 8-byte keys per 8192 logits of every row; -1: bad sizes). */
+#define ISEGMI_RETINA_MAX_LEVELS 5
+typedef struct isegmi_retina_select_args {
+    int32_t nl, N, A, C, top_n;
+    float score_thresh, min_size;
+    int32_t HW[ISEGMI_RETINA_MAX_LEVELS];
+    const float* d_logits[ISEGMI_RETINA_MAX_LEVELS];
+    const float* d_deltas[ISEGMI_RETINA_MAX_LEVELS];
+    const float* d_anchors[ISEGMI_RETINA_MAX_LEVELS];
+    const int32_t* d_image_hw;
+    void* d_ws;
+    int64_t ws_bytes;
+    float* d_sel_scores;
+    int32_t* d_sel_idx;
+    int32_t* d_sel_cnt;
+    float* d_out_boxes;
+    float* d_out_scores;
+    int32_t* d_out_labels;
+    int32_t* d_out_cnt;
+} isegmi_retina_select_args;
+int64_t isegmi_op_retina_select_workspace(int nl, int N, const int32_t* HW, int A, int C, int top_n);
+int isegmi_op_retina_select(const isegmi_retina_select_args* a, void* stream);
+/* isegmi_op_retina_postprocess: select_over_all_levels.  Per image nseg lists of seg_len candidate slots (nseg * seg_len <= 8192), the first d_seg_cnt[n][s] of
+ * list s valid -- isegmi_op_retina_select's decode outputs with nseg = nl, seg_len = top_n; a label outside 1..ncls-1 drops its slot.  For every class greedy NMS
+ * over the class's candidates in (score desc, slot asc) order, IoU and threshold as isegmi_op_nms under nms_flags (a box never meets a box of another class: no
+ * coordinate offsets); kept lists concatenated in class order, NMS order inside a class -- slot order with ISEGMI_NMS_INDEX_ORDER; when more than det_per_img > 0
+ * remain, those with score >= the det_per_img-th largest stay; at most cap rows.  Any distribution over the classes, one class may hold every slot.
+ * Outputs as isegmi_box_post_args': d_out_count [N], d_out_boxes [N][cap][4], d_out_scores [N][cap], d_out_labels [N][cap] (zeros past the count). */
+typedef struct isegmi_retina_post_args {
+    int32_t N, nseg, seg_len, ncls, det_per_img, cap, nms_flags;
+    float nms_thresh;
+    const float* d_boxes;        /* [N][nseg*seg_len][4] */
+    const float* d_scores;       /* [N][nseg*seg_len] */
+    const int32_t* d_labels;     /* [N][nseg*seg_len] */
+    const int32_t* d_seg_cnt;    /* [N][nseg] */
+    void* d_ws;                  /* isegmi_op_retina_postprocess_workspace(N, nseg, seg_len) bytes (-1: bad sizes) */
+    int64_t ws_bytes;
+    int32_t* d_out_count;
+    float* d_out_boxes;
+    float* d_out_scores;
+    int32_t* d_out_labels;
+} isegmi_retina_post_args;
+int64_t isegmi_op_retina_postprocess_workspace(int N, int nseg, int seg_len);
+int isegmi_op_retina_postprocess(const isegmi_retina_post_args* a, void* stream);
+
 /* ---- COCO run-length encoding on the device (the on-disk format behind inference() / tools/test_net.py,
  * README.md:344-347, annotation layout README.md:55-66; Yolact eval.py Detections.add_mask / dump, README.md:243-249) ----
  * pycocotools rleEncode + rleToString restated: for every valid slot (n, k), k < d_count[n], of the uint8 planes d_masks [N][K][plane_h][plane_w]
@@ -446,7 +500,7 @@ int isegmi_op_pose2seg_masks(const float* d_logits, const float* d_mmask, const 
  * state-dict names with BN already folded to (scale, shift) by the Python host; activations,
  * workspaces and outputs live in named device buffers owned by the engine. */
 typedef struct isegmi_engine isegmi_engine;
-/* model_kind: 1 = Yolact R50-FPN, 2 = Mask R-CNN R50/R101-FPN, 3 = Pose2Seg (H = W = 512).  H, W = network input size. */
+/* model_kind: 1 = Yolact R50-FPN, 2 = Mask R-CNN R50/R101-FPN, 3 = Pose2Seg (H = W = 512), 4 = RetinaNet R50/R101-FPN.  H, W = network input size. */
 int isegmi_engine_create(int model_kind, int max_batch, int H, int W, isegmi_engine** out);
 int isegmi_engine_destroy(isegmi_engine* e);
 int isegmi_engine_set_param(isegmi_engine* e, const char* name, float value);
@@ -472,6 +526,15 @@ int isegmi_maskrcnn_forward(isegmi_engine* e, const float* d_images_nhwc3, const
  * per-level base anchors as tensors "anchor_base.<l>" [A][4] and the strides as params "anchor_stride<l>"; the grid is laid out on the
  * device for the current canvas (isegmi_op_grid_anchors). */
 int isegmi_maskrcnn_forward_canvas(isegmi_engine* e, const float* d_images_nhwc3, const int32_t* h_image_hw, int N, int H, int W);
+/* RetinaNet (model_kind 4; reached from tools/test_net.py with configs/retinanet_R-*-FPN_1x.yaml, README.md:344-347): the same calling form as
+ * the Mask R-CNN pair -- d_images [N][H][W][3] zero-padded to a multiple of 32, h_image_hw [N][2] unpadded (h, w), one engine for every canvas up to its (H, W),
+ * anchors ("anchor_base.<l>" [9][4], "anchor_stride<l>", l = 0..4 for P3..P7) laid out again when the canvas changes.  Results: det.count [N], det.box
+ * [N][cap][4], det.score / det.label [N][cap] (cap = max(detections_per_img, detections_cap)); P3..P7, retina.logits<l> / retina.deltas<l>, retina.sel_score /
+ * retina.sel_idx [N][5][top_n] with retina.sel_cnt [N][5], retina.cand_* in named buffers.  Params: retina_pre_nms_top_n (<= 1024), retina_inference_th,
+ * retina_nms_th, retina_num_convs, detections_per_img, detections_cap, resnet_depth, nms_ge / nms_plus_one / nms_index_order.  fp32 only: "fp16" and "graph"
+ * are refused by name, and so is a "retina_levels" other than 5. */
+int isegmi_retinanet_forward(isegmi_engine* e, const float* d_images_nhwc3, const int32_t* h_image_hw, int N);
+int isegmi_retinanet_forward_canvas(isegmi_engine* e, const float* d_images_nhwc3, const int32_t* h_image_hw, int N, int H, int W);
 /* Masker paste of the last forward into (out_h,out_w) planes; boxes first scaled by h_ratios_wh [N][2] =
  * (out_w/w_i, out_h/h_i) like BoxList.resize -> det.masks u8 [N][cap][out_h][out_w], det.box_resized */
 int isegmi_maskrcnn_paste(isegmi_engine* e, const float* h_ratios_wh, int out_h, int out_w);

@@ -1,4 +1,4 @@
-// engine.h -- model engine: packed-weight registry, named activation buffers, per-model forward graphs (yolact.cpp, maskrcnn.cpp, pose2seg.cpp).
+// engine.h -- model engine: packed-weight registry, named activation buffers, per-model forward graphs (yolact.cpp, maskrcnn.cpp, pose2seg.cpp, retinanet.cpp).
 #pragma once
 #include "rpn_levels.h"
 #include <stdarg.h>
@@ -50,7 +50,7 @@ struct StageTime {
 constexpr float STEP_OVERLAP_DEFAULT = 1.0f;
 
 struct Engine {
-    int kind = 0;  // 1 yolact, 2 maskrcnn, 3 pose2seg
+    int kind = 0;  // 1 yolact, 2 maskrcnn, 3 pose2seg, 4 retinanet
     int max_batch = 0, H = 0, W = 0;       // H, W: the LARGEST network input (padded canvas) this engine serves
     int cur_H = 0, cur_W = 0;              // Mask R-CNN: padded canvas of the current forward (<= H, W; to_image_list pads each batch to its own size)
     int anchor_H = -1, anchor_W = -1;      // canvas the anchors.* buffers were generated for

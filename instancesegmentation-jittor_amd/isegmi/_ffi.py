@@ -657,6 +657,85 @@ def rpn_levels(heads, anchors, image_hw, A, pre_nms, post_nms, nms_thr=0.7, min_
     return [[(B[i, l, : c[i, l]], S[i, l, : c[i, l]]) for i in range(N)] for l in range(nl)]
 
 
+# ---------------------------------------------------------------- RetinaNet tail
+RETINA_MAX_LEVELS = 5
+
+
+class RetinaSelectArgs(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("nl", "N", "A", "C", "top_n")] + [("score_thresh", C.c_float), ("min_size", C.c_float),
+               ("HW", C.c_int32 * RETINA_MAX_LEVELS), ("d_logits", C.c_void_p * RETINA_MAX_LEVELS), ("d_deltas", C.c_void_p * RETINA_MAX_LEVELS),
+               ("d_anchors", C.c_void_p * RETINA_MAX_LEVELS), ("d_image_hw", C.c_void_p), ("d_ws", C.c_void_p), ("ws_bytes", C.c_int64)] + \
+               [(n, C.c_void_p) for n in ("d_sel_scores", "d_sel_idx", "d_sel_cnt", "d_out_boxes", "d_out_scores", "d_out_labels", "d_out_cnt")]
+
+
+class RetinaPostArgs(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("N", "nseg", "seg_len", "ncls", "det_per_img", "cap", "nms_flags")] + [("nms_thresh", C.c_float)] + \
+               [(n, C.c_void_p) for n in ("d_boxes", "d_scores", "d_labels", "d_seg_cnt", "d_ws")] + [("ws_bytes", C.c_int64)] + \
+               [(n, C.c_void_p) for n in ("d_out_count", "d_out_boxes", "d_out_scores", "d_out_labels")]
+
+
+def retina_select(logits, A, top_n, score_thr=0.05, deltas=None, anchors=None, image_hw=None, min_size=0.0):
+    """isegmi_op_retina_select: logits[l] [N,H_l,W_l,A*C] -> per level a list over images of (scores, flat indices); with deltas[l] [N,H_l,W_l,A*4],
+    anchors[l] [H_l*W_l*A,4] and image_hw [N,2] also the decoded lists: (sel, dec) with dec[l][i] = (boxes, scores, labels)."""
+    nl = len(logits)
+    lg = [np.ascontiguousarray(x, np.float32) for x in logits]
+    N = lg[0].shape[0]
+    Cc = lg[0].shape[3] // A
+    a = RetinaSelectArgs()
+    a.nl, a.N, a.A, a.C, a.top_n = nl, N, A, Cc, top_n
+    a.score_thresh, a.min_size = score_thr, min_size
+    keep = [DeviceBuffer.from_numpy(x) for x in lg]
+    for l in range(nl):
+        a.HW[l] = lg[l].shape[1] * lg[l].shape[2]
+        a.d_logits[l] = keep[l].ptr.value
+    lib().isegmi_op_retina_select_workspace.restype = C.c_int64
+    wsb = lib().isegmi_op_retina_select_workspace(nl, N, a.HW, A, Cc, top_n)
+    if wsb < 0:
+        raise IsegmiError("isegmi_op_retina_select_workspace: bad sizes")
+    ws = DeviceBuffer((wsb,), np.uint8).poison()
+    a.d_ws, a.ws_bytes = ws.ptr, wsb
+    ss = DeviceBuffer((N, nl, top_n)).poison(); si = DeviceBuffer((N, nl, top_n), np.int32).poison(); sc = DeviceBuffer((N, nl), np.int32).poison()
+    a.d_sel_scores, a.d_sel_idx, a.d_sel_cnt = ss.ptr, si.ptr, sc.ptr
+    dec = deltas is not None
+    if dec:
+        keep += [DeviceBuffer.from_numpy(np.ascontiguousarray(x, np.float32)) for x in deltas]
+        keep += [DeviceBuffer.from_numpy(np.ascontiguousarray(x, np.float32)) for x in anchors]
+        for l in range(nl):
+            a.d_deltas[l] = keep[nl + l].ptr.value
+            a.d_anchors[l] = keep[2 * nl + l].ptr.value
+        dhw = DeviceBuffer.from_numpy(np.ascontiguousarray(image_hw, np.int32))
+        ob = DeviceBuffer((N, nl * top_n, 4)).poison(); os_ = DeviceBuffer((N, nl * top_n)).poison()
+        ol = DeviceBuffer((N, nl * top_n), np.int32).poison(); oc = DeviceBuffer((N, nl), np.int32).poison()
+        a.d_image_hw, a.d_out_boxes, a.d_out_scores, a.d_out_labels, a.d_out_cnt = dhw.ptr, ob.ptr, os_.ptr, ol.ptr, oc.ptr
+    check(lib().isegmi_op_retina_select(C.byref(a), None))
+    c = sc.numpy(); S = ss.numpy(); I = si.numpy()
+    assert (S[np.arange(top_n)[None, None, :] >= c[:, :, None]] == -1).all() and (I[np.arange(top_n)[None, None, :] >= c[:, :, None]] == -1).all()
+    sel = [[(S[i, l, : c[i, l]], I[i, l, : c[i, l]]) for i in range(N)] for l in range(nl)]
+    if not dec:
+        return sel
+    c = oc.numpy(); B = ob.numpy().reshape(N, nl, top_n, 4); S = os_.numpy().reshape(N, nl, top_n); Lb = ol.numpy().reshape(N, nl, top_n)
+    return sel, [[(B[i, l, : c[i, l]], S[i, l, : c[i, l]], Lb[i, l, : c[i, l]]) for i in range(N)] for l in range(nl)]
+
+
+def retina_postprocess(boxes, scores, labels, seg_cnt, ncls=81, nms_thr=0.4, det_per_img=100, cap=128, nms_flags=0):
+    """isegmi_op_retina_postprocess: boxes [N,nseg,seg_len,4], scores / labels [N,nseg,seg_len], seg_cnt [N,nseg] -> list of (boxes, scores, labels)."""
+    boxes = np.ascontiguousarray(boxes, np.float32)
+    N, nseg, seg_len, _ = boxes.shape
+    cap = max(det_per_img, cap)
+    db = DeviceBuffer.from_numpy(boxes); ds = DeviceBuffer.from_numpy(np.ascontiguousarray(scores, np.float32))
+    dl = DeviceBuffer.from_numpy(np.ascontiguousarray(labels, np.int32)); dc = DeviceBuffer.from_numpy(np.ascontiguousarray(seg_cnt, np.int32))
+    lib().isegmi_op_retina_postprocess_workspace.restype = C.c_int64
+    wsb = lib().isegmi_op_retina_postprocess_workspace(N, nseg, seg_len)
+    if wsb < 0:
+        raise IsegmiError("isegmi_op_retina_postprocess_workspace: bad sizes")
+    ws = DeviceBuffer((wsb,), np.uint8).poison()   # dirty on purpose: nothing may be read before it is written
+    oc = DeviceBuffer((N,), np.int32).poison(); ob = DeviceBuffer((N, cap, 4)).poison(); os_ = DeviceBuffer((N, cap)).poison(); ol = DeviceBuffer((N, cap), np.int32).poison()
+    a = RetinaPostArgs(N, nseg, seg_len, ncls, det_per_img, cap, nms_flags, nms_thr, db.ptr, ds.ptr, dl.ptr, dc.ptr, ws.ptr, wsb, oc.ptr, ob.ptr, os_.ptr, ol.ptr)
+    check(lib().isegmi_op_retina_postprocess(C.byref(a), None))
+    c = oc.numpy(); B = ob.numpy(); S = os_.numpy(); Lb = ol.numpy()
+    return [(B[i, : c[i]], S[i, : c[i]], Lb[i, : c[i]]) for i in range(N)]
+
+
 # ---------------------------------------------------------------- fp16 conv (configs[4])
 def pack_conv_weights_f16(desc, w_krsc):
     w = np.ascontiguousarray(w_krsc, np.float32)

@@ -34,8 +34,10 @@ def _save_image_bgr(path, img):
 
 
 def _weights(spec, kind, depth=50, ycfg=None, gn=False):
-    from .weights import maskrcnn_state_dict, yolact_state_dict
+    from .weights import maskrcnn_state_dict, retinanet_state_dict, yolact_state_dict
     if spec in ("", "random", None):
+        if kind == "retinanet":
+            return retinanet_state_dict(1234, depth)
         if kind == "maskrcnn" and gn:
             return maskrcnn_state_dict(1234, depth, gn=True)
         if kind == "yolact" and ycfg is not None:
@@ -122,16 +124,18 @@ def cmd_eval(a):
 
 def cmd_test_net(a):
     """tools/test_net.py: build the model from the yaml, run inference() over the images, write COCO-format json."""
-    from .config import cfg, to_maskrcnn_config
+    from .config import cfg, is_retinanet, to_maskrcnn_config, to_retinanet_config
     from .predictor import COCODemo, inference
     c = cfg.clone()
     if a.config_file:
         c.merge_from_file(a.config_file)
     c.merge_from_list(a.opts)
-    mc = to_maskrcnn_config(c)
+    retina = is_retinanet(c)   # MODEL.RETINANET_ON: the one-stage detector, bbox results only
+    mc = to_retinanet_config(c) if retina else to_maskrcnn_config(c)
     rank, world, local = _rank_world()
     files = sorted(os.path.join(a.images, f) for f in os.listdir(a.images)) if a.images else []
-    demo = COCODemo(mc, min_image_size=mc.MIN_SIZE_TEST, confidence_threshold=0.0, state_dict=_weights(c.MODEL.WEIGHT, "maskrcnn", mc.depth, gn=mc.USE_GN),
+    sd = _weights(c.MODEL.WEIGHT, "retinanet", mc.depth) if retina else _weights(c.MODEL.WEIGHT, "maskrcnn", mc.depth, gn=mc.USE_GN)
+    demo = COCODemo(mc, min_image_size=mc.MIN_SIZE_TEST, confidence_threshold=0.0, state_dict=sd,
                     max_image_size=mc.MAX_SIZE_TEST, device=local, max_batch=a.batch_size)
     stats = {}
     results = inference(demo, lambda i: _load_image_bgr(files[i]), batch_size=a.batch_size, group=a.group, rank=rank, world=world,
@@ -143,7 +147,7 @@ def cmd_test_net(a):
         print("wrote %d results for %d images to %s (%d steps of %d images on %d rank(s))" % (
             len(results), len(files), a.output, stats.get("steps", 0), a.batch_size, world))
         if a.gt:
-            _print_coco_summary(a.gt, results, ("bbox", "segm"))
+            _print_coco_summary(a.gt, results, ("bbox",) if retina else ("bbox", "segm"))
     return results
 
 

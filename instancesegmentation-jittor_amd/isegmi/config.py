@@ -70,7 +70,8 @@ def _defaults():
     c._merge({
         "INPUT": {"MIN_SIZE_TEST": 800, "MAX_SIZE_TEST": 1333, "PIXEL_MEAN": (102.9801, 115.9465, 122.7717), "TO_BGR255": True},
         "DATALOADER": {"SIZE_DIVISIBILITY": 32},
-        "MODEL": {"META_ARCHITECTURE": "GeneralizedRCNN", "WEIGHT": "", "MASK_ON": True,
+        "TEST": {"DETECTIONS_PER_IMG": 100},
+        "MODEL": {"META_ARCHITECTURE": "GeneralizedRCNN", "WEIGHT": "", "MASK_ON": True, "RETINANET_ON": False,
                   "BACKBONE": {"CONV_BODY": "R-50-FPN"},
                   # [UPSTREAM-RECALL] maskrcnn-benchmark defaults.py
                   "GROUP_NORM": {"DIM_PER_GP": -1, "NUM_GROUPS": 32, "EPSILON": 1e-5},
@@ -83,7 +84,11 @@ def _defaults():
                           "ASPECT_RATIOS": (0.5, 1.0, 2.0), "PRE_NMS_TOP_N_TEST": 1000, "POST_NMS_TOP_N_TEST": 1000,
                           "FPN_POST_NMS_TOP_N_TEST": 1000, "NMS_THRESH": 0.7, "MIN_SIZE": 0},
                   "ROI_HEADS": {"SCORE_THRESH": 0.05, "NMS": 0.5, "DETECTIONS_PER_IMG": 100},
-                  "ROI_MASK_HEAD": {"PREDICTOR": "MaskRCNNC4Predictor", "RESOLUTION": 28, "USE_GN": False, "DILATION": 1}},
+                  "ROI_MASK_HEAD": {"PREDICTOR": "MaskRCNNC4Predictor", "RESOLUTION": 28, "USE_GN": False, "DILATION": 1},
+                  # [UPSTREAM-RECALL] maskrcnn-benchmark defaults.py, MODEL.RETINANET
+                  "RETINANET": {"NUM_CLASSES": 81, "ANCHOR_SIZES": (32, 64, 128, 256, 512), "ASPECT_RATIOS": (0.5, 1.0, 2.0),
+                                "ANCHOR_STRIDES": (8, 16, 32, 64, 128), "STRADDLE_THRESH": 0, "OCTAVE": 2.0, "SCALES_PER_OCTAVE": 3, "USE_C5": True,
+                                "NUM_CONVS": 4, "PRIOR_PROB": 0.01, "INFERENCE_TH": 0.05, "NMS_TH": 0.4, "PRE_NMS_TOP_N": 1000}},
     })
     return c
 
@@ -178,3 +183,56 @@ def to_maskrcnn_config(c):
                           RPN_FPN_POST_NMS_TOP_N_TEST=int(r.FPN_POST_NMS_TOP_N_TEST), RPN_NMS_THRESH=float(r.NMS_THRESH),
                           RPN_MIN_SIZE=float(r.MIN_SIZE), ROI_SCORE_THRESH=float(h.SCORE_THRESH), ROI_NMS=float(h.NMS),
                           DETECTIONS_PER_IMG=int(h.DETECTIONS_PER_IMG), **norm)
+
+
+RETINANET_BODIES = ("R-50-FPN-RETINANET", "R-101-FPN-RETINANET")
+
+
+def is_retinanet(c):
+    """True for a yaml-keyed node that asks for the one-stage detector (MODEL.RETINANET_ON)."""
+    return _bool(c.MODEL.get("RETINANET_ON", False))
+
+
+def to_retinanet_config(c):
+    """The yaml-keyed node of a retinanet/retinanet_R-*-FPN_1x.yaml -> RetinaNetConfig; raises, naming the key, for everything that is not built
+    (DESIGN.md 7 and 12)."""
+    from .retinanet import RETINA_MAX_TOP_N, RetinaNetConfig
+    m = c.MODEL
+    r, rn = m.RETINANET, m.RESNETS
+    if not is_retinanet(c):
+        raise ValueError("MODEL.RETINANET_ON=False: not a RetinaNet config (to_maskrcnn_config maps the two-stage models)")
+    if _bool(m.MASK_ON):
+        raise ValueError("MODEL.MASK_ON=True together with MODEL.RETINANET_ON: RetinaMask is not built, set MODEL.MASK_ON: False")
+    body = str(m.BACKBONE.CONV_BODY)
+    if body not in RETINANET_BODIES:
+        raise ValueError("MODEL.BACKBONE.CONV_BODY=%r: built RetinaNet bodies are %s" % (body, ", ".join(RETINANET_BODIES)))
+    if not _bool(r.USE_C5):
+        raise ValueError("MODEL.RETINANET.USE_C5=False (P6 from P5) is not built: LastLevelP6P7 reads C5")
+    if int(r.NUM_CONVS) < 1:
+        raise ValueError("MODEL.RETINANET.NUM_CONVS=%s: at least one tower convolution" % r.NUM_CONVS)
+    if int(r.NUM_CLASSES) != 81:
+        raise ValueError("MODEL.RETINANET.NUM_CLASSES=%s: built for the 80 COCO classes (81)" % r.NUM_CLASSES)
+    for key, on in (("MODEL.RESNETS.TRANS_FUNC", str(rn.TRANS_FUNC) != "BottleneckWithFixedBatchNorm"),
+                    ("MODEL.RESNETS.STEM_FUNC", str(rn.STEM_FUNC) != "StemWithFixedBatchNorm"), ("MODEL.FPN.USE_GN", _bool(m.FPN.USE_GN))):
+        if on:
+            raise ValueError("%s: RetinaNet with GroupNorm is not built (FrozenBatchNorm trunk, plain FPN)" % key)
+    if _bool(m.FPN.USE_RELU):
+        raise ValueError("MODEL.FPN.USE_RELU=True is not built")
+    if not _bool(rn.STRIDE_IN_1X1):
+        raise ValueError("MODEL.RESNETS.STRIDE_IN_1X1=False is built for the GroupNorm Mask R-CNN only")
+    if int(rn.RES5_DILATION) != 1:
+        raise ValueError("MODEL.RESNETS.RES5_DILATION=%s: dilated convolutions are not built" % rn.RES5_DILATION)
+    sizes, strides = tuple(r.ANCHOR_SIZES), tuple(r.ANCHOR_STRIDES)
+    if len(sizes) != 5 or len(strides) != 5 or tuple(int(s) for s in strides) != (8, 16, 32, 64, 128):
+        raise ValueError("MODEL.RETINANET.ANCHOR_STRIDES=%r / ANCHOR_SIZES=%r: the P3-P7 pyramid (strides 8..128, five sizes) is the one built" % (strides, sizes))
+    if not 1 <= int(r.PRE_NMS_TOP_N) <= RETINA_MAX_TOP_N:
+        raise ValueError("MODEL.RETINANET.PRE_NMS_TOP_N=%s: the selection kernels hold 1..%d per level" % (r.PRE_NMS_TOP_N, RETINA_MAX_TOP_N))
+    if int(c.DATALOADER.SIZE_DIVISIBILITY) <= 0 or int(c.DATALOADER.SIZE_DIVISIBILITY) % 32:
+        raise ValueError("DATALOADER.SIZE_DIVISIBILITY=%s: the RetinaNet pyramid needs a multiple of 32" % c.DATALOADER.SIZE_DIVISIBILITY)
+    if int(c.TEST.DETECTIONS_PER_IMG) < 1:
+        raise ValueError("TEST.DETECTIONS_PER_IMG=%s: at least 1" % c.TEST.DETECTIONS_PER_IMG)
+    return RetinaNetConfig(depth=101 if "101" in body else 50, CONV_BODY=body, MIN_SIZE_TEST=int(c.INPUT.MIN_SIZE_TEST), MAX_SIZE_TEST=int(c.INPUT.MAX_SIZE_TEST),
+                           SIZE_DIVISIBILITY=int(c.DATALOADER.SIZE_DIVISIBILITY), NUM_CLASSES=81, ANCHOR_SIZES=tuple(int(s) for s in sizes),
+                           ANCHOR_STRIDES=tuple(int(s) for s in strides), ASPECT_RATIOS=tuple(float(x) for x in r.ASPECT_RATIOS), OCTAVE=float(r.OCTAVE),
+                           SCALES_PER_OCTAVE=int(r.SCALES_PER_OCTAVE), NUM_CONVS=int(r.NUM_CONVS), PRE_NMS_TOP_N=int(r.PRE_NMS_TOP_N),
+                           INFERENCE_TH=float(r.INFERENCE_TH), NMS_TH=float(r.NMS_TH), DETECTIONS_PER_IMG=int(c.TEST.DETECTIONS_PER_IMG))

@@ -20,16 +20,21 @@ class COCODemo:
 
     def __init__(self, cfg=None, min_image_size=800, confidence_threshold=0.5, state_dict=None, max_image_size=1333, device=0, max_batch=2,
                  fp16=False):
-        if cfg is not None and not isinstance(cfg, MaskRCNNConfig):   # the yacs-shaped node of isegmi.config (README.md:313-324)
-            from .config import to_maskrcnn_config
+        from .retinanet import RetinaNetConfig
+        if cfg is not None and not isinstance(cfg, (MaskRCNNConfig, RetinaNetConfig)):   # the yacs-shaped node of isegmi.config (README.md:313-324)
+            from .config import is_retinanet, to_maskrcnn_config, to_retinanet_config
+            retina = is_retinanet(cfg)
             if state_dict is None and getattr(cfg.MODEL, "WEIGHT", ""):
                 w = cfg.MODEL.WEIGHT
-                from .weights import maskrcnn_c4_state_dict, maskrcnn_state_dict
+                from .weights import maskrcnn_c4_state_dict, maskrcnn_state_dict, retinanet_state_dict
                 body = cfg.MODEL.BACKBONE.CONV_BODY
-                rnd = (lambda: maskrcnn_c4_state_dict(1234)) if body.endswith("-C4") else (lambda: maskrcnn_state_dict(1234, 101 if "101" in body else 50))
+                depth = 101 if "101" in body else 50
+                rnd = (lambda: retinanet_state_dict(1234, depth)) if retina else \
+                    (lambda: maskrcnn_c4_state_dict(1234)) if body.endswith("-C4") else (lambda: maskrcnn_state_dict(1234, depth))
                 state_dict = rnd() if w == "random" else dict(np.load(w))
-            cfg = to_maskrcnn_config(cfg)
+            cfg = to_retinanet_config(cfg) if retina else to_maskrcnn_config(cfg)
         self.cfg = cfg or MaskRCNNConfig()
+        self.is_retinanet = isinstance(self.cfg, RetinaNetConfig)   # MODEL.RETINANET_ON: boxes, scores and labels; no masks
         if state_dict is None:
             raise ValueError("COCODemo needs weights: pass state_dict=... or set cfg.MODEL.WEIGHT to an .npz (or 'random'); "
                              "the reference's download URLs (README.md:266) cannot be fetched here")
@@ -49,16 +54,22 @@ class COCODemo:
         if self._model is None:
             d = self.cfg.SIZE_DIVISIBILITY
             m = -(-max(self.max_image_size, self.min_image_size) // d) * d
-            self._model = MaskRCNN(self.state_dict, m, m, cfg=self.cfg, max_batch=want, device=self.device, fp16=self.fp16)
+            if self.is_retinanet:
+                from .retinanet import RetinaNet
+                self._model = RetinaNet(self.state_dict, m, m, cfg=self.cfg, max_batch=want, device=self.device, fp16=self.fp16)
+            else:
+                self._model = MaskRCNN(self.state_dict, m, m, cfg=self.cfg, max_batch=want, device=self.device, fp16=self.fp16)
             self.memory = self._model.reserve()  # (weight bytes, activation / workspace bytes): the predictor's peak device memory
         return self._model
 
     def compute_prediction(self, original_image):
-        """-> BoxList in ORIGINAL image coordinates with scores, labels and mask [n,1,H,W] uint8 (Masker output)."""
+        """-> BoxList in ORIGINAL image coordinates with scores, labels and mask [n,1,H,W] uint8 (Masker output); RetinaNet: no mask field."""
         h, w = original_image.shape[:2]
         resized = maskrcnn_resize_u8(original_image, self.min_image_size, self.max_image_size)
         model = self.engine()
         (pred,) = model([resized])  # device front end: the bytes cross PCIe, mean subtraction + padding (to_image_list) run on the GPU
+        if self.is_retinanet:
+            return pred.resize((w, h))
         model.paste_device(h, w, [(w, h)])
         model.sync()
         n = len(pred)
@@ -138,6 +149,8 @@ def inference(predictor, images, image_ids=None, batch_size=None, group="canvas"
     workers: host threads that load + resize (PIL, which releases the GIL) the NEXT batch while the current one is enqueued and the previous
             one's records are unpacked; 0 = inline."""
     import time
+    if getattr(predictor, "is_retinanet", False):
+        return _inference_boxes(predictor, images, image_ids, batch_size, group, rank, world, sizes, stats, workers)
     from .coco import results_from_records
     from .pipeline import record_capacity, run_record_loop, schedule_batches
     from .transforms import get_size
@@ -230,4 +243,104 @@ def inference(predictor, images, image_ids=None, batch_size=None, group="canvas"
             p.free()
     if stats is not None:
         stats.update(steps=nsteps, images=n_img, seconds=time.perf_counter() - t0, batches=len(batches), batch_size=bs, world=world)
+    return [d for r in per_image if r for d in r]
+
+
+def _inference_boxes(predictor, images, image_ids, batch_size, group, rank, world, sizes, stats, workers):
+    """inference() for a detector without masks (RetinaNet): bbox-only COCO results -- xywh with the legacy +1, no `segmentation` key.  Per step the four
+    fixed-size detection buffers come back through the engine's two asynchronous download slots into pinned memory; step t's download and step t + 1's
+    upload + forward are enqueued before step t's results are unpacked, so the host work hides under the device's."""
+    import time
+    from .coco import maskrcnn_results
+    from .maskrcnn import BoxList, padded_canvas
+    from .pipeline import schedule_batches
+    from .transforms import get_size
+    from . import _ffi
+    if world > 1:
+        raise ValueError("inference(): world=%d for a RetinaNet predictor -- the gathered record block carries masks; multi-rank runs are not built for this model" % world)
+    get = images if callable(images) else images.__getitem__
+    if sizes is None:
+        if callable(images):
+            raise ValueError("inference(): a callable image source needs sizes=[(h, w), ...]")
+        sizes = [im.shape[:2] for im in images]
+    n_img = len(sizes)
+    ids = list(image_ids) if image_ids is not None else list(range(n_img))
+    bs = int(batch_size or predictor.max_batch)
+    model = predictor.engine(bs)
+    cfg = predictor.cfg
+    rs = [get_size(w, h, predictor.min_image_size, predictor.max_image_size) for h, w in sizes]
+    if group == "canvas":
+        keys = [padded_canvas([r], cfg.SIZE_DIVISIBILITY) for r in rs]
+    elif group == "aspect":
+        keys = [int(h >= w) for h, w in sizes]
+    else:
+        raise ValueError("group: 'canvas' or 'aspect'")
+    batches = schedule_batches(keys, bs)
+    pin = [_ffi.PinnedBuffer((bs * model.H * model.W * 3,), np.uint8) for _ in range(2)]
+    out_pin = [_ffi.PinnedBuffer((model.detection_bytes(bs),), np.uint8) for _ in range(2)]
+    for slot in (0, 1):
+        model._u8_staging(slot, bs * model.H * model.W * 3)
+    per_image = [None] * n_img
+
+    def load(i):
+        return maskrcnn_resize_u8(get(i), predictor.min_image_size, predictor.max_image_size)
+    pool = None
+    if workers and workers > 0:
+        from concurrent.futures import ThreadPoolExecutor
+        pool = ThreadPoolExecutor(max_workers=int(workers))
+    prefetch = {}
+
+    def request(j):
+        if j < len(batches) and j not in prefetch:
+            prefetch[j] = [pool.submit(load, i) for i in batches[j]] if pool else None
+
+    def enqueue(j):
+        slot = j & 1
+        b = batches[j]
+        request(j + 1)
+        futs = prefetch.pop(j, None)
+        resized = [f.result() for f in futs] if futs else [load(i) for i in b]
+        off, hw = 0, []
+        for im in resized:
+            pin[slot].array[off:off + im.size] = im.reshape(-1)
+            off += im.size
+            hw.append(im.shape[:2])
+        model.upload_u8_async(pin[slot], hw, slot)
+        model.forward_device(len(b), slot)
+        model.download_detections_async(slot, out_pin[slot], bs)
+        return hw
+
+    def consume(j, hw):
+        slot = j & 1
+        model.download_wait(slot)
+        cnt, box, score, label = model.unpack_detections(out_pin[slot], bs)
+        for k, i in enumerate(batches[j]):
+            c = int(cnt[k])
+            h, w = sizes[i]
+            bl = BoxList(box[k, :c], (int(hw[k][1]), int(hw[k][0]))).resize((w, h))
+            per_image[i] = maskrcnn_results(ids[i], bl.bbox, score[k, :c], label[k, :c])
+
+    t0 = time.perf_counter()
+    try:
+        if batches:
+            request(0)
+        prev = None
+        for j in range(len(batches)):
+            hw = enqueue(j)
+            if prev is not None:
+                consume(*prev)
+            prev = (j, hw)
+        if prev is not None:
+            consume(*prev)
+        model.sync()
+    finally:
+        if pool:
+            pool.shutdown(wait=True, cancel_futures=True)
+        try:
+            model.sync()
+        finally:
+            for p in pin + out_pin:
+                p.free()
+    if stats is not None:
+        stats.update(steps=len(batches), images=n_img, seconds=time.perf_counter() - t0, batches=len(batches), batch_size=bs, world=world)
     return [d for r in per_image if r for d in r]

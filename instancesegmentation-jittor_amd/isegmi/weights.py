@@ -262,6 +262,46 @@ def maskrcnn_state_dict(seed=1234, depth=50, gn=False):
     return sd
 
 
+# Recorded calibration of the RetinaNet predictors (found with the CPU reference tests/retinanet_ref.py on the seeded 256 x 352 test canvas of
+# tests/maskrcnn_gn_common.small_images): the tail must see all of its cases at once -- a (level, image) with more than PRE_NMS_TOP_N candidates, one
+# with a few, more than DETECTIONS_PER_IMG detections before the cut, several classes.  The class bias plays the part of upstream's prior-probability
+# initialisation (-log((1 - pi) / pi)); a per-class spread keeps some classes above the others.
+RETINA_CLS_GAIN = 0.0003
+RETINA_CLS_BIAS = -4.5
+RETINA_CLS_BIAS_SPREAD = 0.5
+RETINA_BBOX_GAIN = 0.0004
+
+
+def retinanet_state_dict(seed=1234, depth=50, num_convs=4, cls_bias=None):
+    """[UPSTREAM-RECALL] maskrcnn-benchmark retinanet_R-50/101-FPN state-dict names: backbone.body.* (the FrozenBN trunk), backbone.fpn.fpn_inner{2,3,4} /
+    fpn_layer{2,3,4} (C2 has neither), backbone.fpn.top_blocks.{p6,p7}, rpn.head.cls_tower.{0,2,4,6} / bbox_tower.{0,2,4,6} (the odd indices are the
+    ReLUs), rpn.head.cls_logits (9 x 80) and rpn.head.bbox_pred (9 x 4).  cls_bias: the constant part of the cls_logits bias (default RETINA_CLS_BIAS)."""
+    rng = np.random.default_rng(seed)
+    sd = {}
+    tmp = {}
+    resnet_state_dict(rng, tmp, "", blocks=(3, 4, 23 if depth == 101 else 6, 3))
+    for k, v in tmp.items():
+        if k.startswith("conv1.") or k.startswith("bn1."):
+            sd["backbone.body.stem." + k] = v
+        else:
+            parts = k.split(".")
+            sd["backbone.body.layer%d.%s" % (int(parts[1]) + 1, ".".join(parts[2:]))] = v
+    for i, cin in ((2, 512), (3, 1024), (4, 2048)):
+        _conv_bias(rng, sd, "backbone.fpn.fpn_inner%d" % i, 256, cin, 1)
+        _conv_bias(rng, sd, "backbone.fpn.fpn_layer%d" % i, 256, 256, 3)
+    _conv_bias(rng, sd, "backbone.fpn.top_blocks.p6", 256, 2048, 3)
+    _conv_bias(rng, sd, "backbone.fpn.top_blocks.p7", 256, 256, 3)
+    for i in range(num_convs):
+        _conv_bias(rng, sd, "rpn.head.cls_tower.%d" % (2 * i), 256, 256, 3)
+        _conv_bias(rng, sd, "rpn.head.bbox_tower.%d" % (2 * i), 256, 256, 3)
+    _conv_bias(rng, sd, "rpn.head.cls_logits", 9 * 80, 256, 3, gain=RETINA_CLS_GAIN)
+    _conv_bias(rng, sd, "rpn.head.bbox_pred", 9 * 4, 256, 3, gain=RETINA_BBOX_GAIN)
+    b = sd["rpn.head.cls_logits.bias"].reshape(9, 80)
+    b += np.float32(RETINA_CLS_BIAS if cls_bias is None else cls_bias)
+    b += (rng.standard_normal(80) * RETINA_CLS_BIAS_SPREAD).astype(np.float32)[None, :]
+    return sd
+
+
 # Recorded calibration of the R-50-C4 heads on the seeded uniform(0,255) image (same intent as above: about a thousand
 # proposals out of the 6000 pre-NMS candidates and about a hundred detections above 0.05).
 C4_RPN_CLS_GAIN = 0.0012

@@ -2,7 +2,7 @@
 upstream key names isegmi.yolact.Yolact / isegmi.maskrcnn.MaskRCNN consume.
 
     python tools/import_pth.py IN OUT.npz [--family maskrcnn_r50_fpn|maskrcnn_r101_fpn|maskrcnn_r50_c4|maskrcnn_r50_fpn_gn|yolact_resnet50|yolact_base|
-                                                    yolact_im700|yolact_darknet53|yolact_plus_resnet50|yolact_plus_base]
+                                                    yolact_im700|yolact_darknet53|yolact_plus_resnet50|yolact_plus_base|retinanet_r50_fpn|retinanet_r101_fpn]
 
 Accepted inputs (torch is used HERE only to unpickle -- a tool, not the product):
   * dbolya/yolact `.pth` (the tables at README.md:209-221): a flat state dict; `module.` prefixes, `num_batches_tracked`, the
@@ -31,7 +31,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "instancesegmentation-jittor_amd")]
 
 FAMILIES = ("maskrcnn_r50_fpn", "maskrcnn_r101_fpn", "maskrcnn_r50_c4", "maskrcnn_r50_fpn_gn", "yolact_resnet50", "yolact_base", "yolact_im700",
-            "yolact_darknet53", "yolact_plus_resnet50", "yolact_plus_base")
+            "yolact_darknet53", "yolact_plus_resnet50", "yolact_plus_base", "retinanet_r50_fpn", "retinanet_r101_fpn")
 
 
 def expected_keys(family):
@@ -48,6 +48,9 @@ def expected_keys(family):
         # [UPSTREAM-RECALL] gn_baselines/e2e_mask_rcnn_R_50_FPN_1x_gn: GroupNorm where the FrozenBN sat (weight / bias only), Sequential(conv, GN)
         # for fpn_innerK / fpn_layerK / mask_fcnK (`.0.weight`, `.1.weight`, `.1.bias`), box head xconvs.{0,3,6,9} / {1,4,7,10} + fc6
         sd = W.maskrcnn_state_dict(0, 50, gn=True)
+    elif family in ("retinanet_r50_fpn", "retinanet_r101_fpn"):
+        # [UPSTREAM-RECALL] retinanet/retinanet_R-50/101-FPN_1x: fpn_inner / fpn_layer 2..4, top_blocks.p6 / p7, rpn.head.{cls,bbox}_tower, cls_logits, bbox_pred
+        sd = W.retinanet_state_dict(0, 101 if "101" in family else 50)
     else:
         cfg = {"yolact_resnet50": YolactConfig(), "yolact_base": YolactConfig.base(), "yolact_im700": YolactConfig.im700(),
                "yolact_darknet53": YolactConfig.darknet53(), "yolact_plus_resnet50": YolactConfig.plus_resnet50(),
