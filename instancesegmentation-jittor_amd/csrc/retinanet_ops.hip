@@ -23,6 +23,7 @@
 #include "../../include/isegmi.h"
 #include "common.h"
 #include "detmath.h"
+#include <float.h>
 #include <math.h>
 
 namespace isegmi {
@@ -184,7 +185,7 @@ __global__ __launch_bounds__(RETINA_NT) void retina_slice_kernel(const RetinaSel
         const int i = tid + q * RETINA_NT;
         const float v = i < n ? x[i] : 0.0f;
         unsigned u = 0u;
-        if (i < n && v > a.prefilter) {
+        if (i < n && v >= a.prefilter) {   // >=: without a pre-filter (-inf) a -inf logit still reaches the sigmoid test; a NaN never passes either test
             const float p = dm_sigmoid(v);
             if (p > a.thr) u = r_f2ord(p);
         }
@@ -559,9 +560,10 @@ int retina_select_launch(const isegmi_retina_select_args* p, hipStream_t st) {
     RetinaSelect a;
     a.nl = p->nl; a.N = p->N; a.C = p->C; a.top_n = p->top_n;
     a.thr = p->score_thresh; a.min_size = p->min_size;
-    // a logit can pass only if its sigmoid can: x > logit(thr), with a margin far above dm_sigmoid's few-ulp error.  The selection itself compares dm_sigmoid(x).
+    // a logit can pass only if its sigmoid can: x > logit(thr), with a margin far above dm_sigmoid's few-ulp error.  The selection itself compares dm_sigmoid(x),
+    // which never reaches 0 (it floors at 4.156e-39, for -inf too): under a threshold below the normal floats every number may pass, so there is no pre-filter.
     a.prefilter = -INFINITY;
-    if (p->score_thresh > 0.0f && p->score_thresh < 1.0f) a.prefilter = logf(p->score_thresh / (1.0f - p->score_thresh)) - 0.25f;
+    if (p->score_thresh >= FLT_MIN && p->score_thresh < 1.0f) a.prefilter = logf(p->score_thresh / (1.0f - p->score_thresh)) - 0.25f;
     int blk = 0;
     int64_t lists = 0;
     for (int l = 0; l < p->nl; ++l) {

@@ -714,6 +714,8 @@ def retina_select(logits, A, top_n, score_thr=0.05, deltas=None, anchors=None, i
     if not dec:
         return sel
     c = oc.numpy(); B = ob.numpy().reshape(N, nl, top_n, 4); S = os_.numpy().reshape(N, nl, top_n); Lb = ol.numpy().reshape(N, nl, top_n)
+    past = np.arange(top_n)[None, None, :] >= c[:, :, None]   # the rows past a count are filled: zero box, score -1, label 0
+    assert (S[past] == -1).all() and (Lb[past] == 0).all() and not B[past].any()
     return sel, [[(B[i, l, : c[i, l]], S[i, l, : c[i, l]], Lb[i, l, : c[i, l]]) for i in range(N)] for l in range(nl)]
 
 

@@ -203,11 +203,319 @@ def post_cases():
 
 
 def pack_post(case, rng=None):
-    """-> boxes [N,nseg,seg_len,4], scores, labels, seg_cnt [N,nseg]"""
+    """-> boxes [N,nseg,seg_len,4], scores, labels, seg_cnt [N,nseg].  case["garbage"]: labels written round-robin into the slots past the counts (which
+    already hold a box and a score that look valid)."""
     N = len(case["s"])
     parts = [_segments(case["b"][n], case["s"][n], case["l"][n], case["nseg"], case["seg_len"], counts=case.get("counts", [None] * N)[n]) for n in range(N)]
-    return tuple(np.stack([p[i] for p in parts]) for i in range(4))
+    B, S, Lb, cnt = (np.stack([p[i] for p in parts]) for i in range(4))
+    if "garbage" in case:
+        past = np.arange(case["seg_len"])[None, None, :] >= cnt[:, :, None]
+        Lb[past] = np.resize(np.array(case["garbage"], np.int64), int(past.sum())).astype(np.int32)
+    return B, S, Lb, cnt
 
 
 def ref_post(case, nms_flags=0, det=100, cap=128, **kw):
+    kw.setdefault("ncls", case.get("ncls", 81))
     return [rr.postprocess(case["b"][n], case["s"][n], case["l"][n], 0.4, det, cap, nms_flags, **kw) for n in range(len(case["s"]))]
+
+
+# ===================================================================================================================== capacity and threshold edges
+# Everything below is built on first use (lru_cache), never at import.  A = C = 1 rows: a level (1, n) is a row of exactly n logits and every label is 1.
+KCAP = 1024                              # csrc/retinanet_ops.hip RETINA_KCAP: the largest top_n
+TOP_NS = (1, 63, 64, 65, 1023, 1024)
+BORDER_ROWS = (8191, 8192, 8193, 16383, 16384, 16385)
+BORDER_TOP_N = 64
+THRESHOLDS = (-1.0, 0.0, 1e-45, 1e-40, 1e-38, 1e-6, 0.3, 0.5, 0.7, 0.95, 1.0 - 2.0 ** -20, 1.0 - 2.0 ** -23, 1.0 - 2.0 ** -24, 1.0, 2.0)
+SPECIALS = (-np.inf, -200.0, -104.0, -88.0, 0.0, 17.0, 100.0, np.inf, np.nan)
+
+
+def candidates(row, thr=0.05):
+    """How many logits of a row the reference's threshold test passes."""
+    return int((ora.map_f32(np.asarray(row, F32).reshape(-1), 1) > F32(thr)).sum())
+
+
+@functools.lru_cache(maxsize=None)
+def topn_cases():
+    """name -> (logits, A, C, top_n) on a single-slice row (4320 logits) and a four-slice row (25 200).  "topn_<k>": image 0 holds k + 37 distinct
+    candidates, image 1 k // 2 distinct ones over a run of k - k // 2 + 30 equal ones, so that the cut falls inside the run.  "topn_1024_exact": 1024
+    candidates in image 0, 1025 in image 1."""
+    rng = np.random.default_rng(60)
+    out = {}
+    for k in TOP_NS:
+        x = _rows(SHAPES[:2], 2, A, C)
+        for lv in x:
+            _scatter(lv[0].reshape(-1), rng, k + 37)
+            f = lv[1].reshape(-1)
+            d = k // 2
+            pos = rng.choice(f.size, k + 30, replace=False)
+            f[pos[:d]] = np.linspace(1.0, 4.0, d, dtype=F32)
+            f[pos[d:]] = F32(0.5)
+        out["topn_%d" % k] = (x, A, C, k)
+    x = _rows(SHAPES[:2], 2, A, C)
+    for lv in x:
+        _scatter(lv[0].reshape(-1), rng, KCAP); _scatter(lv[1].reshape(-1), rng, KCAP + 1)
+    out["topn_1024_exact"] = (x, A, C, KCAP)
+    return out
+
+
+def border_run(n):
+    """The 100 indices centred on the first slice border, cut to the row."""
+    return np.arange(SLICE - 50, min(SLICE + 50, n))
+
+
+@functools.lru_cache(maxsize=None)
+def border_cases():
+    """name -> (logits, 1, 1, 64), rows of 8192 - 1 .. 2 * 8192 + 1 logits, N = 2; image 1 holds one candidate, on the row's last index.
+    "border_distinct_<n>": distinct candidates on the last 20 indices of every slice and the first 20 of the next.
+    "border_tie_<n>": a run of equal logits centred on index 8192 (and a second one on 16384) under so many distinct higher ones that the cut falls inside the
+    first run: its lower indices win, across the border where the row has one."""
+    rng = np.random.default_rng(61)
+    out = {}
+    for n in BORDER_ROWS:
+        x = np.full((2, 1, n, 1), LOW, F32)
+        idx = np.concatenate([np.arange(b - 20, b + 20) for b in range(SLICE, n + 20, SLICE)])
+        idx = idx[idx < n]
+        while True:
+            v = rng.uniform(-2.5, 4.0, idx.size).astype(F32)
+            if len(np.unique(ora.map_f32(v, 1))) == idx.size:
+                break
+        x[0, 0, idx, 0] = v
+        x[1, 0, n - 1, 0] = 1.0
+        out["border_distinct_%d" % n] = ([x], 1, 1, BORDER_TOP_N)
+        x = np.full((2, 1, n, 1), LOW, F32)
+        run = border_run(n)
+        nd = 4 if run.size == 100 else BORDER_TOP_N - run.size + 1    # the cut falls inside the run: all but one of a short run, 60 of a whole one
+        x[0, 0, 100:100 + nd, 0] = np.linspace(1.0, 3.0, nd, dtype=F32)
+        x[0, 0, run, 0] = 0.5
+        if n > 2 * SLICE - 50:
+            x[0, 0, 2 * SLICE - 50:min(2 * SLICE + 50, n), 0] = 0.5   # the same score again around the second border: all of it loses
+        x[1, 0, n - 1, 0] = 1.0
+        out["border_tie_%d" % n] = ([x], 1, 1, BORDER_TOP_N)
+    return out
+
+
+GEOMETRY = ((5, 5000), (3, 3000), (7, 11), (2, 3), (1, 1))   # rows of 25 000, 9000, 77, 6 and 1 logits: 4, 2, 1, 1, 1 slices
+GEOMETRY_TOP_N = 6
+GEOMETRY_KINDS = (0, 1, GEOMETRY_TOP_N, GEOMETRY_TOP_N + 1, -1)   # candidates of a (level, image); -1: every logit
+
+
+GEOMETRY_TABLE = ((4, 0, 3), (1, 4, 2), (2, 3, 4), (3, 1, 0), (0, 4, 1))   # [level][image] -> index into GEOMETRY_KINDS: both long rows pass whole once
+
+
+def geometry_kind(l, n):
+    return GEOMETRY_KINDS[GEOMETRY_TABLE[l][n]]
+
+
+@functools.lru_cache(maxsize=None)
+def geometry_case():
+    """Five levels (the most the op takes), three images, A = C = 1; the candidate count of (level, image) is geometry_kind(l, n), cut to the row."""
+    rng = np.random.default_rng(62)
+    x = _rows(GEOMETRY, 3, 1, 1)
+    for l, lv in enumerate(x):
+        for n in range(3):
+            f = lv[n].reshape(-1)
+            k = geometry_kind(l, n)
+            if k < 0:
+                f[:] = rng.uniform(-2.0, 4.0, f.size).astype(F32)
+            elif k:
+                _scatter(f, rng, min(k, f.size))
+    return x, 1, 1, GEOMETRY_TOP_N
+
+
+def prefilter_of(thr):
+    """The logit pre-filter of retina_select_launch as first built, in float32 like the launcher: logit(thr) - 0.25, None outside (0, 1)."""
+    t = F32(thr)
+    if not (t > 0 and t < 1):
+        return None
+    return F32(F32(np.log(t / (F32(1.0) - t))) - F32(0.25))
+
+
+def _ord(x):
+    u = int(np.array(x, F32).view(np.uint32))
+    return (~u & 0xffffffff) if u & 0x80000000 else (u | 0x80000000)
+
+
+def _unord(o):
+    u = (o & 0x7fffffff) if o & 0x80000000 else (~o & 0xffffffff)
+    return np.array(u, np.uint32).view(F32)[()]
+
+
+@functools.lru_cache(maxsize=None)
+def crossing(thr):
+    """(x_at, x_up): the consecutive floats with sigmoid(x_at) <= thr < sigmoid(x_up), by bisection over the floats of [-120, 120] (the sigmoid is monotone:
+    threshold_logits() checks it around its own crossing, threshold_case() around this one).  None when every float passes or none does."""
+    def passes(x):
+        return bool(ora.map_f32(np.array([x], F32), 1)[0] > F32(thr))
+    lo, hi = _ord(F32(-120.0)), _ord(F32(120.0))
+    if passes(_unord(lo)) or not passes(_unord(hi)):
+        return None
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if passes(_unord(mid)):
+            hi = mid
+        else:
+            lo = mid
+    return _unord(lo), _unord(hi)
+
+
+def _threshold_filler(thr):
+    """LOW where the threshold drops it, NaN (which no threshold passes) under the smaller thresholds: the row then holds fewer than 1024 numbers and the
+    selected list is the whole set that passed."""
+    return LOW if ora.map_f32(np.array([LOW], F32), 1)[0] <= F32(thr) else F32(np.nan)
+
+
+@functools.lru_cache(maxsize=None)
+def threshold_case(thr):
+    """-> (logits, 1, 1, 1024): one row of 4000 with 16 consecutive floats around the crossing of thr, 512 logits over [pre-filter - 1, pre-filter + 1]
+    and SPECIALS, shuffled."""
+    rng = np.random.default_rng(63)
+    vals = [np.array(SPECIALS, F32)]
+    c = crossing(thr)
+    if c is not None:
+        w = np.array([_next(c[0], -k) for k in range(7, 0, -1)] + [c[0], c[1]] + [_next(c[1], k) for k in range(1, 8)], F32)
+        p = ora.map_f32(w, 1)
+        assert (np.diff(p) >= 0).all() and (p[:8] <= F32(thr)).all() and (p[8:] > F32(thr)).all()
+        vals.append(w)
+    pre = prefilter_of(thr)
+    if pre is not None:
+        vals.append((np.float64(pre) + np.linspace(-1.0, 1.0, 512)).astype(F32))
+    vals = np.concatenate(vals)
+    row = np.full(4000, _threshold_filler(thr), F32)
+    row[rng.choice(row.size, vals.size, replace=False)] = vals
+    return [row.reshape(1, 1, 4000, 1)], 1, 1, KCAP
+
+
+TOWER = tuple(a * C for a in range(A))   # the channel of class 1 of each of the nine anchors of a cell
+
+
+@functools.lru_cache(maxsize=None)
+def decode_edge_case(kind):
+    """-> (logits, deltas, anchors, image_hw) of decode_case() with every anchor of cell (0, 0) selected (class 1) on each level.
+    "tiny_image": a 1 x 1 image.  "zero_deltas": all deltas 0, the decoded box is the clipped anchor.  "special_deltas": NaN and +-inf in dx, dy, dw of
+    those nine anchors."""
+    logits, deltas, anchors, hw = decode_case()
+    logits = [lg.copy() for lg in logits]
+    for lg in logits:
+        lg[:, 0, 0, list(TOWER)] = np.linspace(3.0, 4.0, A, dtype=F32)
+    if kind == "tiny_image":
+        hw = np.array([[1, 1], [1, 1]], np.int32)
+    elif kind == "zero_deltas":
+        deltas = [np.zeros_like(d) for d in deltas]
+    elif kind == "special_deltas":
+        deltas = [d.copy() for d in deltas]
+        nan, inf = F32(np.nan), F32(np.inf)
+        for d in deltas:   # (anchor, component, value): dx, dy, dw, dh are components 0..3
+            for a, k, v in ((1, 0, nan), (2, 2, nan), (3, 0, inf), (4, 0, -inf), (5, 2, inf), (6, 2, -inf), (7, 1, nan), (8, 1, inf)):
+                d[:, 0, 0, a * 4 + k] = v
+    else:
+        raise KeyError(kind)
+    return logits, deltas, anchors, hw
+
+
+@functools.lru_cache(maxsize=None)
+def min_size_edge():
+    """(m, m_up): the smaller side (+1) of the best box of level 0, image 0 of the zero-delta case and the next float: min_size m keeps that box, m_up drops it."""
+    logits, deltas, anchors, hw = decode_edge_case("zero_deltas")
+    s, i = rr.select_level(logits[0][0])
+    b, _, _ = rr.decode_level(s[:1], i[:1], deltas[0][0], anchors[0], hw[0][1], hw[0][0])
+    m = min(b[0, 2] - b[0, 0] + F32(1), b[0, 3] - b[0, 1] + F32(1))
+    return F32(m), _next(m)
+
+
+# --------------------------------------------------------------------------------------------------------------------- retina_postprocess
+FULL = 8192                              # csrc/retinanet_ops.hip RETINA_MAX_SLOTS
+FULL_SEG = dict(nseg=8, seg_len=1024)
+
+
+@functools.lru_cache(maxsize=None)
+def full_cases():
+    """Every one of the 8192 slots valid.  "full_one_class"; "full_100_then_8092": class 2 starts inside word 1 and spans 127 words;
+    "full_255_classes": ncls 256 with 4055 of class 1, 37 of class 254, 4100 of class 255 (which starts inside word 63 and spans 65 words);
+    "batch_8192_0_1": three images holding 8192, 0 and 1 candidates."""
+    rng = np.random.default_rng(64)
+    b = _clustered(rng, FULL, centres=40, spread=25.0); s = rng.uniform(0.05, 1.0, FULL).astype(F32)
+    out = {}
+    out["full_one_class"] = dict(b=[b], s=[s], l=[np.full(FULL, 17, np.int32)], **FULL_SEG)
+    out["full_100_then_8092"] = dict(b=[b], s=[s], l=[np.r_[np.full(100, 1), np.full(8092, 2)].astype(np.int32)], **FULL_SEG)
+    out["full_255_classes"] = dict(b=[b], s=[s], l=[np.r_[np.full(37, 254), np.full(4100, 255), np.full(4055, 1)].astype(np.int32)], ncls=256, **FULL_SEG)
+    out["batch_8192_0_1"] = dict(b=[b, b[:0], b[5:6]], s=[s, s[:0], s[5:6]], l=[np.full(FULL, 17, np.int32), np.zeros(0, np.int32), np.full(1, 80, np.int32)],
+                                 counts=[None, [0] * 8, [0, 0, 0, 1, 0, 0, 0, 0]], **FULL_SEG)
+    for c in out.values():
+        for a in c["b"] + c["s"] + c["l"]:
+            a.setflags(write=False)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _full_image_ref(name, n, det, cap):
+    c = full_cases()[name]
+    return rr.postprocess(c["b"][n], c["s"][n], c["l"][n], 0.4, det, cap, 0, ncls=c.get("ncls", 81))
+
+
+def full_ref(name, det, cap):
+    """The reference of a full case, computed once per (image, det, cap): image 0 of the batch case is full_one_class's."""
+    c = full_cases()[name]
+    return [_full_image_ref("full_one_class" if name == "batch_8192_0_1" and n == 0 else name, n, det, cap) for n in range(len(c["s"]))]
+
+
+def class_reach(case, cls, n=0, thr=0.4):
+    """What the greedy scan of one class has to carry, from the oracle's NMS and plain float32 IoUs: dict(s, e: the class's range in the engine's sorted order
+    (class asc, score desc, slot asc); words; far: a kept box among the first 64 of the class overlaps (IoU > thr) one more than 4096 ranks later;
+    upper: ... one in a word 64 or more after the class's first; last: ... one in the class's last word)."""
+    b, s, lab = case["b"][n], case["s"][n], case["l"][n]
+    nc = case.get("ncls", 81) - 1
+    valid = (lab >= 1) & (lab <= nc)
+    start = int((valid & (lab < cls)).sum())
+    idx = np.flatnonzero(lab == cls)
+    idx = idx[np.lexsort((idx, -s[idx].astype(np.float64)))]
+    srt = np.sort(idx)                   # ora.nms breaks score ties by position: hand it the class in slot order
+    kept = set(srt[ora.nms(b[srt], s[srt], thr, 1, 0)].tolist())
+    e = start + idx.size
+    w0 = start >> 6
+    word = (start + np.arange(idx.size)) >> 6
+    bb = b[idx]
+    area = (bb[:, 2] - bb[:, 0] + F32(1)) * (bb[:, 3] - bb[:, 1] + F32(1))
+    far = upper = last = False
+    for r in range(min(64, idx.size)):
+        if int(idx[r]) not in kept:
+            continue
+        w = np.clip(np.minimum(bb[r, 2], bb[:, 2]) - np.maximum(bb[r, 0], bb[:, 0]) + F32(1), 0, None)
+        h = np.clip(np.minimum(bb[r, 3], bb[:, 3]) - np.maximum(bb[r, 1], bb[:, 1]) + F32(1), 0, None)
+        inter = w * h
+        hit = inter / (area[r] + area - inter) > F32(thr)
+        hit[:r + 1] = False
+        far |= bool(hit[r + 4097:].any())
+        upper |= bool(hit[word - w0 >= 64].any())
+        last |= bool(hit[word == word[-1]].any())
+    return dict(s=start, e=e, words=int(word[-1] - w0 + 1), far=far, upper=upper, last=last)
+
+
+GRID = np.array([[x * 30, y * 30, x * 30 + 20, y * 30 + 20] for y in range(15) for x in range(15)], F32)   # 225 disjoint boxes: NMS keeps every one
+CUT_K = 40
+
+
+@functools.lru_cache(maxsize=None)
+def edge_post_cases():
+    """name -> case dict (as post_cases()).
+    "ncls_2": one class.  "labels_out_of_range": labels 0, -1, ncls and 300 inside the valid counts, each on the box of an in-range candidate of a lower score
+    that it would suppress if it were counted into that class; the slots past the counts hold garbage of labels in and out of range.
+    "cut_k40" / "cut_k40_zeros": 40 disjoint boxes, all kept; the 39th and 40th scores tie ("zeros": the scores 31..34 are +-0.0, the rest under them
+    negative), all tied boxes in one class."""
+    rng = np.random.default_rng(65)
+    out = {}
+    b = _clustered(rng, 60, centres=4, spread=8.0, extent=300.0); s = rng.uniform(0.05, 1.0, 60).astype(F32)
+    out["ncls_2"] = dict(b=[b], s=[s], l=[np.ones(60, np.int32)], nseg=3, seg_len=25, counts=[[25, 10, 25]], ncls=2, garbage=(1, 0, 2, -1))
+    for ncls in (2, 81):
+        bb = np.repeat(GRID[:6], 2, 0)                                   # pairs of identical boxes
+        ss = np.tile(np.array([0.9, 0.6], F32), 6) - np.repeat(np.arange(6), 2).astype(F32) * F32(0.01)
+        ll = np.tile(np.array([0, 1], np.int32), 6)                      # the better of each pair carries the bad label, the other label 1
+        ll[0::2] = [0, -1, ncls, 300, -2 ** 31, 2 ** 31 - 1]
+        out["labels_out_of_range_ncls_%d" % ncls] = dict(b=[bb], s=[ss], l=[ll], nseg=2, seg_len=8, counts=[[7, 5]], ncls=ncls, garbage=(1, 0, ncls, -1, 300, ncls - 1))
+    perm = rng.permutation(CUT_K)
+    sc = np.concatenate([np.linspace(0.99, 0.2, CUT_K - 2), np.full(2, 0.1)]).astype(F32)
+    lab = rng.integers(1, 81, CUT_K).astype(np.int32); lab[-2:] = 7
+    out["cut_k40"] = dict(b=[GRID[:CUT_K][perm]], s=[sc[perm]], l=[lab[perm]], nseg=4, seg_len=12, counts=[[12, 4, 12, 12]])
+    sc = np.concatenate([np.linspace(0.99, 0.2, 30), [0.0, -0.0, -0.0, 0.0], np.linspace(-0.1, -0.4, 4), [-0.5, -0.5]]).astype(F32)
+    lab = rng.integers(1, 81, CUT_K).astype(np.int32); lab[30:] = 7
+    out["cut_k40_zeros"] = dict(b=[GRID[:CUT_K][perm]], s=[sc[perm]], l=[lab[perm]], nseg=4, seg_len=12, counts=[[12, 4, 12, 12]])
+    return out

@@ -29,6 +29,45 @@ def reference(which, **kw):
     return x, hw, ref, dets
 
 
+def third_image():
+    """A third image for the small canvas (256 x 352), smaller than both of small_images()."""
+    return np.random.default_rng(20261019).uniform(0, 255, (231, 322, 3)).astype(np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def three():
+    """small_images() + third_image() as one batch on the small canvas, and the reference forward of the third image alone on that canvas (the layers treat
+    the images of a batch independently: images 0 and 1 are reference("small")'s).  -> (x [3], hw [3], ref of image 2, dets of image 2)"""
+    from isegmi.maskrcnn import prepare_images
+    x, hw = prepare_images(small_images() + [third_image()])
+    ref = rr.RetinaNetRef(state_dict(), cap=128)
+    dets = ref.forward(x[2:3], hw[2:3])
+    x.setflags(write=False)
+    return x, hw, ref, dets
+
+
+def state_dict_convs(num_convs):
+    """state_dict() with the towers cut to their first num_convs layers."""
+    drop = tuple("rpn.head.%s_tower.%d." % (t, 2 * i) for t in ("cls", "bbox") for i in range(num_convs, 4))
+    return {k: v for k, v in state_dict().items() if not k.startswith(drop)}
+
+
+@functools.lru_cache(maxsize=None)
+def heads(which, num_convs):
+    """(logits, deltas) of reference(which)'s pyramid under towers of num_convs layers: the trunk and the pyramid are not computed again."""
+    ref = reference(which, cap=128)[2]
+    return rr.RetinaNetRef(state_dict(), num_convs=num_convs).heads(ref.feats["P"])
+
+
+def tail(which, num_convs=4, **kw):
+    """rr.tail on reference(which)'s head outputs (or heads(which, num_convs)'s) with other tail parameters (top_n, thr, nms_thr, det_per_img, ...).
+    -> (sel[l][n], dets)"""
+    x, hw, ref, _ = reference(which, cap=128)
+    logits, deltas = (ref.feats["logits"], ref.feats["deltas"]) if num_convs == 4 else heads(which, num_convs)
+    sel, dec, dets, totals = rr.tail(logits, deltas, ref.feats["anchors"], hw, **dict(ref.kw, **kw))
+    return sel, [dict(box=d[0], score=d[1], label=d[2]) for d in dets]
+
+
 def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
@@ -49,9 +88,15 @@ def assert_forward_equal(model, ref, n, features=True):
             got = model.fetch(name, n)
             assert got.shape == ref.feats["P"][l].shape, (name, got.shape)
             assert np.array_equal(bits(got), bits(ref.feats["P"][l])), name
-    sel = model.selected(n)
+    assert_selected_equal(model, ref.feats["sel"], n)
+
+
+def assert_selected_equal(model, want, n, first=0):
+    """Every level's selected list of the last forward's images first .. first + n - 1 against want[l][0 .. n - 1]."""
+    sel = model.selected(first + n)
     for l in range(5):
         for i in range(n):
-            s, idx = ref.feats["sel"][l][i]
-            assert np.array_equal(sel[l][i][1], idx), (l, i)
-            assert np.array_equal(bits(sel[l][i][0]), bits(s)), (l, i)
+            s, idx = want[l][i]
+            assert len(sel[l][first + i][1]) == len(idx), (l, i, len(sel[l][first + i][1]), len(idx))
+            assert np.array_equal(sel[l][first + i][1], idx), (l, i)
+            assert np.array_equal(bits(sel[l][first + i][0]), bits(s)), (l, i)

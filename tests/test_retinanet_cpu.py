@@ -1,5 +1,6 @@
 """RetinaNet without a GPU: the config mapping and its refusals, the anchors, a torch restatement of the two post-processor functions against
-tests/retinanet_ref.py, the proof that every crafted op input of tests/retinanet_cases.py discriminates the rule it is named for, and the weights."""
+tests/retinanet_ref.py, the proof that every crafted op input of tests/retinanet_cases.py discriminates the rule or reaches the limit it is named for, and
+the weights."""
 import os
 import sys
 
@@ -261,3 +262,220 @@ def test_python_refusals_need_no_device():
         RetinaNet({}, 256, 352, fp16=True)
     with pytest.raises(ValueError, match="graph"):
         RetinaNet({}, 256, 352, graph=True)
+
+
+# ------------------------------------------------------------------------------------------------------------------- capacity and threshold edges
+def _sel(case, thr=0.05, **kw):
+    logits, a, c, top_n = case
+    return [[rr.select_level(lg[n], top_n, thr, **kw) for n in range(lg.shape[0])] for lg in logits]
+
+
+def _same(a, b):
+    return all(np.array_equal(x[1], y[1]) and np.array_equal(x[0], y[0]) for la, lb in zip(a, b) for x, y in zip(la, lb))
+
+
+@pytest.mark.parametrize("k", rc.TOP_NS)
+def test_top_n_cases_hold_more_than_top_n(k):
+    case = rc.topn_cases()["topn_%d" % k]
+    assert case[3] == k and [lg[0].size for lg in case[0]] == [25200, 4320]
+    for lg in case[0]:
+        assert rc.candidates(lg[0]) == k + 37 and rc.candidates(lg[1]) == k + 30
+        assert len(np.unique(ora.map_f32(lg[0].reshape(-1), 1))) == k + 37 + 1          # all distinct (+ the filler)
+    sel, high = _sel(case), _sel(case, tie_high_index=True)
+    for l in range(2):
+        assert len(sel[l][0][0]) == len(sel[l][1][0]) == k
+        assert _same([[sel[l][0]]], [[high[l][0]]]) and not _same([[sel[l][1]]], [[high[l][1]]])   # only the run's winners depend on the tie rule
+        s = sel[l][1][0]
+        assert s[-1] == ora.map_f32(np.array([0.5], rc.F32), 1)[0] and (s == s[-1]).sum() == k - k // 2     # the cut lies inside the run
+
+
+def test_top_n_1024_with_exactly_1024_and_1025_candidates():
+    case = rc.topn_cases()["topn_1024_exact"]
+    assert case[3] == rc.KCAP == 1024
+    for lg, row in zip(case[0], _sel(case)):
+        assert [rc.candidates(lg[0]), rc.candidates(lg[1])] == [1024, 1025]
+        assert len(row[0][0]) == len(row[1][0]) == 1024
+        lost = set(np.flatnonzero(lg[1].reshape(-1) > rc.LOW)) - set(row[1][1].tolist())
+        assert len(lost) == 1 and lg[1].reshape(-1)[list(lost)[0]] == lg[1].reshape(-1)[lg[1].reshape(-1) > rc.LOW].min()
+
+
+@pytest.mark.parametrize("n", rc.BORDER_ROWS)
+def test_border_cases_reach_both_sides_of_a_slice_border(n):
+    S = rc.SLICE
+    case = rc.border_cases()["border_distinct_%d" % n]
+    row = case[0][0]
+    assert row.shape == (2, 1, n, 1) and case[3] == 64
+    cand = np.flatnonzero(row[0].reshape(-1) > rc.LOW)
+    assert S - 1 in cand or n < S                 # the last index of slice 0 ...
+    assert (S in cand) == (n > S)                 # ... and the first of slice 1
+    if n > 2 * S:
+        assert 2 * S - 1 in cand and 2 * S in cand
+    (s0, i0), (s1, i1) = _sel(case)[0]
+    assert len(i0) == min(64, cand.size) and set(i0.tolist()) <= set(cand.tolist())
+    if n > S:
+        assert (i0 < S).any() and (i0 >= S).any()
+    assert i1.tolist() == [n - 1]
+    # the equal run: the cut falls inside it and its lower indices win
+    case = rc.border_cases()["border_tie_%d" % n]
+    row = case[0][0]
+    run = rc.border_run(n)
+    assert run[0] == S - 50 and run[-1] == min(S + 49, n - 1) and (row[0, 0, run, 0] == 0.5).all()
+    assert rc.candidates(row[0]) > 64
+    (s0, i0), (s1, i1) = _sel(case)[0]
+    (h0, j0), _ = _sel(case, tie_high_index=True)[0]
+    assert len(i0) == 64 and not np.array_equal(i0, j0)
+    won = np.sort(i0[s0 == s0[-1]])
+    assert 0 < won.size < run.size and np.array_equal(won, run[:won.size])
+    if n >= 2 * S - 1:
+        assert won[0] < S and won[-1] > S                     # across the border
+        assert not (i0 >= 2 * S - 50).any()                   # the second run, equal in score, loses to the first on the index
+    if n == S + 1:
+        assert won[-1] == S - 1 and S not in i0               # the first logit of slice 1 ties with the last of slice 0 and loses
+    assert i1.tolist() == [n - 1]
+
+
+def test_geometry_case_counts():
+    logits, a, c, top_n = rc.geometry_case()
+    assert len(logits) == 5 and a == c == 1 and all(lg.shape[0] == 3 for lg in logits)
+    assert [-(-lg[0].size // rc.SLICE) for lg in logits] == [4, 2, 1, 1, 1] and logits[4][0].size == 1
+    cnt = np.array([[rc.candidates(lg[n]) for n in range(3)] for lg in logits])
+    want = np.array([[lg[0].size if rc.geometry_kind(l, n) < 0 else min(rc.geometry_kind(l, n), lg[0].size) for n in range(3)] for l, lg in enumerate(logits)])
+    assert np.array_equal(cnt, want)
+    assert {0, 1, top_n, top_n + 1, 25000, 9000, 77} <= set(cnt.reshape(-1).tolist())
+    assert all(len(set(row)) > 1 for row in cnt.tolist()) and all(len(set(col)) > 1 for col in cnt.T.tolist())   # a wrong level or image offset shows
+    sel = _sel(rc.geometry_case())
+    assert np.array_equal([[len(sel[l][n][0]) for n in range(3)] for l in range(5)], np.minimum(cnt, top_n))
+
+
+SIGMOID_FLOOR = 4.1560284e-39      # what ora.map_f32(x, 1) returns for every logit under about -88.4, -inf included
+
+
+def test_sigmoid_never_reaches_zero():
+    p = ora.map_f32(np.array([-np.inf, -200.0, -104.0, -89.0], rc.F32), 1)
+    assert (p == p[0]).all() and p[0] > 0 and abs(float(p[0]) - SIGMOID_FLOOR) < 1e-44
+
+
+@pytest.mark.parametrize("thr", rc.THRESHOLDS)
+def test_threshold_cases(thr):
+    """Every threshold: the reference passes some and drops some of the row; the logits the first pre-filter (logit(thr) - 0.25) would have dropped
+    although their sigmoid passes are in the row."""
+    case = rc.threshold_case(thr)
+    row = case[0][0].reshape(-1)
+    assert row.size == 4000 and case[3] == 1024
+    s, i = rr.select_level(row, 1024, thr)
+    numbers = int((~np.isnan(row)).sum())
+    assert len(i) == rc.candidates(row, thr) < 1024           # nothing is cut: the list is the whole set that passed
+    passed = np.zeros(row.size, bool); passed[i] = True
+    if thr <= 0:
+        assert len(i) == numbers == len(rc.SPECIALS) - 1      # drops only the NaN
+        assert np.isneginf(row[i]).any()
+    elif np.float32(thr) < np.float32(SIGMOID_FLOOR):         # the sigmoid's floor is over the threshold: again only the NaN are dropped ...
+        assert rc.crossing(thr) is None and len(i) == numbers > 500 and np.isneginf(row[i]).any()
+        assert (row[i] <= rc.prefilter_of(thr)).sum() >= 200 + 4     # ... and not the logits at or under logit(thr) - 0.25, the pre-filter as first built
+    elif thr >= 1:
+        assert len(i) == 0 and numbers > 500
+    else:
+        assert 0 < len(i) < numbers
+        pre = rc.prefilter_of(thr)
+        grid = (row >= pre - 1) & (row <= pre + 1)
+        assert grid.sum() >= 512 and (row[grid] <= pre).sum() >= 200 and (row[grid] > pre).sum() >= 200
+        assert not (passed & (row <= pre)).any()              # the reference passes nothing at or under logit(thr) - 0.25
+        x_at, x_up = rc.crossing(thr)
+        assert not passed[row == x_at].any() and passed[row == x_up].all() and (row == x_at).sum() == (row == x_up).sum() == 1
+    if thr == 0.5:
+        assert (row == 0).sum() == 1 and not passed[row == 0].any() and ora.map_f32(np.zeros(1, rc.F32), 1)[0] == 0.5
+    if thr == 1.0 - 2.0 ** -24:
+        assert len(i) > 0 and (s == 1.0).all()
+    assert passed[np.isposinf(row)].all() == (thr < 1) and not passed[np.isnan(row)].any()
+
+
+def test_crossing_agrees_with_threshold_logits():
+    x_at, x_up, _ = rc.threshold_logits()
+    assert rc.crossing(0.05) == (x_at, x_up)
+
+
+def _dec(logits, deltas, anchors, hw, min_size=0.0):
+    out = []
+    for l in range(len(logits)):
+        for n in range(logits[l].shape[0]):
+            s, i = rr.select_level(logits[l][n])
+            out.append((len(s),) + rr.decode_level(s, i, deltas[l][n], anchors[l], hw[n][1], hw[n][0], min_size=min_size))
+    return out
+
+
+def test_decode_edge_cases():
+    d = _dec(*rc.decode_edge_case("tiny_image"))
+    assert all(k == len(sc) > 0 and not b.any() for k, b, sc, lb in d)              # every box is (0, 0, 0, 0): 1 wide, kept under min_size 0
+    case = rc.decode_edge_case("zero_deltas")
+    m, m_up = rc.min_size_edge()
+    assert m_up > m > 1
+    at, up, none = _dec(*case, min_size=m), _dec(*case, min_size=m_up), _dec(*case, min_size=1e9)
+    s, i = rr.select_level(case[0][0][0])
+    an = case[2][0][i[0] // rc.C]
+    hw = case[3][0]
+    clipped = np.clip(an, 0, [hw[1] - 1, hw[0] - 1, hw[1] - 1, hw[0] - 1]).astype(rc.F32)
+    assert np.array_equal(at[0][1][0], clipped) and at[0][2][0] == s[0]                  # the decoded box is the clipped anchor, kept at min_size == its side + 1
+    assert up[0][2][0] != s[0] and len(up[0][2]) < len(at[0][2]) < at[0][0]              # ... dropped one float above; other boxes were dropped before it
+    assert all(len(sc) == 0 and k > 0 for k, b, sc, lb in none)
+    case = rc.decode_edge_case("special_deltas")
+    d = _dec(*case)
+    q = 0
+    for l in range(len(case[0])):
+        for n in range(2):
+            s, i = rr.select_level(case[0][l][n])
+            nan_centre = np.isin(i // rc.C, (1, 7))                                         # dx / dy NaN: a NaN box, which fails `>= min_size`
+            k, b, sc, lb = d[q]; q += 1
+            assert k - len(sc) == nan_centre.sum() >= 2 and np.array_equal(sc, s[~nan_centre])
+            assert np.isfinite(b).all()                                                      # +-inf clip to the border; a NaN dw takes the clamp's value
+            assert set(range(rc.A)) <= set((i // rc.C).tolist())                             # all nine special anchors are among the selected
+    assert all(k == len(sc) for k, b, sc, lb in _dec(*rc.decode_edge_case("zero_deltas")))
+
+
+def _labels_clipped(case):
+    nc = case.get("ncls", 81) - 1
+    return dict(case, l=[np.clip(x, 1, nc) for x in case["l"]])
+
+
+def test_full_cases_reach_the_capacity():
+    F = rc.full_cases()
+    for name in ("full_one_class", "full_100_then_8092", "full_255_classes"):
+        c = F[name]
+        B, S, Lb, cnt = rc.pack_post(c)
+        assert B.shape == (1, 8, 1024, 4) and (cnt == 1024).all()                         # every slot valid
+        assert ((c["l"][0] >= 1) & (c["l"][0] < c.get("ncls", 81))).all()
+    r = rc.class_reach(F["full_one_class"], 17)
+    assert (r["s"], r["e"], r["words"]) == (0, 8192, 128) and r["far"] and r["upper"] and r["last"], r
+    r = rc.class_reach(F["full_100_then_8092"], 2)
+    assert (r["s"], r["e"], r["words"]) == (100, 8192, 127) and r["s"] % 64 != 0 and r["far"] and r["upper"] and r["last"], r
+    c = F["full_255_classes"]
+    assert c["ncls"] == 256 and c["l"][0].max() == 255
+    r = rc.class_reach(c, 255)
+    assert (r["s"], r["e"], r["words"]) == (4092, 8192, 65) and r["s"] % 64 != 0 and r["upper"] and r["last"], r    # rel crosses 64 with w0 = 63
+    assert rc.class_reach(c, 254)["s"] == 4055 and rc.class_reach(c, 1)["last"]
+    for name in ("full_one_class", "full_100_then_8092", "full_255_classes"):
+        uncut, cut = rc.full_ref(name, 0, 8192)[0], rc.full_ref(name, 100, 128)[0]
+        assert 1000 < len(uncut[1]) < 8192 and 100 <= len(cut[1]) <= 128
+    b = F["batch_8192_0_1"]
+    assert [len(s) for s in b["s"]] == [8192, 0, 1] and rc.pack_post(b)[3].sum(1).tolist() == [8192, 0, 1]
+    assert [len(r[1]) for r in rc.full_ref("batch_8192_0_1", 100, 128)][1:] == [0, 1]
+
+
+def test_edge_post_cases_discriminate():
+    P = rc.edge_post_cases()
+    assert P["ncls_2"]["ncls"] == 2 and 0 < len(_post_all(P["ncls_2"])[0][1]) < 60
+    for ncls in (2, 81):
+        c = P["labels_out_of_range_ncls_%d" % ncls]
+        got = _post_all(c)[0]
+        assert got[2] == [1] * 6 and len(set(c["l"][0][0::2].tolist()) & set(range(1, ncls))) == 0
+        assert max(got[1]) < 0.7                                              # only the worse twin of each pair
+        clipped = _post_all(_labels_clipped(c))[0]                            # counted into a class, the better twins would appear and suppress theirs
+        assert clipped != got and max(clipped[1]) > 0.8 and (ncls == 81 or len(clipped[1]) == 6)
+        B, S, Lb, cnt = rc.pack_post(c)
+        past = Lb[0][np.arange(8)[None, :] >= cnt[0][:, None]]
+        assert ((past >= 1) & (past < ncls)).any() and ((past < 1) | (past >= ncls)).any()
+    K = rc.CUT_K
+    for name, dets, counts in (("cut_k40", (1, K - 1, K, K + 1), (1, K, K, K)), ("cut_k40_zeros", (1, 32, K - 1, K, K + 1), (1, 34, K, K, K))):
+        assert [len(_post_all(P[name], det=d, cap=64)[0][1]) for d in dets] == list(counts), name
+        assert len(_post_all(P[name], det=0, cap=64)[0][1]) == K
+    z = P["cut_k40_zeros"]["s"][0]
+    assert (np.signbit(z) & (z == 0)).sum() == 2 and (~np.signbit(z) & (z == 0)).sum() == 2 and (z < 0).sum() == 6

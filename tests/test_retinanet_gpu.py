@@ -1,5 +1,6 @@
 """The RetinaNet engine end to end against tests/retinanet_ref.py, bit for bit: pyramid, every level's selected list, final detections; canvas changes on
-one engine, a partly filled batch, an empty result, a Mask R-CNN engine next to it, and the refusals."""
+one engine, a partly filled batch, an empty result, a Mask R-CNN engine next to it, towers of 1 and 3 layers, a batch of three, the tail's parameters
+changed on a live engine, and the refusals."""
 import dataclasses
 
 import numpy as np
@@ -99,6 +100,73 @@ def test_forks_reach_the_tail(ffi):
         rc.assert_dets_equal(m(x, hw), dets)
     finally:
         m.close()
+
+
+@pytest.mark.parametrize("num_convs", [1, 3])
+def test_other_tower_depths(ffi, num_convs):
+    """retina_num_convs 1 and 3: the towers' ping-pong ends in the other buffer than at 4 (and 1 never writes the second one)."""
+    from isegmi.retinanet import RetinaNet, RetinaNetConfig
+    x, hw, ref, dets4 = rc.reference("small", cap=128)
+    sel, dets = rc.tail("small", num_convs)
+    assert any(not np.array_equal(a["score"], b["score"]) for a, b in zip(dets, dets4))      # the depth reaches the result
+    m = RetinaNet(rc.state_dict_convs(num_convs), 256, 352, RetinaNetConfig(DETECTIONS_CAP=128, NUM_CONVS=num_convs), max_batch=2)
+    try:
+        preds = m(x, hw)
+        logits = rc.heads("small", num_convs)[0]
+        for l in range(5):
+            assert np.array_equal(rc.bits(m.fetch("retina.logits%d" % l, 2)), rc.bits(logits[l])), l
+        rc.assert_selected_equal(m, sel, 2)
+        rc.assert_dets_equal(preds, dets)
+    finally:
+        m.close()
+
+
+def test_three_images_then_one(ffi):
+    """max_batch 3: three images in one forward, then one image on the same engine -- nothing of the images 1 and 2 of the step before reaches it."""
+    from isegmi.retinanet import RetinaNet, RetinaNetConfig
+    x, hw, ref, dets = rc.reference("small", cap=128)
+    x3, hw3, ref3, dets3 = rc.three()
+    assert np.array_equal(rc.bits(x3[:2]), rc.bits(x)) and np.array_equal(hw3[:2], hw) and x3.shape == (3, 256, 352, 3)
+    x1, hw1, ref1, dets1 = rc.reference("first", cap=128)
+    assert len({len(d["score"]) for d in dets + dets3}) > 1 or not np.array_equal(dets[0]["score"], dets3[0]["score"])
+    m = RetinaNet(rc.state_dict(), 256, 352, RetinaNetConfig(DETECTIONS_CAP=128), max_batch=3)
+    try:
+        preds = m(x3, hw3)
+        rc.assert_selected_equal(m, ref.feats["sel"], 2)
+        rc.assert_selected_equal(m, ref3.feats["sel"], 1, first=2)
+        rc.assert_dets_equal(preds, dets + dets3)
+        preds = m(x1, hw1)
+        assert len(preds) == 1
+        rc.assert_forward_equal(m, ref1, 1)
+        rc.assert_dets_equal(preds, dets1)
+        rc.assert_dets_equal(m(x3, hw3), dets + dets3)
+    finally:
+        m.close()
+
+
+def test_tail_parameters_change_on_a_live_engine(model):
+    """Each tail parameter changed and changed back on one engine: top_n alters the row stride of retina.sel_* / retina.cand_* and the workspaces' sizes."""
+    x, hw, ref, dets = rc.reference("small", cap=128)
+    rc.assert_dets_equal(model(x, hw), dets)
+    seen = [[len(d["score"]) for d in dets]]
+    for name, kw, values, back in (("retina_pre_nms_top_n", "top_n", (1024, 100), 1000), ("retina_inference_th", "thr", (0.5, 0.0), 0.05),
+                                   ("retina_nms_th", "nms_thr", (0.6,), 0.4), ("detections_per_img", "det_per_img", (10,), 100)):
+        try:
+            for v in values:
+                model.set_param(name, float(v))
+                sel, want = rc.tail("small", **{kw: v})
+                preds = model(x, hw)
+                rc.assert_selected_equal(model, sel, 2)
+                rc.assert_dets_equal(preds, want)
+                assert any(not np.array_equal(a["score"], b["score"]) for a, b in zip(want, dets)) or \
+                    any(len(sel[l][i][1]) != len(ref.feats["sel"][l][i][1]) for l in range(5) for i in range(2)), (name, v)     # the value reaches the lists or the result
+                seen.append([len(d["score"]) for d in want])
+        finally:
+            model.set_param(name, float(back))
+        preds = model(x, hw)
+        rc.assert_forward_equal(model, ref, 2, features=False)
+        rc.assert_dets_equal(preds, dets)
+    assert len({tuple(s) for s in seen}) > 2, seen
 
 
 def test_refusals(ffi, model):

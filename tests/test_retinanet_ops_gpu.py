@@ -1,5 +1,6 @@
 """The RetinaNet tail kernels (csrc/retinanet_ops.hip) against tests/retinanet_ref.py on the crafted inputs of tests/retinanet_cases.py, bit for bit, and the
-one convolution shape the model adds.  tests/test_retinanet_cpu.py shows on the CPU that each crafted input discriminates the rule it is named for."""
+one convolution shape the model adds.  tests/test_retinanet_cpu.py shows on the CPU that each crafted input discriminates the rule it is named for, or
+reaches the limit it is named for: top_n 1..1024, the slice borders, 8192 slots, 255 classes, the pre-filter over the threshold range."""
 import numpy as np
 import pytest
 
@@ -102,10 +103,77 @@ def test_retina_decode_min_size(ffi):
     assert dropped > 0
 
 
-def _check_post(ffi, case, nms_flags=0, det=100, cap=128):
+# ---- top_n, slice borders, geometry, thresholds, decode edges (each case is shown to reach its edge in tests/test_retinanet_cpu.py)
+@pytest.mark.parametrize("name", ["topn_%d" % k for k in rc.TOP_NS] + ["topn_1024_exact"])
+def test_retina_select_top_n(ffi, name):
+    logits, a, c, top_n = rc.topn_cases()[name]
+    assert _check_select(ffi, logits, a, c, top_n) == [top_n] * 4
+
+
+@pytest.mark.parametrize("kind", ["distinct", "tie"])
+@pytest.mark.parametrize("n", rc.BORDER_ROWS)
+def test_retina_select_slice_borders(ffi, n, kind):
+    logits, a, c, top_n = rc.border_cases()["border_%s_%d" % (kind, n)]
+    counts = _check_select(ffi, logits, a, c, top_n)
+    assert counts == [min(64, rc.candidates(logits[0][0])), 1]
+
+
+def test_retina_select_five_levels_three_images(ffi):
+    logits, a, c, top_n = rc.geometry_case()
+    counts = _check_select(ffi, logits, a, c, top_n)
+    assert counts == [min(top_n, lg[0].size if rc.geometry_kind(l, n) < 0 else rc.geometry_kind(l, n), lg[0].size) for l, lg in enumerate(logits) for n in range(3)]
+
+
+@pytest.mark.parametrize("thr", rc.THRESHOLDS)
+def test_retina_select_thresholds(ffi, thr):
+    """The pre-filter may only drop what the sigmoid test drops: the row holds the floats around the crossing of thr, a grid around logit(thr) - 0.25 and the
+    special logits.  With the pre-filter as first built (`x > logit(thr) - 0.25` for 0 < thr < 1, `x > -inf` otherwise) this test returned 7 of the 8 numbers
+    at thr -1 and 0 (the -inf logit was lost to `-inf > -inf`) and 261 of 520 at thr 1e-45 and 1e-40, which lie under the sigmoid's floor of 4.2e-39: every
+    logit at or under the pre-filter was dropped although its sigmoid exceeds thr.  The other eleven thresholds passed."""
+    logits, a, c, top_n = rc.threshold_case(thr)
+    counts = _check_select(ffi, logits, a, c, top_n, thr)
+    assert counts == [rc.candidates(logits[0], thr)]
+
+
+def _check_decode(ffi, case, min_size=0.0):
+    logits, deltas, anchors, hw = case
+    sel, dec = ffi.retina_select(logits, rc.A, rc.TOP_N, 0.05, deltas, anchors, hw, min_size=float(min_size))
+    kept = []
+    for l in range(len(logits)):
+        for n in range(2):
+            s, i = rr.select_level(logits[l][n])
+            assert np.array_equal(sel[l][n][1], i)
+            b, sc, lb = rr.decode_level(s, i, deltas[l][n], anchors[l], hw[n][1], hw[n][0], min_size=min_size)
+            gb, gs, gl = dec[l][n]
+            assert len(gs) == len(sc), (l, n, len(gs), len(sc))
+            assert np.array_equal(_bits(gb), _bits(b)) and np.array_equal(_bits(gs), _bits(sc)) and np.array_equal(gl, lb)
+            kept.append((len(s), len(sc)))
+    return kept
+
+
+def test_retina_decode_one_pixel_image(ffi):
+    assert all(k == m > 0 for k, m in _check_decode(ffi, rc.decode_edge_case("tiny_image")))
+
+
+def test_retina_decode_min_size_edge(ffi):
+    """min_size equal to a box's side + 1 keeps it (>=), the next float drops it; a min_size over every box leaves counts of 0 and filled rows."""
+    case = rc.decode_edge_case("zero_deltas")
+    m, m_up = rc.min_size_edge()
+    at, up = _check_decode(ffi, case, m), _check_decode(ffi, case, m_up)
+    assert up[0][1] < at[0][1] < at[0][0]
+    assert all(m == 0 and k > 0 for k, m in _check_decode(ffi, case, 1e9))
+
+
+def test_retina_decode_special_deltas(ffi):
+    """NaN in dx / dy makes a NaN box, dropped by the size test; +-inf clips to the border; a NaN dw takes the clamp's value."""
+    assert all(k - m >= 2 for k, m in _check_decode(ffi, rc.decode_edge_case("special_deltas")))
+
+
+def _check_post(ffi, case, nms_flags=0, det=100, cap=128, ref=None):
     B, S, Lb, cnt = rc.pack_post(case)
-    got = ffi.retina_postprocess(B, S, Lb, cnt, 81, 0.4, det, cap, nms_flags)
-    ref = rc.ref_post(case, nms_flags, det, cap)
+    got = ffi.retina_postprocess(B, S, Lb, cnt, case.get("ncls", 81), 0.4, det, cap, nms_flags)
+    ref = rc.ref_post(case, nms_flags, det, cap) if ref is None else ref
+    assert len(got) == len(ref)
     for n, (g, r) in enumerate(zip(got, ref)):
         assert len(g[1]) == len(r[1]), (n, len(g[1]), len(r[1]))
         assert np.array_equal(g[2], r[2]), n
@@ -143,6 +211,33 @@ def test_retina_postprocess_iou_at_threshold(ffi):
 def test_retina_postprocess_uncut(ffi):
     """det_per_img 0: no cut; cap alone bounds the rows."""
     _check_post(ffi, POST["one_class_5000"], det=0, cap=4096)
+
+
+# ---- capacity, class range and the cut's edges (tests/test_retinanet_cpu.py: test_full_cases_reach_the_capacity, test_edge_post_cases_discriminate)
+@pytest.mark.parametrize("det, cap", [(100, 128), (0, 8192)])
+@pytest.mark.parametrize("name", ["full_one_class", "full_100_then_8092", "full_255_classes", "batch_8192_0_1"])
+def test_retina_postprocess_full(ffi, name, det, cap):
+    """All 8192 slots (the 13-bit slot field full, 128 matrix words per row): one class over 128 words; a class that starts inside a word and spans 127;
+    labels 254 / 255 of ncls 256 with a class of 65 words from word 63; 8192, 0 and 1 candidates in one launch."""
+    counts = _check_post(ffi, rc.full_cases()[name], det=det, cap=cap, ref=rc.full_ref(name, det, cap))
+    assert counts[0] >= 100 if det else counts[0] > 1000
+    if name == "batch_8192_0_1":
+        assert counts[1:] == [0, 1]
+
+
+@pytest.mark.parametrize("name", ["ncls_2", "labels_out_of_range_ncls_2", "labels_out_of_range_ncls_81"])
+def test_retina_postprocess_class_range(ffi, name):
+    counts = _check_post(ffi, rc.edge_post_cases()[name])
+    assert counts == [6] or name == "ncls_2"
+
+
+@pytest.mark.parametrize("name, dets, counts", [("cut_k40", (1, 39, 40, 41, 0), (1, 40, 40, 40, 40)), ("cut_k40_zeros", (1, 32, 39, 40, 41, 0), (1, 34, 40, 40, 40, 40))])
+def test_retina_postprocess_cut_edges(ffi, name, dets, counts):
+    """det_per_img 1, one under the number kept (the tie at the cut keeps both), the number kept, one over; a cut inside a group of +0.0 and -0.0."""
+    for det, want in zip(dets, counts):
+        assert _check_post(ffi, rc.edge_post_cases()[name], det=det, cap=64) == [want], det
+    for flags in (4, 7):
+        _check_post(ffi, rc.edge_post_cases()[name], nms_flags=flags, det=39, cap=64)
 
 
 @pytest.mark.parametrize("act", [0, 1])
