@@ -1,6 +1,6 @@
 // engine.h -- model engine: packed-weight registry, named activation buffers, per-model forward graphs (yolact.cpp, maskrcnn.cpp, pose2seg.cpp, retinanet.cpp).
 #pragma once
-#include "rpn_levels.h"
+#include "tail_launch.h"
 #include <stdarg.h>
 
 #include <functional>
@@ -293,7 +293,7 @@ int maskrcnn_forward(Engine& e, const float* d_images, int N);
 int eng_next_event(Engine& e, hipEvent_t* ev);
 int maskrcnn_paste(Engine& e, const float* h_ratios_wh, int out_h, int out_w);
 
-// kernels implemented in other translation units
+// kernels implemented in other translation units (the detection tail's launchers: tail_launch.h)
 int conv2d_launch(const isegmi_conv_desc* d, const float* in, const float* w, const float* scale, const float* shift,
                   const float* res, float* out, hipStream_t st);
 int conv2d_f16_launch(const isegmi_conv_desc* d, const void* in, const void* w, const float* scale, const float* shift, const void* res,
@@ -310,15 +310,12 @@ int bottleneck_f16_launch(const isegmi_bottleneck_desc* d, const void* x, const 
                           const float* s2, const float* b2, const void* w3, const float* s3, const float* b3, const void* wd, const float* sd,
                           const float* bd, void* out, hipStream_t st);
 int pad_c3_to_f16_halo_launch(const float* in, int N, int H, int W, void* out, hipStream_t st);
-int avgpool_full_launch(const float* x, int64_t R, int HW, int C, float* out, hipStream_t st);
 int resize_bilinear_f16_launch(const void* in, int N, int H, int W, int C, int Ho, int Wo, const void* add, int relu, void* out, hipStream_t st);
 int maxpool_to_f16_launch(const void* in, int in_f16, int N, int H, int W, int C, int k, int s, int p, void* out, hipStream_t st);
 int nearest2x_add_f16_launch(const void* coarse, int N, int Hc, int Wc, int C, const void* lat, int H, int W, void* out, hipStream_t st);
 int roi_align_f16_launch(const void* const* feats, const int* Hs, const int* Ws, const float* scales, int nlevels, const float* rois,
                          const int* counts, int N, int K, int C, int PH, int PW, int g, int k_min, void* out, hipStream_t st,
                          const int* order = nullptr, const void* tab = nullptr, int aligned = 0);
-int roi_prep_launch(const float* rois, const int* counts, int N, int K, const int* Hs, const int* Ws, const float* scales, int nlevels, int k_min, int C,
-                    int PH, int PW, int esize, int* order, void* tab, hipStream_t st, int aligned = 0);
 int mask_logits_select_f16_launch(const void* feat, int R, int HW, int C, const float* w, const float* b, const int* labels, float* out,
                                   hipStream_t st);
 int maxpool_launch(const float* in, int N, int H, int W, int C, int k, int s, int p, float* out, hipStream_t st);
@@ -339,8 +336,6 @@ int pad_c3_c4_launch(const float* in, int64_t npix, float* out, hipStream_t st);
 int preprocess_u8_launch(const uint8_t* in, int N, int Hin, int Win, float* out, int Hout, int Wout, int Hpad, int Wpad, int64_t out_img_stride,
                          const float* mean3, const float* std3, int swap_rb, hipStream_t st);
 int pad_c3_c32_launch(const float* in, int64_t npix, float* out, hipStream_t st);
-int topk_launch(const float* keys, int64_t row_stride, int rows, int n, int k, const int* limit, int rows_per_limit,
-                float* out_vals, int* out_idx, int* out_cnt, hipStream_t st);
 int yolact_detect_launch(const isegmi_yolact_detect_args* a, hipStream_t st);
 int yolact_masks_launch(const float* proto, const float* coeffs, const float* boxes, const int* count, int N, int PH, int PW,
                         int mask_dim, int K, int h, int w, float* ws_lo, uint8_t* out_masks, int64_t* out_boxes, hipStream_t st,

@@ -12,31 +12,6 @@
 
 namespace isegmi {
 
-int nms_launch(const float*, const float*, int, int, float, int, int, int, int*, int*, hipStream_t);
-int rpn_sigmoid_launch(const float* head, int64_t total, int A, int CH, float* prob, hipStream_t st);
-int rpn_decode_nms_launch(const float* head, const float* anchors, const float* tk_vals, const int* tk_idx, const int* tk_cnt,
-                          const int* image_hw, int N, int HWA, int A, int CH, int pre_nms, int post_nms, float thr, float min_size,
-                          int ge, int level, int L, int post_cap, float* out_boxes, float* out_scores, int* out_cnt, void* nms_ws,
-                          hipStream_t st);
-int grid_anchors_launch(const float* base, int A, int stride, int gh, int gw, float* out, hipStream_t st);
-int sum_counts_launch(const int* cnt, int N, int L, int* total, hipStream_t st);
-int gather_proposals_launch(const float* cand_boxes, const float* fin_vals, const int* fin_idx, const int* fin_cnt, int N,
-                            int cand_per_img, int K, float* props, float* prop_scores, int* prop_cnt, hipStream_t st);
-int roi_align_launch(const float* const* feats, const int* Hs, const int* Ws, const float* scales, int nlevels, const float* rois,
-                     const int* counts, int N, int K, int C, int PH, int PW, int g, int k_min, int fixed_level, float* out,
-                     int* out_level, hipStream_t st, const int* order = nullptr, const void* tab = nullptr, int aligned = 0);
-int box_postprocess_launch(const isegmi_box_post_args* a, hipStream_t st);
-int mask_logits_select_launch(const float* feat, int R, int HW, int C, const float* w, const float* b, const int* labels, float* out,
-                              hipStream_t st);
-int paste_masks_launch(const float* masks, const float* boxes, const int* counts, int N, int K, int M, int im_h, int im_w, float thr,
-                       uint8_t* out, hipStream_t st, int* win, bool clear);
-int scale_boxes_launch(const float* boxes, const float* ratios, int N, int K, float* out, hipStream_t st);
-int topk_launch(const float* keys, int64_t row_stride, int rows, int n, int k, const int* limit, int rows_per_limit, float* out_vals,
-                int* out_idx, int* out_cnt, hipStream_t st);
-int64_t topk_scratch_elems(int rows, int n, int k);
-int topk_launch_ws(const float* keys, int64_t row_stride, int rows, int n, int k, const int* limit, int rows_per_limit, float* out_vals,
-                   int* out_idx, int* out_cnt, float* ws_vals, int* ws_idx, hipStream_t st);
-
 // SURVEY 7.2 / App. A.6-A.7 semantic forks as engine parameters (defaults = the maskrcnn-benchmark CUDA path): "nms_ge" 1 suppress on iou >= thr;
 // "nms_plus_one" 0 plain areas in the NMS IoU; "nms_index_order" 1 a class's detections in ascending proposal index (CPU nonzero order);
 // "roi_aligned" 1 ROIAlign(aligned=True).

@@ -15,100 +15,11 @@
 // Reference anchor: COCODemo.run_on_opencv_image (README.md:331) reaches every one of these.
 #include "../../include/isegmi.h"
 #include "common.h"
-#include "rpn_levels.h"
-#include "detmath.h"
+#include "tail_launch.h"
+#include "detbox.h"
 #include <string.h>
 
 namespace isegmi {
-
-// scores order as floats: -0.0 == +0.0 share one key and the index decides (ora_nms's comparator; csrc/select.hip has the contract).  NaN scores: outside it.
-__device__ __forceinline__ unsigned f2ord_(float f) {
-    const unsigned u = __float_as_uint(f);
-    if (u == 0x80000000u) return 0x80000000u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f_(unsigned o) {
-    const unsigned u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
-    return __uint_as_float(u);
-}
-
-// ------------------------------------------------------------------ box coder
-__device__ __forceinline__ float4 decode_box(const float4 a, const float4 d, float wx, float wy, float ww, float wh) {
-    const float clipv = 4.135166556742356f;
-    const float widths = a.z - a.x + 1.0f, heights = a.w - a.y + 1.0f;
-    const float ctr_x = a.x + 0.5f * widths, ctr_y = a.y + 0.5f * heights;
-    const float dx = dm_div(d.x, wx), dy = dm_div(d.y, wy);
-    float dw = dm_div(d.z, ww), dh = dm_div(d.w, wh);
-    dw = dw < clipv ? dw : clipv;
-    dh = dh < clipv ? dh : clipv;
-    const float pcx = dx * widths + ctr_x, pcy = dy * heights + ctr_y;
-    const float pw = dm_exp(dw) * widths, ph = dm_exp(dh) * heights;
-    float4 o;
-    o.x = pcx - 0.5f * pw;
-    o.y = pcy - 0.5f * ph;
-    o.z = pcx + 0.5f * pw - 1.0f;
-    o.w = pcy + 0.5f * ph - 1.0f;
-    return o;
-}
-__device__ __forceinline__ float clampf(float v, float hi) { return v < 0.0f ? 0.0f : (v > hi ? hi : v); }
-__device__ __forceinline__ float4 clip_box(float4 b, float im_w, float im_h) {
-    const float mx = im_w - 1.0f, my = im_h - 1.0f;
-    b.x = clampf(b.x, mx); b.y = clampf(b.y, my); b.z = clampf(b.z, mx); b.w = clampf(b.w, my);
-    return b;
-}
-__device__ __forceinline__ float iou_one(const float4 a, const float4 b, float one) {
-    const float aa = (a.z - a.x + one) * (a.w - a.y + one);
-    const float ab = (b.z - b.x + one) * (b.w - b.y + one);
-    const float xx1 = a.x > b.x ? a.x : b.x, yy1 = a.y > b.y ? a.y : b.y;
-    const float xx2 = a.z < b.z ? a.z : b.z, yy2 = a.w < b.w ? a.w : b.w;
-    float w = xx2 - xx1 + one, h = yy2 - yy1 + one;
-    w = w > 0.0f ? w : 0.0f;
-    h = h > 0.0f ? h : 0.0f;
-    const float inter = w * h;
-    return dm_div(inter, aa + ab - inter);
-}
-
-// Division-free, EXACT form of `RN(inter / uni) > thr` (ge: `>= thr`).  RN is monotone, so the fp32 quotient
-// exceeds thr iff the real quotient lies beyond the midpoint between thr and its fp32 neighbour (ties go to the
-// even mantissa).  inter, uni are 24-bit, the midpoint 25-bit: their product is exact in fp64.  ~6 instructions
-// instead of an IEEE-correct fp32 division (~40) in the innermost NMS loop; bit-identical to the oracle's division.
-struct IouThr {
-    double m;       // midpoint
-    bool tie_true;  // result when inter == m * uni exactly
-};
-__device__ __forceinline__ IouThr make_iou_thr(float thr, int ge) {
-    IouThr t;
-    const unsigned b = __float_as_uint(thr);  // thr > 0
-    if (ge) {  // q >= thr  <=>  x >= mid(pred(thr), thr) (tie -> thr iff thr's mantissa is even)
-        const float lo = __uint_as_float(b - 1u);
-        t.m = 0.5 * ((double)lo + (double)thr);
-        t.tie_true = (b & 1u) == 0u;
-    } else {   // q > thr   <=>  x >= mid(thr, succ(thr)) (tie -> succ iff succ's mantissa is even)
-        const float hi = __uint_as_float(b + 1u);
-        t.m = 0.5 * ((double)thr + (double)hi);
-        t.tie_true = ((b + 1u) & 1u) == 0u;
-    }
-    return t;
-}
-__device__ __forceinline__ bool iou_exceeds(const float4 a, const float4 b, float one, const IouThr t) {
-    const float aa = (a.z - a.x + one) * (a.w - a.y + one);
-    const float ab = (b.z - b.x + one) * (b.w - b.y + one);
-    const float xx1 = a.x > b.x ? a.x : b.x, yy1 = a.y > b.y ? a.y : b.y;
-    const float xx2 = a.z < b.z ? a.z : b.z, yy2 = a.w < b.w ? a.w : b.w;
-    float w = xx2 - xx1 + one, h = yy2 - yy1 + one;
-    w = w > 0.0f ? w : 0.0f;
-    h = h > 0.0f ? h : 0.0f;
-    const float inter = w * h;
-    const float uni = aa + ab - inter;
-    if (!(uni > 0.0f)) return false;  // 0/0 or negative union: NaN / non-positive quotient never exceeds thr > 0
-    const double lhs = (double)inter, rhs = t.m * (double)uni;
-    return lhs > rhs || (lhs == rhs && t.tie_true);
-}
-
-// The `ge` / `nms_flags` argument of the engine-level launches below is the OR of the App. A.6 forks (include/isegmi.h): ISEGMI_NMS_GE (1) suppress on
-// iou >= thr instead of >; ISEGMI_NMS_NO_PLUS_ONE (2) plain areas instead of the legacy +1; ISEGMI_NMS_INDEX_ORDER (4, box post-processing only) a class's
-// kept detections in ascending proposal index (the CPU NMS's nonzero order) instead of score order.
-__device__ __forceinline__ float nms_one(int flags) { return (flags & ISEGMI_NMS_NO_PLUS_ONE) ? 0.0f : 1.0f; }
 
 // ------------------------------------------------------------------ greedy NMS core (block = NT threads)
 // sb[0..n) boxes in visiting order (score desc, index asc); pre_dead[i] != 0 marks boxes removed beforehand.
@@ -170,22 +81,7 @@ __device__ int nms_block(NmsSharedT<CAP>& S, int n, float thr, float one, int ge
     return S.kc;
 }
 
-// Generic op: one problem per block; boxes pre-sorted by the caller? No: sorts here (n <= 1024).
-// keys: (score desc, idx asc) bitonic in LDS.
-__device__ void sort_desc_1024(unsigned long long* keys, int npow2) {
-    for (int size = 2; size <= npow2; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = threadIdx.x; t < npow2 / 2; t += blockDim.x) {
-                const int lo = ((t / stride) * stride * 2) + (t % stride), hi = lo + stride;
-                const bool desc = ((lo & size) == 0);
-                const unsigned long long x = keys[lo], y = keys[hi];
-                if (desc ? (x < y) : (x > y)) { keys[lo] = y; keys[hi] = x; }
-            }
-            __syncthreads();
-        }
-}
-__device__ __forceinline__ int next_pow2(int n) { int p = 2; while (p < n) p <<= 1; return p; }
-
+// Generic op: one problem per block, sorted here by (score desc, idx asc) (n <= 1024).
 // boxes [P][n][4], scores [P][n] (any order); keep [P][n] original indices in score order; cnt [P]
 __global__ __launch_bounds__(256) void nms_kernel(const float* __restrict__ boxes, const float* __restrict__ scores, int n,
                                                    float thr, int plus_one, int ge, int max_keep, int* __restrict__ keep,
@@ -197,17 +93,14 @@ __global__ __launch_bounds__(256) void nms_kernel(const float* __restrict__ boxe
     const float* s = scores + (int64_t)pb * n;
     const int np2 = next_pow2(n);
     for (int i = threadIdx.x; i < np2; i += 256)
-        keys[i] = i < n ? (((unsigned long long)f2ord_(s[i]) << 32) | (unsigned long long)(0xffffffffu - (unsigned)i)) : 0ull;
+        keys[i] = i < n ? det_key(s[i], i) : 0ull;
     __syncthreads();
-    sort_desc_1024(keys, np2);
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const int src = (int)(0xffffffffu - (unsigned)(keys[i] & 0xffffffffull));
-        S.sb[i] = *(const float4*)(b + (int64_t)src * 4);
-    }
+    bitonic_sort<true>(keys, np2, blockDim.x);
+    for (int i = threadIdx.x; i < n; i += 256) S.sb[i] = *(const float4*)(b + (int64_t)det_key_index(keys[i]) * 4);
     __syncthreads();
     const int kc = nms_block(S, n, thr, plus_one ? 1.0f : 0.0f, ge, max_keep, nullptr);
     for (int i = threadIdx.x; i < kc; i += 256)
-        keep[(int64_t)pb * n + i] = (int)(0xffffffffu - (unsigned)(keys[S.kept[i]] & 0xffffffffull));
+        keep[(int64_t)pb * n + i] = det_key_index(keys[S.kept[i]]);
     if (threadIdx.x == 0) cnt[pb] = kc;
 }
 
@@ -223,10 +116,10 @@ __global__ __launch_bounds__(1024) void nms_big_kernel(const float* __restrict__
     const float* sc = scores + (int64_t)pb * n;
     const int np2 = next_pow2(n);
     for (int i = threadIdx.x; i < np2; i += blockDim.x)
-        keys[i] = i < n ? (((unsigned long long)f2ord_(sc[i]) << 32) | (unsigned long long)(0xffffffffu - (unsigned)i)) : 0ull;
+        keys[i] = i < n ? det_key(sc[i], i) : 0ull;
     __syncthreads();
-    sort_desc_1024(keys, np2);
-    for (int i = threadIdx.x; i < n; i += blockDim.x) order[i] = (unsigned short)(0xffffffffu - (unsigned)(keys[i] & 0xffffffffull));
+    bitonic_sort<true>(keys, np2, blockDim.x);
+    for (int i = threadIdx.x; i < n; i += blockDim.x) order[i] = (unsigned short)det_key_index(keys[i]);
     __syncthreads();
     for (int i = threadIdx.x; i < n; i += blockDim.x) S.sb[i] = *(const float4*)(b + (int64_t)order[i] * 4);
     __syncthreads();
@@ -272,6 +165,18 @@ __global__ void rpn_sigmoid_levels_kernel(const RpnLevels b, float* __restrict__
     }
 }
 
+// candidate j of image n: BoxCoder(1, 1, 1, 1) on the anchor tk_idx names, clipped to the image
+__device__ __forceinline__ float4 rpn_candidate_box(const float* __restrict__ head, const float* __restrict__ anchors,
+                                                    const int* __restrict__ tk_idx, int n, int j, int pre_nms, int HWA, int A, int CH,
+                                                    float im_w, float im_h) {
+    const int idx = tk_idx[(int64_t)n * pre_nms + j];
+    const int pix = idx / A, a = idx - pix * A;
+    const float* hp = head + ((int64_t)n * (HWA / A) + pix) * CH + A + a * 4;
+    const float4 d = make_float4(hp[0], hp[1], hp[2], hp[3]);
+    const float4 an = *(const float4*)(anchors + (int64_t)idx * 4);
+    return clip_box(decode_box(an, d, 1.f, 1.f, 1.f, 1.f), im_w, im_h);
+}
+
 // grid (N); one (image, level) per block.  tk_vals/tk_idx [N][pre_nms] sorted; tk_cnt [N].
 // out_boxes [N][L][post_cap][4], out_scores [N][L][post_cap] (-1 beyond count), out_cnt [N][L].
 template <int CAP>
@@ -288,15 +193,9 @@ __global__ __launch_bounds__(1024) void rpn_decode_nms_kernel(const float* __res
     const int cnt = tk_cnt[n];
     const float im_h = (float)image_hw[2 * n], im_w = (float)image_hw[2 * n + 1];
     for (int j = threadIdx.x; j < cnt; j += blockDim.x) {
-        const int idx = tk_idx[(int64_t)n * pre_nms + j];
-        const int pix = idx / A, a = idx - pix * A;
-        const float* hp = head + ((int64_t)n * (HWA / A) + pix) * CH + A + a * 4;
-        const float4 d = make_float4(hp[0], hp[1], hp[2], hp[3]);
-        const float4 an = *(const float4*)(anchors + (int64_t)idx * 4);
-        float4 b = clip_box(decode_box(an, d, 1.f, 1.f, 1.f, 1.f), im_w, im_h);
+        const float4 b = rpn_candidate_box(head, anchors, tk_idx, n, j, pre_nms, HWA, A, CH, im_w, im_h);
         S.sb[j] = b;
-        const float ws = b.z - b.x + 1.0f, hs = b.w - b.y + 1.0f;
-        dead[j] = (ws >= min_size && hs >= min_size) ? 0 : 1;
+        dead[j] = box_min_size_ok(b, min_size) ? 0 : 1;
     }
     __syncthreads();
     const int kc = nms_block(S, cnt, thr, nms_one(ge), ge & ISEGMI_NMS_GE, post_nms, dead);
@@ -315,8 +214,8 @@ __global__ __launch_bounds__(1024) void rpn_decode_nms_kernel(const float* __res
 }
 
 // Greedy NMS scan over a finished suppression matrix (ONE wave; M in LDS, NMS_CAP/64 words per row: bit j of M[i][w] set iff
-// box 64w+j comes after box i and IoU(i, j) exceeds the threshold).  A chunk of 64 is resolved from its diagonal words by a
-// 64-step scalar chain (readlane / bitcmp / andn2: no IoU, no memory), then lane (w, q) ORs the kept rows' word w into the
+// box 64w+j comes after box i and IoU(i, j) exceeds the threshold).  A chunk of 64 is resolved from its diagonal words
+// (nms_resolve_chunk), then lane (w, q) ORs the kept rows' word w into the
 // `removed` words with 16 unconditional LDS reads.  dead[i] != 0 removes box i beforehand; at most max_keep boxes are kept.
 // Returns the kept count (uniform); kept[] holds the kept positions in visiting order.
 __device__ __forceinline__ int nms_bit_scan(const unsigned long long* M, int cnt, int max_keep, const unsigned char* dead, unsigned short* kept) {
@@ -339,17 +238,10 @@ __device__ __forceinline__ int nms_bit_scan(const unsigned long long* M, int cnt
             if (kc >= post_nms) break;
             const int i = (c << 6) + lane;
             const unsigned long long d = i < cnt ? M[i * W + c] : 0ull;
-            const int dlo = (int)(unsigned)d, dhi = (int)(unsigned)(d >> 32);
             const unsigned long long rc = __shfl(rem, c, 64);
-            unsigned long long alive = ~(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(rc >> 32)) << 32) |
-                                         (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)rc));
-#pragma unroll
-            for (int b = 0; b < 64; ++b) {  // box b survives => it strikes its later chunk-mates; survivors are the kept ones
-                const unsigned long long db = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane(dhi, b) << 32) |
-                                              (unsigned long long)(unsigned)__builtin_amdgcn_readlane(dlo, b);
-                alive &= ((alive >> b) & 1ull) ? ~db : ~0ull;
-            }
-            unsigned long long keepm = alive;
+            const unsigned long long cand = ~(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(rc >> 32)) << 32) |
+                                              (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)rc));
+            unsigned long long keepm = nms_resolve_chunk(cand, d);
             while (kc + __popcll(keepm) > post_nms) keepm &= ~(1ull << (63 - __builtin_clzll(keepm)));  // uniform; last chunk only
             if ((keepm >> lane) & 1ull) kept[kc + __popcll(keepm & lt_mask)] = (unsigned short)i;
             unsigned long long acc = 0ull;
@@ -369,7 +261,7 @@ __device__ __forceinline__ int nms_bit_scan(const unsigned long long* M, int cnt
     return kc_out;
 }
 
-// The suppression matrix of n <= NMS_CAP boxes built by ONE block (all its waves): wave-task (r, w), r <= w, owns rows
+// The suppression matrix of n <= NMS_CAP boxes (sb: NMS_CAP entries in LDS) built by ONE block (all its waves): wave-task (r, w), r <= w, owns rows
 // 64r..64r+63 (lane = row) x the 64 broadcast column boxes of word w.  For problems that have a block to themselves anyway
 // (a crowded class in the per-class box NMS: 600 candidates took 250 us in nms_block's chunk-against-kept-list form).
 __device__ void nms_matrix_block(const float4* sb, int n, float thr, float one, int ge, unsigned long long* M) {
@@ -379,18 +271,11 @@ __device__ void nms_matrix_block(const float4* sb, int n, float thr, float one, 
     const int nwords = (n + 63) >> 6;
     const int npairs = nwords * (nwords + 1) / 2;
     for (int pair = wave; pair < npairs; pair += nw) {
-        int w = 0;
-        while ((w + 1) * (w + 2) / 2 <= pair) ++w;
-        const int r = pair - w * (w + 1) / 2;
+        int r, w;
+        tri_pair(pair, r, w);
         const int i = (r << 6) + lane;
-        const float4 mine = sb[i < n ? i : 0];
-        unsigned long long m = 0ull;
-#pragma unroll 8
-        for (int b = 0; b < 64; ++b) {
-            const int j = (w << 6) + b;
-            const bool sup = j > i && j < n && iou_exceeds(mine, sb[j < n ? j : 0], one, T);
-            m |= sup ? (1ull << b) : 0ull;
-        }
+        // the columns are read in place: sb holds NMS_CAP boxes, those past n are stale and not eligible
+        const unsigned long long m = nms_tile_word(sb[i < n ? i : 0], sb + (w << 6), i, w, one, T, [n](int j, int) { return j < n; });
         if (i < n) M[i * W + w] = m;
     }
 }
@@ -403,17 +288,6 @@ __device__ void nms_matrix_block(const float4* sb, int n, float thr, float one, 
 //       chunk of 64 is resolved from its diagonal words by a 64-step scalar chain (readlane / bitcmp / andn2), then lane
 //       (w, q) ORs the kept rows' word w into the `removed` words with 16 unconditional LDS reads.
 // Same predicate, same visiting order => the kept list is identical to nms_block's.  ws: [N][NMS_CAP][NMS_CAP/64] u64.
-__device__ __forceinline__ float4 rpn_candidate_box(const float* __restrict__ head, const float* __restrict__ anchors,
-                                                    const int* __restrict__ tk_idx, int n, int j, int pre_nms, int HWA, int A, int CH,
-                                                    float im_w, float im_h) {
-    const int idx = tk_idx[(int64_t)n * pre_nms + j];
-    const int pix = idx / A, a = idx - pix * A;
-    const float* hp = head + ((int64_t)n * (HWA / A) + pix) * CH + A + a * 4;
-    const float4 d = make_float4(hp[0], hp[1], hp[2], hp[3]);
-    const float4 an = *(const float4*)(anchors + (int64_t)idx * 4);
-    return clip_box(decode_box(an, d, 1.f, 1.f, 1.f, 1.f), im_w, im_h);
-}
-
 __global__ __launch_bounds__(256) void rpn_nms_matrix_kernel(const RpnLevels b, const int* __restrict__ tk_idx, const int* __restrict__ tk_cnt,
                                                              const int* __restrict__ image_hw, unsigned long long* __restrict__ ws) {
     constexpr int W = NMS_CAP / 64;
@@ -427,26 +301,16 @@ __global__ __launch_bounds__(256) void rpn_nms_matrix_kernel(const RpnLevels b, 
     const int cnt = tk_cnt[row];
     const int nwords = (cnt + 63) >> 6;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int pair = blockIdx.x * 4 + wave;  // wave-uniform
-    int w = 0;
-    while ((w + 1) * (w + 2) / 2 <= pair) ++w;
-    const int r = pair - w * (w + 1) / 2;
+    int r, w;
+    tri_pair(blockIdx.x * 4 + wave, r, w);  // wave-uniform
     if (w >= nwords) return;  // whole wave; no block-level barrier below
     const float im_h = (float)image_hw[2 * n], im_w = (float)image_hw[2 * n + 1];
     const IouThr T = make_iou_thr(b.thr, b.ge & ISEGMI_NMS_GE);
     const float one = nms_one(b.ge);
     const int i = (r << 6) + lane, jc = (w << 6) + lane;
     const float4 mine = rpn_candidate_box(head, anchors, tk_idx, n, i < cnt ? i : 0, pre_nms, HWA, A, CH, im_w, im_h);
-    cols[wave][lane] = rpn_candidate_box(head, anchors, tk_idx, n, jc < cnt ? jc : 0, pre_nms, HWA, A, CH, im_w, im_h);
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's own LDS writes have landed
-    unsigned long long m = 0ull;
-#pragma unroll 8
-    for (int bb = 0; bb < 64; ++bb) {
-        const int j = (w << 6) + bb;
-        const bool sup = j > i && j < cnt && iou_exceeds(mine, cols[wave][bb], one, T);
-        m |= sup ? (1ull << bb) : 0ull;
-    }
+    nms_stage_cols(cols[wave], lane, rpn_candidate_box(head, anchors, tk_idx, n, jc < cnt ? jc : 0, pre_nms, HWA, A, CH, im_w, im_h));
+    const unsigned long long m = nms_tile_word(mine, cols[wave], i, w, one, T, [cnt](int j, int) { return j < cnt; });
     if (i < cnt) ws[((int64_t)row * NMS_CAP + i) * W + w] = m;
 }
 
@@ -482,8 +346,7 @@ __global__ __launch_bounds__(1024) void rpn_nms_scan_kernel(const RpnLevels b, c
     for (int j = tid; j < cnt; j += 1024) {
         const float4 bx = rpn_candidate_box(head, anchors, tk_idx, n, j, pre_nms, HWA, A, CH, im_w, im_h);
         sb[j] = bx;
-        const float ws_ = bx.z - bx.x + 1.0f, hs = bx.w - bx.y + 1.0f;
-        dead[j] = (ws_ >= min_size && hs >= min_size) ? 0 : 1;
+        dead[j] = box_min_size_ok(bx, min_size) ? 0 : 1;
     }
     __syncthreads();
     if (wave == 0) {
@@ -937,17 +800,17 @@ __global__ __launch_bounds__(BOX_NMS_THREADS) void box_cls_nms_kernel(const floa
         const unsigned long long bm = __ballot(ok);
         if (ok) {
             const int pos = run + __popcll(bm & ((1ull << lane) - 1ull));
-            keys[pos] = ((unsigned long long)f2ord_(p) << 32) | (unsigned long long)(0xffffffffu - (unsigned)i);
+            keys[pos] = det_key(p, i);
         }
         run += __popcll(bm);
     }
     const int np2 = next_pow2(m > 1 ? m : 2);
     for (int i = m + tid; i < np2; i += NT) keys[i] = 0ull;
     __syncthreads();
-    sort_desc_1024(keys, np2);
+    bitonic_sort<true>(keys, np2, blockDim.x);
     const float im_h = (float)image_hw[2 * n], im_w = (float)image_hw[2 * n + 1];
     for (int q = tid; q < m; q += NT) {
-        const int i = (int)(0xffffffffu - (unsigned)(keys[q] & 0xffffffffull));
+        const int i = det_key_index(keys[q]);
         const float4 pr = *(const float4*)(props + ((int64_t)n * R + i) * 4);
         const float* dp = regr + ((int64_t)n * R + i) * regr_stride + 4 * j;
         const float4 d = make_float4(dp[0], dp[1], dp[2], dp[3]);
@@ -990,7 +853,7 @@ __global__ __launch_bounds__(BOX_NMS_THREADS) void box_cls_nms_kernel(const floa
         __syncthreads();
         for (int q = tid; q < kc; q += NT) {
             const int src = S.kept[q];
-            slot[(int)(0xffffffffu - (unsigned)(keys[src] & 0xffffffffull))] = (unsigned short)src;
+            slot[det_key_index(keys[src])] = (unsigned short)src;
         }
         __syncthreads();
         int run = 0;   // kept proposals before this pass of NT indices
@@ -1011,7 +874,7 @@ __global__ __launch_bounds__(BOX_NMS_THREADS) void box_cls_nms_kernel(const floa
     for (int q = tid; q < R; q += NT) {
         if (q < kc) {
             const int src = S.kept[q];
-            cand_scores[ob + q] = ord2f_((unsigned)(keys[src] >> 32));
+            cand_scores[ob + q] = det_key_score(keys[src]);
             *(float4*)(cand_boxes + (ob + q) * 4) = S.sb[src];
         } else cand_scores[ob + q] = -1.0f;
     }
@@ -1028,26 +891,16 @@ __global__ __launch_bounds__(256) void box_nms_matrix_kernel(const BoxCrowd crow
     if (m == 0) return;
     const int nwords = (m + 63) >> 6;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int pair = blockIdx.x * 4 + wave;  // wave-uniform
-    int w = 0;
-    while ((w + 1) * (w + 2) / 2 <= pair) ++w;
-    const int r = pair - w * (w + 1) / 2;
+    int r, w;
+    tri_pair(blockIdx.x * 4 + wave, r, w);  // wave-uniform
     if (w >= nwords) return;  // whole wave; no block-level barrier below
     const IouThr T = make_iou_thr(nms_thr, flags & ISEGMI_NMS_GE);
     const float one = nms_one(flags);
     const float4* sb = (const float4*)(crowd.boxes + (int64_t)crow * R * 4);
     const int i = (r << 6) + lane, jc = (w << 6) + lane;
     const float4 mine = sb[i < m ? i : 0];
-    cols[wave][lane] = sb[jc < m ? jc : 0];
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's own LDS writes have landed
-    unsigned long long bits = 0ull;
-#pragma unroll 8
-    for (int bb = 0; bb < 64; ++bb) {
-        const int jj = (w << 6) + bb;
-        const bool sup = jj > i && jj < m && iou_exceeds(mine, cols[wave][bb], one, T);
-        bits |= sup ? (1ull << bb) : 0ull;
-    }
+    nms_stage_cols(cols[wave], lane, sb[jc < m ? jc : 0]);
+    const unsigned long long bits = nms_tile_word(mine, cols[wave], i, w, one, T, [m](int j, int) { return j < m; });
     if (i < m) crowd.matrix[((int64_t)crow * NMS_CAP + i) * W + w] = bits;
 }
 
@@ -1356,7 +1209,7 @@ int gather_proposals_launch(const float* cand_boxes, const float* fin_vals, cons
 
 int roi_align_launch(const float* const* feats, const int* Hs, const int* Ws, const float* scales, int nlevels, const float* rois,
                      const int* counts, int N, int K, int C, int PH, int PW, int g, int k_min, int fixed_level, float* out,
-                     int* out_level, hipStream_t st, const int* order = nullptr, const void* tab = nullptr, int aligned = 0) {
+                     int* out_level, hipStream_t st, const int* order, const void* tab, int aligned) {
     ARG_CHECK(nlevels >= 1 && nlevels <= 4 && C % 4 == 0, "roi_align levels/C");
     RoiLevels lv;
     for (int i = 0; i < 4; ++i) {
@@ -1399,7 +1252,7 @@ int roi_align_launch(const float* const* feats, const int* Hs, const int* Ws, co
 // `order` is given, order [N][K] = each image's RoI rows (n*K + k) sorted by (level, Morton code of the centre on that level's map), rows beyond
 // counts[n] last.  esize = bytes per feature element (4 fp32, 2 fp16): the table holds byte offsets.
 int roi_prep_launch(const float* rois, const int* counts, int N, int K, const int* Hs, const int* Ws, const float* scales, int nlevels, int k_min, int C,
-                    int PH, int PW, int esize, int* order, void* tab, hipStream_t st, int aligned) {  // (default 0 in engine.h)
+                    int PH, int PW, int esize, int* order, void* tab, hipStream_t st, int aligned) {
     ARG_CHECK(nlevels >= 1 && nlevels <= 4 && N > 0 && K > 0 && K <= ROI_ORDER_MAX && PH > 0 && PW > 0 && PH <= 64 && PW <= 64 && C > 0 &&
                   (esize == 2 || esize == 4) && tab,
               "roi_prep: 1..4 levels, K <= 2048");
@@ -1430,11 +1283,6 @@ int softmax_rows_launch(const float* x, int64_t rows, int C, int64_t in_stride, 
     HIP_TRY(hipGetLastError());
     return ISEGMI_OK;
 }
-
-int topk_segmented_launch(const float* keys, int64_t row_stride, int rows, int nseg, int seg_len, int seg_take, int k, const int* limit,
-                          int rows_per_limit, float* out_vals, int* out_idx, int* out_cnt, hipStream_t st);
-int topk_launch(const float* keys, int64_t row_stride, int rows, int n, int k, const int* limit, int rows_per_limit,
-                float* out_vals, int* out_idx, int* out_cnt, hipStream_t st);
 
 // box post-processing for N images: logits -> detections.  Workspaces are caller-provided.
 int box_postprocess_launch(const isegmi_box_post_args* a, hipStream_t st) {

@@ -18,13 +18,8 @@
 
 namespace isegmi {
 
-int grid_anchors_launch(const float* base, int A, int stride, int gh, int gw, float* out, hipStream_t st);
 int maskrcnn_set_image_hw(Engine& e, const int32_t* h_image_hw, int N);
 int maskrcnn_det_cap(Engine& e);
-int64_t retina_select_workspace_bytes(int nl, int N, const int* HW, int A, int C, int top_n);
-int retina_select_launch(const isegmi_retina_select_args* p, hipStream_t st);
-int64_t retina_post_workspace_bytes(int N, int nseg, int seg_len);
-int retina_postprocess_launch(const isegmi_retina_post_args* p, hipStream_t st);
 
 constexpr int RETINA_LEVELS = 5;
 

@@ -11,7 +11,7 @@
 //      <= 1024 winners by (score desc, index asc), then the decode of the selected: deltas and anchor gathered through the flat index,
 //      BoxCoder(10, 10, 5, 5), clip to the unpadded image, min-size test, ordered compaction.
 // The winners of launch 2 are appended to LDS through an atomic counter; the list holds exactly k_eff <= 1024 unique keys and is fully sorted
-// afterwards, so nothing depends on arrival order.  Key order contract: csrc/select.hip's, on the SIGMOID values (two logits may share one).
+// afterwards, so nothing depends on arrival order.  Key order contract: csrc/detbox.h's, on the SIGMOID values (two logits may share one).
 //
 // retina_postprocess.  Per image up to 8192 candidate slots (nseg lists of seg_len, the first seg_cnt of each valid):
 //   1. sort by (class asc, score desc, slot asc) in LDS; gather boxes / scores / labels in that order; class segment bounds;
@@ -22,7 +22,8 @@
 //      ISEGMI_NMS_INDEX_ORDER -- at most cap rows.
 #include "../../include/isegmi.h"
 #include "common.h"
-#include "detmath.h"
+#include "detbox.h"
+#include "tail_launch.h"
 #include <float.h>
 #include <math.h>
 
@@ -35,70 +36,6 @@ constexpr int RETINA_KCAP = 1024;       // top_n the kernels hold
 constexpr int RETINA_NT = 1024;
 constexpr int RETINA_BINS = 2048;       // 11-bit digits: 6 passes over a 64-bit key
 constexpr int RETINA_MAX_SLOTS = 8192;  // candidate slots per image in retina_postprocess: 64 KB of sort keys in LDS
-
-__device__ __forceinline__ unsigned r_f2ord(float f) {
-    const unsigned u = __float_as_uint(f);
-    if (u == 0x80000000u) return 0x80000000u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float r_ord2f(unsigned o) {
-    const unsigned u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
-    return __uint_as_float(u);
-}
-
-// BoxCoder.decode with the legacy +1 widths and the log(1000/16) clamp, clip, IoU: csrc/rcnn_ops.hip's, restated (the oracle's decode_box / clip_box / iou_plus)
-__device__ __forceinline__ float4 r_decode_box(const float4 a, const float4 d, float wx, float wy, float ww, float wh) {
-    const float clipv = 4.135166556742356f;
-    const float widths = a.z - a.x + 1.0f, heights = a.w - a.y + 1.0f;
-    const float ctr_x = a.x + 0.5f * widths, ctr_y = a.y + 0.5f * heights;
-    const float dx = dm_div(d.x, wx), dy = dm_div(d.y, wy);
-    float dw = dm_div(d.z, ww), dh = dm_div(d.w, wh);
-    dw = dw < clipv ? dw : clipv;
-    dh = dh < clipv ? dh : clipv;
-    const float pcx = dx * widths + ctr_x, pcy = dy * heights + ctr_y;
-    const float pw = dm_exp(dw) * widths, ph = dm_exp(dh) * heights;
-    float4 o;
-    o.x = pcx - 0.5f * pw;
-    o.y = pcy - 0.5f * ph;
-    o.z = pcx + 0.5f * pw - 1.0f;
-    o.w = pcy + 0.5f * ph - 1.0f;
-    return o;
-}
-__device__ __forceinline__ float r_clampf(float v, float hi) { return v < 0.0f ? 0.0f : (v > hi ? hi : v); }
-
-// Division-free exact form of RN(inter / uni) > thr (ge: >=); see csrc/rcnn_ops.hip iou_exceeds
-struct RIouThr {
-    double m;
-    bool tie_true;
-};
-__device__ __forceinline__ RIouThr r_make_iou_thr(float thr, int ge) {
-    RIouThr t;
-    const unsigned b = __float_as_uint(thr);
-    if (ge) {
-        const float lo = __uint_as_float(b - 1u);
-        t.m = 0.5 * ((double)lo + (double)thr);
-        t.tie_true = (b & 1u) == 0u;
-    } else {
-        const float hi = __uint_as_float(b + 1u);
-        t.m = 0.5 * ((double)thr + (double)hi);
-        t.tie_true = ((b + 1u) & 1u) == 0u;
-    }
-    return t;
-}
-__device__ __forceinline__ bool r_iou_exceeds(const float4 a, const float4 b, float one, const RIouThr t) {
-    const float aa = (a.z - a.x + one) * (a.w - a.y + one);
-    const float ab = (b.z - b.x + one) * (b.w - b.y + one);
-    const float xx1 = a.x > b.x ? a.x : b.x, yy1 = a.y > b.y ? a.y : b.y;
-    const float xx2 = a.z < b.z ? a.z : b.z, yy2 = a.w < b.w ? a.w : b.w;
-    float w = xx2 - xx1 + one, h = yy2 - yy1 + one;
-    w = w > 0.0f ? w : 0.0f;
-    h = h > 0.0f ? h : 0.0f;
-    const float inter = w * h;
-    const float uni = aa + ab - inter;
-    if (!(uni > 0.0f)) return false;
-    const double lhs = (double)inter, rhs = t.m * (double)uni;
-    return lhs > rhs || (lhs == rhs && t.tie_true);
-}
 
 struct RetinaLevel {
     const float* logits;   // [N][n]
@@ -187,7 +124,7 @@ __global__ __launch_bounds__(RETINA_NT) void retina_slice_kernel(const RetinaSel
         unsigned u = 0u;
         if (i < n && v >= a.prefilter) {   // >=: without a pre-filter (-inf) a -inf logit still reaches the sigmoid test; a NaN never passes either test
             const float p = dm_sigmoid(v);
-            if (p > a.thr) u = r_f2ord(p);
+            if (p > a.thr) u = f2ord(p);
         }
         keys[i] = u;
         mine += u != 0u;
@@ -203,7 +140,7 @@ __global__ __launch_bounds__(RETINA_NT) void retina_slice_kernel(const RetinaSel
     const int64_t list = L.cand0 + b;
     if (tid == 0) a.cand_cnt[list] = (int)k_eff;
     if (k_eff == 0u) return;
-    auto key_of = [&](int i) { return ((unsigned long long)keys[i] << 32) | (unsigned long long)(0xffffffffu - (unsigned)(off + i)); };
+    auto key_of = [&](int i) { return det_key_ord(keys[i], off + i); };
     unsigned long long T = 1ull;
     if (cnt > k_eff)
         T = radix_select64([&](auto f) { for (int i = tid; i < n; i += RETINA_NT) if (keys[i] != 0u) f(key_of(i)); }, k_eff, hist, sel);
@@ -273,23 +210,12 @@ __global__ __launch_bounds__(RETINA_NT) void retina_merge_kernel(const RetinaSel
         }
     });
     __syncthreads();
-    for (int size = 2; size <= RETINA_KCAP; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            if (tid < RETINA_KCAP / 2) {
-                const int lo = ((tid / stride) * stride * 2) + (tid % stride);
-                const int hi = lo + stride;
-                const bool desc = ((lo & size) == 0);
-                const unsigned long long p = sbuf[lo], q = sbuf[hi];
-                if (desc ? (p < q) : (p > q)) { sbuf[lo] = q; sbuf[hi] = p; }
-            }
-            __syncthreads();
-        }
-    }
+    bitonic_sort<true>(sbuf, RETINA_KCAP, RETINA_NT);
     const int64_t orow = (int64_t)img * a.nl + l;
     const bool real = (unsigned)tid < k_eff;
     const unsigned long long kx = sbuf[tid];
-    const float score = real ? r_ord2f((unsigned)(kx >> 32)) : -1.0f;
-    const int idx = real ? (int)(0xffffffffu - (unsigned)(kx & 0xffffffffull)) : -1;
+    const float score = real ? det_key_score(kx) : -1.0f;
+    const int idx = real ? det_key_index(kx) : -1;
     if (tid < a.top_n) {
         a.sel_scores[orow * a.top_n + tid] = score;
         a.sel_idx[orow * a.top_n + tid] = idx;
@@ -304,11 +230,8 @@ __global__ __launch_bounds__(RETINA_NT) void retina_merge_kernel(const RetinaSel
         const int anchor = idx / a.C;
         const float4 an = *(const float4*)(L.anchors + (int64_t)anchor * 4);
         const float4 d = *(const float4*)(L.deltas + ((int64_t)img * (L.n / a.C) + anchor) * 4);
-        box = r_decode_box(an, d, 10.0f, 10.0f, 5.0f, 5.0f);
-        const float mx = (float)a.image_hw[img * 2 + 1] - 1.0f, my = (float)a.image_hw[img * 2] - 1.0f;
-        box.x = r_clampf(box.x, mx); box.y = r_clampf(box.y, my); box.z = r_clampf(box.z, mx); box.w = r_clampf(box.w, my);
-        const float ws = box.z - box.x + 1.0f, hs = box.w - box.y + 1.0f;
-        ok = ws >= a.min_size && hs >= a.min_size;
+        box = clip_box(decode_box(an, d, 10.0f, 10.0f, 5.0f, 5.0f), (float)a.image_hw[img * 2 + 1], (float)a.image_hw[img * 2]);
+        ok = box_min_size_ok(box, a.min_size);
     }
     const unsigned long long bm = __ballot(ok);
     if (lane == 0) wcnt[wave] = (unsigned)__popcll(bm);
@@ -341,30 +264,13 @@ struct RetinaPost {
 };
 constexpr int RETINA_CB = 512;   // cbound row: [256] class starts, [256] class ends
 
-__device__ __forceinline__ int r_next_pow2(int n) { int p = 2; while (p < n) p <<= 1; return p; }
-// ascending bitonic sort of P (power of two) keys in LDS, whole block
-__device__ void r_sort_asc(unsigned long long* k, int P) {
-    for (int size = 2; size <= P; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = threadIdx.x; t < P / 2; t += blockDim.x) {
-                const int lo = ((t / stride) * stride * 2) + (t % stride);
-                const int hi = lo + stride;
-                const bool asc = ((lo & size) == 0);
-                const unsigned long long p = k[lo], q = k[hi];
-                if (asc ? (p > q) : (p < q)) { k[lo] = q; k[hi] = p; }
-            }
-            __syncthreads();
-        }
-    }
-}
-
 // grid N.  key = label << 45 | ~ord(score) << 13 | slot, ascending: (class asc, score desc, slot asc)
 __global__ __launch_bounds__(1024) void retina_sort_kernel(const RetinaPost a) {
     extern __shared__ unsigned long long skeys[];
     __shared__ int cb[RETINA_CB];
     __shared__ int stotal;
     const int n = blockIdx.x, tid = threadIdx.x;
-    const int P = r_next_pow2(a.M);
+    const int P = next_pow2(a.M);
     if (tid == 0) stotal = 0;
     for (int i = tid; i < RETINA_CB; i += blockDim.x) cb[i] = 0;
     __syncthreads();
@@ -376,7 +282,7 @@ __global__ __launch_bounds__(1024) void retina_sort_kernel(const RetinaPost a) {
             const int64_t src = (int64_t)n * a.M + i;
             const int lab = j < a.seg_cnt[n * a.nseg + seg] ? a.labels[src] : 0;
             if (lab >= 1 && lab <= a.nc) {
-                key = ((unsigned long long)lab << 45) | ((unsigned long long)(~r_f2ord(a.scores[src])) << 13) | (unsigned long long)i;
+                key = ((unsigned long long)lab << 45) | ((unsigned long long)(~f2ord(a.scores[src])) << 13) | (unsigned long long)i;
                 ++mine;
             }
         }
@@ -384,7 +290,7 @@ __global__ __launch_bounds__(1024) void retina_sort_kernel(const RetinaPost a) {
     }
     if (mine) atomicAdd(&stotal, mine);   // a count
     __syncthreads();
-    r_sort_asc(skeys, P);
+    bitonic_sort<false>(skeys, P, blockDim.x);
     const int total = stotal;
     for (int i = tid; i < total; i += blockDim.x) {
         const unsigned long long key = skeys[i];
@@ -410,31 +316,22 @@ __global__ __launch_bounds__(256) void retina_matrix_kernel(const RetinaPost a) 
     const int total = a.total[n];
     const int nwords = (total + 63) >> 6;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int pair = blockIdx.x * 4 + wave;   // wave-uniform
-    int w = 0;
-    while ((w + 1) * (w + 2) / 2 <= pair) ++w;
-    const int r = pair - w * (w + 1) / 2;
+    int r, w;
+    tri_pair(blockIdx.x * 4 + wave, r, w);   // wave-uniform
     if (w >= nwords) return;   // whole wave; no block-level barrier below
     const int* lab = a.slabel + (int64_t)n * a.MP;
     const int rlast = (r << 6) + 63 < total ? (r << 6) + 63 : total - 1;
     if (lab[rlast] < lab[w << 6]) return;   // sorted by class: the tile's rows and columns share none
-    const RIouThr T = r_make_iou_thr(a.thr, a.flags & ISEGMI_NMS_GE);
-    const float one = (a.flags & ISEGMI_NMS_NO_PLUS_ONE) ? 0.0f : 1.0f;
+    const IouThr T = make_iou_thr(a.thr, a.flags & ISEGMI_NMS_GE);
+    const float one = nms_one(a.flags);
     const float4* sb = (const float4*)(a.sbox + (int64_t)n * a.MP * 4);
     const int i = (r << 6) + lane, jc = (w << 6) + lane;
     const float4 mine = sb[i < total ? i : 0];
     const int mylab = lab[i < total ? i : 0];
-    cols[wave][lane] = sb[jc < total ? jc : 0];
-    clab[wave][lane] = jc < total ? lab[jc] : -1;
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): this wave's own LDS writes have landed
-    unsigned long long bits = 0ull;
-#pragma unroll 8
-    for (int bb = 0; bb < 64; ++bb) {
-        const int jj = (w << 6) + bb;
-        const bool sup = jj > i && clab[wave][bb] == mylab && r_iou_exceeds(mine, cols[wave][bb], one, T);
-        bits |= sup ? (1ull << bb) : 0ull;
-    }
+    clab[wave][lane] = jc < total ? lab[jc] : -1;   // a column past `total` matches no class
+    nms_stage_cols(cols[wave], lane, sb[jc < total ? jc : 0]);
+    const int* cl = clab[wave];
+    const unsigned long long bits = nms_tile_word(mine, cols[wave], i, w, one, T, [cl, mylab](int, int b) { return cl[b] == mylab; });
     if (i < total) a.matrix[((int64_t)n * a.MP + i) * a.MW + w] = bits;
 }
 
@@ -451,17 +348,10 @@ __global__ __launch_bounds__(64) void retina_scan_kernel(const RetinaPost a) {
         const int i = (cw << 6) + lane;
         const bool in = i >= s && i < e;
         const unsigned long long d = in ? M[(int64_t)i * a.MW + cw] : 0ull;
-        const int dlo = (int)(unsigned)d, dhi = (int)(unsigned)(d >> 32);
         const int rel = cw - w0;
         const unsigned long long rsrc = rel < 64 ? rem0 : rem1;
         const unsigned long long rc = __shfl(rsrc, rel & 63, 64);
-        unsigned long long alive = ~rc & __ballot(in);
-#pragma unroll
-        for (int b = 0; b < 64; ++b) {   // box b survives => it strikes its later chunk-mates
-            const unsigned long long db = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane(dhi, b) << 32) |
-                                          (unsigned long long)(unsigned)__builtin_amdgcn_readlane(dlo, b);
-            alive &= ((alive >> b) & 1ull) ? ~db : ~0ull;
-        }
+        const unsigned long long alive = nms_resolve_chunk(~rc & __ballot(in), d);
         if (in) kept[i] = (unsigned char)((alive >> lane) & 1ull);
         if (cw == w1) break;
         const int wa = w0 + lane, wb = w0 + 64 + lane;
@@ -483,7 +373,7 @@ __global__ __launch_bounds__(1024) void retina_finalize_kernel(const RetinaPost 
     __shared__ int scnt[2];
     const int n = blockIdx.x, tid = threadIdx.x;
     const int total = a.total[n];
-    const int P = r_next_pow2(total);
+    const int P = next_pow2(total);
     const unsigned char* kept = a.kept + (int64_t)n * a.MP;
     const float* sscore = a.sscore + (int64_t)n * a.MP;
     if (tid < 2) scnt[tid] = 0;
@@ -492,7 +382,7 @@ __global__ __launch_bounds__(1024) void retina_finalize_kernel(const RetinaPost 
     for (int i = tid; i < P; i += blockDim.x) {
         const int ii = i < total ? i : 0;
         const bool k = i < total && kept[ii];
-        skeys[i] = k ? (unsigned long long)(~r_f2ord(sscore[ii])) : ~0ull;
+        skeys[i] = k ? (unsigned long long)(~f2ord(sscore[ii])) : ~0ull;
         mine += k;
     }
     if (mine) atomicAdd(&scnt[0], mine);
@@ -500,7 +390,7 @@ __global__ __launch_bounds__(1024) void retina_finalize_kernel(const RetinaPost 
     const int nk = scnt[0];
     unsigned cut = 0u;   // ordered key of the lowest score that stays
     if (a.det > 0 && nk > a.det) {
-        r_sort_asc(skeys, P);
+        bitonic_sort<false>(skeys, P, blockDim.x);
         cut = ~(unsigned)skeys[a.det - 1];
         __syncthreads();
     }
@@ -508,14 +398,14 @@ __global__ __launch_bounds__(1024) void retina_finalize_kernel(const RetinaPost 
     mine = 0;
     for (int i = tid; i < P; i += blockDim.x) {
         const int ii = i < total ? i : 0;
-        const bool k = i < total && kept[ii] && r_f2ord(sscore[ii]) >= cut;
+        const bool k = i < total && kept[ii] && f2ord(sscore[ii]) >= cut;
         const unsigned ord = by_slot ? (unsigned)a.sslot[(int64_t)n * a.MP + ii] : (unsigned)i;
         skeys[i] = k ? ((unsigned long long)a.slabel[(int64_t)n * a.MP + ii] << 32) | ((unsigned long long)ord << 16) | (unsigned long long)i : ~0ull;
         mine += k;
     }
     if (mine) atomicAdd(&scnt[1], mine);
     __syncthreads();
-    r_sort_asc(skeys, P);
+    bitonic_sort<false>(skeys, P, blockDim.x);
     const int cnt = scnt[1] < a.cap ? scnt[1] : a.cap;
     for (int q = tid; q < a.cap; q += blockDim.x) {
         const int64_t o = (int64_t)n * a.cap + q;
@@ -619,7 +509,7 @@ int retina_postprocess_launch(const isegmi_retina_post_args* p, hipStream_t st) 
     a.total = (int*)w; w += align256(N * 4);
     a.matrix = (unsigned long long*)w;
     a.out_cnt = p->d_out_count; a.out_boxes = p->d_out_boxes; a.out_scores = p->d_out_scores; a.out_labels = p->d_out_labels;
-    const int P = 1 << (32 - __builtin_clz((unsigned)(a.M > 2 ? a.M - 1 : 1)));   // next power of two >= max(M, 2)
+    const int P = next_pow2(a.M);
     const size_t lds = (size_t)P * 8;
     LDS_LIMIT_ONCE(RETINA_MAX_SLOTS * 8, retina_sort_kernel);
     LDS_LIMIT_ONCE(RETINA_MAX_SLOTS * 8, retina_finalize_kernel);

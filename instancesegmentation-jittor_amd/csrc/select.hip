@@ -5,11 +5,7 @@
 // the box post-processor (M9).  Total order = (score descending, index ascending): exactly the
 // oracle's ora_topk, so indices are bit-identical.
 //
-// KEY ORDER CONTRACT.  Keys compare as floats, not as bit patterns: -0.0 and +0.0 are EQUAL (the lower
-// index wins, as in ora_topk, torch.topk and sort), -inf < every finite key < +inf, subnormals keep
-// their value.  f2ord() maps both zeros to one sort key; a returned value is rebuilt from that key, so
-// a selected -0.0 comes back as +0.0 (every other value comes back bit for bit).  NaN keys are outside
-// the contract: a comparator-based reference has no total order with them.
+// Keys compare as floats, -0.0 == +0.0: the KEY ORDER CONTRACT of csrc/detbox.h (f2ord / det_key).
 //
 // One block per problem row:
 //   A. 3-pass radix select (12+12+8 bits, LDS histogram) of the threshold score T with
@@ -20,21 +16,12 @@
 //   C. bitonic sort of <= KCAP 64-bit keys (ordered score << 32 | ~index) in LDS.
 #include "../../include/isegmi.h"
 #include "common.h"
-#include "rpn_levels.h"
+#include "tail_launch.h"
+#include "detbox.h"
 #include <mutex>
 #include <unordered_map>
 
 namespace isegmi {
-
-__device__ __forceinline__ unsigned f2ord(float f) {
-    const unsigned u = __float_as_uint(f);
-    if (u == 0x80000000u) return 0x80000000u;  // -0.0 == +0.0: one key for both, the index decides
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(unsigned o) {
-    const unsigned u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
-    return __uint_as_float(u);
-}
 
 struct TopkArgs {
     const float* keys;      // row r at keys + r*row_stride
@@ -191,7 +178,7 @@ __device__ __forceinline__ void topk_block(const TopkArgs& a, const int bx) {   
             const unsigned long long bsel = __ballot(sel);
             if (sel) {
                 const unsigned pos = run_sel + (unsigned)__popcll(bsel & lt_mask);
-                if (pos < (unsigned)KCAP) sbuf[pos] = ((unsigned long long)u << 32) | (unsigned long long)(0xffffffffu - (unsigned)phys(i));
+                if (pos < (unsigned)KCAP) sbuf[pos] = det_key_ord(u, phys(i));
             }
             run_sel += (unsigned)__popcll(bsel);
             run_eq += (unsigned)__popcll(beq);
@@ -205,28 +192,17 @@ __device__ __forceinline__ void topk_block(const TopkArgs& a, const int bx) {   
         for (int i = tid; i < a.k; i += NT) {
             const unsigned long long kx = sbuf[i];
             const bool real = i < k_eff;
-            a.out_vals[(int64_t)orow * a.k + i] = real ? ord2f((unsigned)(kx >> 32)) : ord2f(0u);
-            a.out_idx[(int64_t)orow * a.k + i] = real ? (int)(0xffffffffu - (unsigned)(kx & 0xffffffffull)) + slice_off : -1;
+            a.out_vals[(int64_t)orow * a.k + i] = real ? det_key_score(kx) : ord2f(0u);
+            a.out_idx[(int64_t)orow * a.k + i] = real ? det_key_index(kx) + slice_off : -1;
         }
         return;
     }
     // ---- C. bitonic sort, descending
-    for (int size = 2; size <= KCAP; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = tid; t < KCAP / 2; t += NT) {
-                const int lo = ((t / stride) * stride * 2) + (t % stride);
-                const int hi = lo + stride;
-                const bool desc = ((lo & size) == 0);
-                const unsigned long long x = sbuf[lo], y = sbuf[hi];
-                if (desc ? (x < y) : (x > y)) { sbuf[lo] = y; sbuf[hi] = x; }
-            }
-            __syncthreads();
-        }
-    }
+    bitonic_sort<true>(sbuf, KCAP, NT);
     for (int i = tid; i < k_eff; i += NT) {
         const unsigned long long kx = sbuf[i];
-        const int pos = (int)(0xffffffffu - (unsigned)(kx & 0xffffffffull));
-        a.out_vals[(int64_t)orow * a.k + i] = ord2f((unsigned)(kx >> 32));
+        const int pos = det_key_index(kx);
+        a.out_vals[(int64_t)orow * a.k + i] = det_key_score(kx);
         a.out_idx[(int64_t)orow * a.k + i] = a.remap ? a.remap[(int64_t)row * a.n + pos] : pos;
     }
     if (tid == 0 && a.out_cnt) a.out_cnt[orow] = k_eff;

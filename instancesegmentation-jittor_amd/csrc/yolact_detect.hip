@@ -14,6 +14,7 @@
 #include "../../include/isegmi.h"
 #include "common.h"
 #include "detmath.h"
+#include "tail_launch.h"
 
 namespace isegmi {
 
@@ -317,9 +318,6 @@ __global__ void yolact_int_boxes_kernel(const float* __restrict__ boxes, const i
         } else { o[0] = o[1] = o[2] = o[3] = 0; }
     }
 }
-
-int topk_launch(const float* keys, int64_t row_stride, int rows, int n, int k, const int* limit, int rows_per_limit,
-                float* out_vals, int* out_idx, int* out_cnt, hipStream_t st);
 
 int yolact_detect_launch(const isegmi_yolact_detect_args* a, hipStream_t st) {
     ARG_CHECK(a->N > 0 && a->P > 0 && a->ncls >= 2 && a->ncls <= 256, "detect sizes");

@@ -185,7 +185,7 @@ def naive_iou_exceeds(inter, uni, thr, ge, fp32_product=False):
 
 
 def midpoint_iou_exceeds(inter, uni, thr, ge):
-    """numpy restatement of csrc/rcnn_ops.hip make_iou_thr / iou_exceeds: the real quotient against the midpoint between thr and its fp32 neighbour, in fp64
+    """numpy restatement of csrc/detbox.h make_iou_thr / iou_exceeds: the real quotient against the midpoint between thr and its fp32 neighbour, in fp64
     (exact: 24-bit inter and uni, 25-bit midpoint), ties to the even mantissa; a union that is not > 0 never exceeds."""
     thr = F32(thr)
     b = bits1(thr)
