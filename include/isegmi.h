@@ -319,7 +319,7 @@ typedef struct isegmi_box_post_args {
     float score_thresh, nms_thresh;
     int64_t logits_stride, regr_stride;   /* floats between consecutive rois */
     const float* d_logits;     /* [N*R] rows of ncls */
-    const float* d_regr;       /* [N*R] rows; class j deltas at 4j..4j+3 */
+    const float* d_regr;       /* [N*R] rows; class j deltas at 4j..4j+3 (cls_agnostic: 4..7 for every class) */
     const float* d_props;      /* [N][R][4] */
     const int32_t* d_prop_cnt; /* [N] */
     const int32_t* d_image_hw; /* [N][2] unpadded (h, w) */
@@ -339,6 +339,9 @@ typedef struct isegmi_box_post_args {
     void* d_ws_crowd_keys;       /* [N][ncls-1][R] 8-byte keys */
     float* d_ws_crowd_boxes;     /* [N][ncls-1][R][4] */
     int32_t* d_ws_crowd_m;       /* [N][ncls-1] */
+    /* MODEL.CLS_AGNOSTIC_BBOX_REG: d_regr rows hold eight deltas and EVERY class decodes the last four (4..7), once per proposal in effect; 0 = per-class
+     * deltas.  Appended last: a caller that zeroes the struct (required) keeps the per-class behaviour. */
+    int32_t cls_agnostic;
 } isegmi_box_post_args;
 int isegmi_op_box_postprocess(const isegmi_box_post_args* a, void* stream);
 /* mask predictor tail (A.8): out[r,p] = sigmoid(<feat[r,p,:], w[label_r,:]> + b[label_r]); label 0 -> zeros */
@@ -597,6 +600,12 @@ int isegmi_engine_get_timings(isegmi_engine* e, char* names, int names_cap, floa
 int isegmi_engine_rle(isegmi_engine* e, const int32_t* h_image_hw);
 int isegmi_engine_coco_record_bytes(isegmi_engine* e, int N, int64_t* bytes, int64_t* chars_offset);
 int isegmi_engine_pack_coco_records(isegmi_engine* e, void* d_dst, int64_t cap, int n_block, int64_t* bytes);
+/* Box-only record block of the last forward of a Mask R-CNN-family engine (Faster R-CNN: set_param "mask_on" 0), ONE launch on the results stream:
+ *   [status i32 x 4 = 0][box f32 x n_block*K*4][count i32 x n_block][score f32 x n_block*K][label i32 x n_block*K], every section starting on a multiple
+ *   of 8 bytes; box = det.box * (ratio_w, ratio_h, ratio_w, ratio_h) in fp32 -- xyxy in ORIGINAL image coordinates, h_ratios_wh [N][2] as for
+ *   isegmi_maskrcnn_paste.  No string offsets, no characters; image slots past the last forward's batch are zero.
+ * isegmi_engine_coco_record_bytes returns this block's size (chars_offset = the size) while the engine's "mask_on" is 0. */
+int isegmi_engine_pack_box_records(isegmi_engine* e, const float* h_ratios_wh, void* d_dst, int64_t cap, int n_block, int64_t* bytes);
 int isegmi_engine_download_async(isegmi_engine* e, int slot, void* h_dst_pinned, const void* d_src, int64_t bytes);
 int isegmi_engine_download_fence(isegmi_engine* e, int slot);
 int isegmi_engine_download_wait(isegmi_engine* e, int slot);

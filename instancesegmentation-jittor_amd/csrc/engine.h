@@ -292,6 +292,8 @@ int yolact_postprocess(Engine& e, int h, int w, const int32_t* h_image_hw = null
 int maskrcnn_forward(Engine& e, const float* d_images, int N);
 int eng_next_event(Engine& e, hipEvent_t* ev);
 int maskrcnn_paste(Engine& e, const float* h_ratios_wh, int out_h, int out_w);
+bool maskrcnn_mask_on(Engine& e);
+int maskrcnn_stage_ratios(Engine& e, const float* h_ratios_wh, int N, hipStream_t ps, void** d_ratios);
 
 // kernels implemented in other translation units (the detection tail's launchers: tail_launch.h)
 int conv2d_launch(const isegmi_conv_desc* d, const float* in, const float* w, const float* scale, const float* shift,

@@ -59,6 +59,25 @@ int maskrcnn_det_cap(Engine& e) {
     return cap > dpi ? cap : dpi;
 }
 
+// MODEL.MASK_ON: "mask_on" 0 = Faster R-CNN -- the forward ends behind box_postprocess, no mask buffer is ever allocated, the results leave
+// through isegmi_engine_pack_box_records.  Read each forward: an engine whose weights include the mask head may be toggled.
+bool maskrcnn_mask_on(Engine& e) { return e.param("mask_on", 1.0f) != 0.0f; }
+
+// The box predictor's shape: "num_classes" (MODEL.ROI_BOX_HEAD.NUM_CLASSES, background included) and "cls_agnostic" (MODEL.CLS_AGNOSTIC_BBOX_REG: two
+// sets of four deltas, the last one decoded for every class).  `width` = outputs of the fused cls_score | bbox_pred layer.
+static int box_predictor_shape(Engine& e, int width, int* ncls, int* agnostic) {
+    const int nc = (int)e.param("num_classes", 81.0f), ag = e.param("cls_agnostic", 0.0f) != 0.0f ? 1 : 0;
+    if (nc < 2 || nc > 257) { set_error("num_classes (MODEL.ROI_BOX_HEAD.NUM_CLASSES) must be 2..257, got " + std::to_string(nc)); return ISEGMI_ERR_STATE; }
+    const int want = ag ? nc + 8 : nc * 5;
+    if (width != want) {
+        set_error("cls_bbox layer has " + std::to_string(width) + " outputs; " + std::to_string(nc) + " classes need " +
+                  (ag ? std::to_string(nc) + "+8 (class-agnostic regression: cls_agnostic 1)" : std::to_string(nc) + "+" + std::to_string(4 * nc) + " (per-class regression: cls_agnostic 0)"));
+        return ISEGMI_ERR_STATE;
+    }
+    *ncls = nc; *agnostic = ag;
+    return ISEGMI_OK;
+}
+
 // Anchors of one level for the current canvas: the host sets the A base anchors ("anchor_base.<l>", generate_anchors) and the stride
 // ("anchor_stride<l>"); the grid is laid out on the device whenever the canvas changed (always under graph capture, so that a replayed graph
 // never depends on which canvas ran last).  Runs on the main stream, after the forward's WAR wait on the previous forward's tail.
@@ -385,11 +404,12 @@ int maskrcnn_forward(Engine& e, const float* d_images, int N) {
     TRY(eng_conv(e, "roi_heads.box.feature_extractor.fc7", f6, 1, 0, 1, nullptr, "box.fc7", &f7));
     }
     TRY(eng_conv(e, "roi_heads.box.predictor.cls_bbox", f7, 1, 0, 0, nullptr, "box.cls_bbox", &cb, /*out_f32=*/true));
-    const int ncls = 81, dpi = (int)e.param("detections_per_img", 100), cap = maskrcnn_det_cap(e);
-    if (cb.C != ncls * 5) { set_error("cls_bbox layer must have 81+324 outputs"); return ISEGMI_ERR_STATE; }
+    int ncls = 0, agnostic = 0;
+    TRY(box_predictor_shape(e, cb.C, &ncls, &agnostic));
+    const int dpi = (int)e.param("detections_per_img", 100), cap = maskrcnn_det_cap(e);
     isegmi_box_post_args a;
     memset(&a, 0, sizeof(a));
-    a.N = N; a.R = R; a.ncls = ncls; a.det_per_img = dpi; a.cap = cap; a.nms_flags = ge;
+    a.N = N; a.R = R; a.ncls = ncls; a.det_per_img = dpi; a.cap = cap; a.nms_flags = ge; a.cls_agnostic = agnostic;
     a.score_thresh = e.param("roi_score_thresh", 0.05f);
     a.nms_thresh = e.param("roi_nms_thresh", 0.5f);
     a.logits_stride = cb.C; a.regr_stride = cb.C;
@@ -412,10 +432,15 @@ int maskrcnn_forward(Engine& e, const float* d_images, int N) {
     TRY(eng_buf(e, "det.label", (int64_t)N * cap * 4, &p, 1, {N, cap})); a.d_out_labels = (int*)p;
     {
         // logits + box regressions of every proposal once, the proposals, the detections out
-        OpScope op(e, st, "box_postprocess (softmax + decode + per-class NMS + top-100)", (double)N * R * ((double)ncls * 5 * 4 + 16) + (double)N * cap * 24);
+        OpScope op(e, st, "box_postprocess (softmax + decode + per-class NMS + top-100)", (double)N * R * ((double)cb.C * 4 + 16) + (double)N * cap * 24);
         TRY(box_postprocess_launch(&a, st));
     }
     eng_mark(e, "box_head");
+    if (!maskrcnn_mask_on(e)) {   // Faster R-CNN: det.* is the result; the tail's bookkeeping as behind the mask head
+        TRY(eng_tail_end(e));
+        e.cur = e.stream;
+        return ISEGMI_OK;
+    }
 
     // ---- mask head
     Tensor m;
@@ -566,11 +591,12 @@ static int maskrcnn_c4_forward(Engine& e, const float* d_images, int N) {
     TRY(eng_act(e, "box.pooled", N * R, 1, 1, f5.C, &pooled));
     TRY(avgpool_full_launch(f5.d, (int64_t)N * R, f5.H * f5.W, f5.C, pooled.d, st));
     TRY(eng_conv(e, "roi_heads.box.predictor.cls_bbox", pooled, 1, 0, 0, nullptr, "box.cls_bbox", &cb));
-    const int ncls = 81, dpi = (int)e.param("detections_per_img", 100), cap = maskrcnn_det_cap(e);
-    if (cb.C != ncls * 5) { set_error("cls_bbox layer must have 81+324 outputs"); return ISEGMI_ERR_STATE; }
+    int ncls = 0, agnostic = 0;
+    TRY(box_predictor_shape(e, cb.C, &ncls, &agnostic));
+    const int dpi = (int)e.param("detections_per_img", 100), cap = maskrcnn_det_cap(e);
     isegmi_box_post_args a;
     memset(&a, 0, sizeof(a));
-    a.N = N; a.R = R; a.ncls = ncls; a.det_per_img = dpi; a.cap = cap; a.nms_flags = ge;
+    a.N = N; a.R = R; a.ncls = ncls; a.det_per_img = dpi; a.cap = cap; a.nms_flags = ge; a.cls_agnostic = agnostic;
     a.score_thresh = e.param("roi_score_thresh", 0.05f);
     a.nms_thresh = e.param("roi_nms_thresh", 0.5f);
     a.logits_stride = cb.C; a.regr_stride = cb.C;
@@ -593,6 +619,10 @@ static int maskrcnn_c4_forward(Engine& e, const float* d_images, int N) {
     TRY(eng_buf(e, "det.label", (int64_t)N * cap * 4, &p, 1, {N, cap})); a.d_out_labels = (int*)p;
     TRY(box_postprocess_launch(&a, st));
     eng_mark(e, "box_head");
+    if (!maskrcnn_mask_on(e)) {   // Faster R-CNN: no second pass of the conv5 head over the detections
+        e.cur = e.stream;
+        return ISEGMI_OK;
+    }
 
     // ---- mask head: the shared extractor on the detections, then MaskRCNNC4Predictor
     Tensor mroi, m5, up;
@@ -619,23 +649,30 @@ static int maskrcnn_c4_forward(Engine& e, const float* d_images, int N) {
     return ISEGMI_OK;
 }
 
+// The per-image (w, h) resize ratios of the results stage in "ws.ratios", staged only when they changed: in stream order behind every earlier reader (the
+// previous paste / box-record pack ran on a results stream this one is ordered behind).
+int maskrcnn_stage_ratios(Engine& e, const float* h_ratios_wh, int N, hipStream_t ps, void** d_ratios) {
+    void* rt;
+    TRY(eng_buf(e, "ws.ratios", (int64_t)e.max_batch * 8, &rt));
+    std::vector<float> now(h_ratios_wh, h_ratios_wh + 2 * N);
+    if (now != e.last_ratios || e.last_ratios_ptr != (const void*)rt) {
+        TRY(eng_stage_small(e, h_ratios_wh, (size_t)N * 8, rt, ps));
+        e.last_ratios = now;
+        e.last_ratios_ptr = rt;
+    }
+    *d_ratios = rt;
+    return ISEGMI_OK;
+}
+
 int maskrcnn_paste(Engine& e, const float* h_ratios_wh, int out_h, int out_w) {
     const int N = e.last_N;
     if (N <= 0) { set_error("paste before forward"); return ISEGMI_ERR_STATE; }
     const int cap = maskrcnn_det_cap(e);
+    if (!maskrcnn_mask_on(e)) { set_error("paste: the engine is box-only (mask_on 0, MODEL.MASK_ON False): there are no masks to paste"); return ISEGMI_ERR_STATE; }
     void *p, *rb, *rt;
-    TRY(eng_buf(e, "ws.ratios", (int64_t)e.max_batch * 8, &rt));
     hipStream_t ps = (e.multi_stream && e.tail_pending) ? e.tail : e.stream;  // results stream of the last forward
     e.cur = ps;
-    {
-        // in stream order behind every earlier reader of ws.ratios (the previous paste ran on a results stream this one is ordered behind)
-        std::vector<float> now(h_ratios_wh, h_ratios_wh + 2 * N);
-        if (now != e.last_ratios || e.last_ratios_ptr != (const void*)rt) {
-            TRY(eng_stage_small(e, h_ratios_wh, (size_t)N * 8, rt, ps));
-            e.last_ratios = now;
-            e.last_ratios_ptr = rt;
-        }
-    }
+    TRY(maskrcnn_stage_ratios(e, h_ratios_wh, N, ps, &rt));
     TRY(eng_buf(e, "det.box_resized", (int64_t)N * cap * 16, &rb, 0, {N, cap, 4}));
     TRY(scale_boxes_launch((const float*)e.bufs["det.box"].d, (const float*)rt, N, cap, (float*)rb, ps));
     TRY(eng_buf(e, "det.masks", (int64_t)N * cap * out_h * out_w, &p, 2, {N, cap, out_h, out_w}));
@@ -706,6 +743,7 @@ extern "C" int isegmi_maskrcnn_pack_records(isegmi_engine* h, void* d_dst, int64
     ARG_CHECK(e.kind == 2, "engine is not a Mask R-CNN engine");
     const int N = e.last_N;
     ARG_CHECK(N > 0, "pack before forward");
+    ARG_CHECK(maskrcnn_mask_on(e), "pack_records carries the RoI masks: a box-only engine (mask_on 0) packs with isegmi_engine_pack_box_records");
     const int K = maskrcnn_det_cap(e);
     hipStream_t rs = (e.multi_stream && e.tail_pending) ? e.tail : e.stream;  // results stream
     const bool c4 = e.param("arch_c4", 0.0f) != 0.0f;  // MaskRCNNC4Predictor: 14x14 masks

@@ -726,7 +726,7 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
     }
 }
 
-// grid (ncls-1, N).  prob [N][R][ncls]; regr [N][R][regr_stride] (class j deltas at 4j..4j+3); props [N][R][4];
+// grid (ncls-1, N).  prob [N][R][ncls]; regr [N][R][regr_stride] (class j deltas at 4j..4j+3; `agnostic`: at 4..7 for every class); props [N][R][4];
 // prop_cnt [N].  cand_scores/cand_boxes [N][ncls-1][R] in NMS (score) order, -1 beyond the kept count.
 // 16 waves: a crowded class's suppression matrix is ~60 dependent instructions per IoU test, and a wave alone on its SIMD
 // issues one every ~6 cycles (11 us per 64x64 matrix block); four waves per SIMD fill the issue slots.
@@ -750,7 +750,8 @@ __global__ __launch_bounds__(BOX_NMS_THREADS) void box_cls_nms_kernel(const floa
                                                            const int* __restrict__ prop_cnt, const int* __restrict__ image_hw, int R,
                                                            int ncls, float score_thr, float nms_thr, int ge,
                                                            float* __restrict__ cand_scores, float* __restrict__ cand_boxes,
-                                                           int* __restrict__ kept_total, const BoxCrowd crowd, const int phase) {
+                                                           int* __restrict__ kept_total, const BoxCrowd crowd, const int phase,
+                                                           const int agnostic) {
     __shared__ NmsShared S;
     __shared__ unsigned long long keys[NMS_CAP];
     constexpr int NT = BOX_NMS_THREADS, NW = NT / 64;
@@ -812,7 +813,8 @@ __global__ __launch_bounds__(BOX_NMS_THREADS) void box_cls_nms_kernel(const floa
     for (int q = tid; q < m; q += NT) {
         const int i = det_key_index(keys[q]);
         const float4 pr = *(const float4*)(props + ((int64_t)n * R + i) * 4);
-        const float* dp = regr + ((int64_t)n * R + i) * regr_stride + 4 * j;
+        // CLS_AGNOSTIC_BBOX_REG: rows of eight, every class decodes the last four (box_regression[:, -4:])
+        const float* dp = regr + ((int64_t)n * R + i) * regr_stride + (agnostic ? 4 : 4 * j);
         const float4 d = make_float4(dp[0], dp[1], dp[2], dp[3]);
         S.sb[q] = clip_box(decode_box(pr, d, 10.f, 10.f, 5.f, 5.f), im_w, im_h);
     }
@@ -1290,6 +1292,8 @@ int box_postprocess_launch(const isegmi_box_post_args* a, hipStream_t st) {
     ARG_CHECK(a->det_per_img > 0 && a->det_per_img <= 1024 && a->cap >= a->det_per_img, "det_per_img / cap");
     ARG_CHECK(a->nms_thresh > 0.0f, "nms threshold must be > 0");
     const int nc = a->ncls - 1;
+    const int agnostic = a->cls_agnostic != 0;
+    ARG_CHECK(a->regr_stride >= (agnostic ? 8 : 4 * (int64_t)a->ncls), "box post: regr_stride shorter than the deltas of a row (4 * ncls, or 8 when cls_agnostic)");
     int rc = softmax_rows_launch(a->d_logits, (int64_t)a->N * a->R, a->ncls, a->logits_stride, a->d_ws_prob, st);
     if (rc) return rc;
     HIP_TRY(hipMemsetAsync(a->d_ws_kept_total, 0, sizeof(int) * (size_t)a->N, st));
@@ -1303,13 +1307,13 @@ int box_postprocess_launch(const isegmi_box_post_args* a, hipStream_t st) {
     // phase 0 with a hand-over needs the dynamic LDS only for the index-order fork's slot table (2 KB): two blocks share a CU
     hipLaunchKernelGGL(box_cls_nms_kernel, dim3(nc, a->N), dim3(BOX_NMS_THREADS), crowd.matrix ? 4096 : matrix_bytes, st, a->d_ws_prob, a->d_regr,
                        a->regr_stride, a->d_props, a->d_prop_cnt, a->d_image_hw, a->R, a->ncls, a->score_thresh, a->nms_thresh, a->nms_flags,
-                       a->d_ws_cand_scores, a->d_ws_cand_boxes, a->d_ws_kept_total, crowd, 0);
+                       a->d_ws_cand_scores, a->d_ws_cand_boxes, a->d_ws_kept_total, crowd, 0, agnostic);
     if (crowd.matrix) {
         constexpr int W = NMS_CAP / 64, pairs = W * (W + 1) / 2;
         hipLaunchKernelGGL(box_nms_matrix_kernel, dim3(cdiv(pairs, 4), nc * a->N), dim3(256), 0, st, crowd, a->R, a->nms_thresh, a->nms_flags);
         hipLaunchKernelGGL(box_cls_nms_kernel, dim3(nc, a->N), dim3(BOX_NMS_THREADS), matrix_bytes, st, a->d_ws_prob, a->d_regr, a->regr_stride,
                            a->d_props, a->d_prop_cnt, a->d_image_hw, a->R, a->ncls, a->score_thresh, a->nms_thresh, a->nms_flags,
-                           a->d_ws_cand_scores, a->d_ws_cand_boxes, a->d_ws_kept_total, crowd, 1);
+                           a->d_ws_cand_scores, a->d_ws_cand_boxes, a->d_ws_kept_total, crowd, 1, agnostic);
     }
     HIP_TRY(hipGetLastError());
     // the per-class lists are sorted (score order): nothing past a class's first det_per_img entries can make the image's top det_per_img; in index

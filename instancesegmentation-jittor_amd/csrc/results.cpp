@@ -13,6 +13,9 @@
 //   [str_off i32 x (N*K + 1)]    characters of slot (n, k): chars[str_off[n*K+k] .. str_off[n*K+k+1])
 //   [pad to 8]
 //   [chars   u8 x cap_chars]     pycocotools "counts" strings, back to back
+//
+// Box-only block (Faster R-CNN: a Mask R-CNN-family engine with "mask_on" 0), every section starting on a multiple of 8 bytes:
+//   [status  i32 x 4 = 0][box f32 x N*K*4, original-image xyxy][count i32 x N][score f32 x N*K][label i32 x N*K]      no str_off, no characters
 #include <string.h>
 
 #include "engine.h"
@@ -66,9 +69,24 @@ static int record_layout(Engine& e, int N, std::vector<Section>* out, int64_t* c
     return ISEGMI_OK;
 }
 
+static bool box_only(Engine& e) { return e.kind == 2 && !maskrcnn_mask_on(e); }
+
+// byte offsets of the box-only block's sections for n image slots
+struct BoxRecordLayout { int64_t box, count, score, label, total; };
+static BoxRecordLayout box_record_layout(int n, int K) {
+    BoxRecordLayout l;
+    l.box = 16;
+    l.count = align8(l.box + (int64_t)n * K * 16);
+    l.score = align8(l.count + (int64_t)n * 4);
+    l.label = align8(l.score + (int64_t)n * K * 4);
+    l.total = align8(l.label + (int64_t)n * K * 4);
+    return l;
+}
+
 // RLE of det.masks (the planes the last yolact_postprocess / maskrcnn_paste wrote) on the results stream.
 int eng_rle(Engine& e, const int32_t* h_image_hw) {
     const int N = e.last_N;
+    if (box_only(e)) { set_error("rle: the engine is box-only (mask_on 0, MODEL.MASK_ON False): there are no masks to encode"); return ISEGMI_ERR_STATE; }
     if (N <= 0) { set_error("rle before forward"); return ISEGMI_ERR_STATE; }
     auto mit = e.bufs.find("det.masks");
     if (mit == e.bufs.end() || mit->second.shape.size() != 4 || mit->second.shape[0] != N) { set_error("rle: run postprocess / paste of this batch first"); return ISEGMI_ERR_STATE; }
@@ -127,6 +145,11 @@ extern "C" int isegmi_engine_rle(isegmi_engine* h, const int32_t* h_image_hw) {
 
 extern "C" int isegmi_engine_coco_record_bytes(isegmi_engine* h, int N, int64_t* bytes, int64_t* chars_offset) {
     ARG_CHECK(h && bytes && N > 0 && N <= h->e.max_batch, "record_bytes args");
+    if (box_only(h->e)) {
+        *bytes = box_record_layout(N, det_cap(h->e)).total;
+        if (chars_offset) *chars_offset = *bytes;
+        return ISEGMI_OK;
+    }
     return record_layout(h->e, N, nullptr, chars_offset, bytes);
 }
 
@@ -154,11 +177,72 @@ __global__ void pack_coco_kernel(const PackK p) {
     for (int64_t i = tid; i <= nbk; i += nth) ((int*)(p.dst + p.off_stroff))[i] = p.str_off[i <= nk ? i : nk];
 }
 
+// The box-only block in one launch: boxes scaled to original-image coordinates (x * ratio_w, y * ratio_h: one fp32 multiplication each, as
+// scale_boxes_kernel), counts, scores, labels; image slots n .. nb-1, the status words and the padding between sections are zero.
+struct PackBoxK {
+    const float* box; const float* ratios; const int* count; const float* score; const int* label;
+    int n, nb, K;
+    char* dst;
+    BoxRecordLayout l;
+};
+__global__ void pack_box_records_kernel(const PackBoxK p) {
+    const int64_t nk = (int64_t)p.n * p.K, nbk = (int64_t)p.nb * p.K;
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
+    if (tid < 4) ((int*)p.dst)[tid] = 0;
+    for (int64_t i = tid; i < nbk; i += nth) {
+        float4 b = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (i < nk) {
+            const int img = (int)(i / p.K);
+            const float rw = p.ratios[2 * img], rh = p.ratios[2 * img + 1];
+            const float4 s = *(const float4*)(p.box + i * 4);
+            b = make_float4(s.x * rw, s.y * rh, s.z * rw, s.w * rh);
+        }
+        *(float4*)(p.dst + p.l.box + i * 16) = b;
+    }
+    // each section up to the next one's start (the padding words of an odd-sized section included)
+    for (int64_t i = tid; i < (p.l.score - p.l.count) / 4; i += nth) ((int*)(p.dst + p.l.count))[i] = i < p.n ? p.count[i] : 0;
+    for (int64_t i = tid; i < (p.l.label - p.l.score) / 4; i += nth) ((float*)(p.dst + p.l.score))[i] = i < nk ? p.score[i] : 0.0f;
+    for (int64_t i = tid; i < (p.l.total - p.l.label) / 4; i += nth) ((int*)(p.dst + p.l.label))[i] = i < nk ? p.label[i] : 0;
+}
+
+extern "C" int isegmi_engine_pack_box_records(isegmi_engine* h, const float* h_ratios_wh, void* d_dst, int64_t cap, int n_block, int64_t* bytes) {
+    ARG_CHECK(h && h_ratios_wh && d_dst && bytes, "null");
+    Engine& e = h->e;
+    ARG_CHECK(e.kind == 2, "pack_box_records: engine is not a Mask R-CNN / Faster R-CNN engine");
+    const int N = e.last_N;
+    ARG_CHECK(N > 0, "pack before forward");
+    ARG_CHECK(n_block >= N && n_block <= e.max_batch, "n_block: between the last forward's batch and max_batch");
+    const int K = det_cap(e);
+    PackBoxK p;
+    memset(&p, 0, sizeof(p));
+    p.l = box_record_layout(n_block, K);
+    ARG_CHECK(p.l.total <= cap, "record buffer too small");
+    const char* names[4] = {"det.box", "det.count", "det.score", "det.label"};
+    const int64_t need[4] = {(int64_t)N * K * 16, (int64_t)N * 4, (int64_t)N * K * 4, (int64_t)N * K * 4};
+    void* src[4];
+    for (int i = 0; i < 4; ++i) {
+        auto it = e.bufs.find(names[i]);
+        if (it == e.bufs.end() || it->second.d == nullptr || it->second.bytes < need[i]) { set_error(std::string("pack_box_records: buffer not produced yet: ") + names[i]); return ISEGMI_ERR_STATE; }
+        src[i] = it->second.d;
+    }
+    hipStream_t rs = eng_results_stream(e);
+    void* rt;
+    TRY(maskrcnn_stage_ratios(e, h_ratios_wh, N, rs, &rt));
+    p.box = (const float*)src[0]; p.count = (const int*)src[1]; p.score = (const float*)src[2]; p.label = (const int*)src[3];
+    p.ratios = (const float*)rt; p.n = N; p.nb = n_block; p.K = K; p.dst = (char*)d_dst;
+    hipLaunchKernelGGL(pack_box_records_kernel, dim3(16), dim3(256), 0, rs, p);
+    HIP_TRY(hipGetLastError());
+    if (rs == e.tail && e.tail) HIP_TRY(hipEventRecord(e.tail_done, e.tail));   // reads det.*: extend the WAR fence
+    *bytes = p.l.total;
+    return ISEGMI_OK;
+}
+
 extern "C" int isegmi_engine_pack_coco_records(isegmi_engine* h, void* d_dst, int64_t cap, int n_block, int64_t* bytes) {
     ARG_CHECK(h && d_dst && bytes, "null");
     Engine& e = h->e;
     const int N = e.last_N;
     ARG_CHECK(N > 0, "pack before forward");
+    ARG_CHECK(!box_only(e), "pack_coco_records carries RLE strings: a box-only engine (mask_on 0) packs with isegmi_engine_pack_box_records");
     ARG_CHECK(n_block >= N && n_block <= e.max_batch, "n_block: between the last forward's batch and max_batch");
     std::vector<Section> secs;
     int64_t coff = 0, total = 0;

@@ -134,7 +134,14 @@ def cmd_test_net(a):
     mc = to_retinanet_config(c) if retina else to_maskrcnn_config(c)
     rank, world, local = _rank_world()
     files = sorted(os.path.join(a.images, f) for f in os.listdir(a.images)) if a.images else []
-    sd = _weights(c.MODEL.WEIGHT, "retinanet", mc.depth) if retina else _weights(c.MODEL.WEIGHT, "maskrcnn", mc.depth, gn=mc.USE_GN)
+    if retina:
+        sd = _weights(c.MODEL.WEIGHT, "retinanet", mc.depth)
+    elif c.MODEL.WEIGHT in ("", "random", None):   # the seeded generator of the configured model: body, norm, MASK_ON, NUM_CLASSES, CLS_AGNOSTIC_BBOX_REG
+        from .weights import random_maskrcnn_state_dict
+        sd = random_maskrcnn_state_dict(mc, 1234)
+    else:
+        sd = _weights(c.MODEL.WEIGHT, "maskrcnn", mc.depth, gn=mc.USE_GN)
+    box_only = retina or not mc.MASK_ON   # RetinaNet and Faster R-CNN (MODEL.MASK_ON False): bbox results only
     demo = COCODemo(mc, min_image_size=mc.MIN_SIZE_TEST, confidence_threshold=0.0, state_dict=sd,
                     max_image_size=mc.MAX_SIZE_TEST, device=local, max_batch=a.batch_size)
     stats = {}
@@ -147,7 +154,7 @@ def cmd_test_net(a):
         print("wrote %d results for %d images to %s (%d steps of %d images on %d rank(s))" % (
             len(results), len(files), a.output, stats.get("steps", 0), a.batch_size, world))
         if a.gt:
-            _print_coco_summary(a.gt, results, ("bbox",) if retina else ("bbox", "segm"))
+            _print_coco_summary(a.gt, results, ("bbox",) if box_only else ("bbox", "segm"))
     return results
 
 

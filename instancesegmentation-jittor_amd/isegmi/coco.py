@@ -204,14 +204,29 @@ def rle_to_bbox(counts, h):
     return [float(x0), float(y0), float(x1 - x0 + 1), float(y1 - y0 + 1)]
 
 
-def maskrcnn_results(image_id, boxes_xyxy, scores, labels, masks=None):
+def label_categories(num_classes=81, category_ids=None):
+    """The json category id of every contiguous label 1 .. num_classes - 1, as a list indexed by label (entry 0, the background, is None).
+    category_ids given: its entry label - 1 (a data set's own contiguous -> json id map; it must name num_classes - 1 ids).  Otherwise 81 classes map
+    to the COCO ids (COCO_CATEGORY_IDS), and for any other class count the label IS the category id."""
+    n = int(num_classes)
+    if category_ids is not None:
+        ids = [int(c) for c in category_ids]
+        if len(ids) != n - 1:
+            raise ValueError("category_ids names %d ids, the model has %d classes besides the background" % (len(ids), n - 1))
+        return [None] + ids
+    return [None] + (list(COCO_CATEGORY_IDS) if n == 81 else list(range(1, n)))
+
+
+def maskrcnn_results(image_id, boxes_xyxy, scores, labels, masks=None, categories=None):
     """maskrcnn-benchmark prepare_for_coco_detection/segmentation: bbox xywh with the legacy +1 widths,
-    category_id via the contiguous->json id map, segmentation = RLE of the pasted HxW mask."""
+    category_id via the contiguous->json id map (categories: a label_categories() list; default the 80 COCO classes), segmentation = RLE of the
+    pasted HxW mask (masks None: bbox-only results, no `segmentation` key)."""
     out = []
     b = np.asarray(boxes_xyxy, np.float32).reshape(-1, 4)
+    cats = categories if categories is not None else label_categories()
     for k in range(b.shape[0]):
         x1, y1, x2, y2 = (float(v) for v in b[k])
-        d = {"image_id": int(image_id), "category_id": COCO_CATEGORY_IDS[int(labels[k]) - 1],
+        d = {"image_id": int(image_id), "category_id": cats[int(labels[k])],
              "bbox": [x1, y1, x2 - x1 + 1.0, y2 - y1 + 1.0], "score": float(scores[k])}
         if masks is not None:
             d["segmentation"] = rle_encode(masks[k])
@@ -236,14 +251,17 @@ def yolact_results(image_id, classes, scores, boxes_xyxy_int, masks=None, mask_s
     return out
 
 
-def results_from_records(rec, image_ids, image_hw, kind, K=100, score_threshold=None, top_k=None):
+def results_from_records(rec, image_ids, image_hw, kind, K=100, score_threshold=None, top_k=None, categories=None):
     """One rank's unpacked record block (isegmi.dist.unpack_coco_records: the device-side output of a step) -> COCO result dicts, the
     same records maskrcnn_results / yolact_results build from host arrays: bbox conversion and category map here, `segmentation.counts`
     straight from the device-made strings.  image_ids / image_hw: per image slot of the batch (None id = an empty padding slot).
     score_threshold / top_k (Yolact eval.py --score_threshold / --top_k): keep score > threshold, then the first top_k (score order).
-    kind: 1 Yolact, 2 Mask R-CNN, 3 Pose2Seg (category 1, score 1.0, bbox = the mask's tight box)."""
+    kind: 1 Yolact, 2 Mask R-CNN, 3 Pose2Seg (category 1, score 1.0, bbox = the mask's tight box).  A box-only block (Faster R-CNN: no str_off in
+    `rec`) gives bbox-only results without a `segmentation` key.  categories (kind 2): a label_categories() list, default the 80 COCO classes."""
     out = []
-    count, box, score, label, so, chars = rec["count"], rec["box"], rec["score"], rec["label"], rec["str_off"], rec["chars"]
+    count, box, score, label = rec["count"], rec["box"], rec["score"], rec["label"]
+    so, chars = rec.get("str_off"), rec.get("chars")
+    lab_cat = categories if categories is not None else label_categories()
     ms = rec.get("mscore")
     for n, iid in enumerate(image_ids):
         c = int(count[n])
@@ -256,20 +274,21 @@ def results_from_records(rec, image_ids, image_hw, kind, K=100, score_threshold=
             cats = [1] * c
         elif kind == 2:   # prepare_for_coco_detection: xyxy -> xywh with the legacy +1
             bb = np.stack([b[:, 0], b[:, 1], b[:, 2] - b[:, 0] + 1.0, b[:, 3] - b[:, 1] + 1.0], 1).tolist()
-            cats = [COCO_CATEGORY_IDS[int(l) - 1] for l in label[n, :c]]
+            cats = [lab_cat[int(l)] for l in label[n, :c]]
         else:           # Detections.add_bbox: [x1, y1, w, h] rounded to 0.1
             bb = (np.round(np.stack([b[:, 0], b[:, 1], b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]], 1) * 10) / 10).tolist()
             cats = [COCO_CATEGORY_IDS[int(l)] for l in label[n, :c]]
         sc = np.asarray(score[n, :c], np.float64).tolist()
-        offs = so[n * K:n * K + c + 1].tolist()
+        offs = so[n * K:n * K + c + 1].tolist() if so is not None else None
         keep = range(c)
         if score_threshold is not None:
             keep = [k for k in keep if score[n, k] > np.float32(score_threshold)]
         if top_k is not None:
             keep = list(keep)[:top_k]
         for k in keep:
-            d = {"image_id": int(iid), "category_id": cats[k], "bbox": bb[k], "score": sc[k],
-                 "segmentation": {"size": [h, w], "counts": chars[offs[k]:offs[k + 1]].decode("ascii")}}
+            d = {"image_id": int(iid), "category_id": cats[k], "bbox": bb[k], "score": sc[k]}
+            if offs is not None:
+                d["segmentation"] = {"size": [h, w], "counts": chars[offs[k]:offs[k + 1]].decode("ascii")}
             if ms is not None:
                 d["mask_score"] = float(ms[n, k])
             out.append(d)

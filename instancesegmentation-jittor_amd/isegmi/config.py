@@ -70,8 +70,10 @@ def _defaults():
     c._merge({
         "INPUT": {"MIN_SIZE_TEST": 800, "MAX_SIZE_TEST": 1333, "PIXEL_MEAN": (102.9801, 115.9465, 122.7717), "TO_BGR255": True},
         "DATALOADER": {"SIZE_DIVISIBILITY": 32},
-        "TEST": {"DETECTIONS_PER_IMG": 100},
-        "MODEL": {"META_ARCHITECTURE": "GeneralizedRCNN", "WEIGHT": "", "MASK_ON": True, "RETINANET_ON": False,
+        "TEST": {"DETECTIONS_PER_IMG": 100, "BBOX_AUG": {"ENABLED": False}},
+        # MASK_ON: upstream's default is False; this project's is True -- the e2e_faster_rcnn_* yamls under configs/ spell it out
+        "MODEL": {"META_ARCHITECTURE": "GeneralizedRCNN", "WEIGHT": "", "MASK_ON": True, "RETINANET_ON": False, "RPN_ONLY": False, "KEYPOINT_ON": False,
+                  "CLS_AGNOSTIC_BBOX_REG": False,
                   "BACKBONE": {"CONV_BODY": "R-50-FPN"},
                   # [UPSTREAM-RECALL] maskrcnn-benchmark defaults.py
                   "GROUP_NORM": {"DIM_PER_GP": -1, "NUM_GROUPS": 32, "EPSILON": 1e-5},
@@ -79,7 +81,7 @@ def _defaults():
                               "RES5_DILATION": 1},
                   "FPN": {"USE_GN": False, "USE_RELU": False},
                   "ROI_BOX_HEAD": {"FEATURE_EXTRACTOR": "FPN2MLPFeatureExtractor", "USE_GN": False, "NUM_STACKED_CONVS": 4, "CONV_HEAD_DIM": 256,
-                                   "MLP_HEAD_DIM": 1024, "DILATION": 1},
+                                   "MLP_HEAD_DIM": 1024, "DILATION": 1, "NUM_CLASSES": 81},
                   "RPN": {"USE_FPN": True, "ANCHOR_SIZES": (32, 64, 128, 256, 512), "ANCHOR_STRIDE": (4, 8, 16, 32, 64),
                           "ASPECT_RATIOS": (0.5, 1.0, 2.0), "PRE_NMS_TOP_N_TEST": 1000, "POST_NMS_TOP_N_TEST": 1000,
                           "FPN_POST_NMS_TOP_N_TEST": 1000, "NMS_THRESH": 0.7, "MIN_SIZE": 0},
@@ -100,10 +102,11 @@ def _bool(v):
     return v if isinstance(v, bool) else str(v).strip().lower() in ("true", "1", "yes")
 
 
-def _norm_config(c, body):
+def _norm_config(c, body, mask_on=True):
     """The norm / head keys (MODEL.GROUP_NORM, RESNETS, FPN, ROI_BOX_HEAD, ROI_MASK_HEAD) -> MaskRCNNConfig fields.  Built: FrozenBatchNorm everywhere
     with the 2-MLP box head (today's models), or [UPSTREAM-RECALL] gn_baselines -- GroupNorm in backbone, FPN, Xconv1fc box head and mask head
-    together.  Everything else raises and names the key (none silently degrade)."""
+    together.  Everything else raises and names the key (none silently degrade).  mask_on False (MODEL.MASK_ON: Faster R-CNN): the
+    ROI_MASK_HEAD keys are not consulted, "together" is backbone + FPN + box head."""
     m = c.MODEL
     rn, fpn, bh, mh, g = m.RESNETS, m.FPN, m.ROI_BOX_HEAD, m.ROI_MASK_HEAD, m.GROUP_NORM
     trans, stem = str(rn.TRANS_FUNC), str(rn.STEM_FUNC)
@@ -111,8 +114,8 @@ def _norm_config(c, body):
         raise ValueError("MODEL.RESNETS.TRANS_FUNC=%r: built are BottleneckWithFixedBatchNorm and BottleneckWithGN" % trans)
     if stem not in ("StemWithFixedBatchNorm", "StemWithGN"):
         raise ValueError("MODEL.RESNETS.STEM_FUNC=%r: built are StemWithFixedBatchNorm and StemWithGN" % stem)
-    for key, node in (("MODEL.RESNETS.RES5_DILATION", rn.RES5_DILATION), ("MODEL.ROI_BOX_HEAD.DILATION", bh.DILATION),
-                      ("MODEL.ROI_MASK_HEAD.DILATION", mh.DILATION)):
+    for key, node in (("MODEL.RESNETS.RES5_DILATION", rn.RES5_DILATION), ("MODEL.ROI_BOX_HEAD.DILATION", bh.DILATION)) + \
+                     ((("MODEL.ROI_MASK_HEAD.DILATION", mh.DILATION),) if mask_on else ()):
         if int(node) != 1:
             raise ValueError("%s=%s: dilated convolutions are not built" % (key, node))
     if _bool(fpn.USE_RELU):
@@ -121,7 +124,8 @@ def _norm_config(c, body):
     if fx not in ("FPN2MLPFeatureExtractor", "FPNXconv1fcFeatureExtractor"):
         raise ValueError("MODEL.ROI_BOX_HEAD.FEATURE_EXTRACTOR=%r: built are FPN2MLPFeatureExtractor and FPNXconv1fcFeatureExtractor" % fx)
     flags = (("MODEL.RESNETS.TRANS_FUNC", trans == "BottleneckWithGN"), ("MODEL.RESNETS.STEM_FUNC", stem == "StemWithGN"),
-             ("MODEL.FPN.USE_GN", _bool(fpn.USE_GN)), ("MODEL.ROI_BOX_HEAD.USE_GN", _bool(bh.USE_GN)), ("MODEL.ROI_MASK_HEAD.USE_GN", _bool(mh.USE_GN)))
+             ("MODEL.FPN.USE_GN", _bool(fpn.USE_GN)), ("MODEL.ROI_BOX_HEAD.USE_GN", _bool(bh.USE_GN))) + \
+            ((("MODEL.ROI_MASK_HEAD.USE_GN", _bool(mh.USE_GN)),) if mask_on else ())
     on = [k for k, v in flags if v]
     stride_in_1x1 = _bool(rn.STRIDE_IN_1X1)
     if not on:
@@ -136,7 +140,8 @@ def _norm_config(c, body):
         raise ValueError("%s: GroupNorm is built for the FPN bodies only (MODEL.BACKBONE.CONV_BODY=%r)" % (on[0], body))
     off = [k for k, v in flags if not v]
     if off:
-        raise ValueError("%s asks for GroupNorm but %s does not: GroupNorm is built for backbone, FPN, box head and mask head together" % (on[0], off[0]))
+        raise ValueError("%s asks for GroupNorm but %s does not: GroupNorm is built for backbone, FPN, box head%s together" %
+                         (on[0], off[0], " and mask head" if mask_on else ""))
     if fx != "FPNXconv1fcFeatureExtractor":
         raise ValueError("MODEL.ROI_BOX_HEAD.FEATURE_EXTRACTOR=%r with MODEL.ROI_BOX_HEAD.USE_GN: only FPNXconv1fcFeatureExtractor has GroupNorm" % fx)
     groups, per = int(g.NUM_GROUPS), int(g.DIM_PER_GP)
@@ -147,7 +152,7 @@ def _norm_config(c, body):
         raise ValueError("MODEL.ROI_BOX_HEAD.NUM_STACKED_CONVS=%d: at least one convolution" % nconv)
     if conv_dim % 32 or mlp_dim % 32:
         raise ValueError("MODEL.ROI_BOX_HEAD.CONV_HEAD_DIM / MLP_HEAD_DIM must be multiples of 32 (%d, %d)" % (conv_dim, mlp_dim))
-    for layer, ch in gn_model_layers(box_head_conv_dim=conv_dim):   # every GroupNorm width of the model, res5's 2048 included
+    for layer, ch in gn_model_layers(box_head_conv_dim=conv_dim, mask=mask_on):   # every GroupNorm width of the model, res5's 2048 included
         gn_groups(ch, groups, per, layer)
     return dict(USE_GN=True, GN_NUM_GROUPS=groups if per <= 0 else 32, GN_DIM_PER_GP=per if per > 0 else -1, GN_EPSILON=float(g.EPSILON),
                 STRIDE_IN_1X1=stride_in_1x1, BOX_HEAD=fx, BOX_HEAD_STACKED_CONVS=nconv, BOX_HEAD_CONV_DIM=conv_dim, BOX_HEAD_MLP_DIM=mlp_dim)
@@ -158,7 +163,19 @@ def to_maskrcnn_config(c):
     body = c.MODEL.BACKBONE.CONV_BODY
     r = c.MODEL.RPN
     h = c.MODEL.ROI_HEADS
-    norm = _norm_config(c, body)
+    mask_on = _bool(c.MODEL.MASK_ON)
+    norm = _norm_config(c, body, mask_on)
+    if body not in ("R-50-FPN", "R-101-FPN", "R-50-C4"):
+        raise ValueError("built bodies: R-50-FPN, R-101-FPN, R-50-C4 (got %r)" % body)
+    for key, on in (("MODEL.RPN_ONLY", c.MODEL.get("RPN_ONLY", False)), ("MODEL.KEYPOINT_ON", c.MODEL.get("KEYPOINT_ON", False)),
+                    ("TEST.BBOX_AUG.ENABLED", c.TEST.get("BBOX_AUG", {}).get("ENABLED", False))):
+        if _bool(on):
+            raise ValueError("%s=True is not built (DESIGN.md 13: RPN-only models, keypoint heads and test-time box augmentation are out of scope)" % key)
+    # [UPSTREAM-RECALL] DESIGN.md 13: the three keys that shape the RoI heads
+    ncls = int(c.MODEL.ROI_BOX_HEAD.NUM_CLASSES)
+    if not 2 <= ncls <= 257:
+        raise ValueError("MODEL.ROI_BOX_HEAD.NUM_CLASSES=%d: the box post-processing kernels hold 2..257 classes (background included)" % ncls)
+    heads = dict(MASK_ON=mask_on, NUM_CLASSES=ncls, CLS_AGNOSTIC_BBOX_REG=_bool(c.MODEL.get("CLS_AGNOSTIC_BBOX_REG", False)))
     if body == "R-50-C4":
         # the yaml the reference prints (README.md:263-273): everything it does not set comes from maskrcnn-benchmark's
         # defaults.py -- one stride-16 map, no FPN merge, SIZE_DIVISIBILITY 0 (the engine pads to 16), 14x14 masks
@@ -169,9 +186,7 @@ def to_maskrcnn_config(c):
                               ASPECT_RATIOS=tuple(float(x) for x in r.ASPECT_RATIOS), RPN_PRE_NMS_TOP_N_TEST=int(r.PRE_NMS_TOP_N_TEST),
                               RPN_POST_NMS_TOP_N_TEST=int(r.POST_NMS_TOP_N_TEST), RPN_NMS_THRESH=float(r.NMS_THRESH),
                               RPN_MIN_SIZE=float(r.MIN_SIZE), ROI_SCORE_THRESH=float(h.SCORE_THRESH), ROI_NMS=float(h.NMS),
-                              DETECTIONS_PER_IMG=int(h.DETECTIONS_PER_IMG))
-    if body not in ("R-50-FPN", "R-101-FPN"):
-        raise ValueError("built bodies: R-50-FPN, R-101-FPN, R-50-C4 (got %r)" % body)
+                              DETECTIONS_PER_IMG=int(h.DETECTIONS_PER_IMG), **heads)
     for k in ("PRE_NMS_TOP_N_TEST", "POST_NMS_TOP_N_TEST", "FPN_POST_NMS_TOP_N_TEST"):
         if int(c.MODEL.RPN[k]) > 1024:
             raise ValueError("MODEL.RPN.%s=%d: the per-level FPN selection kernels hold at most 1024 boxes" % (k, c.MODEL.RPN[k]))
@@ -182,7 +197,7 @@ def to_maskrcnn_config(c):
                           RPN_PRE_NMS_TOP_N_TEST=int(r.PRE_NMS_TOP_N_TEST), RPN_POST_NMS_TOP_N_TEST=int(r.POST_NMS_TOP_N_TEST),
                           RPN_FPN_POST_NMS_TOP_N_TEST=int(r.FPN_POST_NMS_TOP_N_TEST), RPN_NMS_THRESH=float(r.NMS_THRESH),
                           RPN_MIN_SIZE=float(r.MIN_SIZE), ROI_SCORE_THRESH=float(h.SCORE_THRESH), ROI_NMS=float(h.NMS),
-                          DETECTIONS_PER_IMG=int(h.DETECTIONS_PER_IMG), **norm)
+                          DETECTIONS_PER_IMG=int(h.DETECTIONS_PER_IMG), **heads, **norm)
 
 
 RETINANET_BODIES = ("R-50-FPN-RETINANET", "R-101-FPN-RETINANET")

@@ -79,11 +79,20 @@ def unpack_maskrcnn_records(buf, n, K=K_DEFAULT, M=28):
 
 
 # ------------------------------------------------------------------------------------------------ COCO record block (device-side output)
-def coco_record_layout(n, K=K_DEFAULT, kind=2, has_mscore=False, cap_chars=0):
+def coco_record_layout(n, K=K_DEFAULT, kind=2, has_mscore=False, cap_chars=0, box_only=False):
     """Byte layout of the fixed-size block isegmi_engine_pack_coco_records writes for a batch of n images (csrc/results.cpp):
-    -> (sections {name: (offset, nbytes, dtype, shape)}, chars_offset, total_bytes).  kind: 1 Yolact (int64 boxes), 2 Mask R-CNN (fp32)."""
+    -> (sections {name: (offset, nbytes, dtype, shape)}, chars_offset, total_bytes).  kind: 1 Yolact (int64 boxes), 2 Mask R-CNN (fp32).
+    box_only: the block isegmi_engine_pack_box_records writes (Faster R-CNN) -- status (zeros), box, count, score, label, every section
+    starting on a multiple of 8 bytes; no str_off, no characters: chars_offset = total_bytes."""
     y = kind == 1
     secs, off = {}, 0
+    if box_only:
+        assert kind == 2 and not has_mscore and not cap_chars, "the box-only block is the Mask R-CNN family's"
+        for name, nb, dt, shp in (("status", 16, np.int32, (4,)), ("box", n * K * 16, np.float32, (n, K, 4)), ("count", n * 4, np.int32, (n,)),
+                                  ("score", n * K * 4, np.float32, (n, K)), ("label", n * K * 4, np.int32, (n, K))):
+            secs[name] = (off, nb, dt, shp)
+            off = (off + nb + 7) & ~7
+        return secs, off, off
     for name, nb, dt, shp in (("status", 16, np.int32, (4,)),
                               ("box", n * K * (32 if y else 16), np.int64 if y else np.float32, (n, K, 4)),
                               ("count", n * 4, np.int32, (n,)),
@@ -101,17 +110,19 @@ class CocoRecordError(RuntimeError):
     pass
 
 
-def unpack_coco_records(buf, n, K=K_DEFAULT, kind=2, has_mscore=False, cap_chars=0, strict=True):
+def unpack_coco_records(buf, n, K=K_DEFAULT, kind=2, has_mscore=False, cap_chars=0, strict=True, box_only=False):
     """One rank's block -> dict(status, box, count, score, label[, mscore], str_off, chars=bytes, overflow=None).  If the engine flagged an
     overflow of its RLE capacities (the strings are incomplete): strict raises CocoRecordError; otherwise the dict carries
     overflow = (bits, runs, characters) -- bit 1: runs over rle_cap_runs (`runs` = what the step needs; characters unknown then), bit 2:
     characters over rle_cap_chars -- and no strings; isegmi.pipeline.run_record_loop raises the capacities and redoes the step."""
     buf = np.ascontiguousarray(buf, np.uint8).ravel()
-    secs, coff, total = coco_record_layout(n, K, kind, has_mscore, cap_chars)
+    secs, coff, total = coco_record_layout(n, K, kind, has_mscore, cap_chars, box_only)
     assert buf.size >= total, (buf.size, total)
     out = {name: buf[off:off + nb].view(dt).reshape(shp) for name, (off, nb, dt, shp) in secs.items()}
     st = out["status"]
     out["overflow"] = None
+    if box_only:   # no strings, nothing that can overflow: dict(status, box, count, score, label, overflow=None)
+        return out
     if st[2] != 0:
         if strict:
             raise CocoRecordError("device RLE overflow (%s): %d runs, %d characters; raise the engine's rle_cap_runs / rle_cap_chars" %
@@ -228,9 +239,13 @@ class RcclGather:
         st = C.c_void_p()
         _ffi.check(L.isegmi_engine_stream(net._h, C.byref(st)))
         _ffi.check(L.isegmi_comm_fence_producer(self._c, slot, st))
-        nb = C.c_int64()
-        _ffi.check(L.isegmi_engine_pack_coco_records(net._h, send.ptr, C.c_int64(self.nbytes), int(n_block), C.byref(nb)))
-        assert nb.value == self.nbytes, (nb.value, self.nbytes)
+        if getattr(net, "box_only", False):   # Faster R-CNN: the box-only block (isegmi_engine_pack_box_records)
+            nbv = net.pack_box_records(send, n_block)
+        else:
+            nb = C.c_int64()
+            _ffi.check(L.isegmi_engine_pack_coco_records(net._h, send.ptr, C.c_int64(self.nbytes), int(n_block), C.byref(nb)))
+            nbv = nb.value
+        assert nbv == self.nbytes, (nbv, self.nbytes)
         _ffi.check(L.isegmi_engine_stream(net._h, C.byref(st)))
         _ffi.check(L.isegmi_comm_allgather_slot(self._c, slot, send.ptr, recv.ptr, C.c_int64(self.nbytes), st))
         self.slot_bytes[slot] = self.nbytes

@@ -61,6 +61,11 @@ class MaskRCNNConfig:
     BOX_HEAD_STACKED_CONVS: int = 4   # MODEL.ROI_BOX_HEAD.NUM_STACKED_CONVS
     BOX_HEAD_CONV_DIM: int = 256      # MODEL.ROI_BOX_HEAD.CONV_HEAD_DIM
     BOX_HEAD_MLP_DIM: int = 1024      # MODEL.ROI_BOX_HEAD.MLP_HEAD_DIM
+    # [UPSTREAM-RECALL] DESIGN.md 13.  MASK_ON False = Faster R-CNN (e2e_faster_rcnn_*): roi_heads = [box] only, results are boxes, scores and labels.
+    # Upstream's default is False; this project's stays True (the yamls under configs/ spell the key out).
+    MASK_ON: bool = True
+    NUM_CLASSES: int = 81                  # MODEL.ROI_BOX_HEAD.NUM_CLASSES, background included (2..257)
+    CLS_AGNOSTIC_BBOX_REG: bool = False    # MODEL.CLS_AGNOSTIC_BBOX_REG: bbox_pred has 2 * 4 outputs, the last four decoded once per proposal
 
     @staticmethod
     def c4():
@@ -96,12 +101,13 @@ def gn_groups(channels, num_groups, dim_per_gp, layer):
     return channels // cpg
 
 
-def gn_model_layers(box_head_conv_dim=256):
-    """(name, channels) of every distinct GroupNorm width of the gn_baselines model, for the checks that run before any weight is seen."""
+def gn_model_layers(box_head_conv_dim=256, mask=True):
+    """(name, channels) of every distinct GroupNorm width of the gn_baselines model, for the checks that run before any weight is seen.  mask=False:
+    without the mask head (MODEL.MASK_ON False)."""
     out = [("backbone.body.stem", 64)]
     for li in range(1, 5):
         out += [("backbone.body.layer%d (conv1 / conv2)" % li, 64 << (li - 1)), ("backbone.body.layer%d (conv3 / downsample)" % li, 256 << (li - 1))]
-    return out + [("backbone.fpn", 256), ("MODEL.ROI_BOX_HEAD.CONV_HEAD_DIM", box_head_conv_dim), ("roi_heads.mask.feature_extractor", 256)]
+    return out + [("backbone.fpn", 256), ("MODEL.ROI_BOX_HEAD.CONV_HEAD_DIM", box_head_conv_dim)] + ([("roi_heads.mask.feature_extractor", 256)] if mask else [])
 
 
 # ---------------------------------------------------------------------------------------- anchors (A.3)
@@ -240,9 +246,14 @@ class MaskRCNN:
         if cfg.USE_GN and cfg.is_c4:
             raise ValueError("USE_GN with the C4 body is not built")
         if cfg.USE_GN:   # before the engine exists: a refused configuration costs nothing and needs no device
-            for layer, ch in gn_model_layers(cfg.BOX_HEAD_CONV_DIM):
+            for layer, ch in gn_model_layers(cfg.BOX_HEAD_CONV_DIM, mask=bool(cfg.MASK_ON)):
                 gn_groups(ch, cfg.GN_NUM_GROUPS, cfg.GN_DIM_PER_GP, layer)
+        if not 2 <= int(cfg.NUM_CLASSES) <= 257:
+            raise ValueError("MODEL.ROI_BOX_HEAD.NUM_CLASSES=%s: the box post-processing kernels hold 2..257 classes (background included)" % (cfg.NUM_CLASSES,))
         self.cfg, self.H, self.W, self.max_batch = cfg, H, W, max_batch
+        self._mask_head_in(state_dict)   # before the engine exists: MASK_ON True with a mask-less dict is refused here
+        self.mask_on = bool(cfg.MASK_ON)
+        self._ratios = None
         self.mask_buf = "det.mask14" if cfg.is_c4 else "det.mask28"
         _ffi.lib()
         _ffi.set_device(device)
@@ -251,6 +262,8 @@ class MaskRCNN:
         self.fp16 = bool(fp16)
         if self.fp16:  # fp16 storage + f16 MFMA convs (BASELINE configs[4]); must precede weight loading
             self.set_param("fp16", 1.0)
+        for k, v in (("mask_on", self.mask_on), ("num_classes", cfg.NUM_CLASSES), ("cls_agnostic", bool(cfg.CLS_AGNOSTIC_BBOX_REG))):
+            self.set_param(k, float(v))
         if cfg.is_c4:
             self.set_param("arch_c4", 1.0)
             self._load_c4(state_dict)
@@ -277,9 +290,53 @@ class MaskRCNN:
         self._hw = np.tile(np.array([[self.H, self.W]], np.int32), (self.max_batch, 1))
         self._canvas = (self.H, self.W)
         self.forward_device(self.max_batch)
-        self.paste_device(self.H, self.W)
+        if self.mask_on:   # box-only: no paste stage, no det.masks / det.mask28 -- the smaller footprint is what memory() then reports
+            self.paste_device(self.H, self.W)
         self.sync()
         return self.memory()
+
+    @property
+    def box_only(self):
+        """MODEL.MASK_ON False (Faster R-CNN), or a mask engine toggled with set_mask_on(False): boxes, scores and labels only."""
+        return not self.mask_on
+
+    def set_mask_on(self, on):
+        """Toggle the mask head of a live engine ("mask_on" is read each forward).  Turning it on needs the mask head's weights."""
+        if on and not self.has_mask_head:
+            raise ValueError("set_mask_on(True): the engine was built without mask weights (MODEL.MASK_ON False)")
+        self.mask_on = bool(on)
+        self.set_param("mask_on", float(self.mask_on))
+
+    def _mask_head_in(self, sd):
+        """Whether the loaders take the mask head from `sd`: MASK_ON True needs its weights (ValueError naming the key otherwise); with MASK_ON False
+        present roi_heads.mask.* keys are ignored."""
+        has = "roi_heads.mask.predictor.mask_fcn_logits.weight" in sd
+        if self.cfg.MASK_ON and not has:
+            raise ValueError("MODEL.MASK_ON is True but the state dict has no roi_heads.mask.* weights: a Faster R-CNN checkpoint needs MODEL.MASK_ON: False")
+        self.has_mask_head = bool(self.cfg.MASK_ON) and has
+        return self.has_mask_head
+
+    def _set_box_predictor(self, sd, cin):
+        """cls_score | bbox_pred as ONE 1x1 layer: NUM_CLASSES logits, then 4 * NUM_CLASSES deltas, or 8 with CLS_AGNOSTIC_BBOX_REG."""
+        cfg = self.cfg
+        wc, wb = sd["roi_heads.box.predictor.cls_score.weight"], sd["roi_heads.box.predictor.bbox_pred.weight"]
+        ncls = int(cfg.NUM_CLASSES)
+        if wc.shape[0] != ncls:
+            raise ValueError("roi_heads.box.predictor.cls_score has %d outputs, MODEL.ROI_BOX_HEAD.NUM_CLASSES is %d" % (wc.shape[0], ncls))
+        nreg, form = (8, "2 * 4 (MODEL.CLS_AGNOSTIC_BBOX_REG: True)") if cfg.CLS_AGNOSTIC_BBOX_REG else (4 * ncls, "4 * NUM_CLASSES (MODEL.CLS_AGNOSTIC_BBOX_REG: False)")
+        if wb.shape[0] != nreg:
+            raise ValueError("roi_heads.box.predictor.bbox_pred has %d outputs: %d classes need %d = %s" % (wb.shape[0], ncls, nreg, form))
+        wp = np.concatenate([wc, wb], 0)
+        bp = np.concatenate([sd["roi_heads.box.predictor.cls_score.bias"], sd["roi_heads.box.predictor.bbox_pred.bias"]])
+        self._set_conv_krsc("roi_heads.box.predictor.cls_bbox", wp.reshape(ncls + nreg, 1, 1, cin), None, bp)
+
+    def _set_mask_logits(self, sd):
+        ncls = int(self.cfg.NUM_CLASSES)
+        w = sd["roi_heads.mask.predictor.mask_fcn_logits.weight"]
+        if w.shape[0] != ncls:
+            raise ValueError("roi_heads.mask.predictor.mask_fcn_logits has %d channels, MODEL.ROI_BOX_HEAD.NUM_CLASSES is %d" % (w.shape[0], ncls))
+        self._set_tensor("mask_logits.w", w.reshape(ncls, 256).astype(np.float32))
+        self._set_tensor("mask_logits.b", sd["roi_heads.mask.predictor.mask_fcn_logits.bias"].astype(np.float32))
 
 
     def set_param(self, name, value):
@@ -326,18 +383,16 @@ class MaskRCNN:
         self._set_conv_krsc("roi_heads.box.feature_extractor.fc6", w6, None, sd["roi_heads.box.feature_extractor.fc6.bias"])
         w7 = sd["roi_heads.box.feature_extractor.fc7.weight"].reshape(1024, 1, 1, 1024)
         self._set_conv_krsc("roi_heads.box.feature_extractor.fc7", w7, None, sd["roi_heads.box.feature_extractor.fc7.bias"])
-        wp = np.concatenate([sd["roi_heads.box.predictor.cls_score.weight"], sd["roi_heads.box.predictor.bbox_pred.weight"]], 0)
-        bp = np.concatenate([sd["roi_heads.box.predictor.cls_score.bias"], sd["roi_heads.box.predictor.bbox_pred.bias"]])
-        self._set_conv_krsc("roi_heads.box.predictor.cls_bbox", wp.reshape(405, 1, 1, 1024), None, bp)
-        for i in range(1, 5):
-            nm = "roi_heads.mask.feature_extractor.mask_fcn%d" % i
-            self._set_conv_krsc(nm, to_krsc(sd[nm + ".weight"]), None, sd[nm + ".bias"])
-        wd = sd["roi_heads.mask.predictor.conv5_mask.weight"]  # [Cin][Cout][2][2]
-        for ab in range(4):
-            wab = np.ascontiguousarray(wd[:, :, ab >> 1, ab & 1].T).reshape(256, 1, 1, 256)
-            self._set_conv_krsc("roi_heads.mask.predictor.conv5_mask.%d" % ab, wab, None, sd["roi_heads.mask.predictor.conv5_mask.bias"])
-        self._set_tensor("mask_logits.w", sd["roi_heads.mask.predictor.mask_fcn_logits.weight"].reshape(81, 256).astype(np.float32))
-        self._set_tensor("mask_logits.b", sd["roi_heads.mask.predictor.mask_fcn_logits.bias"].astype(np.float32))
+        self._set_box_predictor(sd, 1024)
+        if self._mask_head_in(sd):
+            for i in range(1, 5):
+                nm = "roi_heads.mask.feature_extractor.mask_fcn%d" % i
+                self._set_conv_krsc(nm, to_krsc(sd[nm + ".weight"]), None, sd[nm + ".bias"])
+            wd = sd["roi_heads.mask.predictor.conv5_mask.weight"]  # [Cin][Cout][2][2]
+            for ab in range(4):
+                wab = np.ascontiguousarray(wd[:, :, ab >> 1, ab & 1].T).reshape(256, 1, 1, 256)
+                self._set_conv_krsc("roi_heads.mask.predictor.conv5_mask.%d" % ab, wab, None, sd["roi_heads.mask.predictor.conv5_mask.bias"])
+            self._set_mask_logits(sd)
         # AnchorGenerator: the A base anchors per level go over; the engine lays the grid out for each batch's canvas (isegmi_op_grid_anchors)
         for l, (stride, size) in enumerate(zip(cfg.ANCHOR_STRIDE, cfg.ANCHOR_SIZES)):
             self._set_tensor("anchor_base.%d" % l, generate_anchors(stride, size, cfg.ASPECT_RATIOS))
@@ -395,18 +450,16 @@ class MaskRCNN:
         if w6.shape != (md, cd * 49):
             raise ValueError("%s.fc6.weight %s: expected (MLP_HEAD_DIM, CONV_HEAD_DIM * 7 * 7) = (%d, %d)" % (fx, w6.shape, md, cd * 49))
         self._set_conv_krsc(fx + ".fc6", w6.reshape(md, cd, 7, 7).transpose(0, 2, 3, 1), None, sd[fx + ".fc6.bias"])
-        wp = np.concatenate([sd["roi_heads.box.predictor.cls_score.weight"], sd["roi_heads.box.predictor.bbox_pred.weight"]], 0)
-        bp = np.concatenate([sd["roi_heads.box.predictor.cls_score.bias"], sd["roi_heads.box.predictor.bbox_pred.bias"]])
-        self._set_conv_krsc("roi_heads.box.predictor.cls_bbox", wp.reshape(405, 1, 1, md), None, bp)
-        for i in range(1, 5):
-            nm = "roi_heads.mask.feature_extractor.mask_fcn%d" % i
-            self._set_gn_conv(sd, nm, nm + ".0", nm + ".1")
-        wd = sd["roi_heads.mask.predictor.conv5_mask.weight"]  # [Cin][Cout][2][2]
-        for ab in range(4):
-            wab = np.ascontiguousarray(wd[:, :, ab >> 1, ab & 1].T).reshape(256, 1, 1, 256)
-            self._set_conv_krsc("roi_heads.mask.predictor.conv5_mask.%d" % ab, wab, None, sd["roi_heads.mask.predictor.conv5_mask.bias"])
-        self._set_tensor("mask_logits.w", sd["roi_heads.mask.predictor.mask_fcn_logits.weight"].reshape(81, 256).astype(np.float32))
-        self._set_tensor("mask_logits.b", sd["roi_heads.mask.predictor.mask_fcn_logits.bias"].astype(np.float32))
+        self._set_box_predictor(sd, md)
+        if self._mask_head_in(sd):
+            for i in range(1, 5):
+                nm = "roi_heads.mask.feature_extractor.mask_fcn%d" % i
+                self._set_gn_conv(sd, nm, nm + ".0", nm + ".1")
+            wd = sd["roi_heads.mask.predictor.conv5_mask.weight"]  # [Cin][Cout][2][2]
+            for ab in range(4):
+                wab = np.ascontiguousarray(wd[:, :, ab >> 1, ab & 1].T).reshape(256, 1, 1, 256)
+                self._set_conv_krsc("roi_heads.mask.predictor.conv5_mask.%d" % ab, wab, None, sd["roi_heads.mask.predictor.conv5_mask.bias"])
+            self._set_mask_logits(sd)
         for l, (stride, size) in enumerate(zip(cfg.ANCHOR_STRIDE, cfg.ANCHOR_SIZES)):
             self._set_tensor("anchor_base.%d" % l, generate_anchors(stride, size, cfg.ASPECT_RATIOS))
             self.set_param("anchor_stride%d" % l, float(stride))
@@ -437,15 +490,13 @@ class MaskRCNN:
         wcb = np.concatenate([to_krsc(sd["rpn.head.cls_logits.weight"]), to_krsc(sd["rpn.head.bbox_pred.weight"])], 0)
         bcb = np.concatenate([sd["rpn.head.cls_logits.bias"], sd["rpn.head.bbox_pred.bias"]])
         self._set_conv_krsc("rpn.head.cls_bbox", wcb, None, bcb)
-        wp = np.concatenate([sd["roi_heads.box.predictor.cls_score.weight"], sd["roi_heads.box.predictor.bbox_pred.weight"]], 0)
-        bp = np.concatenate([sd["roi_heads.box.predictor.cls_score.bias"], sd["roi_heads.box.predictor.bbox_pred.bias"]])
-        self._set_conv_krsc("roi_heads.box.predictor.cls_bbox", wp.reshape(405, 1, 1, 2048), None, bp)
-        wd = sd["roi_heads.mask.predictor.conv5_mask.weight"]  # [Cin 2048][Cout 256][2][2]
-        for ab in range(4):
-            wab = np.ascontiguousarray(wd[:, :, ab >> 1, ab & 1].T).reshape(256, 1, 1, wd.shape[0])
-            self._set_conv_krsc("roi_heads.mask.predictor.conv5_mask.%d" % ab, wab, None, sd["roi_heads.mask.predictor.conv5_mask.bias"])
-        self._set_tensor("mask_logits.w", sd["roi_heads.mask.predictor.mask_fcn_logits.weight"].reshape(81, 256).astype(np.float32))
-        self._set_tensor("mask_logits.b", sd["roi_heads.mask.predictor.mask_fcn_logits.bias"].astype(np.float32))
+        self._set_box_predictor(sd, 2048)
+        if self._mask_head_in(sd):
+            wd = sd["roi_heads.mask.predictor.conv5_mask.weight"]  # [Cin 2048][Cout 256][2][2]
+            for ab in range(4):
+                wab = np.ascontiguousarray(wd[:, :, ab >> 1, ab & 1].T).reshape(256, 1, 1, wd.shape[0])
+                self._set_conv_krsc("roi_heads.mask.predictor.conv5_mask.%d" % ab, wab, None, sd["roi_heads.mask.predictor.conv5_mask.bias"])
+            self._set_mask_logits(sd)
         self._set_tensor("anchor_base.0", generate_anchors_multi(16, cfg.ANCHOR_SIZES, cfg.ASPECT_RATIOS))
         self.set_param("anchor_stride0", 16.0)
 
@@ -515,13 +566,36 @@ class MaskRCNN:
 
     def paste_device(self, out_h, out_w, orig_sizes_wh=None):
         """Masker paste into (out_h, out_w); orig_sizes_wh [N,2] are the sizes boxes are resized to (default: no resize)."""
+        if self.box_only:
+            raise RuntimeError("paste_device: the engine is box-only (MODEL.MASK_ON False): there are no masks to paste")
+        ratios = self._resize_ratios(orig_sizes_wh)
+        _ffi.check(_ffi.lib().isegmi_maskrcnn_paste(self._h, ratios.ctypes.data_as(C.c_void_p), out_h, out_w))
+
+    def _resize_ratios(self, orig_sizes_wh):
+        """(out_w / w, out_h / h) per image of the last upload as float32, computed like BoxList.resize."""
         n = self._hw.shape[0]
         if orig_sizes_wh is None:
-            ratios = np.ones((n, 2), np.float32)
-        else:
-            o = np.asarray(orig_sizes_wh, np.float64).reshape(n, 2)
-            ratios = np.stack([o[:, 0] / self._hw[:, 1], o[:, 1] / self._hw[:, 0]], 1).astype(np.float32)
-        _ffi.check(_ffi.lib().isegmi_maskrcnn_paste(self._h, ratios.ctypes.data_as(C.c_void_p), out_h, out_w))
+            return np.ones((n, 2), np.float32)
+        o = np.asarray(orig_sizes_wh, np.float64).reshape(n, 2)
+        return np.ascontiguousarray(np.stack([o[:, 0] / self._hw[:, 1], o[:, 1] / self._hw[:, 0]], 1).astype(np.float32))
+
+    def rle_device(self, image_hw=None):
+        if self.box_only:
+            raise RuntimeError("rle_device: the engine is box-only (MODEL.MASK_ON False): there are no masks to encode")
+        return _Y.rle_device(self, image_hw)
+
+    def set_output_sizes(self, orig_sizes_wh=None):
+        """Box-only results stage: the (w, h) the boxes of the last upload are resized to by pack_box_records (default: no resize)."""
+        self._ratios = self._resize_ratios(orig_sizes_wh)
+
+    def pack_box_records(self, dev_buffer, n_block):
+        """isegmi_engine_pack_box_records: the box-only record block (isegmi.dist.coco_record_layout(..., box_only=True)) of the last forward, boxes
+        in the coordinates set_output_sizes named, into dev_buffer on the results stream.  -> bytes written."""
+        n = self._hw.shape[0]
+        r = self._ratios if self._ratios is not None and self._ratios.shape[0] == n else np.ones((n, 2), np.float32)
+        nb = C.c_int64()
+        _ffi.check(_ffi.lib().isegmi_engine_pack_box_records(self._h, r.ctypes.data_as(C.c_void_p), dev_buffer.ptr, C.c_int64(dev_buffer.nbytes), int(n_block), C.byref(nb)))
+        return nb.value
 
     def sync(self):
         _ffi.check(_ffi.lib().isegmi_engine_sync(self._h))
@@ -531,19 +605,21 @@ class MaskRCNN:
 
     def __call__(self, batch_nhwc3, image_hw=None):
         """-> list of BoxList (one per image, in network-input coordinates) with scores, labels, mask [n,1,28,28]
-        (14x14 for the C4 predictor).  With image_hw = None the first argument is a list of already-resized uint8 BGR images and goes
+        (14x14 for the C4 predictor; no mask field from a box-only engine).  With image_hw = None the first argument is a list of already-resized uint8 BGR images and goes
         through the device front end (upload_u8: mean subtraction and padding on the GPU)."""
         n = self.upload_u8(batch_nhwc3) if image_hw is None else self.upload(batch_nhwc3, image_hw)
         self.forward_device(n)
         self.sync()
         cnt = self.fetch("det.count", n)
-        box, score, label, m28 = (self.fetch(k, n) for k in ("det.box", "det.score", "det.label", self.mask_buf))
+        box, score, label = (self.fetch(k, n) for k in ("det.box", "det.score", "det.label"))
+        m28 = self.fetch(self.mask_buf, n) if self.mask_on else None
         out = []
         for i in range(n):
             c = int(cnt[i])
             bl = BoxList(box[i, :c], (int(self._hw[i, 1]), int(self._hw[i, 0])))
             bl.add_field("scores", score[i, :c]); bl.add_field("labels", label[i, :c].astype(np.int64))
-            bl.add_field("mask", m28[i, :c, None])
+            if m28 is not None:
+                bl.add_field("mask", m28[i, :c, None])
             out.append(bl)
         return out
 
@@ -569,5 +645,5 @@ MaskRCNN.mark_step = _Y.mark_step
 MaskRCNN._u8_staging = _Y._u8_staging
 MaskRCNN._preprocess_u8 = _Y._preprocess_u8
 MaskRCNN.step_times = _Y.step_times
-for _n in ("wait_mark", "rle_device", "coco_record_bytes", "pack_coco_records", "download_async", "download_fence", "download_wait", "memory"):
+for _n in ("wait_mark", "coco_record_bytes", "pack_coco_records", "download_async", "download_fence", "download_wait", "memory"):
     setattr(MaskRCNN, _n, getattr(_Y, _n))

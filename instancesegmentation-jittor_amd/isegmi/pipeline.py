@@ -18,8 +18,9 @@ class RecordPipeline:
         self.kind = net.KIND
         self.K = int(net.cfg.max_num_detections if self.kind == 1 else net.cfg.det_cap)
         self.has_mscore = bool(self.kind == 1 and getattr(net, "has_maskiou", False))
+        self.box_only = bool(getattr(net, "box_only", False))   # Faster R-CNN: the box-only block -- no strings, no RLE capacities, no mask planes
         self.nbytes, self.chars_off = net.coco_record_bytes(self.batch)
-        secs, coff, _ = coco_record_layout(self.batch, self.K, self.kind, self.has_mscore, 0)
+        secs, coff, _ = coco_record_layout(self.batch, self.K, self.kind, self.has_mscore, 0, self.box_only)
         assert coff == self.chars_off, (coff, self.chars_off)
         self.cap_chars = self.nbytes - self.chars_off
         if gather is None:
@@ -37,12 +38,16 @@ class RecordPipeline:
         self.pending = []  # (slot, meta) of steps whose records have not been handed out yet
         # the mask planes are consumed by the run-length encoder alone, through the box windows the paste / mask assembly kernels leave next to
         # them: their zero background (242 MB per Yolact bs=8 step, 107 MB per Mask R-CNN image) is not written while the pipeline is open
-        net.set_param("sparse_masks", 1.0)
+        if not self.box_only:
+            net.set_param("sparse_masks", 1.0)
 
     def _emit(self, slot):
         if self.gather is None:
             self.net.download_fence(slot)        # the slot's previous download has left the device buffer
-            self.net.pack_coco_records(self.dev[slot], self.batch)
+            if self.box_only:
+                self.net.pack_box_records(self.dev[slot], self.batch)
+            else:
+                self.net.pack_coco_records(self.dev[slot], self.batch)
             self.net.download_async(slot, self.pin[slot], self.dev[slot], self.nbytes)
         else:
             self.gather.gather_coco_from(self.net, self.batch)
@@ -57,11 +62,11 @@ class RecordPipeline:
         return [self._unpack(blocks[r]) for r in range(self.gather.world)]
 
     def _unpack(self, buf):
-        r = unpack_coco_records(buf, self.batch, self.K, self.kind, self.has_mscore, self.cap_chars, strict=self.strict)
+        r = unpack_coco_records(buf, self.batch, self.K, self.kind, self.has_mscore, self.cap_chars, strict=self.strict, box_only=self.box_only)
         return {k: (np.array(v) if isinstance(v, np.ndarray) else v) for k, v in r.items()}  # copies: the pinned slot is reused two steps later
 
     def submit(self, meta=None):
-        """Call after net.rle_device() of the current step.  Returns (meta, [records per rank]) of the previous step, or None."""
+        """Call after net.rle_device() of the current step (box-only: after the forward and net.set_output_sizes()).  Returns (meta, [records per rank]) of the previous step, or None."""
         slot = self.step % 2
         out = None
         if len(self.pending) == 2:  # the slot about to be reused still holds an unread step
@@ -112,7 +117,8 @@ class RecordPipeline:
             self.net.sync()
         finally:
             try:
-                self.net.set_param("sparse_masks", 0.0)
+                if not self.box_only:
+                    self.net.set_param("sparse_masks", 0.0)
             finally:
                 for b in self.dev + self.pin:
                     try:

@@ -26,15 +26,18 @@ class COCODemo:
             retina = is_retinanet(cfg)
             if state_dict is None and getattr(cfg.MODEL, "WEIGHT", ""):
                 w = cfg.MODEL.WEIGHT
-                from .weights import maskrcnn_c4_state_dict, maskrcnn_state_dict, retinanet_state_dict
+                from .weights import random_maskrcnn_state_dict, retinanet_state_dict
                 body = cfg.MODEL.BACKBONE.CONV_BODY
                 depth = 101 if "101" in body else 50
-                rnd = (lambda: retinanet_state_dict(1234, depth)) if retina else \
-                    (lambda: maskrcnn_c4_state_dict(1234)) if body.endswith("-C4") else (lambda: maskrcnn_state_dict(1234, depth))
+                # MODEL.WEIGHT random: the seeded generator of the configured model (body, norm, MASK_ON, NUM_CLASSES, CLS_AGNOSTIC_BBOX_REG)
+                rnd = (lambda: retinanet_state_dict(1234, depth)) if retina else (lambda: random_maskrcnn_state_dict(to_maskrcnn_config(cfg), 1234))
                 state_dict = rnd() if w == "random" else dict(np.load(w))
             cfg = to_retinanet_config(cfg) if retina else to_maskrcnn_config(cfg)
         self.cfg = cfg or MaskRCNNConfig()
         self.is_retinanet = isinstance(self.cfg, RetinaNetConfig)   # MODEL.RETINANET_ON: boxes, scores and labels; no masks
+        self.box_only = not self.is_retinanet and not self.cfg.MASK_ON   # MODEL.MASK_ON False: Faster R-CNN, the same
+        if not self.is_retinanet and self.cfg.NUM_CLASSES != 81:      # labels of another class count have no COCO names
+            self.CATEGORIES = ("__background",) + tuple("class %d" % i for i in range(1, self.cfg.NUM_CLASSES))
         if state_dict is None:
             raise ValueError("COCODemo needs weights: pass state_dict=... or set cfg.MODEL.WEIGHT to an .npz (or 'random'); "
                              "the reference's download URLs (README.md:266) cannot be fetched here")
@@ -63,12 +66,13 @@ class COCODemo:
         return self._model
 
     def compute_prediction(self, original_image):
-        """-> BoxList in ORIGINAL image coordinates with scores, labels and mask [n,1,H,W] uint8 (Masker output); RetinaNet: no mask field."""
+        """-> BoxList in ORIGINAL image coordinates with scores, labels and mask [n,1,H,W] uint8 (Masker output); RetinaNet and Faster R-CNN
+        (MODEL.MASK_ON False): no mask field."""
         h, w = original_image.shape[:2]
         resized = maskrcnn_resize_u8(original_image, self.min_image_size, self.max_image_size)
         model = self.engine()
         (pred,) = model([resized])  # device front end: the bytes cross PCIe, mean subtraction + padding (to_image_list) run on the GPU
-        if self.is_retinanet:
+        if self.is_retinanet or self.box_only:
             return pred.resize((w, h))
         model.paste_device(h, w, [(w, h)])
         model.sync()
@@ -132,7 +136,7 @@ class COCODemo:
 
 
 def inference(predictor, images, image_ids=None, batch_size=None, group="canvas", rank=0, world=1, sizes=None, stats=None, force_gather=False,
-              workers=4):
+              workers=4, category_ids=None):
     """engine/inference.py-shaped evaluation (README.md:344-347): images -> COCO-format result list (bbox + segm) ready for json.dump.
 
     The path the benchmark measures, end to end: batches of `batch_size` resized uint8 images go up through pinned memory (double-buffered),
@@ -147,11 +151,15 @@ def inference(predictor, images, image_ids=None, batch_size=None, group="canvas"
             ASPECT_RATIO_GROUPING (portrait / landscape), results then depend on the batch composition exactly as upstream's do.
     stats:  optional dict, receives steps / images / seconds of the device loop.
     workers: host threads that load + resize (PIL, which releases the GIL) the NEXT batch while the current one is enqueued and the previous
-            one's records are unpacked; 0 = inline."""
+            one's records are unpacked; 0 = inline.
+    category_ids: the data set's json category id of labels 1, 2, ... (two-stage models; default: the COCO ids for 81 classes, the label itself for
+            any other class count).
+    A Faster R-CNN predictor (MODEL.MASK_ON False) takes the same loop with the box-only record block: no paste, no RLE, bbox-only results (xywh with
+    the legacy +1, no `segmentation` key)."""
     import time
     if getattr(predictor, "is_retinanet", False):
         return _inference_boxes(predictor, images, image_ids, batch_size, group, rank, world, sizes, stats, workers)
-    from .coco import results_from_records
+    from .coco import label_categories, results_from_records
     from .pipeline import record_capacity, run_record_loop, schedule_batches
     from .transforms import get_size
     from .maskrcnn import padded_canvas
@@ -166,6 +174,8 @@ def inference(predictor, images, image_ids=None, batch_size=None, group="canvas"
     bs = int(batch_size or predictor.max_batch)
     model = predictor.engine(bs)
     cfg = predictor.cfg
+    categories = label_categories(getattr(cfg, "NUM_CLASSES", 81), category_ids)
+    box_only = bool(getattr(model, "box_only", False))
     rs = [get_size(w, h, predictor.min_image_size, predictor.max_image_size) for h, w in sizes]   # resized (h, w) per image
     if group == "canvas":
         keys = [padded_canvas([r], cfg.SIZE_DIVISIBILITY) for r in rs]
@@ -188,7 +198,7 @@ def inference(predictor, images, image_ids=None, batch_size=None, group="canvas"
             b = batches[j]
             slot_ids = [ids[i] for i in b] + [None] * (bs - len(b))
             slot_hw = [sizes[i] for i in b] + [(1, 1)] * (bs - len(b))
-            res = results_from_records(rec, slot_ids, slot_hw, 2, K)
+            res = results_from_records(rec, slot_ids, slot_hw, 2, K, categories=categories)
             by_id = {}
             for d in res:
                 by_id.setdefault(d["image_id"], []).append(d)
@@ -224,6 +234,9 @@ def inference(predictor, images, image_ids=None, batch_size=None, group="canvas"
         model.upload_u8_async(pin[slot], hw, slot)
         model.forward_device(len(b), slot)
         oh = [sizes[i] for i in b]
+        if box_only:   # the record block's one launch scales the boxes to the original sizes
+            model.set_output_sizes([(w, h) for h, w in oh])
+            return True
         model.paste_device(max(h for h, _ in oh), max(w for _, w in oh), [(w, h) for h, w in oh])
         model.rle_device(oh)
         return True

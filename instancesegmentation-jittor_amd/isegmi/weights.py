@@ -177,8 +177,22 @@ def _gn(rng, sd, prefix, c, wscale=1.0):
     sd[prefix + ".bias"] = (rng.standard_normal(c) * 0.1).astype(np.float32)
 
 
-def maskrcnn_gn_state_dict(seed=1234, depth=50, stacked_convs=4, conv_head_dim=256, mlp_head_dim=1024):
-    """[UPSTREAM-RECALL] maskrcnn-benchmark gn_baselines/e2e_mask_rcnn_R_50_FPN_1x_gn state-dict names: the norms sit where the FrozenBN sat
+def _box_predictor_widths(num_classes, cls_agnostic):
+    """(cls_score rows, bbox_pred rows) of the box predictor: MODEL.ROI_BOX_HEAD.NUM_CLASSES logits; 4 deltas per class, or two sets of four with
+    MODEL.CLS_AGNOSTIC_BBOX_REG."""
+    if not 2 <= int(num_classes) <= 257:
+        raise ValueError("num_classes (MODEL.ROI_BOX_HEAD.NUM_CLASSES) = %s: 2..257" % (num_classes,))
+    return int(num_classes), 8 if cls_agnostic else 4 * int(num_classes)
+
+
+def _drop_mask_head(sd):
+    """Faster R-CNN (MODEL.MASK_ON False): the mask head is drawn and dropped, so every remaining tensor equals the Mask R-CNN dict's of the same seed."""
+    return {k: v for k, v in sd.items() if not k.startswith("roi_heads.mask.")}
+
+
+def maskrcnn_gn_state_dict(seed=1234, depth=50, stacked_convs=4, conv_head_dim=256, mlp_head_dim=1024, mask=True, num_classes=81, cls_agnostic=False):
+    """mask=False: without roi_heads.mask.* (e2e_faster_rcnn_*); num_classes / cls_agnostic size the predictors.
+    [UPSTREAM-RECALL] maskrcnn-benchmark gn_baselines/e2e_mask_rcnn_R_50_FPN_1x_gn state-dict names: the norms sit where the FrozenBN sat
     (stem.bn1, bn1/bn2/bn3, downsample.1) with weight and bias only; fpn_innerK / fpn_layerK / mask_fcnK are Sequential(conv, GN) -> `.0.weight`,
     `.1.{weight,bias}`; box head xconvs.{0,3,6,9} (conv) and xconvs.{1,4,7,10} (GN), fc6, no fc7.  GN convolutions have no bias."""
     rng = np.random.default_rng(seed)
@@ -210,23 +224,26 @@ def maskrcnn_gn_state_dict(seed=1234, depth=50, stacked_convs=4, conv_head_dim=2
     def fc(name, cout, cin, gain=1.0):
         sd[name + ".weight"] = (rng.standard_normal((cout, cin)) * gain * np.sqrt(2.0 / cin)).astype(np.float32)
         sd[name + ".bias"] = (rng.standard_normal(cout) * 0.01).astype(np.float32)
+    ncls, nreg = _box_predictor_widths(num_classes, cls_agnostic)
     fc("roi_heads.box.feature_extractor.fc6", mlp_head_dim, conv_head_dim * 7 * 7)
-    fc("roi_heads.box.predictor.cls_score", 81, mlp_head_dim, MRCNN_GN_CLS_GAIN)
-    fc("roi_heads.box.predictor.bbox_pred", 324, mlp_head_dim, MRCNN_GN_BBOX_GAIN)
+    fc("roi_heads.box.predictor.cls_score", ncls, mlp_head_dim, MRCNN_GN_CLS_GAIN)
+    fc("roi_heads.box.predictor.bbox_pred", nreg, mlp_head_dim, MRCNN_GN_BBOX_GAIN)
     sd["roi_heads.box.predictor.cls_score.bias"][0] += MRCNN_GN_BG_BIAS
     for i in range(1, 5):
         sd["roi_heads.mask.feature_extractor.mask_fcn%d.0.weight" % i] = _conv(rng, 256, 256, 3)
         _gn(rng, sd, "roi_heads.mask.feature_extractor.mask_fcn%d.1" % i, 256)
     sd["roi_heads.mask.predictor.conv5_mask.weight"] = (rng.standard_normal((256, 256, 2, 2)) * np.sqrt(2.0 / 256)).astype(np.float32)
     sd["roi_heads.mask.predictor.conv5_mask.bias"] = (rng.standard_normal(256) * 0.01).astype(np.float32)
-    _conv_bias(rng, sd, "roi_heads.mask.predictor.mask_fcn_logits", 81, 256, 1, gain=MRCNN_GN_MASK_LOGIT_GAIN)
-    return sd
+    _conv_bias(rng, sd, "roi_heads.mask.predictor.mask_fcn_logits", ncls, 256, 1, gain=MRCNN_GN_MASK_LOGIT_GAIN)
+    return sd if mask else _drop_mask_head(sd)
 
 
-def maskrcnn_state_dict(seed=1234, depth=50, gn=False):
-    """maskrcnn-benchmark e2e_mask_rcnn_R_50/101_FPN state-dict names; gn=True: the GroupNorm model (maskrcnn_gn_state_dict)."""
+def maskrcnn_state_dict(seed=1234, depth=50, gn=False, mask=True, num_classes=81, cls_agnostic=False):
+    """maskrcnn-benchmark e2e_mask_rcnn_R_50/101_FPN state-dict names; gn=True: the GroupNorm model (maskrcnn_gn_state_dict).
+    mask=False: the e2e_faster_rcnn_* key set (no roi_heads.mask.*); num_classes / cls_agnostic size the predictors."""
     if gn:
-        return maskrcnn_gn_state_dict(seed, depth)
+        return maskrcnn_gn_state_dict(seed, depth, mask=mask, num_classes=num_classes, cls_agnostic=cls_agnostic)
+    ncls, nreg = _box_predictor_widths(num_classes, cls_agnostic)
     rng = np.random.default_rng(seed)
     sd = {}
     blocks = (3, 4, 23 if depth == 101 else 6, 3)
@@ -251,15 +268,15 @@ def maskrcnn_state_dict(seed=1234, depth=50, gn=False):
         sd[name + ".bias"] = (rng.standard_normal(cout) * 0.01).astype(np.float32)
     fc("roi_heads.box.feature_extractor.fc6", 1024, 256 * 7 * 7)
     fc("roi_heads.box.feature_extractor.fc7", 1024, 1024)
-    fc("roi_heads.box.predictor.cls_score", 81, 1024, MRCNN_CLS_GAIN)
-    fc("roi_heads.box.predictor.bbox_pred", 324, 1024, MRCNN_BBOX_GAIN)
+    fc("roi_heads.box.predictor.cls_score", ncls, 1024, MRCNN_CLS_GAIN)
+    fc("roi_heads.box.predictor.bbox_pred", nreg, 1024, MRCNN_BBOX_GAIN)
     sd["roi_heads.box.predictor.cls_score.bias"][0] += MRCNN_BG_BIAS
     for i in range(1, 5):
         _conv_bias(rng, sd, "roi_heads.mask.feature_extractor.mask_fcn%d" % i, 256, 256, 3)
     sd["roi_heads.mask.predictor.conv5_mask.weight"] = (rng.standard_normal((256, 256, 2, 2)) * np.sqrt(2.0 / 256)).astype(np.float32)
     sd["roi_heads.mask.predictor.conv5_mask.bias"] = (rng.standard_normal(256) * 0.01).astype(np.float32)
-    _conv_bias(rng, sd, "roi_heads.mask.predictor.mask_fcn_logits", 81, 256, 1, gain=MRCNN_MASK_LOGIT_GAIN)
-    return sd
+    _conv_bias(rng, sd, "roi_heads.mask.predictor.mask_fcn_logits", ncls, 256, 1, gain=MRCNN_MASK_LOGIT_GAIN)
+    return sd if mask else _drop_mask_head(sd)
 
 
 # Recorded calibration of the RetinaNet predictors (found with the CPU reference tests/retinanet_ref.py on the seeded 256 x 352 test canvas of
@@ -312,10 +329,12 @@ C4_BBOX_GAIN = 0.0002
 C4_MASK_LOGIT_GAIN = 0.0005
 
 
-def maskrcnn_c4_state_dict(seed=1234):
+def maskrcnn_c4_state_dict(seed=1234, mask=True, num_classes=81, cls_agnostic=False):
     """maskrcnn-benchmark e2e_mask_rcnn_R_50_C4_1x state-dict names: backbone.body.{stem,layer1..3}; rpn.head on 1024 channels with
     15 anchors; roi_heads.box.feature_extractor.head.layer4 (conv5 head, shared with the mask branch); FastRCNNPredictor on 2048;
-    MaskRCNNC4Predictor (ConvTranspose 2048 -> 256, 1x1 -> 81)."""
+    MaskRCNNC4Predictor (ConvTranspose 2048 -> 256, 1x1 -> 81).  mask=False: e2e_faster_rcnn_R_50_C4_1x (no roi_heads.mask.*, the shared
+    extractor's mask-side alias included); num_classes / cls_agnostic size the predictors."""
+    ncls, nreg = _box_predictor_widths(num_classes, cls_agnostic)
     rng = np.random.default_rng(seed)
     sd = {}
     tmp = {}
@@ -339,13 +358,24 @@ def maskrcnn_c4_state_dict(seed=1234):
     def fc(name, cout, cin, gain=1.0):
         sd[name + ".weight"] = (rng.standard_normal((cout, cin)) * gain * np.sqrt(2.0 / cin)).astype(np.float32)
         sd[name + ".bias"] = (rng.standard_normal(cout) * 0.01).astype(np.float32)
-    fc("roi_heads.box.predictor.cls_score", 81, 2048, C4_CLS_GAIN)
-    fc("roi_heads.box.predictor.bbox_pred", 324, 2048, C4_BBOX_GAIN)
+    fc("roi_heads.box.predictor.cls_score", ncls, 2048, C4_CLS_GAIN)
+    fc("roi_heads.box.predictor.bbox_pred", nreg, 2048, C4_BBOX_GAIN)
     sd["roi_heads.box.predictor.cls_score.bias"][0] += C4_BG_BIAS
     sd["roi_heads.mask.predictor.conv5_mask.weight"] = (rng.standard_normal((2048, 256, 2, 2)) * np.sqrt(2.0 / 2048)).astype(np.float32)
     sd["roi_heads.mask.predictor.conv5_mask.bias"] = (rng.standard_normal(256) * 0.01).astype(np.float32)
-    _conv_bias(rng, sd, "roi_heads.mask.predictor.mask_fcn_logits", 81, 256, 1, gain=C4_MASK_LOGIT_GAIN)
-    return sd
+    _conv_bias(rng, sd, "roi_heads.mask.predictor.mask_fcn_logits", ncls, 256, 1, gain=C4_MASK_LOGIT_GAIN)
+    return sd if mask else _drop_mask_head(sd)
+
+
+def random_maskrcnn_state_dict(cfg, seed=1234):
+    """The seeded weights of `MODEL.WEIGHT random` for a MaskRCNNConfig: the generator of its body / norm, sized by MASK_ON, NUM_CLASSES and
+    CLS_AGNOSTIC_BBOX_REG."""
+    kw = dict(mask=bool(cfg.MASK_ON), num_classes=int(cfg.NUM_CLASSES), cls_agnostic=bool(cfg.CLS_AGNOSTIC_BBOX_REG))
+    if cfg.is_c4:
+        return maskrcnn_c4_state_dict(seed, **kw)
+    if cfg.USE_GN:
+        return maskrcnn_gn_state_dict(seed, cfg.depth, cfg.BOX_HEAD_STACKED_CONVS, cfg.BOX_HEAD_CONV_DIM, cfg.BOX_HEAD_MLP_DIM, **kw)
+    return maskrcnn_state_dict(seed, cfg.depth, **kw)
 
 
 # Synthetic pose templates in the 64 x 64 align frame, COCO keypoint order (nose, eyes, ears, shoulders, elbows, wrists, hips, knees,

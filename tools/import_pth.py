@@ -2,7 +2,8 @@
 upstream key names isegmi.yolact.Yolact / isegmi.maskrcnn.MaskRCNN consume.
 
     python tools/import_pth.py IN OUT.npz [--family maskrcnn_r50_fpn|maskrcnn_r101_fpn|maskrcnn_r50_c4|maskrcnn_r50_fpn_gn|yolact_resnet50|yolact_base|
-                                                    yolact_im700|yolact_darknet53|yolact_plus_resnet50|yolact_plus_base|retinanet_r50_fpn|retinanet_r101_fpn]
+                                                    yolact_im700|yolact_darknet53|yolact_plus_resnet50|yolact_plus_base|retinanet_r50_fpn|retinanet_r101_fpn|
+                                                    fasterrcnn_r50_fpn|fasterrcnn_r101_fpn|fasterrcnn_r50_c4|fasterrcnn_r50_fpn_gn]
 
 Accepted inputs (torch is used HERE only to unpickle -- a tool, not the product):
   * dbolya/yolact `.pth` (the tables at README.md:209-221): a flat state dict; `module.` prefixes, `num_batches_tracked`, the
@@ -31,14 +32,20 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "instancesegmentation-jittor_amd")]
 
 FAMILIES = ("maskrcnn_r50_fpn", "maskrcnn_r101_fpn", "maskrcnn_r50_c4", "maskrcnn_r50_fpn_gn", "yolact_resnet50", "yolact_base", "yolact_im700",
-            "yolact_darknet53", "yolact_plus_resnet50", "yolact_plus_base", "retinanet_r50_fpn", "retinanet_r101_fpn")
+            "yolact_darknet53", "yolact_plus_resnet50", "yolact_plus_base", "retinanet_r50_fpn", "retinanet_r101_fpn",
+            "fasterrcnn_r50_fpn", "fasterrcnn_r101_fpn", "fasterrcnn_r50_c4", "fasterrcnn_r50_fpn_gn")
 
 
 def expected_keys(family):
     """The complete state-dict key set (and shapes) of a model family, from the synthetic generators."""
     from isegmi import weights as W
     from isegmi.yolact import YolactConfig
-    if family == "maskrcnn_r50_fpn":
+    if family.startswith("fasterrcnn_"):
+        # [UPSTREAM-RECALL] e2e_faster_rcnn_*: the Mask R-CNN family's key set without roi_heads.mask.* (DESIGN.md 13)
+        sd = {"fasterrcnn_r50_fpn": lambda: W.maskrcnn_state_dict(0, 50, mask=False), "fasterrcnn_r101_fpn": lambda: W.maskrcnn_state_dict(0, 101, mask=False),
+              "fasterrcnn_r50_c4": lambda: W.maskrcnn_c4_state_dict(0, mask=False),
+              "fasterrcnn_r50_fpn_gn": lambda: W.maskrcnn_state_dict(0, 50, gn=True, mask=False)}[family]()
+    elif family == "maskrcnn_r50_fpn":
         sd = W.maskrcnn_state_dict(0, 50)
     elif family == "maskrcnn_r101_fpn":
         sd = W.maskrcnn_state_dict(0, 101)
@@ -118,8 +125,8 @@ def convert(sd, family=None, allow_partial=False):
         flat[k[7:] if k.startswith("module.") else k] = _to_numpy(v)
     out = {}
     if is_caffe2(set(flat)):
-        if family is None or not family.startswith("maskrcnn"):
-            raise ValueError("a Detectron / Caffe2 checkpoint needs --family maskrcnn_*")
+        if family is None or not family.startswith(("maskrcnn", "fasterrcnn")):
+            raise ValueError("a Detectron / Caffe2 checkpoint needs --family maskrcnn_* or fasterrcnn_*")
         exp = expected_keys(family)
         short = {}
         for k, v in flat.items():
