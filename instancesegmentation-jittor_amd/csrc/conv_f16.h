@@ -1,5 +1,7 @@
 // conv_f16.h -- what the fp16 convolution translation units share (csrc/conv_mfma_f16.hip: the v_mfma_f32_32x32x16_f16 kernels and the launcher;
-// csrc/conv_mfma_f16_m16.hip: the backbone tiles on v_mfma_f32_16x16x32_f16): build-time cache-policy knobs, vector types, the kernel argument block.
+// csrc/conv_mfma_f16_m16.hip: the backbone tiles on v_mfma_f32_16x16x32_f16) up to and including the K loop: build-time cache-policy knobs, vector types, the
+// kernel argument block, the XCD-aware tile order, the persistent kernels' loader role.  What follows the K loop -- epilogues, fused head, launchers -- is
+// conv_f16_epilogue.h, which includes this file.
 #pragma once
 #include "../../include/isegmi.h"
 #include "common.h"
@@ -83,6 +85,20 @@ struct ConvKH {
 // Epilogue: each wave transposes its fp32 strip through LDS and stores / loads the residual 16 B per lane.
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
+// XCD-aware tile order: of `total` tiles, tile v (a block id, or bid + i * grid in the persistent kernels: the grid is a multiple of 8 or the whole
+// grid, so v keeps bid's XCD) is the (v >> 3)-th of the contiguous run of logical tiles that belongs to XCD v & 7
+struct ConvF16TileOrder {
+    int q8, r8g, ntiles;
+    __device__ __forceinline__ ConvF16TileOrder(const int total, const int ntiles_) : q8(total >> 3), r8g(total & 7), ntiles(ntiles_) {}
+    template <int BM, int BN>
+    __device__ __forceinline__ void origin(const int v, int& m0, int& n0) const {
+        const int xcd = v & 7;
+        const int logical = (xcd < r8g ? xcd * (q8 + 1) : r8g * (q8 + 1) + (xcd - r8g) * q8) + (v >> 3);
+        const int nt = logical % ntiles, mt = logical / ntiles;
+        m0 = mt * BM; n0 = nt * BN;
+    }
+};
+
 // ---------------------------------------------------------------------------------------------------------------------
 // The LOADER role of the persistent loader-wave kernels (conv_f16_persist_kernel in BOTH translation units: the v_mfma_f32_32x32x16_f16 tiles of
 // conv_mfma_f16.hip and the v_mfma_f32_16x16x32_f16 tiles of conv_mfma_f16_m16.hip).  Nothing in it depends on the MFMA shape -- chunk images, the LDS-DMA
@@ -102,13 +118,7 @@ __device__ __forceinline__ void conv_f16_persist_loader(conv_f16_karg_t kp0, cha
     constexpr int STAGEB = (BM + BN) * 128;
     constexpr int PP = PPA + PPB;
     constexpr unsigned OOB = 0x80000000u;
-    const int q8 = total >> 3, r8g = total & 7;
-    auto tile_origin = [&](int v, int& m0, int& n0) {  // v = bid + i * G: same XCD as bid (G is a multiple of 8 or the whole grid)
-        const int xcd = v & 7;
-        const int logical = (xcd < r8g ? xcd * (q8 + 1) : r8g * (q8 + 1) + (xcd - r8g) * q8) + (v >> 3);
-        const int nt = logical % p_ntiles, mt = logical / p_ntiles;
-        m0 = mt * BM; n0 = nt * BN;
-    };
+    const ConvF16TileOrder order(total, p_ntiles);
     karg_t kl = kp0;
     asm volatile("" : "+s"(kl));
     const ConvKH& p = *(const ConvKH*)kl;
@@ -125,7 +135,7 @@ __device__ __forceinline__ void conv_f16_persist_loader(conv_f16_karg_t kp0, cha
     bool live = true;
     auto setup_tile = [&](int vv) {  // per-lane row bases of tile vv; the only place with integer divisions
         int m0, n0;
-        tile_origin(vv, m0, n0);
+        order.template origin<BM, BN>(vv, m0, n0);
 #pragma unroll
         for (int j = 0; j < PPA; ++j) {
             const int row = (lw + j * NL) * 8 + r8;

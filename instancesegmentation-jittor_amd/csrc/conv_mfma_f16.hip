@@ -7,144 +7,9 @@
 // k = 8h..8h+7 of a 16-deep step), so the NHWC channel run is used as stored.  Numerics: products are exact in fp32, the
 // 16-term sum inside one MFMA is not an ordered fmaf chain, so parity with the oracle is TOLERANCE-based here (tests
 // state it).
-#include "conv_f16.h"
+#include "conv_f16_epilogue.h"
 
 namespace isegmi {
-
-
-// Shared epilogue (fp32 math): y = fmaf(acc, scale, shift) + residual -> act -> fp16 (or fp32) NHWC store.  Vector path: each
-// wave transposes its 32-row fp32 strips through a private LDS region (all staging LDS is free by now) so that residual
-// loads and output stores are 16 B per lane; strided destinations / Cout % 8 != 0 take the per-element path.
-// vector path of conv_f16_epilogue (32-row strips through the wave's private LDS region).  RES: a residual is added -- its 16-B loads run
-// a rolling window of two passes ahead of their use (see epi8_prefetch: a load awaited on the spot also drains the previous pass's stores);
-// without a residual no load is issued at all (round 2 sent a dropped out-of-range load per pass and waited for it).
-template <int TM, int TN, bool RES>
-__device__ __forceinline__ void conv_f16_epilogue_vec(const ConvKH& p, f32x16h (&acc)[TM][TN], char* smemg, int wave, int lane, int wm, int wn, int m0, int n0) {
-    constexpr unsigned OOB = 0x80000000u;
-    constexpr int PITCH = TN * 32 + 4;
-    constexpr int LPR = TN * 4, RPP = 64 / LPR, NPASS = 32 / RPP, NQ = TM * NPASS, D = 2 < NQ ? 2 : NQ;
-    const int lr = lane & 31, lh = lane >> 5;
-    const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, p.out_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_res = __builtin_amdgcn_make_buffer_rsrc((void*)(RES ? (const void*)p.res : (const void*)p.out), 0, RES ? p.res_bytes : 0u, 0x00020000);
-    const unsigned esz = p.out_f32 ? 4u : 2u;
-    float* ew = (float*)smemg + wave * 32 * PITCH;
-    const int er = lane / LPR, ec = (lane % LPR) * 8;
-    const int co8 = n0 + wn * TN * 32 + ec;
-    const bool cok8 = co8 < p.Cout;
-    // pass q covers tile rows RPP q ..: a lane's offsets advance by one stride per pass; rows past M are behind the descriptors' ranges
-    // (contiguous destinations; strided ones take the general arithmetic)
-    const unsigned rstep = (unsigned)p.Cout * (2u * RPP), ostep = (unsigned)p.out_pix_stride * esz * RPP;
-    unsigned rnext = cok8 ? ((unsigned)(m0 + wm * TM * 32 + er) * (unsigned)p.Cout + (unsigned)co8) * 2u : OOB;
-    unsigned onext = cok8 ? ((unsigned)(m0 + wm * TM * 32 + er) * (unsigned)p.out_pix_stride + (unsigned)co8) * esz : OOB;
-    u32x4h rw[D];
-    if (RES) {
-#pragma unroll
-        for (int q = 0; q < D; ++q) { rw[q] = __builtin_amdgcn_raw_buffer_load_b128(rs_res, rnext, 0, CONV_F16_RES_AUX); rnext += rstep; }
-    }
-#pragma unroll
-    for (int a = 0; a < TM; ++a) {
-#pragma unroll
-        for (int b = 0; b < TN; ++b) {
-            const int co = n0 + (wn * TN + b) * 32 + lr;
-            const bool cok = co < p.Cout;
-            const float sc = (cok && p.scale) ? p.scale[co] : 1.0f;
-            const float sh = (cok && p.shift) ? p.shift[co] : 0.0f;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) ew[((e & 3) + 8 * (e >> 2) + 4 * lh) * PITCH + b * 32 + lr] = fmaf(acc[a][b][e], sc, sh);
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int ps = 0; ps < NPASS; ++ps) {
-            const int q = a * NPASS + ps;
-            const int rr = ps * RPP + er;
-            const f32x4h v0 = *(const f32x4h*)(ew + rr * PITCH + ec);
-            const f32x4h v1 = *(const f32x4h*)(ew + rr * PITCH + ec + 4);
-            unsigned ooff;
-            if (p.contiguous) { ooff = onext; onext += ostep; }
-            else {
-                const int m = m0 + wm * TM * 32 + q * RPP + er;
-                const int ni = m / p.out_div, pi = m - ni * p.out_div;
-                ooff = (m < p.M && cok8) ? (unsigned)(((int64_t)ni * p.out_img_stride + (int64_t)pi * p.out_pix_stride + co8) * esz) : OOB;
-            }
-            float y[8];
-            if (RES) {
-                const f16x8 rh = __builtin_bit_cast(f16x8, rw[q % D]);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) y[i] = (i < 4 ? v0[i] : v1[i - 4]) + (float)rh[i];
-                if (q + D < NQ) { rw[q % D] = __builtin_amdgcn_raw_buffer_load_b128(rs_res, rnext, 0, CONV_F16_RES_AUX); rnext += rstep; }
-            } else {
-#pragma unroll
-                for (int i = 0; i < 8; ++i) y[i] = i < 4 ? v0[i] : v1[i - 4];
-            }
-            if (p.act == 1) {
-#pragma unroll
-                for (int i = 0; i < 8; ++i) y[i] = y[i] > 0.0f ? y[i] : 0.0f;
-            }
-            if (p.out_f32) {
-                u32x4h o0, o1;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) { o0[i] = __builtin_bit_cast(unsigned, y[i]); o1[i] = __builtin_bit_cast(unsigned, y[i + 4]); }
-                __builtin_amdgcn_raw_buffer_store_b128(o0, rs_out, ooff, 0, CONV_F16_OUT_AUX);
-                __builtin_amdgcn_raw_buffer_store_b128(o1, rs_out, ooff >= OOB ? OOB : ooff + 16u, 0, CONV_F16_OUT_AUX);
-            } else {
-                f16x8 o;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) o[i] = (half_t)y[i];
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4h, o), rs_out, ooff, 0, CONV_F16_OUT_AUX);
-            }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    }
-}
-
-template <int TM, int TN>
-__device__ __forceinline__ void conv_f16_epilogue(const ConvKH& p, f32x16h (&acc)[TM][TN], char* smemg, int wave, int lane, int wm, int wn,
-                                                  int m0, int n0) {
-    constexpr unsigned OOB = 0x80000000u;
-    const int lr = lane & 31, lh = lane >> 5;
-    if (p.vec_epi) {  // uniform
-        if (p.res) conv_f16_epilogue_vec<TM, TN, true>(p, acc, smemg, wave, lane, wm, wn, m0, n0);
-        else conv_f16_epilogue_vec<TM, TN, false>(p, acc, smemg, wave, lane, wm, wn, m0, n0);
-        return;
-    }
-    // ---- per-element path (strided destinations with Cout % 8 != 0: the RPN / prediction heads): y = fmaf(acc, scale, shift) + residual -> act
-    const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, p.out_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_res = __builtin_amdgcn_make_buffer_rsrc((void*)(p.res ? (const void*)p.res : (const void*)p.out), 0, p.res ? p.res_bytes : 0u, 0x00020000);
-    const unsigned esz = p.out_f32 ? 4u : 2u;
-#pragma unroll
-    for (int a = 0; a < TM; ++a) {
-        unsigned rowoff[16], resoff[16];
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int m = m0 + (wm * TM + a) * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
-            resoff[e] = m < p.M ? (unsigned)m * (unsigned)p.Cout * 2u : OOB;
-            if (p.contiguous) rowoff[e] = m < p.M ? (unsigned)m * (unsigned)p.out_pix_stride * esz : OOB;
-            else {
-                const int ni = m / p.out_div, pi = m - ni * p.out_div;
-                rowoff[e] = m < p.M ? (unsigned)(((int64_t)ni * p.out_img_stride + (int64_t)pi * p.out_pix_stride) * esz) : OOB;
-            }
-        }
-#pragma unroll
-        for (int b = 0; b < TN; ++b) {
-            const int co = n0 + (wn * TN + b) * 32 + lr;
-            const bool cok = co < p.Cout;
-            const float sc = (cok && p.scale) ? p.scale[co] : 1.0f;
-            const float sh = (cok && p.shift) ? p.shift[co] : 0.0f;
-            const unsigned cooff = cok ? (unsigned)co : OOB;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const unsigned short hb = __builtin_amdgcn_raw_buffer_load_b16(rs_res, (resoff[e] | cooff) >= OOB ? OOB : resoff[e] + cooff * 2u, 0, 0);
-                float y = fmaf(acc[a][b][e], sc, sh);
-                y = y + (float)__builtin_bit_cast(half_t, hb);
-                y = p.act == 1 ? (y > 0.0f ? y : 0.0f) : y;
-                const unsigned off = (rowoff[e] | cooff) >= OOB ? OOB : rowoff[e] + cooff * esz;
-                if (p.out_f32) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, y), rs_out, off, 0, 0);
-                else __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, (half_t)y), rs_out, off, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-}
 
 // LW > 0: LW extra LOADER waves issue every LDS-DMA piece and the NW MFMA waves issue none (an LDS-DMA instruction stalls its
 // wave for 100-180 cycles while the fill path is busy -- time the MFMA waves then spend on matrix work); LW == 0: every wave
@@ -168,11 +33,8 @@ __global__ __launch_bounds__((WM * WN + LW) * 64, OCC) void conv_f16_glds_kernel
     const int lw = LW > 0 ? wave - NW : wave;           // index among the loading waves
     const bool loads = LW == 0 || wave >= NW;
 
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q8 = nwg >> 3, r8g = nwg & 7, xcd = bid & 7;
-    const int logical = (xcd < r8g ? xcd * (q8 + 1) : r8g * (q8 + 1) + (xcd - r8g) * q8) + (bid >> 3);
-    const int nt = logical % p.ntiles, mt = logical / p.ntiles;
-    const int m0 = mt * BM, n0 = nt * BN;
+    int m0, n0;
+    ConvF16TileOrder((int)gridDim.x, p.ntiles).template origin<BM, BN>((int)blockIdx.x, m0, n0);
 
     const int r8 = lane >> 3, cs = lane & 7;
     int hi0[PPA], wi0[PPA], abase[PPA];
@@ -344,7 +206,7 @@ __global__ __launch_bounds__((WM * WN + LW) * 64, OCC) void conv_f16_glds_kernel
     }
     asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");  // trailing all-OOB pieces have landed; LDS is free
 
-    conv_f16_epilogue<TM, TN>(p, acc, smemg, wave, lane, wm, wn, m0, n0);
+    conv_f16_epilogue(p, acc, smemg, wave, lane, wm, wn, m0, n0);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -360,164 +222,8 @@ __global__ __launch_bounds__((WM * WN + LW) * 64, OCC) void conv_f16_glds_kernel
 // Barrier E tells every MFMA wave that all of them are done reading the last chunk's stage: that stage is the epilogue's
 // scratch (the loader refills it only after barrier #t+1, which needs the MFMA waves), so no LDS is set aside for it.  The
 // epilogue transposes 8 rows at a time (2.2 KB per wave).  Tile order: virtual block v = bid + i * grid keeps v & 7 = bid & 7,
-// so the XCD-aware remap of the one-tile kernel applies to v unchanged.
-// Round 3: the residual of a tile is REQUESTED BEFORE its K loop and consumed strip by strip behind a rolling window.  Before, every
-// 8-row strip issued its residual load and waited for it on the spot -- and on gfx9 a wave's stores count in the same vmcnt as its loads, so
-// the wait also drained the previous strip's stores: eight exposed memory round trips per 64x64 wave tile, on layers whose K loop is four
-// 16-MFMA chunks (R101 res4 conv3: 14.7 % MfmaUtil at 3.9 TB/s, on neither roof).  Now the first EPI_D strips' residuals are in flight
-// during the K loop (the MFMA waves issue no other vector-memory instruction there), strip q's slot is refilled with strip q + EPI_D's
-// right after use, and the counted waits the compiler derives from program order never drain the stores of the strip just written.
-// Offsets: a lane's residual / output offset is ONE add per strip -- lane base (its row inside the strip, its 8 channels; the out-of-range
-// constant for a column past Cout) plus a wave-uniform row term; rows past M fall behind descriptors cut at M rows (contiguous
-// destinations; strided ones keep the general arithmetic).
-#ifndef ISEGMI_EPI_D
-#define ISEGMI_EPI_D 2
-#endif
-constexpr int EPI_D = ISEGMI_EPI_D;   // residual passes in flight per lane (tools/build_variant.sh ... -DISEGMI_EPI_D=4 for an A/B)
-
-template <int TM, int TN>
-struct Epi8 {
-    static_assert(TN == 2 || TN == 4, "8-row strips are 64 or 128 channels wide");
-    static constexpr int LPR = TN * 4, RPP = 64 / LPR, NPASS = 8 / RPP, NQ = TM * 4 * NPASS;  // passes (b128 per lane) per wave tile
-    static constexpr int D = EPI_D < NQ ? EPI_D : NQ;
-    u32x4h r[D];
-    unsigned rnext;   // residual offset (bytes) of the next pass to request, or >= OOB for a column past Cout; pass q covers tile rows RPP q ..
-    int ux, uy, un;   // UP2X: output pixel (x, y, image) of the next pass to request
-};
-
-// UP2X (FPN top-down merge, SURVEY 8a M3: `last_inner = inner_lateral + interpolate(last_inner, scale_factor=2, mode="nearest")`): the residual of output pixel
-// (n, y, x) is pixel (n, min(y >> 1, Hc - 1), min(x >> 1, Wc - 1)) of the coarser level.  A lane's pass-to-pass step is RPP pixels along the row: the walk is
-// incremental (one wrap test per pass), the two divisions that start it are per tile.
-template <int TM, int TN>
-__device__ __forceinline__ unsigned epi8_up2x_next(const ConvKH& p, Epi8<TM, TN>& E, int co8) {
-    constexpr unsigned OOB = 0x80000000u;
-    int yc = E.uy >> 1, xc = E.ux >> 1;
-    yc = yc > p.rHc - 1 ? p.rHc - 1 : yc;
-    xc = xc > p.rWc - 1 ? p.rWc - 1 : xc;
-    const unsigned off = co8 < p.Cout ? ((unsigned)((E.un * p.rHc + yc) * p.rWc + xc) * (unsigned)p.Cout + (unsigned)co8) * 2u : OOB;   // images past N are past the range
-    E.ux += Epi8<TM, TN>::RPP;
-    if (E.ux >= p.Wo) { E.ux -= p.Wo; E.uy += 1; if (E.uy >= p.Ho) { E.uy = 0; E.un += 1; } }
-    return off;
-}
-
-// before the K loop: the first D residual passes of the wave's tile
-template <int TM, int TN, bool UP2X = false>
-__device__ __forceinline__ void epi8_prefetch(const ConvKH& p, Epi8<TM, TN>& E, int lane, int wm, int wn, int m0, int n0) {
-    constexpr unsigned OOB = 0x80000000u;
-    constexpr int LPR = Epi8<TM, TN>::LPR, RPP = Epi8<TM, TN>::RPP;
-    // no branch on p.res here: a conditional prefetch makes the window a phi, and the compiler then parks the loaded registers in copies
-    // behind an s_waitcnt vmcnt(0) in FRONT of the K loop; without a residual the descriptor is empty and the loads return zeros unused
-    const int er = lane / LPR, ec = (lane % LPR) * 8;
-    const int co8 = n0 + wn * TN * 32 + ec;
-    E.rnext = co8 < p.Cout ? ((unsigned)(m0 + wm * TM * 32 + er) * (unsigned)p.Cout + (unsigned)co8) * 2u : OOB;
-    const __amdgpu_buffer_rsrc_t rs_res = __builtin_amdgcn_make_buffer_rsrc((void*)(p.res ? (const void*)p.res : (const void*)p.out), 0, p.res ? p.res_bytes : 0u, 0x00020000);
-    const unsigned rstep = (unsigned)p.Cout * (2u * RPP);
-    if constexpr (UP2X) {
-        const int m = m0 + wm * TM * 32 + er, hw = p.Ho * p.Wo;
-        E.un = m / hw;
-        const int rem = m - E.un * hw;
-        E.uy = rem / p.Wo;
-        E.ux = rem - E.uy * p.Wo;
-#pragma unroll
-        for (int q = 0; q < Epi8<TM, TN>::D; ++q) E.r[q] = __builtin_amdgcn_raw_buffer_load_b128(rs_res, epi8_up2x_next<TM, TN>(p, E, co8), 0, CONV_F16_RES_AUX);
-        return;
-    }
-#pragma unroll
-    for (int q = 0; q < Epi8<TM, TN>::D; ++q) { E.r[q] = __builtin_amdgcn_raw_buffer_load_b128(rs_res, E.rnext, 0, CONV_F16_RES_AUX); E.rnext += rstep; }
-}
-
-template <int TM, int TN, bool RES, bool UP2X = false>
-__device__ __forceinline__ void epi8_finish_impl(const ConvKH& p, f32x16h (&acc)[TM][TN], Epi8<TM, TN>& E, float* ew, int lane, int wm, int wn, int m0, int n0) {
-    constexpr unsigned OOB = 0x80000000u;
-    constexpr int PITCH = TN * 32 + 4;
-    constexpr int LPR = Epi8<TM, TN>::LPR, RPP = Epi8<TM, TN>::RPP, NPASS = Epi8<TM, TN>::NPASS, NQ = Epi8<TM, TN>::NQ, D = Epi8<TM, TN>::D;
-    const int lr = lane & 31, lh = lane >> 5;
-    const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, p.out_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_res = __builtin_amdgcn_make_buffer_rsrc((void*)(RES ? (const void*)p.res : (const void*)p.out), 0, RES ? p.res_bytes : 0u, 0x00020000);
-    const unsigned esz = p.out_f32 ? 4u : 2u;
-    const int er = lane / LPR, ec = (lane % LPR) * 8;
-    const int co8 = n0 + wn * TN * 32 + ec;
-    const bool cok8 = co8 < p.Cout;
-    const unsigned rstep = (unsigned)p.Cout * (2u * RPP);
-    // contiguous destination: offset = lane base + pass * step, rows past M are out of the descriptor's range
-    const unsigned ostep = (unsigned)p.out_pix_stride * esz * RPP;
-    unsigned onext = cok8 ? ((unsigned)(m0 + wm * TM * 32 + er) * (unsigned)p.out_pix_stride + (unsigned)co8) * esz : OOB;
-    float sc[TN], sh[TN];
-#pragma unroll
-    for (int b = 0; b < TN; ++b) {
-        const int co = n0 + (wn * TN + b) * 32 + lr;
-        const bool cok = co < p.Cout;
-        sc[b] = (cok && p.scale) ? p.scale[co] : 1.0f;
-        sh[b] = (cok && p.shift) ? p.shift[co] : 0.0f;
-    }
-#pragma unroll
-    for (int a = 0; a < TM; ++a) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {  // accumulator registers 4g..4g+3 = tile rows 8g + (0..3) + 4 * (lane >> 5)
-#pragma unroll
-            for (int b = 0; b < TN; ++b)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) ew[(j + 4 * lh) * PITCH + b * 32 + lr] = fmaf(acc[a][b][4 * g + j], sc[b], sh[b]);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-            for (int ps = 0; ps < NPASS; ++ps) {
-                const int q = (a * 4 + g) * NPASS + ps;
-                const int rr = ps * RPP + er;
-                const f32x4h v0 = *(const f32x4h*)(ew + rr * PITCH + ec);
-                const f32x4h v1 = *(const f32x4h*)(ew + rr * PITCH + ec + 4);
-                unsigned ooff;
-                if (p.contiguous) { ooff = onext; onext += ostep; }
-                else {
-                    const int m = m0 + wm * TM * 32 + q * RPP + er;
-                    const int ni = m / p.out_div, pi = m - ni * p.out_div;
-                    ooff = (m < p.M && cok8) ? (unsigned)(((int64_t)ni * p.out_img_stride + (int64_t)pi * p.out_pix_stride + co8) * esz) : OOB;
-                }
-                float y[8];
-                if (RES) {
-                    const f16x8 rh = __builtin_bit_cast(f16x8, E.r[q % D]);
-                    if constexpr (UP2X) {
-                        // the lateral conv's result is rounded to fp16 FIRST, as the two-launch path stores it before nearest2x_add_f16 adds the coarser level
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) y[i] = (float)(half_t)(i < 4 ? v0[i] : v1[i - 4]) + (float)rh[i];
-                        if (q + D < NQ) E.r[q % D] = __builtin_amdgcn_raw_buffer_load_b128(rs_res, epi8_up2x_next<TM, TN>(p, E, co8), 0, CONV_F16_RES_AUX);
-                    } else {
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) y[i] = (i < 4 ? v0[i] : v1[i - 4]) + (float)rh[i];
-                        if (q + D < NQ) { E.r[q % D] = __builtin_amdgcn_raw_buffer_load_b128(rs_res, E.rnext, 0, CONV_F16_RES_AUX); E.rnext += rstep; }
-                    }
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) y[i] = i < 4 ? v0[i] : v1[i - 4];
-                }
-                if (p.act == 1) {
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) y[i] = y[i] > 0.0f ? y[i] : 0.0f;
-                }
-                if (p.out_f32) {
-                    u32x4h o0, o1;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) { o0[i] = __builtin_bit_cast(unsigned, y[i]); o1[i] = __builtin_bit_cast(unsigned, y[i + 4]); }
-                    __builtin_amdgcn_raw_buffer_store_b128(o0, rs_out, ooff, 0, CONV_F16_OUT_AUX);
-                    __builtin_amdgcn_raw_buffer_store_b128(o1, rs_out, ooff >= OOB ? OOB : ooff + 16u, 0, CONV_F16_OUT_AUX);
-                } else {
-                    f16x8 o;
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) o[i] = (half_t)y[i];
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4h, o), rs_out, ooff, 0, CONV_F16_OUT_AUX);
-                }
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        }
-    }
-}
-
-template <int TM, int TN, bool UP2X = false>
-__device__ __forceinline__ void epi8_finish(const ConvKH& p, f32x16h (&acc)[TM][TN], Epi8<TM, TN>& E, float* ew, int lane, int wm, int wn, int m0, int n0) {
-    if constexpr (UP2X) { epi8_finish_impl<TM, TN, true, true>(p, acc, E, ew, lane, wm, wn, m0, n0); return; }
-    if (p.res) epi8_finish_impl<TM, TN, true>(p, acc, E, ew, lane, wm, wn, m0, n0);   // uniform
-    else epi8_finish_impl<TM, TN, false>(p, acc, E, ew, lane, wm, wn, m0, n0);
-}
-
+// so the XCD-aware remap of the one-tile kernel applies to v unchanged (ConvF16TileOrder).  The epilogue and its residual window: epi8_prefetch /
+// epi8_finish in conv_f16_epilogue.h.  The same kernel on v_mfma_f32_16x16x32_f16 lives in conv_mfma_f16_m16.hip.
 template <int BM, int BN, int WM, int WN, int NSTAGE, int OCC, int LW, bool UP2X = false>
 __global__ __launch_bounds__((WM * WN + LW) * 64, OCC) void conv_f16_persist_kernel(const ConvKH p_arg) {
     static_assert(LW > 0 && NSTAGE >= 2 && NSTAGE <= 3, "loader waves, a 2- or 3-deep ring");
@@ -541,13 +247,7 @@ __global__ __launch_bounds__((WM * WN + LW) * 64, OCC) void conv_f16_persist_ker
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int total = p_mtiles * p_ntiles, G = (int)gridDim.x, bid = (int)blockIdx.x;
-    const int q8 = total >> 3, r8g = total & 7;
-    auto tile_origin = [&](int v, int& m0, int& n0) {  // v = bid + i * G: same XCD as bid (G is a multiple of 8 or the whole grid)
-        const int xcd = v & 7;
-        const int logical = (xcd < r8g ? xcd * (q8 + 1) : r8g * (q8 + 1) + (xcd - r8g) * q8) + (v >> 3);
-        const int nt = logical % p_ntiles, mt = logical / p_ntiles;
-        m0 = mt * BM; n0 = nt * BN;
-    };
+    const ConvF16TileOrder order(total, p_ntiles);
     const int my_tiles = (total - bid + G - 1) / G;  // >= 1: the launcher never starts more blocks than tiles
 
     conv_f16_role_prio(wave >= NW);
@@ -588,19 +288,19 @@ __global__ __launch_bounds__((WM * WN + LW) * 64, OCC) void conv_f16_persist_ker
     int st = 0;
     for (int v = bid; v < total; v += G) {
         int m0, n0;
-        tile_origin(v, m0, n0);
+        order.template origin<BM, BN>(v, m0, n0);
 #pragma unroll
         for (int a = 0; a < TM; ++a)
 #pragma unroll
             for (int b = 0; b < TN; ++b)
 #pragma unroll
                 for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.0f;
-        Epi8<TM, TN> E;
+        Epi8<TM * 32, TN> E;
         {
             karg_t k1 = kp0;
             asm volatile("" : "+s"(k1));
             const ConvKH& p = *(const ConvKH*)k1;
-            if (p.vec_epi) epi8_prefetch<TM, TN, UP2X>(p, E, lane, wm, wn, m0, n0);  // the tile's first residual strips travel under its K loop
+            if (p.vec_epi) epi8_prefetch<TM * 32, TN, UP2X>(p, E, lane, wm, wn, m0, n0);  // the tile's first residual strips travel under its K loop
         }
         int last = 0;
         for (int t = 0; t < p_nchunks; ++t) {
@@ -613,79 +313,8 @@ __global__ __launch_bounds__((WM * WN + LW) * 64, OCC) void conv_f16_persist_ker
         karg_t k2 = kp0;
         asm volatile("" : "+s"(k2));
         const ConvKH& p = *(const ConvKH*)k2;
-        if (p.vec_epi) epi8_finish<TM, TN, UP2X>(p, acc, E, (float*)(smemg + last * STAGEB) + wave * 8 * (TN * 32 + 4), lane, wm, wn, m0, n0);
-        else conv_f16_epilogue<TM, TN>(p, acc, smemg, wave, lane, wm, wn, m0, n0);  // per-element path: no LDS
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// FUSED 1x1 HEAD (round 4; RPNHead under configs[4]: `t = relu(conv3x3(x)); logits, deltas = cls_logits(t), bbox_pred(t)`).  On a 192 x 256
-// row-strip tile the block holds ALL 256 channels of its 192 pixels, so the 1x1 convolution that follows (256 -> f_cout <= 32 outputs: 3 objectness + 12
-// box deltas) can run on the tile before it ever leaves the CU: the BN + ReLU result goes to LDS as fp16 -- rounded exactly where the two-launch path
-// rounds it when it stores t -- in a row-major [pixel][256] image (16-B columns XOR-swizzled by the row), the head's packed weights (32 rows) next to
-// it, and six waves multiply one 32-pixel tile each on the same 16 k-steps the stand-alone 1x1 launch would walk.  t is never written (275 MB per
-// P2 level at R101 bs=8) nor read back.  Bit-identical to the two launches (tests/test_rpn_head_f16_gpu.py).
-template <int TM, int TN>
-__device__ __forceinline__ void conv_f16_epilogue_head(const ConvKH& p, f32x16h (&acc)[TM][TN], char* smemg, int wave, int lane, int wm, int wn, int m0) {
-    constexpr unsigned OOB = 0x80000000u;
-    constexpr int BMH = 192, T_BYTES = BMH * 512;   // the tile image; the head's weights follow it (32 rows x 512 B)
-    const int lr = lane & 31, lh = lane >> 5;
-    const int tid = wave * 64 + lane;                // 12 MFMA waves: 768 threads
-    // head weights: rows 0..31 of the packed [128][256] image (zero rows past f_cout), 16 KB = 1024 16-B pieces
-    u32x4h wv[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int piece = tid + j * 768;
-        wv[j] = piece < 1024 ? *(const u32x4h*)((const char*)p.f_w + piece * 16) : u32x4h{0u, 0u, 0u, 0u};
-    }
-    // 1. y = relu(fmaf(acc, scale, shift)) -> fp16 -> T[row][channel]
-#pragma unroll
-    for (int a = 0; a < TM; ++a)
-#pragma unroll
-        for (int b = 0; b < TN; ++b) {
-            const int co = (wn * TN + b) * 32 + lr;
-            const float sc = p.scale ? p.scale[co] : 1.0f, sh = p.shift ? p.shift[co] : 0.0f;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int row = (wm * TM + a) * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
-                float y = fmaf(acc[a][b][e], sc, sh);
-                y = y > 0.0f ? y : 0.0f;
-                *(half_t*)(smemg + row * 512 + (((co >> 3) ^ (row & 15)) << 4) + (co & 7) * 2) = (half_t)y;
-            }
-        }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int piece = tid + j * 768;
-        if (piece < 1024) {
-            const int row = piece >> 5, c16 = piece & 31;
-            *(u32x4h*)(smemg + T_BYTES + row * 512 + ((c16 ^ (row & 15)) << 4)) = wv[j];
-        }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // the MFMA waves (the loader waves have left)
-    if (wave >= BMH / 32) return;
-    // 2. wave w: pixels 32 w .. + 31 of the tile x 32 head outputs, K = 256 in the order the stand-alone 1x1 launch walks it
-    f32x16h h;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) h[e] = 0.0f;
-    const int prow = wave * 32 + lr;
-    const char* pa = smemg + prow * 512;
-    const char* pb = smemg + T_BYTES + lr * 512;
-#pragma unroll
-    for (int ks = 0; ks < 16; ++ks) {
-        const f16x8 fa = *(const f16x8*)(pa + (((ks * 2 + lh) ^ (prow & 15)) << 4));
-        const f16x8 fb = *(const f16x8*)(pb + (((ks * 2 + lh) ^ (lr & 15)) << 4));
-        h = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa, fb, h, 0, 0, 0);
-    }
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)p.f_out, 0, p.f_out_bytes, 0x00020000);
-    const bool cok = lr < p.f_cout;
-    const float sc2 = (cok && p.f_scale) ? p.f_scale[lr] : 1.0f, sh2 = (cok && p.f_shift) ? p.f_shift[lr] : 0.0f;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-        const int m = m0 + wave * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
-        float y = fmaf(h[e], sc2, sh2);
-        y = y + 0.0f;   // the stand-alone launch's per-element epilogue adds its (absent) residual: -0 becomes +0 there, so here too
-        const unsigned off = (cok && m < p.M) ? ((unsigned)m * (unsigned)p.f_cout + (unsigned)lr) * 4u : OOB;
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, y), rs, off, 0, 0);
+        if (p.vec_epi) epi8_finish<UP2X>(p, acc, E, (float*)(smemg + last * STAGEB) + wave * 8 * (TN * 32 + 4), lane, wm, wn, m0, n0);
+        else conv_f16_epilogue(p, acc, smemg, wave, lane, wm, wn, m0, n0);  // per-element path: no LDS
     }
 }
 
@@ -703,18 +332,6 @@ __device__ __forceinline__ void conv_f16_epilogue_head(const ConvKH& p, f32x16h 
 // front of the next barrier leaves exactly those B pieces in flight (`vmcnt(RB)`, in-order completion).  Worth +3 % on the 634-GF layer and no more: with
 // the loaders stopped after two groups (tile bit 4096) the kernel is only 8 % faster, and in a loop it holds the package at 1381 of its 1400 W
 // (profiles/r04_f16_power.txt): these layers are bound by the power cap, not by a pipe.  LDS: 2 strips + 3 B chunks = 163 840 B, all there is.
-#ifdef ISEGMI_STRIP_TRACE
-// development build only (-DISEGMI_STRIP_TRACE, tools/strip_trace.py): block 0 keeps four cycle stamps per step and wave in LDS behind the staging buffers and dumps them to p.trace
-#define STRIP_TRACE(u, slot)                                                                                      \
-    do {                                                                                                          \
-        if (bid == 0 && (u) < 64 && !(p.dbg & 16)) {                                                              \
-            const unsigned long long t_ = __builtin_amdgcn_s_memtime();                                           \
-            *(volatile unsigned*)(smemg + TRACE_OFF + ((wave * 64 + (u)) * 4 + (slot)) * 4) = (unsigned)t_;        \
-        }                                                                                                         \
-    } while (0)
-#else
-#define STRIP_TRACE(u, slot) do {} while (0)
-#endif
 template <int BM, int BN, int WM, int WN, int LW, int NB = 2>
 __global__ __launch_bounds__((WM * WN + LW) * 64, 1) void conv3x3_f16_strip_kernel(const ConvKH p) {
     static_assert(NB == 2 || (NB == 3 && LW > 0 && (BN / 8) % LW == 0), "the three-buffer form needs loader waves and whole B piece rounds");
@@ -803,9 +420,9 @@ __global__ __launch_bounds__((WM * WN + LW) * 64, 1) void conv3x3_f16_strip_kern
     asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
     STRIP_TRACE(63, 0);
     if constexpr (BM == 192 && BN == 256 && WM == 3 && WN == 4 && NB == 3) {
-        if (p.f_w) { conv_f16_epilogue_head<TM, TN>(p, acc, smemg, wave, lane, wm, wn, m0); return; }   // uniform
+        if (p.f_w) { conv_f16_epilogue_head(p, acc, smemg, wave, lane, wm, wn, m0); return; }   // uniform
     }
-    conv_f16_epilogue<TM, TN>(p, acc, smemg, wave, lane, wm, wn, m0, n0);
+    conv_f16_epilogue(p, acc, smemg, wave, lane, wm, wn, m0, n0);
     STRIP_TRACE(63, 1);
 #ifdef ISEGMI_STRIP_TRACE
     if (bid == 0 && p.trace && wave == 0 && lane == 0) {
@@ -816,46 +433,14 @@ __global__ __launch_bounds__((WM * WN + LW) * 64, 1) void conv3x3_f16_strip_kern
 #endif
 }
 
+// the shared launchers (conv_f16_epilogue.h) with this unit's kernels and their accumulator arrays
 template <int BM, int BN, int WM, int WN, int LW = 0, int NB = 2>
 static int launch_strip(ConvKH& k, hipStream_t st) {
-    k.mtiles = cdiv(k.M, BM);
-    k.ntiles = cdiv(k.Cout, BN);
-    constexpr int NW = WM * WN, TN = BN / WN / 32;
-    size_t lds = 2 * (size_t)(BM + 64) * 128 + NB * (size_t)BN * 128;
-    static_assert(2 * (BM + 64) * 128 + NB * BN * 128 <= 163840, "LDS");
-    const size_t epi = (size_t)NW * 32 * (TN * 32 + 4) * 4;
-    if (epi > lds) lds = epi;
-    size_t lds_attr = lds;
-#ifdef ISEGMI_STRIP_TRACE
-    if (NB == 2) lds_attr = lds + 16384;
-    static unsigned* trace_buf = nullptr;
-    const bool tracing = NB == 2 && getenv("ISEGMI_STRIP_TRACE_DUMP") != nullptr;   // (NB = 3 fills the LDS: no room for the stamps)
-    if (tracing) {
-        lds = 2 * (size_t)(BM + 64) * 128 + NB * (size_t)BN * 128 + 16384;
-        if (!trace_buf) HIP_TRY(hipMalloc((void**)&trace_buf, 16448));
-        HIP_TRY(hipMemsetAsync(trace_buf, 0, 16448, st));
-    }
-    k.trace = tracing ? trace_buf : nullptr;
-    if (tracing && getenv("ISEGMI_STRIP_TRACE_LIGHT")) k.dbg |= 16;
-#endif
-    LDS_LIMIT_ONCE((int)lds_attr, conv3x3_f16_strip_kernel<BM, BN, WM, WN, LW, NB>);
-    hipLaunchKernelGGL((conv3x3_f16_strip_kernel<BM, BN, WM, WN, LW, NB>), dim3((unsigned)(k.mtiles * k.ntiles)), dim3((NW + LW) * 64), lds, st, k);
-    HIP_TRY(hipGetLastError());
-#ifdef ISEGMI_STRIP_TRACE
-    if (tracing) {
-        static unsigned host[4112];
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipMemcpy(host, trace_buf, 16448, hipMemcpyDeviceToHost));
-        FILE* f = fopen(getenv("ISEGMI_STRIP_TRACE_DUMP"), "w");
-        if (f) {
-            fprintf(f, "-1 -1 %u %u 0 0\n", host[4096], host[4097]);
-            for (int w = 0; w < NW + LW; ++w)
-                for (int u = 0; u < 64; ++u) fprintf(f, "%d %d %u %u %u %u\n", w, u, host[(w * 64 + u) * 4], host[(w * 64 + u) * 4 + 1], host[(w * 64 + u) * 4 + 2], host[(w * 64 + u) * 4 + 3]);
-            fclose(f);
-        }
-    }
-#endif
-    return ISEGMI_OK;
+    return conv_f16_launch_strip<conv3x3_f16_strip_kernel<BM, BN, WM, WN, LW, NB>, f32x16h[BM / WM / 32][BN / WN / 32], BM, BN, WM, WN, LW, NB>(k, st);
+}
+template <int BM, int BN, int WM, int WN, int NSTAGE, int OCC, int LW, bool UP2X = false>
+static int launch_p(ConvKH& k, hipStream_t st, bool few) {
+    return conv_f16_launch_p<conv_f16_persist_kernel<BM, BN, WM, WN, NSTAGE, OCC, LW, UP2X>, f32x16h[BM / WM / 32][BN / WN / 32], BM, BN, WM, WN, NSTAGE, OCC, LW>(k, st, few);
 }
 
 template <int BM, int BN, int WM, int WN, int NSTAGE, int OCC, bool STEM = false, int LW = 0>
@@ -872,26 +457,6 @@ static int launch_g(ConvKH& k, hipStream_t st) {
     return ISEGMI_OK;
 }
 
-// persistent loader-wave kernel: at most one block per CU slot, each walking tiles bid, bid + grid, ...; `few` (test hook) forces
-// an 8-block grid so that small test shapes exercise the multi-tile stream
-template <int BM, int BN, int WM, int WN, int NSTAGE, int OCC, int LW, bool UP2X = false>
-static int launch_p(ConvKH& k, hipStream_t st, bool few) {
-    k.mtiles = cdiv(k.M, BM);
-    k.ntiles = cdiv(k.Cout, BN);
-    constexpr int NW = WM * WN, TN = BN / WN / 32;
-    size_t lds = (size_t)NSTAGE * (BM + BN) * 128;
-    const size_t epi = (size_t)NW * 32 * (TN * 32 + 4) * 4;  // the per-element epilogue path uses none; kept >= the one-tile kernel's request
-    (void)epi;
-    LDS_LIMIT_ONCE((int)lds, conv_f16_persist_kernel<BM, BN, WM, WN, NSTAGE, OCC, LW, UP2X>);
-    const int ncu = device_cu_count();
-    const int64_t total = (int64_t)k.mtiles * k.ntiles;
-    int64_t slots = few ? 8 : (int64_t)(ncu / 8) * 8 * OCC;  // a multiple of 8, so that a block's tiles stay on its XCD
-    if (slots < 8) slots = 8;
-    const unsigned grid = (unsigned)(total < slots ? total : slots);
-    hipLaunchKernelGGL((conv_f16_persist_kernel<BM, BN, WM, WN, NSTAGE, OCC, LW, UP2X>), dim3(grid), dim3((NW + LW) * 64), lds, st, k);
-    HIP_TRY(hipGetLastError());
-    return ISEGMI_OK;
-}
 
 // 0: v_mfma_f32_32x32x16_f16 everywhere; 1: the row-strip tile (30 -> 40) and the fused RPN head on v_mfma_f32_16x16x32_f16; 2: 1 + the persistent tiles
 // (34 / 37 / 39 -> 44 / 47 / 49) and the UP2X merge; 3 (default): 1 + the 144-row forms (41 / 46) where 192-row tiles leave CUs idle in a single round

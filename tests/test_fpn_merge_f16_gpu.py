@@ -9,6 +9,23 @@ pytestmark = pytest.mark.gpu
 
 @pytest.mark.parametrize("shape", [(2, 100, 168, 512), (1, 200, 336, 256), (3, 25, 42, 1024), (2, 51, 85, 256), (1, 13, 21, 2048), (8, 50, 84, 1024)])
 def test_fused_merge_equals_conv_then_upsample_add(ffi, shape):
+    _check_fused_merge(ffi, shape)
+
+
+@pytest.mark.parametrize("mfma_shape", [3, 2])
+def test_fused_merge_equals_conv_then_upsample_add_on_both_mfma_shapes(ffi, mfma_shape):
+    """The UP2X epilogue is one body over both accumulator layouts (csrc/conv_f16_epilogue.h).  Only isegmi_set_f16_mfma_shape 2 sends the merge to the
+    v_mfma_f32_16x16x32_f16 tile (48); 0, 1 and 3 (the default) all run it on the v_mfma_f32_32x32x16_f16 form of tile 37, so the pair here is 3 and 2.
+    Odd extents: the min(y >> 1, Hc - 1) clamp is live."""
+    assert ffi.get_f16_mfma_shape() == 3
+    ffi.set_f16_mfma_shape(mfma_shape)
+    try:
+        _check_fused_merge(ffi, (2, 51, 85, 256))
+    finally:
+        ffi.set_f16_mfma_shape(3)
+
+
+def _check_fused_merge(ffi, shape):
     N, H, W, Cin = shape
     rng = np.random.default_rng(H * 131 + W + Cin)
     x = np.maximum(rng.standard_normal((N, H, W, Cin)), 0).astype(np.float16)

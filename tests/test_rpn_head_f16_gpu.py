@@ -1,4 +1,4 @@
-"""The fused RPN head of the fp16 path (conv_f16_epilogue_head in csrc/conv_mfma_f16.hip: 3x3 conv + BN + ReLU with the cls + bbox 1x1 on the tile while it
+"""The fused RPN head of the fp16 path (conv_f16_epilogue_head in csrc/conv_f16_epilogue.h: 3x3 conv + BN + ReLU with the cls + bbox 1x1 on the tile while it
 is in LDS, configs[4]) against the two launches it replaces: BIT-identical with the 3x3 on the same row-strip tile (t is rounded to fp16 where the two-launch path stores it; the 1x1 walks the same
 16 k-steps).  Levels too small for the 192 x 256 row-strip tile must report fused = 0 and launch nothing."""
 import numpy as np
@@ -19,6 +19,25 @@ def _case(rng, N, H, W, Cin=256, cout2=15):
 @pytest.mark.parametrize("shape", [(2, 100, 168), (1, 200, 336), (2, 131, 197), (8, 50, 84), (1, 211, 333), (3, 67, 91)])
 @pytest.mark.parametrize("cout2", [15, 3, 32])
 def test_fused_head_equals_two_launches(ffi, shape, cout2):
+    _check_fused_head(ffi, shape, cout2)
+
+
+@pytest.mark.parametrize("shape", [(3, 67, 91), (1, 131, 197)])
+@pytest.mark.parametrize("mfma_shape", [0, 3])
+def test_fused_head_equals_two_launches_on_both_mfma_shapes(ffi, mfma_shape, shape):
+    """The head's epilogue is one body over both accumulator layouts (csrc/conv_f16_epilogue.h): isegmi_set_f16_mfma_shape 0 runs the fused launch on
+    the v_mfma_f32_32x32x16_f16 row-strip tile (30), 3 (the default; 1 and 2 route the same) on its v_mfma_f32_16x16x32_f16 twin (40).  (3, 67, 91):
+    M = 18 291 is 96 tiles, under the half round of 192-row tiles the fusion starts at -- under either setting it must report fused = 0 and launch
+    nothing.  (1, 131, 197): M = 25 807 is the smallest such level that IS fused, and no multiple of 192 either: the last tile has dead rows."""
+    assert ffi.get_f16_mfma_shape() == 3
+    ffi.set_f16_mfma_shape(mfma_shape)
+    try:
+        _check_fused_head(ffi, shape, 15)
+    finally:
+        ffi.set_f16_mfma_shape(3)
+
+
+def _check_fused_head(ffi, shape, cout2):
     N, H, W = shape
     rng = np.random.default_rng(H * 131 + W + cout2)
     x, w, sc, sh, w2, sc2, sh2 = _case(rng, N, H, W, 256, cout2)
