@@ -165,6 +165,18 @@ int isegmi_op_maxpool(const float* d_in, int N, int H, int W, int C, int k, int 
 /* bilinear align_corners=False to (Ho,Wo), optional +add, optional relu (Y3, Y4) */
 int isegmi_op_resize_bilinear(const float* d_in, int N, int H, int W, int C, int Ho, int Wo,
                               const float* d_add, int relu, float* d_out, void* stream);
+/* Keypoint R-CNN predictor tail ([UPSTREAM-RECALL] KeypointRCNNPredictor): d_in [R][Hi][Wi][4*K] is ConvTranspose2d(4, 2, 1) run as a 3x3
+ * convolution with parity-major outputs (channel (2 py + px) * K + k belongs to pixel (2y + py, 2x + px)); d_out [R][4 Hi][4 Wi][K] = bilinear x2
+ * (align_corners False) of that pixel shuffle, bit-identical to shuffling on the host and calling isegmi_op_resize_bilinear. */
+int isegmi_op_keypoint_heatmap(const float* d_in, int64_t R, int Hi, int Wi, int K, float* d_out, void* stream);
+/* Keypointer / heatmaps_to_keypoints on the device, one launch, the resized maps never exist in memory: for detection slot (n, c) with c < d_count[n] and box
+ * (x1, y1, x2, y2) = d_boxes[n][c]: w = max(x2 - x1, 1), wc = ceil(w) (h likewise); each of the K maps d_heat[n * cap + c][S][S][k] is resized bicubically
+ * (A = -0.75, half-pixel centres, clamped taps, horizontal pass first, every product and sum a separate fp32 operation) to hc x wc; the first maximum in
+ * row-major order at (x_int, y_int) gives d_kpt[n][c][k] = ((x_int + 0.5) * (w / wc) + x1, (y_int + 0.5) * (h / hc) + y1, 1) and d_kscore[n][c][k] = the
+ * resized value there.  Slots c >= d_count[n] are written as zeros and their maps are not read.  S <= 64, K <= 32, N * cap <= 65535; resized sides are
+ * cut at 16384.  NaN maps are outside the contract. */
+int isegmi_op_keypoint_decode(const float* d_heat, const float* d_boxes, const int32_t* d_count, int N, int cap, int S, int K, float* d_kpt,
+                              float* d_kscore, void* stream);
 /* modulated deformable im2col: the sampling stage of the DCNv2 3x3 convolutions of the YOLACT++ backbones
  * (the YOLACT++ rows of README.md:216-221).  d_offset_mask [N][Ho][Wo][3*R*S] is the raw conv_offset_mask
  * output (channel 2k = dy_k, 2k+1 = dx_k, 2*R*S+k = mask logit); d_out [N][Ho][Wo][R*S][C] feeds a 1x1
@@ -606,6 +618,11 @@ int isegmi_engine_pack_coco_records(isegmi_engine* e, void* d_dst, int64_t cap, 
  *   isegmi_maskrcnn_paste.  No string offsets, no characters; image slots past the last forward's batch are zero.
  * isegmi_engine_coco_record_bytes returns this block's size (chars_offset = the size) while the engine's "mask_on" is 0. */
 int isegmi_engine_pack_box_records(isegmi_engine* e, const float* h_ratios_wh, void* d_dst, int64_t cap, int n_block, int64_t* bytes);
+/* Keypoint record block of the last forward of a Keypoint R-CNN engine (set_param "keypoint_on" 1), ONE launch on the results stream: the
+ *   box-only block above with two more sections behind label, [kpt f32 x n_block*K*NK*3][kscore f32 x n_block*K*NK] (NK keypoints per detection): kpt's x and
+ *   y = det.kpt * (ratio_w, ratio_h), one fp32 multiplication each, v copied; every section starts on a multiple of 8 bytes, unused slots are zero.
+ * isegmi_engine_coco_record_bytes returns this block's size (chars_offset = the size) while the engine's "keypoint_on" is 1. */
+int isegmi_engine_pack_keypoint_records(isegmi_engine* e, const float* h_ratios_wh, void* d_dst, int64_t cap, int n_block, int64_t* bytes);
 int isegmi_engine_download_async(isegmi_engine* e, int slot, void* h_dst_pinned, const void* d_src, int64_t bytes);
 int isegmi_engine_download_fence(isegmi_engine* e, int slot);
 int isegmi_engine_download_wait(isegmi_engine* e, int slot);

@@ -99,4 +99,12 @@ __device__ __forceinline__ void dm_bil_coef(int dst, int in_sz, int out_sz, int&
     dm_bil_coef_s(dst, in_sz, dm_div((float)in_sz, (float)out_sz), i0, i1, l0, l1);
 }
 
+// one bilinear sample from its four taps: the rounding sequence of every fp32 bilinear resize here (oracle: ora_resize_bilinear)
+__device__ __forceinline__ float dm_bil1(float lx0, float lx1, float ly0, float ly1, float v00, float v01, float v10, float v11) {
+    float top = lx0 * v00; top = fmaf(lx1, v01, top);
+    float bot = lx0 * v10; bot = fmaf(lx1, v11, bot);
+    float v = ly0 * top; v = fmaf(ly1, bot, v);
+    return v;
+}
+
 }  // namespace isegmi

@@ -293,6 +293,8 @@ int maskrcnn_forward(Engine& e, const float* d_images, int N);
 int eng_next_event(Engine& e, hipEvent_t* ev);
 int maskrcnn_paste(Engine& e, const float* h_ratios_wh, int out_h, int out_w);
 bool maskrcnn_mask_on(Engine& e);
+bool maskrcnn_keypoint_on(Engine& e);
+int maskrcnn_num_keypoints(Engine& e);
 int maskrcnn_stage_ratios(Engine& e, const float* h_ratios_wh, int N, hipStream_t ps, void** d_ratios);
 
 // kernels implemented in other translation units (the detection tail's launchers: tail_launch.h)

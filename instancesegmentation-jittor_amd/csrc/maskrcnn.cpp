@@ -63,6 +63,24 @@ int maskrcnn_det_cap(Engine& e) {
 // through isegmi_engine_pack_box_records.  Read each forward: an engine whose weights include the mask head may be toggled.
 bool maskrcnn_mask_on(Engine& e) { return e.param("mask_on", 1.0f) != 0.0f; }
 
+// MODEL.KEYPOINT_ON: "keypoint_on" 1 = Keypoint R-CNN -- behind box_postprocess the keypoint head runs over the detections and the results
+// leave through isegmi_engine_pack_keypoint_records.  Built on the FrozenBN FPN bodies in fp32, next to no mask head.
+bool maskrcnn_keypoint_on(Engine& e) { return e.param("keypoint_on", 0.0f) != 0.0f; }
+int maskrcnn_num_keypoints(Engine& e) { return (int)e.param("num_keypoints", 17.0f); }
+
+static int keypoint_refusals(Engine& e) {
+    if (!maskrcnn_keypoint_on(e)) return ISEGMI_OK;
+    const char* why = maskrcnn_mask_on(e) ? "mask_on 1 (MODEL.MASK_ON True): a model with both heads is not built, set mask_on 0"
+                      : e.fp16 ? "fp16: the keypoint head is fp32 only"
+                      : e.param("arch_c4", 0.0f) != 0.0f ? "arch_c4 (the R-50-C4 body): the keypoint head reads P2..P5"
+                      : eng_has_gn(e, "backbone.body.stem.conv1") ? "GroupNorm weights (USE_GN): the keypoint head is built on the FrozenBN bodies"
+                      : nullptr;
+    if (why) { set_error(std::string("keypoint_on 1 (MODEL.KEYPOINT_ON) together with ") + why); return ISEGMI_ERR_STATE; }
+    const int nk = maskrcnn_num_keypoints(e);
+    if (nk < 1 || nk > 32) { set_error("num_keypoints (MODEL.ROI_KEYPOINT_HEAD.NUM_CLASSES) must be 1..32, got " + std::to_string(nk)); return ISEGMI_ERR_STATE; }
+    return ISEGMI_OK;
+}
+
 // The box predictor's shape: "num_classes" (MODEL.ROI_BOX_HEAD.NUM_CLASSES, background included) and "cls_agnostic" (MODEL.CLS_AGNOSTIC_BBOX_REG: two
 // sets of four deltas, the last one decoded for every class).  `width` = outputs of the fused cls_score | bbox_pred layer.
 static int box_predictor_shape(Engine& e, int width, int* ncls, int* agnostic) {
@@ -95,6 +113,7 @@ static int level_anchors(Engine& e, int l, int A, int gh, int gw, bool regen, co
 }
 
 int maskrcnn_forward(Engine& e, const float* d_images, int N) {
+    TRY(keypoint_refusals(e));
     if (e.param("arch_c4", 0.0f) != 0.0f) return maskrcnn_c4_forward(e, d_images, N);
     const int H = e.cur_H, W = e.cur_W;
     const bool regen_anchors = e.capturing || e.anchor_H != H || e.anchor_W != W;
@@ -436,6 +455,50 @@ int maskrcnn_forward(Engine& e, const float* d_images, int N) {
         TRY(box_postprocess_launch(&a, st));
     }
     eng_mark(e, "box_head");
+    if (maskrcnn_keypoint_on(e)) {
+        // ---- keypoint head: RoIAlign 14x14 on the detections -> conv_fcn1.. (3x3 + ReLU) -> ConvTranspose2d(4, 2, 1) as ONE 3x3 convolution
+        // with 4 * K parity-major outputs -> pixel shuffle + bilinear x2 -> fused bicubic resize + arg-max per (detection, keypoint)
+        const int NK = maskrcnn_num_keypoints(e);
+        Tensor kf;
+        TRY(eng_act(e, "kp.roi_feat", N * cap, 14, 14, 256, &kf));
+        {
+            OpScope op(e, st, "roi_align 14x14 (keypoint head)", feat_bytes + (double)N * cap * 20 + (double)N * cap * 196 * 256 * 4);
+            int* order = nullptr;
+            void* tab = nullptr;
+            if ((roi_table & 2) && cap <= 2048) {
+                TRY(eng_buf(e, "kp.roi_order", (int64_t)N * cap * 4, &p, 1, {N, cap}));
+                order = (int*)p;
+                TRY(eng_buf(e, "kp.roi_table", (int64_t)N * cap * 57 * 16, &tab, 1, {N * cap, 57, 4}));
+                TRY(roi_prep_launch(a.d_out_boxes, a.d_out_count, N, cap, Hs, Ws, scales, 4, 2, 256, 14, 14, 4, order, tab, st, roi_aligned));
+            }
+            TRY(roi_align_launch(feats, Hs, Ws, scales, 4, a.d_out_boxes, a.d_out_count, N, cap, 256, 14, 14, 2, 2, -1, kf.d, nullptr, st, order, tab, roi_aligned));
+        }
+        for (int i = 1; e.convs.count("roi_heads.keypoint.feature_extractor.conv_fcn" + std::to_string(i)); ++i) {
+            Tensor o;
+            TRY(eng_conv(e, "roi_heads.keypoint.feature_extractor.conv_fcn" + std::to_string(i), kf, 1, 1, 1, nullptr, "kp.fcn" + std::to_string(i), &o));
+            kf = o;
+        }
+        Tensor low;
+        TRY(eng_conv(e, "roi_heads.keypoint.predictor.kps_score_lowres", kf, 1, 1, 0, nullptr, "kp.lowres68", &low, /*out_f32=*/true));
+        if (low.C != 4 * NK) { set_error("kps_score_lowres has " + std::to_string(low.C) + " packed outputs; num_keypoints " + std::to_string(NK) + " needs 4 * " + std::to_string(NK)); return ISEGMI_ERR_STATE; }
+        Tensor heat;
+        TRY(eng_act(e, "kp.heat", N * cap, 56, 56, NK, &heat));
+        void *kq, *ks;
+        TRY(eng_buf(e, "det.kpt", (int64_t)N * cap * NK * 12, &kq, 0, {N, cap, NK, 3}));
+        TRY(eng_buf(e, "det.kscore", (int64_t)N * cap * NK * 4, &ks, 0, {N, cap, NK}));
+        {
+            OpScope op(e, st, "keypoint_heatmap (pixel shuffle + bilinear x2)", (double)N * cap * (196.0 * 4 + 3136.0) * NK * 4);
+            TRY(keypoint_heatmap_launch(low.d, (int64_t)N * cap, 14, 14, NK, heat.d, st));
+        }
+        {
+            OpScope op(e, st, "keypoint_decode (bicubic resize to the box + arg-max)", (double)N * cap * NK * (3136.0 + 4) * 4);
+            TRY(keypoint_decode_launch(heat.d, a.d_out_boxes, a.d_out_count, N, cap, 56, NK, (float*)kq, (float*)ks, st));
+        }
+        eng_mark(e, "keypoint_head");
+        TRY(eng_tail_end(e));
+        e.cur = e.stream;
+        return ISEGMI_OK;
+    }
     if (!maskrcnn_mask_on(e)) {   // Faster R-CNN: det.* is the result; the tail's bookkeeping as behind the mask head
         TRY(eng_tail_end(e));
         e.cur = e.stream;

@@ -16,6 +16,9 @@
 //
 // Box-only block (Faster R-CNN: a Mask R-CNN-family engine with "mask_on" 0), every section starting on a multiple of 8 bytes:
 //   [status  i32 x 4 = 0][box f32 x N*K*4, original-image xyxy][count i32 x N][score f32 x N*K][label i32 x N*K]      no str_off, no characters
+//
+// Keypoint block (Keypoint R-CNN: "keypoint_on" 1): the box-only block with two more sections behind label, each on a multiple of 8 bytes:
+//   ... [label i32 x N*K][kpt f32 x N*K*NK*3, (x, y) in original-image coordinates, v][kscore f32 x N*K*NK]           NK keypoints per detection
 #include <string.h>
 
 #include "engine.h"
@@ -83,6 +86,17 @@ static BoxRecordLayout box_record_layout(int n, int K) {
     return l;
 }
 
+// the keypoint block: the box-only sections, then kpt and kscore
+struct KeypointRecordLayout { BoxRecordLayout b; int64_t kpt, kscore, total; };
+static KeypointRecordLayout keypoint_record_layout(int n, int K, int NK) {
+    KeypointRecordLayout l;
+    l.b = box_record_layout(n, K);
+    l.kpt = l.b.total;
+    l.kscore = align8(l.kpt + (int64_t)n * K * NK * 12);
+    l.total = align8(l.kscore + (int64_t)n * K * NK * 4);
+    return l;
+}
+
 // RLE of det.masks (the planes the last yolact_postprocess / maskrcnn_paste wrote) on the results stream.
 int eng_rle(Engine& e, const int32_t* h_image_hw) {
     const int N = e.last_N;
@@ -146,7 +160,7 @@ extern "C" int isegmi_engine_rle(isegmi_engine* h, const int32_t* h_image_hw) {
 extern "C" int isegmi_engine_coco_record_bytes(isegmi_engine* h, int N, int64_t* bytes, int64_t* chars_offset) {
     ARG_CHECK(h && bytes && N > 0 && N <= h->e.max_batch, "record_bytes args");
     if (box_only(h->e)) {
-        *bytes = box_record_layout(N, det_cap(h->e)).total;
+        *bytes = maskrcnn_keypoint_on(h->e) ? keypoint_record_layout(N, det_cap(h->e), maskrcnn_num_keypoints(h->e)).total : box_record_layout(N, det_cap(h->e)).total;
         if (chars_offset) *chars_offset = *bytes;
         return ISEGMI_OK;
     }
@@ -185,9 +199,8 @@ struct PackBoxK {
     char* dst;
     BoxRecordLayout l;
 };
-__global__ void pack_box_records_kernel(const PackBoxK p) {
+__device__ __forceinline__ void pack_box_sections(const PackBoxK& p, int64_t tid, int64_t nth) {
     const int64_t nk = (int64_t)p.n * p.K, nbk = (int64_t)p.nb * p.K;
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
     if (tid < 4) ((int*)p.dst)[tid] = 0;
     for (int64_t i = tid; i < nbk; i += nth) {
         float4 b = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -204,25 +217,58 @@ __global__ void pack_box_records_kernel(const PackBoxK p) {
     for (int64_t i = tid; i < (p.l.label - p.l.score) / 4; i += nth) ((float*)(p.dst + p.l.score))[i] = i < nk ? p.score[i] : 0.0f;
     for (int64_t i = tid; i < (p.l.total - p.l.label) / 4; i += nth) ((int*)(p.dst + p.l.label))[i] = i < nk ? p.label[i] : 0;
 }
+__global__ void pack_box_records_kernel(const PackBoxK p) {
+    pack_box_sections(p, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+}
 
-extern "C" int isegmi_engine_pack_box_records(isegmi_engine* h, const float* h_ratios_wh, void* d_dst, int64_t cap, int n_block, int64_t* bytes) {
+// The keypoint block in one launch: the box-only sections as above, then the keypoints -- x * ratio_w, y * ratio_h (one fp32 multiplication each, as the
+// boxes), v copied -- and their logits; slots at or beyond an image's count were zeroed by keypoint_decode_kernel, slots n .. nb-1 and the padding are zero here.
+struct PackKeypointK {
+    PackBoxK b;
+    const float* kpt; const float* kscore;
+    int NK;
+    int64_t off_kpt, off_kscore, total;
+};
+__global__ void pack_keypoint_records_kernel(const PackKeypointK p) {
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
+    pack_box_sections(p.b, tid, nth);
+    const int64_t per_img = (int64_t)p.b.K * p.NK, live = (int64_t)p.b.n * per_img;
+    for (int64_t i = tid; i < (p.off_kscore - p.off_kpt) / 4; i += nth) {
+        float v = 0.0f;
+        if (i < live * 3) {
+            const int c = (int)(i % 3), img = (int)(i / (per_img * 3));
+            v = p.kpt[i];
+            if (c < 2) v = v * p.b.ratios[2 * img + c];
+        }
+        ((float*)(p.b.dst + p.off_kpt))[i] = v;
+    }
+    for (int64_t i = tid; i < (p.total - p.off_kscore) / 4; i += nth) ((float*)(p.b.dst + p.off_kscore))[i] = i < live ? p.kscore[i] : 0.0f;
+}
+
+// both box record forms: `keypoints` adds the kpt / kscore sections (one launch either way)
+static int pack_box_family(isegmi_engine* h, const float* h_ratios_wh, void* d_dst, int64_t cap, int n_block, int64_t* bytes, bool keypoints) {
+    const std::string who = keypoints ? "pack_keypoint_records" : "pack_box_records";   // the entry point that was called
     ARG_CHECK(h && h_ratios_wh && d_dst && bytes, "null");
     Engine& e = h->e;
-    ARG_CHECK(e.kind == 2, "pack_box_records: engine is not a Mask R-CNN / Faster R-CNN engine");
+    ARG_CHECK(e.kind == 2, (who + ": engine is not a Mask R-CNN / Faster R-CNN engine").c_str());
+    ARG_CHECK(!keypoints || maskrcnn_keypoint_on(e), "pack_keypoint_records: the engine has no keypoint head (keypoint_on 0, MODEL.KEYPOINT_ON False)");
     const int N = e.last_N;
     ARG_CHECK(N > 0, "pack before forward");
     ARG_CHECK(n_block >= N && n_block <= e.max_batch, "n_block: between the last forward's batch and max_batch");
-    const int K = det_cap(e);
-    PackBoxK p;
-    memset(&p, 0, sizeof(p));
-    p.l = box_record_layout(n_block, K);
-    ARG_CHECK(p.l.total <= cap, "record buffer too small");
-    const char* names[4] = {"det.box", "det.count", "det.score", "det.label"};
-    const int64_t need[4] = {(int64_t)N * K * 16, (int64_t)N * 4, (int64_t)N * K * 4, (int64_t)N * K * 4};
-    void* src[4];
-    for (int i = 0; i < 4; ++i) {
+    const int K = det_cap(e), NK = keypoints ? maskrcnn_num_keypoints(e) : 0;
+    PackKeypointK pk;
+    memset(&pk, 0, sizeof(pk));
+    PackBoxK& p = pk.b;
+    const KeypointRecordLayout kl = keypoint_record_layout(n_block, K, NK);
+    p.l = kl.b;
+    const int64_t total = keypoints ? kl.total : kl.b.total;
+    ARG_CHECK(total <= cap, "record buffer too small");
+    const char* names[6] = {"det.box", "det.count", "det.score", "det.label", "det.kpt", "det.kscore"};
+    const int64_t need[6] = {(int64_t)N * K * 16, (int64_t)N * 4, (int64_t)N * K * 4, (int64_t)N * K * 4, (int64_t)N * K * NK * 12, (int64_t)N * K * NK * 4};
+    void* src[6];
+    for (int i = 0; i < (keypoints ? 6 : 4); ++i) {
         auto it = e.bufs.find(names[i]);
-        if (it == e.bufs.end() || it->second.d == nullptr || it->second.bytes < need[i]) { set_error(std::string("pack_box_records: buffer not produced yet: ") + names[i]); return ISEGMI_ERR_STATE; }
+        if (it == e.bufs.end() || it->second.d == nullptr || it->second.bytes < need[i]) { set_error(who + ": buffer not produced yet: " + names[i]); return ISEGMI_ERR_STATE; }
         src[i] = it->second.d;
     }
     hipStream_t rs = eng_results_stream(e);
@@ -230,11 +276,25 @@ extern "C" int isegmi_engine_pack_box_records(isegmi_engine* h, const float* h_r
     TRY(maskrcnn_stage_ratios(e, h_ratios_wh, N, rs, &rt));
     p.box = (const float*)src[0]; p.count = (const int*)src[1]; p.score = (const float*)src[2]; p.label = (const int*)src[3];
     p.ratios = (const float*)rt; p.n = N; p.nb = n_block; p.K = K; p.dst = (char*)d_dst;
-    hipLaunchKernelGGL(pack_box_records_kernel, dim3(16), dim3(256), 0, rs, p);
+    if (keypoints) {
+        pk.kpt = (const float*)src[4]; pk.kscore = (const float*)src[5]; pk.NK = NK;
+        pk.off_kpt = kl.kpt; pk.off_kscore = kl.kscore; pk.total = kl.total;
+        hipLaunchKernelGGL(pack_keypoint_records_kernel, dim3(32), dim3(256), 0, rs, pk);
+    } else {
+        hipLaunchKernelGGL(pack_box_records_kernel, dim3(16), dim3(256), 0, rs, p);
+    }
     HIP_TRY(hipGetLastError());
     if (rs == e.tail && e.tail) HIP_TRY(hipEventRecord(e.tail_done, e.tail));   // reads det.*: extend the WAR fence
-    *bytes = p.l.total;
+    *bytes = total;
     return ISEGMI_OK;
+}
+
+extern "C" int isegmi_engine_pack_box_records(isegmi_engine* h, const float* h_ratios_wh, void* d_dst, int64_t cap, int n_block, int64_t* bytes) {
+    return pack_box_family(h, h_ratios_wh, d_dst, cap, n_block, bytes, false);
+}
+
+extern "C" int isegmi_engine_pack_keypoint_records(isegmi_engine* h, const float* h_ratios_wh, void* d_dst, int64_t cap, int n_block, int64_t* bytes) {
+    return pack_box_family(h, h_ratios_wh, d_dst, cap, n_block, bytes, true);
 }
 
 extern "C" int isegmi_engine_pack_coco_records(isegmi_engine* h, void* d_dst, int64_t cap, int n_block, int64_t* bytes) {

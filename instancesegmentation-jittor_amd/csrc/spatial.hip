@@ -34,14 +34,6 @@ __global__ void maxpool_kernel(const float* __restrict__ in, int N, int H, int W
     }
 }
 
-__device__ __forceinline__ float bil1(float lx0, float lx1, float ly0, float ly1, float v00, float v01, float v10,
-                                      float v11) {
-    float top = lx0 * v00; top = fmaf(lx1, v01, top);
-    float bot = lx0 * v10; bot = fmaf(lx1, v11, bot);
-    float v = ly0 * top; v = fmaf(ly1, bot, v);
-    return v;
-}
-
 __global__ void resize_bilinear_kernel(const float* __restrict__ in, int N, int H, int W, int C, int Ho, int Wo,
                                        const float* __restrict__ add, int relu, float* __restrict__ out) {
     const int c4n = C >> 2;
@@ -61,10 +53,10 @@ __global__ void resize_bilinear_kernel(const float* __restrict__ in, int N, int 
         const float4 v10 = *(const float4*)(b + ((int64_t)y1 * W + x0) * C);
         const float4 v11 = *(const float4*)(b + ((int64_t)y1 * W + x1) * C);
         float4 o;
-        o.x = bil1(lx0, lx1, ly0, ly1, v00.x, v01.x, v10.x, v11.x);
-        o.y = bil1(lx0, lx1, ly0, ly1, v00.y, v01.y, v10.y, v11.y);
-        o.z = bil1(lx0, lx1, ly0, ly1, v00.z, v01.z, v10.z, v11.z);
-        o.w = bil1(lx0, lx1, ly0, ly1, v00.w, v01.w, v10.w, v11.w);
+        o.x = dm_bil1(lx0, lx1, ly0, ly1, v00.x, v01.x, v10.x, v11.x);
+        o.y = dm_bil1(lx0, lx1, ly0, ly1, v00.y, v01.y, v10.y, v11.y);
+        o.z = dm_bil1(lx0, lx1, ly0, ly1, v00.z, v01.z, v10.z, v11.z);
+        o.w = dm_bil1(lx0, lx1, ly0, ly1, v00.w, v01.w, v10.w, v11.w);
         const int64_t oo = (((int64_t)n * Ho + y) * Wo + x) * C + c4 * 4;
         if (add) {
             const float4 a = *(const float4*)(add + oo);

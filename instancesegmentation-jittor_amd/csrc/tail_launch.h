@@ -58,4 +58,9 @@ int retina_select_launch(const isegmi_retina_select_args* p, hipStream_t st);
 int64_t retina_post_workspace_bytes(int N, int nseg, int seg_len);
 int retina_postprocess_launch(const isegmi_retina_post_args* p, hipStream_t st);
 
+
+// ---- csrc/keypoint_ops.hip
+int keypoint_heatmap_launch(const float* in, int64_t R, int Hi, int Wi, int K, float* out, hipStream_t st);
+int keypoint_decode_launch(const float* heat, const float* boxes, const int* count, int N, int cap, int S, int K, float* kpt, float* kscore, hipStream_t st);
+
 }  // namespace isegmi

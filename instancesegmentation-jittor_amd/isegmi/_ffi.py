@@ -266,6 +266,40 @@ def resize_bilinear(x, Ho, Wo, add=None, relu=0):
     return do.numpy()
 
 
+def _kp(name):
+    """A keypoint-tail entry point with its argtypes declared: an ABI change raises instead of shifting arguments."""
+    f = getattr(lib(), name)
+    if f.argtypes is None:
+        V, I, L = C.c_void_p, C.c_int, C.c_int64
+        f.argtypes = {"isegmi_op_keypoint_heatmap": [V, L, I, I, I, V, V], "isegmi_op_keypoint_decode": [V, V, V, I, I, I, I, V, V, V]}[name]
+        f.restype = I
+    return f
+
+
+def keypoint_heatmap(x, K):
+    """isegmi_op_keypoint_heatmap: x [R, Hi, Wi, 4 * K] (the packed transposed convolution's output) -> [R, 4 Hi, 4 Wi, K]."""
+    x = np.ascontiguousarray(x, np.float32)
+    R, Hi, Wi, c = x.shape
+    assert c == 4 * K, (c, K)
+    dx = DeviceBuffer.from_numpy(x); do = DeviceBuffer((R, 4 * Hi, 4 * Wi, K)).poison()
+    check(_kp("isegmi_op_keypoint_heatmap")(dx.ptr, R, Hi, Wi, K, do.ptr, None))
+    return do.numpy()
+
+
+def keypoint_decode(heat, boxes, count):
+    """isegmi_op_keypoint_decode: heat [N * cap, S, S, K], boxes [N, cap, 4], count [N] -> (kpt [N, cap, K, 3], kscore [N, cap, K])."""
+    heat = np.ascontiguousarray(heat, np.float32)
+    boxes = np.ascontiguousarray(boxes, np.float32)
+    count = np.ascontiguousarray(count, np.int32)
+    N, cap = boxes.shape[:2]
+    R, S, S2, K = heat.shape
+    assert R == N * cap and S == S2 and boxes.shape == (N, cap, 4) and count.shape == (N,), (heat.shape, boxes.shape, count.shape)
+    dh, db, dc = DeviceBuffer.from_numpy(heat), DeviceBuffer.from_numpy(boxes), DeviceBuffer.from_numpy(count)
+    dk, ds = DeviceBuffer((N, cap, K, 3)).poison(), DeviceBuffer((N, cap, K)).poison()
+    check(_kp("isegmi_op_keypoint_decode")(dh.ptr, db.ptr, dc.ptr, N, cap, S, K, dk.ptr, ds.ptr, None))
+    return dk.numpy(), ds.numpy()
+
+
 def resize_bilinear_f16(x, Ho, Wo, add=None, relu=0):
     """isegmi_op_resize_bilinear_f16: x [N,H,W,C] and add [N,Ho,Wo,C] cast to fp16 -> fp16 [N,Ho,Wo,C]."""
     x = np.ascontiguousarray(x, np.float16)

@@ -124,14 +124,15 @@ def cmd_eval(a):
 
 def cmd_test_net(a):
     """tools/test_net.py: build the model from the yaml, run inference() over the images, write COCO-format json."""
-    from .config import cfg, is_retinanet, to_maskrcnn_config, to_retinanet_config
+    from .config import cfg, is_keypoint_rcnn, is_retinanet, to_keypointrcnn_config, to_maskrcnn_config, to_retinanet_config
     from .predictor import COCODemo, inference
     c = cfg.clone()
     if a.config_file:
         c.merge_from_file(a.config_file)
     c.merge_from_list(a.opts)
     retina = is_retinanet(c)   # MODEL.RETINANET_ON: the one-stage detector, bbox results only
-    mc = to_retinanet_config(c) if retina else to_maskrcnn_config(c)
+    # MODEL.KEYPOINT_ON: Keypoint R-CNN -- one json entry per detection with `keypoints`; --gt prints the bbox numbers (DESIGN.md 14)
+    mc = to_retinanet_config(c) if retina else to_keypointrcnn_config(c) if is_keypoint_rcnn(c) else to_maskrcnn_config(c)
     rank, world, local = _rank_world()
     files = sorted(os.path.join(a.images, f) for f in os.listdir(a.images)) if a.images else []
     if retina:

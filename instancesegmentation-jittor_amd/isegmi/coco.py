@@ -217,10 +217,11 @@ def label_categories(num_classes=81, category_ids=None):
     return [None] + (list(COCO_CATEGORY_IDS) if n == 81 else list(range(1, n)))
 
 
-def maskrcnn_results(image_id, boxes_xyxy, scores, labels, masks=None, categories=None):
+def maskrcnn_results(image_id, boxes_xyxy, scores, labels, masks=None, categories=None, keypoints=None):
     """maskrcnn-benchmark prepare_for_coco_detection/segmentation: bbox xywh with the legacy +1 widths,
     category_id via the contiguous->json id map (categories: a label_categories() list; default the 80 COCO classes), segmentation = RLE of the
-    pasted HxW mask (masks None: bbox-only results, no `segmentation` key)."""
+    pasted HxW mask (masks None: bbox-only results, no `segmentation` key).  keypoints [n, NK, 3] (Keypoint R-CNN): every entry also
+    carries `keypoints`, the NK * 3 numbers x, y, v of prepare_for_coco_keypoint -- ONE entry per detection where upstream writes a bbox and a keypoint file."""
     out = []
     b = np.asarray(boxes_xyxy, np.float32).reshape(-1, 4)
     cats = categories if categories is not None else label_categories()
@@ -230,6 +231,8 @@ def maskrcnn_results(image_id, boxes_xyxy, scores, labels, masks=None, categorie
              "bbox": [x1, y1, x2 - x1 + 1.0, y2 - y1 + 1.0], "score": float(scores[k])}
         if masks is not None:
             d["segmentation"] = rle_encode(masks[k])
+        if keypoints is not None:
+            d["keypoints"] = np.asarray(keypoints[k], np.float64).reshape(-1).tolist()
         out.append(d)
     return out
 
@@ -257,12 +260,13 @@ def results_from_records(rec, image_ids, image_hw, kind, K=100, score_threshold=
     straight from the device-made strings.  image_ids / image_hw: per image slot of the batch (None id = an empty padding slot).
     score_threshold / top_k (Yolact eval.py --score_threshold / --top_k): keep score > threshold, then the first top_k (score order).
     kind: 1 Yolact, 2 Mask R-CNN, 3 Pose2Seg (category 1, score 1.0, bbox = the mask's tight box).  A box-only block (Faster R-CNN: no str_off in
-    `rec`) gives bbox-only results without a `segmentation` key.  categories (kind 2): a label_categories() list, default the 80 COCO classes."""
+    `rec`) gives bbox-only results without a `segmentation` key; a keypoint block (Keypoint R-CNN: `kpt` in `rec`) adds `keypoints`, NK * 3 numbers x, y, v.
+    categories (kind 2): a label_categories() list, default the 80 COCO classes."""
     out = []
     count, box, score, label = rec["count"], rec["box"], rec["score"], rec["label"]
     so, chars = rec.get("str_off"), rec.get("chars")
     lab_cat = categories if categories is not None else label_categories()
-    ms = rec.get("mscore")
+    ms, kp = rec.get("mscore"), rec.get("kpt")
     for n, iid in enumerate(image_ids):
         c = int(count[n])
         if iid is None or c == 0:
@@ -291,6 +295,8 @@ def results_from_records(rec, image_ids, image_hw, kind, K=100, score_threshold=
                 d["segmentation"] = {"size": [h, w], "counts": chars[offs[k]:offs[k + 1]].decode("ascii")}
             if ms is not None:
                 d["mask_score"] = float(ms[n, k])
+            if kp is not None:
+                d["keypoints"] = np.asarray(kp[n, k], np.float64).reshape(-1).tolist()
             out.append(d)
     return out
 

@@ -87,6 +87,10 @@ def _defaults():
                           "FPN_POST_NMS_TOP_N_TEST": 1000, "NMS_THRESH": 0.7, "MIN_SIZE": 0},
                   "ROI_HEADS": {"SCORE_THRESH": 0.05, "NMS": 0.5, "DETECTIONS_PER_IMG": 100},
                   "ROI_MASK_HEAD": {"PREDICTOR": "MaskRCNNC4Predictor", "RESOLUTION": 28, "USE_GN": False, "DILATION": 1},
+                  # [UPSTREAM-RECALL] maskrcnn-benchmark defaults.py, MODEL.ROI_KEYPOINT_HEAD
+                  "ROI_KEYPOINT_HEAD": {"FEATURE_EXTRACTOR": "KeypointRCNNFeatureExtractor", "PREDICTOR": "KeypointRCNNPredictor", "POOLER_RESOLUTION": 14,
+                                        "POOLER_SAMPLING_RATIO": 2, "POOLER_SCALES": (0.25, 0.125, 0.0625, 0.03125), "CONV_LAYERS": (512,) * 8,
+                                        "RESOLUTION": 56, "NUM_CLASSES": 17, "SHARE_BOX_FEATURE_EXTRACTOR": False},
                   # [UPSTREAM-RECALL] maskrcnn-benchmark defaults.py, MODEL.RETINANET
                   "RETINANET": {"NUM_CLASSES": 81, "ANCHOR_SIZES": (32, 64, 128, 256, 512), "ASPECT_RATIOS": (0.5, 1.0, 2.0),
                                 "ANCHOR_STRIDES": (8, 16, 32, 64, 128), "STRADDLE_THRESH": 0, "OCTAVE": 2.0, "SCALES_PER_OCTAVE": 3, "USE_C5": True,
@@ -160,6 +164,12 @@ def _norm_config(c, body, mask_on=True):
 
 def to_maskrcnn_config(c):
     """Map the yaml-keyed node onto the frozen dataclass the engine consumes; rejects what the path does not build."""
+    if is_keypoint_rcnn(c):
+        raise ValueError("MODEL.KEYPOINT_ON=True: a Keypoint R-CNN config (DESIGN.md 14) -- to_keypointrcnn_config maps it")
+    return _two_stage_config(c)
+
+
+def _two_stage_config(c):
     body = c.MODEL.BACKBONE.CONV_BODY
     r = c.MODEL.RPN
     h = c.MODEL.ROI_HEADS
@@ -167,10 +177,9 @@ def to_maskrcnn_config(c):
     norm = _norm_config(c, body, mask_on)
     if body not in ("R-50-FPN", "R-101-FPN", "R-50-C4"):
         raise ValueError("built bodies: R-50-FPN, R-101-FPN, R-50-C4 (got %r)" % body)
-    for key, on in (("MODEL.RPN_ONLY", c.MODEL.get("RPN_ONLY", False)), ("MODEL.KEYPOINT_ON", c.MODEL.get("KEYPOINT_ON", False)),
-                    ("TEST.BBOX_AUG.ENABLED", c.TEST.get("BBOX_AUG", {}).get("ENABLED", False))):
+    for key, on in (("MODEL.RPN_ONLY", c.MODEL.get("RPN_ONLY", False)), ("TEST.BBOX_AUG.ENABLED", c.TEST.get("BBOX_AUG", {}).get("ENABLED", False))):
         if _bool(on):
-            raise ValueError("%s=True is not built (DESIGN.md 13: RPN-only models, keypoint heads and test-time box augmentation are out of scope)" % key)
+            raise ValueError("%s=True is not built (DESIGN.md 13: RPN-only models and test-time box augmentation are out of scope)" % key)
     # [UPSTREAM-RECALL] DESIGN.md 13: the three keys that shape the RoI heads
     ncls = int(c.MODEL.ROI_BOX_HEAD.NUM_CLASSES)
     if not 2 <= ncls <= 257:
@@ -198,6 +207,47 @@ def to_maskrcnn_config(c):
                           RPN_FPN_POST_NMS_TOP_N_TEST=int(r.FPN_POST_NMS_TOP_N_TEST), RPN_NMS_THRESH=float(r.NMS_THRESH),
                           RPN_MIN_SIZE=float(r.MIN_SIZE), ROI_SCORE_THRESH=float(h.SCORE_THRESH), ROI_NMS=float(h.NMS),
                           DETECTIONS_PER_IMG=int(h.DETECTIONS_PER_IMG), **heads, **norm)
+
+
+def is_keypoint_rcnn(c):
+    """True for a yaml-keyed node that asks for the keypoint head (MODEL.KEYPOINT_ON)."""
+    return _bool(c.MODEL.get("KEYPOINT_ON", False))
+
+
+def to_keypointrcnn_config(c):
+    """The yaml-keyed node of an e2e_keypoint_rcnn_R_*_FPN_1x.yaml -> MaskRCNNConfig with KEYPOINT_ON; raises, naming the key, for everything that is not
+    built.  The box side of the model goes through the two-stage mapping, so its refusals (RPN_ONLY, TEST.BBOX_AUG.ENABLED, class
+    count, norms) hold here too."""
+    import dataclasses
+    m = c.MODEL
+    k = m.ROI_KEYPOINT_HEAD
+    if not is_keypoint_rcnn(c):
+        raise ValueError("MODEL.KEYPOINT_ON=False: not a Keypoint R-CNN config (to_maskrcnn_config maps the other two-stage models)")
+    if _bool(m.MASK_ON):
+        raise ValueError("MODEL.MASK_ON=True together with MODEL.KEYPOINT_ON: a model with both heads is not built, set MODEL.MASK_ON: False")
+    body = str(m.BACKBONE.CONV_BODY)
+    if body not in ("R-50-FPN", "R-101-FPN"):
+        raise ValueError("MODEL.BACKBONE.CONV_BODY=%r with MODEL.KEYPOINT_ON: the keypoint head is built on R-50-FPN and R-101-FPN (it reads P2..P5)" % body)
+    mc = _two_stage_config(c)
+    if mc.USE_GN:
+        raise ValueError("MODEL.KEYPOINT_ON with GroupNorm (MODEL.RESNETS.TRANS_FUNC / MODEL.FPN.USE_GN ...): the keypoint head is built on the FrozenBN bodies")
+    if _bool(k.SHARE_BOX_FEATURE_EXTRACTOR):
+        raise ValueError("MODEL.ROI_KEYPOINT_HEAD.SHARE_BOX_FEATURE_EXTRACTOR=True is not built: the keypoint head has its own extractor")
+    for key, built in (("FEATURE_EXTRACTOR", "KeypointRCNNFeatureExtractor"), ("PREDICTOR", "KeypointRCNNPredictor")):
+        if str(k[key]) != built:
+            raise ValueError("MODEL.ROI_KEYPOINT_HEAD.%s=%r: built is %s" % (key, k[key], built))
+    for key, built in (("POOLER_RESOLUTION", 14), ("RESOLUTION", 56), ("POOLER_SAMPLING_RATIO", 2)):
+        if int(k[key]) != built:
+            raise ValueError("MODEL.ROI_KEYPOINT_HEAD.%s=%s: built at %d" % (key, k[key], built))
+    if tuple(float(v) for v in k.POOLER_SCALES) != (0.25, 0.125, 0.0625, 0.03125):
+        raise ValueError("MODEL.ROI_KEYPOINT_HEAD.POOLER_SCALES=%r: the pooler reads P2..P5 (1/4 .. 1/32)" % (k.POOLER_SCALES,))
+    layers = tuple(int(v) for v in k.CONV_LAYERS)
+    if not layers or any(v <= 0 or v % 32 for v in layers):
+        raise ValueError("MODEL.ROI_KEYPOINT_HEAD.CONV_LAYERS=%r: at least one layer, widths multiples of 32" % (k.CONV_LAYERS,))
+    nk = int(k.NUM_CLASSES)
+    if not 1 <= nk <= 32:
+        raise ValueError("MODEL.ROI_KEYPOINT_HEAD.NUM_CLASSES=%d: the decode kernel holds 1..32 keypoints" % nk)
+    return dataclasses.replace(mc, KEYPOINT_ON=True, KEYPOINT_CONV_LAYERS=layers, NUM_KEYPOINTS=nk)
 
 
 RETINANET_BODIES = ("R-50-FPN-RETINANET", "R-101-FPN-RETINANET")

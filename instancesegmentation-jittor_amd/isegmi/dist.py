@@ -79,17 +79,22 @@ def unpack_maskrcnn_records(buf, n, K=K_DEFAULT, M=28):
 
 
 # ------------------------------------------------------------------------------------------------ COCO record block (device-side output)
-def coco_record_layout(n, K=K_DEFAULT, kind=2, has_mscore=False, cap_chars=0, box_only=False):
+def coco_record_layout(n, K=K_DEFAULT, kind=2, has_mscore=False, cap_chars=0, box_only=False, keypoints=0):
     """Byte layout of the fixed-size block isegmi_engine_pack_coco_records writes for a batch of n images (csrc/results.cpp):
     -> (sections {name: (offset, nbytes, dtype, shape)}, chars_offset, total_bytes).  kind: 1 Yolact (int64 boxes), 2 Mask R-CNN (fp32).
     box_only: the block isegmi_engine_pack_box_records writes (Faster R-CNN) -- status (zeros), box, count, score, label, every section
-    starting on a multiple of 8 bytes; no str_off, no characters: chars_offset = total_bytes."""
+    starting on a multiple of 8 bytes; no str_off, no characters: chars_offset = total_bytes.
+    keypoints = NK > 0 (with box_only): the block isegmi_engine_pack_keypoint_records writes (Keypoint R-CNN) -- two more sections behind
+    label, kpt [n, K, NK, 3] (x, y in original-image coordinates, v) and kscore [n, K, NK]."""
     y = kind == 1
     secs, off = {}, 0
+    NK = int(keypoints)
+    assert not NK or box_only, "the keypoint sections follow the box-only block"
     if box_only:
         assert kind == 2 and not has_mscore and not cap_chars, "the box-only block is the Mask R-CNN family's"
         for name, nb, dt, shp in (("status", 16, np.int32, (4,)), ("box", n * K * 16, np.float32, (n, K, 4)), ("count", n * 4, np.int32, (n,)),
-                                  ("score", n * K * 4, np.float32, (n, K)), ("label", n * K * 4, np.int32, (n, K))):
+                                  ("score", n * K * 4, np.float32, (n, K)), ("label", n * K * 4, np.int32, (n, K))) + \
+                                 ((("kpt", n * K * NK * 12, np.float32, (n, K, NK, 3)), ("kscore", n * K * NK * 4, np.float32, (n, K, NK))) if NK else ()):
             secs[name] = (off, nb, dt, shp)
             off = (off + nb + 7) & ~7
         return secs, off, off
@@ -110,18 +115,18 @@ class CocoRecordError(RuntimeError):
     pass
 
 
-def unpack_coco_records(buf, n, K=K_DEFAULT, kind=2, has_mscore=False, cap_chars=0, strict=True, box_only=False):
+def unpack_coco_records(buf, n, K=K_DEFAULT, kind=2, has_mscore=False, cap_chars=0, strict=True, box_only=False, keypoints=0):
     """One rank's block -> dict(status, box, count, score, label[, mscore], str_off, chars=bytes, overflow=None).  If the engine flagged an
     overflow of its RLE capacities (the strings are incomplete): strict raises CocoRecordError; otherwise the dict carries
     overflow = (bits, runs, characters) -- bit 1: runs over rle_cap_runs (`runs` = what the step needs; characters unknown then), bit 2:
     characters over rle_cap_chars -- and no strings; isegmi.pipeline.run_record_loop raises the capacities and redoes the step."""
     buf = np.ascontiguousarray(buf, np.uint8).ravel()
-    secs, coff, total = coco_record_layout(n, K, kind, has_mscore, cap_chars, box_only)
+    secs, coff, total = coco_record_layout(n, K, kind, has_mscore, cap_chars, box_only, keypoints)
     assert buf.size >= total, (buf.size, total)
     out = {name: buf[off:off + nb].view(dt).reshape(shp) for name, (off, nb, dt, shp) in secs.items()}
     st = out["status"]
     out["overflow"] = None
-    if box_only:   # no strings, nothing that can overflow: dict(status, box, count, score, label, overflow=None)
+    if box_only:   # no strings, nothing that can overflow: dict(status, box, count, score, label[, kpt, kscore], overflow=None)
         return out
     if st[2] != 0:
         if strict:
@@ -239,7 +244,9 @@ class RcclGather:
         st = C.c_void_p()
         _ffi.check(L.isegmi_engine_stream(net._h, C.byref(st)))
         _ffi.check(L.isegmi_comm_fence_producer(self._c, slot, st))
-        if getattr(net, "box_only", False):   # Faster R-CNN: the box-only block (isegmi_engine_pack_box_records)
+        if getattr(net, "keypoint_on", False):   # Keypoint R-CNN: the box-only block + keypoints (isegmi_engine_pack_keypoint_records)
+            nbv = net.pack_keypoint_records(send, n_block)
+        elif getattr(net, "box_only", False):   # Faster R-CNN: the box-only block (isegmi_engine_pack_box_records)
             nbv = net.pack_box_records(send, n_block)
         else:
             nb = C.c_int64()

@@ -66,6 +66,10 @@ class MaskRCNNConfig:
     MASK_ON: bool = True
     NUM_CLASSES: int = 81                  # MODEL.ROI_BOX_HEAD.NUM_CLASSES, background included (2..257)
     CLS_AGNOSTIC_BBOX_REG: bool = False    # MODEL.CLS_AGNOSTIC_BBOX_REG: bbox_pred has 2 * 4 outputs, the last four decoded once per proposal
+    # [UPSTREAM-RECALL] DESIGN.md 14.  KEYPOINT_ON = Keypoint R-CNN (e2e_keypoint_rcnn_*): roi_heads = [box, keypoint]; MASK_ON False, FrozenBN FPN body, fp32.
+    KEYPOINT_ON: bool = False
+    KEYPOINT_CONV_LAYERS: tuple = (512,) * 8   # MODEL.ROI_KEYPOINT_HEAD.CONV_LAYERS: widths of conv_fcn1.. (multiples of 32)
+    NUM_KEYPOINTS: int = 17                    # MODEL.ROI_KEYPOINT_HEAD.NUM_CLASSES (1..32)
 
     @staticmethod
     def c4():
@@ -184,6 +188,29 @@ def prepare_images(images_bgr_f32, divisibility=32):
     return out, hw
 
 
+KEYPOINT_LOWRES_KEY = "roi_heads.keypoint.predictor.kps_score_lowres.weight"
+
+
+def pack_keypoint_deconv(w, b):
+    """ConvTranspose2d(Cin, K, kernel 4, stride 2, padding 1) as ONE 3x3, pad-1 convolution with 4 * K outputs followed by a pixel shuffle:
+        out[2y + py][2x + px][k] = sum over dy, dx in -1..1 of in[y + dy][x + dx][:] . W[:, k, py + 1 - 2 dy, px + 1 - 2 dx]     (kernel index outside 0..3: no tap)
+    w [Cin][K][4][4] as ConvTranspose2d stores it, b [K] -> (KRSC weights [(2 py + px) * K + k][dy + 1][dx + 1][cin], the bias repeated four times)."""
+    w = np.asarray(w, np.float32)
+    cin, K = w.shape[:2]
+    assert w.shape[2:] == (4, 4), w.shape
+    w3 = np.zeros((4 * K, 3, 3, cin), np.float32)
+    for py in (0, 1):
+        for px in (0, 1):
+            o = (2 * py + px) * K
+            for dy in (-1, 0, 1):
+                ky = py + 1 - 2 * dy
+                for dx in (-1, 0, 1):
+                    kx = px + 1 - 2 * dx
+                    if 0 <= ky <= 3 and 0 <= kx <= 3:
+                        w3[o:o + K, dy + 1, dx + 1, :] = w[:, :, ky, kx].T
+    return w3, np.tile(np.asarray(b, np.float32), 4)
+
+
 class BoxList:
     """Minimal structures/bounding_box.BoxList (M13): xyxy boxes, size=(w,h), named fields."""
 
@@ -219,6 +246,8 @@ class BoxList:
         r = np.array([rw, rh, rw, rh], np.float32)
         b = BoxList(self.bbox * r, size, self.mode)
         for k, v in self.extra_fields.items():
+            if k == "keypoints":   # PersonKeypoints.resize: x and y by the ratios (one fp32 multiplication each), v untouched
+                v = np.asarray(v, np.float32) * np.array([rw, rh, 1.0], np.float32)
             b.add_field(k, v)
         return b
 
@@ -250,9 +279,17 @@ class MaskRCNN:
                 gn_groups(ch, cfg.GN_NUM_GROUPS, cfg.GN_DIM_PER_GP, layer)
         if not 2 <= int(cfg.NUM_CLASSES) <= 257:
             raise ValueError("MODEL.ROI_BOX_HEAD.NUM_CLASSES=%s: the box post-processing kernels hold 2..257 classes (background included)" % (cfg.NUM_CLASSES,))
+        if cfg.KEYPOINT_ON:   # what the keypoint head is built next to
+            for bad, why in ((fp16, "fp16=True: the keypoint head is fp32 only"), (cfg.is_c4, "the C4 body (CONV_BODY %s): the keypoint head reads P2..P5" % cfg.CONV_BODY),
+                             (cfg.USE_GN, "GroupNorm (USE_GN): the keypoint head is built on the FrozenBN bodies"),
+                             (cfg.MASK_ON, "MASK_ON True: a model with both heads is not built, set MODEL.MASK_ON: False")):
+                if bad:
+                    raise ValueError("KEYPOINT_ON (MODEL.KEYPOINT_ON) together with " + why)
         self.cfg, self.H, self.W, self.max_batch = cfg, H, W, max_batch
         self._mask_head_in(state_dict)   # before the engine exists: MASK_ON True with a mask-less dict is refused here
+        self._keypoint_head_in(state_dict)
         self.mask_on = bool(cfg.MASK_ON)
+        self.keypoint_on = bool(cfg.KEYPOINT_ON)   # MODEL.KEYPOINT_ON: __call__ adds keypoints / keypoint_logits, results leave through pack_keypoint_records
         self._ratios = None
         self.mask_buf = "det.mask14" if cfg.is_c4 else "det.mask28"
         _ffi.lib()
@@ -262,7 +299,8 @@ class MaskRCNN:
         self.fp16 = bool(fp16)
         if self.fp16:  # fp16 storage + f16 MFMA convs (BASELINE configs[4]); must precede weight loading
             self.set_param("fp16", 1.0)
-        for k, v in (("mask_on", self.mask_on), ("num_classes", cfg.NUM_CLASSES), ("cls_agnostic", bool(cfg.CLS_AGNOSTIC_BBOX_REG))):
+        for k, v in (("mask_on", self.mask_on), ("num_classes", cfg.NUM_CLASSES), ("cls_agnostic", bool(cfg.CLS_AGNOSTIC_BBOX_REG)),
+                     ("keypoint_on", self.keypoint_on), ("num_keypoints", cfg.NUM_KEYPOINTS)):
             self.set_param(k, float(v))
         if cfg.is_c4:
             self.set_param("arch_c4", 1.0)
@@ -271,6 +309,8 @@ class MaskRCNN:
             self._load_gn(state_dict)
         else:
             self._load(state_dict)
+        if self.keypoint_on:
+            self._set_keypoint_head(state_dict)
         self.set_param("stride_in_1x1", float(bool(cfg.STRIDE_IN_1X1)))
         for k, v in (("resnet_depth", cfg.depth), ("rpn_pre_nms_top_n", cfg.RPN_PRE_NMS_TOP_N_TEST),
                      ("rpn_post_nms_top_n", cfg.RPN_POST_NMS_TOP_N_TEST), ("rpn_fpn_post_nms_top_n", cfg.RPN_FPN_POST_NMS_TOP_N_TEST),
@@ -315,6 +355,36 @@ class MaskRCNN:
             raise ValueError("MODEL.MASK_ON is True but the state dict has no roi_heads.mask.* weights: a Faster R-CNN checkpoint needs MODEL.MASK_ON: False")
         self.has_mask_head = bool(self.cfg.MASK_ON) and has
         return self.has_mask_head
+
+    def _keypoint_head_in(self, sd):
+        """KEYPOINT_ON and the state dict must agree about the keypoint head: either side without the other raises ValueError naming the key."""
+        has = [k for k in sd if k.startswith("roi_heads.keypoint.")]
+        if self.cfg.KEYPOINT_ON and KEYPOINT_LOWRES_KEY not in sd:
+            raise ValueError("MODEL.KEYPOINT_ON is True but the state dict has no %s: a Faster R-CNN checkpoint needs MODEL.KEYPOINT_ON: False" % KEYPOINT_LOWRES_KEY)
+        if not self.cfg.KEYPOINT_ON and has:
+            raise ValueError("the state dict has keypoint head weights (%s) but MODEL.KEYPOINT_ON is False: a Keypoint R-CNN checkpoint needs "
+                             "MODEL.KEYPOINT_ON: True" % has[0])
+
+    def _set_keypoint_head(self, sd):
+        """[UPSTREAM-RECALL] KeypointRCNNFeatureExtractor conv_fcn1.. (3x3, bias, ReLU) and KeypointRCNNPredictor kps_score_lowres, the transposed convolution
+        packed as one 3x3 layer (pack_keypoint_deconv)."""
+        cfg = self.cfg
+        fx, cin = "roi_heads.keypoint.feature_extractor.conv_fcn", 256
+        for i, cout in enumerate(cfg.KEYPOINT_CONV_LAYERS, 1):
+            if "%s%d.weight" % (fx, i) not in sd:
+                raise ValueError("%s%d.weight is missing: MODEL.ROI_KEYPOINT_HEAD.CONV_LAYERS names %d layers" % (fx, i, len(cfg.KEYPOINT_CONV_LAYERS)))
+            w = sd["%s%d.weight" % (fx, i)]
+            if w.shape != (cout, cin, 3, 3):
+                raise ValueError("%s%d.weight %s: MODEL.ROI_KEYPOINT_HEAD.CONV_LAYERS asks for %s" % (fx, i, w.shape, (cout, cin, 3, 3)))
+            self._set_conv_krsc("%s%d" % (fx, i), to_krsc(w), None, sd["%s%d.bias" % (fx, i)])
+            cin = cout
+        if "%s%d.weight" % (fx, len(cfg.KEYPOINT_CONV_LAYERS) + 1) in sd:
+            raise ValueError("%s%d.weight: more layers than MODEL.ROI_KEYPOINT_HEAD.CONV_LAYERS names (%d)" % (fx, len(cfg.KEYPOINT_CONV_LAYERS) + 1, len(cfg.KEYPOINT_CONV_LAYERS)))
+        wd = sd[KEYPOINT_LOWRES_KEY]
+        if wd.shape != (cin, cfg.NUM_KEYPOINTS, 4, 4):
+            raise ValueError("%s %s: expected (%d, MODEL.ROI_KEYPOINT_HEAD.NUM_CLASSES = %d, 4, 4)" % (KEYPOINT_LOWRES_KEY, wd.shape, cin, cfg.NUM_KEYPOINTS))
+        w3, b4 = pack_keypoint_deconv(wd, sd["roi_heads.keypoint.predictor.kps_score_lowres.bias"])
+        self._set_conv_krsc("roi_heads.keypoint.predictor.kps_score_lowres", w3, None, b4)
 
     def _set_box_predictor(self, sd, cin):
         """cls_score | bbox_pred as ONE 1x1 layer: NUM_CLASSES logits, then 4 * NUM_CLASSES deltas, or 8 with CLS_AGNOSTIC_BBOX_REG."""
@@ -597,6 +667,15 @@ class MaskRCNN:
         _ffi.check(_ffi.lib().isegmi_engine_pack_box_records(self._h, r.ctypes.data_as(C.c_void_p), dev_buffer.ptr, C.c_int64(dev_buffer.nbytes), int(n_block), C.byref(nb)))
         return nb.value
 
+    def pack_keypoint_records(self, dev_buffer, n_block):
+        """isegmi_engine_pack_keypoint_records: the box-only block plus kpt / kscore (isegmi.dist.coco_record_layout(..., box_only=True, keypoints=NK)),
+        boxes and keypoints in the coordinates set_output_sizes named.  -> bytes written."""
+        n = self._hw.shape[0]
+        r = self._ratios if self._ratios is not None and self._ratios.shape[0] == n else np.ones((n, 2), np.float32)
+        nb = C.c_int64()
+        _ffi.check(_ffi.lib().isegmi_engine_pack_keypoint_records(self._h, r.ctypes.data_as(C.c_void_p), dev_buffer.ptr, C.c_int64(dev_buffer.nbytes), int(n_block), C.byref(nb)))
+        return nb.value
+
     def sync(self):
         _ffi.check(_ffi.lib().isegmi_engine_sync(self._h))
 
@@ -605,7 +684,7 @@ class MaskRCNN:
 
     def __call__(self, batch_nhwc3, image_hw=None):
         """-> list of BoxList (one per image, in network-input coordinates) with scores, labels, mask [n,1,28,28]
-        (14x14 for the C4 predictor; no mask field from a box-only engine).  With image_hw = None the first argument is a list of already-resized uint8 BGR images and goes
+        (14x14 for the C4 predictor; no mask field from a box-only engine; a keypoint engine adds keypoints [n,17,3] and keypoint_logits [n,17]).  With image_hw = None the first argument is a list of already-resized uint8 BGR images and goes
         through the device front end (upload_u8: mean subtraction and padding on the GPU)."""
         n = self.upload_u8(batch_nhwc3) if image_hw is None else self.upload(batch_nhwc3, image_hw)
         self.forward_device(n)
@@ -613,6 +692,7 @@ class MaskRCNN:
         cnt = self.fetch("det.count", n)
         box, score, label = (self.fetch(k, n) for k in ("det.box", "det.score", "det.label"))
         m28 = self.fetch(self.mask_buf, n) if self.mask_on else None
+        kpt, kscore = (self.fetch("det.kpt", n), self.fetch("det.kscore", n)) if self.keypoint_on else (None, None)
         out = []
         for i in range(n):
             c = int(cnt[i])
@@ -620,6 +700,8 @@ class MaskRCNN:
             bl.add_field("scores", score[i, :c]); bl.add_field("labels", label[i, :c].astype(np.int64))
             if m28 is not None:
                 bl.add_field("mask", m28[i, :c, None])
+            if kpt is not None:
+                bl.add_field("keypoints", kpt[i, :c]); bl.add_field("keypoint_logits", kscore[i, :c])
             out.append(bl)
         return out
 

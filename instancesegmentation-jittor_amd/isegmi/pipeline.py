@@ -19,8 +19,9 @@ class RecordPipeline:
         self.K = int(net.cfg.max_num_detections if self.kind == 1 else net.cfg.det_cap)
         self.has_mscore = bool(self.kind == 1 and getattr(net, "has_maskiou", False))
         self.box_only = bool(getattr(net, "box_only", False))   # Faster R-CNN: the box-only block -- no strings, no RLE capacities, no mask planes
+        self.keypoints = int(net.cfg.NUM_KEYPOINTS) if getattr(net, "keypoint_on", False) else 0   # Keypoint R-CNN: kpt / kscore sections behind the box-only block
         self.nbytes, self.chars_off = net.coco_record_bytes(self.batch)
-        secs, coff, _ = coco_record_layout(self.batch, self.K, self.kind, self.has_mscore, 0, self.box_only)
+        secs, coff, _ = coco_record_layout(self.batch, self.K, self.kind, self.has_mscore, 0, self.box_only, self.keypoints)
         assert coff == self.chars_off, (coff, self.chars_off)
         self.cap_chars = self.nbytes - self.chars_off
         if gather is None:
@@ -44,7 +45,9 @@ class RecordPipeline:
     def _emit(self, slot):
         if self.gather is None:
             self.net.download_fence(slot)        # the slot's previous download has left the device buffer
-            if self.box_only:
+            if self.keypoints:
+                self.net.pack_keypoint_records(self.dev[slot], self.batch)
+            elif self.box_only:
                 self.net.pack_box_records(self.dev[slot], self.batch)
             else:
                 self.net.pack_coco_records(self.dev[slot], self.batch)
@@ -62,7 +65,8 @@ class RecordPipeline:
         return [self._unpack(blocks[r]) for r in range(self.gather.world)]
 
     def _unpack(self, buf):
-        r = unpack_coco_records(buf, self.batch, self.K, self.kind, self.has_mscore, self.cap_chars, strict=self.strict, box_only=self.box_only)
+        r = unpack_coco_records(buf, self.batch, self.K, self.kind, self.has_mscore, self.cap_chars, strict=self.strict, box_only=self.box_only,
+                                keypoints=self.keypoints)
         return {k: (np.array(v) if isinstance(v, np.ndarray) else v) for k, v in r.items()}  # copies: the pinned slot is reused two steps later
 
     def submit(self, meta=None):

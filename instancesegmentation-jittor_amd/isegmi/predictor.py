@@ -22,17 +22,18 @@ class COCODemo:
                  fp16=False):
         from .retinanet import RetinaNetConfig
         if cfg is not None and not isinstance(cfg, (MaskRCNNConfig, RetinaNetConfig)):   # the yacs-shaped node of isegmi.config (README.md:313-324)
-            from .config import is_retinanet, to_maskrcnn_config, to_retinanet_config
+            from .config import is_keypoint_rcnn, is_retinanet, to_keypointrcnn_config, to_maskrcnn_config, to_retinanet_config
             retina = is_retinanet(cfg)
+            to_two_stage = to_keypointrcnn_config if is_keypoint_rcnn(cfg) else to_maskrcnn_config   # MODEL.KEYPOINT_ON
             if state_dict is None and getattr(cfg.MODEL, "WEIGHT", ""):
                 w = cfg.MODEL.WEIGHT
                 from .weights import random_maskrcnn_state_dict, retinanet_state_dict
                 body = cfg.MODEL.BACKBONE.CONV_BODY
                 depth = 101 if "101" in body else 50
                 # MODEL.WEIGHT random: the seeded generator of the configured model (body, norm, MASK_ON, NUM_CLASSES, CLS_AGNOSTIC_BBOX_REG)
-                rnd = (lambda: retinanet_state_dict(1234, depth)) if retina else (lambda: random_maskrcnn_state_dict(to_maskrcnn_config(cfg), 1234))
+                rnd = (lambda: retinanet_state_dict(1234, depth)) if retina else (lambda: random_maskrcnn_state_dict(to_two_stage(cfg), 1234))
                 state_dict = rnd() if w == "random" else dict(np.load(w))
-            cfg = to_retinanet_config(cfg) if retina else to_maskrcnn_config(cfg)
+            cfg = to_retinanet_config(cfg) if retina else to_two_stage(cfg)
         self.cfg = cfg or MaskRCNNConfig()
         self.is_retinanet = isinstance(self.cfg, RetinaNetConfig)   # MODEL.RETINANET_ON: boxes, scores and labels; no masks
         self.box_only = not self.is_retinanet and not self.cfg.MASK_ON   # MODEL.MASK_ON False: Faster R-CNN, the same
@@ -67,7 +68,7 @@ class COCODemo:
 
     def compute_prediction(self, original_image):
         """-> BoxList in ORIGINAL image coordinates with scores, labels and mask [n,1,H,W] uint8 (Masker output); RetinaNet and Faster R-CNN
-        (MODEL.MASK_ON False): no mask field."""
+        (MODEL.MASK_ON False): no mask field.  Keypoint R-CNN (MODEL.KEYPOINT_ON): keypoints [n,17,3] in original-image coordinates and keypoint_logits [n,17]."""
         h, w = original_image.shape[:2]
         resized = maskrcnn_resize_u8(original_image, self.min_image_size, self.max_image_size)
         model = self.engine()
@@ -112,7 +113,22 @@ class COCODemo:
             y1, y2 = max(0, min(H - 1, y1)), max(0, min(H - 1, y2))
             image[y1:y2 + 1, [x1, x2]] = colors[k]
             image[[y1, y2], x1:x2 + 1] = colors[k]
+        if predictions.has_field("keypoints"):
+            self.overlay_keypoints(image, predictions)
         return self.overlay_class_names(image, predictions)
+
+    KP_THRESH = 2.0   # [UPSTREAM-RECALL] demo/predictor.py vis_keypoints: kp_thresh
+
+    def overlay_keypoints(self, image, predictions):
+        """A 5 x 5 dot, coloured by keypoint index (one colour per joint, the same in every detection), for every keypoint whose logit exceeds KP_THRESH (upstream also draws the skeleton's limbs)."""
+        H, W = image.shape[:2]
+        kps, logits = predictions.get_field("keypoints"), predictions.get_field("keypoint_logits")
+        colors = self.compute_colors_for_labels(np.arange(1, kps.shape[1] + 1))
+        for k in range(len(predictions)):
+            for j in np.nonzero(logits[k] > self.KP_THRESH)[0]:
+                x, y = int(kps[k, j, 0]), int(kps[k, j, 1])
+                image[max(0, y - 2):min(H, y + 3), max(0, x - 2):min(W, x + 3)] = colors[j]
+        return image
 
     def overlay_class_names(self, image, predictions):
         """demo/predictor.py overlay_class_names: "<class name>: <score>" in white at the top-left corner of every box (README.md:331-334:

@@ -367,9 +367,33 @@ def maskrcnn_c4_state_dict(seed=1234, mask=True, num_classes=81, cls_agnostic=Fa
     return sd if mask else _drop_mask_head(sd)
 
 
+KEYPOINT_SEED_OFFSET = 7919   # the head's own generator: seed + this, so the trunk's tensors equal maskrcnn_state_dict's of the same seed
+
+
+def keypointrcnn_state_dict(seed=1234, depth=50, conv_layers=(512,) * 8, num_keypoints=17):
+    """[UPSTREAM-RECALL] maskrcnn-benchmark e2e_keypoint_rcnn_R_50/101_FPN state-dict names: the two-class box-only model
+    (maskrcnn_state_dict(seed, depth, mask=False, num_classes=2), tensor for tensor) plus roi_heads.keypoint.feature_extractor.conv_fcn{1..}.{weight,bias}
+    (3x3, 256 -> 512 -> ... -> 512) and roi_heads.keypoint.predictor.kps_score_lowres.{weight,bias}, the weight [512][17][4][4] as ConvTranspose2d stores it.
+    The head is drawn from a generator of its own."""
+    sd = maskrcnn_state_dict(seed, depth, mask=False, num_classes=2)
+    rng = np.random.default_rng(seed + KEYPOINT_SEED_OFFSET)
+    cin = 256
+    for i, cout in enumerate(conv_layers, 1):
+        _conv_bias(rng, sd, "roi_heads.keypoint.feature_extractor.conv_fcn%d" % i, int(cout), cin, 3)
+        cin = int(cout)
+    # He initialisation: a transposed convolution's output pixel sums 4 live taps x cin inputs
+    sd["roi_heads.keypoint.predictor.kps_score_lowres.weight"] = (rng.standard_normal((cin, num_keypoints, 4, 4)) * np.sqrt(2.0 / (4 * cin))).astype(np.float32)
+    sd["roi_heads.keypoint.predictor.kps_score_lowres.bias"] = (rng.standard_normal(num_keypoints) * 0.01).astype(np.float32)
+    return sd
+
+
 def random_maskrcnn_state_dict(cfg, seed=1234):
     """The seeded weights of `MODEL.WEIGHT random` for a MaskRCNNConfig: the generator of its body / norm, sized by MASK_ON, NUM_CLASSES and
     CLS_AGNOSTIC_BBOX_REG."""
+    if getattr(cfg, "KEYPOINT_ON", False):   # Keypoint R-CNN (DESIGN.md 14): the two-class box-only trunk plus the keypoint head
+        if int(cfg.NUM_CLASSES) != 2 or cfg.CLS_AGNOSTIC_BBOX_REG:
+            raise ValueError("MODEL.KEYPOINT_ON: the seeded generator draws the upstream model, MODEL.ROI_BOX_HEAD.NUM_CLASSES 2 with per-class regression")
+        return keypointrcnn_state_dict(seed, cfg.depth, cfg.KEYPOINT_CONV_LAYERS, cfg.NUM_KEYPOINTS)
     kw = dict(mask=bool(cfg.MASK_ON), num_classes=int(cfg.NUM_CLASSES), cls_agnostic=bool(cfg.CLS_AGNOSTIC_BBOX_REG))
     if cfg.is_c4:
         return maskrcnn_c4_state_dict(seed, **kw)

@@ -3,7 +3,8 @@ upstream key names isegmi.yolact.Yolact / isegmi.maskrcnn.MaskRCNN consume.
 
     python tools/import_pth.py IN OUT.npz [--family maskrcnn_r50_fpn|maskrcnn_r101_fpn|maskrcnn_r50_c4|maskrcnn_r50_fpn_gn|yolact_resnet50|yolact_base|
                                                     yolact_im700|yolact_darknet53|yolact_plus_resnet50|yolact_plus_base|retinanet_r50_fpn|retinanet_r101_fpn|
-                                                    fasterrcnn_r50_fpn|fasterrcnn_r101_fpn|fasterrcnn_r50_c4|fasterrcnn_r50_fpn_gn]
+                                                    fasterrcnn_r50_fpn|fasterrcnn_r101_fpn|fasterrcnn_r50_c4|fasterrcnn_r50_fpn_gn|
+                                                    keypointrcnn_r50_fpn|keypointrcnn_r101_fpn]
 
 Accepted inputs (torch is used HERE only to unpickle -- a tool, not the product):
   * dbolya/yolact `.pth` (the tables at README.md:209-221): a flat state dict; `module.` prefixes, `num_batches_tracked`, the
@@ -33,7 +34,8 @@ sys.path[:0] = [os.path.join(ROOT, "instancesegmentation-jittor_amd")]
 
 FAMILIES = ("maskrcnn_r50_fpn", "maskrcnn_r101_fpn", "maskrcnn_r50_c4", "maskrcnn_r50_fpn_gn", "yolact_resnet50", "yolact_base", "yolact_im700",
             "yolact_darknet53", "yolact_plus_resnet50", "yolact_plus_base", "retinanet_r50_fpn", "retinanet_r101_fpn",
-            "fasterrcnn_r50_fpn", "fasterrcnn_r101_fpn", "fasterrcnn_r50_c4", "fasterrcnn_r50_fpn_gn")
+            "fasterrcnn_r50_fpn", "fasterrcnn_r101_fpn", "fasterrcnn_r50_c4", "fasterrcnn_r50_fpn_gn",
+            "keypointrcnn_r50_fpn", "keypointrcnn_r101_fpn")
 
 
 def expected_keys(family):
@@ -45,6 +47,9 @@ def expected_keys(family):
         sd = {"fasterrcnn_r50_fpn": lambda: W.maskrcnn_state_dict(0, 50, mask=False), "fasterrcnn_r101_fpn": lambda: W.maskrcnn_state_dict(0, 101, mask=False),
               "fasterrcnn_r50_c4": lambda: W.maskrcnn_c4_state_dict(0, mask=False),
               "fasterrcnn_r50_fpn_gn": lambda: W.maskrcnn_state_dict(0, 50, gn=True, mask=False)}[family]()
+    elif family.startswith("keypointrcnn_"):
+        # [UPSTREAM-RECALL] e2e_keypoint_rcnn_R_50/101_FPN_1x: the two-class box-only key set plus roi_heads.keypoint.* 
+        sd = W.keypointrcnn_state_dict(0, 101 if "101" in family else 50)
     elif family == "maskrcnn_r50_fpn":
         sd = W.maskrcnn_state_dict(0, 50)
     elif family == "maskrcnn_r101_fpn":
@@ -125,6 +130,9 @@ def convert(sd, family=None, allow_partial=False):
         flat[k[7:] if k.startswith("module.") else k] = _to_numpy(v)
     out = {}
     if is_caffe2(set(flat)):
+        if family is not None and family.startswith("keypointrcnn"):
+            raise ValueError("a Detectron / Caffe2 checkpoint cannot be imported as %s: the name mapping does not cover the keypoint head's blobs (conv_fcn*, "
+                             "kps_score_lowres); convert it to a maskrcnn-benchmark .pth first" % family)
         if family is None or not family.startswith(("maskrcnn", "fasterrcnn")):
             raise ValueError("a Detectron / Caffe2 checkpoint needs --family maskrcnn_* or fasterrcnn_*")
         exp = expected_keys(family)
