@@ -261,6 +261,18 @@ typedef struct isegmi_yolact_detect_args {
 } isegmi_yolact_detect_args;
 int isegmi_op_yolact_detect(const isegmi_yolact_detect_args* a, void* stream);
 
+/* ---- Yolact mask coefficients of selected priors (the engines' `lazy_coeffs`: the forward runs the loc | conf rows of the fused prediction head
+ * only, and the 32 coefficients of the <= max_det kept detections per image are computed after the final top-k) ----
+ * d_feats[l] (l < nlevels <= 5; a HOST array of device pointers): the head's input map of level l, [N][Hs[l]][Ws[l]][Cin] fp32.  d_wpacked / d_scale /
+ * d_shift: a packed stride-1 R x S fp32 layer (isegmi_pack_conv_weights) with at least row0 + 32 A output channels.  d_rows [N][max_det][5] int32:
+ * slot (n, q) = (image, level, ho, wo, anchor); d_count [N]: valid slots of image n.  d_out [N][max_det][32]: for slot (n, q), q < count[n],
+ * out[j] = the layer's output channel row0 + 32 anchor + j at pixel (ho, wo) of that image and level, with act 0 -- bit for bit what isegmi_op_conv2d
+ * stores there (the same k-ordered fmaf chain and epilogue), pre-tanh.  Slots past the count, and slots whose row is out of range (a negative level
+ * marks one), are NOT written. */
+int isegmi_op_yolact_coeff_rows(int nlevels, const float* const* d_feats, const int32_t* Hs, const int32_t* Ws, int N, int Cin, int R, int S,
+                                int pad, const float* d_wpacked, const float* d_scale, const float* d_shift, int A, int row0,
+                                const int32_t* d_rows, const int32_t* d_count, int max_det, float* d_out, void* stream);
+
 /* ---- Yolact postprocess masks (Y7; App. A.9) ----
  * d_proto [N][PH][PW][32]; d_coeffs [N][K][32]; d_boxes [N][K][4] relative; d_count [N].
  * d_ws_lo [N][K][PH][PW] fp32 workspace (holds the crop windows' pixels of the proto-resolution masks afterwards, the rest is

@@ -20,6 +20,7 @@
 #include <type_traits>
 #include "../../include/isegmi.h"
 #include "common.h"
+#include "conv_korder.h"
 #include "detmath.h"
 
 #ifndef CONV_F32_RES_AUX  // cache policy of the residual loads (0 default, 2 = nt); see conv_mfma_f16.hip
@@ -62,7 +63,6 @@ __device__ __forceinline__ void conv_tile_of(const ConvK& p, const int logical, 
 }
 
 constexpr int LDS_ROW = 36;
-constexpr int CONV_KGROUP_CHUNKS = 4;  // 128 input channels per K group (ORA_CONV_CGROUP in the oracle)
 
 
 
@@ -224,19 +224,11 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvK p) {
         }
 #pragma unroll
         for (int j = 0; j < BPASS; ++j) {
-            const float* src = wsrc + (int64_t)(64 * j) * p.wrow + (STEM ? chunk : (kr * p.S + ks) * p.cin_chunks + kg + kc) * 32;
+            const float* src = wsrc + (int64_t)(64 * j) * p.wrow + (STEM ? chunk : conv_k_wchunk(kr, ks, kc, kg, p.S, p.cin_chunks)) * 32;
             rb[j][0] = *(const u32x4*)src;
             rb[j][1] = *(const u32x4*)(src + 4);
         }
-        if (!STEM) {
-            if (++kc == glen) {
-                kc = 0;
-                if (++ks == p.S) {
-                    ks = 0;
-                    if (++kr == p.R) { kr = 0; kg += glen; glen = min(p.kgroup, p.cin_chunks - kg); if (glen <= 0) { glen = 1; kg = 0; } }
-                }
-            }
-        }
+        if (!STEM) (void)conv_k_next(kr, ks, kc, kg, glen, p.R, p.S, p.kgroup, p.cin_chunks);
     };
     auto store_chunk = [&](int stage) {
         float* As = smem + stage * STAGE;
@@ -401,19 +393,14 @@ __device__ __forceinline__ void conv_v2_body(const ConvK& p, float* smem, const 
     auto load_chunk = [&](int slot) {
         const bool live = chunk < p.nchunks;
         const u32x4 rsa = live ? rs_in : rs_null, rsb = live ? rs_w : rs_null;  // scalar selects
-        const unsigned soffb = (unsigned)((kr * p.S + ks) * p.cin_chunks + kg + kc) * 128u;   // scalar: the chunk's place in the (r, s, cin) packed weight row
+        const unsigned soffb = (unsigned)conv_k_wchunk(kr, ks, kc, kg, p.S, p.cin_chunks) * 128u;   // scalar: the chunk's place in the (r, s, cin) packed weight row
         asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(ra[slot][0]) : "v"(avoff), "s"(rsa), "s"(soffa) : "memory");
         asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:16" : "=v"(ra[slot][1]) : "v"(avoff), "s"(rsa), "s"(soffa) : "memory");
         asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(rb[slot][0]) : "v"(wbase), "s"(rsb), "s"(soffb) : "memory");
         asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:16" : "=v"(rb[slot][1]) : "v"(wbase), "s"(rsb), "s"(soffb) : "memory");
         ++chunk;
         soffa += 128u;
-        if (++kc == glen) {  // uniform: next tap (of this channel group, or the first of the next group) -- the only place with per-lane work
-            kc = 0;
-            if (++ks == p.S) {
-                ks = 0;
-                if (++kr == p.R) { kr = 0; kg += glen; glen = min(p.kgroup, p.cin_chunks - kg); if (glen <= 0) { glen = 1; kg = 0; } }  // past the end: loads are dead
-            }
+        if (conv_k_next(kr, ks, kc, kg, glen, p.R, p.S, p.kgroup, p.cin_chunks)) {  // uniform: next tap (of this channel group, or the first of the next group) -- the only place with per-lane work
             soffa = (unsigned)kg * 128u;
             int tr = __builtin_amdgcn_readfirstlane(kr), ts = __builtin_amdgcn_readfirstlane(ks);
             asm volatile("" : "+s"(tr), "+s"(ts));  // keeps the tap change behind its branch: speculated, its VALU work would run every chunk
@@ -643,7 +630,7 @@ __device__ __forceinline__ void conv_mfma16_body(const ConvK& p, float* smem16, 
     auto load_chunk = [&](int slot) {
         const bool live = chunk < c_end && !EXPERIMENT_NO_LOADS;
         const u32x4 rsa = live ? rs_in : rs_null, rsb = live ? rs_w : rs_null;
-        const unsigned soffb = (unsigned)((kr * p.S + ks) * p.cin_chunks + kg + kc) * 128u;
+        const unsigned soffb = (unsigned)conv_k_wchunk(kr, ks, kc, kg, p.S, p.cin_chunks) * 128u;
         asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(ra[slot]) : "v"(avoff), "s"(rsa), "s"(soffa) : "memory");
 #pragma unroll
         for (int t = 0; t < WN; ++t) {  // weight rows lrow and lrow + 32
@@ -652,12 +639,7 @@ __device__ __forceinline__ void conv_mfma16_body(const ConvK& p, float* smem16, 
         }
         ++chunk;
         soffa += 128u;
-        if (++kc == glen) {  // uniform: next tap (of this channel group, or the first of the next group)
-            kc = 0;
-            if (++ks == p.S) {
-                ks = 0;
-                if (++kr == p.R) { kr = 0; kg += glen; glen = min(p.kgroup, p.cin_chunks - kg); if (glen <= 0) { glen = 1; kg = 0; } }
-            }
+        if (conv_k_next(kr, ks, kc, kg, glen, p.R, p.S, p.kgroup, p.cin_chunks)) {  // uniform: next tap (of this channel group, or the first of the next group)
             soffa = (unsigned)kg * 128u;
             int tr = __builtin_amdgcn_readfirstlane(kr), ts = __builtin_amdgcn_readfirstlane(ks);
             asm volatile("" : "+s"(tr), "+s"(ts));  // keeps the tap change behind its branch: speculated, its VALU work would run every chunk
@@ -933,7 +915,6 @@ __global__ __launch_bounds__(256, 4) void conv_group_kernel(const ConvGroupK g) 
     else conv_mfma16_body<4, false, 1>(g.k[i], smem, bid, nwg);
 }
 
-static inline int perm8(int e) { return 4 * (e & 1) + (e >> 1); }
 static bool is_stem(const isegmi_conv_desc* d) { return d->Cin == 4 && d->R == 7 && d->S == 7; }
 static int cout_pad(const isegmi_conv_desc* d) { return cdiv(d->Cout, 128) * 128; }
 static int n_chunks(const isegmi_conv_desc* d) { return is_stem(d) ? 7 : d->R * d->S * (d->Cin / 32); }
@@ -1032,7 +1013,7 @@ static int conv_fill(const isegmi_conv_desc* d, const float* in, const float* w,
     // the mask head) and res5's 3x3s 26x; with 128-channel groups the window of one group stays in L2 for its nine taps: 10.2 -> 8.5 GB fetched
     // + written per Yolact step (1.51x -> 1.26x algorithmic), 9.8 -> 8.6 GB Mask R-CNN (profiles/r03_conv_traffic_*.txt).  Groups of 32 or 64
     // channels fetch no less (1.22-1.27x) and pay for twice / four times the tap changes (+0.7 % / +1.8 % conv time; 128: +0.1-0.9 %).
-    k.kgroup = (d->R * d->S == 1 || is_stem(d)) ? k.cin_chunks : (k.cin_chunks < CONV_KGROUP_CHUNKS ? k.cin_chunks : CONV_KGROUP_CHUNKS);
+    k.kgroup = conv_kgroup(d->R, d->S, k.cin_chunks, is_stem(d));
     k.wrow = (int64_t)k.nchunks * 32;
     const int64_t in_bytes = (int64_t)d->N * d->H * d->W * d->Cin * 4;
     ARG_CHECK(in_bytes < (1ll << 31), "conv input must be < 2 GiB (32-bit buffer offsets)");
@@ -1287,11 +1268,11 @@ extern "C" int isegmi_pack_conv_weights(const isegmi_conv_desc* d, const float* 
         if (is_stem(d)) {
             for (int r = 0; r < 7; ++r)
                 for (int e = 0; e < 28; ++e) {  // e = s*4 + c
-                    const int grp = e >> 3, pos = perm8(e & 7);
+                    const int grp = e >> 3, pos = conv_perm8(e & 7);
                     dst[r * 32 + grp * 8 + pos] = src[r * 28 + e];
                 }
         } else {
-            for (int k = 0; k < K; ++k) dst[(k & ~7) + perm8(k & 7)] = src[k];
+            for (int k = 0; k < K; ++k) dst[(k & ~7) + conv_perm8(k & 7)] = src[k];
         }
     }
     return ISEGMI_OK;

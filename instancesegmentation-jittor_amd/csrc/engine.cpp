@@ -813,7 +813,10 @@ extern "C" int isegmi_engine_destroy(isegmi_engine* h) {
     for (int i = 0; i < Engine::PIN_SLOTS; ++i) if (e.pin_ev[i]) (void)hipEventDestroy(e.pin_ev[i]);
     if (e.pin_ring) (void)hipHostFree(e.pin_ring);
     for (auto& ev : e.step_marks) (void)hipEventDestroy(ev);
-    for (auto& kv : e.convs) { (void)hipFree(kv.second.d_w); if (kv.second.d_scale) (void)hipFree(kv.second.d_scale); if (kv.second.d_shift) (void)hipFree(kv.second.d_shift); }
+    for (auto& kv : e.convs) {
+        if (kv.second.view) continue;
+        (void)hipFree(kv.second.d_w); if (kv.second.d_scale) (void)hipFree(kv.second.d_scale); if (kv.second.d_shift) (void)hipFree(kv.second.d_shift);
+    }
     for (auto& kv : e.tensors) (void)hipFree(kv.second.d);
     for (auto& kv : e.bufs) (void)hipFree(kv.second.d);
     for (auto& ev : e.ev_pool) (void)hipEventDestroy(ev);
@@ -846,6 +849,7 @@ extern "C" int isegmi_engine_graph_stats(isegmi_engine* h, int64_t* captures, in
 extern "C" int isegmi_engine_set_conv(isegmi_engine* h, const char* name, int Cout, int R, int S, int Cin, const float* h_w_krsc,
                                       const float* h_scale, const float* h_shift) {
     ARG_CHECK(h && name && h_w_krsc, "null");
+    ARG_CHECK(strchr(name, '[') == nullptr, "set_conv: '[' in a layer name (row-range views are the engine's)");
     isegmi_conv_desc d;
     memset(&d, 0, sizeof(d));
     d.N = 1; d.H = R; d.W = S; d.Cin = Cin; d.Cout = Cout; d.R = R; d.S = S; d.stride = 1; d.pad = 0;
@@ -873,6 +877,7 @@ extern "C" int isegmi_engine_set_conv(isegmi_engine* h, const char* name, int Co
     }
     if (h_scale) { HIP_TRY(hipMalloc((void**)&L.d_scale, (size_t)Cout * 4)); HIP_TRY(hipMemcpy(L.d_scale, h_scale, (size_t)Cout * 4, hipMemcpyHostToDevice)); }
     if (h_shift) { HIP_TRY(hipMalloc((void**)&L.d_shift, (size_t)Cout * 4)); HIP_TRY(hipMemcpy(L.d_shift, h_shift, (size_t)Cout * 4, hipMemcpyHostToDevice)); }
+    if (h->e.kind == 1 && std::string(name) == kHeadCat) yolact_head_views(h->e);
     return ISEGMI_OK;
 }
 
@@ -913,7 +918,7 @@ extern "C" int isegmi_yolact_forward(isegmi_engine* h, const float* d_images_nhw
         rc = eng_graph_run(e, key, [&]() { return yolact_forward(e, d_images_nhwc3, N); });
     }
     e.lane = 0;
-    if (rc == ISEGMI_OK) e.last_N = N;
+    if (rc == ISEGMI_OK) { e.last_N = N; e.coeff_cols_valid = !yolact_lazy_coeffs(e, N); }   // (here, not in the graph body: a replay runs no host code)
     return rc;
 }
 
@@ -1052,6 +1057,8 @@ extern "C" int isegmi_engine_buffer_info(isegmi_engine* h, const char* name, voi
     ARG_CHECK(h && name, "null");
     auto it = h->e.bufs.find(name);
     if (it == h->e.bufs.end()) { set_error(std::string("no such buffer: ") + name); return ISEGMI_ERR_ARG; }
+    // lazy_coeffs: the last forward left headcat's coefficient columns unwritten; whoever asks for the buffer gets all of it
+    if (h->e.kind == 1 && !h->e.coeff_cols_valid && it->first == "headcat") TRY(yolact_fill_coeff_columns(h->e));
     const RawBuf& b = it->second;
     if (d_ptr) *d_ptr = b.d;
     if (bytes) *bytes = b.bytes;
@@ -1066,6 +1073,7 @@ extern "C" int isegmi_engine_memory(isegmi_engine* h, int64_t* weight_bytes, int
     int64_t wb = 0, bb = 0;
     for (auto& kv : h->e.convs) {
         const ConvLayer& L = kv.second;
+        if (L.view) continue;
         isegmi_conv_desc d;
         memset(&d, 0, sizeof(d));
         d.N = 1; d.H = L.R; d.W = L.S; d.Cin = L.Cin; d.Cout = L.Cout; d.R = L.R; d.S = L.S; d.stride = 1;

@@ -32,6 +32,7 @@ struct ConvLayer {
     bool f16 = false;
     float* d_scale = nullptr;  // may be null (=1)
     float* d_shift = nullptr;  // may be null (=0)
+    bool view = false;         // a row range of another layer: d_w / d_scale / d_shift point into ITS allocations (never freed, never counted)
 };
 
 struct RawBuf {
@@ -130,6 +131,9 @@ struct Engine {
     std::vector<float> last_ratios;
     const void* last_ratios_ptr = nullptr;
     int last_N = 0;
+    // Yolact fp32 "lazy_coeffs": the forward runs only the loc|conf rows of the fused head and computes the mask coefficients of the kept detections on
+    // the tail stream; columns [85 A, 117 A) of `headcat` then hold nothing until a fetch of that buffer asks for them (yolact_fill_coeff_columns).
+    bool coeff_cols_valid = true;
     // timing
     bool timing = false;
     std::vector<StageTime> marks;
@@ -289,6 +293,15 @@ int eng_gn(Engine& e, const std::string& layer, Tensor* x, const Tensor* residua
 
 int yolact_forward(Engine& e, const float* d_images, int N);
 int yolact_postprocess(Engine& e, int h, int w, const int32_t* h_image_hw = nullptr);
+// "lazy_coeffs" (yolact.cpp): the two row-range views of the fused head, whether a forward of N images takes the lazy schedule, and the fill of headcat's
+// coefficient columns on demand
+constexpr const char* kHeadCat = "prediction_layers.0.head_cat";
+constexpr const char* kHeadCatLocConf = "prediction_layers.0.head_cat[loc|conf]";
+constexpr const char* kHeadCatCoeff = "prediction_layers.0.head_cat[coeff]";
+constexpr int kYolactClasses = 81, kYolactMaskDim = 32;
+void yolact_head_views(Engine& e);
+bool yolact_lazy_coeffs(Engine& e, int N);
+int yolact_fill_coeff_columns(Engine& e);
 int maskrcnn_forward(Engine& e, const float* d_images, int N);
 int eng_next_event(Engine& e, hipEvent_t* ev);
 int maskrcnn_paste(Engine& e, const float* h_ratios_wh, int out_h, int out_w);
@@ -341,6 +354,16 @@ int preprocess_u8_launch(const uint8_t* in, int N, int Hin, int Win, float* out,
                          const float* mean3, const float* std3, int swap_rb, hipStream_t st);
 int pad_c3_c32_launch(const float* in, int64_t npix, float* out, hipStream_t st);
 int yolact_detect_launch(const isegmi_yolact_detect_args* a, hipStream_t st);
+// Detect in two halves: everything up to the final per-image top-k, then the gather.  coeff_sel (optional, [N][max_det][mask_dim] pre-tanh): the gather
+// takes slot (n, q)'s coefficients from there instead of from d_mask.
+int yolact_detect_select_launch(const isegmi_yolact_detect_args* a, hipStream_t st);
+int yolact_detect_gather_launch(const isegmi_yolact_detect_args* a, const float* coeff_sel, hipStream_t st);
+// yolact_coeff.hip: the coefficient rows of selected priors, bit-identical to the head convolution's outputs
+struct CoeffLevels { const float* feat[5]; int H[5], W[5]; int n = 0; };
+int yolact_coeff_index_launch(const int32_t* fin_idx, const int32_t* tk_idx, const int32_t* fin_cnt, int N, int nc, int top_k, int max_det, int A,
+                              const CoeffLevels& lv, int32_t* rows, hipStream_t st);
+int yolact_coeff_rows_launch(const CoeffLevels& lv, int N, int Cin, int R, int S, int pad, const float* w_packed, const float* scale, const float* shift,
+                             int A, int row0, int mask_dim, const int32_t* rows, const int32_t* count, int max_det, float* out, hipStream_t st);
 int yolact_masks_launch(const float* proto, const float* coeffs, const float* boxes, const int* count, int N, int PH, int PW,
                         int mask_dim, int K, int h, int w, float* ws_lo, uint8_t* out_masks, int64_t* out_boxes, hipStream_t st,
                         const int* image_hw = nullptr, int* win = nullptr, bool clear = true, bool dense_lo = false);

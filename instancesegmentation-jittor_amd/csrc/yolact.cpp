@@ -148,11 +148,103 @@ struct HeadOut {
     int A = 0, Ptot = 0, CH = 0;
     bool fused = false;
     void *loc = nullptr, *conf = nullptr, *mask = nullptr, *headcat = nullptr;
+    Tensor up[5];   // head.up0..4, the fused head's inputs (lazy_coeffs: the tail stream reads them again)
 };
-constexpr int kNumClasses = 81, kMaskDim = 32;
+constexpr int kNumClasses = kYolactClasses, kMaskDim = kYolactMaskDim;
+
+// ---- lazy_coeffs (fp32, fused head): the forward computes the loc|conf columns of the head only; see DESIGN.md section 4 "Mask coefficients of the kept
+// detections only".
+// Two views of the packed head_cat layer, built when the layer is registered: rows [0, 85 A) with their bias, and rows [85 A, 117 A) with theirs.  No copy:
+// a view's pointers point into the layer's allocations.  A launch's weight descriptor spans the view's Cout rounded up to 128 rows (conv_fill's w_bytes),
+// and a column tile reads whole tiles of rows: the first view's over-read rows are the layer's own next rows (their columns are past Cout and dropped), the
+// second view's are the layer's zero padding rows -- provided 85 A + pad128(32 A) stays inside the layer's pad128(117 A) rows, which is checked here
+// (A = 3: 255 + 128 <= 384; A = 9: 765 + 384 <= 1152).  Where it does not hold there are no views and the engine keeps the full head.
+void yolact_head_views(Engine& e) {
+    e.convs.erase(kHeadCatLocConf);
+    e.convs.erase(kHeadCatCoeff);
+    auto it = e.convs.find(kHeadCat);
+    if (it == e.convs.end() || it->second.f16) return;
+    const ConvLayer L = it->second;
+    const int per = 4 + kNumClasses + kMaskDim;
+    if (L.Cout % per != 0 || L.Cin % 32 != 0) return;
+    const int A = L.Cout / per, split = A * (4 + kNumClasses);
+    const int64_t wrow = (int64_t)L.R * L.S * L.Cin;
+    auto packed_rows = [&](int cout) -> int64_t {
+        isegmi_conv_desc d;
+        memset(&d, 0, sizeof(d));
+        d.N = 1; d.H = L.R; d.W = L.S; d.Cin = L.Cin; d.Cout = cout; d.R = L.R; d.S = L.S; d.stride = 1;
+        int64_t nf = 0;
+        return isegmi_conv_packed_floats(&d, &nf) == ISEGMI_OK ? nf / wrow : -1;
+    };
+    const int64_t all = packed_rows(L.Cout), lo = packed_rows(split), hi = packed_rows(L.Cout - split);
+    if (all < 0 || lo < 0 || hi < 0 || lo > all || split + hi > all) return;
+    ConvLayer a = L, b = L;
+    a.view = b.view = true;
+    a.Cout = split;
+    b.Cout = L.Cout - split;
+    b.d_w = L.d_w + (int64_t)split * wrow;
+    b.d_scale = L.d_scale ? L.d_scale + split : nullptr;
+    b.d_shift = L.d_shift ? L.d_shift + split : nullptr;
+    e.convs[kHeadCatLocConf] = a;
+    e.convs[kHeadCatCoeff] = b;
+}
+
+// Does a forward of N images take the lazy schedule?  Parameter "lazy_coeffs": 1 on, 0 off (the schedule before it, launch for launch), -1 (default) by
+// batch size: on from LAZY_COEFFS_MIN_BATCH images (profiles/lazy_coeffs.md).  fp16 and the unfused head keep the full head whatever it says.
+constexpr int LAZY_COEFFS_MIN_BATCH = 3;
+bool yolact_lazy_coeffs(Engine& e, int N) {
+    if (e.kind != 1 || e.fp16 || e.convs.count(kHeadCatLocConf) == 0 || e.convs.count(kHeadCatCoeff) == 0) return false;
+    const float p = e.param("lazy_coeffs", -1.0f);
+    return p < 0.0f ? N >= LAZY_COEFFS_MIN_BATCH : p != 0.0f;
+}
+
+static void coeff_levels(const Tensor* up, CoeffLevels* lv) {
+    lv->n = 5;
+    for (int l = 0; l < 5; ++l) { lv->feat[l] = up[l].d; lv->H[l] = up[l].H; lv->W[l] = up[l].W; }
+}
+
+// A fetch of `headcat` after a lazy forward: run the coefficient view over all five levels into columns [85 A, 117 A) of the buffer, from the head.up<l>
+// maps the forward left behind.  Everything the engine has in flight is waited for first and the fill itself is waited for, so no stream is left with
+// new work or new dependencies; det.* and the pending-event flags are not touched.
+int yolact_fill_coeff_columns(Engine& e) {
+    const int N = e.last_N;
+    auto hc = e.bufs.find("headcat");
+    if (N <= 0 || hc == e.bufs.end() || e.convs.count(kHeadCatCoeff) == 0) { set_error("headcat: no lazy forward to complete"); return ISEGMI_ERR_STATE; }
+    const int A = (int)e.param("num_priors", 3), CH = A * (4 + kNumClasses + kMaskDim);
+    Tensor up[5];
+    int64_t pix = 0, poff[5];
+    for (int l = 0; l < 5; ++l) {
+        auto it = e.bufs.find("head.up" + std::to_string(l));
+        if (it == e.bufs.end() || it->second.shape.size() != 4 || it->second.shape[0] != N) { set_error("headcat: head.up maps missing"); return ISEGMI_ERR_STATE; }
+        const RawBuf& b = it->second;
+        up[l].d = (float*)b.d; up[l].N = N; up[l].H = (int)b.shape[1]; up[l].W = (int)b.shape[2]; up[l].C = (int)b.shape[3]; up[l].dt = 0;
+        poff[l] = pix;
+        pix += (int64_t)up[l].H * up[l].W;
+    }
+    if (hc->second.bytes < (int64_t)N * pix * CH * 4) { set_error("headcat: buffer smaller than the head.up maps imply"); return ISEGMI_ERR_STATE; }
+    hipStream_t all[5] = {e.lane_stream[0], e.lane_stream[1], e.heads, e.tail, e.stream};
+    for (hipStream_t st : all) if (st) HIP_TRY(hipStreamSynchronize(st));
+    std::vector<ConvGroupItem> g(5);
+    for (int l = 0; l < 5; ++l) {
+        g[l].layer = kHeadCatCoeff; g[l].in = up[l]; g[l].pad = 1; g[l].act = 0;
+        g[l].dst = (float*)hc->second.d + poff[l] * CH + A * (4 + kNumClasses); g[l].out_div = up[l].H * up[l].W;
+        g[l].out_img_stride = pix * CH; g[l].out_pix_stride = CH; g[l].out_f32 = true;
+    }
+    // not a forward's launch: outside the conv timing / trace accounting
+    const bool ct = e.conv_timing, tr = e.conv_trace;
+    hipStream_t cur = e.cur;
+    e.conv_timing = e.conv_trace = false;
+    e.cur = e.stream;
+    const int rc = eng_conv_group(e, g);
+    e.conv_timing = ct; e.conv_trace = tr; e.cur = cur;
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(e.stream));
+    e.coeff_cols_valid = true;
+    return ISEGMI_OK;
+}
 
 // protonet on P3 and the shared prediction head on P3..P7
-static int proto_and_heads(Engine& e, const Tensor* P, int N, bool grp, HeadOut* h) {
+static int proto_and_heads(Engine& e, const Tensor* P, int N, bool grp, bool lazy, HeadOut* h) {
     const int dt = e.fp16 ? 1 : 0;
     // shared prediction head geometry
     const int A = (int)e.param("num_priors", 3), ncls = kNumClasses, md = kMaskDim;  // 9 for YOLACT++ (3 scales x 3 aspect ratios per cell)
@@ -165,7 +257,9 @@ static int proto_and_heads(Engine& e, const Tensor* P, int N, bool grp, HeadOut*
     // The three prediction convs (bbox 12, conf 243, mask 96) run as ONE 351-wide convolution when the host supplied
     // the fused layer: 6 instead of 1+4+2 64-wide column tiles per pixel tile, 5 launches instead of 15.  Its output
     // row per pixel is [A x 4 loc | A x 81 conf | A x 32 mask(pre-tanh)]; Detect reads it in place (HeadLayout).
-    const bool fused = e.convs.count("prediction_layers.0.head_cat") != 0;
+    const bool fused = e.convs.count(kHeadCat) != 0;
+    // lazy_coeffs: the loc|conf view of the layer (Cout = 85 A) into the same rows, same pixel stride CH; columns [85 A, CH) stay unwritten
+    const char* head_layer = lazy ? kHeadCatLocConf : kHeadCat;
     const int CH = A * (4 + ncls + md);
     void *loc = nullptr, *conf = nullptr, *mask = nullptr, *headcat = nullptr;
     if (fused) {
@@ -175,13 +269,14 @@ static int proto_and_heads(Engine& e, const Tensor* P, int N, bool grp, HeadOut*
         TRY(eng_buf(e, "conf", (int64_t)N * Ptot * ncls * 4, &conf, 0, {N, Ptot, ncls}));
         TRY(eng_buf(e, "mask", (int64_t)N * Ptot * md * 4, &mask, 0, {N, Ptot, md}));
     }
+    Tensor* up = h->up;
     auto head_level = [&](int l) -> int {
-        Tensor uf;
+        Tensor& uf = up[l];
         const std::string ln = "head.up" + std::to_string(l);
         TRY(eng_conv(e, "prediction_layers.0.upfeature.0", P[l], 1, 1, 1, nullptr, ln, &uf));
         const int hw = uf.H * uf.W;
         if (fused) {
-            TRY(eng_conv_into(e, "prediction_layers.0.head_cat", uf, 1, 1, 0, (float*)headcat + (int64_t)(off[l] / A) * CH, hw,
+            TRY(eng_conv_into(e, head_layer, uf, 1, 1, 0, (float*)headcat + (int64_t)(off[l] / A) * CH, hw,
                               (int64_t)(Ptot / A) * CH, CH, /*out_f32=*/true));
             return ISEGMI_OK;
         }
@@ -213,14 +308,14 @@ static int proto_and_heads(Engine& e, const Tensor* P, int N, bool grp, HeadOut*
         TRY(eng_conv(e, "proto_net.10", t, 1, 0, 1, nullptr, "proto", &proto, /*out_f32=*/true));
     }
     if (grp) {   // the shared head over all five levels: upfeature x 5 as one launch, head_cat x 5 as one launch (main stream; the protonet on side 0)
-        Tensor uf[5];
+        Tensor* uf = up;
         std::vector<ConvGroupItem> gu(5), gh(5);
         for (int l = 0; l < 5; ++l) {
             gu[l].layer = "prediction_layers.0.upfeature.0"; gu[l].in = P[l]; gu[l].pad = 1; gu[l].act = 1; gu[l].out_name = "head.up" + std::to_string(l); gu[l].out = &uf[l];
         }
         TRY(eng_conv_group(e, gu));
         for (int l = 0; l < 5; ++l) {
-            gh[l].layer = "prediction_layers.0.head_cat"; gh[l].in = uf[l]; gh[l].pad = 1; gh[l].act = 0;
+            gh[l].layer = head_layer; gh[l].in = uf[l]; gh[l].pad = 1; gh[l].act = 0;
             gh[l].dst = (float*)headcat + (int64_t)(off[l] / A) * CH; gh[l].out_div = uf[l].H * uf[l].W;
             gh[l].out_img_stride = (int64_t)(Ptot / A) * CH; gh[l].out_pix_stride = CH; gh[l].out_f32 = true;
         }
@@ -305,12 +400,17 @@ int yolact_forward(Engine& e, const float* d_images, int N) {
         HIP_TRY(hipStreamWaitEvent(e.stream, e.heads_done, 0));
         e.heads_pending = false;
     }
-    const bool grp = !dt && e.param("conv_groups", 1.0f) != 0.0f && e.param("conv_tile", 0) == 0.0f && e.convs.count("prediction_layers.0.head_cat") != 0;
+    const bool grp = !dt && e.param("conv_groups", 1.0f) != 0.0f && e.param("conv_tile", 0) == 0.0f && e.convs.count(kHeadCat) != 0;
+    const bool lazy = yolact_lazy_coeffs(e, N);
+    if (!lazy && !dt && e.param("lazy_coeffs", -1.0f) > 0.0f && e.convs.count(kHeadCat) != 0) {
+        set_error("lazy_coeffs: the fused head's rows do not split inside its padded weight image");
+        return ISEGMI_ERR_STATE;
+    }
     TRY(yolact_fpn(e, C, N, grp, pipe, P));
     eng_mark(e, "fpn");
     e.lane_tag.clear();   // everything allocated from here on (protonet, heads, Detect) exists once: it runs in step order behind the WAR point in proto_and_heads
     HeadOut head;
-    TRY(proto_and_heads(e, P, N, grp, &head));
+    TRY(proto_and_heads(e, P, N, grp, lazy, &head));
     eng_mark(e, "proto+heads");
     isegmi_yolact_detect_args a;
     TRY(detect_args(e, N, head, &a));
@@ -325,10 +425,27 @@ int yolact_forward(Engine& e, const float* d_images, int N) {
         ds = e.tail;
     }
     {
-        // confidences, box regressions and mask coefficients of every prior once (the fused head's [N][P][4 + 81 + 32] rows) + priors
+        // confidences and box regressions of every prior once (the fused head's [N][P][4 + 81] columns) + priors + the mask coefficients of
+        // the kept detections (the gather reads no other prior's)
         OpScope op(e, ds, "yolact_detect (softmax + decode + per-class top-k + fast-NMS + gather)",
-                   (double)N * a.P * ((double)(4 + a.ncls - 1 + a.mask_dim) * 4) + (double)a.P * 16);
-        TRY(yolact_detect_launch(&a, ds));
+                   (double)N * a.P * ((double)(4 + a.ncls - 1) * 4) + (double)a.P * 16 + (double)N * a.max_det * a.mask_dim * 4);
+        if (lazy) {
+            // Detect split at the final top-k: the kept slots' rows, their 32 coefficients each from head.up<level> (ordered behind the heads phase by the
+            // event above; the next forward's writers of head.up wait on tail_done), then the gather from ws.coeff_sel
+            const ConvLayer& Lc = e.convs[kHeadCatCoeff];
+            CoeffLevels lv;
+            coeff_levels(head.up, &lv);
+            void *rows, *sel;
+            TRY(eng_buf(e, "ws.coeff_rows", (int64_t)N * a.max_det * 5 * 4, &rows, 1));
+            TRY(eng_buf(e, "ws.coeff_sel", (int64_t)N * a.max_det * a.mask_dim * 4, &sel, 0, {N, a.max_det, a.mask_dim}));
+            TRY(yolact_detect_select_launch(&a, ds));
+            TRY(yolact_coeff_index_launch(a.d_ws_fin_idx, a.d_ws_tk_idx, a.d_ws_fin_cnt, N, a.ncls - 1, a.top_k, a.max_det, head.A, lv, (int32_t*)rows, ds));
+            TRY(yolact_coeff_rows_launch(lv, N, Lc.Cin, Lc.R, Lc.S, 1, Lc.d_w, Lc.d_scale, Lc.d_shift, head.A, 0, a.mask_dim, (const int32_t*)rows,
+                                         a.d_ws_fin_cnt, a.max_det, (float*)sel, ds));
+            TRY(yolact_detect_gather_launch(&a, (const float*)sel, ds));
+        } else {
+            TRY(yolact_detect_launch(&a, ds));
+        }
     }
     if (pipe) { HIP_TRY(hipEventRecord(e.heads_done, e.stream)); e.heads_pending = true; }
     TRY(eng_tail_end(e));

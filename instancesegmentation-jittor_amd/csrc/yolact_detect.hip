@@ -161,7 +161,7 @@ __global__ __launch_bounds__(1024) void yolact_fast_nms_kernel(const float* __re
 __global__ void yolact_gather_kernel(const float* __restrict__ boxes, const float* __restrict__ mask, const int* __restrict__ tk_idx,
                                      const float* __restrict__ fin_vals, const int* __restrict__ fin_idx,
                                      const int* __restrict__ fin_cnt, int P, int nc, int top_k, int mask_dim, int max_det,
-                                     const HeadLayout L,
+                                     const HeadLayout L, const float* __restrict__ coeff_sel,
                                      int* __restrict__ out_count, float* __restrict__ out_boxes, float* __restrict__ out_scores,
                                      int* __restrict__ out_classes, float* __restrict__ out_coeffs, int* __restrict__ out_prior) {
     const int n = blockIdx.x;
@@ -177,7 +177,8 @@ __global__ void yolact_gather_kernel(const float* __restrict__ boxes, const floa
             out_scores[o] = fin_vals[o];
             out_classes[o] = c;
             out_prior[o] = prior;
-            const float* mp = head_ptr(mask, L, n, P, prior, mask_dim, L.off_mask);
+            // coeff_sel: the slot's coefficients were computed for it ([N][max_det][mask_dim], yolact_coeff.hip) instead of for every prior
+            const float* mp = coeff_sel ? coeff_sel + o * mask_dim : head_ptr(mask, L, n, P, prior, mask_dim, L.off_mask);
             for (int k = 0; k < mask_dim; ++k) out_coeffs[o * mask_dim + k] = L.mask_tanh ? dm_tanh(mp[k]) : mp[k];
         } else {
             *(float4*)(out_boxes + o * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -319,7 +320,15 @@ __global__ void yolact_int_boxes_kernel(const float* __restrict__ boxes, const i
     }
 }
 
-int yolact_detect_launch(const isegmi_yolact_detect_args* a, hipStream_t st) {
+static HeadLayout head_layout(const isegmi_yolact_detect_args* a) {
+    HeadLayout L;
+    L.A = a->A > 0 ? a->A : 1; L.pix_stride = a->pix_stride; L.off_loc = a->off_loc; L.off_conf = a->off_conf; L.off_mask = a->off_mask;
+    L.mask_tanh = a->mask_tanh;
+    return L;
+}
+
+// Detect up to the final per-image top-k (ws.fin_vals / fin_idx / fin_cnt); the gather below turns those into the det.* rows
+int yolact_detect_select_launch(const isegmi_yolact_detect_args* a, hipStream_t st) {
     ARG_CHECK(a->N > 0 && a->P > 0 && a->ncls >= 2 && a->ncls <= 256, "detect sizes");
     ARG_CHECK(a->top_k > 0 && a->top_k <= 256 && a->max_det > 0 && a->max_det <= 128, "top_k<=256, max_det<=128");
     ARG_CHECK(a->mask_dim > 0, "mask_dim");
@@ -328,9 +337,7 @@ int yolact_detect_launch(const isegmi_yolact_detect_args* a, hipStream_t st) {
     int* keep_count = a->d_ws_counts;
     int* kept2 = a->d_ws_counts + a->N;
     const size_t lds = ((size_t)SM_ROWS * a->ncls + (size_t)(SM_PARTS + 1) * SM_ROWS) * sizeof(float);
-    HeadLayout L;
-    L.A = a->A > 0 ? a->A : 1; L.pix_stride = a->pix_stride; L.off_loc = a->off_loc; L.off_conf = a->off_conf; L.off_mask = a->off_mask;
-    L.mask_tanh = a->mask_tanh;
+    const HeadLayout L = head_layout(a);
     ARG_CHECK(a->pix_stride == 0 || (a->A > 0 && a->P % a->A == 0), "fused head layout needs A > 0 and P % A == 0");
     hipLaunchKernelGGL(yolact_softmax_decode_kernel, dim3(cdiv(a->P, SM_ROWS), a->N), dim3(SM_ROWS * SM_PARTS), lds, st, a->d_conf, a->d_loc,
                        a->d_priors, a->P, a->ncls, a->conf_thresh, L, a->d_ws_scoresT, a->d_ws_boxes, keep_count);
@@ -343,12 +350,22 @@ int yolact_detect_launch(const isegmi_yolact_detect_args* a, hipStream_t st) {
     HIP_TRY(hipGetLastError());
     rc = topk_launch(a->d_ws_cand, (int64_t)nc * a->top_k, a->N, nc * a->top_k, a->max_det, kept2, 1, a->d_ws_fin_vals,
                      a->d_ws_fin_idx, a->d_ws_fin_cnt, st);
-    if (rc) return rc;
+    return rc;
+}
+
+int yolact_detect_gather_launch(const isegmi_yolact_detect_args* a, const float* coeff_sel, hipStream_t st) {
+    const int nc = a->ncls - 1;
+    const HeadLayout L = head_layout(a);
     hipLaunchKernelGGL(yolact_gather_kernel, dim3(a->N), dim3(128), 0, st, a->d_ws_boxes, a->d_mask, a->d_ws_tk_idx, a->d_ws_fin_vals,
-                       a->d_ws_fin_idx, a->d_ws_fin_cnt, a->P, nc, a->top_k, a->mask_dim, a->max_det, L, a->d_out_count,
+                       a->d_ws_fin_idx, a->d_ws_fin_cnt, a->P, nc, a->top_k, a->mask_dim, a->max_det, L, coeff_sel, a->d_out_count,
                        a->d_out_boxes, a->d_out_scores, a->d_out_classes, a->d_out_coeffs, a->d_out_prior);
     HIP_TRY(hipGetLastError());
     return ISEGMI_OK;
+}
+
+int yolact_detect_launch(const isegmi_yolact_detect_args* a, hipStream_t st) {
+    const int rc = yolact_detect_select_launch(a, st);
+    return rc ? rc : yolact_detect_gather_launch(a, nullptr, st);
 }
 
 // ---- YOLACT++ fast mask re-scoring (FastMaskIoUNet) ends: the first layer (one input channel: the cropped proto-resolution

@@ -478,6 +478,34 @@ def yolact_detect(conf_logits, loc, mask, priors, conf_thresh=0.05, nms_thresh=0
     return out, bufs["d_ws_boxes"].numpy()
 
 
+def yolact_coeff_rows(feats, w_krsc, bias, A, rows, counts, row0, pad=1, sentinel=None, scale=None):
+    """isegmi_op_yolact_coeff_rows: feats = list of <= 5 [N,H,W,Cin] maps; w_krsc / bias = the whole head layer (>= row0 + 32 A output channels);
+    rows [N,max_det,5] int32 (image, level, ho, wo, anchor); counts [N].  -> [N,max_det,32] pre-tanh; slots past the count keep `sentinel` in
+    every element (default: 0xFF bytes)."""
+    V, I = C.c_void_p, C.c_int
+    f = lib().isegmi_op_yolact_coeff_rows
+    if f.argtypes is None:   # declared: an ABI change raises instead of shifting arguments
+        f.argtypes = [I, V, V, V, I, I, I, I, I, V, V, V, I, I, V, V, I, V, V]
+        f.restype = I
+    feats = [np.ascontiguousarray(x, np.float32) for x in feats]
+    N, Cin = feats[0].shape[0], feats[0].shape[3]
+    Cout, R, S, _ = w_krsc.shape
+    rows = np.ascontiguousarray(rows, np.int32)
+    assert rows.ndim == 3 and rows.shape[0] == N and rows.shape[2] == 5, rows.shape
+    max_det = rows.shape[1]
+    d = make_conv_desc(1, R, S, Cin, Cout, R, S, 1, 0)
+    dw = DeviceBuffer.from_numpy(pack_conv_weights(d, w_krsc))
+    db = None if bias is None else DeviceBuffer.from_numpy(np.asarray(bias, np.float32))
+    dsc = None if scale is None else DeviceBuffer.from_numpy(np.asarray(scale, np.float32))
+    dfs = [DeviceBuffer.from_numpy(x) for x in feats]
+    ptrs = (C.c_void_p * len(dfs))(*[b.ptr.value for b in dfs])
+    hs = (C.c_int32 * len(dfs))(*[x.shape[1] for x in feats]); ws = (C.c_int32 * len(dfs))(*[x.shape[2] for x in feats])
+    dr = DeviceBuffer.from_numpy(rows); dc = DeviceBuffer.from_numpy(np.ascontiguousarray(counts, np.int32))
+    do = DeviceBuffer((N, max_det, 32)).poison() if sentinel is None else DeviceBuffer.from_numpy(np.full((N, max_det, 32), sentinel, np.float32))
+    check(f(len(dfs), ptrs, hs, ws, N, Cin, R, S, pad, dw.ptr, _ptr(dsc), _ptr(db), A, row0, dr.ptr, dc.ptr, max_det, do.ptr, None))
+    return do.numpy()
+
+
 def yolact_masks(proto, coeffs, boxes, counts, h, w):
     """proto [N,PH,PW,32]; coeffs [N,K,32]; boxes [N,K,4]; counts [N] -> (masks u8 [N,K,h,w], boxes i64 [N,K,4])"""
     proto = np.ascontiguousarray(proto, np.float32)
