@@ -659,7 +659,7 @@ int isegmi_engine_op_stats(isegmi_engine* e, char* names, int names_cap, double*
 int isegmi_engine_conv_report(isegmi_engine* e, char* buf, int cap);
 
 /* ---- COCO evaluation on the device (csrc/cocoeval.hip) ----
- * What of pycocotools' maskApi.c / cocoeval.py these restate (rleArea, rleToBbox, rleIou, bbIou, COCOeval.evaluateImg) is
+ * What of pycocotools' maskApi.c / cocoeval.py these restate (rleArea, rleToBbox, rleIou, bbIou, COCOeval.computeOks / evaluateImg) is
  * [UPSTREAM-RECALL -- unverified].  An RLE is its run counts as isegmi.coco.rle_from_string yields them: column-major, zeros first.
  * M RLEs lie back to back in d_counts; d_off [M + 1] (int64) are their first runs; d_hw [M][2] = (h, w), h * w < 2^32.
  *
@@ -676,6 +676,18 @@ int isegmi_op_rle_prefix(const uint32_t* d_counts, const int64_t* d_off, const i
 int isegmi_op_rle_iou(const uint32_t* d_bounds, const uint32_t* d_cum, const int64_t* d_off, const int32_t* d_hw, const int64_t* d_area,
                       const int32_t* d_bbox, int M, const int32_t* d_pairs, int64_t P, double* d_out, void* stream);
 int isegmi_op_bbox_iou(const double* d_boxes, int B, const int32_t* d_pairs, int64_t P, double* d_out, void* stream);
+/* isegmi_op_oks: object keypoint similarity of the same pair list ([UPSTREAM-RECALL -- unverified] COCOeval.computeOks).  M items (gts and
+ * dets in one list): d_kpts [M][K][3] = (x, y, v), d_box [M][4] xywh and d_area [M] (read for a gt only), d_vars [K] = (sigmas * 2) ** 2 as the
+ * host computes it, 1 <= K <= 32; d_pairs [P][3] = (det item, gt item, unused).  Per pair, every operation one IEEE double operation in this order:
+ *   k1 = #{k : vg_k > 0}
+ *   k1 > 0 : only the keypoints with vg_k > 0 count;  dx = xd - xg, dy = yd - yg
+ *   k1 == 0: all K count;  x0 = bx - bw, x1 = bx + bw*2, dx = max(0, x0 - xd) + max(0, xd - x1), y likewise
+ *   e = ((dx*dx + dy*dy) / vars_k) / (area + 2^-52) / 2;   d_out[p] = (sum of exp(-e)) / n,  n = k1, or K when k1 == 0
+ * The terms are added in keypoint-index order by one add each (upstream's np.sum uses another order: a deliberate deviation).  A keypoint
+ * that does not count is selected out, so its coordinates may be anything, NaN included; the detection's v is never read.  A pair's value
+ * depends on its two items alone, not on P or on the other pairs.  -1.0 marks an item index outside [0, M). */
+int isegmi_op_oks(const double* d_kpts, const double* d_box, const double* d_area, const double* d_vars, int M, int K, const int32_t* d_pairs,
+                  int64_t P, double* d_out, void* stream);
 /* isegmi_op_coco_match: evaluateImg's greedy matching, one sequential scan per (group, area range, IoU threshold).  A group is one
  * (image, category) -- or one image with useCats = 0.  Group g owns detections [d_det_off[g], d_det_off[g + 1]) (already sorted by score, best
  * first, and cut to maxDets[-1]), gts [d_gt_off[g], d_gt_off[g + 1]) and the row-major [D][G] IoU block at d_ious + d_iou_off[g].

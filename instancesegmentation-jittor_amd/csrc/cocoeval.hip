@@ -1,6 +1,7 @@
-// cocoeval.hip -- the device half of COCO evaluation: mask IoU straight on run-length encodings, box IoU, and the
-// greedy detection <-> ground-truth matching of COCOeval.evaluateImg.  Everything that describes pycocotools (maskApi.c rleArea / rleToBbox /
-// rleIou / bbIou, cocoeval.py evaluateImg) is [UPSTREAM-RECALL -- unverified]: restated from memory, upstream source is not available.
+// cocoeval.hip -- the device half of COCO evaluation: mask IoU straight on run-length encodings, box IoU,
+// object keypoint similarity (OKS), and the greedy detection <-> ground-truth matching of COCOeval.evaluateImg.  Everything that describes
+// pycocotools (maskApi.c rleArea / rleToBbox / rleIou / bbIou, cocoeval.py computeOks / evaluateImg) is [UPSTREAM-RECALL -- unverified]:
+// restated from memory, upstream source is not available.
 //
 //   coco_rle_prefix   one block per RLE: inclusive prefix sums of its run counts -> run END positions (bounds) and the number of set pixels up
 //                     to and including each run (cum); from them the area (rleArea) and the tight box (rleToBbox) of the mask
@@ -8,6 +9,7 @@
 //                     bounds for F(e) - F(s), F(p) = set pixels before position p; the integer partial sums are added across the wave with
 //                     shuffles.  Intersection and areas are integers (exact, order-independent); the one floating operation is one IEEE double division
 //   coco_bbox_iou     one thread per pair, bbIou's operation order
+//   coco_oks          one thread per pair: computeOks' operation order, the terms added in keypoint-index order
 //   coco_match        one thread per (group, area range, IoU threshold): the sequential greedy scan
 //
 // No atomics, no LDS beyond the block scans of coco_rle_prefix, nothing allocated here.
@@ -175,6 +177,50 @@ __global__ __launch_bounds__(256) void coco_bbox_iou_kernel(const double* __rest
     out[p] = o;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- keypoint similarity (OKS)
+// [UPSTREAM-RECALL -- unverified] COCOeval.computeOks, every operation one IEEE double operation in this order (-ffp-contract=off):
+//   k1 = #{k : vg_k > 0}
+//   k1 > 0 : only the keypoints with vg_k > 0 count;  dx = xd - xg, dy = yd - yg
+//   k1 == 0: all K count;  x0 = bx - bw, x1 = bx + bw * 2, dx = max(0, x0 - xd) + max(0, xd - x1), y likewise (the gt's coordinates are not read)
+//   e = ((dx * dx + dy * dy) / vars_k) / (area + 2^-52) / 2;   oks = (exp(-e_0) + exp(-e_1) + ..) / n,  n = k1, or K when k1 == 0
+// The terms are added in keypoint-index order, one add each (upstream's np.sum pairs them differently: a stated deviation).  A
+// keypoint that does not count is branched over, never multiplied by zero: its coordinates may hold anything, NaN included.  The det's v is not read.
+// One thread per pair, the whole sum in that thread: the value of a pair depends on nothing but its two items.  The pairs of a group are a
+// row-major [D][G] block, so the lanes of a wave hold a few detections against the same G gts: one load instruction touches at most G distinct gt
+// records and ceil(64 / G) + 1 det records, the rest of the lanes read an address another lane reads.  -1.0 flags an index outside [0, M).
+__global__ __launch_bounds__(256) void coco_oks_kernel(const double* __restrict__ kpts, const double* __restrict__ box,
+                                                       const double* __restrict__ area, const double* __restrict__ vars, int M, int K,
+                                                       const int32_t* __restrict__ pairs, int64_t P, double* __restrict__ out) {
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= P) return;
+    const int d = pairs[3 * p], g = pairs[3 * p + 1];
+    if (d < 0 || d >= M || g < 0 || g >= M) { out[p] = -1.0; return; }
+    const double* kd = kpts + (int64_t)d * K * 3;
+    const double* kg = kpts + (int64_t)g * K * 3;
+    int k1 = 0;
+    for (int k = 0; k < K; ++k) k1 += kg[3 * k + 2] > 0.0 ? 1 : 0;
+    const double den = area[g] + 0x1p-52;   // np.spacing(1)
+    double sum = 0.0;
+    if (k1 > 0) {
+        for (int k = 0; k < K; ++k) {
+            if (!(kg[3 * k + 2] > 0.0)) continue;
+            const double dx = kd[3 * k] - kg[3 * k], dy = kd[3 * k + 1] - kg[3 * k + 1];
+            const double e = (dx * dx + dy * dy) / vars[k] / den / 2.0;
+            sum = sum + exp(-e);
+        }
+    } else {
+        const double* b = box + 4 * (int64_t)g;
+        const double x0 = b[0] - b[2], x1 = b[0] + b[2] * 2.0, y0 = b[1] - b[3], y1 = b[1] + b[3] * 2.0;
+        for (int k = 0; k < K; ++k) {
+            const double xd = kd[3 * k], yd = kd[3 * k + 1];
+            const double dx = fmax(0.0, x0 - xd) + fmax(0.0, xd - x1), dy = fmax(0.0, y0 - yd) + fmax(0.0, yd - y1);
+            const double e = (dx * dx + dy * dy) / vars[k] / den / 2.0;
+            sum = sum + exp(-e);
+        }
+    }
+    out[p] = sum / (double)(k1 > 0 ? k1 : K);
+}
+
 // ---------------------------------------------------------------------------------------------------------------- greedy matching
 struct CocoMatchK {
     int n_groups, A, T;
@@ -284,6 +330,17 @@ extern "C" int isegmi_op_bbox_iou(const double* d_boxes, int B, const int32_t* d
     if (P == 0) return ISEGMI_OK;
     ARG_CHECK(d_boxes && d_pairs && d_out, "bbox_iou: null pointer");
     hipLaunchKernelGGL(coco_bbox_iou_kernel, dim3((unsigned)cdiv64(P, 256)), dim3(256), 0, (hipStream_t)stream, d_boxes, B, d_pairs, P, d_out);
+    HIP_TRY(hipGetLastError());
+    return ISEGMI_OK;
+}
+
+extern "C" int isegmi_op_oks(const double* d_kpts, const double* d_box, const double* d_area, const double* d_vars, int M, int K,
+                             const int32_t* d_pairs, int64_t P, double* d_out, void* stream) {
+    ARG_CHECK(M >= 0 && K >= 1 && K <= 32 && P >= 0 && P < (1ll << 38), "oks sizes");
+    if (P == 0) return ISEGMI_OK;
+    ARG_CHECK(d_kpts && d_box && d_area && d_vars && d_pairs && d_out, "oks: null pointer");
+    hipLaunchKernelGGL(coco_oks_kernel, dim3((unsigned)cdiv64(P, 256)), dim3(256), 0, (hipStream_t)stream, d_kpts, d_box, d_area, d_vars, M, K,
+                       d_pairs, P, d_out);
     HIP_TRY(hipGetLastError());
     return ISEGMI_OK;
 }

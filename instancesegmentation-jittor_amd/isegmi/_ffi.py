@@ -1034,6 +1034,7 @@ _COCO_SIGS = {
     "isegmi_op_rle_prefix": [_VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP],
     "isegmi_op_rle_iou": [_VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _I64, _VP, _VP],
     "isegmi_op_bbox_iou": [_VP, _I32, _VP, _I64, _VP, _VP],
+    "isegmi_op_oks": [_VP, _VP, _VP, _VP, _I32, _I32, _VP, _I64, _VP, _VP],
     "isegmi_coco_match_bytes": [_I64, _I64, _I32, _I32, _PI64, _PI64, _PI64, _PI64],
     "isegmi_op_coco_match": [C.POINTER(CocoMatchArgs), _VP],
 }
@@ -1134,6 +1135,31 @@ def bbox_iou(boxes, pairs):
     sync()
     out = do.numpy()
     for b in (db, dp, do):
+        b.free()
+    return out
+
+
+def oks_device(d_kpts, d_box, d_area, d_vars, M, K, d_pairs, P, d_out, stream=None):
+    """isegmi_op_oks over device buffers: d_kpts [M][K][3], d_box [M][4], d_area [M], d_vars [K] float64; d_pairs [P][3] int32 -> d_out [P] float64."""
+    check(coco_fn("isegmi_op_oks")(_ptr(d_kpts), _ptr(d_box), _ptr(d_area), _ptr(d_vars), int(M), int(K), _ptr(d_pairs), int(P), _ptr(d_out),
+                                   stream))
+
+
+def oks(kpts, box, area, variances, pairs):
+    """Host convenience: kpts [M][K][3] (x, y, v), box [M][4] xywh, area [M], variances [K] = (sigmas * 2) ** 2, pairs [P][3] (det item, gt item,
+    unused) -> float64 [P] in computeOks' operation order, the terms added in keypoint-index order."""
+    variances = np.ascontiguousarray(variances, np.float64).ravel()
+    K = len(variances)
+    kpts = np.ascontiguousarray(kpts, np.float64).reshape(-1, K, 3)
+    M = len(kpts)
+    box = np.ascontiguousarray(box, np.float64).reshape(M, 4); area = np.ascontiguousarray(area, np.float64).reshape(M)
+    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 3)
+    bufs = [DeviceBuffer.from_numpy(a) for a in (kpts, box, area, variances, pairs)]
+    do = DeviceBuffer((len(pairs),), np.float64)
+    oks_device(*bufs[:4], M, K, bufs[4], len(pairs), do)
+    sync()
+    out = do.numpy()
+    for b in bufs + [do]:
         b.free()
     return out
 

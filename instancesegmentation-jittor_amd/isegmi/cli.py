@@ -4,7 +4,7 @@
   python -m isegmi.cli eval --trained_model=weights.npz --images=in_dir:out_dir [--output_coco_json=dets.json]
   python -m isegmi.cli test_net --config-file cfg.yaml [--images dir] [--output results.json]
   python -m isegmi.cli pose2seg_test --weights random --anno person_keypoints.json --image-root DIR [--output segm.json] [--batch-size 8]
-  python -m isegmi.cli coco_eval --gt instances.json --dt results.json --iou-type segm|bbox [--cat-ids ...] [--max-dets ...] [--out stats.json]
+  python -m isegmi.cli coco_eval --gt instances.json --dt results.json --iou-type segm|bbox|keypoints [--cat-ids ...] [--max-dets ...] [--out stats.json]
 
 eval, test_net and pose2seg_test take an optional `--gt instances.json`: after writing their json they print the COCO AP / AR summary.
 
@@ -131,7 +131,7 @@ def cmd_test_net(a):
         c.merge_from_file(a.config_file)
     c.merge_from_list(a.opts)
     retina = is_retinanet(c)   # MODEL.RETINANET_ON: the one-stage detector, bbox results only
-    # MODEL.KEYPOINT_ON: Keypoint R-CNN -- one json entry per detection with `keypoints`; --gt prints the bbox numbers
+    # MODEL.KEYPOINT_ON: Keypoint R-CNN -- one json entry per detection with `keypoints`; --gt prints the bbox block and then the keypoints block
     mc = to_retinanet_config(c) if retina else to_keypointrcnn_config(c) if is_keypoint_rcnn(c) else to_maskrcnn_config(c)
     rank, world, local = _rank_world()
     files = sorted(os.path.join(a.images, f) for f in os.listdir(a.images)) if a.images else []
@@ -155,7 +155,7 @@ def cmd_test_net(a):
         print("wrote %d results for %d images to %s (%d steps of %d images on %d rank(s))" % (
             len(results), len(files), a.output, stats.get("steps", 0), a.batch_size, world))
         if a.gt:
-            _print_coco_summary(a.gt, results, ("bbox",) if box_only else ("bbox", "segm"))
+            _print_coco_summary(a.gt, results, ("bbox", "keypoints") if is_keypoint_rcnn(c) else ("bbox",) if box_only else ("bbox", "segm"))
     return results
 
 
@@ -233,10 +233,10 @@ def build_parser():
     c = sub.add_parser("coco_eval", help="COCO AP / AR of a result json against an annotation json (pycocotools COCOeval restated)")
     c.add_argument("--gt", required=True, help="COCO annotation json")
     c.add_argument("--dt", required=True, help="COCO result json")
-    c.add_argument("--iou-type", dest="iou_type", default="segm", choices=["segm", "bbox"])
+    c.add_argument("--iou-type", dest="iou_type", default="segm", choices=["segm", "bbox", "keypoints"])
     c.add_argument("--cat-ids", dest="cat_ids", type=int, nargs="+", default=None)
     c.add_argument("--max-dets", dest="max_dets", type=int, nargs="+", default=None)
-    c.add_argument("--out", default=None, help="also write the twelve stats as json")
+    c.add_argument("--out", default=None, help="also write the stats (twelve; ten for keypoints) as json")
     return ap
 
 

@@ -1,15 +1,17 @@
-"""COCO evaluation: mask / box AP and AR of a COCO result list against a COCO annotation file.
+"""COCO evaluation: mask / box / keypoint AP and AR of a COCO result list against a COCO annotation file.
 
 The reference's test commands (Pose2Seg test.py --coco, Yolact eval.py, detectron tools/test_net.py) all end in pycocotools' COCOeval.
 pycocotools is not available, so COCO.loadRes, COCOeval.evaluate / accumulate / summarize are restated here.  Everything that describes
 pycocotools is [UPSTREAM-RECALL -- unverified]: written from memory of its behaviour, not from its source.  The mask / box IoU of every
-(detection, ground truth) pair and the greedy matching run on the GPU (csrc/cocoeval.hip through isegmi._ffi); accumulate and summarize
-are numpy.  Keypoint (OKS) evaluation is not covered.
+(detection, ground truth) pair -- under "keypoints" their object keypoint similarity (OKS, COCOeval.computeOks) -- and the greedy matching run
+on the GPU (csrc/cocoeval.hip through isegmi._ffi); accumulate and summarize are numpy.
 
 Deliberate deviations from upstream:
   * dtMatches / gtMatches hold 1 + the partner's index inside its (image, category) group, 0 = unmatched.  Upstream stores annotation ids, so
     that a ground truth with id 0 looks unmatched.
   * a detection's area under iou_type "segm" is its mask area even when the record also carries a bbox (upstream's loadRes looks at "bbox" first).
+  * a detection's area under iou_type "keypoints" is the extent area of its keypoints even when the record also carries a bbox (same reason).
+  * OKS adds its K terms in keypoint-index order (upstream's np.sum pairs them differently); the order is fixed and stated.
   * the headline AP / AR lines use maxDets[-1] (upstream hard-codes 100 and prints -1 when maxDets has no 100).
 """
 import json
@@ -20,6 +22,16 @@ from . import coco as _coco
 
 AREA_RNG = [[0 ** 2, 1e5 ** 2], [0 ** 2, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2]]
 AREA_RNG_LBL = ["all", "small", "medium", "large"]
+KPT_AREA_RNG = [[0 ** 2, 1e5 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2]]
+KPT_AREA_RNG_LBL = ["all", "medium", "large"]
+KPT_OKS_SIGMAS = np.array([.26, .25, .25, .35, .35, .79, .79, .72, .72, .62, .62, 1.07, 1.07, .87, .87, .89, .89]) / 10.0
+
+
+def _kpt_extent(kp):
+    """loadRes' keypoint branch: (area, [x0, y0, w, h]) of the extents of the x and y of K * 3 numbers (v is not looked at)."""
+    x, y = kp[0::3], kp[1::3]
+    x0, x1, y0, y1 = min(x), max(x), min(y), max(y)
+    return (x1 - x0) * (y1 - y0), [x0, y0, x1 - x0, y1 - y0]
 
 
 def _seg_counts(seg, h, w):
@@ -73,6 +85,9 @@ class COCOGt:
                 r["bbox"] = _coco.rle_to_bbox(r["counts"], r["size"][0])
             else:
                 r["bbox"] = None
+            if a.get("keypoints") is not None:
+                r["keypoints"] = [float(v) for v in a["keypoints"]]
+                r["num_keypoints"] = int(a["num_keypoints"]) if "num_keypoints" in a else sum(1 for v in r["keypoints"][2::3] if v > 0)
             self.anns.append(r)
 
     def img_ids(self):
@@ -89,7 +104,8 @@ class COCODt:
 
 def load_results(gt, results_or_path):
     """COCO.loadRes: a result list (or its json) -> COCODt.  Records with a `segmentation` get their mask area and tight box; records with a
-    `bbox` keep it.  Ids are 1..n in list order.  An image id the annotation file does not know raises."""
+    `bbox` keep it; records with `keypoints` keep them with their extent area and box (a record may carry nothing else).  Ids are 1..n in list
+    order.  An image id the annotation file does not know raises."""
     res = results_or_path
     if not isinstance(res, (list, tuple)):
         with open(res) as f:
@@ -106,8 +122,14 @@ def load_results(gt, results_or_path):
             r["counts"], r["size"] = _seg_counts(a["segmentation"], im.get("height"), im.get("width"))
             r["seg_area"] = float(_coco.rle_area(r["counts"]))
             r["seg_bbox"] = _coco.rle_to_bbox(r["counts"], r["size"][0])
-        elif r["bbox"] is None:
-            raise ValueError("result %d has neither bbox nor segmentation" % k)
+        if a.get("keypoints") is not None:
+            r["keypoints"] = [float(v) for v in a["keypoints"]]
+            if len(r["keypoints"]) >= 3 and len(r["keypoints"]) % 3 == 0:
+                r["kp_area"], r["kp_bbox"] = _kpt_extent(r["keypoints"])
+            elif r["counts"] is None and r["bbox"] is None:
+                raise ValueError("result %d: keypoints must be K * 3 numbers, got %d" % (k, len(r["keypoints"])))
+        if r["counts"] is None and r["bbox"] is None and "keypoints" not in r:
+            raise ValueError("result %d has neither bbox, segmentation nor keypoints" % k)
         out.append(r)
     return COCODt(out)
 
@@ -117,7 +139,10 @@ class Params:
 
     def __init__(self, iou_type="segm"):
         if iou_type not in ("segm", "bbox"):
-            raise ValueError("iou_type %r: only segm and bbox are evaluated (keypoints are out of scope)" % (iou_type,))
+            raise ValueError("iou_type %r: Params covers segm and bbox; keypoints have their own defaults in KeypointParams" % (iou_type,))
+        self._defaults(iou_type)
+
+    def _defaults(self, iou_type):
         self.iouType = iou_type
         self.imgIds = []
         self.catIds = []
@@ -129,6 +154,18 @@ class Params:
         self.useCats = 1
 
 
+class KeypointParams(Params):
+    """[UPSTREAM-RECALL -- unverified] upstream's defaults for `keypoints`: at most 20 detections per image, no `small` range, the per-keypoint
+    sigmas of the 17 COCO person keypoints.  K = len(kpt_oks_sigmas); other sigmas (1 to 32 of them) may be set."""
+
+    def __init__(self):
+        self._defaults("keypoints")
+        self.maxDets = [20]
+        self.areaRng = [list(r) for r in KPT_AREA_RNG]
+        self.areaRngLbl = list(KPT_AREA_RNG_LBL)
+        self.kpt_oks_sigmas = KPT_OKS_SIGMAS.copy()
+
+
 class COCOeval:
     """evaluate() -> accumulate() -> summarize(), as pycocotools' class of the same name.
     mem_budget: bytes of device memory one chunk of groups may take for its pair list, IoU blocks and match arrays."""
@@ -136,7 +173,7 @@ class COCOeval:
     def __init__(self, gt, dt, iou_type="segm", mem_budget=512 << 20):
         self.gt = gt if isinstance(gt, COCOGt) else COCOGt(gt)
         self.dt = dt if isinstance(dt, COCODt) else load_results(self.gt, dt)
-        self.params = Params(iou_type)
+        self.params = KeypointParams() if iou_type == "keypoints" else Params(iou_type)
         self.params.imgIds = self.gt.img_ids()
         self.params.catIds = self.gt.cat_ids()
         self.mem_budget = int(mem_budget)
@@ -152,6 +189,11 @@ class COCOeval:
         p.catIds = sorted(set(int(c) for c in p.catIds)) if p.useCats else [-1]
         p.maxDets = sorted(int(m) for m in p.maxDets)
         segm = p.iouType == "segm"
+        kpt = p.iouType == "keypoints"
+        if kpt:
+            K = len(p.kpt_oks_sigmas)
+            if not 1 <= K <= 32:
+                raise ValueError("kpt_oks_sigmas: %d sigmas, the OKS kernel takes 1 to 32" % K)
         img_pos = {i: k for k, i in enumerate(p.imgIds)}
         cat_pos = {c: k for k, c in enumerate(p.catIds)}
         groups = {}   # (k, i) -> ([gt ann indices], [dt ann indices])
@@ -164,6 +206,10 @@ class COCOeval:
                 raise ValueError("ground truth %r has no segmentation" % (a["id"],))
             if not segm and a["bbox"] is None:
                 raise ValueError("ground truth %r has no bbox" % (a["id"],))
+            if kpt and a.get("keypoints") is None:
+                raise ValueError("ground truth %r has no keypoints" % (a["id"],))
+            if kpt and len(a["keypoints"]) != 3 * K:
+                raise ValueError("ground truth %r has %d keypoint numbers, %d sigmas need %d" % (a["id"], len(a["keypoints"]), K, 3 * K))
             groups.setdefault((k, i), ([], []))[0].append(n)
         for n, a in enumerate(self.dt.anns):
             i = img_pos.get(a["image_id"])
@@ -172,6 +218,10 @@ class COCOeval:
                 continue
             if segm and a["counts"] is None:
                 raise ValueError("detection %d has no segmentation" % a["id"])
+            if kpt and a.get("keypoints") is None:
+                raise ValueError("detection %d has no keypoints" % a["id"])
+            if kpt and len(a["keypoints"]) != 3 * K:
+                raise ValueError("detection %d has %d keypoint numbers, %d sigmas need %d" % (a["id"], len(a["keypoints"]), K, 3 * K))
             groups.setdefault((k, i), ([], []))[1].append(n)
         return groups
 
@@ -183,19 +233,22 @@ class COCOeval:
         t0 = time.perf_counter()
         groups = self._prepare()
         segm = p.iouType == "segm"
+        kpt = p.iouType == "keypoints"
         ga, da = self.gt.anns, self.dt.anns
         n_gt_all = len(ga)
         if segm:
             d_area_all = np.array([a.get("seg_area", 0.0) for a in da], np.float64)
+        elif kpt:
+            d_area_all = np.array([a.get("kp_area", 0.0) for a in da], np.float64)
         else:
             for a in da:
                 if a["bbox"] is None:
-                    a["bbox"] = a["seg_bbox"]
+                    a["bbox"] = a["seg_bbox"] if "seg_bbox" in a else a["kp_bbox"]
             d_area_all = np.array([a["bbox"][2] * a["bbox"][3] for a in da], np.float64)
         d_score_all = np.array([a["score"] for a in da], np.float64)
         g_area_all = np.array([a["area"] for a in ga], np.float64)
         g_crowd_all = np.array([a["iscrowd"] != 0 for a in ga], np.uint8)
-        g_ign_all = np.array([a["ignore"] != 0 for a in ga], np.uint8)
+        g_ign_all = np.array([a["ignore"] != 0 or (kpt and a.get("num_keypoints", 1) == 0) for a in ga], np.uint8)
         keys = sorted(groups)
         max_det = p.maxDets[-1]
         # per group: gts in annotation order, dets by descending score (stable), cut to maxDets[-1]
@@ -212,7 +265,7 @@ class COCOeval:
                     if da[n]["size"] != sz:
                         raise ValueError("detection %d is %r, its image's ground truth is %r" % (da[n]["id"], da[n]["size"], sz))
         t1 = time.perf_counter()
-        # ---- upload every mask / box once
+        # ---- upload every mask / box / keypoint set once
         if segm:
             used_g = [n for n in range(n_gt_all) if ga[n]["counts"] is not None]
             slot_g = np.full(n_gt_all, -1, np.int64); slot_g[used_g] = np.arange(len(used_g))
@@ -220,6 +273,21 @@ class COCOeval:
                                [ga[n]["size"] for n in used_g] + [a["size"] for a in da])
             slot_d = len(used_g) + np.arange(len(da), dtype=np.int64)
             n_items = rles.M
+        elif kpt:
+            # one item list, gts first: a gt brings keypoints, box and area; of a det only the keypoints are read
+            K = len(p.kpt_oks_sigmas)
+            used_g = [n for n in range(n_gt_all) if ga[n].get("keypoints") is not None and len(ga[n]["keypoints"]) == 3 * K
+                      and ga[n]["bbox"] is not None]
+            used_d = [n for n in range(len(da)) if da[n].get("keypoints") is not None and len(da[n]["keypoints"]) == 3 * K]
+            slot_g = np.full(n_gt_all, -1, np.int64); slot_g[used_g] = np.arange(len(used_g))
+            slot_d = np.full(len(da), -1, np.int64); slot_d[used_d] = len(used_g) + np.arange(len(used_d))
+            n_items = len(used_g) + len(used_d)
+            kp = np.array([ga[n]["keypoints"] for n in used_g] + [da[n]["keypoints"] for n in used_d], np.float64).reshape(n_items, K, 3)
+            kbox = np.zeros((n_items, 4), np.float64); karea = np.zeros(n_items, np.float64)
+            kbox[:len(used_g)] = np.array([ga[n]["bbox"] for n in used_g], np.float64).reshape(-1, 4)
+            karea[:len(used_g)] = g_area_all[used_g]
+            sig = np.asarray(p.kpt_oks_sigmas, np.float64)
+            d_kp = [_ffi.DeviceBuffer.from_numpy(a) for a in (kp, kbox, karea, (sig * 2) ** 2)]
         else:
             used_g = [n for n in range(n_gt_all) if ga[n]["bbox"] is not None]
             slot_g = np.full(n_gt_all, -1, np.int64); slot_g[used_g] = np.arange(len(used_g))
@@ -231,6 +299,7 @@ class COCOeval:
         t2 = time.perf_counter() - (rles.prefix_seconds if segm else 0.0)
         A, T = len(p.areaRng), len(p.iouThrs)
         Dn = np.array([len(d) for d in d_lists], np.int64); Gn = np.array([len(g) for g in g_lists], np.int64)
+        # per pair 12 bytes of pair list and 8 of IoU / OKS; the items (RLEs, boxes, keypoint sets) are uploaded once, outside the chunks
         cost = Dn * Gn * 20 + A * T * (Dn * 5 + Gn * 4) + A * Gn + 64
         self.evalImgs = {}
         self.timings = {"prepare": t1 - t0, "upload": t2 - t1, "prefix": rles.prefix_seconds if segm else 0.0, "iou": 0.0, "match": 0.0,
@@ -260,6 +329,8 @@ class COCOeval:
             d_pairs = _ffi.DeviceBuffer.from_numpy(pairs); d_ious = _ffi.DeviceBuffer((max(P, 1),), np.float64)
             if segm:
                 _ffi.rle_iou_device(rles, d_pairs, P, d_ious)
+            elif kpt:
+                _ffi.oks_device(*d_kp, n_items, K, d_pairs, P, d_ious)
             else:
                 _ffi.bbox_iou_device(d_boxes, n_items, d_pairs, P, d_ious)
             _ffi.sync()
@@ -283,6 +354,9 @@ class COCOeval:
             lo = hi
         if segm:
             rles.free()
+        elif kpt:
+            for b in d_kp:
+                b.free()
         else:
             d_boxes.free()
         self.timings["total"] = time.perf_counter() - t0
@@ -344,7 +418,7 @@ def accumulate(eval_imgs, p):
 
 
 def summarize(ev, p):
-    """-> (stats [12], the twelve lines in upstream's format)."""
+    """-> (stats [12], the twelve lines in upstream's format); under `keypoints` stats [10] and ten lines, all at maxDets[-1] (20)."""
     lines = []
 
     def one(ap, iou_thr=None, area="all", max_dets=None):
@@ -362,6 +436,16 @@ def summarize(ev, p):
             "Average Precision" if ap else "Average Recall", "(AP)" if ap else "(AR)", iou_s, area, max_dets, mean))
         return mean
     md = p.maxDets
+    if p.iouType == "keypoints":
+        stats = np.zeros(10)
+        for ap in (1, 0):
+            o = 0 if ap else 5
+            stats[o + 0] = one(ap, max_dets=md[-1])
+            stats[o + 1] = one(ap, iou_thr=.5, max_dets=md[-1])
+            stats[o + 2] = one(ap, iou_thr=.75, max_dets=md[-1])
+            stats[o + 3] = one(ap, area="medium", max_dets=md[-1])
+            stats[o + 4] = one(ap, area="large", max_dets=md[-1])
+        return stats, lines
     stats = np.zeros(12)
     stats[0] = one(1)
     stats[1] = one(1, iou_thr=.5, max_dets=md[-1])
@@ -379,7 +463,7 @@ def summarize(ev, p):
 
 
 def evaluate_results(gt, results, iou_types=("bbox", "segm"), cat_ids=None, max_dets=None, verbose=False, mem_budget=512 << 20):
-    """One call from a result list (or json path) to {iou_type: stats [12]}."""
+    """One call from a result list (or json path) to {iou_type: stats [12]} ([10] for "keypoints")."""
     gt = gt if isinstance(gt, COCOGt) else COCOGt(gt)
     dt = results if isinstance(results, COCODt) else load_results(gt, results)
     out = {}
