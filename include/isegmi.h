@@ -521,6 +521,21 @@ int isegmi_op_pose2seg_masks(const float* d_logits, const float* d_mmask, const 
                              const int32_t* d_image_hw, int N, int K, int Hmax, int Wmax, int32_t* d_ws_box, uint8_t* d_masks, float* d_boxes,
                              float* d_scores, int32_t* d_labels, int32_t* d_count_out, void* stream);
 
+/* ---- Keypoint R-CNN -> Pose2Seg hand-off (csrc/pose_handoff.hip) ----
+ * One launch, one workgroup per image, all pointers DEVICE memory in the Keypoint R-CNN engine's layouts: d_score [N][cap], d_count [N], d_kpt
+ * [N][cap][NK][3] in network-input coordinates, d_kscore [N][cap][NK], d_ratios_wh [N][2] = (ratio_w, ratio_h) as isegmi_engine_pack_keypoint_records takes
+ * them.  A slot j < d_count[n] is a candidate when score > person_thresh (strict); the min(#candidates, K) best are kept, by score descending, equal scores
+ * by slot ascending -- the input need not be sorted, a surplus is cut.  Keypoint k of a kept person becomes (x * ratio_w, y * ratio_h, v), one fp32
+ * multiplication each, v = 2 when kscore > kp_thresh (strict), else 0.  Outputs: d_kpts_out [R][17][3] compact, image by image (image n's rows start at
+ * the sum of d_count_out[m], m < n; room for N * K rows), d_score_out [N][K] (0 in unused slots), d_src_slot [N][K] int32 (the detection slot a person
+ * came from, -1 unused), d_count_out [N].  The layout does not depend on execution order.  NK must be 17 (ISEGMI_ERR_ARG naming num_keypoints);
+ * cap <= 4096; N * K <= 65535.  NaN scores are outside the contract. */
+int isegmi_op_pose_handoff(const float* d_score, const int32_t* d_count, const float* d_kpt, const float* d_kscore, const float* d_ratios_wh, int N,
+                           int cap, int NK, float person_thresh, float kp_thresh, int K, float* d_kpts_out, float* d_score_out, int32_t* d_src_slot,
+                           int32_t* d_count_out, void* stream);
+/* d_scores_out [N][K] takes d_scores_in [N][K] in the slots k < d_counts[n]; the other slots are left alone */
+int isegmi_op_pose_scores(const float* d_scores_in, const int32_t* d_counts, int N, int K, float* d_scores_out, void* stream);
+
 /* ---- model engine ----
  * Replaces the model object the reference builds inside COCODemo(cfg, ...) (README.md:320-324)
  * and Yolact eval.py (README.md:243): weights are pushed per layer under their upstream
@@ -574,6 +589,25 @@ int isegmi_maskrcnn_paste(isegmi_engine* e, const float* h_ratios_wh, int out_h,
  * fpn_bilinear; fp16 and graph are refused (ISEGMI_ERR_ARG). */
 int isegmi_pose2seg_forward(isegmi_engine* e, const uint8_t* d_u8_staging, const int32_t* h_sizes_hw, const float* d_kpts,
                             const int32_t* h_counts, int N);
+/* The same forward in its two halves, for persons that are produced on the device while the backbone already runs:
+ *   body:    everything that does not depend on the persons -- per-image table, letterbox, ResNet body, FPN down to p2s.p2 -- of the N images;
+ *   persons: template fit ... masks of the body's batch.  d_kpts [R][17][3] device memory, h_counts [N] on the host (they size the activations).
+ *            producer_stream != NULL: d_kpts (and d_scores) were written by work enqueued on that stream so far; the main stream waits for an event
+ *            recorded there instead of for an upload.  d_scores != NULL: [N][max_instances] fp32, det.score takes them in the live slots (k < h_counts[n])
+ *            in place of 1; every other slot and buffer is as isegmi_pose2seg_forward leaves it.
+ * isegmi_pose2seg_forward is body then persons(d_kpts, NULL, h_counts, NULL).  persons without a body of this engine in front is ISEGMI_ERR_STATE.
+ *   wait_persons: host wait until the last persons call that took d_kpts from a producer stream has finished reading it and its d_scores -- and with it
+ *            that step's body and image upload: the WAR point for the producer's next write into d_kpts and for the caller's pinned image buffer, and a
+ *            producer loop's bound on the steps it keeps in flight (two sets of buffers: two steps). */
+int isegmi_pose2seg_body(isegmi_engine* e, const uint8_t* d_u8_staging, const int32_t* h_sizes_hw, int N);
+int isegmi_pose2seg_persons(isegmi_engine* e, const float* d_kpts, const float* d_scores, const int32_t* h_counts, void* producer_stream);
+int isegmi_pose2seg_wait_persons(isegmi_engine* e, const float* d_kpts);
+/* isegmi_op_pose_handoff on the results stream of a Keypoint R-CNN engine (model_kind 2, "keypoint_on" 1), from the det.score / det.count / det.kpt /
+ * det.kscore buffers of its last forward; h_ratios_wh [N][2] on the host as for isegmi_engine_pack_keypoint_records, K = the Pose2Seg engine's
+ * max_instances; the four outputs are the caller's device buffers (N * K rows of keypoints).  An engine without keypoint_on and a call before the first
+ * forward are refused by name.  The caller downloads d_count_out (isegmi_engine_download_async / _wait of THIS engine) to size the Pose2Seg step. */
+int isegmi_engine_pose_handoff(isegmi_engine* kp_engine, const float* h_ratios_wh, float person_thresh, float kp_thresh, int K, float* d_kpts_out,
+                               float* d_score_out, int32_t* d_src_slot, int32_t* d_count_out);
 /* postprocess (Y7): masks of the last forward at (out_h,out_w) -> det.masks u8, det.box_int i64 */
 int isegmi_yolact_postprocess(isegmi_engine* e, int out_h, int out_w);
 /* the same with image n assembled at ITS (h, w) = h_image_hw[n] inside a common plane of the batch's maximum size (a batch of images of

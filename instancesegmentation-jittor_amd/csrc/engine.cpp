@@ -813,6 +813,7 @@ extern "C" int isegmi_engine_destroy(isegmi_engine* h) {
     for (int i = 0; i < Engine::PIN_SLOTS; ++i) if (e.pin_ev[i]) (void)hipEventDestroy(e.pin_ev[i]);
     if (e.pin_ring) (void)hipHostFree(e.pin_ring);
     for (auto& ev : e.step_marks) (void)hipEventDestroy(ev);
+    for (auto& kv : e.p2s_kpts_read) (void)hipEventDestroy(kv.second);
     for (auto& kv : e.convs) {
         if (kv.second.view) continue;
         (void)hipFree(kv.second.d_w); if (kv.second.d_scale) (void)hipFree(kv.second.d_scale); if (kv.second.d_shift) (void)hipFree(kv.second.d_shift);

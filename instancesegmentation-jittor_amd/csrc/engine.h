@@ -131,6 +131,11 @@ struct Engine {
     std::vector<float> last_ratios;
     const void* last_ratios_ptr = nullptr;
     int last_N = 0;
+    // Pose2Seg in two halves: what isegmi_pose2seg_body leaves for isegmi_pose2seg_persons -- the batch's image sizes and P2 -- and, per
+    // device keypoint buffer a producer stream fills, the event behind the last persons call that read it (isegmi_pose2seg_wait_persons)
+    std::vector<int32_t> p2s_hw;
+    Tensor p2s_p2;
+    std::map<const void*, hipEvent_t> p2s_kpts_read;
     // Yolact fp32 "lazy_coeffs": the forward runs only the loc|conf rows of the fused head and computes the mask coefficients of the kept detections on
     // the tail stream; columns [85 A, 117 A) of `headcat` then hold nothing until a fetch of that buffer asks for them (yolact_fill_coeff_columns).
     bool coeff_cols_valid = true;

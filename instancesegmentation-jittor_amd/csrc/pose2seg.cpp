@@ -4,6 +4,8 @@
 // det.label / det.count, so isegmi_engine_rle and isegmi_engine_pack_coco_records work as for Mask R-CNN (fp32 boxes, i32 labels).
 //
 // Params: max_instances (32; the record capacity K), cat_skeleton (1), align_corners (0), warp_round_u8 (1), swap_rb (0), fpn_bilinear (0 = nearest x2).
+// The forward is two halves: isegmi_pose2seg_body, everything up to p2s.p2, and isegmi_pose2seg_persons, fit ... masks, which may take
+// keypoints and scores another engine's stream wrote on the device; isegmi_pose2seg_forward is the two in sequence.
 // fp16 and graph are refused.  Layers (isegmi_engine_set_conv, BN folded): backbone.conv1 (Cin 4), backbone.layers.L.B.{conv1,conv2,conv3,downsample.0},
 // fpn.lateral2..5, fpn.output2, segnet.conv1 (Cin = the RoI tensor's channels), segnet.stage1.B.*, segnet.stage2.B.*, segnet.conv_out; tensor
 // pose_templates [T][17][3] fp32.
@@ -46,30 +48,32 @@ static int p2s_stage(Engine& e, const void* h, size_t bytes, void* d) {
     return ISEGMI_OK;
 }
 
-static int pose2seg_forward(Engine& e, const uint8_t* d_u8, const int32_t* h_hw, const float* d_kpts, const int32_t* h_counts, int N) {
-    const int K = pose2seg_det_cap(e);
+// m1 of an image in fp64 (the restatement's m1_of): into the 512 x 512 input plane, centred at the largest scale that fits
+static void p2s_m1(int h, int w, double m1[6]) {
+    const double s = std::min(512.0 / w, 512.0 / h);
+    const double tx = 256.0 - s * w / 2.0, ty = 256.0 - s * h / 2.0;
+    const double m[6] = {s, 0.0, tx, 0.0, s, ty};
+    for (int i = 0; i < 6; ++i) m1[i] = m[i];
+}
+
+// The half of the forward that does not depend on the persons: per-image table, letterbox, ResNet body, FPN down to p2s.p2 (left in e.p2s_p2 / e.p2s_hw)
+static int pose2seg_body(Engine& e, const uint8_t* d_u8, const int32_t* h_hw, int N) {
     const bool cat = e.param("cat_skeleton", 1.0f) != 0.0f;
     e.cur = e.stream;
-    // per-image table of the letterbox and the fit: m1 in fp64 (the restatement's m1_of), its inverse rounded to fp32
+    e.p2s_hw.clear();
+    // per-image table of the letterbox: the inverse of m1 rounded to fp32
     std::vector<isegmi_p2s_image> table(N);
-    std::vector<double> m1s((size_t)N * 6);
-    std::vector<int32_t> roi_img, roi_off(N);
     int64_t off = 0;
-    int Hmax = 0, Wmax = 0, R = 0;
     for (int n = 0; n < N; ++n) {
         const int h = h_hw[2 * n], w = h_hw[2 * n + 1];
-        const double s = std::min(512.0 / w, 512.0 / h);
-        const double tx = 256.0 - s * w / 2.0, ty = 256.0 - s * h / 2.0;
-        const double m1[6] = {s, 0.0, tx, 0.0, s, ty};
+        double m1[6];
+        p2s_m1(h, w, m1);
+        const double s = m1[0], tx = m1[2], ty = m1[5];
         const double mi[6] = {1.0 / s, 0.0, -tx / s, 0.0, 1.0 / s, -ty / s};
         memset(&table[n], 0, sizeof(table[n]));
         table[n].offset = off; table[n].h = h; table[n].w = w;
-        for (int i = 0; i < 6; ++i) { table[n].minv[i] = (float)mi[i]; m1s[(size_t)n * 6 + i] = m1[i]; }
+        for (int i = 0; i < 6; ++i) table[n].minv[i] = (float)mi[i];
         off += (int64_t)h * w * 3;
-        Hmax = std::max(Hmax, h); Wmax = std::max(Wmax, w);
-        roi_off[n] = R;
-        for (int k = 0; k < h_counts[n]; ++k) roi_img.push_back(n);
-        R += h_counts[n];
     }
     void* q;
     TRY(eng_buf(e, "p2s.table", (int64_t)e.max_batch * sizeof(isegmi_p2s_image), &q, 2));
@@ -112,6 +116,32 @@ static int pose2seg_forward(Engine& e, const uint8_t* d_u8, const int32_t* h_hw,
     const int croi = cat ? p2.C + 64 : p2.C;
     auto c1 = e.convs.find("segnet.conv1");
     if (c1 == e.convs.end() || c1->second.Cin != croi) { set_error("pose2seg: segnet.conv1 must take " + std::to_string(croi) + " input channels"); return ISEGMI_ERR_STATE; }
+    e.p2s_p2 = p2;
+    e.p2s_hw.assign(h_hw, h_hw + 2 * N);
+    return ISEGMI_OK;
+}
+
+// The half that does: template fit, Affine-Align, skeleton features, SegModule, masks -- of the batch the last pose2seg_body ran.  `producer`: the stream
+// whose work so far wrote d_kpts / d_scores (the hand-off); the main stream waits for an event recorded there, which takes the place of eng_wait_upload.
+static int pose2seg_persons(Engine& e, const float* d_kpts, const float* d_scores, const int32_t* h_counts, hipStream_t producer) {
+    const int K = pose2seg_det_cap(e);
+    const bool cat = e.param("cat_skeleton", 1.0f) != 0.0f;
+    const int N = (int)(e.p2s_hw.size() / 2);
+    const int32_t* h_hw = e.p2s_hw.data();
+    const Tensor p2 = e.p2s_p2;
+    const int croi = cat ? p2.C + 64 : p2.C;
+    e.cur = e.stream;
+    std::vector<double> m1s((size_t)N * 6);
+    std::vector<int32_t> roi_img, roi_off(N);
+    int Hmax = 0, Wmax = 0, R = 0;
+    for (int n = 0; n < N; ++n) {
+        p2s_m1(h_hw[2 * n], h_hw[2 * n + 1], &m1s[(size_t)n * 6]);
+        Hmax = std::max(Hmax, h_hw[2 * n]); Wmax = std::max(Wmax, h_hw[2 * n + 1]);
+        roi_off[n] = R;
+        for (int k = 0; k < h_counts[n]; ++k) roi_img.push_back(n);
+        R += h_counts[n];
+    }
+    void* q;
     // fit, Affine-Align, skeleton -> RoI tensor; SegModule -> logits
     const int Rb = R > 0 ? R : 1;
     float *m3, *G, *mm, *kal;
@@ -132,7 +162,14 @@ static int pose2seg_forward(Engine& e, const uint8_t* d_u8, const int32_t* h_hw,
         TRY(eng_buf(e, "p2s.m1", (int64_t)e.max_batch * 48, &q));
         double* d_m1 = (double*)q;
         TRY(p2s_stage(e, m1s.data(), (size_t)N * 48, d_m1));
-        TRY(eng_wait_upload(e, d_kpts, (int64_t)R * 204, e.stream));
+        if (producer) {
+            hipEvent_t ev;
+            TRY(eng_next_event(e, &ev));
+            HIP_TRY(hipEventRecord(ev, producer));
+            HIP_TRY(hipStreamWaitEvent(e.stream, ev, 0));
+        } else {
+            TRY(eng_wait_upload(e, d_kpts, (int64_t)R * 204, e.stream));
+        }
         TRY(isegmi_op_pose2seg_fit(d_kpts, d_ri, R, d_m1, (const float*)tp->second.d, (int)(tp->second.bytes / 204), (int)e.param("align_corners", 0.0f),
                                    m3, G, mm, kal, fit, e.stream));
         Tensor roi;
@@ -172,6 +209,12 @@ static int pose2seg_forward(Engine& e, const uint8_t* d_u8, const int32_t* h_hw,
         TRY(isegmi_op_pose2seg_masks(logits.d, mm, (const int32_t*)d_cnt, (const int32_t*)d_off, (const int32_t*)d_hw, N, K, Hmax, Wmax, (int32_t*)ws,
                                      (uint8_t*)masks, (float*)boxes, (float*)scores, (int32_t*)labels, (int32_t*)cnt_out, e.stream));
     }
+    if (d_scores && R > 0) TRY(isegmi_op_pose_scores(d_scores, (const int32_t*)d_cnt, N, K, (float*)scores, e.stream));
+    if (producer && d_kpts) {   // the last read of the producer's buffers: what isegmi_pose2seg_wait_persons waits for
+        hipEvent_t& ev = e.p2s_kpts_read[d_kpts];
+        if (ev == nullptr) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(ev, e.stream));
+    }
     return ISEGMI_OK;
 }
 
@@ -179,9 +222,8 @@ static int pose2seg_forward(Engine& e, const uint8_t* d_u8, const int32_t* h_hw,
 
 using namespace isegmi;
 
-extern "C" int isegmi_pose2seg_forward(isegmi_engine* h, const uint8_t* d_u8_staging, const int32_t* h_sizes_hw, const float* d_kpts,
-                                       const int32_t* h_counts, int N) {
-    ARG_CHECK(h && d_u8_staging && h_sizes_hw && h_counts, "null");
+static int p2s_check_body(isegmi_engine* h, const uint8_t* d_u8_staging, const int32_t* h_sizes_hw, int N) {
+    ARG_CHECK(h && d_u8_staging && h_sizes_hw, "null");
     Engine& e = h->e;
     ARG_CHECK(e.kind == 3, "engine is not a Pose2Seg engine");
     ARG_CHECK(N > 0 && N <= e.max_batch, "batch size");
@@ -189,9 +231,14 @@ extern "C" int isegmi_pose2seg_forward(isegmi_engine* h, const uint8_t* d_u8_sta
     if (e.param("graph", 0.0f) != 0.0f) { set_error("pose2seg: graph capture is not supported (graph must be 0)"); return ISEGMI_ERR_ARG; }
     const int K = pose2seg_det_cap(e);
     ARG_CHECK(K >= 1 && (int64_t)e.max_batch * K <= 65535, "max_instances");
+    for (int n = 0; n < N; ++n) ARG_CHECK(h_sizes_hw[2 * n] > 0 && h_sizes_hw[2 * n + 1] > 0, "image sizes");
+    return ISEGMI_OK;
+}
+
+static int p2s_check_persons(Engine& e, const float* d_kpts, const int32_t* h_counts, int N) {
+    const int K = pose2seg_det_cap(e);
     int R = 0;
     for (int n = 0; n < N; ++n) {
-        ARG_CHECK(h_sizes_hw[2 * n] > 0 && h_sizes_hw[2 * n + 1] > 0, "image sizes");
         if (h_counts[n] < 0 || h_counts[n] > K) {
             char b[160];
             snprintf(b, sizeof(b), "pose2seg: image %d has %d persons, more than max_instances = %d", n, h_counts[n], K);
@@ -201,7 +248,44 @@ extern "C" int isegmi_pose2seg_forward(isegmi_engine* h, const uint8_t* d_u8_sta
         R += h_counts[n];
     }
     ARG_CHECK(R == 0 || d_kpts, "keypoints");
-    const int rc = pose2seg_forward(e, d_u8_staging, h_sizes_hw, d_kpts, h_counts, N);
+    return ISEGMI_OK;
+}
+
+extern "C" int isegmi_pose2seg_forward(isegmi_engine* h, const uint8_t* d_u8_staging, const int32_t* h_sizes_hw, const float* d_kpts,
+                                       const int32_t* h_counts, int N) {
+    ARG_CHECK(h_counts, "null");
+    TRY(p2s_check_body(h, d_u8_staging, h_sizes_hw, N));
+    Engine& e = h->e;
+    TRY(p2s_check_persons(e, d_kpts, h_counts, N));
+    TRY(pose2seg_body(e, d_u8_staging, h_sizes_hw, N));
+    const int rc = pose2seg_persons(e, d_kpts, nullptr, h_counts, nullptr);
+    e.p2s_hw.clear();   // one persons half per body
+    if (rc != ISEGMI_OK) return rc;
+    e.last_N = N;
+    return ISEGMI_OK;
+}
+
+extern "C" int isegmi_pose2seg_body(isegmi_engine* h, const uint8_t* d_u8_staging, const int32_t* h_sizes_hw, int N) {
+    TRY(p2s_check_body(h, d_u8_staging, h_sizes_hw, N));
+    return pose2seg_body(h->e, d_u8_staging, h_sizes_hw, N);
+}
+
+extern "C" int isegmi_pose2seg_persons(isegmi_engine* h, const float* d_kpts, const float* d_scores, const int32_t* h_counts, void* producer_stream) {
+    ARG_CHECK(h && h_counts, "null");
+    Engine& e = h->e;
+    ARG_CHECK(e.kind == 3, "engine is not a Pose2Seg engine");
+    if (e.p2s_hw.empty()) { set_error("pose2seg_persons: no body of this batch: call isegmi_pose2seg_body first"); return ISEGMI_ERR_STATE; }
+    const int N = (int)(e.p2s_hw.size() / 2);
+    TRY(p2s_check_persons(e, d_kpts, h_counts, N));
+    const int rc = pose2seg_persons(e, d_kpts, d_scores, h_counts, (hipStream_t)producer_stream);
+    e.p2s_hw.clear();   // one persons half per body
     if (rc == ISEGMI_OK) e.last_N = N;
     return rc;
+}
+
+extern "C" int isegmi_pose2seg_wait_persons(isegmi_engine* h, const float* d_kpts) {
+    ARG_CHECK(h && d_kpts, "null");
+    auto it = h->e.p2s_kpts_read.find(d_kpts);
+    if (it != h->e.p2s_kpts_read.end()) HIP_TRY(hipEventSynchronize(it->second));
+    return ISEGMI_OK;
 }

@@ -297,6 +297,36 @@ extern "C" int isegmi_engine_pack_keypoint_records(isegmi_engine* h, const float
     return pack_box_family(h, h_ratios_wh, d_dst, cap, n_block, bytes, true);
 }
 
+// Keypoint R-CNN -> Pose2Seg: isegmi_op_pose_handoff over the last forward's det.* buffers on the results stream, into the caller's buffers
+extern "C" int isegmi_engine_pose_handoff(isegmi_engine* h, const float* h_ratios_wh, float person_thresh, float kp_thresh, int K, float* d_kpts_out,
+                                          float* d_score_out, int32_t* d_src_slot, int32_t* d_count_out) {
+    ARG_CHECK(h && h_ratios_wh && d_kpts_out && d_score_out && d_src_slot && d_count_out, "null");
+    Engine& e = h->e;
+    ARG_CHECK(e.kind == 2, "pose_handoff: engine is not a Mask R-CNN-family engine");
+    ARG_CHECK(maskrcnn_keypoint_on(e), "pose_handoff: the engine has no keypoint head (keypoint_on 0, MODEL.KEYPOINT_ON False)");
+    const int N = e.last_N;
+    ARG_CHECK(N > 0, "pose_handoff before forward");
+    const int cap = det_cap(e), NK = maskrcnn_num_keypoints(e);
+    const char* names[4] = {"det.score", "det.count", "det.kpt", "det.kscore"};
+    const int64_t need[4] = {(int64_t)N * cap * 4, (int64_t)N * 4, (int64_t)N * cap * NK * 12, (int64_t)N * cap * NK * 4};
+    void* src[4];
+    for (int i = 0; i < 4; ++i) {
+        auto it = e.bufs.find(names[i]);
+        if (it == e.bufs.end() || it->second.d == nullptr || it->second.bytes < need[i]) { set_error(std::string("pose_handoff: buffer not produced yet: ") + names[i]); return ISEGMI_ERR_STATE; }
+        src[i] = it->second.d;
+    }
+    hipStream_t rs = eng_results_stream(e);
+    void* rt;
+    TRY(maskrcnn_stage_ratios(e, h_ratios_wh, N, rs, &rt));
+    {
+        OpScope op(e, rs, "pose hand-off (threshold, rank, scale)", (double)N * cap * (4 + NK * 16));
+        TRY(isegmi_op_pose_handoff((const float*)src[0], (const int32_t*)src[1], (const float*)src[2], (const float*)src[3], (const float*)rt, N, cap, NK,
+                                   person_thresh, kp_thresh, K, d_kpts_out, d_score_out, d_src_slot, d_count_out, rs));
+    }
+    if (rs == e.tail && e.tail) HIP_TRY(hipEventRecord(e.tail_done, e.tail));   // reads det.*: extend the WAR fence
+    return ISEGMI_OK;
+}
+
 extern "C" int isegmi_engine_pack_coco_records(isegmi_engine* h, void* d_dst, int64_t cap, int n_block, int64_t* bytes) {
     ARG_CHECK(h && d_dst && bytes, "null");
     Engine& e = h->e;

@@ -980,6 +980,13 @@ _P2S_SIGS = {
     "isegmi_op_pose2seg_align": [_VP, _I32, _I32, _I32, _VP, _VP, _I32, _VP, _I32, _VP],
     "isegmi_op_pose2seg_skeleton": [_VP, _I32, _VP, _I32, _I32, _VP],
     "isegmi_op_pose2seg_masks": [_VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+    # the Keypoint R-CNN -> Pose2Seg hand-off (csrc/pose_handoff.hip) and the forward in two halves
+    "isegmi_op_pose_handoff": [_VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, C.c_float, C.c_float, _I32, _VP, _VP, _VP, _VP, _VP],
+    "isegmi_op_pose_scores": [_VP, _VP, _I32, _I32, _VP, _VP],
+    "isegmi_pose2seg_body": [_VP, _VP, _VP, _I32],
+    "isegmi_pose2seg_persons": [_VP, _VP, _VP, _VP, _VP],
+    "isegmi_pose2seg_wait_persons": [_VP, _VP],
+    "isegmi_engine_pose_handoff": [_VP, _VP, C.c_float, C.c_float, _I32, _VP, _VP, _VP, _VP],
 }
 
 
@@ -1017,6 +1024,26 @@ def p2s_masks(d_logits, d_mmask, d_counts, d_roi_off, d_image_hw, N, K, Hmax, Wm
     check(p2s_fn("isegmi_op_pose2seg_masks")(_ptr(d_logits), _ptr(d_mmask), _ptr(d_counts), _ptr(d_roi_off), _ptr(d_image_hw), int(N), int(K),
                                              int(Hmax), int(Wmax), _ptr(d_ws_box), _ptr(d_masks), _ptr(d_boxes), _ptr(d_scores), _ptr(d_labels),
                                              _ptr(d_count_out), stream))
+
+
+def pose_handoff(score, count, kpt, kscore, ratios_wh, person_thresh, kp_thresh, K, poison=True):
+    """isegmi_op_pose_handoff on host arrays (tests, diagnostics): score [N, cap], count [N], kpt [N, cap, NK, 3], kscore [N, cap, NK], ratios_wh [N, 2] ->
+    (kpts_out [N * K, 17, 3] -- the first count_out.sum() rows are the persons --, score_out [N, K], src_slot [N, K], count_out [N]).  The outputs start
+    out as 0xFF bytes (`poison`), so a slot the kernel did not write shows."""
+    score = np.ascontiguousarray(score, np.float32)
+    N, cap = score.shape
+    kpt = np.ascontiguousarray(kpt, np.float32)
+    NK = kpt.shape[2]
+    ins = [DeviceBuffer.from_numpy(a) for a in (score, np.ascontiguousarray(count, np.int32), kpt, np.ascontiguousarray(kscore, np.float32),
+                                                np.ascontiguousarray(ratios_wh, np.float32))]
+    outs = [DeviceBuffer((N * K, 17, 3)), DeviceBuffer((N, K)), DeviceBuffer((N, K), np.int32), DeviceBuffer((N,), np.int32)]
+    if poison:
+        for o in outs:
+            o.poison()
+    check(p2s_fn("isegmi_op_pose_handoff")(*[b.ptr for b in ins], int(N), int(cap), int(NK), float(person_thresh), float(kp_thresh), int(K),
+                                           *[b.ptr for b in outs], None))
+    sync()
+    return tuple(o.numpy() for o in outs)
 
 
 # ---------------------------------------------------------------- COCO evaluation on the device (csrc/cocoeval.hip; DESIGN.md section 10)

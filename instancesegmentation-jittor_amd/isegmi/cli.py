@@ -4,6 +4,7 @@
   python -m isegmi.cli eval --trained_model=weights.npz --images=in_dir:out_dir [--output_coco_json=dets.json]
   python -m isegmi.cli test_net --config-file cfg.yaml [--images dir] [--output results.json]
   python -m isegmi.cli pose2seg_test --weights random --anno person_keypoints.json --image-root DIR [--output segm.json] [--batch-size 8]
+  python -m isegmi.cli pose2seg_test --weights random --keypoint-config kp.yaml --keypoint-weights random|FILE --anno images.json --image-root DIR
   python -m isegmi.cli coco_eval --gt instances.json --dt results.json --iou-type segm|bbox|keypoints [--cat-ids ...] [--max-dets ...] [--out stats.json]
 
 eval, test_net and pose2seg_test take an optional `--gt instances.json`: after writing their json they print the COCO AP / AR summary.
@@ -169,9 +170,11 @@ def cmd_pose2seg_test(a):
         sd = dict(np.load(a.weights))
     else:
         raise SystemExit("%s: Pose2Seg takes .npz weights in this engine's names (importing last.pkl is out of scope)" % a.weights)
+    _, _, local = _rank_world()
+    if hasattr(a, "keypoint_config") or hasattr(a, "keypoint_weights"):
+        return _pose2seg_from_detector(a, sd, local)
     images, kps = read_person_keypoints(a.anno)
     images = [im for im in images if im["id"] in kps]
-    _, _, local = _rank_world()
     net = Pose2Seg(sd, Pose2SegConfig(), max_batch=a.batch_size, max_instances=a.max_instances, device=local)
     results = test(net, lambda i: _load_image_bgr(os.path.join(a.image_root, images[i]["file_name"])), [kps[im["id"]] for im in images],
                    [im["id"] for im in images], batch_size=a.batch_size)
@@ -179,6 +182,50 @@ def cmd_pose2seg_test(a):
     with open(a.output, "w") as f:
         json.dump(results, f)
     print("wrote %d person masks for %d images to %s" % (len(results), len(images), a.output))
+    if a.gt:
+        _print_coco_summary(a.gt, results, ("segm",))
+    return results
+
+
+def _pose2seg_from_detector(a, sd, local):
+    """pose2seg_test with --keypoint-config / --keypoint-weights: --anno supplies only the image list, a Keypoint R-CNN finds the persons and their
+    keypoints; every entry's score is the detection's box score."""
+    from .config import cfg, is_keypoint_rcnn, to_keypointrcnn_config
+    from .maskrcnn import MaskRCNN
+    from .pose2seg import KeypointPose2Seg, Pose2Seg, Pose2SegConfig, test_from_images
+    if not getattr(a, "keypoint_config", None):
+        raise SystemExit("--keypoint-weights needs --keypoint-config YAML (the Keypoint R-CNN's config)")
+    c = cfg.clone()
+    c.merge_from_file(a.keypoint_config)
+    c.merge_from_list(getattr(a, "keypoint_opts", []))
+    if not is_keypoint_rcnn(c):
+        raise SystemExit("%s: MODEL.KEYPOINT_ON is False; --keypoint-config takes a Keypoint R-CNN config" % a.keypoint_config)
+    mc = to_keypointrcnn_config(c)
+    spec = getattr(a, "keypoint_weights", "random") or "random"
+    if spec == "random":
+        from .weights import random_maskrcnn_state_dict
+        ksd = random_maskrcnn_state_dict(mc, 1234)
+    elif spec.endswith(".npz"):
+        ksd = dict(np.load(spec))
+    else:
+        raise SystemExit("%s: convert upstream .pth/.pkl with tools/import_pth.py first" % spec)
+    with open(a.anno) as f:
+        images = list(json.load(f).get("images", []))
+    d = mc.SIZE_DIVISIBILITY
+    side = -(-max(mc.MIN_SIZE_TEST, mc.MAX_SIZE_TEST) // d) * d
+    det = MaskRCNN(ksd, side, side, cfg=mc, max_batch=a.batch_size, device=local)
+    net = Pose2Seg(sd, Pose2SegConfig(), max_batch=a.batch_size, max_instances=a.max_instances, device=local)
+    pipe = KeypointPose2Seg(det, net, person_threshold=getattr(a, "person_threshold", 0.5), keypoint_threshold=getattr(a, "keypoint_threshold", 2.0))
+    try:
+        results = test_from_images(pipe, lambda i: _load_image_bgr(os.path.join(a.image_root, images[i]["file_name"])), [im["id"] for im in images],
+                                   batch_size=a.batch_size)
+    finally:
+        pipe.close()
+        net.close()
+        det.close()
+    with open(a.output, "w") as f:
+        json.dump(results, f)
+    print("wrote %d person masks for %d images to %s (persons from the keypoint detector)" % (len(results), len(images), a.output))
     if a.gt:
         _print_coco_summary(a.gt, results, ("segm",))
     return results
@@ -228,6 +275,14 @@ def build_parser():
     p.add_argument("--output", default="segm.json")
     p.add_argument("--batch-size", dest="batch_size", type=int, default=8)
     p.add_argument("--max-instances", dest="max_instances", type=int, default=32)
+    # the detector flags leave no attribute behind unless given: without them the command is the one it was
+    p.add_argument("--keypoint-config", dest="keypoint_config", default=argparse.SUPPRESS,
+                   help="Keypoint R-CNN yaml: the persons and their keypoints come from this detector, --anno then supplies only the image list")
+    p.add_argument("--keypoint-weights", dest="keypoint_weights", default=argparse.SUPPRESS, help="random or FILE (.npz) for the detector of --keypoint-config")
+    p.add_argument("--keypoint-opts", dest="keypoint_opts", nargs="*", default=argparse.SUPPRESS, help="KEY VALUE pairs merged into the detector's config, as test_net's opts")
+    p.add_argument("--person-threshold", dest="person_threshold", type=float, default=argparse.SUPPRESS, help="with --keypoint-config: keep detections with score > this")
+    p.add_argument("--keypoint-threshold", dest="keypoint_threshold", type=float, default=argparse.SUPPRESS,
+                   help="with --keypoint-config: a keypoint is visible where its logit > this")
     for q in (e, t, p):
         q.add_argument("--gt", default=None, help="COCO annotation json: print the COCO AP / AR summary of the written results (isegmi.cocoeval)")
     c = sub.add_parser("coco_eval", help="COCO AP / AR of a result json against an annotation json (pycocotools COCOeval restated)")

@@ -259,7 +259,8 @@ def results_from_records(rec, image_ids, image_hw, kind, K=100, score_threshold=
     same records maskrcnn_results / yolact_results build from host arrays: bbox conversion and category map here, `segmentation.counts`
     straight from the device-made strings.  image_ids / image_hw: per image slot of the batch (None id = an empty padding slot).
     score_threshold / top_k (Yolact eval.py --score_threshold / --top_k): keep score > threshold, then the first top_k (score order).
-    kind: 1 Yolact, 2 Mask R-CNN, 3 Pose2Seg (category 1, score 1.0, bbox = the mask's tight box).  A box-only block (Faster R-CNN: no str_off in
+    kind: 1 Yolact, 2 Mask R-CNN, 3 Pose2Seg (category 1, bbox = the mask's tight box; the score is the record's, like every kind's: 1.0 as
+    isegmi_pose2seg_forward writes it, the detection's box score from a KeypointPose2Seg step).  A box-only block (Faster R-CNN: no str_off in
     `rec`) gives bbox-only results without a `segmentation` key; a keypoint block (Keypoint R-CNN: `kpt` in `rec`) adds `keypoints`, NK * 3 numbers x, y, v.
     categories (kind 2): a label_categories() list, default the 80 COCO classes."""
     out = []

@@ -676,6 +676,21 @@ class MaskRCNN:
         _ffi.check(_ffi.lib().isegmi_engine_pack_keypoint_records(self._h, r.ctypes.data_as(C.c_void_p), dev_buffer.ptr, C.c_int64(dev_buffer.nbytes), int(n_block), C.byref(nb)))
         return nb.value
 
+    def pose_handoff(self, person_threshold, keypoint_threshold, K, d_kpts, d_score, d_slot, d_count):
+        """isegmi_engine_pose_handoff: the last forward's persons as Pose2Seg takes them, keypoints in the coordinates set_output_sizes
+        named, into four device buffers ([n * K, 17, 3] f32, [n, K] f32, [n, K] i32, [n] i32) on the results stream.  -> the ratios used."""
+        n = self._hw.shape[0] if self._hw is not None else self.max_batch   # before the first upload the engine refuses by name
+        r = self._ratios if self._ratios is not None and self._ratios.shape[0] == n else np.ones((n, 2), np.float32)
+        _ffi.check(_ffi.p2s_fn("isegmi_engine_pose_handoff")(self._h, r.ctypes.data_as(C.c_void_p), float(person_threshold), float(keypoint_threshold), int(K),
+                                                             d_kpts.ptr, d_score.ptr, d_slot.ptr, d_count.ptr))
+        return r
+
+    def results_stream(self):
+        """the stream the last forward's results (and everything packed or handed off from them) complete on"""
+        st = C.c_void_p()
+        _ffi.check(_ffi.lib().isegmi_engine_stream(self._h, C.byref(st)))
+        return st
+
     def sync(self):
         _ffi.check(_ffi.lib().isegmi_engine_sync(self._h))
 

@@ -5,6 +5,13 @@ in, one mask per person out.  The contract is DESIGN.md section 9.
     masks = net([img_bgr_u8, ...], [kpts (n, 17, 3), ...])      # per image a list of (h, w) uint8 masks
     results = test(net, images, keypoints, image_ids)            # COCO segmentation dicts, category 1, score 1.0
 
+Without annotations a Keypoint R-CNN finds the persons: its keypoints reach Pose2Seg on the device, only the person counts
+come to the host.
+
+    pipe = KeypointPose2Seg(keypoint_model, net, person_threshold=0.5, keypoint_threshold=2.0)
+    for masks, boxes, scores, kpts in pipe([img_bgr_u8, ...]): ...   # per image: (h, w) uint8 masks, tight boxes, box scores, the (n, 17, 3) keypoints used
+    results = test_from_images(pipe, images, image_ids)          # the same dicts, score = the detection's box score
+
 The model runs on an engine of model_kind 3 (csrc/pose2seg.cpp, isegmi_pose2seg_forward): the fp32 MFMA convolutions for the ResNet-50 body,
 the FPN top-down chain to P2 and the SegModule; csrc/pose2seg_ops.hip for the letterbox, the template fit, Affine-Align, the skeleton
 features and the fused softmax + reverse warp.  Its masks, boxes, RLE and record block are the other models' (isegmi_engine_rle,
@@ -201,6 +208,56 @@ class Pose2Seg:
         return pin, dev
 
     # -- the model ---------------------------------------------------------------------------------------------------------------------
+    def _image_sizes(self, images):
+        hw = []
+        for im in images:
+            im = np.asarray(im)
+            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3 or im.shape[0] < 1 or im.shape[1] < 1:
+                raise TypeError("Pose2Seg takes uint8 [h, w, 3] images")
+            hw.append(im.shape[:2])
+        return hw
+
+    def _upload_images(self, images, hw, slot):
+        """the images back to back through slot `slot`'s pinned buffer on the copy stream -> the device staging buffer"""
+        nbytes = sum(h * w * 3 for h, w in hw)
+        pin, dev = self._staging(slot, 0, nbytes)
+        off = 0
+        for im in images:
+            a = np.ascontiguousarray(im).reshape(-1)
+            pin.array[off:off + a.size] = a
+            off += a.size
+        _ffi.check(_ffi.lib().isegmi_engine_upload_async(self._h, dev.ptr, pin.ptr, C.c_int64(nbytes)))
+        return dev
+
+    def body(self, images, slot=None):
+        """The half of the forward that needs no persons (isegmi_pose2seg_body): upload, letterbox, ResNet body, FPN down to P2.  persons() ends the step."""
+        N = len(images)
+        if not 1 <= N <= self.max_batch:
+            raise ValueError("batch of %d images; this model takes 1..%d" % (N, self.max_batch))
+        hw = self._image_sizes(images)
+        slot = self._slot if slot is None else slot
+        self._slot = 1 - slot
+        dev = self._upload_images(images, hw, slot)
+        hwa = np.ascontiguousarray(hw, np.int32)
+        _ffi.check(_ffi.p2s_fn("isegmi_pose2seg_body")(self._h, dev.ptr, hwa.ctypes.data_as(C.c_void_p), N))
+        self._body = dict(N=N, K=self.max_instances, hw=[tuple(x) for x in hw], Hmax=int(hwa[:, 0].max()), Wmax=int(hwa[:, 1].max()))
+        return self._body
+
+    def persons(self, d_kpts, counts, d_scores=None, producer_stream=None):
+        """The other half (isegmi_pose2seg_persons) of the batch body() enqueued: d_kpts a device buffer [R][17][3] (or its pointer), counts [N] on the
+        host; d_scores [N][max_instances] on the device become det.score of the live slots; producer_stream: the stream that wrote both."""
+        L = getattr(self, "_body", None)
+        if L is None:
+            raise RuntimeError("persons() before body()")
+        counts = np.ascontiguousarray(counts, np.int32).reshape(-1)
+        if counts.shape[0] != L["N"]:
+            raise ValueError("one person count per image of the body's batch (%d), got %d" % (L["N"], counts.shape[0]))
+        ptr = lambda b: None if b is None else getattr(b, "ptr", b)
+        self._body = None
+        _ffi.check(_ffi.p2s_fn("isegmi_pose2seg_persons")(self._h, ptr(d_kpts), ptr(d_scores), counts.ctypes.data_as(C.c_void_p), producer_stream))
+        self.last = dict(L, R=int(counts.sum()), counts=counts)
+        return self.last
+
     def forward(self, images, keypoints, slot=None):
         """Enqueues upload + the whole forward of one batch (isegmi_pose2seg_forward); results stay in the engine's buffers."""
         N = len(images)
@@ -208,7 +265,7 @@ class Pose2Seg:
             raise ValueError("batch of %d images; this model takes 1..%d" % (N, self.max_batch))
         if len(keypoints) != N:
             raise ValueError("one keypoint array per image")
-        kps, hw = [], []
+        kps = []
         for kp in keypoints:
             k = np.zeros((0, 17, 3), np.float32) if kp is None or np.size(kp) == 0 else np.asarray(kp, np.float32)
             if k.ndim == 2:
@@ -218,21 +275,10 @@ class Pose2Seg:
             if k.shape[0] > self.max_instances:
                 raise ValueError("%d persons in one image: more than max_instances = %d" % (k.shape[0], self.max_instances))
             kps.append(k)
-        for im in images:
-            im = np.asarray(im)
-            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3 or im.shape[0] < 1 or im.shape[1] < 1:
-                raise TypeError("Pose2Seg takes uint8 [h, w, 3] images")
-            hw.append(im.shape[:2])
+        hw = self._image_sizes(images)
         slot = self._slot if slot is None else slot
         self._slot = 1 - slot
-        nbytes = sum(h * w * 3 for h, w in hw)
-        pin, dev = self._staging(slot, 0, nbytes)
-        off = 0
-        for im in images:
-            a = np.ascontiguousarray(im).reshape(-1)
-            pin.array[off:off + a.size] = a
-            off += a.size
-        _ffi.check(_ffi.lib().isegmi_engine_upload_async(self._h, dev.ptr, pin.ptr, C.c_int64(nbytes)))
+        dev = self._upload_images(images, hw, slot)
         counts = np.array([k.shape[0] for k in kps], np.int32)
         R = int(counts.sum())
         dk = None
@@ -338,6 +384,160 @@ def test(net, images, keypoints, image_ids, batch_size=None, rank=0, world=1):
                 per_image[i] = by_id.get(image_ids[i], [])
 
     run_record_loop(net, bs, -(-len(batches) // world), enqueue, consume, rank, world)
+    return [d for r in per_image if r for d in r]
+
+
+class KeypointPose2Seg:
+    """KeypointPose2Seg(keypoint_model, pose2seg_net, person_threshold=0.5, keypoint_threshold=2.0): images in, person masks out.
+    keypoint_model is a Keypoint R-CNN engine (isegmi.maskrcnn.MaskRCNN with MODEL.KEYPOINT_ON), pose2seg_net a Pose2Seg; the detector's keypoints reach
+    Pose2Seg on the device (isegmi_engine_pose_handoff: detections with score > person_threshold, the best max_instances of an image by score, a keypoint
+    visible where its logit > keypoint_threshold) -- only the N person counts come to the host, while Pose2Seg's backbone already runs.  The defaults are
+    the reference README's confidence_threshold and vis_keypoints' kp_thresh.  Images are uint8 [h, w, 3] BGR; the detector sees them resized as COCODemo
+    resizes them (MIN_SIZE_TEST / MAX_SIZE_TEST of its config unless given), Pose2Seg the originals."""
+
+    def __init__(self, keypoint_model, pose2seg_net, person_threshold=0.5, keypoint_threshold=2.0, min_image_size=None, max_image_size=None):
+        det, net = keypoint_model, pose2seg_net
+        if not getattr(det, "keypoint_on", False):
+            raise ValueError("KeypointPose2Seg: the detector has no keypoint head (MODEL.KEYPOINT_ON False)")
+        if int(det.cfg.NUM_KEYPOINTS) != 17:
+            raise ValueError("KeypointPose2Seg: Pose2Seg takes COCO's 17 keypoints, the detector has num_keypoints = %d" % det.cfg.NUM_KEYPOINTS)
+        self.det, self.net = det, net
+        self.person_threshold, self.keypoint_threshold = float(person_threshold), float(keypoint_threshold)
+        self.min_image_size = int(det.cfg.MIN_SIZE_TEST if min_image_size is None else min_image_size)
+        self.max_image_size = int(det.cfg.MAX_SIZE_TEST if max_image_size is None else max_image_size)
+        self.max_batch, self.max_instances = min(det.max_batch, net.max_batch), net.max_instances
+        B, K = self.max_batch, self.max_instances
+        # two slots of hand-off outputs: step t + 1's detector may write while Pose2Seg still reads step t's persons
+        self._out = [dict(kpts=_ffi.DeviceBuffer((B * K, 17, 3)), score=_ffi.DeviceBuffer((B, K)), slot=_ffi.DeviceBuffer((B, K), np.int32),
+                          count=_ffi.DeviceBuffer((B,), np.int32), pin=_ffi.PinnedBuffer((B,), np.int32), u8=None) for _ in range(2)]
+        self._slot = 0
+        self.last = {}
+
+    # the record loop (isegmi.pipeline.run_record_loop) drives the Pose2Seg engine, where the results are
+    KIND = Pose2Seg.KIND
+    cfg = property(lambda self: self.net.cfg)
+
+    def __getattr__(self, name):
+        if name in ("set_param", "rle_device", "coco_record_bytes", "pack_coco_records", "download_async", "download_fence", "download_wait", "read"):
+            return getattr(self.net, name)
+        raise AttributeError(name)
+
+    def sync(self):
+        self.det.sync()
+        self.net.sync()
+
+    def forward(self, images_bgr_u8, slot=None):
+        """Enqueues one batch: detector -> hand-off -> (Pose2Seg body, then the count download is waited for) -> Pose2Seg persons.  The results stay in the
+        Pose2Seg engine's buffers (masks / boxes / scores / count; collect(), rle_device(), the record block)."""
+        from .transforms import maskrcnn_resize_u8
+        N = len(images_bgr_u8)
+        if not 1 <= N <= self.max_batch:
+            raise ValueError("batch of %d images; this pipeline takes 1..%d" % (N, self.max_batch))
+        det, net, K = self.det, self.net, self.max_instances
+        hw = net._image_sizes(images_bgr_u8)
+        slot = self._slot if slot is None else int(slot)
+        self._slot = 1 - slot
+        o = self._out[slot]
+        # this slot's last step (the one before last) is through: its hand-off buffers and both engines' pinned image buffers may be written again
+        _ffi.check(_ffi.p2s_fn("isegmi_pose2seg_wait_persons")(net._h, o["kpts"].ptr))
+        resized = [maskrcnn_resize_u8(np.asarray(im), self.min_image_size, self.max_image_size) for im in images_bgr_u8]
+        nbytes = sum(r.size for r in resized)
+        if o["u8"] is None or o["u8"].nbytes < nbytes:
+            self.sync()
+            if o["u8"] is not None:
+                o["u8"].free()
+            o["u8"] = _ffi.PinnedBuffer((nbytes,), np.uint8)
+        off = 0
+        for r in resized:
+            o["u8"].array[off:off + r.size] = r.reshape(-1)
+            off += r.size
+        det.upload_u8_async(o["u8"], [r.shape[:2] for r in resized], slot)
+        det.forward_device(N, slot)
+        det.set_output_sizes([(w, h) for h, w in hw])   # the keypoints leave in the originals' coordinates, as the keypoint records do
+        producer = det.results_stream()
+        ratios = det.pose_handoff(self.person_threshold, self.keypoint_threshold, K, o["kpts"], o["score"], o["slot"], o["count"])
+        det.download_async(slot, o["pin"], o["count"], N * 4)
+        net.body(images_bgr_u8, slot)                  # enqueued BEFORE the wait: the counts come down behind the 512 x 512 backbone
+        det.download_wait(slot)
+        counts = np.array(o["pin"].array[:N], np.int32)
+        net.persons(o["kpts"], counts, o["score"], producer)
+        self.last = dict(net.last, slot=slot, ratios=ratios)
+        return self.last
+
+    def collect(self):
+        """-> per image (masks [list of (h, w) uint8], tight boxes [n, 4], scores [n], keypoints [n, 17, 3] as Pose2Seg took them) of the last forward"""
+        L, K = self.last, self.max_instances
+        masks, boxes = self.net.collect()
+        N, counts = L["N"], L["counts"]
+        scores = self.net.read("scores", (N, K))
+        o = self._out[L["slot"]]
+        kp = o["kpts"].numpy()[:int(counts.sum())]
+        off = np.concatenate([[0], np.cumsum(counts)])
+        return [(masks[n], boxes[n], scores[n, :int(counts[n])].copy(), kp[off[n]:off[n + 1]].copy()) for n in range(N)]
+
+    def source_slots(self):
+        """[N, K] int32: the detection slot of the detector's last forward each person came from (-1: unused); joins boxes and labels back"""
+        self.sync()
+        return self._out[self.last["slot"]]["slot"].numpy()[:self.last["N"]]
+
+    def __call__(self, images_bgr_u8):
+        self.forward(images_bgr_u8)
+        return self.collect()
+
+    def close(self):
+        for o in getattr(self, "_out", []):
+            for b in o.values():
+                if b is not None:
+                    b.free()
+        self._out = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def test_from_images(pipe, images, image_ids, batch_size=None, rank=0, world=1):
+    """test() without annotations: a KeypointPose2Seg finds the persons.  -> COCO segmentation dicts (category 1, bbox = the mask's tight box) whose
+    score is the detection's box score.  images: list of uint8 [h, w, 3] BGR (or a callable i -> image)."""
+    from .coco import results_from_records
+    from .pipeline import run_record_loop
+    bs = int(batch_size or pipe.max_batch)
+    assert bs <= pipe.max_batch
+    load = images if callable(images) else (lambda i: images[i])
+    n_img = len(image_ids)
+    batches = [list(range(j, min(j + bs, n_img))) for j in range(0, n_img, bs)]
+    hws = {}
+    per_image = [None] * n_img
+
+    def enqueue(step, slot):
+        j = step * world + rank
+        if j >= len(batches):
+            return False
+        b = batches[j]
+        ims = [load(i) for i in b]
+        for i, im in zip(b, ims):
+            hws[i] = np.asarray(im).shape[:2]
+        pipe.forward(ims, slot=slot)
+        pipe.rle_device([hws[i] for i in b])
+        return True
+
+    def consume(step, recs):
+        for r, rec in enumerate(recs):
+            j = step * world + r
+            if j >= len(batches):
+                continue
+            b = batches[j]
+            res = results_from_records(rec, [image_ids[i] for i in b] + [None] * (bs - len(b)), [hws[i] for i in b] + [(1, 1)] * (bs - len(b)),
+                                       3, pipe.max_instances)   # kind 3 takes `score` from the record: here the persons' box scores
+            by_id = {}
+            for d in res:
+                by_id.setdefault(d["image_id"], []).append(d)
+            for i in b:
+                per_image[i] = by_id.get(image_ids[i], [])
+
+    run_record_loop(pipe, bs, -(-len(batches) // world), enqueue, consume, rank, world)
     return [d for r in per_image if r for d in r]
 
 
