@@ -49,9 +49,11 @@ __device__ __forceinline__ void kp_cubic(int d, float scale, int n_in, int& s, f
 }
 __device__ __forceinline__ int kp_clamp(int v, int n) { return v < 0 ? 0 : (v > n - 1 ? n - 1 : v); }
 
-// the larger value wins; equal values (as floats: -0 == +0): the lower row-major position
+// np.argmax's order: a NaN is maximal; otherwise the larger value wins; equal values (as floats: -0 == +0) and two NaNs: the lower row-major position.
+// (bv, bp) starts as (-inf, INT_MAX), which loses to every position, an all -inf map's included.
 __device__ __forceinline__ void kp_better(float v, int p, float& bv, int& bp) {
-    if (v > bv || (v == bv && p < bp)) { bv = v; bp = p; }
+    const bool nan = v != v;
+    if (v > bv || ((v == bv || nan) && p < bp) || (nan && bv == bv)) { bv = v; bp = p; }
 }
 
 // One workgroup per (detection slot, keypoint).  The keypoint's S x S map sits in LDS; a thread owns output columns (their four horizontal taps and weights

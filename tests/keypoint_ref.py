@@ -15,6 +15,7 @@ from oracle import ora
 F = np.float32
 A = F(-0.75)
 A5, A8, A4, A2, A3 = F(-3.75), F(-6.0), F(-3.0), F(1.25), F(2.25)
+MAX_SIDE = 16384
 
 
 def cubic_taps(n_out, n_in):
@@ -50,11 +51,12 @@ def resize_bicubic(m, hc, wc):
 
 
 def box_sizes(box):
-    """-> (w, h fp32, wc, hc int) of heatmaps_to_keypoints: widths without +1, at least 1, ceil."""
+    """-> (w, h fp32, wc, hc int) of heatmaps_to_keypoints: widths without +1, at least 1, ceil; resized sides cut at 16 384 as the operator cuts them
+    (w and h themselves stay)."""
     box = np.asarray(box, F)
     w = np.maximum(box[2] - box[0], F(1.0))
     h = np.maximum(box[3] - box[1], F(1.0))
-    return w, h, int(np.ceil(w)), int(np.ceil(h))
+    return w, h, min(int(np.ceil(w)), MAX_SIDE), min(int(np.ceil(h)), MAX_SIDE)
 
 
 def decode_one(maps, box):
