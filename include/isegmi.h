@@ -94,6 +94,19 @@ int isegmi_op_conv2d(const isegmi_conv_desc* d, const float* d_in, const float* 
 int isegmi_op_conv2d_group(int n, const isegmi_conv_desc* descs, const float* const* d_in, const float* const* d_w, const float* const* d_scale,
                            const float* const* d_shift, const float* const* d_res, float* const* d_out, void* stream);
 
+/* Grouped 3x3 convolution (ResNeXt conv2: MODEL.RESNETS.NUM_GROUPS > 1) on v_mfma_f32_16x16x4_f32, fp32 NHWC.  The descriptor is isegmi_conv_desc as it
+ * stands; `groups` rides next to it.  Supported: R = S = 3, pad 1, stride 1 or 2, Cin == Cout with Cin % 64 == 0, cg = Cin / groups in {8, 16, 32, 64},
+ * act 0 or 1, a dense contiguous output (out_div / out_img_stride / out_pix_stride 0) and tile 0; anything else is ISEGMI_ERR_ARG and launches nothing.
+ * N * Ho * Wo == 0 is a successful no-op.  Numerics: the fp32 contract of isegmi_op_conv2d per group -- output channel co of group g = co / cg is ONE chain
+ * acc = fmaf(x_k, w_k, acc) from +0 over k = (r, s, c) ascending, c over the group's own input channels g cg .. g cg + cg - 1 (padding taps are x = 0
+ * products), then y = fmaf(acc, scale, shift) + residual -> act.  An output depends on its own group's input channels only, non-finite values included.
+ * groups == 1 with Cin == 64 equals isegmi_op_conv2d bit for bit.  h_w is [Cout][3][3][Cin / groups]; the packed image has as many floats as h_w. */
+int isegmi_conv_grouped_packed_floats(const isegmi_conv_desc* d, int groups, int64_t* n);
+int isegmi_pack_conv_weights_grouped(const isegmi_conv_desc* d, int groups, const float* h_w, float* h_packed);
+int isegmi_op_conv2d_grouped(const isegmi_conv_desc* d, int groups, const float* d_in, const float* d_wpacked,
+                             const float* d_scale, const float* d_shift, const float* d_residual,
+                             float* d_out, void* stream);
+
 /* fp16 variant (BASELINE configs[4]: "fp16 MFMA conv"): fp16 storage, v_mfma_f32_32x32x16_f16, fp32 accumulate
  * and epilogue.  Cin % 64 == 0 (or the stem, below); act none/relu; d_in / d_wpacked / d_residual are fp16, d_out fp16 or (out_f32)
  * fp32.  The 16-term sum inside one MFMA is not an ordered chain: parity with the oracle is tolerance-based. */
@@ -553,6 +566,11 @@ int isegmi_engine_graph_stats(isegmi_engine* h, int64_t* captures, int64_t* repl
 /* h_w_krsc: natural [Cout][R][S][Cin]; h_scale / h_shift [Cout] or NULL */
 int isegmi_engine_set_conv(isegmi_engine* e, const char* name, int Cout, int R, int S, int Cin,
                            const float* h_w_krsc, const float* h_scale, const float* h_shift);
+/* A grouped 3x3 layer (ResNeXt conv2; isegmi_op_conv2d_grouped): Cin == Cout, h_w [Cout][3][3][Cout / groups], groups > 1.  The layer carries its group
+ * count: the trunk launches the grouped kernel for it, sizes the bottleneck buffers from the weights, never takes `conv_split_k` for it and counts its
+ * grouped FLOPs in the timing records.  fp32 Mask R-CNN (FPN bodies) and RetinaNet engines; an fp16 engine, a C4 body and (at the forward) GroupNorm
+ * weights next to a grouped layer are refused by name. */
+int isegmi_engine_set_conv_grouped(isegmi_engine* e, const char* name, int Cout, int groups, const float* h_w, const float* h_scale, const float* h_shift);
 /* constant tensors (priors, anchors, deconv weights ...) */
 int isegmi_engine_set_tensor(isegmi_engine* e, const char* name, const void* h_data, int64_t bytes);
 /* Yolact.forward (Y2-Y6): d_images NHWC3 fp32 [N][H][W][3] already normalised (Y1). Asynchronous

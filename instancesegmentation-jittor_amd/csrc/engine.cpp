@@ -47,6 +47,12 @@ static int timed_conv(Engine& e, const std::string& label, const isegmi_conv_des
     const int Ho = (d->H + 2 * d->pad - d->R) / d->stride + 1, Wo = (d->W + 2 * d->pad - d->S) / d->stride + 1;
     ConvScope cs(e);
     cs.trace(label, "", d->N, d->H, d->W, d->Cin, d->Cout, d->R, d->stride, Ho * Wo * d->N, res != nullptr);
+    if (L->groups > 1) {   // a grouped layer does Cin / groups products per output: its algorithmic FLOPs are the dense ones over `groups`
+        TRY(conv2d_grouped_launch(d, L->groups, in, L->d_w, L->d_scale, L->d_shift, res, (float*)out, e.cur));
+        cs.done(2.0 * d->N * Ho * Wo * (double)d->Cout * d->R * d->S * (d->Cin / L->groups), "%s [M=%d K=%d Cout=%d %dx%d/%d groups=%d]", label.c_str(),
+                d->N * Ho * Wo, d->R * d->S * (d->Cin / L->groups), d->Cout, d->R, d->S, d->stride, L->groups);
+        return ISEGMI_OK;
+    }
     TRY(L->f16 ? conv2d_f16_launch(d, in, L->d_w, L->d_scale, L->d_shift, res, out, out_f32 ? 1 : 0, e.cur)
                : conv2d_launch(d, in, L->d_w, L->d_scale, L->d_shift, res, (float*)out, e.cur));
     const int cin_true = (d->Cin == 4 && d->R == 7) ? 3 : d->Cin;   // the stem's fourth input channel is padding
@@ -62,6 +68,7 @@ int eng_conv_into(Engine& e, const std::string& layer, const Tensor& in, int str
     if (rc) return rc;
     if (L->Cin != in.C) { set_error("conv " + layer + ": Cin mismatch"); return ISEGMI_ERR_ARG; }
     if ((in.dt == 1) != L->f16) { set_error("conv " + layer + ": activation / weight precision mismatch"); return ISEGMI_ERR_STATE; }
+    if (L->groups > 1) { set_error("conv " + layer + ": a grouped layer writes a dense output only"); return ISEGMI_ERR_ARG; }
     isegmi_conv_desc d;
     memset(&d, 0, sizeof(d));
     d.N = in.N; d.H = in.H; d.W = in.W; d.Cin = in.C; d.Cout = L->Cout; d.R = L->R; d.S = L->S; d.stride = stride; d.pad = pad;
@@ -88,7 +95,8 @@ int eng_conv(Engine& e, const std::string& layer, const Tensor& in, int stride, 
     // `conv_split_k` (default 0): the fixed-tree split-K evaluation (conv tile 15) for the backbone's bottleneck convolutions the caller
     // marks -- every conv2 / conv3 and the conv1 of a stage's later blocks -- where the shape rule takes them (small M, K >= 1024: a bs = 1 forward).  An
     // OPT-IN NUMERICS MODE: results are bit-exact against the oracle models run with conv_split_k (the same layers, the same rule), not against the default.
-    if (may_split && !L->f16 && d.tile == 0 && (int)e.param("conv_split_k", 0) != 0 && isegmi_conv_split_qualifies(&d)) d.tile = 15;
+    if (may_split && !L->f16 && L->groups == 1 && d.tile == 0 && (int)e.param("conv_split_k", 0) != 0 && isegmi_conv_split_qualifies(&d)) d.tile = 15;
+    if (L->groups > 1) d.tile = 0;   // one kernel, one k-ordered chain per output: never split-K whatever the shape rule says, no forced tile
     return timed_conv(e, layer, &d, in.d, L, residual ? residual->d : nullptr, out->d, out_f32);
 }
 
@@ -100,7 +108,7 @@ int eng_conv_group(Engine& e, std::vector<ConvGroupItem>& items) {
     for (int i = 0; i < n; ++i) {
         int rc = find_conv(e, items[i].layer, &Ls[i]);
         if (rc) return rc;
-        if (Ls[i]->f16 || items[i].in.dt == 1 || (Ls[i]->Cin == 4 && Ls[i]->R == 7)) grouped = false;
+        if (Ls[i]->f16 || items[i].in.dt == 1 || (Ls[i]->Cin == 4 && Ls[i]->R == 7) || Ls[i]->groups > 1) grouped = false;
     }
     if (!grouped) {
         for (auto& it : items) {
@@ -860,7 +868,7 @@ extern "C" int isegmi_engine_set_conv(isegmi_engine* h, const char* name, int Co
     if (L.d_w) { (void)hipFree(L.d_w); L.d_w = nullptr; }
     if (L.d_scale) { (void)hipFree(L.d_scale); L.d_scale = nullptr; }
     if (L.d_shift) { (void)hipFree(L.d_shift); L.d_shift = nullptr; }
-    L.Cout = Cout; L.R = R; L.S = S; L.Cin = Cin; L.f16 = f16;
+    L.Cout = Cout; L.R = R; L.S = S; L.Cin = Cin; L.f16 = f16; L.groups = 1;
     if (f16) {
         int64_t nh = 0;
         TRY(isegmi_conv_packed_halfs(&d, &nh));
@@ -879,6 +887,35 @@ extern "C" int isegmi_engine_set_conv(isegmi_engine* h, const char* name, int Co
     if (h_scale) { HIP_TRY(hipMalloc((void**)&L.d_scale, (size_t)Cout * 4)); HIP_TRY(hipMemcpy(L.d_scale, h_scale, (size_t)Cout * 4, hipMemcpyHostToDevice)); }
     if (h_shift) { HIP_TRY(hipMalloc((void**)&L.d_shift, (size_t)Cout * 4)); HIP_TRY(hipMemcpy(L.d_shift, h_shift, (size_t)Cout * 4, hipMemcpyHostToDevice)); }
     if (h->e.kind == 1 && std::string(name) == kHeadCat) yolact_head_views(h->e);
+    return ISEGMI_OK;
+}
+
+// a grouped 3x3 layer (ResNeXt conv2): Cin == Cout, weights [Cout][3][3][Cin / groups].  fp32 Mask R-CNN / RetinaNet engines only.
+extern "C" int isegmi_engine_set_conv_grouped(isegmi_engine* h, const char* name, int Cout, int groups, const float* h_w, const float* h_scale,
+                                              const float* h_shift) {
+    ARG_CHECK(h && name && h_w, "null");
+    ARG_CHECK(strchr(name, '[') == nullptr, "set_conv_grouped: '[' in a layer name (row-range views are the engine's)");
+    ARG_CHECK(groups > 1, "set_conv_grouped: groups must be > 1 (isegmi_engine_set_conv takes the dense layers)");
+    if (h->e.fp16) { set_error(std::string("grouped convolution ") + name + ": fp16 engines have no grouped kernel (fp16 ResNeXt is not built)"); return ISEGMI_ERR_ARG; }
+    if (h->e.param("arch_c4", 0.0f) != 0.0f) { set_error(std::string("grouped convolution ") + name + ": the C4 body (arch_c4) has no ResNeXt form"); return ISEGMI_ERR_ARG; }
+    if (h->e.kind != 2 && h->e.kind != 4) { set_error(std::string("grouped convolution ") + name + ": only the Mask R-CNN and RetinaNet engines run ResNeXt bodies"); return ISEGMI_ERR_ARG; }
+    isegmi_conv_desc d;
+    memset(&d, 0, sizeof(d));
+    d.N = 1; d.H = 3; d.W = 3; d.Cin = Cout; d.Cout = Cout; d.R = 3; d.S = 3; d.stride = 1; d.pad = 1;
+    int64_t nf = 0;
+    TRY(isegmi_conv_grouped_packed_floats(&d, groups, &nf));
+    std::vector<float> packed((size_t)nf);
+    TRY(isegmi_pack_conv_weights_grouped(&d, groups, h_w, packed.data()));
+    eng_graph_reset(h->e);
+    ConvLayer& L = h->e.convs[name];
+    if (L.d_w) { (void)hipFree(L.d_w); L.d_w = nullptr; }
+    if (L.d_scale) { (void)hipFree(L.d_scale); L.d_scale = nullptr; }
+    if (L.d_shift) { (void)hipFree(L.d_shift); L.d_shift = nullptr; }
+    L.Cout = Cout; L.R = 3; L.S = 3; L.Cin = Cout; L.f16 = false; L.groups = groups;
+    HIP_TRY(hipMalloc((void**)&L.d_w, (size_t)nf * 4));
+    HIP_TRY(hipMemcpy(L.d_w, packed.data(), (size_t)nf * 4, hipMemcpyHostToDevice));
+    if (h_scale) { HIP_TRY(hipMalloc((void**)&L.d_scale, (size_t)Cout * 4)); HIP_TRY(hipMemcpy(L.d_scale, h_scale, (size_t)Cout * 4, hipMemcpyHostToDevice)); }
+    if (h_shift) { HIP_TRY(hipMalloc((void**)&L.d_shift, (size_t)Cout * 4)); HIP_TRY(hipMemcpy(L.d_shift, h_shift, (size_t)Cout * 4, hipMemcpyHostToDevice)); }
     return ISEGMI_OK;
 }
 

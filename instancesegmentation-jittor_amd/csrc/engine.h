@@ -32,6 +32,7 @@ struct ConvLayer {
     bool f16 = false;
     float* d_scale = nullptr;  // may be null (=1)
     float* d_shift = nullptr;  // may be null (=0)
+    int groups = 1;            // > 1: a grouped 3x3 (ResNeXt conv2): d_w is the isegmi_pack_conv_weights_grouped image of [Cout][3][3][Cin / groups] weights
     bool view = false;         // a row range of another layer: d_w / d_scale / d_shift point into ITS allocations (never freed, never counted)
 };
 
@@ -318,6 +319,8 @@ int maskrcnn_stage_ratios(Engine& e, const float* h_ratios_wh, int N, hipStream_
 // kernels implemented in other translation units (the detection tail's launchers: tail_launch.h)
 int conv2d_launch(const isegmi_conv_desc* d, const float* in, const float* w, const float* scale, const float* shift,
                   const float* res, float* out, hipStream_t st);
+int conv2d_grouped_launch(const isegmi_conv_desc* d, int groups, const float* in, const float* w, const float* scale, const float* shift, const float* res,
+                          float* out, hipStream_t st);
 int conv2d_f16_launch(const isegmi_conv_desc* d, const void* in, const void* w, const float* scale, const float* shift, const void* res,
                       void* out, int out_f32, hipStream_t st);
 int conv2d_f16_up2x_launch(const isegmi_conv_desc* d, const void* in, const void* w, const float* scale, const float* shift, const void* coarse, int Hc, int Wc,

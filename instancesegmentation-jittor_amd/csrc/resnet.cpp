@@ -127,6 +127,13 @@ int resnet_stage(Engine& e, const ResStage& s, const Tensor& in, Tensor* out) {
             TRY(eng_conv(e, nm + ".conv1", x, st1, 0, act, nullptr, sg + ".t1", &t1, false, /*may_split=*/s.full && b > 0));   // (`conv_split_k`: see eng_conv)
             if (gn) TRY(eng_gn(e, nm + ".conv1", &t1, nullptr, true));
         }
+        // ResNeXt: conv2 uploaded with grouped weights (isegmi_engine_set_conv_grouped) runs the grouped kernel through eng_conv like any other layer; t1 /
+        // t2 take their width from the weights, in the full and in the plain form.  Built next to FrozenBN and in fp32 only.
+        const auto c2 = e.convs.find(nm + ".conv2");
+        if (c2 != e.convs.end() && c2->second.groups > 1) {
+            if (gn) { set_error("grouped convolution " + nm + ".conv2 with GroupNorm weights: ResNeXt bodies with GroupNorm are not built"); return ISEGMI_ERR_STATE; }
+            if (t1.dt) { set_error("grouped convolution " + nm + ".conv2 in an fp16 engine: fp16 ResNeXt is not built"); return ISEGMI_ERR_STATE; }
+        }
         if (e.convs.count(nm + ".conv2.conv_offset_mask")) TRY(dcn_conv2(e, nm, blk, t1, st2, sg + ".t2", &t2));
         else TRY(eng_conv(e, nm + ".conv2", t1, st2, 1, act, nullptr, sg + ".t2", &t2, false, /*may_split=*/s.full));
         if (gn) TRY(eng_gn(e, nm + ".conv2", &t2, nullptr, true));

@@ -212,6 +212,42 @@ def conv2d(x, w_krsc, stride=1, pad=0, scale=None, shift=None, residual=None, ac
     return do.numpy()
 
 
+def pack_conv_weights_grouped(desc, groups, w):
+    """host: [Cout,3,3,Cin/groups] fp32 -> the packed 1-D fp32 image of isegmi_op_conv2d_grouped."""
+    w = np.ascontiguousarray(w, np.float32)
+    n = C.c_int64()
+    check(lib().isegmi_conv_grouped_packed_floats(C.byref(desc), C.c_int(groups), C.byref(n)))
+    assert w.shape == (desc.Cout, 3, 3, desc.Cin // groups), (w.shape, desc.Cout, desc.Cin, groups)
+    out = np.empty(n.value, np.float32)
+    check(lib().isegmi_pack_conv_weights_grouped(C.byref(desc), C.c_int(groups), w.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def op_conv2d_grouped(desc, groups, d_in, d_wpacked, d_scale=None, d_shift=None, d_residual=None, d_out=None):
+    check(lib().isegmi_op_conv2d_grouped(C.byref(desc), C.c_int(groups), _ptr(d_in), _ptr(d_wpacked), _ptr(d_scale), _ptr(d_shift),
+                                         _ptr(d_residual), _ptr(d_out), None))
+
+
+def conv2d_grouped(x, w, groups, stride=1, scale=None, shift=None, residual=None, act=0, guard=0):
+    """Convenience host->device->host grouped 3x3 / pad 1 convolution (tests / small inputs): x [N,H,W,C], w [C,3,3,C/groups].  guard > 0: the output
+    buffer gets that many floats of 0xFF bytes behind it, and (output, guard region after the launch) is returned."""
+    x = np.ascontiguousarray(x, np.float32)
+    N, H, W, Cin = x.shape
+    d = make_conv_desc(N, H, W, Cin, w.shape[0], w.shape[1], w.shape[2], stride, 1, act)
+    dw = DeviceBuffer.from_numpy(pack_conv_weights_grouped(d, groups, w))
+    ho, wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    dx = DeviceBuffer.from_numpy(x)
+    ds = None if scale is None else DeviceBuffer.from_numpy(np.asarray(scale, np.float32))
+    dh = None if shift is None else DeviceBuffer.from_numpy(np.asarray(shift, np.float32))
+    dr = None if residual is None else DeviceBuffer.from_numpy(np.asarray(residual, np.float32))
+    n_out = N * ho * wo * Cin
+    do = DeviceBuffer((n_out + int(guard),)).poison()
+    op_conv2d_grouped(d, groups, dx, dw, ds, dh, dr, do)
+    flat = do.numpy()
+    out = flat[:n_out].reshape(N, ho, wo, Cin)
+    return (out, flat[n_out:]) if guard else out
+
+
 def conv2d_group(items):
     """isegmi_op_conv2d_group: several independent fp32 convolutions as ONE launch.  items: dicts with x, w (KRSC) and optionally stride, pad, scale,
     shift, residual, act.  -> list of outputs (each what conv2d gives for the member alone, bit for bit)."""

@@ -34,11 +34,11 @@ def _save_image_bgr(path, img):
     Image.fromarray(np.ascontiguousarray(img[:, :, ::-1])).save(path)
 
 
-def _weights(spec, kind, depth=50, ycfg=None, gn=False):
+def _weights(spec, kind, depth=50, ycfg=None, gn=False, groups=1, width_per_group=64):
     from .weights import maskrcnn_state_dict, retinanet_state_dict, yolact_state_dict
     if spec in ("", "random", None):
         if kind == "retinanet":
-            return retinanet_state_dict(1234, depth)
+            return retinanet_state_dict(1234, depth, groups=groups, width_per_group=width_per_group)
         if kind == "maskrcnn" and gn:
             return maskrcnn_state_dict(1234, depth, gn=True)
         if kind == "yolact" and ycfg is not None:
@@ -137,7 +137,7 @@ def cmd_test_net(a):
     rank, world, local = _rank_world()
     files = sorted(os.path.join(a.images, f) for f in os.listdir(a.images)) if a.images else []
     if retina:
-        sd = _weights(c.MODEL.WEIGHT, "retinanet", mc.depth)
+        sd = _weights(c.MODEL.WEIGHT, "retinanet", mc.depth, groups=mc.NUM_GROUPS, width_per_group=mc.WIDTH_PER_GROUP)
     elif c.MODEL.WEIGHT in ("", "random", None):   # the seeded generator of the configured model: body, norm, MASK_ON, NUM_CLASSES, CLS_AGNOSTIC_BBOX_REG
         from .weights import random_maskrcnn_state_dict
         sd = random_maskrcnn_state_dict(mc, 1234)

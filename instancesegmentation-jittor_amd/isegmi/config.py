@@ -13,7 +13,7 @@ import copy
 
 import yaml
 
-from .maskrcnn import MaskRCNNConfig, gn_groups, gn_model_layers
+from .maskrcnn import MaskRCNNConfig, gn_groups, gn_model_layers, resnext_check
 
 
 def _literal(v):
@@ -78,7 +78,7 @@ def _defaults():
                   # [UPSTREAM-RECALL] maskrcnn-benchmark defaults.py
                   "GROUP_NORM": {"DIM_PER_GP": -1, "NUM_GROUPS": 32, "EPSILON": 1e-5},
                   "RESNETS": {"TRANS_FUNC": "BottleneckWithFixedBatchNorm", "STEM_FUNC": "StemWithFixedBatchNorm", "STRIDE_IN_1X1": True,
-                              "RES5_DILATION": 1},
+                              "RES5_DILATION": 1, "NUM_GROUPS": 1, "WIDTH_PER_GROUP": 64, "RES2_OUT_CHANNELS": 256, "STEM_OUT_CHANNELS": 64},
                   "FPN": {"USE_GN": False, "USE_RELU": False},
                   "ROI_BOX_HEAD": {"FEATURE_EXTRACTOR": "FPN2MLPFeatureExtractor", "USE_GN": False, "NUM_STACKED_CONVS": 4, "CONV_HEAD_DIM": 256,
                                    "MLP_HEAD_DIM": 1024, "DILATION": 1, "NUM_CLASSES": 81},
@@ -104,6 +104,24 @@ cfg = _defaults()
 
 def _bool(v):
     return v if isinstance(v, bool) else str(v).strip().lower() in ("true", "1", "yes")
+
+
+def _resnext_config(c, body, gn_key=None):
+    """[UPSTREAM-RECALL] MODEL.RESNETS.NUM_GROUPS / WIDTH_PER_GROUP / RES2_OUT_CHANNELS / STEM_OUT_CHANNELS -> (groups, width per group).  ResNeXt
+    (NUM_GROUPS > 1) is built on the FrozenBN FPN bodies with WIDTH_PER_GROUP 8; everything else raises and names its key.
+    gn_key: the yaml key that asks for GroupNorm, if one does."""
+    rn = c.MODEL.RESNETS
+    for key, built in (("RES2_OUT_CHANNELS", 256), ("STEM_OUT_CHANNELS", 64)):
+        if int(rn.get(key, built)) != built:
+            raise ValueError("MODEL.RESNETS.%s=%s: the trunk is built at %d" % (key, rn[key], built))
+    groups, width = int(rn.get("NUM_GROUPS", 1)), int(rn.get("WIDTH_PER_GROUP", 64))
+    resnext_check(groups, width)
+    if groups > 1:
+        if gn_key:
+            raise ValueError("MODEL.RESNETS.NUM_GROUPS=%d with GroupNorm (%s): ResNeXt is built on the FrozenBN bodies" % (groups, gn_key))
+        if str(body).endswith("-C4"):
+            raise ValueError("MODEL.RESNETS.NUM_GROUPS=%d with MODEL.BACKBONE.CONV_BODY=%r: ResNeXt is built on the FPN bodies" % (groups, body))
+    return groups, width
 
 
 def _norm_config(c, body, mask_on=True):
@@ -132,13 +150,16 @@ def _norm_config(c, body, mask_on=True):
             ((("MODEL.ROI_MASK_HEAD.USE_GN", _bool(mh.USE_GN)),) if mask_on else ())
     on = [k for k, v in flags if v]
     stride_in_1x1 = _bool(rn.STRIDE_IN_1X1)
+    num_groups, width_per_group = _resnext_config(c, body, on[0] if on else None)
     if not on:
         if fx != "FPN2MLPFeatureExtractor":
             raise ValueError("MODEL.ROI_BOX_HEAD.FEATURE_EXTRACTOR=%r is built with GroupNorm only (USE_GN: True)" % fx)
-        if not stride_in_1x1:
+        if not stride_in_1x1 and num_groups == 1:
             raise ValueError("MODEL.RESNETS.STRIDE_IN_1X1=False is built for the GroupNorm model only")
         if int(bh.MLP_HEAD_DIM) != 1024:
             raise ValueError("MODEL.ROI_BOX_HEAD.MLP_HEAD_DIM=%s: FPN2MLPFeatureExtractor is built at 1024" % bh.MLP_HEAD_DIM)
+        if num_groups > 1:   # ResNeXt: either stride placement (the X-101-32x8d yamls say False)
+            return dict(NUM_GROUPS=num_groups, WIDTH_PER_GROUP=width_per_group, STRIDE_IN_1X1=stride_in_1x1)
         return {}
     if body.endswith("-C4"):
         raise ValueError("%s: GroupNorm is built for the FPN bodies only (MODEL.BACKBONE.CONV_BODY=%r)" % (on[0], body))
@@ -229,6 +250,8 @@ def to_keypointrcnn_config(c):
     if body not in ("R-50-FPN", "R-101-FPN"):
         raise ValueError("MODEL.BACKBONE.CONV_BODY=%r with MODEL.KEYPOINT_ON: the keypoint head is built on R-50-FPN and R-101-FPN (it reads P2..P5)" % body)
     mc = _two_stage_config(c)
+    if mc.NUM_GROUPS > 1:
+        raise ValueError("MODEL.RESNETS.NUM_GROUPS=%d with MODEL.KEYPOINT_ON: Keypoint R-CNN on ResNeXt is not built" % mc.NUM_GROUPS)
     if mc.USE_GN:
         raise ValueError("MODEL.KEYPOINT_ON with GroupNorm (MODEL.RESNETS.TRANS_FUNC / MODEL.FPN.USE_GN ...): the keypoint head is built on the FrozenBN bodies")
     if _bool(k.SHARE_BOX_FEATURE_EXTRACTOR):
@@ -283,8 +306,10 @@ def to_retinanet_config(c):
             raise ValueError("%s: RetinaNet with GroupNorm is not built (FrozenBatchNorm trunk, plain FPN)" % key)
     if _bool(m.FPN.USE_RELU):
         raise ValueError("MODEL.FPN.USE_RELU=True is not built")
-    if not _bool(rn.STRIDE_IN_1X1):
+    num_groups, width_per_group = _resnext_config(c, body)
+    if not _bool(rn.STRIDE_IN_1X1) and num_groups == 1:
         raise ValueError("MODEL.RESNETS.STRIDE_IN_1X1=False is built for the GroupNorm Mask R-CNN only")
+    resnext = dict(NUM_GROUPS=num_groups, WIDTH_PER_GROUP=width_per_group, STRIDE_IN_1X1=_bool(rn.STRIDE_IN_1X1)) if num_groups > 1 else {}
     if int(rn.RES5_DILATION) != 1:
         raise ValueError("MODEL.RESNETS.RES5_DILATION=%s: dilated convolutions are not built" % rn.RES5_DILATION)
     sizes, strides = tuple(r.ANCHOR_SIZES), tuple(r.ANCHOR_STRIDES)
@@ -300,4 +325,4 @@ def to_retinanet_config(c):
                            SIZE_DIVISIBILITY=int(c.DATALOADER.SIZE_DIVISIBILITY), NUM_CLASSES=81, ANCHOR_SIZES=tuple(int(s) for s in sizes),
                            ANCHOR_STRIDES=tuple(int(s) for s in strides), ASPECT_RATIOS=tuple(float(x) for x in r.ASPECT_RATIOS), OCTAVE=float(r.OCTAVE),
                            SCALES_PER_OCTAVE=int(r.SCALES_PER_OCTAVE), NUM_CONVS=int(r.NUM_CONVS), PRE_NMS_TOP_N=int(r.PRE_NMS_TOP_N),
-                           INFERENCE_TH=float(r.INFERENCE_TH), NMS_TH=float(r.NMS_TH), DETECTIONS_PER_IMG=int(c.TEST.DETECTIONS_PER_IMG))
+                           INFERENCE_TH=float(r.INFERENCE_TH), NMS_TH=float(r.NMS_TH), DETECTIONS_PER_IMG=int(c.TEST.DETECTIONS_PER_IMG), **resnext)

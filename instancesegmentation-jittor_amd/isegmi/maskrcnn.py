@@ -70,6 +70,10 @@ class MaskRCNNConfig:
     KEYPOINT_ON: bool = False
     KEYPOINT_CONV_LAYERS: tuple = (512,) * 8   # MODEL.ROI_KEYPOINT_HEAD.CONV_LAYERS: widths of conv_fcn1.. (multiples of 32)
     NUM_KEYPOINTS: int = 17                    # MODEL.ROI_KEYPOINT_HEAD.NUM_CLASSES (1..32)
+    # [UPSTREAM-RECALL] DESIGN.md 16.  ResNeXt trunks (e2e_*_X_101_32x8d_FPN_1x): conv2 of every bottleneck is a grouped 3x3 with NUM_GROUPS groups, a stage's
+    # bottleneck width is NUM_GROUPS * WIDTH_PER_GROUP * 2^stage.  FrozenBN FPN bodies, fp32, no keypoint head.
+    NUM_GROUPS: int = 1          # MODEL.RESNETS.NUM_GROUPS
+    WIDTH_PER_GROUP: int = 64    # MODEL.RESNETS.WIDTH_PER_GROUP
 
     @staticmethod
     def c4():
@@ -85,6 +89,40 @@ class MaskRCNNConfig:
     @property
     def det_cap(self):
         return max(self.DETECTIONS_PER_IMG, self.DETECTIONS_CAP)
+
+
+GROUPED_CONV_WIDTHS = (8, 16, 32, 64)   # channels per group the grouped kernel takes (csrc/conv_grouped.hip)
+
+
+def resnext_check(num_groups, width_per_group):
+    """THE rule of which ResNeXt trunks are built, stated once (config.py and the model classes both ask here): every stage's channels per group,
+    WIDTH_PER_GROUP * 2^stage, lie in the grouped kernel's set, and the widths are multiples of 64.  Raises ValueError naming the yaml key."""
+    g, w = int(num_groups), int(width_per_group)
+    if g < 1:
+        raise ValueError("MODEL.RESNETS.NUM_GROUPS=%d: at least 1" % g)
+    if g == 1:
+        if w != 64:
+            raise ValueError("MODEL.RESNETS.WIDTH_PER_GROUP=%d with NUM_GROUPS 1: the plain ResNet trunk is built at 64" % w)
+        return
+    for stage in range(4):
+        if (w << stage) not in GROUPED_CONV_WIDTHS:
+            raise ValueError("MODEL.RESNETS.WIDTH_PER_GROUP=%d gives groups of %d channels in res%d: the grouped convolution kernel takes %s per group "
+                             "(WIDTH_PER_GROUP 8)" % (w, w << stage, stage + 2, ", ".join(str(v) for v in GROUPED_CONV_WIDTHS)))
+    if (g * w) % 64:
+        raise ValueError("MODEL.RESNETS.NUM_GROUPS=%d x WIDTH_PER_GROUP=%d = %d: the bottleneck width must be a multiple of 64" % (g, w, g * w))
+
+
+def resnext_refusals(cfg, fp16):
+    """What a ResNeXt trunk (NUM_GROUPS > 1) is not built next to; ValueError naming the key."""
+    resnext_check(cfg.NUM_GROUPS, cfg.WIDTH_PER_GROUP)
+    if cfg.NUM_GROUPS == 1:
+        return
+    for bad, why in ((fp16, "fp16=True: fp16 ResNeXt is not built (the grouped convolution kernel is fp32)"),
+                     (cfg.is_c4, "the C4 body (MODEL.BACKBONE.CONV_BODY %s): ResNeXt is built on the FPN bodies" % cfg.CONV_BODY),
+                     (getattr(cfg, "USE_GN", False), "GroupNorm (USE_GN): ResNeXt is built on the FrozenBN bodies"),
+                     (getattr(cfg, "KEYPOINT_ON", False), "MODEL.KEYPOINT_ON: Keypoint R-CNN on ResNeXt is not built")):
+        if bad:
+            raise ValueError("MODEL.RESNETS.NUM_GROUPS=%d together with %s" % (cfg.NUM_GROUPS, why))
 
 
 GN_TILE_CHANNELS = 64   # csrc/groupnorm.hip GN_TILE_C
@@ -279,6 +317,7 @@ class MaskRCNN:
                 gn_groups(ch, cfg.GN_NUM_GROUPS, cfg.GN_DIM_PER_GP, layer)
         if not 2 <= int(cfg.NUM_CLASSES) <= 257:
             raise ValueError("MODEL.ROI_BOX_HEAD.NUM_CLASSES=%s: the box post-processing kernels hold 2..257 classes (background included)" % (cfg.NUM_CLASSES,))
+        resnext_refusals(cfg, fp16)
         if cfg.KEYPOINT_ON:   # what the keypoint head is built next to
             for bad, why in ((fp16, "fp16=True: the keypoint head is fp32 only"), (cfg.is_c4, "the C4 body (CONV_BODY %s): the keypoint head reads P2..P5" % cfg.CONV_BODY),
                              (cfg.USE_GN, "GroupNorm (USE_GN): the keypoint head is built on the FrozenBN bodies"),
@@ -420,6 +459,28 @@ class MaskRCNN:
         sh = None if shift is None else np.ascontiguousarray(shift, np.float32)
         _ffi.check(_ffi.lib().isegmi_engine_set_conv(self._h, name.encode(), cout, r, s, cin, fp(w), fp(sc), fp(sh)))
 
+    def _set_conv2(self, sd, src, dst, stage):
+        """conv2 of bottleneck `src` (stage 0..3): checked against MODEL.RESNETS.NUM_GROUPS / WIDTH_PER_GROUP -- weight [width, width / groups, 3, 3] with
+        width = groups * width_per_group * 2^stage; ValueError naming the key otherwise -- and uploaded dense (groups 1) or grouped."""
+        cfg = self.cfg
+        groups, wpg = int(getattr(cfg, "NUM_GROUPS", 1)), int(getattr(cfg, "WIDTH_PER_GROUP", 64))
+        key = src + ".conv2.weight"
+        w = np.asarray(sd[key])
+        width = (groups * wpg) << stage
+        if w.ndim != 4 or w.shape[1] * groups != w.shape[0]:
+            raise ValueError("%s %s: MODEL.RESNETS.NUM_GROUPS=%d needs shape[1] * %d == shape[0] (a ResNeXt checkpoint needs its NUM_GROUPS / WIDTH_PER_GROUP)"
+                             % (key, tuple(w.shape), groups, groups))
+        if w.shape[0] != width:
+            raise ValueError("%s %s: MODEL.RESNETS.NUM_GROUPS=%d x WIDTH_PER_GROUP=%d gives a bottleneck width of %d in res%d"
+                             % (key, tuple(w.shape), groups, wpg, width, stage + 2))
+        scale, shift = fold_frozen_batchnorm(sd, src + ".bn2", cfg.FROZEN_BN_EPS)
+        if groups == 1:
+            return self._set_conv_krsc(dst + ".conv2", to_krsc(w), scale, shift)
+        wk = to_krsc(w)   # [width, 3, 3, width / groups]
+        fp = lambda a: np.ascontiguousarray(a, np.float32).ctypes.data_as(C.c_void_p)
+        wk, scale, shift = (np.ascontiguousarray(a, np.float32) for a in (wk, scale, shift))
+        _ffi.check(_ffi.lib().isegmi_engine_set_conv_grouped(self._h, (dst + ".conv2").encode(), width, groups, fp(wk), fp(scale), fp(shift)))
+
     def _set_tensor(self, name, a):
         a = np.ascontiguousarray(a)
         _ffi.check(_ffi.lib().isegmi_engine_set_tensor(self._h, name.encode(), a.ctypes.data_as(C.c_void_p), C.c_int64(a.nbytes)))
@@ -433,9 +494,10 @@ class MaskRCNN:
         for li, nb in enumerate(blocks, 1):
             for b in range(nb):
                 nm = "backbone.body.layer%d.%d" % (li, b)
-                for i in (1, 2, 3):
+                for i in (1, 3):
                     self._set_conv_krsc("%s.conv%d" % (nm, i), to_krsc(sd["%s.conv%d.weight" % (nm, i)]),
                                         *fold_frozen_batchnorm(sd, "%s.bn%d" % (nm, i), cfg.FROZEN_BN_EPS))
+                self._set_conv2(sd, nm, nm, li - 1)
                 if b == 0:
                     self._set_conv_krsc(nm + ".downsample.0", to_krsc(sd[nm + ".downsample.0.weight"]),
                                         *fold_frozen_batchnorm(sd, nm + ".downsample.1", cfg.FROZEN_BN_EPS))
@@ -534,10 +596,14 @@ class MaskRCNN:
             self._set_tensor("anchor_base.%d" % l, generate_anchors(stride, size, cfg.ASPECT_RATIOS))
             self.set_param("anchor_stride%d" % l, float(stride))
 
-    def _load_bottlenecks(self, sd, src_prefix, dst_prefix, nblocks):
+    def _load_bottlenecks(self, sd, src_prefix, dst_prefix, nblocks, stage=None):
+        """stage (0..3): conv2 is checked against MODEL.RESNETS.NUM_GROUPS / WIDTH_PER_GROUP and may be grouped (_set_conv2); None: the plain trunks."""
         for b in range(nblocks):
             src, dst = "%s.%d" % (src_prefix, b), "%s.%d" % (dst_prefix, b)
             for i in (1, 2, 3):
+                if i == 2 and stage is not None:
+                    self._set_conv2(sd, src, dst, stage)
+                    continue
                 self._set_conv_krsc("%s.conv%d" % (dst, i), to_krsc(sd["%s.conv%d.weight" % (src, i)]),
                                     *fold_frozen_batchnorm(sd, "%s.bn%d" % (src, i), self.cfg.FROZEN_BN_EPS))
             if b == 0:

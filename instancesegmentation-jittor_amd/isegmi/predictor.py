@@ -31,7 +31,8 @@ class COCODemo:
                 body = cfg.MODEL.BACKBONE.CONV_BODY
                 depth = 101 if "101" in body else 50
                 # MODEL.WEIGHT random: the seeded generator of the configured model (body, norm, MASK_ON, NUM_CLASSES, CLS_AGNOSTIC_BBOX_REG)
-                rnd = (lambda: retinanet_state_dict(1234, depth)) if retina else (lambda: random_maskrcnn_state_dict(to_two_stage(cfg), 1234))
+                rn = cfg.MODEL.RESNETS
+                rnd = (lambda: retinanet_state_dict(1234, depth, groups=int(rn.get("NUM_GROUPS", 1)), width_per_group=int(rn.get("WIDTH_PER_GROUP", 64)))) if retina else (lambda: random_maskrcnn_state_dict(to_two_stage(cfg), 1234))
                 state_dict = rnd() if w == "random" else dict(np.load(w))
             cfg = to_retinanet_config(cfg) if retina else to_two_stage(cfg)
         self.cfg = cfg or MaskRCNNConfig()

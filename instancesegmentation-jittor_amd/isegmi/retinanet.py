@@ -8,7 +8,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _ffi
-from .maskrcnn import BoxList, MaskRCNN, generate_anchors_multi
+from .maskrcnn import BoxList, MaskRCNN, generate_anchors_multi, resnext_refusals
 from .weights import fold_frozen_batchnorm, to_krsc
 
 RETINA_MAX_TOP_N = 1024   # csrc/retinanet_ops.hip RETINA_KCAP
@@ -40,6 +40,8 @@ class RetinaNetConfig:
     NMS_OUTPUT_ORDER: str = "score"
     FROZEN_BN_EPS: float = 0.0
     STRIDE_IN_1X1: bool = True
+    NUM_GROUPS: int = 1          # MODEL.RESNETS.NUM_GROUPS / WIDTH_PER_GROUP: the ResNeXt trunk (retinanet_X_101_32x8d_FPN_1x), as MaskRCNNConfig
+    WIDTH_PER_GROUP: int = 64
 
     @property
     def det_cap(self):
@@ -70,6 +72,7 @@ class RetinaNet(MaskRCNN):
     def __init__(self, state_dict, H, W, cfg=RetinaNetConfig(), max_batch=2, device=0, fp16=False, graph=False):
         if fp16:
             raise ValueError("RetinaNet: fp16=True is not built (fp32 only)")
+        resnext_refusals(cfg, fp16)
         if graph:
             raise ValueError("RetinaNet: graph=True (hipGraph capture) is not built")
         if len(cfg.ANCHOR_STRIDES) != RETINA_LEVELS or len(cfg.ANCHOR_SIZES) != RETINA_LEVELS:
@@ -102,7 +105,7 @@ class RetinaNet(MaskRCNN):
         w = np.concatenate([w, np.zeros(w.shape[:3] + (1,), np.float32)], -1)
         self._set_conv_krsc("backbone.body.stem.conv1", w, *fold_frozen_batchnorm(sd, "backbone.body.stem.bn1", cfg.FROZEN_BN_EPS))
         for li, nb in enumerate((3, 4, 23 if cfg.depth == 101 else 6, 3), 1):
-            self._load_bottlenecks(sd, "backbone.body.layer%d" % li, "backbone.body.layer%d" % li, nb)
+            self._load_bottlenecks(sd, "backbone.body.layer%d" % li, "backbone.body.layer%d" % li, nb, stage=li - 1)
         names = ["backbone.fpn.fpn_%s%d" % (k, i) for i in (2, 3, 4) for k in ("inner", "layer")] + ["backbone.fpn.top_blocks.p6", "backbone.fpn.top_blocks.p7"]
         names += ["rpn.head.%s_tower.%d" % (t, 2 * i) for i in range(cfg.NUM_CONVS) for t in ("cls", "bbox")] + ["rpn.head.cls_logits", "rpn.head.bbox_pred"]
         for nm in names:

@@ -27,21 +27,24 @@ def _conv_bias(rng, sd, name, cout, cin, k, gain=1.0, bias_std=0.01):
     sd[name + ".bias"] = (rng.standard_normal(cout) * bias_std).astype(np.float32)
 
 
-def resnet_state_dict(rng, sd, prefix, blocks=(3, 4, 6, 3), layer_fmt="layers.%d.%d", stem_conv="conv1", stem_bn="bn1"):
+def resnet_state_dict(rng, sd, prefix, blocks=(3, 4, 6, 3), layer_fmt="layers.%d.%d", stem_conv="conv1", stem_bn="bn1", groups=1, width_per_group=64):
+    """groups / width_per_group: [UPSTREAM-RECALL] ResNeXt (MODEL.RESNETS.NUM_GROUPS / WIDTH_PER_GROUP) -- a stage's bottleneck width is
+    groups * width_per_group * 2^stage and conv2 is a grouped 3x3 whose weight is [width, width / groups, 3, 3]; the defaults are the plain ResNet."""
     sd[prefix + stem_conv + ".weight"] = _conv(rng, 64, 3, 7)
     _bn(rng, sd, prefix + stem_bn, 64)
     inpl = 64
     for li, nb in enumerate(blocks):
-        planes = 64 << li
+        planes = (groups * width_per_group) << li
+        out = 256 << li
         for b in range(nb):
             nm = prefix + layer_fmt % (li, b)
             sd[nm + ".conv1.weight"] = _conv(rng, planes, inpl, 1); _bn(rng, sd, nm + ".bn1", planes)
-            sd[nm + ".conv2.weight"] = _conv(rng, planes, planes, 3); _bn(rng, sd, nm + ".bn2", planes)
-            sd[nm + ".conv3.weight"] = _conv(rng, planes * 4, planes, 1); _bn(rng, sd, nm + ".bn3", planes * 4, 0.25)
+            sd[nm + ".conv2.weight"] = _conv(rng, planes, planes // groups, 3); _bn(rng, sd, nm + ".bn2", planes)
+            sd[nm + ".conv3.weight"] = _conv(rng, out, planes, 1); _bn(rng, sd, nm + ".bn3", out, 0.25)
             if b == 0:
-                sd[nm + ".downsample.0.weight"] = _conv(rng, planes * 4, inpl, 1)
-                _bn(rng, sd, nm + ".downsample.1", planes * 4)
-            inpl = planes * 4
+                sd[nm + ".downsample.0.weight"] = _conv(rng, out, inpl, 1)
+                _bn(rng, sd, nm + ".downsample.1", out)
+            inpl = out
 
 
 # Recorded calibration of the Yolact predictor (see module docstring): found with the CPU oracle on
@@ -238,9 +241,12 @@ def maskrcnn_gn_state_dict(seed=1234, depth=50, stacked_convs=4, conv_head_dim=2
     return sd if mask else _drop_mask_head(sd)
 
 
-def maskrcnn_state_dict(seed=1234, depth=50, gn=False, mask=True, num_classes=81, cls_agnostic=False):
+def maskrcnn_state_dict(seed=1234, depth=50, gn=False, mask=True, num_classes=81, cls_agnostic=False, groups=1, width_per_group=64):
     """maskrcnn-benchmark e2e_mask_rcnn_R_50/101_FPN state-dict names; gn=True: the GroupNorm model (maskrcnn_gn_state_dict).
-    mask=False: the e2e_faster_rcnn_* key set (no roi_heads.mask.*); num_classes / cls_agnostic size the predictors."""
+    mask=False: the e2e_faster_rcnn_* key set (no roi_heads.mask.*); num_classes / cls_agnostic size the predictors.
+    groups / width_per_group: the ResNeXt trunks (e2e_*_X_101_32x8d_FPN_1x: 32, 8); the defaults are the ResNet dicts, bit for bit."""
+    if gn and groups != 1:
+        raise ValueError("maskrcnn_state_dict: groups > 1 (ResNeXt) with gn=True is not built")
     if gn:
         return maskrcnn_gn_state_dict(seed, depth, mask=mask, num_classes=num_classes, cls_agnostic=cls_agnostic)
     ncls, nreg = _box_predictor_widths(num_classes, cls_agnostic)
@@ -249,7 +255,7 @@ def maskrcnn_state_dict(seed=1234, depth=50, gn=False, mask=True, num_classes=81
     blocks = (3, 4, 23 if depth == 101 else 6, 3)
     # ResNet body: same tensors as torchvision but under backbone.body.{stem,layerN}
     tmp = {}
-    resnet_state_dict(rng, tmp, "", blocks=blocks)
+    resnet_state_dict(rng, tmp, "", blocks=blocks, groups=groups, width_per_group=width_per_group)
     for k, v in tmp.items():
         if k.startswith("conv1.") or k.startswith("bn1."):
             sd["backbone.body.stem." + k] = v
@@ -289,14 +295,14 @@ RETINA_CLS_BIAS_SPREAD = 0.5
 RETINA_BBOX_GAIN = 0.0004
 
 
-def retinanet_state_dict(seed=1234, depth=50, num_convs=4, cls_bias=None):
+def retinanet_state_dict(seed=1234, depth=50, num_convs=4, cls_bias=None, groups=1, width_per_group=64):
     """[UPSTREAM-RECALL] maskrcnn-benchmark retinanet_R-50/101-FPN state-dict names: backbone.body.* (the FrozenBN trunk), backbone.fpn.fpn_inner{2,3,4} /
     fpn_layer{2,3,4} (C2 has neither), backbone.fpn.top_blocks.{p6,p7}, rpn.head.cls_tower.{0,2,4,6} / bbox_tower.{0,2,4,6} (the odd indices are the
     ReLUs), rpn.head.cls_logits (9 x 80) and rpn.head.bbox_pred (9 x 4).  cls_bias: the constant part of the cls_logits bias (default RETINA_CLS_BIAS)."""
     rng = np.random.default_rng(seed)
     sd = {}
     tmp = {}
-    resnet_state_dict(rng, tmp, "", blocks=(3, 4, 23 if depth == 101 else 6, 3))
+    resnet_state_dict(rng, tmp, "", blocks=(3, 4, 23 if depth == 101 else 6, 3), groups=groups, width_per_group=width_per_group)   # (groups > 1: retinanet_X_101_32x8d_FPN_1x)
     for k, v in tmp.items():
         if k.startswith("conv1.") or k.startswith("bn1."):
             sd["backbone.body.stem." + k] = v
@@ -399,7 +405,7 @@ def random_maskrcnn_state_dict(cfg, seed=1234):
         return maskrcnn_c4_state_dict(seed, **kw)
     if cfg.USE_GN:
         return maskrcnn_gn_state_dict(seed, cfg.depth, cfg.BOX_HEAD_STACKED_CONVS, cfg.BOX_HEAD_CONV_DIM, cfg.BOX_HEAD_MLP_DIM, **kw)
-    return maskrcnn_state_dict(seed, cfg.depth, **kw)
+    return maskrcnn_state_dict(seed, cfg.depth, groups=int(getattr(cfg, "NUM_GROUPS", 1)), width_per_group=int(getattr(cfg, "WIDTH_PER_GROUP", 64)), **kw)
 
 
 # Synthetic pose templates in the 64 x 64 align frame, COCO keypoint order (nose, eyes, ears, shoulders, elbows, wrists, hips, knees,

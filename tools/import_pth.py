@@ -4,7 +4,7 @@ upstream key names isegmi.yolact.Yolact / isegmi.maskrcnn.MaskRCNN consume.
     python tools/import_pth.py IN OUT.npz [--family maskrcnn_r50_fpn|maskrcnn_r101_fpn|maskrcnn_r50_c4|maskrcnn_r50_fpn_gn|yolact_resnet50|yolact_base|
                                                     yolact_im700|yolact_darknet53|yolact_plus_resnet50|yolact_plus_base|retinanet_r50_fpn|retinanet_r101_fpn|
                                                     fasterrcnn_r50_fpn|fasterrcnn_r101_fpn|fasterrcnn_r50_c4|fasterrcnn_r50_fpn_gn|
-                                                    keypointrcnn_r50_fpn|keypointrcnn_r101_fpn]
+                                                    keypointrcnn_r50_fpn|keypointrcnn_r101_fpn|maskrcnn_x101_fpn|fasterrcnn_x101_fpn|retinanet_x101_fpn]
 
 Accepted inputs (torch is used HERE only to unpickle -- a tool, not the product):
   * dbolya/yolact `.pth` (the tables at README.md:209-221): a flat state dict; `module.` prefixes, `num_batches_tracked`, the
@@ -35,14 +35,19 @@ sys.path[:0] = [os.path.join(ROOT, "instancesegmentation-jittor_amd")]
 FAMILIES = ("maskrcnn_r50_fpn", "maskrcnn_r101_fpn", "maskrcnn_r50_c4", "maskrcnn_r50_fpn_gn", "yolact_resnet50", "yolact_base", "yolact_im700",
             "yolact_darknet53", "yolact_plus_resnet50", "yolact_plus_base", "retinanet_r50_fpn", "retinanet_r101_fpn",
             "fasterrcnn_r50_fpn", "fasterrcnn_r101_fpn", "fasterrcnn_r50_c4", "fasterrcnn_r50_fpn_gn",
-            "keypointrcnn_r50_fpn", "keypointrcnn_r101_fpn")
+            "keypointrcnn_r50_fpn", "keypointrcnn_r101_fpn", "maskrcnn_x101_fpn", "fasterrcnn_x101_fpn", "retinanet_x101_fpn")
 
 
 def expected_keys(family):
     """The complete state-dict key set (and shapes) of a model family, from the synthetic generators."""
     from isegmi import weights as W
     from isegmi.yolact import YolactConfig
-    if family.startswith("fasterrcnn_"):
+    if family.endswith("_x101_fpn"):
+        # [UPSTREAM-RECALL] *_X_101_32x8d_FPN_1x (DESIGN.md 16): the R-101 key sets with ResNeXt widths -- conv2 [width, width / 32, 3, 3], width = 256 << stage
+        x = dict(groups=32, width_per_group=8)
+        sd = {"maskrcnn_x101_fpn": lambda: W.maskrcnn_state_dict(0, 101, **x), "fasterrcnn_x101_fpn": lambda: W.maskrcnn_state_dict(0, 101, mask=False, **x),
+              "retinanet_x101_fpn": lambda: W.retinanet_state_dict(0, 101, **x)}[family]()
+    elif family.startswith("fasterrcnn_"):
         # [UPSTREAM-RECALL] e2e_faster_rcnn_*: the Mask R-CNN family's key set without roi_heads.mask.* (DESIGN.md 13)
         sd = {"fasterrcnn_r50_fpn": lambda: W.maskrcnn_state_dict(0, 50, mask=False), "fasterrcnn_r101_fpn": lambda: W.maskrcnn_state_dict(0, 101, mask=False),
               "fasterrcnn_r50_c4": lambda: W.maskrcnn_c4_state_dict(0, mask=False),
