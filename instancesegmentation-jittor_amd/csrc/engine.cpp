@@ -1051,7 +1051,7 @@ extern "C" int isegmi_engine_mark_step(isegmi_engine* h) {
     ARG_CHECK(e.step_marks.size() < 65536, "too many pending step marks");
     hipEvent_t ev;
     HIP_TRY(hipEventCreate(&ev));
-    HIP_TRY(hipEventRecord(ev, (e.multi_stream && e.tail_pending) ? e.tail : e.stream));
+    HIP_TRY(hipEventRecord(ev, eng_results_stream(e)));
     e.step_marks.push_back(ev);
     return ISEGMI_OK;
 }
@@ -1084,8 +1084,7 @@ extern "C" int isegmi_engine_step_times(isegmi_engine* h, float* ms, int cap, in
 
 extern "C" int isegmi_engine_stream(isegmi_engine* h, void** stream) {
     ARG_CHECK(h && stream, "null");
-    // the stream on which the last forward's RESULTS complete (Yolact: the tail stream)
-    *stream = (void*)((h->e.multi_stream && h->e.tail_pending) ? h->e.tail : h->e.stream);
+    *stream = (void*)eng_results_stream(h->e);  // (Yolact: the tail stream)
     return ISEGMI_OK;
 }
 
@@ -1194,7 +1193,7 @@ extern "C" int isegmi_yolact_pack_records(isegmi_engine* h, void* d_dst, int64_t
     const int N = e.last_N;
     ARG_CHECK(N > 0, "pack before forward");
     const int K = (int)e.param("max_num_detections", 100);
-    hipStream_t rs = (e.multi_stream && e.tail_pending) ? e.tail : e.stream;  // results stream
+    hipStream_t rs = eng_results_stream(e);
     const char* names[5] = {"det.count", "det.box", "det.score", "det.class", "det.coeff"};
     const int64_t sizes[5] = {(int64_t)N * 4, (int64_t)N * K * 16, (int64_t)N * K * 4, (int64_t)N * K * 4, (int64_t)N * K * 32 * 4};
     int64_t off = 0;

@@ -172,14 +172,14 @@ int eng_buf(Engine& e, const std::string& name, int64_t bytes, void** out, int d
 int eng_act(Engine& e, const std::string& name, int N, int H, int W, int C, Tensor* t, int dt = 0);
 int eng_conv(Engine& e, const std::string& layer, const Tensor& in, int stride, int pad, int act, const Tensor* residual,
              const std::string& out_name, Tensor* out, bool out_f32 = false, bool may_split = false);
-// conv writing into a caller-provided strided destination (heads -> concatenated buffers, deconv parities)
+// runs `body` (a forward's enqueue code) eagerly or, with the "graph" parameter, as a captured hipGraph keyed by `key`
 int eng_graph_run(Engine& e, const std::string& key, const std::function<int()>& body);
 void eng_graph_reset(Engine& e);
 int eng_tail_end(Engine& e);
 int eng_input_consumed(Engine& e);  // call right after the last kernel that reads the caller's input buffer
 int eng_wait_upload(Engine& e, const void* d_ptr, int64_t bytes, hipStream_t st);  // st waits for every pending upload / front-end write into [d_ptr, d_ptr + bytes)
 int eng_stage_small(Engine& e, const void* h_src, size_t bytes, void* d_dst, hipStream_t st);  // host array -> pinned ring slot -> async H2D on st
-hipStream_t eng_results_stream(Engine& e);  // the stream the last forward's results complete on  // st waits for a pending upload_async whose destination holds d_ptr
+hipStream_t eng_results_stream(Engine& e);  // the stream the last forward's results complete on
 int eng_bottleneck_f16(Engine& e, const std::string& block, const Tensor& x, bool first, const std::string& out_name, Tensor* out, bool* fused);
 int eng_conv_up2x_f16(Engine& e, const std::string& layer, const Tensor& x, const Tensor& coarse, const std::string& out_name, Tensor* out, bool* merged);
 // several independent convolutions of one point of the graph as ONE launch (fp32: conv2d_group_launch; fp16, a forced tile, a single member or
@@ -202,6 +202,7 @@ int conv2d_group_launch(int n, const isegmi_conv_desc* const* d, const float* co
 int eng_rpn_head_f16(Engine& e, const std::string& conv, const std::string& headl, const Tensor& x, const std::string& out_name, Tensor* out, bool* fused);
 int eng_stem_pool_f16(Engine& e, const std::string& layer, const Tensor& halo, int H, int W, const std::string& out_name, Tensor* out, bool* fused);
 int eng_conv_stem_f16(Engine& e, const std::string& layer, const Tensor& halo, int H, int W, const std::string& out_name, Tensor* out);
+// conv writing into a caller-provided strided destination (heads -> concatenated buffers, deconv parities)
 int eng_conv_into(Engine& e, const std::string& layer, const Tensor& in, int stride, int pad, int act, void* dst, int out_div,
                   int64_t out_img_stride, int64_t out_pix_stride, bool out_f32 = false);
 void eng_mark(Engine& e, const char* name);
@@ -309,6 +310,15 @@ void yolact_head_views(Engine& e);
 bool yolact_lazy_coeffs(Engine& e, int N);
 int yolact_fill_coeff_columns(Engine& e);
 int maskrcnn_forward(Engine& e, const float* d_images, int N);
+// maskrcnn.cpp: what the R-CNN graphs, retinanet.cpp and the results stage share
+int maskrcnn_set_image_hw(Engine& e, const int32_t* h_image_hw, int N);
+int maskrcnn_det_cap(Engine& e);
+int maskrcnn_nms_flags(Engine& e);
+int rcnn_trunk(Engine& e, const float* d_images, int N, bool full, Tensor* C);
+int level_anchors(Engine& e, int l, const RawBuf& base, int A, int gh, int gw, int64_t cap_cells, bool regen, const float** out);
+int rcnn_canvas_check(Engine& e, int N, int H, int W);
+int rcnn_begin_canvas(Engine& e, const float* d_images, const int32_t* h_image_hw, int N, int H, int W);
+int pose2seg_det_cap(Engine& e);  // pose2seg.cpp
 int eng_next_event(Engine& e, hipEvent_t* ev);
 int maskrcnn_paste(Engine& e, const float* h_ratios_wh, int out_h, int out_w);
 bool maskrcnn_mask_on(Engine& e);

@@ -26,8 +26,6 @@
 namespace isegmi {
 int rle_encode_launch(const isegmi_rle_args* a, hipStream_t st);
 
-int maskrcnn_det_cap(Engine& e);
-int pose2seg_det_cap(Engine& e);
 // Pose2Seg (kind 3) takes the Mask R-CNN record form (f32 boxes, i32 labels) with K = its max_instances
 static int det_cap(Engine& e) {
     return e.kind == 1 ? (int)e.param("max_num_detections", 100) : e.kind == 3 ? pose2seg_det_cap(e) : maskrcnn_det_cap(e);

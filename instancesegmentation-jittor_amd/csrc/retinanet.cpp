@@ -2,7 +2,7 @@
 // (stride in the first 1x1, FrozenBN folded by the host) -> P3-P7 FPN (laterals on C3-C5, nearest top-down, LastLevelP6P7 on C5) -> RetinaNetHead, one
 // set of weights over the five levels (two towers of 3x3 256 -> 256 + ReLU, cls_logits 3x3 -> A*80, bbox_pred 3x3 -> A*4) -> thresholded top-k and decode
 // per (level, image) -> class-wise NMS and the detections-per-image cut (csrc/retinanet_ops.hip).  Everything runs on the engine's main stream; results
-// land in det.count / det.box / det.score / det.label like the Mask R-CNN box head's.
+// land in det.count / det.box / det.score / det.label like the Mask R-CNN box head's.  Trunk, anchors, NMS flags, canvas checks: maskrcnn.cpp's shared stages.
 //
 // Every point of the graph that holds several independent convolutions is ONE grouped launch (eng_conv_group): the three laterals; the three output
 // convolutions with the two evaluations of top_blocks.p6 (P6 goes on without the ReLU, P7 reads relu(P6): the small p6 convolution runs with act 0 and
@@ -17,9 +17,6 @@
 #include "engine.h"
 
 namespace isegmi {
-
-int maskrcnn_set_image_hw(Engine& e, const int32_t* h_image_hw, int N);
-int maskrcnn_det_cap(Engine& e);
 
 constexpr int RETINA_LEVELS = 5;
 
@@ -36,26 +33,8 @@ static int retinanet_forward(Engine& e, const float* d_images, int N) {
     e.cur = e.stream;
     hipStream_t st = e.stream;
     eng_mark(e, "start");
-    int* d_hw = (int*)e.last_hw_ptr;
-
-    Tensor x;
-    TRY(resnet_stem(e, "backbone.body.stem.conv1", d_images, N, H, W, &x));
-    eng_mark(e, "stem");
-    const int depth = (int)e.param("resnet_depth", 50);
-    const int blocks[4] = {3, 4, depth == 101 ? 23 : 6, 3};
     Tensor C[4];
-    for (int li = 0; li < 4; ++li) {
-        ResStage rs;
-        rs.layers = rs.bufs = "backbone.body.layer" + std::to_string(li + 1);
-        rs.blocks = blocks[li];
-        rs.stride = li > 0 ? 2 : 1;
-        rs.stride_in_1x1 = e.param("stride_in_1x1", 1.0f) != 0.0f;
-        rs.full = true;
-        rs.stage = "res" + std::to_string(li + 2);
-        TRY(resnet_stage(e, rs, x, &x));
-        C[li] = x;
-        eng_mark(e, li == 0 ? "res2" : li == 1 ? "res3" : li == 2 ? "res4" : "res5");
-    }
+    TRY(rcnn_trunk(e, d_images, N, true, C));
 
     // ---- FPN: in_channels_list [0, 512, 1024, 2048] -- C2 has no lateral and no output
     Tensor lat[2], last[3], P[5], p6r;
@@ -118,8 +97,6 @@ static int retinanet_forward(Engine& e, const float* d_images, int N) {
     const int nclass = logits[0].C / A;
     const int top_n = (int)e.param("retina_pre_nms_top_n", 1000.0f);
     const int dpi = (int)e.param("detections_per_img", 100), cap = maskrcnn_det_cap(e);
-    const int flags = ((int)e.param("nms_ge", 0) ? ISEGMI_NMS_GE : 0) | ((int)e.param("nms_plus_one", 1) ? 0 : ISEGMI_NMS_NO_PLUS_ONE) |
-                      ((int)e.param("nms_index_order", 0) ? ISEGMI_NMS_INDEX_ORDER : 0);
     isegmi_retina_select_args sa;
     memset(&sa, 0, sizeof(sa));
     sa.nl = L; sa.N = N; sa.A = A; sa.C = nclass; sa.top_n = top_n;
@@ -130,15 +107,11 @@ static int retinanet_forward(Engine& e, const float* d_images, int N) {
         const std::string ls = std::to_string(l);
         auto base = e.tensors.find("anchor_base." + ls);
         if (base == e.tensors.end() || base->second.bytes != (int64_t)A * 16) { set_error("tensor not set (or of the wrong size): anchor_base." + ls); return ISEGMI_ERR_STATE; }
-        const int stride = (int)e.param("anchor_stride" + ls, 0.0f);
-        if (stride <= 0) { set_error("anchor_stride" + ls + " not set"); return ISEGMI_ERR_STATE; }
         int mh, mw;
         hw_max[l] = retina_level_hw(e.H, e.W, l, &mh, &mw);
-        void* q;
-        TRY(eng_buf(e, "anchors." + ls, (int64_t)hw_max[l] * A * 16, &q, 0, {(int64_t)logits[l].H * logits[l].W * A, 4}));
-        if (regen_anchors) TRY(grid_anchors_launch((const float*)base->second.d, A, stride, logits[l].H, logits[l].W, (float*)q, st));
+        TRY(level_anchors(e, l, base->second, A, logits[l].H, logits[l].W, hw_max[l], regen_anchors, &sa.d_anchors[l]));
         sa.HW[l] = logits[l].H * logits[l].W;
-        sa.d_logits[l] = logits[l].d; sa.d_deltas[l] = deltas[l].d; sa.d_anchors[l] = (const float*)q;
+        sa.d_logits[l] = logits[l].d; sa.d_deltas[l] = deltas[l].d;
         logit_bytes += (double)N * sa.HW[l] * A * nclass * 4;
     }
     const int64_t ws_sel = retina_select_workspace_bytes(L, e.max_batch, hw_max, A, nclass, top_n);
@@ -154,7 +127,7 @@ static int retinanet_forward(Engine& e, const float* d_images, int N) {
     TRY(eng_buf(e, "retina.cand_score", B * L * top_n * 4, &q, 0, {N, L * top_n})); sa.d_out_scores = (float*)q;
     TRY(eng_buf(e, "retina.cand_label", B * L * top_n * 4, &q, 1, {N, L * top_n})); sa.d_out_labels = (int32_t*)q;
     TRY(eng_buf(e, "retina.cand_cnt", B * L * 4, &q, 1, {N, L})); sa.d_out_cnt = (int32_t*)q;
-    sa.d_image_hw = d_hw;
+    sa.d_image_hw = (int*)e.last_hw_ptr;
     {   // algorithmic bytes: every logit once + deltas and anchor of the selected (32 B) + the candidate rows written (24 B)
         OpScope op(e, st, "retina_select (sigmoid + threshold + top-k + decode, all levels)", logit_bytes + (double)N * L * top_n * 56);
         TRY(retina_select_launch(&sa, st));
@@ -162,7 +135,7 @@ static int retinanet_forward(Engine& e, const float* d_images, int N) {
     eng_mark(e, "select");
     isegmi_retina_post_args pa;
     memset(&pa, 0, sizeof(pa));
-    pa.N = N; pa.nseg = L; pa.seg_len = top_n; pa.ncls = nclass + 1; pa.det_per_img = dpi; pa.cap = cap; pa.nms_flags = flags;
+    pa.N = N; pa.nseg = L; pa.seg_len = top_n; pa.ncls = nclass + 1; pa.det_per_img = dpi; pa.cap = cap; pa.nms_flags = maskrcnn_nms_flags(e);
     pa.nms_thresh = e.param("retina_nms_th", 0.4f);
     pa.d_boxes = sa.d_out_boxes; pa.d_scores = sa.d_out_scores; pa.d_labels = sa.d_out_labels; pa.d_seg_cnt = sa.d_out_cnt;
     TRY(eng_buf(e, "retina.post_ws", ws_post, &q, 2)); pa.d_ws = q; pa.ws_bytes = ws_post;
@@ -187,8 +160,7 @@ extern "C" int isegmi_retinanet_forward_canvas(isegmi_engine* h, const float* d_
     ARG_CHECK(h && d_images && h_image_hw, "null");
     Engine& e = h->e;
     ARG_CHECK(e.kind == 4, "engine is not a RetinaNet engine");
-    ARG_CHECK(N > 0 && N <= e.max_batch, "batch size");
-    ARG_CHECK(H > 0 && W > 0 && H <= e.H && W <= e.W, "canvas must fit inside the engine's maximum input size");
+    TRY(rcnn_canvas_check(e, N, H, W));
     ARG_CHECK(H % 32 == 0 && W % 32 == 0, "RetinaNet input must be padded to a multiple of 32");
     if (e.param("fp16", 0.0f) != 0.0f || e.fp16) { set_error("retinanet: fp16 is not supported (fp32 only)"); return ISEGMI_ERR_ARG; }
     if (e.param("graph", 0.0f) != 0.0f) { set_error("retinanet: graph capture is not supported (graph must be 0)"); return ISEGMI_ERR_ARG; }
@@ -196,12 +168,7 @@ extern "C" int isegmi_retinanet_forward_canvas(isegmi_engine* h, const float* d_
     const int top_n = (int)e.param("retina_pre_nms_top_n", 1000.0f);
     if (top_n < 1 || top_n > 1024) { set_error("retinanet: retina_pre_nms_top_n must be 1..1024 (what the selection kernels hold)"); return ISEGMI_ERR_ARG; }
     if ((int)e.param("retina_num_convs", 4.0f) < 1) { set_error("retinanet: retina_num_convs must be at least 1"); return ISEGMI_ERR_ARG; }
-    for (int i = 0; i < N; ++i)
-        ARG_CHECK(h_image_hw[2 * i] > 0 && h_image_hw[2 * i] <= H && h_image_hw[2 * i + 1] > 0 && h_image_hw[2 * i + 1] <= W,
-                  "image_hw must fit inside the padded canvas");
-    TRY(eng_wait_upload(e, d_images, (int64_t)N * H * W * 3 * 4, e.stream));
-    TRY(maskrcnn_set_image_hw(e, h_image_hw, N));
-    e.cur_H = H; e.cur_W = W;
+    TRY(rcnn_begin_canvas(e, d_images, h_image_hw, N, H, W));
     const int rc = retinanet_forward(e, d_images, N);
     e.cur = e.stream;
     if (rc == ISEGMI_OK) e.last_N = N;

@@ -461,7 +461,7 @@ int yolact_postprocess(Engine& e, int h, int w, const int32_t* h_image_hw) {
     RawBuf& proto = e.bufs["proto"];
     const int PH = (int)proto.shape[1], PW = (int)proto.shape[2], md = (int)proto.shape[3];
     void *lo, *masks, *ib;
-    hipStream_t rs = (e.multi_stream && e.tail_pending) ? e.tail : e.stream;  // results stream of the last forward
+    hipStream_t rs = eng_results_stream(e);
     int* d_ihw = nullptr;
     if (h_image_hw) {
         for (int i = 0; i < N; ++i)
