@@ -1212,6 +1212,7 @@ int gather_proposals_launch(const float* cand_boxes, const float* fin_vals, cons
 int roi_align_launch(const float* const* feats, const int* Hs, const int* Ws, const float* scales, int nlevels, const float* rois,
                      const int* counts, int N, int K, int C, int PH, int PW, int g, int k_min, int fixed_level, float* out,
                      int* out_level, hipStream_t st, const int* order, const void* tab, int aligned) {
+    ARG_CHECK(feats && Hs && Ws && scales && rois && counts && out && fixed_level < nlevels, "roi_align args");
     ARG_CHECK(nlevels >= 1 && nlevels <= 4 && C % 4 == 0, "roi_align levels/C");
     RoiLevels lv;
     for (int i = 0; i < 4; ++i) {

@@ -8,6 +8,10 @@ import os
 
 import numpy as np
 
+from . import _abi
+from ._abi import (RETINA_MAX_LEVELS, BottleneckDesc, BoxPostArgs, CocoMatchArgs, ConvDesc, P2sImage, RetinaPostArgs,  # noqa: F401 (re-exported)
+                   RetinaSelectArgs, RleArgs, YolactDetectArgs)
+
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG, "lib", "libisegmi.so")
 
@@ -28,21 +32,17 @@ def lib():
             raise IsegmiError(
                 "libisegmi.so not built (%s): run `python -c 'import __graft_entry__ as g; g.build()'` "
                 "or `make -C instancesegmentation-jittor_amd`; there is no CPU fallback" % LIB_PATH)
-        _lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-        _lib.isegmi_last_error.restype = C.c_char_p
-        _lib.isegmi_op_roi_table_bytes.restype = C.c_int64
+        loaded = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
+        missing = _abi.declare(loaded)   # restype / argtypes of the whole C ABI, once: a wrong arity or a float for an integer raises at the call
+        if missing:
+            raise IsegmiError("%s does not export %s (include/isegmi.h declares it): rebuild the library" % (LIB_PATH, ", ".join(missing)))
+        _lib = loaded
     return _lib
 
 
 def check(rc):
     if rc != 0:
         raise IsegmiError("libisegmi error %d: %s" % (rc, lib().isegmi_last_error().decode(errors="replace")))
-
-
-class ConvDesc(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in
-                ("N", "H", "W", "Cin", "Cout", "R", "S", "stride", "pad", "act", "tile", "out_div")] + \
-               [("out_img_stride", C.c_int64), ("out_pix_stride", C.c_int64)]
 
 
 def device_count():
@@ -52,7 +52,7 @@ def device_count():
 
 
 def set_device(i):
-    check(lib().isegmi_set_device(C.c_int(i)))
+    check(lib().isegmi_set_device(i))
 
 
 def sync():
@@ -74,7 +74,7 @@ def get_f16_mfma_shape():
 def box_calibrate(ms_per_leg=30.0):
     """{mfma_f32_tflops, mfma_f16_tflops, hbm_copy_gbs} of bare loops on the current device (isegmi_box_calibrate)."""
     a, b, c = C.c_double(), C.c_double(), C.c_double()
-    check(lib().isegmi_box_calibrate(C.c_double(ms_per_leg), C.byref(a), C.byref(b), C.byref(c)))
+    check(lib().isegmi_box_calibrate(ms_per_leg, C.byref(a), C.byref(b), C.byref(c)))
     return {"mfma_f32_tflops": round(a.value, 1), "mfma_f16_tflops": round(b.value, 1), "hbm_copy_gbs": round(c.value, 1)}
 
 
@@ -86,7 +86,7 @@ class DeviceBuffer:
         self.dtype = np.dtype(dtype)
         self.nbytes = int(np.prod(self.shape, dtype=np.int64)) * self.dtype.itemsize
         p = C.c_void_p()
-        check(lib().isegmi_malloc(C.byref(p), C.c_int64(self.nbytes)))
+        check(lib().isegmi_malloc(C.byref(p), self.nbytes))
         self.ptr = p
 
     @classmethod
@@ -94,27 +94,27 @@ class DeviceBuffer:
         a = np.ascontiguousarray(a)
         b = cls(a.shape, a.dtype)
         if b.nbytes:
-            check(lib().isegmi_h2d(b.ptr, a.ctypes.data_as(C.c_void_p), C.c_int64(b.nbytes)))
+            check(lib().isegmi_h2d(b.ptr, a.ctypes.data_as(C.c_void_p), b.nbytes))
         return b
 
     def upload(self, a):
         a = np.ascontiguousarray(a, dtype=self.dtype)
         assert a.nbytes == self.nbytes, (a.shape, self.shape)
-        check(lib().isegmi_h2d(self.ptr, a.ctypes.data_as(C.c_void_p), C.c_int64(self.nbytes)))
+        check(lib().isegmi_h2d(self.ptr, a.ctypes.data_as(C.c_void_p), self.nbytes))
 
     def numpy(self):
         out = np.empty(self.shape, self.dtype)
         if self.nbytes:
-            check(lib().isegmi_d2h(out.ctypes.data_as(C.c_void_p), self.ptr, C.c_int64(self.nbytes)))
+            check(lib().isegmi_d2h(out.ctypes.data_as(C.c_void_p), self.ptr, self.nbytes))
         return out
 
     def zero(self):
-        check(lib().isegmi_memset(self.ptr, C.c_int(0), C.c_int64(self.nbytes)))
+        check(lib().isegmi_memset(self.ptr, 0, self.nbytes))
 
     def poison(self):
         """0xFF in every byte (NaN as fp16 / fp32, -1 as an integer): an element a kernel never wrote cannot pass as a zero."""
         if self.nbytes:
-            check(lib().isegmi_memset(self.ptr, C.c_int(0xFF), C.c_int64(self.nbytes)))
+            check(lib().isegmi_memset(self.ptr, 0xFF, self.nbytes))
         return self
 
     def free(self):
@@ -137,7 +137,7 @@ class PinnedBuffer:
         self.dtype = np.dtype(dtype)
         self.nbytes = int(np.prod(self.shape, dtype=np.int64)) * self.dtype.itemsize
         p = C.c_void_p()
-        check(lib().isegmi_malloc_host(C.byref(p), C.c_int64(self.nbytes)))
+        check(lib().isegmi_malloc_host(C.byref(p), self.nbytes))
         self.ptr = p
         self.array = np.frombuffer((C.c_char * self.nbytes).from_address(p.value), self.dtype).reshape(self.shape)
 
@@ -216,15 +216,15 @@ def pack_conv_weights_grouped(desc, groups, w):
     """host: [Cout,3,3,Cin/groups] fp32 -> the packed 1-D fp32 image of isegmi_op_conv2d_grouped."""
     w = np.ascontiguousarray(w, np.float32)
     n = C.c_int64()
-    check(lib().isegmi_conv_grouped_packed_floats(C.byref(desc), C.c_int(groups), C.byref(n)))
+    check(lib().isegmi_conv_grouped_packed_floats(C.byref(desc), groups, C.byref(n)))
     assert w.shape == (desc.Cout, 3, 3, desc.Cin // groups), (w.shape, desc.Cout, desc.Cin, groups)
     out = np.empty(n.value, np.float32)
-    check(lib().isegmi_pack_conv_weights_grouped(C.byref(desc), C.c_int(groups), w.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+    check(lib().isegmi_pack_conv_weights_grouped(C.byref(desc), groups, w.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
     return out
 
 
 def op_conv2d_grouped(desc, groups, d_in, d_wpacked, d_scale=None, d_shift=None, d_residual=None, d_out=None):
-    check(lib().isegmi_op_conv2d_grouped(C.byref(desc), C.c_int(groups), _ptr(d_in), _ptr(d_wpacked), _ptr(d_scale), _ptr(d_shift),
+    check(lib().isegmi_op_conv2d_grouped(C.byref(desc), groups, _ptr(d_in), _ptr(d_wpacked), _ptr(d_scale), _ptr(d_shift),
                                          _ptr(d_residual), _ptr(d_out), None))
 
 
@@ -302,23 +302,13 @@ def resize_bilinear(x, Ho, Wo, add=None, relu=0):
     return do.numpy()
 
 
-def _kp(name):
-    """A keypoint-tail entry point with its argtypes declared: an ABI change raises instead of shifting arguments."""
-    f = getattr(lib(), name)
-    if f.argtypes is None:
-        V, I, L = C.c_void_p, C.c_int, C.c_int64
-        f.argtypes = {"isegmi_op_keypoint_heatmap": [V, L, I, I, I, V, V], "isegmi_op_keypoint_decode": [V, V, V, I, I, I, I, V, V, V]}[name]
-        f.restype = I
-    return f
-
-
 def keypoint_heatmap(x, K):
     """isegmi_op_keypoint_heatmap: x [R, Hi, Wi, 4 * K] (the packed transposed convolution's output) -> [R, 4 Hi, 4 Wi, K]."""
     x = np.ascontiguousarray(x, np.float32)
     R, Hi, Wi, c = x.shape
     assert c == 4 * K, (c, K)
     dx = DeviceBuffer.from_numpy(x); do = DeviceBuffer((R, 4 * Hi, 4 * Wi, K)).poison()
-    check(_kp("isegmi_op_keypoint_heatmap")(dx.ptr, R, Hi, Wi, K, do.ptr, None))
+    check(lib().isegmi_op_keypoint_heatmap(dx.ptr, R, Hi, Wi, K, do.ptr, None))
     return do.numpy()
 
 
@@ -332,7 +322,7 @@ def keypoint_decode(heat, boxes, count):
     assert R == N * cap and S == S2 and boxes.shape == (N, cap, 4) and count.shape == (N,), (heat.shape, boxes.shape, count.shape)
     dh, db, dc = DeviceBuffer.from_numpy(heat), DeviceBuffer.from_numpy(boxes), DeviceBuffer.from_numpy(count)
     dk, ds = DeviceBuffer((N, cap, K, 3)).poison(), DeviceBuffer((N, cap, K)).poison()
-    check(_kp("isegmi_op_keypoint_decode")(dh.ptr, db.ptr, dc.ptr, N, cap, S, K, dk.ptr, ds.ptr, None))
+    check(lib().isegmi_op_keypoint_decode(dh.ptr, db.ptr, dc.ptr, N, cap, S, K, dk.ptr, ds.ptr, None))
     return dk.numpy(), ds.numpy()
 
 
@@ -355,7 +345,7 @@ def preprocess_u8(images_u8, Hout, Wout, Hpad, Wpad, mean3, std3, swap_rb):
     N, H, W, _ = x.shape
     dx = DeviceBuffer.from_numpy(x); do = DeviceBuffer((N, Hpad, Wpad, 3))
     m = (C.c_float * 3)(*[float(v) for v in mean3]); sd = (C.c_float * 3)(*[float(v) for v in std3])
-    check(lib().isegmi_op_preprocess_u8(dx.ptr, N, H, W, do.ptr, Hout, Wout, Hpad, Wpad, C.c_int64(Hpad * Wpad * 3), m, sd, int(bool(swap_rb)), None))
+    check(lib().isegmi_op_preprocess_u8(dx.ptr, N, H, W, do.ptr, Hout, Wout, Hpad, Wpad, Hpad * Wpad * 3, m, sd, int(bool(swap_rb)), None))
     return do.numpy()
 
 
@@ -379,25 +369,11 @@ def upsample_nearest2x_add(coarse, lateral):
     return do.numpy()
 
 
-def _group_norm_fn():
-    """isegmi_op_group_norm with its argtypes declared: an ABI change raises instead of shifting arguments."""
-    f = lib().isegmi_op_group_norm
-    if f.argtypes is None:
-        V, I, L = C.c_void_p, C.c_int, C.c_int64
-        f.argtypes = [V, L, I, I, I, I, V, V, C.c_float, V, I, V, V, L, V]
-        f.restype = I
-        w = lib().isegmi_op_group_norm_workspace_bytes
-        w.argtypes = [L, I, I, I, I]
-        w.restype = L
-    return f
-
-
 def group_norm_device(d_x, N, H, W, Cc, groups, d_gamma, d_beta, eps=1e-5, d_residual=None, relu=False, d_out=None, d_ws=None, ws_bytes=None,
                       alloc_ws=True, offsets=None):
     """isegmi_op_group_norm on DeviceBuffers (d_out None: in place; d_ws None: allocated here when the shape needs one).  Returns the workspace.
     For the launcher's refusals: `ws_bytes` is the workspace size handed over (default: the buffer's), `alloc_ws` False passes a null workspace where
     none is given, `offsets` {"x" | "out" | "gamma" | "beta" | "residual" | "ws": bytes} moves a pointer into its (over-allocated) buffer."""
-    f = _group_norm_fn()
     need = lib().isegmi_op_group_norm_workspace_bytes(N, H, W, Cc, groups)
     if d_ws is None and need and alloc_ws:
         d_ws = DeviceBuffer((need,), np.uint8)
@@ -407,8 +383,8 @@ def group_norm_device(d_x, N, H, W, Cc, groups, d_gamma, d_beta, eps=1e-5, d_res
         return C.c_void_p(buf.ptr.value + off[key]) if buf is not None and off.get(key) else _ptr(buf)
     if ws_bytes is None:
         ws_bytes = d_ws.nbytes if d_ws is not None else 0
-    check(f(at(d_x, "x"), N, H, W, Cc, groups, at(d_gamma, "gamma"), at(d_beta, "beta"), float(eps), at(d_residual, "residual"), int(bool(relu)),
-            at(d_out or d_x, "out"), at(d_ws, "ws"), ws_bytes, None))
+    check(lib().isegmi_op_group_norm(at(d_x, "x"), N, H, W, Cc, groups, at(d_gamma, "gamma"), at(d_beta, "beta"), float(eps), at(d_residual, "residual"),
+                                     int(bool(relu)), at(d_out or d_x, "out"), at(d_ws, "ws"), ws_bytes, None))
     return d_ws
 
 
@@ -444,14 +420,14 @@ def pad_c3_to_c4(x):
     assert x.shape[-1] == 3, x.shape
     npix = x.size // 3
     dx = DeviceBuffer.from_numpy(x); do = DeviceBuffer(x.shape[:-1] + (4,)).poison()
-    check(lib().isegmi_op_pad_c3_to_c4(dx.ptr, C.c_int64(npix), do.ptr, None))
+    check(lib().isegmi_op_pad_c3_to_c4(dx.ptr, npix, do.ptr, None))
     return do.numpy()
 
 
 def map_f32(x, fn):
     x = np.ascontiguousarray(x, np.float32)
     dx = DeviceBuffer.from_numpy(x); dy = DeviceBuffer(x.shape)
-    check(lib().isegmi_op_map_f32(dx.ptr, dy.ptr, C.c_int64(x.size), fn, None))
+    check(lib().isegmi_op_map_f32(dx.ptr, dy.ptr, x.size, fn, None))
     return dy.numpy()
 
 
@@ -470,19 +446,8 @@ def topk(keys2d, k, limit=None, rows_per_limit=1, row_stride=None):
     dv = DeviceBuffer((rows, k), np.float32); di = DeviceBuffer((rows, k), np.int32); dc = DeviceBuffer((rows,), np.int32)
     dv.zero(); di.zero()
     dl = None if limit is None else DeviceBuffer.from_numpy(np.asarray(limit, np.int32))
-    check(lib().isegmi_op_topk(dk.ptr, C.c_int64(row_stride), rows, n, k, _ptr(dl), rows_per_limit, dv.ptr, di.ptr, dc.ptr, None))
+    check(lib().isegmi_op_topk(dk.ptr, row_stride, rows, n, k, _ptr(dl), rows_per_limit, dv.ptr, di.ptr, dc.ptr, None))
     return dv.numpy(), di.numpy(), dc.numpy()
-
-
-class YolactDetectArgs(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("N", "P", "ncls", "mask_dim", "top_k", "max_det")] + \
-               [("conf_thresh", C.c_float), ("nms_thresh", C.c_float)] + \
-               [(n, C.c_void_p) for n in (
-                   "d_conf", "d_loc", "d_mask", "d_priors", "d_ws_scoresT", "d_ws_boxes", "d_ws_counts", "d_ws_tk_vals",
-                   "d_ws_tk_idx", "d_ws_tk_cnt", "d_ws_cand", "d_ws_fin_vals", "d_ws_fin_idx", "d_ws_fin_cnt",
-                   "d_out_count", "d_out_boxes", "d_out_scores", "d_out_classes", "d_out_coeffs", "d_out_prior")] + \
-               [("A", C.c_int32), ("mask_tanh", C.c_int32), ("pix_stride", C.c_int64), ("off_loc", C.c_int32), ("off_conf", C.c_int32),
-                ("off_mask", C.c_int32), ("second_threshold", C.c_int32)]
 
 
 def yolact_detect(conf_logits, loc, mask, priors, conf_thresh=0.05, nms_thresh=0.5, top_k=200, max_det=100, second_threshold=0):
@@ -518,11 +483,6 @@ def yolact_coeff_rows(feats, w_krsc, bias, A, rows, counts, row0, pad=1, sentine
     """isegmi_op_yolact_coeff_rows: feats = list of <= 5 [N,H,W,Cin] maps; w_krsc / bias = the whole head layer (>= row0 + 32 A output channels);
     rows [N,max_det,5] int32 (image, level, ho, wo, anchor); counts [N].  -> [N,max_det,32] pre-tanh; slots past the count keep `sentinel` in
     every element (default: 0xFF bytes)."""
-    V, I = C.c_void_p, C.c_int
-    f = lib().isegmi_op_yolact_coeff_rows
-    if f.argtypes is None:   # declared: an ABI change raises instead of shifting arguments
-        f.argtypes = [I, V, V, V, I, I, I, I, I, V, V, V, I, I, V, V, I, V, V]
-        f.restype = I
     feats = [np.ascontiguousarray(x, np.float32) for x in feats]
     N, Cin = feats[0].shape[0], feats[0].shape[3]
     Cout, R, S, _ = w_krsc.shape
@@ -538,7 +498,8 @@ def yolact_coeff_rows(feats, w_krsc, bias, A, rows, counts, row0, pad=1, sentine
     hs = (C.c_int32 * len(dfs))(*[x.shape[1] for x in feats]); ws = (C.c_int32 * len(dfs))(*[x.shape[2] for x in feats])
     dr = DeviceBuffer.from_numpy(rows); dc = DeviceBuffer.from_numpy(np.ascontiguousarray(counts, np.int32))
     do = DeviceBuffer((N, max_det, 32)).poison() if sentinel is None else DeviceBuffer.from_numpy(np.full((N, max_det, 32), sentinel, np.float32))
-    check(f(len(dfs), ptrs, hs, ws, N, Cin, R, S, pad, dw.ptr, _ptr(dsc), _ptr(db), A, row0, dr.ptr, dc.ptr, max_det, do.ptr, None))
+    check(lib().isegmi_op_yolact_coeff_rows(len(dfs), ptrs, hs, ws, N, Cin, R, S, pad, dw.ptr, _ptr(dsc), _ptr(db), A, row0, dr.ptr, dc.ptr, max_det,
+                                            do.ptr, None))
     return do.numpy()
 
 
@@ -566,7 +527,7 @@ def nms(boxes, scores, thr, plus_one=1, ge=0, max_keep=0):
     P, n = scores.shape
     db = DeviceBuffer.from_numpy(boxes); ds = DeviceBuffer.from_numpy(scores)
     dk = DeviceBuffer((P, n), np.int32); dc = DeviceBuffer((P,), np.int32)
-    check(lib().isegmi_op_nms(db.ptr, ds.ptr, P, n, C.c_float(thr), plus_one, ge, max_keep, dk.ptr, dc.ptr, None))
+    check(lib().isegmi_op_nms(db.ptr, ds.ptr, P, n, thr, plus_one, ge, max_keep, dk.ptr, dc.ptr, None))
     k, c = dk.numpy(), dc.numpy()
     return [k[i, : c[i]].copy() for i in range(P)]
 
@@ -625,7 +586,7 @@ def avgpool_full(x):
     x = np.ascontiguousarray(x, np.float32)
     R_, H, W, Cc = x.shape
     dx = DeviceBuffer.from_numpy(x); do = DeviceBuffer((R_, Cc)).poison()
-    check(lib().isegmi_op_avgpool_full(dx.ptr, C.c_int64(R_), H * W, Cc, do.ptr, None))
+    check(lib().isegmi_op_avgpool_full(dx.ptr, R_, H * W, Cc, do.ptr, None))
     return do.numpy()
 
 
@@ -641,16 +602,6 @@ def roi_align_f16(feats, scales, rois, counts, PH, PW, sampling=2, k_min=2, alig
     do = DeviceBuffer((N * K, PH, PW, Cc), np.float16)
     check(lib().isegmi_op_roi_align_f16(ptrs, Hs, Ws, sc, len(fb), dr.ptr, dcnt.ptr, N, K, Cc, PH, PW, sampling, aligned, k_min, do.ptr, None))
     return do.numpy()
-
-
-class BoxPostArgs(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("N", "R", "ncls", "det_per_img", "cap", "nms_flags")] + \
-               [("score_thresh", C.c_float), ("nms_thresh", C.c_float), ("logits_stride", C.c_int64), ("regr_stride", C.c_int64)] + \
-               [(n, C.c_void_p) for n in ("d_logits", "d_regr", "d_props", "d_prop_cnt", "d_image_hw", "d_ws_prob", "d_ws_cand_scores",
-                                          "d_ws_cand_boxes", "d_ws_kept_total", "d_ws_top_vals", "d_ws_top_idx", "d_out_count",
-                                          "d_out_boxes", "d_out_scores", "d_out_labels", "d_ws_crowd_matrix", "d_ws_crowd_keys",
-                                          "d_ws_crowd_boxes", "d_ws_crowd_m")] + \
-               [("cls_agnostic", C.c_int32)]
 
 
 def box_postprocess(logits, regr, props, prop_cnt, image_hw, score_thr=0.05, nms_thr=0.5, det_per_img=100, nms_flags=0, cap=0, chip_wide=True,
@@ -719,7 +670,7 @@ def paste_masks(masks, boxes, counts, im_h, im_w, thr=0.5):
     N, K, M, _ = masks.shape
     dm = DeviceBuffer.from_numpy(masks); db = DeviceBuffer.from_numpy(np.ascontiguousarray(boxes, np.float32))
     dc = DeviceBuffer.from_numpy(np.ascontiguousarray(counts, np.int32)); do = DeviceBuffer((N, K, im_h, im_w), np.uint8)
-    check(lib().isegmi_op_paste_masks(dm.ptr, db.ptr, dc.ptr, N, K, M, im_h, im_w, C.c_float(thr), do.ptr, None))
+    check(lib().isegmi_op_paste_masks(dm.ptr, db.ptr, dc.ptr, N, K, M, im_h, im_w, thr, do.ptr, None))
     return do.numpy()
 
 
@@ -734,7 +685,7 @@ def rpn_level(head, anchors, image_hw, A, pre_nms, post_nms, nms_thr=0.7, min_si
     wp = DeviceBuffer((N, HW * A)); tv = DeviceBuffer((N, pre_nms)); ti = DeviceBuffer((N, pre_nms), np.int32); tc = DeviceBuffer((N,), np.int32)
     ob = DeviceBuffer((N, post_nms, 4)); os_ = DeviceBuffer((N, post_nms)); oc = DeviceBuffer((N,), np.int32)
     wn = DeviceBuffer((N, 131072), np.uint8) if chip_wide and pre_nms <= 1024 else None
-    check(lib().isegmi_op_rpn_level(dh.ptr, da.ptr, dhw.ptr, N, HW, A, pre_nms, post_nms, C.c_float(nms_thr), C.c_float(min_size), nms_flags,
+    check(lib().isegmi_op_rpn_level(dh.ptr, da.ptr, dhw.ptr, N, HW, A, pre_nms, post_nms, nms_thr, min_size, nms_flags,
                                     wp.ptr, tv.ptr, ti.ptr, tc.ptr, ob.ptr, os_.ptr, oc.ptr, wn.ptr if wn is not None else None, None))
     c = oc.numpy(); B = ob.numpy(); S = os_.numpy()
     return [(B[i, : c[i]], S[i, : c[i]]) for i in range(N)]
@@ -755,29 +706,13 @@ def rpn_levels(heads, anchors, image_hw, A, pre_nms, post_nms, nms_thr=0.7, min_
     tv = DeviceBuffer((nl, N, pre_nms)); ti = DeviceBuffer((nl, N, pre_nms), np.int32); tc = DeviceBuffer((nl, N), np.int32)
     wn = DeviceBuffer((nl * N, 131072), np.uint8)
     ob = DeviceBuffer((N, nl, post_nms, 4)); os_ = DeviceBuffer((N, nl, post_nms)); oc = DeviceBuffer((N, nl), np.int32)
-    check(lib().isegmi_op_rpn_levels(nl, ph, pa, HW, dhw.ptr, N, A, pre_nms, post_nms, C.c_float(nms_thr), C.c_float(min_size), nms_flags, wp.ptr, cv.ptr, ci.ptr,
+    check(lib().isegmi_op_rpn_levels(nl, ph, pa, HW, dhw.ptr, N, A, pre_nms, post_nms, nms_thr, min_size, nms_flags, wp.ptr, cv.ptr, ci.ptr,
                                      tv.ptr, ti.ptr, tc.ptr, wn.ptr, ob.ptr, os_.ptr, oc.ptr, None))
     c = oc.numpy(); B = ob.numpy(); S = os_.numpy()
     return [[(B[i, l, : c[i, l]], S[i, l, : c[i, l]]) for i in range(N)] for l in range(nl)]
 
 
 # ---------------------------------------------------------------- RetinaNet tail
-RETINA_MAX_LEVELS = 5
-
-
-class RetinaSelectArgs(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("nl", "N", "A", "C", "top_n")] + [("score_thresh", C.c_float), ("min_size", C.c_float),
-               ("HW", C.c_int32 * RETINA_MAX_LEVELS), ("d_logits", C.c_void_p * RETINA_MAX_LEVELS), ("d_deltas", C.c_void_p * RETINA_MAX_LEVELS),
-               ("d_anchors", C.c_void_p * RETINA_MAX_LEVELS), ("d_image_hw", C.c_void_p), ("d_ws", C.c_void_p), ("ws_bytes", C.c_int64)] + \
-               [(n, C.c_void_p) for n in ("d_sel_scores", "d_sel_idx", "d_sel_cnt", "d_out_boxes", "d_out_scores", "d_out_labels", "d_out_cnt")]
-
-
-class RetinaPostArgs(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("N", "nseg", "seg_len", "ncls", "det_per_img", "cap", "nms_flags")] + [("nms_thresh", C.c_float)] + \
-               [(n, C.c_void_p) for n in ("d_boxes", "d_scores", "d_labels", "d_seg_cnt", "d_ws")] + [("ws_bytes", C.c_int64)] + \
-               [(n, C.c_void_p) for n in ("d_out_count", "d_out_boxes", "d_out_scores", "d_out_labels")]
-
-
 def retina_select(logits, A, top_n, score_thr=0.05, deltas=None, anchors=None, image_hw=None, min_size=0.0):
     """isegmi_op_retina_select: logits[l] [N,H_l,W_l,A*C] -> per level a list over images of (scores, flat indices); with deltas[l] [N,H_l,W_l,A*4],
     anchors[l] [H_l*W_l*A,4] and image_hw [N,2] also the decoded lists: (sel, dec) with dec[l][i] = (boxes, scores, labels)."""
@@ -792,7 +727,6 @@ def retina_select(logits, A, top_n, score_thr=0.05, deltas=None, anchors=None, i
     for l in range(nl):
         a.HW[l] = lg[l].shape[1] * lg[l].shape[2]
         a.d_logits[l] = keep[l].ptr.value
-    lib().isegmi_op_retina_select_workspace.restype = C.c_int64
     wsb = lib().isegmi_op_retina_select_workspace(nl, N, a.HW, A, Cc, top_n)
     if wsb < 0:
         raise IsegmiError("isegmi_op_retina_select_workspace: bad sizes")
@@ -830,7 +764,6 @@ def retina_postprocess(boxes, scores, labels, seg_cnt, ncls=81, nms_thr=0.4, det
     cap = max(det_per_img, cap)
     db = DeviceBuffer.from_numpy(boxes); ds = DeviceBuffer.from_numpy(np.ascontiguousarray(scores, np.float32))
     dl = DeviceBuffer.from_numpy(np.ascontiguousarray(labels, np.int32)); dc = DeviceBuffer.from_numpy(np.ascontiguousarray(seg_cnt, np.int32))
-    lib().isegmi_op_retina_postprocess_workspace.restype = C.c_int64
     wsb = lib().isegmi_op_retina_postprocess_workspace(N, nseg, seg_len)
     if wsb < 0:
         raise IsegmiError("isegmi_op_retina_postprocess_workspace: bad sizes")
@@ -931,10 +864,6 @@ def conv2d_f16(x, w_krsc, stride=1, pad=0, scale=None, shift=None, residual=None
     return do.numpy()
 
 
-class BottleneckDesc(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("N", "H", "W", "Cin", "Cmid", "flags")]
-
-
 def bottleneck_ds_f16(x, w1, sb1, w2, sb2, w3, sb3, wd, sbd, flags=0):
     """First block of res2 with its projection shortcut (isegmi_op_bottleneck_ds_f16): x fp16 [N,H,W,64]; wd [256,1,1,64].  Returns fp16 [N,H,W,256]."""
     x = np.ascontiguousarray(x, np.float16)
@@ -973,12 +902,6 @@ def bottleneck_f16(x, w1, sb1, w2, sb2, w3, sb3, flags=0):
 
 
 # ---------------------------------------------------------------- COCO RLE on the device
-class RleArgs(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("N", "K", "plane_h", "plane_w", "cap_runs", "cap_chars")] + \
-               [(n, C.c_void_p) for n in ("d_masks", "d_count", "d_image_hw", "d_windows", "d_ws_trans", "d_ws_col", "d_ws_nruns", "d_ws_tile", "d_ws_len",
-                                          "d_ws_starts", "d_out_run_off", "d_out_counts", "d_out_str_off", "d_out_chars", "d_out_status")]
-
-
 def rle_encode(masks, count=None, image_hw=None, cap_runs=None, cap_chars=None, windows=None):
     """masks [N,K,h,w] uint8 -> (run_off [N*K+1], counts, str_off [N*K+1], chars bytes, status [4]): pycocotools rleEncode + rleToString of
     every valid slot (k < count[n]) over the top-left image_hw[n] window of its plane (host convenience wrapper of isegmi_op_rle_encode).
@@ -1004,62 +927,30 @@ def rle_encode(masks, count=None, image_hw=None, cap_runs=None, cap_chars=None, 
 
 
 # ---------------------------------------------------------------- Pose2Seg pose-guided stages (csrc/pose2seg_ops.hip)
-class P2sImage(C.Structure):
-    """isegmi_p2s_image: one image of a letterbox batch."""
-    _fields_ = [("offset", C.c_int64), ("h", C.c_int32), ("w", C.c_int32), ("minv", C.c_float * 6), ("reserved", C.c_int32 * 2)]
-
-
-_VP, _I32 = C.c_void_p, C.c_int
-_P2S_SIGS = {
-    "isegmi_op_pose2seg_letterbox": [_VP, _VP, _I32, _I32, C.POINTER(C.c_float), C.POINTER(C.c_float), _I32, _I32, _VP, _VP],
-    "isegmi_op_pose2seg_fit": [_VP, _VP, _I32, _VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP],
-    "isegmi_op_pose2seg_align": [_VP, _I32, _I32, _I32, _VP, _VP, _I32, _VP, _I32, _VP],
-    "isegmi_op_pose2seg_skeleton": [_VP, _I32, _VP, _I32, _I32, _VP],
-    "isegmi_op_pose2seg_masks": [_VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
-    # the Keypoint R-CNN -> Pose2Seg hand-off (csrc/pose_handoff.hip) and the forward in two halves (DESIGN.md 15)
-    "isegmi_op_pose_handoff": [_VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, C.c_float, C.c_float, _I32, _VP, _VP, _VP, _VP, _VP],
-    "isegmi_op_pose_scores": [_VP, _VP, _I32, _I32, _VP, _VP],
-    "isegmi_pose2seg_body": [_VP, _VP, _VP, _I32],
-    "isegmi_pose2seg_persons": [_VP, _VP, _VP, _VP, _VP],
-    "isegmi_pose2seg_wait_persons": [_VP, _VP],
-    "isegmi_engine_pose_handoff": [_VP, _VP, C.c_float, C.c_float, _I32, _VP, _VP, _VP, _VP],
-}
-
-
-def p2s_fn(name):
-    """The Pose2Seg entry point `name` with its argtypes / restype declared: an ABI change raises instead of shifting arguments."""
-    f = getattr(lib(), name)
-    if f.argtypes is None:
-        f.argtypes = _P2S_SIGS[name]
-        f.restype = C.c_int
-    return f
-
-
 def p2s_letterbox(d_u8, d_table, N, S, mean3, std3, swap_rb, round_u8, d_out, stream=None):
     m = (C.c_float * 3)(*[float(v) for v in mean3]); sd = (C.c_float * 3)(*[float(v) for v in std3])
-    check(p2s_fn("isegmi_op_pose2seg_letterbox")(_ptr(d_u8), _ptr(d_table), int(N), int(S), m, sd, int(bool(swap_rb)), int(bool(round_u8)),
-                                                 _ptr(d_out), stream))
-
-
-def p2s_fit(d_kpts, d_roi_img, R, d_m1, d_templates, T, align_corners, d_m3, d_G, d_mmask, d_kalign, d_fit, stream=None):
-    check(p2s_fn("isegmi_op_pose2seg_fit")(_ptr(d_kpts), _ptr(d_roi_img), int(R), _ptr(d_m1), _ptr(d_templates), int(T), int(bool(align_corners)),
-                                           _ptr(d_m3), _ptr(d_G), _ptr(d_mmask), _ptr(d_kalign), _ptr(d_fit), stream))
-
-
-def p2s_align(d_feat, Hf, Wf, Cc, d_roi_img, d_G, R, d_out, out_c, stream=None):
-    check(p2s_fn("isegmi_op_pose2seg_align")(_ptr(d_feat), int(Hf), int(Wf), int(Cc), _ptr(d_roi_img), _ptr(d_G), int(R), _ptr(d_out), int(out_c),
+    check(lib().isegmi_op_pose2seg_letterbox(_ptr(d_u8), _ptr(d_table), int(N), int(S), m, sd, int(bool(swap_rb)), int(bool(round_u8)), _ptr(d_out),
                                              stream))
 
 
+def p2s_fit(d_kpts, d_roi_img, R, d_m1, d_templates, T, align_corners, d_m3, d_G, d_mmask, d_kalign, d_fit, stream=None):
+    check(lib().isegmi_op_pose2seg_fit(_ptr(d_kpts), _ptr(d_roi_img), int(R), _ptr(d_m1), _ptr(d_templates), int(T), int(bool(align_corners)),
+                                       _ptr(d_m3), _ptr(d_G), _ptr(d_mmask), _ptr(d_kalign), _ptr(d_fit), stream))
+
+
+def p2s_align(d_feat, Hf, Wf, Cc, d_roi_img, d_G, R, d_out, out_c, stream=None):
+    check(lib().isegmi_op_pose2seg_align(_ptr(d_feat), int(Hf), int(Wf), int(Cc), _ptr(d_roi_img), _ptr(d_G), int(R), _ptr(d_out), int(out_c), stream))
+
+
 def p2s_skeleton(d_kalign, R, d_out, out_c, c0, stream=None):
-    check(p2s_fn("isegmi_op_pose2seg_skeleton")(_ptr(d_kalign), int(R), _ptr(d_out), int(out_c), int(c0), stream))
+    check(lib().isegmi_op_pose2seg_skeleton(_ptr(d_kalign), int(R), _ptr(d_out), int(out_c), int(c0), stream))
 
 
 def p2s_masks(d_logits, d_mmask, d_counts, d_roi_off, d_image_hw, N, K, Hmax, Wmax, d_ws_box, d_masks, d_boxes, d_scores, d_labels, d_count_out,
               stream=None):
-    check(p2s_fn("isegmi_op_pose2seg_masks")(_ptr(d_logits), _ptr(d_mmask), _ptr(d_counts), _ptr(d_roi_off), _ptr(d_image_hw), int(N), int(K),
-                                             int(Hmax), int(Wmax), _ptr(d_ws_box), _ptr(d_masks), _ptr(d_boxes), _ptr(d_scores), _ptr(d_labels),
-                                             _ptr(d_count_out), stream))
+    check(lib().isegmi_op_pose2seg_masks(_ptr(d_logits), _ptr(d_mmask), _ptr(d_counts), _ptr(d_roi_off), _ptr(d_image_hw), int(N), int(K),
+                                         int(Hmax), int(Wmax), _ptr(d_ws_box), _ptr(d_masks), _ptr(d_boxes), _ptr(d_scores), _ptr(d_labels),
+                                         _ptr(d_count_out), stream))
 
 
 def pose_handoff(score, count, kpt, kscore, ratios_wh, person_thresh, kp_thresh, K, poison=True):
@@ -1076,42 +967,13 @@ def pose_handoff(score, count, kpt, kscore, ratios_wh, person_thresh, kp_thresh,
     if poison:
         for o in outs:
             o.poison()
-    check(p2s_fn("isegmi_op_pose_handoff")(*[b.ptr for b in ins], int(N), int(cap), int(NK), float(person_thresh), float(kp_thresh), int(K),
-                                           *[b.ptr for b in outs], None))
+    check(lib().isegmi_op_pose_handoff(*[b.ptr for b in ins], int(N), int(cap), int(NK), float(person_thresh), float(kp_thresh), int(K),
+                                       *[b.ptr for b in outs], None))
     sync()
     return tuple(o.numpy() for o in outs)
 
 
 # ---------------------------------------------------------------- COCO evaluation on the device (csrc/cocoeval.hip)
-class CocoMatchArgs(C.Structure):
-    """isegmi_coco_match_args."""
-    _fields_ = [("n_groups", C.c_int32), ("A", C.c_int32), ("T", C.c_int32), ("reserved", C.c_int32),
-                ("n_dets", C.c_int64), ("n_gts", C.c_int64), ("n_ious", C.c_int64)] + \
-               [(n, C.c_void_p) for n in ("d_det_off", "d_gt_off", "d_iou_off", "d_ious", "d_det_area", "d_gt_area", "d_gt_crowd", "d_gt_ignore",
-                                          "d_area_rng", "d_iou_thrs", "d_dt_match", "d_dt_ignore", "d_gt_match", "d_gt_ignore_out")]
-
-
-_I64, _PI64 = C.c_int64, C.POINTER(C.c_int64)
-_COCO_SIGS = {
-    "isegmi_coco_rle_prefix_bytes": [_I64, _I32, _PI64, _PI64, _PI64, _PI64],
-    "isegmi_op_rle_prefix": [_VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP],
-    "isegmi_op_rle_iou": [_VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _I64, _VP, _VP],
-    "isegmi_op_bbox_iou": [_VP, _I32, _VP, _I64, _VP, _VP],
-    "isegmi_op_oks": [_VP, _VP, _VP, _VP, _I32, _I32, _VP, _I64, _VP, _VP],
-    "isegmi_coco_match_bytes": [_I64, _I64, _I32, _I32, _PI64, _PI64, _PI64, _PI64],
-    "isegmi_op_coco_match": [C.POINTER(CocoMatchArgs), _VP],
-}
-
-
-def coco_fn(name):
-    """The COCO-evaluation entry point `name` with its argtypes / restype declared: an ABI change raises instead of shifting arguments."""
-    f = getattr(lib(), name)
-    if f.argtypes is None:
-        f.argtypes = _COCO_SIGS[name]
-        f.restype = C.c_int
-    return f
-
-
 class RleSet:
     """M run-length encodings on the device, prefix-summed once (isegmi_op_rle_prefix): the operand of rle_iou.
     counts_list: per RLE its run counts (column-major, zeros first, as isegmi.coco.rle_from_string yields them); hw [M][2] = (h, w).
@@ -1128,7 +990,7 @@ class RleSet:
         if total and (flat.min() < 0 or flat.max() >= 1 << 32):
             raise IsegmiError("RLE run counts must fit uint32")
         sz = [C.c_int64() for _ in range(4)]
-        check(coco_fn("isegmi_coco_rle_prefix_bytes")(total, self.M, *[C.byref(s) for s in sz]))
+        check(lib().isegmi_coco_rle_prefix_bytes(total, self.M, *[C.byref(s) for s in sz]))
         self.d_counts = DeviceBuffer.from_numpy(flat.astype(np.uint32))
         self.d_off = DeviceBuffer.from_numpy(off)
         self.d_hw = DeviceBuffer.from_numpy(hw)
@@ -1146,7 +1008,7 @@ class RleSet:
         self.prefix_seconds = time.perf_counter() - t0      # the prefix kernel alone, uploads excluded (tools/cocoeval_bench.py)
 
     def prefix(self, stream=None):
-        check(coco_fn("isegmi_op_rle_prefix")(self.d_counts.ptr, self.d_off.ptr, self.d_hw.ptr, self.M, self.d_bounds.ptr, self.d_cum.ptr,
+        check(lib().isegmi_op_rle_prefix(self.d_counts.ptr, self.d_off.ptr, self.d_hw.ptr, self.M, self.d_bounds.ptr, self.d_cum.ptr,
                                               self.d_area.ptr, self.d_bbox.ptr, stream))
 
     @property
@@ -1170,7 +1032,7 @@ class RleSet:
 
 def rle_iou_device(rles, d_pairs, P, d_out, stream=None):
     """isegmi_op_rle_iou over device buffers: d_pairs [P][3] int32 (det, gt, crowd) -> d_out [P] float64."""
-    check(coco_fn("isegmi_op_rle_iou")(rles.d_bounds.ptr, rles.d_cum.ptr, rles.d_off.ptr, rles.d_hw.ptr, rles.d_area.ptr, rles.d_bbox.ptr,
+    check(lib().isegmi_op_rle_iou(rles.d_bounds.ptr, rles.d_cum.ptr, rles.d_off.ptr, rles.d_hw.ptr, rles.d_area.ptr, rles.d_bbox.ptr,
                                        rles.M, _ptr(d_pairs), int(P), _ptr(d_out), stream))
 
 
@@ -1186,7 +1048,7 @@ def rle_iou(rles, pairs):
 
 
 def bbox_iou_device(d_boxes, B, d_pairs, P, d_out, stream=None):
-    check(coco_fn("isegmi_op_bbox_iou")(_ptr(d_boxes), int(B), _ptr(d_pairs), int(P), _ptr(d_out), stream))
+    check(lib().isegmi_op_bbox_iou(_ptr(d_boxes), int(B), _ptr(d_pairs), int(P), _ptr(d_out), stream))
 
 
 def bbox_iou(boxes, pairs):
@@ -1204,7 +1066,7 @@ def bbox_iou(boxes, pairs):
 
 def oks_device(d_kpts, d_box, d_area, d_vars, M, K, d_pairs, P, d_out, stream=None):
     """isegmi_op_oks over device buffers: d_kpts [M][K][3], d_box [M][4], d_area [M], d_vars [K] float64; d_pairs [P][3] int32 -> d_out [P] float64."""
-    check(coco_fn("isegmi_op_oks")(_ptr(d_kpts), _ptr(d_box), _ptr(d_area), _ptr(d_vars), int(M), int(K), _ptr(d_pairs), int(P), _ptr(d_out),
+    check(lib().isegmi_op_oks(_ptr(d_kpts), _ptr(d_box), _ptr(d_area), _ptr(d_vars), int(M), int(K), _ptr(d_pairs), int(P), _ptr(d_out),
                                    stream))
 
 
@@ -1247,7 +1109,7 @@ def coco_match(det_off, gt_off, iou_off, ious, det_area, gt_area, gt_crowd, gt_i
         d_ious = up(np.asarray(ious, np.float64).ravel(), np.float64)
     n_ious = d_ious.nbytes // 8
     sz = [C.c_int64() for _ in range(4)]
-    check(coco_fn("isegmi_coco_match_bytes")(n_dets, n_gts, A, T, *[C.byref(s) for s in sz]))
+    check(lib().isegmi_coco_match_bytes(n_dets, n_gts, A, T, *[C.byref(s) for s in sz]))
     o_dtm = DeviceBuffer((A, T, n_dets), np.int32); o_dti = DeviceBuffer((A, T, n_dets), np.uint8)
     o_gtm = DeviceBuffer((A, T, n_gts), np.int32); o_gti = DeviceBuffer((A, n_gts), np.uint8)
     own += [o_dtm, o_dti, o_gtm, o_gti]
@@ -1259,7 +1121,7 @@ def coco_match(det_off, gt_off, iou_off, ious, det_area, gt_area, gt_crowd, gt_i
                       d_ious.ptr, up(det_area, np.float64).ptr, up(gt_area, np.float64).ptr, up(gt_crowd, np.uint8).ptr,
                       up(gt_ignore, np.uint8).ptr, up(area_rng, np.float64).ptr, up(iou_thrs, np.float64).ptr,
                       o_dtm.ptr, o_dti.ptr, o_gtm.ptr, o_gti.ptr)
-    check(coco_fn("isegmi_op_coco_match")(C.byref(a), stream))
+    check(lib().isegmi_op_coco_match(C.byref(a), stream))
     sync()
     out = (o_dtm.numpy(), o_dti.numpy(), o_gtm.numpy(), o_gti.numpy())
     for b in own:

@@ -225,12 +225,12 @@ class RcclGather:
         _ffi.check(L.isegmi_comm_fence_producer(self._c, slot, st))  # WAR: the slot's previous gather has finished
         nb = C.c_int64()
         if getattr(net, "KIND", 1) == 2:
-            _ffi.check(L.isegmi_maskrcnn_pack_records(net._h, send.ptr, C.c_int64(self.nbytes), C.byref(nb)))
+            _ffi.check(L.isegmi_maskrcnn_pack_records(net._h, send.ptr, self.nbytes, C.byref(nb)))
         else:
-            _ffi.check(L.isegmi_yolact_pack_records(net._h, send.ptr, C.c_int64(self.nbytes), int(with_proto), C.byref(nb)))
+            _ffi.check(L.isegmi_yolact_pack_records(net._h, send.ptr, self.nbytes, int(with_proto), C.byref(nb)))
         assert nb.value == self.nbytes, (nb.value, self.nbytes)
         _ffi.check(L.isegmi_engine_stream(net._h, C.byref(st)))
-        _ffi.check(L.isegmi_comm_allgather_slot(self._c, slot, send.ptr, recv.ptr, C.c_int64(self.nbytes), st))
+        _ffi.check(L.isegmi_comm_allgather_slot(self._c, slot, send.ptr, recv.ptr, self.nbytes, st))
         self.slot_bytes[slot] = self.nbytes
         self.log.append(("data", self.nbytes, "results"))
         self.step += 1
@@ -250,11 +250,11 @@ class RcclGather:
             nbv = net.pack_box_records(send, n_block)
         else:
             nb = C.c_int64()
-            _ffi.check(L.isegmi_engine_pack_coco_records(net._h, send.ptr, C.c_int64(self.nbytes), int(n_block), C.byref(nb)))
+            _ffi.check(L.isegmi_engine_pack_coco_records(net._h, send.ptr, self.nbytes, int(n_block), C.byref(nb)))
             nbv = nb.value
         assert nbv == self.nbytes, (nbv, self.nbytes)
         _ffi.check(L.isegmi_engine_stream(net._h, C.byref(st)))
-        _ffi.check(L.isegmi_comm_allgather_slot(self._c, slot, send.ptr, recv.ptr, C.c_int64(self.nbytes), st))
+        _ffi.check(L.isegmi_comm_allgather_slot(self._c, slot, send.ptr, recv.ptr, self.nbytes, st))
         self.slot_bytes[slot] = self.nbytes
         self.log.append(("data", self.nbytes, "results"))
         self.step += 1
@@ -271,7 +271,7 @@ class RcclGather:
         st = C.c_void_p()
         if net is not None:
             _ffi.check(L.isegmi_engine_stream(net._h, C.byref(st)))
-        _ffi.check(L.isegmi_comm_allgather_slot(self._c, slot, self.sends[slot].ptr, self.recvs[slot].ptr, C.c_int64(self.nbytes), st if net is not None else None))
+        _ffi.check(L.isegmi_comm_allgather_slot(self._c, slot, self.sends[slot].ptr, self.recvs[slot].ptr, self.nbytes, st if net is not None else None))
         self.slot_bytes[slot] = self.nbytes
         self.log.append(("empty", self.nbytes, "results" if net is not None else "own"))
         self.step += 1
@@ -292,8 +292,8 @@ class RcclGather:
         assert 0 < a.size <= self.capacity, (a.size, self.capacity)
         self.wait()
         slot = self.step % self.SLOTS
-        _ffi.check(L.isegmi_h2d(self.sends[slot].ptr, a.ctypes.data_as(C.c_void_p), C.c_int64(a.size)))
-        _ffi.check(L.isegmi_comm_allgather_slot(self._c, slot, self.sends[slot].ptr, self.recvs[slot].ptr, C.c_int64(a.size), None))
+        _ffi.check(L.isegmi_h2d(self.sends[slot].ptr, a.ctypes.data_as(C.c_void_p), a.size))
+        _ffi.check(L.isegmi_comm_allgather_slot(self._c, slot, self.sends[slot].ptr, self.recvs[slot].ptr, a.size, None))
         self.slot_bytes[slot] = int(a.size)
         self.log.append(("control", int(a.size), "own"))
         self.step += 1
@@ -322,7 +322,7 @@ class RcclGather:
         _ffi.check(_ffi.lib().isegmi_comm_wait_slot(self._c, slot))
         nb = self.slot_bytes[slot]
         out = np.empty((self.world, nb), np.uint8)
-        _ffi.check(_ffi.lib().isegmi_d2h(out.ctypes.data_as(C.c_void_p), self.recvs[slot].ptr, C.c_int64(self.world * nb)))
+        _ffi.check(_ffi.lib().isegmi_d2h(out.ctypes.data_as(C.c_void_p), self.recvs[slot].ptr, self.world * nb))
         return out
 
     def close(self):

@@ -11,6 +11,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _ffi
+from .engine import Engine
 from .weights import fold_frozen_batchnorm, to_krsc
 
 PIXEL_MEAN = (102.9801, 115.9465, 122.7717)  # BGR, TO_BGR255
@@ -296,7 +297,7 @@ def padded_canvas(image_hw, divisibility=32):
     return (int(-(-hw[:, 0].max() // divisibility) * divisibility), int(-(-hw[:, 1].max() // divisibility) * divisibility))
 
 
-class MaskRCNN:
+class MaskRCNN(Engine):
     """GeneralizedRCNN engine wrapper: `model = MaskRCNN(sd, H, W)`; `preds = model(batch, image_hw)`.
 
     (H, W) is the LARGEST padded canvas the engine serves.  Every batch runs on its own canvas (to_image_list pads a batch to the maximum
@@ -331,10 +332,7 @@ class MaskRCNN:
         self.keypoint_on = bool(cfg.KEYPOINT_ON)   # MODEL.KEYPOINT_ON: __call__ adds keypoints / keypoint_logits, results leave through pack_keypoint_records
         self._ratios = None
         self.mask_buf = "det.mask14" if cfg.is_c4 else "det.mask28"
-        _ffi.lib()
-        _ffi.set_device(device)
-        self._h = C.c_void_p()
-        _ffi.check(_ffi.lib().isegmi_engine_create(self.KIND, max_batch, H, W, C.byref(self._h)))
+        self._create(device, max_batch, H, W)
         self.fp16 = bool(fp16)
         if self.fp16:  # fp16 storage + f16 MFMA convs (BASELINE configs[4]); must precede weight loading
             self.set_param("fp16", 1.0)
@@ -447,18 +445,6 @@ class MaskRCNN:
         self._set_tensor("mask_logits.w", w.reshape(ncls, 256).astype(np.float32))
         self._set_tensor("mask_logits.b", sd["roi_heads.mask.predictor.mask_fcn_logits.bias"].astype(np.float32))
 
-
-    def set_param(self, name, value):
-        _ffi.check(_ffi.lib().isegmi_engine_set_param(self._h, name.encode(), C.c_float(value)))
-
-    def _set_conv_krsc(self, name, w, scale=None, shift=None):
-        w = np.ascontiguousarray(w, np.float32)
-        cout, r, s, cin = w.shape
-        fp = lambda a: None if a is None else np.ascontiguousarray(a, np.float32).ctypes.data_as(C.c_void_p)
-        sc = None if scale is None else np.ascontiguousarray(scale, np.float32)
-        sh = None if shift is None else np.ascontiguousarray(shift, np.float32)
-        _ffi.check(_ffi.lib().isegmi_engine_set_conv(self._h, name.encode(), cout, r, s, cin, fp(w), fp(sc), fp(sh)))
-
     def _set_conv2(self, sd, src, dst, stage):
         """conv2 of bottleneck `src` (stage 0..3): checked against MODEL.RESNETS.NUM_GROUPS / WIDTH_PER_GROUP -- weight [width, width / groups, 3, 3] with
         width = groups * width_per_group * 2^stage; ValueError naming the key otherwise -- and uploaded dense (groups 1) or grouped."""
@@ -476,14 +462,7 @@ class MaskRCNN:
         scale, shift = fold_frozen_batchnorm(sd, src + ".bn2", cfg.FROZEN_BN_EPS)
         if groups == 1:
             return self._set_conv_krsc(dst + ".conv2", to_krsc(w), scale, shift)
-        wk = to_krsc(w)   # [width, 3, 3, width / groups]
-        fp = lambda a: np.ascontiguousarray(a, np.float32).ctypes.data_as(C.c_void_p)
-        wk, scale, shift = (np.ascontiguousarray(a, np.float32) for a in (wk, scale, shift))
-        _ffi.check(_ffi.lib().isegmi_engine_set_conv_grouped(self._h, (dst + ".conv2").encode(), width, groups, fp(wk), fp(scale), fp(shift)))
-
-    def _set_tensor(self, name, a):
-        a = np.ascontiguousarray(a)
-        _ffi.check(_ffi.lib().isegmi_engine_set_tensor(self._h, name.encode(), a.ctypes.data_as(C.c_void_p), C.c_int64(a.nbytes)))
+        self._set_conv_grouped(dst + ".conv2", to_krsc(w), groups, scale, shift)   # [width, 3, 3, width / groups]
 
     def _load(self, sd):
         cfg = self.cfg
@@ -648,7 +627,7 @@ class MaskRCNN:
         x = np.ascontiguousarray(batch_nhwc3, np.float32)
         assert x.ndim == 4 and x.shape[3] == 3 and x.shape[0] <= self.max_batch, x.shape
         self._set_canvas(x.shape[1], x.shape[2])
-        _ffi.check(_ffi.lib().isegmi_h2d(self.input_buffer(slot).ptr, x.ctypes.data_as(C.c_void_p), C.c_int64(x.nbytes)))
+        _ffi.check(_ffi.lib().isegmi_h2d(self.input_buffer(slot).ptr, x.ctypes.data_as(C.c_void_p), x.nbytes))
         self._hw = np.ascontiguousarray(image_hw, np.int32).reshape(-1, 2)
         assert self._hw.shape[0] == x.shape[0]
         return x.shape[0]
@@ -665,7 +644,7 @@ class MaskRCNN:
         self._set_canvas(*(canvas or padded_canvas(hw, self.cfg.SIZE_DIVISIBILITY)))
         flat = np.concatenate([im.reshape(-1) for im in ims])
         st = self._u8_staging(slot, flat.nbytes)
-        _ffi.check(_ffi.lib().isegmi_h2d(st.ptr, flat.ctypes.data_as(C.c_void_p), C.c_int64(flat.nbytes)))
+        _ffi.check(_ffi.lib().isegmi_h2d(st.ptr, flat.ctypes.data_as(C.c_void_p), flat.nbytes))
         self._front_end(st, hw, slot)
         return len(ims)
 
@@ -693,7 +672,7 @@ class MaskRCNN:
         assert pinned_u8.nbytes >= nbytes and hw.shape[0] <= self.max_batch
         self._set_canvas(*(canvas or padded_canvas(hw, self.cfg.SIZE_DIVISIBILITY)))
         st = self._u8_staging(slot, nbytes)
-        _ffi.check(_ffi.lib().isegmi_engine_upload_async(self._h, st.ptr, pinned_u8.ptr, C.c_int64(nbytes)))
+        _ffi.check(_ffi.lib().isegmi_engine_upload_async(self._h, st.ptr, pinned_u8.ptr, nbytes))
         self._front_end(st, hw, slot)
 
     def forward_device(self, n, slot=0):
@@ -718,7 +697,7 @@ class MaskRCNN:
     def rle_device(self, image_hw=None):
         if self.box_only:
             raise RuntimeError("rle_device: the engine is box-only (MODEL.MASK_ON False): there are no masks to encode")
-        return _Y.rle_device(self, image_hw)
+        return super().rle_device(image_hw)
 
     def set_output_sizes(self, orig_sizes_wh=None):
         """Box-only results stage: the (w, h) the boxes of the last upload are resized to by pack_box_records (default: no resize)."""
@@ -730,7 +709,7 @@ class MaskRCNN:
         n = self._hw.shape[0]
         r = self._ratios if self._ratios is not None and self._ratios.shape[0] == n else np.ones((n, 2), np.float32)
         nb = C.c_int64()
-        _ffi.check(_ffi.lib().isegmi_engine_pack_box_records(self._h, r.ctypes.data_as(C.c_void_p), dev_buffer.ptr, C.c_int64(dev_buffer.nbytes), int(n_block), C.byref(nb)))
+        _ffi.check(_ffi.lib().isegmi_engine_pack_box_records(self._h, r.ctypes.data_as(C.c_void_p), dev_buffer.ptr, dev_buffer.nbytes, int(n_block), C.byref(nb)))
         return nb.value
 
     def pack_keypoint_records(self, dev_buffer, n_block):
@@ -739,7 +718,7 @@ class MaskRCNN:
         n = self._hw.shape[0]
         r = self._ratios if self._ratios is not None and self._ratios.shape[0] == n else np.ones((n, 2), np.float32)
         nb = C.c_int64()
-        _ffi.check(_ffi.lib().isegmi_engine_pack_keypoint_records(self._h, r.ctypes.data_as(C.c_void_p), dev_buffer.ptr, C.c_int64(dev_buffer.nbytes), int(n_block), C.byref(nb)))
+        _ffi.check(_ffi.lib().isegmi_engine_pack_keypoint_records(self._h, r.ctypes.data_as(C.c_void_p), dev_buffer.ptr, dev_buffer.nbytes, int(n_block), C.byref(nb)))
         return nb.value
 
     def pose_handoff(self, person_threshold, keypoint_threshold, K, d_kpts, d_score, d_slot, d_count):
@@ -747,21 +726,13 @@ class MaskRCNN:
         named, into four device buffers ([n * K, 17, 3] f32, [n, K] f32, [n, K] i32, [n] i32) on the results stream.  -> the ratios used."""
         n = self._hw.shape[0] if self._hw is not None else self.max_batch   # before the first upload the engine refuses by name
         r = self._ratios if self._ratios is not None and self._ratios.shape[0] == n else np.ones((n, 2), np.float32)
-        _ffi.check(_ffi.p2s_fn("isegmi_engine_pose_handoff")(self._h, r.ctypes.data_as(C.c_void_p), float(person_threshold), float(keypoint_threshold), int(K),
+        _ffi.check(_ffi.lib().isegmi_engine_pose_handoff(self._h, r.ctypes.data_as(C.c_void_p), float(person_threshold), float(keypoint_threshold), int(K),
                                                              d_kpts.ptr, d_score.ptr, d_slot.ptr, d_count.ptr))
         return r
 
     def results_stream(self):
         """the stream the last forward's results (and everything packed or handed off from them) complete on"""
-        st = C.c_void_p()
-        _ffi.check(_ffi.lib().isegmi_engine_stream(self._h, C.byref(st)))
-        return st
-
-    def sync(self):
-        _ffi.check(_ffi.lib().isegmi_engine_sync(self._h))
-
-    fetch = None  # bound below (shared with Yolact)
-    timings = None
+        return self.stream()
 
     def __call__(self, batch_nhwc3, image_hw=None):
         """-> list of BoxList (one per image, in network-input coordinates) with scores, labels, mask [n,1,28,28]
@@ -785,28 +756,3 @@ class MaskRCNN:
                 bl.add_field("keypoints", kpt[i, :c]); bl.add_field("keypoint_logits", kscore[i, :c])
             out.append(bl)
         return out
-
-    def close(self):
-        if self._h:
-            _ffi.lib().isegmi_engine_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-from .yolact import Yolact as _Y  # noqa: E402
-
-MaskRCNN.fetch = _Y.fetch
-MaskRCNN.timings = _Y.timings
-MaskRCNN.input_buffer = _Y.input_buffer
-MaskRCNN.upload_async = _Y.upload_async
-MaskRCNN.mark_step = _Y.mark_step
-MaskRCNN._u8_staging = _Y._u8_staging
-MaskRCNN._preprocess_u8 = _Y._preprocess_u8
-MaskRCNN.step_times = _Y.step_times
-for _n in ("wait_mark", "coco_record_bytes", "pack_coco_records", "download_async", "download_fence", "download_wait", "memory"):
-    setattr(MaskRCNN, _n, getattr(_Y, _n))

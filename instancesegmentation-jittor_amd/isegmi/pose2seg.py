@@ -23,6 +23,7 @@ from dataclasses import dataclass, replace
 import numpy as np
 
 from . import _ffi
+from .engine import Engine
 from .weights import fold_batchnorm, to_krsc
 
 S_IN, S_FEAT, S_ALIGN = 512, 128, 64
@@ -108,7 +109,7 @@ def engine_layers(sd, cfg):
     return out
 
 
-class Pose2Seg:
+class Pose2Seg(Engine):
     """Pose2Seg(state_dict, cfg, max_batch, max_instances, device): upstream's `model([img], [kpts], [masks])` call shape on an engine of
     model_kind 3 (isegmi_pose2seg_forward).  Images are uint8 [h, w, 3] in the caller's channel order (upstream: cv2.imread BGR); keypoints
     (n, 17, 3) COCO (x, y, v).  Images and keypoints go up through pinned memory on the engine's copy stream (two slots)."""
@@ -134,65 +135,17 @@ class Pose2Seg:
         if templates.ndim != 3 or templates.shape[1:] != (17, 3) or not 1 <= templates.shape[0] <= 64:
             raise ValueError("pose_templates must be [T][17][3] with 1 <= T <= 64, got %s" % (templates.shape,))
         layers = engine_layers(state_dict, cfg)
-        _ffi.set_device(device)
-        self._h = C.c_void_p()
-        _ffi.check(_ffi.lib().isegmi_engine_create(self.KIND, self.max_batch, S_IN, S_IN, C.byref(self._h)))
+        self._create(device, self.max_batch, S_IN, S_IN)
         for k, v in (("max_instances", cfg.max_instances), ("cat_skeleton", cfg.cat_skeleton), ("align_corners", cfg.align_corners),
                      ("warp_round_u8", cfg.warp_round_u8), ("swap_rb", cfg.swap_rb), ("fpn_bilinear", cfg.fpn_upsample == "bilinear")):
             self.set_param(k, float(v))
-        fp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
         for name, w, sc, sh in layers:
-            cout, r, s, cin = w.shape
-            sc = None if sc is None else np.ascontiguousarray(sc, np.float32)
-            sh = None if sh is None else np.ascontiguousarray(sh, np.float32)
-            _ffi.check(_ffi.lib().isegmi_engine_set_conv(self._h, name.encode(), cout, r, s, cin, fp(w), fp(sc), fp(sh)))
-        _ffi.check(_ffi.lib().isegmi_engine_set_tensor(self._h, b"pose_templates", templates.ctypes.data_as(C.c_void_p), C.c_int64(templates.nbytes)))
+            self._set_conv_krsc(name, w, sc, sh)
+        self._set_tensor("pose_templates", templates)
         self._pin = [[None, None], [None, None]]   # [slot][images, keypoints]
         self._dev = [[None, None], [None, None]]
         self._slot = 0
         self.last = {}
-
-    # -- engine plumbing shared with the other models' wrappers (isegmi.pipeline drives these) ------------------------------------------
-    def set_param(self, name, value):
-        _ffi.check(_ffi.lib().isegmi_engine_set_param(self._h, name.encode(), C.c_float(value)))
-
-    def sync(self):
-        _ffi.check(_ffi.lib().isegmi_engine_sync(self._h))
-
-    def rle_device(self, image_hw=None):
-        hw = None if image_hw is None else np.ascontiguousarray(image_hw, np.int32).reshape(-1, 2)
-        _ffi.check(_ffi.lib().isegmi_engine_rle(self._h, None if hw is None else hw.ctypes.data_as(C.c_void_p)))
-
-    def coco_record_bytes(self, n):
-        nb, co = C.c_int64(), C.c_int64()
-        _ffi.check(_ffi.lib().isegmi_engine_coco_record_bytes(self._h, n, C.byref(nb), C.byref(co)))
-        return nb.value, co.value
-
-    def pack_coco_records(self, dev_buffer, n_block):
-        nb = C.c_int64()
-        _ffi.check(_ffi.lib().isegmi_engine_pack_coco_records(self._h, dev_buffer.ptr, C.c_int64(dev_buffer.nbytes), int(n_block), C.byref(nb)))
-        return nb.value
-
-    def download_async(self, slot, pinned, dev_buffer, nbytes):
-        _ffi.check(_ffi.lib().isegmi_engine_download_async(self._h, slot, pinned.ptr, dev_buffer.ptr, C.c_int64(nbytes)))
-
-    def download_fence(self, slot):
-        _ffi.check(_ffi.lib().isegmi_engine_download_fence(self._h, slot))
-
-    def download_wait(self, slot):
-        _ffi.check(_ffi.lib().isegmi_engine_download_wait(self._h, slot))
-
-    def conv_stats(self):
-        """(flops, ms, launches) of the conv launches since the last call (needs set_param("conv_timing", 1))."""
-        f, ms, n = C.c_double(), C.c_double(), C.c_int64()
-        _ffi.check(_ffi.lib().isegmi_engine_conv_stats(self._h, C.byref(f), C.byref(ms), C.byref(n)))
-        return f.value, ms.value, n.value
-
-    def _buffer(self, name):
-        p, nb, dt, nd = C.c_void_p(), C.c_int64(), C.c_int32(), C.c_int32()
-        shp = (C.c_int64 * 4)()
-        _ffi.check(_ffi.lib().isegmi_engine_buffer_info(self._h, name.encode(), C.byref(p), C.byref(nb), C.byref(dt), shp, C.byref(nd)))
-        return p, nb.value
 
     def _staging(self, slot, which, nbytes):
         """pinned source + device destination of slot `slot` (which: 0 images, 1 keypoints), grown on demand"""
@@ -226,7 +179,7 @@ class Pose2Seg:
             a = np.ascontiguousarray(im).reshape(-1)
             pin.array[off:off + a.size] = a
             off += a.size
-        _ffi.check(_ffi.lib().isegmi_engine_upload_async(self._h, dev.ptr, pin.ptr, C.c_int64(nbytes)))
+        _ffi.check(_ffi.lib().isegmi_engine_upload_async(self._h, dev.ptr, pin.ptr, nbytes))
         return dev
 
     def body(self, images, slot=None):
@@ -239,7 +192,7 @@ class Pose2Seg:
         self._slot = 1 - slot
         dev = self._upload_images(images, hw, slot)
         hwa = np.ascontiguousarray(hw, np.int32)
-        _ffi.check(_ffi.p2s_fn("isegmi_pose2seg_body")(self._h, dev.ptr, hwa.ctypes.data_as(C.c_void_p), N))
+        _ffi.check(_ffi.lib().isegmi_pose2seg_body(self._h, dev.ptr, hwa.ctypes.data_as(C.c_void_p), N))
         self._body = dict(N=N, K=self.max_instances, hw=[tuple(x) for x in hw], Hmax=int(hwa[:, 0].max()), Wmax=int(hwa[:, 1].max()))
         return self._body
 
@@ -254,7 +207,7 @@ class Pose2Seg:
             raise ValueError("one person count per image of the body's batch (%d), got %d" % (L["N"], counts.shape[0]))
         ptr = lambda b: None if b is None else getattr(b, "ptr", b)
         self._body = None
-        _ffi.check(_ffi.p2s_fn("isegmi_pose2seg_persons")(self._h, ptr(d_kpts), ptr(d_scores), counts.ctypes.data_as(C.c_void_p), producer_stream))
+        _ffi.check(_ffi.lib().isegmi_pose2seg_persons(self._h, ptr(d_kpts), ptr(d_scores), counts.ctypes.data_as(C.c_void_p), producer_stream))
         self.last = dict(L, R=int(counts.sum()), counts=counts)
         return self.last
 
@@ -286,7 +239,7 @@ class Pose2Seg:
             kall = np.ascontiguousarray(np.concatenate(kps), np.float32).view(np.uint8).reshape(-1)
             kpin, dk = self._staging(slot, 1, kall.size)
             kpin.array[:kall.size] = kall
-            _ffi.check(_ffi.lib().isegmi_engine_upload_async(self._h, dk.ptr, kpin.ptr, C.c_int64(kall.size)))
+            _ffi.check(_ffi.lib().isegmi_engine_upload_async(self._h, dk.ptr, kpin.ptr, kall.size))
         hwa = np.ascontiguousarray(hw, np.int32)
         _ffi.check(_ffi.lib().isegmi_pose2seg_forward(self._h, dev.ptr, hwa.ctypes.data_as(C.c_void_p), None if dk is None else dk.ptr,
                                                       counts.ctypes.data_as(C.c_void_p), N))
@@ -299,12 +252,12 @@ class Pose2Seg:
         if name in ("roi", "logits", "fit") and not self.last.get("R"):
             raise ValueError("the last batch had no person: there is no %s" % name)
         self.sync()
-        p, nb = self._buffer(self._NAMES.get(name, name))
+        p, nb = self._buffer_info(self._NAMES.get(name, name))[:2]
         out = np.empty(shape, dtype)
         if out.nbytes > nb:
             raise ValueError("%s holds %d bytes, %d asked" % (name, nb, out.nbytes))
         if out.nbytes:
-            _ffi.check(_ffi.lib().isegmi_d2h(out.ctypes.data_as(C.c_void_p), p, C.c_int64(out.nbytes)))
+            _ffi.check(_ffi.lib().isegmi_d2h(out.ctypes.data_as(C.c_void_p), p, out.nbytes))
         return out
 
     def collect(self):
@@ -326,20 +279,12 @@ class Pose2Seg:
         return self.collect()[0]
 
     def close(self):
-        if getattr(self, "_h", None):
-            _ffi.lib().isegmi_engine_destroy(self._h)
-            self._h = None
+        super().close()
         for row in getattr(self, "_pin", []) + getattr(self, "_dev", []):
             for b in row:
                 if b is not None:
                     b.free()
         self._pin, self._dev = [], []
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def test(net, images, keypoints, image_ids, batch_size=None, rank=0, world=1):
@@ -439,7 +384,7 @@ class KeypointPose2Seg:
         self._slot = 1 - slot
         o = self._out[slot]
         # this slot's last step (the one before last) is through: its hand-off buffers and both engines' pinned image buffers may be written again
-        _ffi.check(_ffi.p2s_fn("isegmi_pose2seg_wait_persons")(net._h, o["kpts"].ptr))
+        _ffi.check(_ffi.lib().isegmi_pose2seg_wait_persons(net._h, o["kpts"].ptr))
         resized = [maskrcnn_resize_u8(np.asarray(im), self.min_image_size, self.max_image_size) for im in images_bgr_u8]
         nbytes = sum(r.size for r in resized)
         if o["u8"] is None or o["u8"].nbytes < nbytes:

@@ -85,10 +85,7 @@ class RetinaNet(MaskRCNN):
         self.cfg, self.H, self.W, self.max_batch = cfg, H, W, max_batch
         self.fp16 = False
         self.mask_buf = None
-        _ffi.lib()
-        _ffi.set_device(device)
-        self._h = C.c_void_p()
-        _ffi.check(_ffi.lib().isegmi_engine_create(self.KIND, max_batch, H, W, C.byref(self._h)))
+        self._create(device, max_batch, H, W)
         self._load(state_dict)
         for k, v in (("resnet_depth", cfg.depth), ("stride_in_1x1", float(bool(cfg.STRIDE_IN_1X1))), ("retina_pre_nms_top_n", cfg.PRE_NMS_TOP_N),
                      ("retina_inference_th", cfg.INFERENCE_TH), ("retina_nms_th", cfg.NMS_TH), ("retina_num_convs", cfg.NUM_CONVS),
@@ -160,11 +157,6 @@ class RetinaNet(MaskRCNN):
         K = self.cfg.det_cap
         return sum(n * (b if name == "det.count" else b * K) for name, b, _ in self._DET)
 
-    def _buffer_ptr(self, name):
-        p = C.c_void_p(); nb = C.c_int64(); dt = C.c_int32(); nd = C.c_int32(); shp = (C.c_int64 * 4)()
-        _ffi.check(_ffi.lib().isegmi_engine_buffer_info(self._h, name.encode(), C.byref(p), C.byref(nb), C.byref(dt), shp, C.byref(nd)))
-        return p.value
-
     def download_detections_async(self, slot, pinned, n):
         """Enqueue the copies of the last forward's detection buffers (first n images) into `pinned` behind it; download_wait(slot) then waits for them."""
         K = self.cfg.det_cap
@@ -172,7 +164,7 @@ class RetinaNet(MaskRCNN):
         off = 0
         for name, b, _ in self._DET:
             nbytes = n * (b if name == "det.count" else b * K)
-            _ffi.check(_ffi.lib().isegmi_engine_download_async(self._h, slot, C.c_void_p(pinned.ptr.value + off), C.c_void_p(self._buffer_ptr(name)), C.c_int64(nbytes)))
+            _ffi.check(_ffi.lib().isegmi_engine_download_async(self._h, slot, C.c_void_p(pinned.ptr.value + off), self._buffer_info(name)[0], nbytes))
             off += nbytes
 
     def unpack_detections(self, pinned, n):

@@ -13,6 +13,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _ffi
+from .engine import Engine
 from .weights import dcn_blocks, fold_batchnorm, to_krsc
 
 MEANS = (103.94, 116.78, 123.68)  # BGR
@@ -123,7 +124,7 @@ def _level_sizes(size):
     return [c3, c4, c5, p6, p7]
 
 
-class Yolact:
+class Yolact(Engine):
     """`net = Yolact(state_dict); preds = net(batch)`; `postprocess(preds, w, h, score_threshold)`."""
 
     KIND = 1
@@ -137,10 +138,7 @@ class Yolact:
         self.size = int(input_size or cfg.max_size)
         self.max_batch = max_batch
         self.fuse_heads = bool(fuse_heads)
-        L = _ffi.lib()
-        _ffi.set_device(device)
-        self._h = C.c_void_p()
-        _ffi.check(L.isegmi_engine_create(self.KIND, max_batch, self.size, self.size, C.byref(self._h)))
+        self._create(device, max_batch, self.size, self.size)
         self.set_param("resnet_depth", float(cfg.depth))
         self.set_param("num_priors", float(cfg.num_priors))
         self.set_param("darknet", 1.0 if cfg.backbone == "darknet53" else 0.0)
@@ -160,11 +158,7 @@ class Yolact:
         w = to_krsc(w_oihw)
         if pad_cin_to and w.shape[3] < pad_cin_to:
             w = np.concatenate([w, np.zeros(w.shape[:3] + (pad_cin_to - w.shape[3],), np.float32)], -1)
-        cout, r, s, cin = w.shape
-        fp = lambda a: None if a is None else np.ascontiguousarray(a, np.float32).ctypes.data_as(C.c_void_p)
-        sc = None if scale is None else np.ascontiguousarray(scale, np.float32)
-        sh = None if shift is None else np.ascontiguousarray(shift, np.float32)
-        _ffi.check(_ffi.lib().isegmi_engine_set_conv(self._h, name.encode(), cout, r, s, cin, fp(w), fp(sc), fp(sh)))
+        self._set_conv_krsc(name, w, scale, shift)
 
     def _load(self, sd):
         dcn = dcn_blocks(self.cfg.depth, self.cfg.dcn_layers, self.cfg.dcn_interval)
@@ -235,52 +229,12 @@ class Yolact:
         self.priors = np.concatenate(pri, 0)
         self._set_tensor("priors", self.priors)
 
-    def _set_tensor(self, name, a):
-        a = np.ascontiguousarray(a)
-        _ffi.check(_ffi.lib().isegmi_engine_set_tensor(self._h, name.encode(), a.ctypes.data_as(C.c_void_p), C.c_int64(a.nbytes)))
-
-    def set_param(self, name, value):
-        _ffi.check(_ffi.lib().isegmi_engine_set_param(self._h, name.encode(), C.c_float(value)))
-
     # -- execution -----------------------------------------------------------------------------
     def upload(self, batch_nhwc3):
         x = np.ascontiguousarray(batch_nhwc3, np.float32)
         assert x.ndim == 4 and x.shape[1:] == (self.size, self.size, 3) and x.shape[0] <= self.max_batch, x.shape
-        _ffi.check(_ffi.lib().isegmi_h2d(self._d_in.ptr, x.ctypes.data_as(C.c_void_p), C.c_int64(x.nbytes)))
+        _ffi.check(_ffi.lib().isegmi_h2d(self._d_in.ptr, x.ctypes.data_as(C.c_void_p), x.nbytes))
         return x.shape[0]
-
-
-    def input_buffer(self, slot=0):
-        """Device input buffer `slot` (0 or 1; the second one is allocated on first use, for double-buffered uploads)."""
-        if slot == 0:
-            return self._d_in
-        if getattr(self, "_d_in2", None) is None:
-            self._d_in2 = _ffi.DeviceBuffer(self._d_in.shape)
-        return self._d_in2
-
-    def upload_async(self, pinned, slot=0):
-        """Asynchronous H2D of a whole batch from a _ffi.PinnedBuffer into input buffer `slot` on the engine's copy stream; the
-        next forward is ordered behind it and it is ordered behind the previous forward's read of its input."""
-        d = self.input_buffer(slot)
-        assert pinned.nbytes <= d.nbytes
-        _ffi.check(_ffi.lib().isegmi_engine_upload_async(self._h, d.ptr, pinned.ptr, C.c_int64(pinned.nbytes)))
-
-    # -- device front end: bytes go over PCIe, the transform runs on the engine's stream ------------------------------------
-    def _u8_staging(self, slot, nbytes):
-        st = getattr(self, "_u8", None)
-        if st is None:
-            st = self._u8 = [None, None]
-        if st[slot] is None or st[slot].nbytes < nbytes:
-            if st[slot] is not None:
-                self.sync()  # a queued transform may still read the old buffer
-                st[slot].free()
-            st[slot] = _ffi.DeviceBuffer((int(nbytes),), np.uint8)
-        return st[slot]
-
-    def _preprocess_u8(self, d_u8_ptr, n, hin, win, d_out_ptr, hout, wout, hpad, wpad, mean, std, swap_rb):
-        m = (C.c_float * 3)(*[float(v) for v in mean]); sd = (C.c_float * 3)(*[float(v) for v in std])
-        _ffi.check(_ffi.lib().isegmi_engine_preprocess_u8(self._h, C.c_void_p(d_u8_ptr), n, hin, win, C.c_void_p(d_out_ptr), hout, wout, hpad, wpad,
-                                                          C.c_int64(hpad * wpad * 3), m, sd, 1 if swap_rb else 0))
 
     def _u8_norm(self):
         darknet = self.cfg.backbone == "darknet53"
@@ -294,7 +248,7 @@ class Yolact:
         ims = self._as_u8_list(images_bgr_u8)
         flat = ims[0].reshape(-1) if len(ims) == 1 else np.concatenate([im.reshape(-1) for im in ims])
         st = self._u8_staging(slot, flat.nbytes)
-        _ffi.check(_ffi.lib().isegmi_h2d(st.ptr, flat.ctypes.data_as(C.c_void_p), C.c_int64(flat.nbytes)))
+        _ffi.check(_ffi.lib().isegmi_h2d(st.ptr, flat.ctypes.data_as(C.c_void_p), flat.nbytes))
         self._front_end(st, [im.shape[:2] for im in ims], slot)
         return len(ims)
 
@@ -329,21 +283,8 @@ class Yolact:
         nbytes = sum(a * b * 3 for a, b in sizes)
         assert pinned_u8.nbytes >= nbytes and len(sizes) <= self.max_batch
         st = self._u8_staging(slot, nbytes)
-        _ffi.check(_ffi.lib().isegmi_engine_upload_async(self._h, st.ptr, pinned_u8.ptr, C.c_int64(nbytes)))
+        _ffi.check(_ffi.lib().isegmi_engine_upload_async(self._h, st.ptr, pinned_u8.ptr, nbytes))
         self._front_end(st, sizes, slot)
-
-    def mark_step(self):
-        _ffi.check(_ffi.lib().isegmi_engine_mark_step(self._h))
-
-    def wait_mark(self, back=0):
-        """host wait for the completion mark `back` marks before the newest one: bounds the steps a producer loop keeps in flight"""
-        _ffi.check(_ffi.lib().isegmi_engine_wait_mark(self._h, int(back)))
-
-    def step_times(self, cap=65536):
-        """Intervals (ms) between consecutive mark_step() completion marks; clears the marks."""
-        ms = (C.c_float * cap)(); cnt = C.c_int()
-        _ffi.check(_ffi.lib().isegmi_engine_step_times(self._h, ms, cap, C.byref(cnt)))
-        return [float(ms[i]) for i in range(cnt.value)]
 
     def forward_device(self, n, slot=0):
         """Launch forward on the batch already resident in the engine's input buffer (asynchronous)."""
@@ -358,62 +299,6 @@ class Yolact:
         """postprocess with image n assembled at ITS (h, w) = image_hw[n] inside a common plane of the batch's maximum size."""
         hw = np.ascontiguousarray(image_hw, np.int32).reshape(-1, 2)
         _ffi.check(_ffi.lib().isegmi_yolact_postprocess_sizes(self._h, hw.ctypes.data_as(C.c_void_p), hw.shape[0]))
-
-    def sync(self):
-        _ffi.check(_ffi.lib().isegmi_engine_sync(self._h))
-
-    # -- device-side COCO output (shared with MaskRCNN): RLE of the masks, one fixed-size record block per batch ---------------------
-    def rle_device(self, image_hw=None):
-        """pycocotools RLE (counts + compressed strings) of det.masks of the last postprocess / paste, on the results stream; image_hw
-        [n, 2] = every image's own (h, w) inside the mask planes (None: the whole plane)."""
-        hw = None if image_hw is None else np.ascontiguousarray(image_hw, np.int32).reshape(-1, 2)
-        _ffi.check(_ffi.lib().isegmi_engine_rle(self._h, None if hw is None else hw.ctypes.data_as(C.c_void_p)))
-
-    def coco_record_bytes(self, n):
-        """(total bytes, offset of the strings) of the record block of a batch of n images (isegmi_engine_pack_coco_records)."""
-        nb, co = C.c_int64(), C.c_int64()
-        _ffi.check(_ffi.lib().isegmi_engine_coco_record_bytes(self._h, n, C.byref(nb), C.byref(co)))
-        return nb.value, co.value
-
-    def pack_coco_records(self, dev_buffer, n_block):
-        nb = C.c_int64()
-        _ffi.check(_ffi.lib().isegmi_engine_pack_coco_records(self._h, dev_buffer.ptr, C.c_int64(dev_buffer.nbytes), int(n_block), C.byref(nb)))
-        return nb.value
-
-    def download_async(self, slot, pinned, dev_buffer, nbytes):
-        _ffi.check(_ffi.lib().isegmi_engine_download_async(self._h, slot, pinned.ptr, dev_buffer.ptr, C.c_int64(nbytes)))
-
-    def download_fence(self, slot):
-        _ffi.check(_ffi.lib().isegmi_engine_download_fence(self._h, slot))
-
-    def download_wait(self, slot):
-        _ffi.check(_ffi.lib().isegmi_engine_download_wait(self._h, slot))
-
-    def memory(self):
-        """(weight_bytes, buffer_bytes) of device memory held by the engine (+ the input slots owned by this wrapper)."""
-        wb, bb = C.c_int64(), C.c_int64()
-        _ffi.check(_ffi.lib().isegmi_engine_memory(self._h, C.byref(wb), C.byref(bb)))
-        extra = self._d_in.nbytes + (self._d_in2.nbytes if getattr(self, "_d_in2", None) is not None else 0)
-        return wb.value, bb.value + extra
-
-    def fetch(self, name, rows=None):
-        """D2H copy of a named engine buffer (optionally only its first `rows` leading rows)."""
-        p = C.c_void_p(); nb = C.c_int64(); dt = C.c_int32(); nd = C.c_int32(); shp = (C.c_int64 * 4)()
-        _ffi.check(_ffi.lib().isegmi_engine_buffer_info(self._h, name.encode(), C.byref(p), C.byref(nb), C.byref(dt), shp, C.byref(nd)))
-        dtype = [np.float32, np.int32, np.uint8, np.int64, np.float16][dt.value]
-        shape = tuple(int(shp[i]) for i in range(nd.value))
-        if rows is not None:
-            shape = (rows,) + shape[1:]
-        out = np.empty(shape, dtype)
-        if out.nbytes:
-            _ffi.check(_ffi.lib().isegmi_d2h(out.ctypes.data_as(C.c_void_p), p, C.c_int64(out.nbytes)))
-        return out
-
-    def timings(self):
-        names = C.create_string_buffer(4096); ms = (C.c_float * 64)(); cnt = C.c_int()
-        _ffi.check(_ffi.lib().isegmi_engine_get_timings(self._h, names, 4096, ms, 64, C.byref(cnt)))
-        ns = names.value.decode().split(";") if cnt.value else []
-        return [(ns[i], float(ms[i])) for i in range(cnt.value)]
 
     def __call__(self, batch_nhwc3):
         """Upstream-shaped result: list (one per image) of {'detection': {...}|None, 'net': self}.  A uint8 [N, H, W, 3] batch is taken as
@@ -433,17 +318,6 @@ class Yolact:
                                            prior=prior[i, :c], **{"class": cls[i, :c]})
             out.append({"detection": det, "net": self, "_index": i, "_forward": self._forward_id})
         return out
-
-    def close(self):
-        if self._h:
-            _ffi.lib().isegmi_engine_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def postprocess(det_output, w, h, batch_idx=0, score_threshold=0.0):

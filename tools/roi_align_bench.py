@@ -36,14 +36,14 @@ def timeit(run, n=50):
     for _ in range(n): run()
     _ffi.sync(); return (time.perf_counter() - t0) / n * 1e6
 def plain():
-    if f16: _ffi.check(L.isegmi_op_roi_align_f16(ptrs, Hs, Ws, sc, 4, dr.ptr, dcnt.ptr, N, K, Cc, PH, PH, 2, 2, do.ptr, None))
-    else: _ffi.check(L.isegmi_op_roi_align(ptrs, Hs, Ws, sc, 4, dr.ptr, dcnt.ptr, N, K, Cc, PH, PH, 2, 2, -1, do.ptr, None, None))
+    if f16: _ffi.check(L.isegmi_op_roi_align_f16(ptrs, Hs, Ws, sc, 4, dr.ptr, dcnt.ptr, N, K, Cc, PH, PH, 2, 0, 2, do.ptr, None))   # sampling 2, aligned 0, k_min 2
+    else: _ffi.check(L.isegmi_op_roi_align(ptrs, Hs, Ws, sc, 4, dr.ptr, dcnt.ptr, N, K, Cc, PH, PH, 2, 0, 2, -1, do.ptr, None, None))
 use_order = [True]
 def ordered():
     fn = L.isegmi_op_roi_align_f16_ordered if f16 else L.isegmi_op_roi_align_ordered
     _ffi.check(fn(ptrs, Hs, Ws, sc, 4, dr.ptr, dcnt.ptr, dord.ptr if use_order[0] else None, dtab.ptr, N, K, Cc, PH, PH, 2, do.ptr, None))
 def order():
-    _ffi.check(L.isegmi_op_roi_prep(dr.ptr, dcnt.ptr, N, K, Hs, Ws, sc, 4, 2, Cc, PH, PH, 2 if f16 else 4, dord.ptr, dtab.ptr, None))
+    _ffi.check(L.isegmi_op_roi_prep(dr.ptr, dcnt.ptr, N, K, Hs, Ws, sc, 4, 2, Cc, PH, PH, 2 if f16 else 4, 0, dord.ptr, dtab.ptr, None))
 fp = sum(N * h * w * Cc for h, w in shapes) * np.dtype(dt).itemsize + N * K * PH * PH * Cc * np.dtype(dt).itemsize
 print("N %d %s %s: algorithmic %.0f MB" % (N, "f16" if f16 else "f32", "clustered" if clustered else "uniform", fp / 1e6))
 plain(); _ffi.sync(); ref = do.numpy().copy()
@@ -52,7 +52,7 @@ print("prep pass                  %7.1f us" % timeit(order))
 for name, o in (("row order", None), ("random", rng.permutation(N * K).astype(np.int32)), ("roi_prep order", 0)):
     order(); _ffi.sync()
     use_order[0] = o is not None
-    if use_order[0] and not isinstance(o, int): _ffi.check(L.isegmi_h2d(dord.ptr, o.ctypes.data_as(C.c_void_p), C.c_int64(o.nbytes)))
+    if use_order[0] and not isinstance(o, int): _ffi.check(L.isegmi_h2d(dord.ptr, o.ctypes.data_as(C.c_void_p), o.nbytes))
     ordered(); _ffi.sync()
     assert np.array_equal(do.numpy(), ref)
     t = timeit(ordered); print("table, %-18s  %7.1f us  %.0f GB/s" % (name, t, fp / t / 1e3), flush=True)
