@@ -466,6 +466,25 @@ typedef struct isegmi_retina_post_args {
 } isegmi_retina_post_args;
 int64_t isegmi_op_retina_postprocess_workspace(int N, int nseg, int seg_len);
 int isegmi_op_retina_postprocess(const isegmi_retina_post_args* a, void* stream);
+/* ---- YOLOv3 tail and route ([UPSTREAM-RECALL] the public yolov3.cfg, unverified) ----
+ * isegmi_op_yolo_select: objectness x class selection, top-n cut and grid decode for nl <= 3 levels x N images in two launches, straight from the raw head
+ * tensors.  d_heads[l] is [N][H_l][W_l][A * (5 + C)] as the convolution wrote it, channel a * (5 + C) + k, k = 0..4 = tx, ty, tw, th, to, then the class logits;
+ * grid_hw [nl][2] = (H_l, W_l), strides [nl], anchors_wh [nl][A][2] in pixels: host arrays.  A (cell, anchor, class) is a candidate iff s = sigmoid(to) *
+ * sigmoid(t_c) > conf_thresh (strict; multi_label 0: only the class of the largest sigmoid, lowest index on ties).  Per (level, image) the min(#candidates,
+ * top_n) best by (s desc, flat index ((y W + x) A + a) C + c asc) are decoded -- bx = (sigmoid(tx) + x) stride, bw = exp(tw) anchor_w, corners bx -+ bw / 2,
+ * clipped to [0, canvas_w] x [0, canvas_h]; a NaN box and a box with a side below min_wh are dropped -- into isegmi_op_retina_postprocess's input layout:
+ * d_out_boxes [N][nl * top_n][4], d_out_scores / d_out_labels [N][nl * top_n] (label c + 1; rows past a count: zero box, score -1, label 0), d_out_cnt [N][nl],
+ * and d_out_total [N][nl] = the candidates BEFORE the top_n cut.  A 1..8, C 1..256, top_n 1..1024, conf_thresh >= 0.  d_ws: isegmi_op_yolo_select_workspace
+ * bytes (-1: bad sizes).  isegmi_op_yolo_slice_records: the anchor records one block of the first launch takes for class count C. */
+#define ISEGMI_YOLO_MAX_LEVELS 3
+int isegmi_op_yolo_slice_records(int C);
+int64_t isegmi_op_yolo_select_workspace(int nl, int N, const int32_t* grid_hw, int A, int C, int top_n);
+int isegmi_op_yolo_select(int nl, int N, const float* const* d_heads, const int32_t* grid_hw, const int32_t* strides, const float* anchors_wh, int A, int C,
+                          int top_n, float conf_thresh, int multi_label, float min_wh, int canvas_w, int canvas_h, void* d_ws, int64_t ws_bytes,
+                          float* d_out_boxes, float* d_out_scores, int32_t* d_out_labels, int32_t* d_out_cnt, int32_t* d_out_total, void* stream);
+/* darknet's upsample + route: d_out [N][2 Hc][2 Wc][Cc + Cs] = [d_coarse[n][y / 2][x / 2] | d_skip[n][y][x]]; Cc, Cs multiples of 32.  NULL pointers and
+ * sizes <= 0 are refused before any launch. */
+int isegmi_op_concat_up2x(const float* d_coarse, int N, int Hc, int Wc, int Cc, const float* d_skip, int Cs, float* d_out, void* stream);
 
 /* ---- COCO run-length encoding on the device (the on-disk format behind inference() / tools/test_net.py,
  * README.md:344-347, annotation layout README.md:55-66; Yolact eval.py Detections.add_mask / dump, README.md:243-249) ----
@@ -555,7 +574,8 @@ int isegmi_op_pose_scores(const float* d_scores_in, const int32_t* d_counts, int
  * state-dict names with BN already folded to (scale, shift) by the Python host; activations,
  * workspaces and outputs live in named device buffers owned by the engine. */
 typedef struct isegmi_engine isegmi_engine;
-/* model_kind: 1 = Yolact R50-FPN, 2 = Mask R-CNN R50/R101-FPN, 3 = Pose2Seg (H = W = 512), 4 = RetinaNet R50/R101-FPN.  H, W = network input size. */
+/* model_kind: 1 = Yolact R50-FPN, 2 = Mask R-CNN R50/R101-FPN, 3 = Pose2Seg (H = W = 512), 4 = RetinaNet R50/R101-FPN, 5 = YOLOv3 (Darknet-53).  H, W = network
+ * input size. */
 int isegmi_engine_create(int model_kind, int max_batch, int H, int W, isegmi_engine** out);
 int isegmi_engine_destroy(isegmi_engine* e);
 int isegmi_engine_set_param(isegmi_engine* e, const char* name, float value);
@@ -595,6 +615,13 @@ int isegmi_maskrcnn_forward_canvas(isegmi_engine* e, const float* d_images_nhwc3
  * are refused by name, and so is a "retina_levels" other than 5. */
 int isegmi_retinanet_forward(isegmi_engine* e, const float* d_images_nhwc3, const int32_t* h_image_hw, int N);
 int isegmi_retinanet_forward_canvas(isegmi_engine* e, const float* d_images_nhwc3, const int32_t* h_image_hw, int N, int H, int W);
+/* YOLOv3 (model_kind 5): d_images [N][H][W][3] = the letterboxed canvas of the engine's (H, W) (multiples of 32 in 32..1024), RGB, x / 255.
+ * Darknet-53 -> three heads (head.<s>.conv0..6, head.<s>.route, s = 0 at stride 32) -> isegmi_op_yolo_select -> isegmi_op_retina_postprocess.  Results in
+ * canvas coordinates: det.count [N], det.box [N][cap][4], det.score / det.label [N][cap]; yolo.head<s> (raw head tensors), yolo.cand_* and yolo.cand_cnt /
+ * yolo.cand_total [N][3] in named buffers.  Params: yolo_anchor0..17 = the anchors [3][3][2] (pixels, stride 32 first), yolo_conf_thresh (0.5), yolo_nms_thresh (0.4),
+ * yolo_pre_nms_top_n (1024, 1..1024), yolo_multi_label (1), yolo_min_wh (0), detections_per_img, detections_cap, nms_ge / nms_plus_one (0 here) /
+ * nms_index_order.  fp32 only: "fp16" and "graph" are refused by name. */
+int isegmi_yolov3_forward(isegmi_engine* e, const float* d_images_nhwc3, int N);
 /* Masker paste of the last forward into (out_h,out_w) planes; boxes first scaled by h_ratios_wh [N][2] =
  * (out_w/w_i, out_h/h_i) like BoxList.resize -> det.masks u8 [N][cap][out_h][out_w], det.box_resized */
 int isegmi_maskrcnn_paste(isegmi_engine* e, const float* h_ratios_wh, int out_h, int out_w);

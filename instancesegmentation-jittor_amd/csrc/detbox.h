@@ -1,6 +1,6 @@
 // detbox.h -- the device code that makes the detectors' discrete decisions, in one place: ordered sort keys, box decode / clip / min-size, the exact IoU
-// predicate, the block-wide bitonic sort, the 64 x 64 suppression-matrix tile and the chunk resolve of the greedy scan.  Shared by csrc/select.hip (top-k),
-// csrc/rcnn_ops.hip (RPN, box head) and csrc/retinanet_ops.hip; every result here is pinned bit for bit against oracle/ora_ops.c by the tests of those files.
+// predicate, the block-wide bitonic sort, the radix select, the 64 x 64 suppression-matrix tile and the chunk resolve of the greedy scan.  Shared by csrc/select.hip
+// (top-k), csrc/rcnn_ops.hip (RPN, box head), csrc/retinanet_ops.hip and csrc/yolo_ops.hip; every result here is pinned bit for bit against oracle/ora_ops.c by the tests of those files.
 // Box arithmetic follows the oracle operation for operation (compile with -ffp-contract=off, see detmath.h).
 #pragma once
 #include "../../include/isegmi.h"
@@ -132,6 +132,49 @@ __device__ __forceinline__ void bitonic_sort(unsigned long long* keys, const uns
             }
             __syncthreads();
         }
+}
+
+// ------------------------------------------------------------------ radix select
+constexpr int DET_RADIX_BINS = 2048;   // 11-bit digits: 6 passes over a 64-bit key
+// The k-th largest of `total` >= k unique 64-bit keys (k >= 1): six 11-bit digits from the top, one LDS histogram each.  each(f) calls f(key) for every key,
+// block-wide, in any order.  All threads return the same value.
+template <class Each>
+__device__ unsigned long long radix_select64(Each each, unsigned k, unsigned* hist, unsigned* sel) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    unsigned long long prefix = 0ull;
+    unsigned kk = k;
+    for (int pass = 0; pass < 6; ++pass) {
+        const int shift = 55 - 11 * pass;
+        for (int i = tid; i < DET_RADIX_BINS; i += blockDim.x) hist[i] = 0u;
+        __syncthreads();
+        each([&](unsigned long long key) {
+            const bool match = pass == 0 || (key >> (shift + 11)) == (prefix >> (shift + 11));
+            if (match) atomicAdd(&hist[(unsigned)(key >> shift) & (DET_RADIX_BINS - 1)], 1u);   // a count: order-free
+        });
+        __syncthreads();
+        if (tid < 64) {   // wave 0: lane owns 32 consecutive bins; suffix sums across lanes, then a walk down its own bins
+            constexpr int PER = DET_RADIX_BINS / 64;
+            unsigned tsum = 0u;
+            for (int j = 0; j < PER; ++j) tsum += hist[lane * PER + j];
+            unsigned v = tsum;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const unsigned o = __shfl_down(v, off, 64);
+                if (lane + off < 64) v += o;
+            }
+            unsigned above = v - tsum;
+            for (int j = PER - 1; j >= 0; --j) {
+                const unsigned h = hist[lane * PER + j];
+                if (above < kk && above + h >= kk) { sel[0] = (unsigned)(lane * PER + j); sel[1] = kk - above; }
+                above += h;
+            }
+        }
+        __syncthreads();
+        prefix |= (unsigned long long)sel[0] << shift;
+        kk = sel[1];
+        __syncthreads();
+    }
+    return prefix;
 }
 
 // ------------------------------------------------------------------ suppression-matrix tile

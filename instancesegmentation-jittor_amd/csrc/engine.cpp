@@ -1,5 +1,5 @@
 // engine.cpp -- engine object behind the C ABI: weights, buffers, conv launches, streams and lanes, uploads, timings.  The models' forward graphs
-// are in yolact.cpp, maskrcnn.cpp, pose2seg.cpp and retinanet.cpp, over the ResNet trunk of resnet.cpp.
+// are in yolact.cpp, maskrcnn.cpp, pose2seg.cpp, retinanet.cpp and yolov3.cpp, over the trunks of resnet.cpp and darknet.cpp.
 #include <mutex>
 #include "engine.h"
 
@@ -775,7 +775,8 @@ extern "C" int isegmi_engine_lane_layout(isegmi_engine* h, int32_t* out, int n) 
 
 extern "C" int isegmi_engine_create(int model_kind, int max_batch, int H, int W, isegmi_engine** out) {
     ARG_CHECK(out, "null out");
-    ARG_CHECK(model_kind >= 1 && model_kind <= 4, "model_kind: 1 yolact, 2 maskrcnn, 3 pose2seg, 4 retinanet");
+    ARG_CHECK(model_kind >= 1 && model_kind <= 5, "model_kind: 1 yolact, 2 maskrcnn, 3 pose2seg, 4 retinanet, 5 yolov3");
+    ARG_CHECK(model_kind != 5 || (H % 32 == 0 && W % 32 == 0 && H <= 1024 && W <= 1024), "yolov3: canvas sides are multiples of 32 in 32..1024");
     ARG_CHECK(model_kind != 3 || (H == 512 && W == 512), "pose2seg: the input plane is 512 x 512");
     ARG_CHECK(max_batch > 0 && H > 0 && W > 0, "sizes");
     isegmi_engine* h = new isegmi_engine();

@@ -1,4 +1,4 @@
-// engine.h -- model engine: packed-weight registry, named activation buffers, per-model forward graphs (yolact.cpp, maskrcnn.cpp, pose2seg.cpp, retinanet.cpp).
+// engine.h -- model engine: packed-weight registry, named activation buffers, per-model forward graphs (yolact.cpp, maskrcnn.cpp, pose2seg.cpp, retinanet.cpp, yolov3.cpp).
 #pragma once
 #include "tail_launch.h"
 #include <stdarg.h>
@@ -52,7 +52,7 @@ struct StageTime {
 constexpr float STEP_OVERLAP_DEFAULT = 1.0f;
 
 struct Engine {
-    int kind = 0;  // 1 yolact, 2 maskrcnn, 3 pose2seg, 4 retinanet
+    int kind = 0;  // 1 yolact, 2 maskrcnn, 3 pose2seg, 4 retinanet, 5 yolov3
     int max_batch = 0, H = 0, W = 0;       // H, W: the LARGEST network input (padded canvas) this engine serves
     int cur_H = 0, cur_W = 0;              // Mask R-CNN: padded canvas of the current forward (<= H, W; to_image_list pads each batch to its own size)
     int anchor_H = -1, anchor_W = -1;      // canvas the anchors.* buffers were generated for
@@ -298,6 +298,8 @@ int resnet_stage(Engine& e, const ResStage& s, const Tensor& in, Tensor* out);
 bool eng_has_gn(Engine& e, const std::string& layer);
 int eng_gn(Engine& e, const std::string& layer, Tensor* x, const Tensor* residual, bool relu);
 
+// darknet.cpp: the Darknet-53 trunk of yolact_darknet53_config and YOLOv3 -> C[0..2] at strides 8, 16, 32; before_c3: waited on before C[0] is overwritten
+int darknet_backbone(Engine& e, const std::string& prefix, const float* d_images, int N, Tensor* C, hipEvent_t before_c3);
 int yolact_forward(Engine& e, const float* d_images, int N);
 int yolact_postprocess(Engine& e, int h, int w, const int32_t* h_image_hw = nullptr);
 // "lazy_coeffs" (yolact.cpp): the two row-range views of the fused head, whether a forward of N images takes the lazy schedule, and the fill of headcat's

@@ -34,7 +34,7 @@ namespace {
 constexpr int RETINA_SLICE = 8192;      // logits per slice: 32 KB of keys in LDS
 constexpr int RETINA_KCAP = 1024;       // top_n the kernels hold
 constexpr int RETINA_NT = 1024;
-constexpr int RETINA_BINS = 2048;       // 11-bit digits: 6 passes over a 64-bit key
+constexpr int RETINA_BINS = DET_RADIX_BINS;
 constexpr int RETINA_MAX_SLOTS = 8192;  // candidate slots per image in retina_postprocess: 64 KB of sort keys in LDS
 
 struct RetinaLevel {
@@ -56,47 +56,6 @@ struct RetinaSelect {
     float* sel_scores; int* sel_idx; int* sel_cnt;
     float* out_boxes; float* out_scores; int* out_labels; int* out_cnt;
 };
-
-// The k-th largest of `total` >= k unique 64-bit keys (k >= 1): six 11-bit digits from the top, one LDS histogram each.  each(f) calls f(key) for every key,
-// block-wide, in any order.  All threads return the same value.
-template <class Each>
-__device__ unsigned long long radix_select64(Each each, unsigned k, unsigned* hist, unsigned* sel) {
-    const int tid = threadIdx.x, lane = tid & 63;
-    unsigned long long prefix = 0ull;
-    unsigned kk = k;
-    for (int pass = 0; pass < 6; ++pass) {
-        const int shift = 55 - 11 * pass;
-        for (int i = tid; i < RETINA_BINS; i += blockDim.x) hist[i] = 0u;
-        __syncthreads();
-        each([&](unsigned long long key) {
-            const bool match = pass == 0 || (key >> (shift + 11)) == (prefix >> (shift + 11));
-            if (match) atomicAdd(&hist[(unsigned)(key >> shift) & (RETINA_BINS - 1)], 1u);   // a count: order-free
-        });
-        __syncthreads();
-        if (tid < 64) {   // wave 0: lane owns 32 consecutive bins; suffix sums across lanes, then a walk down its own bins
-            constexpr int PER = RETINA_BINS / 64;
-            unsigned tsum = 0u;
-            for (int j = 0; j < PER; ++j) tsum += hist[lane * PER + j];
-            unsigned v = tsum;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const unsigned o = __shfl_down(v, off, 64);
-                if (lane + off < 64) v += o;
-            }
-            unsigned above = v - tsum;
-            for (int j = PER - 1; j >= 0; --j) {
-                const unsigned h = hist[lane * PER + j];
-                if (above < kk && above + h >= kk) { sel[0] = (unsigned)(lane * PER + j); sel[1] = kk - above; }
-                above += h;
-            }
-        }
-        __syncthreads();
-        prefix |= (unsigned long long)sel[0] << shift;
-        kk = sel[1];
-        __syncthreads();
-    }
-    return prefix;
-}
 
 // launch 1: grid = sum over levels of N * slices
 __global__ __launch_bounds__(RETINA_NT) void retina_slice_kernel(const RetinaSelect a) {

@@ -58,6 +58,13 @@ int retina_select_launch(const isegmi_retina_select_args* p, hipStream_t st);
 int64_t retina_post_workspace_bytes(int N, int nseg, int seg_len);
 int retina_postprocess_launch(const isegmi_retina_post_args* p, hipStream_t st);
 
+// ---- csrc/yolo_ops.hip
+int yolo_slice_records(int C);   // anchor records per slice of yolo_select's first launch (-1: C outside 1..256)
+int64_t yolo_select_workspace_bytes(int nl, int N, const int* grid_hw, int A, int C, int top_n);
+int yolo_select_launch(int nl, int N, const float* const* d_heads, const int* grid_hw, const int* strides, const float* anchors_wh, int A, int C, int top_n,
+                       float conf_thresh, int multi_label, float min_wh, int canvas_w, int canvas_h, void* d_ws, int64_t ws_bytes, float* d_out_boxes,
+                       float* d_out_scores, int* d_out_labels, int* d_out_cnt, int* d_out_total, hipStream_t st);
+int concat_up2x_launch(const float* coarse, int N, int Hc, int Wc, int Cc, const float* skip, int Cs, float* out, hipStream_t st);
 
 // ---- csrc/keypoint_ops.hip
 int keypoint_heatmap_launch(const float* in, int64_t R, int Hi, int Wi, int K, float* out, hipStream_t st);

@@ -34,38 +34,6 @@ struct HeadsScope {
     ~HeadsScope() { if (on) { e.stream = s; for (int k = 0; k < 3; ++k) e.side[k] = sd[k]; e.cur = s; } }
 };
 
-// yolact_darknet53_config: DarkNetBackbone([1, 2, 8, 8, 4]), selected layers 2-4 -> C[0..2]
-static int darknet_backbone(Engine& e, const float* d_images, int N, Tensor* C) {
-    if (e.fp16) { set_error("the Darknet53 backbone runs in fp32 only"); return ISEGMI_ERR_STATE; }
-    // _preconv: 3x3 on the 3-channel image, via a zero-padded 32-channel copy; every conv is Conv + BN + LeakyReLU(0.1), a
-    // block is 1x1 (C -> C/2) then 3x3 (C/2 -> C) with the shortcut added AFTER the activation (act 4)
-    Tensor x4, x;
-    TRY(eng_act(e, "input32", N, e.H, e.W, 32, &x4));
-    TRY(pad_c3_c32_launch(d_images, (int64_t)N * e.H * e.W, x4.d, e.cur));
-    TRY(eng_input_consumed(e));
-    TRY(eng_conv(e, "backbone._preconv.0", x4, 1, 1, 3, nullptr, "stem", &x));
-    eng_mark(e, "stem");
-    const int nblk[5] = {1, 2, 8, 8, 4};
-    for (int li = 0; li < 5; ++li) {
-        const std::string ln = "backbone.layers." + std::to_string(li);
-        // C3 (layer 2's output, then C4, C5) is about to be overwritten: the previous step's lateral convs must have read them
-        if (li == 2 && e.lat_pending[e.lane]) HIP_TRY(hipStreamWaitEvent(e.stream, e.lat_done[e.lane], 0));
-        Tensor y;
-        TRY(eng_conv(e, ln + ".0.0", x, 2, 1, 3, nullptr, ln + ".down", &y));
-        x = y;
-        for (int b = 1; b <= nblk[li]; ++b) {
-            const std::string nm = ln + "." + std::to_string(b);
-            Tensor t1;
-            TRY(eng_conv(e, nm + ".conv1", x, 1, 0, 3, nullptr, nm + ".t1", &t1));
-            TRY(eng_conv(e, nm + ".conv2", t1, 1, 1, 4, &x, nm + ".out", &y));
-            x = y;
-        }
-        if (li >= 2) C[li - 2] = x;
-        if (li >= 1) eng_mark(e, li == 1 ? "layer1" : li == 2 ? "layer2" : li == 3 ? "layer3" : "layer4");
-    }
-    return ISEGMI_OK;
-}
-
 // ResNet-50 / -101, stride on the 3x3, a DCNv2 conv2 where the weights have one (YOLACT++) -> C[0..2] = res3.C, res4.C, res5.C
 static int resnet_backbone(Engine& e, const float* d_images, int N, Tensor* C) {
     Tensor x;
@@ -382,7 +350,8 @@ int yolact_forward(Engine& e, const float* d_images, int N) {
     const int dt = e.fp16 ? 1 : 0;  // fp16 storage + f16 MFMA convolutions (optional mode; heads / prototypes / Detect stay fp32)
     if (dt && e.convs.count("prediction_layers.0.head_cat") == 0) { set_error("fp16 Yolact needs the fused prediction head"); return ISEGMI_ERR_STATE; }
     Tensor C[3], P[5];   // C3-C5, P3-P7
-    if (e.param("darknet", 0.0f) != 0.0f) TRY(darknet_backbone(e, d_images, N, C));
+    // yolact_darknet53_config.  C3 (then C4, C5) is about to be overwritten there: the previous step's lateral convs must have read them
+    if (e.param("darknet", 0.0f) != 0.0f) TRY(darknet_backbone(e, "backbone.", d_images, N, C, e.lat_pending[e.lane] ? e.lat_done[e.lane] : nullptr));
     else TRY(resnet_backbone(e, d_images, N, C));
     if (pipe) {  // hand the rest of this forward to the heads stream group; the caller's next forward starts its backbone at once
         hipEvent_t ev;

@@ -775,6 +775,57 @@ def retina_postprocess(boxes, scores, labels, seg_cnt, ncls=81, nms_thr=0.4, det
     return [(B[i, : c[i]], S[i, : c[i]], Lb[i, : c[i]]) for i in range(N)]
 
 
+# ---------------------------------------------------------------- YOLOv3 tail and route
+def yolo_slice_records(Cc):
+    """Anchor records one block of yolo_select's first launch takes for class count Cc."""
+    return lib().isegmi_op_yolo_slice_records(int(Cc))
+
+
+def yolo_select_device(heads, strides, anchors_wh, A, top_n, conf_thresh, multi_label, min_wh, canvas_w, canvas_h):
+    """isegmi_op_yolo_select on poisoned outputs; heads[l] [N,H_l,W_l,A*(5+C)].  -> the device buffers (boxes, scores, labels, cnt, total), still on the
+    device (the chained test hands them to retina_postprocess), and their shapes' N, nl."""
+    nl = len(heads)
+    hs = [np.ascontiguousarray(x, np.float32) for x in heads]
+    N = hs[0].shape[0]
+    Cc = hs[0].shape[3] // A - 5
+    keep = [DeviceBuffer.from_numpy(x) for x in hs]
+    ptrs = (C.c_void_p * nl)(*[b.ptr.value for b in keep])
+    grid = (C.c_int32 * (2 * nl))(*[v for x in hs for v in x.shape[1:3]])
+    st = (C.c_int32 * nl)(*[int(s) for s in strides])
+    an = np.ascontiguousarray(anchors_wh, np.float32).reshape(nl, A, 2)
+    wsb = lib().isegmi_op_yolo_select_workspace(nl, N, grid, A, Cc, top_n)
+    if wsb < 0:
+        raise IsegmiError("isegmi_op_yolo_select_workspace: bad sizes")
+    ws = DeviceBuffer((wsb,), np.uint8).poison()
+    ob = DeviceBuffer((N, nl * top_n, 4)).poison(); os_ = DeviceBuffer((N, nl * top_n)).poison(); ol = DeviceBuffer((N, nl * top_n), np.int32).poison()
+    oc = DeviceBuffer((N, nl), np.int32).poison(); ot = DeviceBuffer((N, nl), np.int32).poison()
+    check(lib().isegmi_op_yolo_select(nl, N, ptrs, grid, st, an.ctypes.data_as(C.c_void_p), A, Cc, top_n, conf_thresh, int(multi_label), min_wh, int(canvas_w),
+                                      int(canvas_h), ws.ptr, wsb, ob.ptr, os_.ptr, ol.ptr, oc.ptr, ot.ptr, None))
+    sync()
+    return ob, os_, ol, oc, ot
+
+
+def yolo_select(heads, strides, anchors_wh, A=3, top_n=1024, conf_thresh=0.5, multi_label=1, min_wh=0.0, canvas_w=416, canvas_h=416):
+    """-> (dec, total): dec[l][i] = (boxes, scores, labels) of level l, image i in selection order; total [N, nl] candidates before the cut."""
+    nl, N = len(heads), np.asarray(heads[0]).shape[0]
+    ob, os_, ol, oc, ot = yolo_select_device(heads, strides, anchors_wh, A, top_n, conf_thresh, multi_label, min_wh, canvas_w, canvas_h)
+    c = oc.numpy(); B = ob.numpy().reshape(N, nl, top_n, 4); S = os_.numpy().reshape(N, nl, top_n); Lb = ol.numpy().reshape(N, nl, top_n)
+    past = np.arange(top_n)[None, None, :] >= c[:, :, None]   # the rows past a count are filled: zero box, score -1, label 0
+    assert (S[past] == -1).all() and (Lb[past] == 0).all() and not B[past].any()
+    return [[(B[i, l, : c[i, l]], S[i, l, : c[i, l]], Lb[i, l, : c[i, l]]) for i in range(N)] for l in range(nl)], ot.numpy()
+
+
+def concat_up2x(coarse, skip):
+    """isegmi_op_concat_up2x: coarse [N,Hc,Wc,Cc], skip [N,2Hc,2Wc,Cs] -> [N,2Hc,2Wc,Cc+Cs]."""
+    coarse = np.ascontiguousarray(coarse, np.float32); skip = np.ascontiguousarray(skip, np.float32)
+    N, Hc, Wc, Cc = coarse.shape
+    assert skip.shape[:3] == (N, 2 * Hc, 2 * Wc)
+    dc = DeviceBuffer.from_numpy(coarse); ds = DeviceBuffer.from_numpy(skip)
+    out = DeviceBuffer((N, 2 * Hc, 2 * Wc, Cc + skip.shape[3])).poison()
+    check(lib().isegmi_op_concat_up2x(dc.ptr, N, Hc, Wc, Cc, ds.ptr, skip.shape[3], out.ptr, None))
+    return out.numpy()
+
+
 # ---------------------------------------------------------------- fp16 conv (configs[4])
 def pack_conv_weights_f16(desc, w_krsc):
     w = np.ascontiguousarray(w_krsc, np.float32)

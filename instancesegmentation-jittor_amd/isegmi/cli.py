@@ -5,9 +5,10 @@
   python -m isegmi.cli test_net --config-file cfg.yaml [--images dir] [--output results.json]
   python -m isegmi.cli pose2seg_test --weights random --anno person_keypoints.json --image-root DIR [--output segm.json] [--batch-size 8]
   python -m isegmi.cli pose2seg_test --weights random --keypoint-config kp.yaml --keypoint-weights random|FILE --anno images.json --image-root DIR
+  python -m isegmi.cli yolo_detect --cfg configs/yolov3.cfg --weights random|FILE.npz|FILE.weights --images DIR --output dets.json [--img-size 416]
   python -m isegmi.cli coco_eval --gt instances.json --dt results.json --iou-type segm|bbox|keypoints [--cat-ids ...] [--max-dets ...] [--out stats.json]
 
-eval, test_net and pose2seg_test take an optional `--gt instances.json`: after writing their json they print the COCO AP / AR summary.
+eval, test_net, pose2seg_test and yolo_detect take an optional `--gt instances.json`: after writing their json they print the COCO AP / AR summary.
 
 `--trained_model` / `MODEL.WEIGHT` take the .npz written by tools/import_pth.py; the literal value `random` uses the
 seeded synthetic weights (there is no network to fetch the reference's .pth files).  Images are read with PIL.
@@ -231,6 +232,62 @@ def _pose2seg_from_detector(a, sd, local):
     return results
 
 
+def yolo_config(a):
+    """The YoloV3Config of a yolo_detect command line: the .cfg's model, the canvas of --img-size, the thresholds given."""
+    from .config import parse_darknet_cfg
+    kw = {}
+    if a.conf_thres is not None:
+        kw["conf_thresh"] = a.conf_thres
+    if a.nms_thres is not None:
+        kw["nms_thresh"] = a.nms_thres
+    if a.bn_eps is not None:
+        kw["bn_eps"] = a.bn_eps
+    if a.best_class:
+        kw["multi_label"] = False
+    with open(a.cfg) as f:
+        ycfg = parse_darknet_cfg(f.read(), **kw)
+    if a.img_size:
+        import dataclasses
+        hw = a.img_size if len(a.img_size) == 2 else a.img_size * 2
+        ycfg = dataclasses.replace(ycfg, height=hw[0], width=hw[1]).validate()
+    return ycfg
+
+
+def cmd_yolo_detect(a):
+    """YOLOv3 detect / test: letterbox, forward, boxes back in image coordinates -> bbox-only COCO json (xywh, plain widths)."""
+    from .coco import dump, label_categories, yolo_results
+    from .weights import load_darknet_weights, yolov3_state_dict
+    from .yolov3 import YoloDetector
+    _, world, local = _rank_world()
+    if world > 1:
+        raise SystemExit("yolo_detect: WORLD_SIZE=%d: multi-rank inference (world > 1) is not built for YOLOv3" % world)
+    ycfg = yolo_config(a)
+    if a.weights in ("", "random", None):
+        sd = yolov3_state_dict(1234, ycfg.classes)
+    elif a.weights.endswith(".npz"):
+        sd = dict(np.load(a.weights))
+    elif a.weights.endswith(".weights"):
+        sd = load_darknet_weights(a.weights, ycfg)
+    else:
+        raise SystemExit("%s: --weights takes random, an .npz in this engine's names or a darknet .weights file" % a.weights)
+    files = sorted(os.path.join(a.images, f) for f in os.listdir(a.images))
+    cats = label_categories(ycfg.classes + 1)
+    det = YoloDetector(sd, ycfg, max_batch=a.batch_size, device=local)
+    results = []
+    try:
+        for i0 in range(0, len(files), a.batch_size):
+            dets = det.detect([_load_image_bgr(f) for f in files[i0:i0 + a.batch_size]])
+            for k, (boxes, scores, labels) in enumerate(dets):
+                results += yolo_results(i0 + k, boxes, scores, labels, cats)
+    finally:
+        det.close()
+    dump(results, a.output)
+    print("wrote %d detections for %d images to %s" % (len(results), len(files), a.output))
+    if a.gt:
+        _print_coco_summary(a.gt, results, ("bbox",))
+    return results
+
+
 def _print_coco_summary(gt_path, results, iou_types, cat_ids=None, max_dets=None):
     """The COCO summary of a result list against an annotation file, as the reference's test commands print it."""
     from .cocoeval import evaluate_results
@@ -283,7 +340,18 @@ def build_parser():
     p.add_argument("--person-threshold", dest="person_threshold", type=float, default=argparse.SUPPRESS, help="with --keypoint-config: keep detections with score > this")
     p.add_argument("--keypoint-threshold", dest="keypoint_threshold", type=float, default=argparse.SUPPRESS,
                    help="with --keypoint-config: a keypoint is visible where its logit > this")
-    for q in (e, t, p):
+    y = sub.add_parser("yolo_detect", help="YOLOv3 detection over a directory of images -> bbox-only COCO json")
+    y.add_argument("--cfg", default="configs/yolov3.cfg", help="darknet yolov3.cfg (only this topology is built)")
+    y.add_argument("--weights", default="random", help="random (seeded synthetic weights), FILE.npz in this engine's names, or a darknet FILE.weights")
+    y.add_argument("--images", required=True, help="directory of images; image_id = index in sorted order")
+    y.add_argument("--img-size", dest="img_size", type=int, nargs="+", default=None, help="canvas side, or height and width (multiples of 32 in 32..1024; default: the cfg's)")
+    y.add_argument("--conf-thres", dest="conf_thres", type=float, default=None, help="objectness x class score threshold (default 0.5)")
+    y.add_argument("--nms-thres", dest="nms_thres", type=float, default=None, help="class-wise NMS IoU threshold (default 0.4)")
+    y.add_argument("--bn-eps", dest="bn_eps", type=float, default=None, help="BatchNorm epsilon of the fold: 1e-5 (default) or darknet's 1e-6")
+    y.add_argument("--best-class", dest="best_class", action="store_true", help="one candidate per anchor, its best class, instead of every class over the threshold")
+    y.add_argument("--output", default="dets.json")
+    y.add_argument("--batch-size", dest="batch_size", type=int, default=8)
+    for q in (e, t, p, y):
         q.add_argument("--gt", default=None, help="COCO annotation json: print the COCO AP / AR summary of the written results (isegmi.cocoeval)")
     c = sub.add_parser("coco_eval", help="COCO AP / AR of a result json against an annotation json (pycocotools COCOeval restated)")
     c.add_argument("--gt", required=True, help="COCO annotation json")
@@ -297,7 +365,8 @@ def build_parser():
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
-    return {"eval": cmd_eval, "test_net": cmd_test_net, "pose2seg_test": cmd_pose2seg_test, "coco_eval": cmd_coco_eval}[a.cmd](a)
+    return {"eval": cmd_eval, "test_net": cmd_test_net, "pose2seg_test": cmd_pose2seg_test, "yolo_detect": cmd_yolo_detect,
+            "coco_eval": cmd_coco_eval}[a.cmd](a)
 
 
 if __name__ == "__main__":

@@ -237,6 +237,18 @@ def maskrcnn_results(image_id, boxes_xyxy, scores, labels, masks=None, categorie
     return out
 
 
+def yolo_results(image_id, boxes_xyxy, scores, labels, categories=None):
+    """YOLOv3 bbox-only COCO entries: bbox = (x1, y1, x2 - x1, y2 - y1), plain widths (no +1); category_id through the contiguous -> json id map
+    (categories: a label_categories() list; default the 80 COCO classes)."""
+    cats = categories if categories is not None else label_categories()
+    b = np.asarray(boxes_xyxy, np.float32).reshape(-1, 4)
+    out = []
+    for k in range(b.shape[0]):
+        x1, y1, x2, y2 = (float(v) for v in b[k])
+        out.append({"image_id": int(image_id), "category_id": cats[int(labels[k])], "bbox": [x1, y1, x2 - x1, y2 - y1], "score": float(scores[k])})
+    return out
+
+
 def yolact_results(image_id, classes, scores, boxes_xyxy_int, masks=None, mask_scores=None):
     """Yolact eval.py Detections.add_bbox/add_mask: bbox [x1,y1,w,h] rounded to 0.1, class 0..79 -> COCO id.
     mask_scores (YOLACT++ re-scoring): upstream writes the mask entry with the re-scored value; kept here as "mask_score"."""

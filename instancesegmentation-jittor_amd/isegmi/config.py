@@ -326,3 +326,101 @@ def to_retinanet_config(c):
                            ANCHOR_STRIDES=tuple(int(s) for s in strides), ASPECT_RATIOS=tuple(float(x) for x in r.ASPECT_RATIOS), OCTAVE=float(r.OCTAVE),
                            SCALES_PER_OCTAVE=int(r.SCALES_PER_OCTAVE), NUM_CONVS=int(r.NUM_CONVS), PRE_NMS_TOP_N=int(r.PRE_NMS_TOP_N),
                            INFERENCE_TH=float(r.INFERENCE_TH), NMS_TH=float(r.NMS_TH), DETECTIONS_PER_IMG=int(c.TEST.DETECTIONS_PER_IMG), **resnext)
+
+
+# ---- darknet .cfg (YOLOv3)
+_NET_KEYS = (("batch", 1), ("subdivisions", 1), ("channels", 3), ("momentum", 0.9), ("decay", 0.0005), ("angle", 0), ("saturation", 1.5),
+             ("exposure", 1.5), ("hue", 0.1), ("learning_rate", 0.001), ("burn_in", 1000), ("max_batches", 500200), ("policy", "steps"),
+             ("steps", "400000,450000"), ("scales", ".1,.1"))
+
+
+def yolov3_sections(ycfg):
+    """The section list of yolov3.cfg for a YoloV3Config, from the public layer list: [(section, {key: str value})], [net] first."""
+    def conv(filters, size, stride=1, bn=True):
+        d = {"batch_normalize": "1"} if bn else {}
+        d.update(size=str(size), stride=str(stride), pad="1", filters=str(filters), activation="leaky" if bn else "linear")
+        return ("convolutional", d)
+    out = [("net", dict([("batch", "1"), ("subdivisions", "1"), ("width", str(ycfg.width)), ("height", str(ycfg.height))] + [(k, str(v)) for k, v in _NET_KEYS[2:]]))]
+    out.append(conv(32, 3))
+    for li, nb in enumerate((1, 2, 8, 8, 4)):
+        ch = 32 << li
+        out.append(conv(ch * 2, 3, 2))
+        for _ in range(nb):
+            out += [conv(ch, 1), conv(ch * 2, 3), ("shortcut", {"from": "-3", "activation": "linear"})]
+    anchors = ", ".join("%d,%d" % tuple(a) for a in ycfg.anchors)
+    for s, m in enumerate((512, 256, 128)):
+        if s:
+            out += [("route", {"layers": "-4"}), conv(m, 1), ("upsample", {"stride": "2"}), ("route", {"layers": "-1, %d" % (61, 36)[s - 1]})]
+        for i in range(6):
+            out.append(conv(2 * m if i & 1 else m, 3 if i & 1 else 1))
+        out.append(conv(3 * (5 + ycfg.classes), 1, bn=False))
+        out.append(("yolo", {"mask": ",".join(str(i) for i in ycfg.masks[s]), "anchors": anchors, "classes": str(ycfg.classes), "num": str(len(ycfg.anchors)),
+                             "jitter": ".3", "ignore_thresh": ".7", "truth_thresh": "1", "random": "1"}))
+    return out
+
+
+def yolov3_cfg_text(ycfg):
+    return "\n".join("[%s]\n%s\n" % (sec, "\n".join("%s=%s" % kv for kv in d.items())) for sec, d in yolov3_sections(ycfg))
+
+
+def _cfg_sections(text):
+    out = []
+    for n, line in enumerate(text.splitlines(), 1):
+        line = line.split("#", 1)[0].strip()
+        if not line:
+            continue
+        if line.startswith("["):
+            if not line.endswith("]"):
+                raise ValueError("cfg line %d: unterminated section header %r" % (n, line))
+            out.append((line[1:-1].strip(), {}))
+        else:
+            k, eq, v = line.partition("=")
+            if not eq or not out:
+                raise ValueError("cfg line %d: expected key=value inside a section, got %r" % (n, line))
+            out[-1][1][k.strip()] = v.strip()
+    return out
+
+
+def parse_darknet_cfg(text, **overrides):
+    """A darknet yolov3.cfg -> YoloV3Config (canvas from [net], classes / anchors / masks from the [yolo] sections; `overrides` set the inference
+    keys a .cfg does not carry).  Only the YOLOv3 topology is accepted: Darknet-53, three heads, A = 3.  Any other layer list -- yolov3-tiny and -spp
+    with their [maxpool] sections, another filter count, a missing route -- raises ValueError naming the first section that differs."""
+    from .yolov3 import YoloV3Config
+    secs = _cfg_sections(text)
+    if not secs or secs[0][0] not in ("net", "network"):
+        raise ValueError("cfg: the first section must be [net]")
+    net = secs[0][1]
+    yolos = [d for s, d in secs if s == "yolo"]
+    for i, (s, _) in enumerate(secs[1:]):
+        if s not in ("convolutional", "shortcut", "route", "upsample", "yolo"):
+            raise ValueError("cfg section %d [%s]: not part of the YOLOv3 topology (Darknet-53 and three heads; yolov3-tiny / -spp are not built)" % (i, s))
+    if len(yolos) != 3:
+        raise ValueError("cfg: %d [yolo] sections; the YOLOv3 topology has three" % len(yolos))
+    try:
+        nums = [int(v) for v in yolos[0]["anchors"].replace(" ", "").split(",")]
+        masks = tuple(tuple(int(v) for v in y["mask"].replace(" ", "").split(",")) for y in yolos)
+        ycfg = YoloV3Config(height=int(net["height"]), width=int(net["width"]), classes=int(yolos[0]["classes"]),
+                            anchors=tuple(zip(nums[0::2], nums[1::2])), masks=masks, **overrides)
+    except KeyError as e:
+        raise ValueError("cfg: missing key %s in [net] / [yolo]" % e)
+    if any(len(m) != 3 for m in masks):
+        raise ValueError("cfg [yolo] mask=%s: three anchors per head are built (A = 3)" % (",".join(map(str, next(m for m in masks if len(m) != 3)))))
+    for y in yolos[1:]:
+        if y.get("anchors", "").replace(" ", "") != yolos[0]["anchors"].replace(" ", "") or y.get("classes") != yolos[0]["classes"]:
+            raise ValueError("cfg [yolo]: the three sections must share anchors and classes")
+    ycfg.validate()
+    want = yolov3_sections(ycfg)[1:]
+    structural = {"convolutional": ("batch_normalize", "filters", "size", "stride", "pad", "activation"), "shortcut": ("from", "activation"),
+                  "route": ("layers",), "upsample": ("stride",), "yolo": ("mask", "classes", "num")}
+    for i, (s, d) in enumerate(secs[1:]):
+        if i >= len(want):
+            raise ValueError("cfg section %d [%s]: past the end of the YOLOv3 topology (%d layers)" % (i, s, len(want)))
+        ws, wd = want[i]
+        got = {k: d.get(k, "0" if k == "batch_normalize" else None) for k in structural[s]}
+        exp = {k: wd.get(k, "0" if k == "batch_normalize" else None) for k in structural.get(ws, ())}
+        norm = lambda m: {k: (v.replace(" ", "") if isinstance(v, str) else v) for k, v in m.items()}
+        if s != ws or norm(got) != norm(exp):
+            raise ValueError("cfg section %d [%s] %s: the YOLOv3 topology has [%s] %s here" % (i, s, norm(got), ws, norm(exp)))
+    if len(secs) - 1 != len(want):
+        raise ValueError("cfg: %d layers; the YOLOv3 topology has %d (it ends after section %d [%s])" % (len(secs) - 1, len(want), len(secs) - 2, secs[-1][0]))
+    return ycfg

@@ -1,6 +1,6 @@
 """The model-independent half of an engine wrapper: one `isegmi_engine` handle and everything every model does with it -- parameters, weight
 marshalling, streams and marks, named buffers, the uint8 front end, the device-side COCO output and the asynchronous download slots.
-Yolact, MaskRCNN (and with it RetinaNet) and Pose2Seg derive from Engine; isegmi.pipeline and isegmi.dist drive this interface."""
+Yolact, MaskRCNN (and with it RetinaNet), Pose2Seg and YoloV3 derive from Engine; isegmi.pipeline and isegmi.dist drive this interface."""
 import ctypes as C
 
 import numpy as np
@@ -175,3 +175,36 @@ class Engine:
             self.close()
         except Exception:
             pass
+
+
+class DetectionBlock:
+    """Mixin of the box detectors (RetinaNet, YoloV3): the four detection buffers of a step as one block through the engine's asynchronous download
+    slots (isegmi.predictor.inference).  The class has `cfg.det_cap` and the Engine methods."""
+    # -- the four detection buffers of a step through the engine's asynchronous download slots (isegmi.predictor.inference) --------------
+    _DET = (("det.count", 4, np.int32), ("det.box", 16, np.float32), ("det.score", 4, np.float32), ("det.label", 4, np.int32))
+
+    def detection_bytes(self, n):
+        """Bytes of one step's block for n images: [count i32 x n][box f32 x n*cap*4][score f32 x n*cap][label i32 x n*cap]."""
+        K = self.cfg.det_cap
+        return sum(n * (b if name == "det.count" else b * K) for name, b, _ in self._DET)
+
+    def download_detections_async(self, slot, pinned, n):
+        """Enqueue the copies of the last forward's detection buffers (first n images) into `pinned` behind it; download_wait(slot) then waits for them."""
+        K = self.cfg.det_cap
+        assert pinned.nbytes >= self.detection_bytes(n)
+        off = 0
+        for name, b, _ in self._DET:
+            nbytes = n * (b if name == "det.count" else b * K)
+            _ffi.check(_ffi.lib().isegmi_engine_download_async(self._h, slot, C.c_void_p(pinned.ptr.value + off), self._buffer_info(name)[0], nbytes))
+            off += nbytes
+
+    def unpack_detections(self, pinned, n):
+        """-> copies of (count [n], box [n, cap, 4], score [n, cap], label [n, cap]) out of a block download_detections_async filled."""
+        K = self.cfg.det_cap
+        out, off = [], 0
+        for name, b, dt in self._DET:
+            nbytes = n * (b if name == "det.count" else b * K)
+            a = np.array(pinned.array[off:off + nbytes]).view(dt)
+            out.append(a if name == "det.count" else a.reshape((n, K, 4) if name == "det.box" else (n, K)))
+            off += nbytes
+        return out

@@ -8,6 +8,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _ffi
+from .engine import DetectionBlock
 from .maskrcnn import BoxList, MaskRCNN, generate_anchors_multi, resnext_refusals
 from .weights import fold_frozen_batchnorm, to_krsc
 
@@ -66,7 +67,7 @@ def retina_level_shapes(H, W):
     return out
 
 
-class RetinaNet(MaskRCNN):
+class RetinaNet(MaskRCNN, DetectionBlock):
     KIND = 4
 
     def __init__(self, state_dict, H, W, cfg=RetinaNetConfig(), max_batch=2, device=0, fp16=False, graph=False):
@@ -148,35 +149,6 @@ class RetinaNet(MaskRCNN):
         self.forward_device(n)
         self.sync()
         return self.boxlists(n, *(self.fetch(k, n) for k in ("det.count", "det.box", "det.score", "det.label")))
-
-    # -- the four detection buffers of a step through the engine's asynchronous download slots (isegmi.predictor.inference) --------------
-    _DET = (("det.count", 4, np.int32), ("det.box", 16, np.float32), ("det.score", 4, np.float32), ("det.label", 4, np.int32))
-
-    def detection_bytes(self, n):
-        """Bytes of one step's block for n images: [count i32 x n][box f32 x n*cap*4][score f32 x n*cap][label i32 x n*cap]."""
-        K = self.cfg.det_cap
-        return sum(n * (b if name == "det.count" else b * K) for name, b, _ in self._DET)
-
-    def download_detections_async(self, slot, pinned, n):
-        """Enqueue the copies of the last forward's detection buffers (first n images) into `pinned` behind it; download_wait(slot) then waits for them."""
-        K = self.cfg.det_cap
-        assert pinned.nbytes >= self.detection_bytes(n)
-        off = 0
-        for name, b, _ in self._DET:
-            nbytes = n * (b if name == "det.count" else b * K)
-            _ffi.check(_ffi.lib().isegmi_engine_download_async(self._h, slot, C.c_void_p(pinned.ptr.value + off), self._buffer_info(name)[0], nbytes))
-            off += nbytes
-
-    def unpack_detections(self, pinned, n):
-        """-> copies of (count [n], box [n, cap, 4], score [n, cap], label [n, cap]) out of a block download_detections_async filled."""
-        K = self.cfg.det_cap
-        out, off = [], 0
-        for name, b, dt in self._DET:
-            nbytes = n * (b if name == "det.count" else b * K)
-            a = np.array(pinned.array[off:off + nbytes]).view(dt)
-            out.append(a if name == "det.count" else a.reshape((n, K, 4) if name == "det.box" else (n, K)))
-            off += nbytes
-        return out
 
     def selected(self, n):
         """Every level's selected list of the last forward: [l][i] = (scores, flat indices)."""

@@ -62,3 +62,35 @@ def yolact_transform(image_bgr_u8, size=550, darknet=False):
     from .yolact import darknet_base_transform, fast_base_transform
     x = bilinear_resize(np.asarray(image_bgr_u8, np.float32), size, size)[None]
     return darknet_base_transform(x) if darknet else fast_base_transform(x)
+
+
+def letterbox_geometry(h, w, S_h, S_w):
+    """YOLOv3 letterbox of an h x w image on an S_h x S_w canvas -> (gain, nh, nw, pad_x, pad_y): gain = min(S_h / h, S_w / w), the resized image
+    (round(h gain), round(w gain)) sits centred; the left / top padding is the floor of half the slack."""
+    gain = min(S_h / h, S_w / w)
+    nh, nw = min(max(int(round(h * gain)), 1), S_h), min(max(int(round(w * gain)), 1), S_w)
+    return gain, nh, nw, (S_w - nw) // 2, (S_h - nh) // 2
+
+
+def yolo_letterbox(image_bgr_u8, S_h=416, S_w=416):
+    """HxWx3 uint8 BGR -> (canvas [S_h, S_w, 3] float32 RGB in 0..1, (gain, pad_x, pad_y)): PIL bilinear resize (bytes, as maskrcnn_resize_u8), x / 255, no
+    mean / std, centred on a canvas filled with 0.5."""
+    from PIL import Image
+    h, w = image_bgr_u8.shape[:2]
+    gain, nh, nw, px, py = letterbox_geometry(h, w, S_h, S_w)
+    rgb = Image.fromarray(np.ascontiguousarray(image_bgr_u8[:, :, ::-1]))
+    if (nh, nw) != (h, w):
+        rgb = rgb.resize((nw, nh), Image.BILINEAR)
+    out = np.full((S_h, S_w, 3), 0.5, np.float32)
+    out[py:py + nh, px:px + nw] = np.asarray(rgb, np.float32) / np.float32(255.0)
+    return out, (gain, px, py)
+
+
+def yolo_unletterbox(boxes_xyxy, geometry, h, w):
+    """Canvas coordinates back to the original h x w image, in float32: (x - pad_x) / gain, (y - pad_y) / gain, clipped to [0, w] x [0, h]."""
+    gain, px, py = geometry
+    b = np.asarray(boxes_xyxy, np.float32).reshape(-1, 4)
+    out = (b - np.asarray([px, py, px, py], np.float32)) / np.float32(gain)
+    out[:, 0::2] = np.clip(out[:, 0::2], np.float32(0), np.float32(w))
+    out[:, 1::2] = np.clip(out[:, 1::2], np.float32(0), np.float32(h))
+    return out.astype(np.float32)

@@ -154,6 +154,121 @@ def fold_frozen_batchnorm(sd, prefix, eps=0.0):
     return scale, (b - m * scale).astype(np.float32)
 
 
+# ---- YOLOv3 ([UPSTREAM-RECALL] the public yolov3.cfg, unverified)
+YOLO_HEAD_WIDTHS = (512, 256, 128)   # M_s of head s (s = 0 at stride 32)
+# Recorded calibration of the random predictors (found with the CPU reference on seeded uniform images): a few hundred of a 64 x 96 canvas's 30 240
+# (anchor, class) pairs pass objectness x class > 0.05, on every level, and their boxes overlap enough for NMS to remove some.
+YOLO_HEAD_BN_SCALE = (0.55, 0.55, 0.69)   # the BN weights of head s: the layers of a head would otherwise grow the trunk's already large maps
+YOLO_BOX_GAIN = 0.25
+YOLO_OBJ_GAIN = 0.6
+YOLO_OBJ_BIAS = -1.0
+YOLO_CLS_GAIN = 0.6
+YOLO_CLS_BIAS = -2.9
+YOLO_CLS_BIAS_SPREAD = 0.5   # per (anchor, class): a few pairs sit near the threshold at every cell, so that small canvases have candidates too
+
+
+def yolov3_layers(classes=80):
+    """The 75 convolutions of yolov3.cfg in file order: (conv name, BN prefix or None, Cout, Cin, kernel).  A layer with a BN prefix is conv + BN +
+    LeakyReLU(0.1) and has no bias; the three predictors (head.<s>.conv6) have a bias and no BN."""
+    out = [("backbone._preconv.0", "backbone._preconv.1", 32, 3, 3)]
+    cin = 32
+    for li, nb in enumerate((1, 2, 8, 8, 4)):
+        ch = 32 << li
+        nm = "backbone.layers.%d" % li
+        out.append((nm + ".0.0", nm + ".0.1", ch * 2, cin, 3))
+        cin = ch * 2
+        for b in range(1, nb + 1):
+            out.append(("%s.%d.conv1" % (nm, b), "%s.%d.bn1" % (nm, b), ch, cin, 1))
+            out.append(("%s.%d.conv2" % (nm, b), "%s.%d.bn2" % (nm, b), cin, ch, 3))
+    for s, m in enumerate(YOLO_HEAD_WIDTHS):
+        cin = 1024 if s == 0 else m + (512 >> (s - 1))   # concat(route 256 | C4 512) = 768, concat(route 128 | C3 256) = 384
+        if s:
+            out.append(("head.%d.route" % s, "head.%d.route_bn" % s, m, YOLO_HEAD_WIDTHS[s - 1], 1))
+        for i in range(6):
+            k = 3 if i & 1 else 1
+            out.append(("head.%d.conv%d" % (s, i), "head.%d.bn%d" % (s, i), 2 * m if k == 3 else m, cin, k))
+            cin = 2 * m if k == 3 else m
+        out.append(("head.%d.conv6" % s, None, 3 * (5 + classes), 2 * m, 1))
+    assert len(out) == 75
+    return out
+
+
+def yolov3_state_dict(seed=1234, classes=80):
+    """Seeded random YOLOv3 weights: the trunk is darknet53_state_dict's, the heads are head.<s>.conv0..6 / head.<s>.bn0..5 and head.<s>.route /
+    head.<s>.route_bn (s = 1, 2).  The predictors carry the recorded gains / biases above."""
+    rng = np.random.default_rng(seed)
+    sd = {}
+    darknet53_state_dict(rng, sd, "backbone.")
+    for name, bn, cout, cin, k in yolov3_layers(classes):
+        if name.startswith("backbone."):
+            continue
+        if bn is not None:
+            sd[name + ".weight"] = _conv(rng, cout, cin, k)
+            _bn(rng, sd, bn, cout, YOLO_HEAD_BN_SCALE[int(name.split('.')[1])])
+            continue
+        w = _conv(rng, cout, cin, k).reshape(3, 5 + classes, cin, k, k)
+        b = (rng.standard_normal((3, 5 + classes)) * 0.1).astype(np.float32)
+        w[:, :4] *= np.float32(YOLO_BOX_GAIN); w[:, 4] *= np.float32(YOLO_OBJ_GAIN); w[:, 5:] *= np.float32(YOLO_CLS_GAIN)
+        b[:, 5:] *= np.float32(YOLO_CLS_BIAS_SPREAD / 0.1)
+        b[:, 4] += np.float32(YOLO_OBJ_BIAS); b[:, 5:] += np.float32(YOLO_CLS_BIAS)
+        sd[name + ".weight"] = w.reshape(cout, cin, k, k)
+        sd[name + ".bias"] = b.reshape(cout)
+    return sd
+
+
+DARKNET_WEIGHTS_HEADER = (0, 2, 0)   # major, minor, revision: minor >= 2 means a 64-bit `seen` follows
+
+
+def save_darknet_weights(sd, path, classes=80, seen=0):
+    """Write a state dict as a darknet .weights file: header (three int32, then int64 `seen`), then per convolution in cfg order bias (BN: beta), and
+    for a BN layer gamma, running mean, running var, then the weight [Cout][Cin][R][S]; all float32, little endian."""
+    with open(path, "wb") as f:
+        f.write(np.asarray(DARKNET_WEIGHTS_HEADER, "<i4").tobytes())
+        f.write(np.asarray([seen], "<i8").tobytes())
+        for name, bn, cout, cin, k in yolov3_layers(classes):
+            parts = [sd[bn + ".bias"], sd[bn + ".weight"], sd[bn + ".running_mean"], sd[bn + ".running_var"]] if bn else [sd[name + ".bias"]]
+            w = np.asarray(sd[name + ".weight"], np.float32)
+            if w.shape != (cout, cin, k, k) or any(np.asarray(p).shape != (cout,) for p in parts):
+                raise ValueError("%s: expected a weight of shape %s and %d-element vectors" % (name, (cout, cin, k, k), cout))
+            for p in parts + [w]:
+                f.write(np.ascontiguousarray(p, "<f4").tobytes())
+
+
+def load_darknet_weights(path, cfg=None):
+    """Read a darknet yolov3 .weights file into this project's state-dict names (BN statistics unfolded: YoloV3 folds them with cfg.bn_eps).  The file must
+    hold exactly the 75 convolutions of the topology: one that ends early or has floats left over raises and names the layer."""
+    classes = 80 if cfg is None else cfg.classes
+    raw = np.fromfile(path, np.uint8)
+    if raw.size < 20:
+        raise ValueError("%s: shorter than the 20-byte darknet header" % path)
+    major, minor, _ = np.frombuffer(raw[:12].tobytes(), "<i4")
+    if major * 10 + minor < 2:
+        raise ValueError("%s: header version %d.%d has a 32-bit `seen`; only the 64-bit form (0.2 and later) is read" % (path, major, minor))
+    body = raw[20:]
+    if body.size % 4:
+        raise ValueError("%s: %d bytes after the header are not a whole number of floats" % (path, body.size))
+    data = np.frombuffer(body.tobytes(), "<f4")
+    sd, off = {}, 0
+
+    def take(n, what):
+        nonlocal off
+        if off + n > data.size:
+            raise ValueError("%s: file too short: it ran out in %s (needs %d floats at offset %d, %d left)" % (path, what, n, off, data.size - off))
+        a = data[off:off + n].astype(np.float32)
+        off += n
+        return a
+    for name, bn, cout, cin, k in yolov3_layers(classes):
+        if bn:
+            for key in (".bias", ".weight", ".running_mean", ".running_var"):
+                sd[bn + key] = take(cout, name + " (BN" + key + ")")
+        else:
+            sd[name + ".bias"] = take(cout, name + " (bias)")
+        sd[name + ".weight"] = take(cout * cin * k * k, name + " (weight)").reshape(cout, cin, k, k)
+    if off != data.size:
+        raise ValueError("%s: file too long: %d floats left after the last layer head.2.conv6 (another topology or class count?)" % (path, data.size - off))
+    return sd
+
+
 # Recorded calibration of the Mask R-CNN predictors (found with the CPU oracle on the seeded image):
 # enough RPN proposals survive NMS and roughly 100 detections per image pass SCORE_THRESH 0.05.
 MRCNN_RPN_CLS_GAIN = 0.0012

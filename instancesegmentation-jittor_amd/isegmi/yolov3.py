@@ -1,0 +1,178 @@
+"""YOLOv3 inference, host side ([UPSTREAM-RECALL] the public yolov3.cfg / COCO-80 model, unverified: the reference's yolo.jittor directory is
+empty).  `net = YoloV3(sd, H, W)`; `dets = net(batch)` -> per image boxes (canvas coordinates), scores, labels 1..C.  `YoloDetector(...).detect(images)`
+adds the letterbox front end and maps the boxes back to the original images.  All numerics run in libisegmi.so (engine kind 5); this module moves
+config, weights and results across the C ABI.  The device front end (preprocess_u8) is not built for this model: the letterbox runs on the host."""
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _ffi
+from .engine import DetectionBlock, Engine
+from .weights import fold_batchnorm, to_krsc, yolov3_layers
+
+YOLO_MAX_TOP_N = 1024    # csrc/yolo_ops.hip YOLO_KCAP
+YOLO_MAX_CLASSES = 255   # the class-wise NMS holds 256 labels with the background
+YOLO_STRIDES = (32, 16, 8)
+YOLO_ANCHORS = ((10, 13), (16, 30), (33, 23), (30, 61), (62, 45), (59, 119), (116, 90), (156, 198), (373, 326))
+YOLO_MASKS = ((6, 7, 8), (3, 4, 5), (0, 1, 2))
+
+
+@dataclass(frozen=True)
+class YoloV3Config:
+    """yolov3.cfg inference constants.  anchors: the cfg's nine (w, h) pairs in pixels; masks: the anchors of the [yolo] layers in file order (stride 32
+    first).  multi_label True: every class with objectness x class > conf_thresh is a candidate (darknet, ultralytics); False: the best class only
+    (the PyTorch-YOLOv3 ports).  bn_eps: 1e-5 (the PyTorch ports); darknet's own normaliser uses 1e-6."""
+    height: int = 416
+    width: int = 416
+    classes: int = 80
+    anchors: tuple = YOLO_ANCHORS
+    masks: tuple = YOLO_MASKS
+    conf_thresh: float = 0.5
+    nms_thresh: float = 0.4
+    pre_nms_top_n: int = 1024
+    multi_label: bool = True
+    min_wh: float = 0.0
+    detections_per_img: int = 100
+    detections_cap: int = 0
+    nms_ge: int = 0
+    nms_plus_one: int = 0          # plain areas
+    nms_output_order: str = "score"
+    bn_eps: float = 1e-5
+
+    @property
+    def det_cap(self):
+        return max(self.detections_per_img, self.detections_cap)
+
+    def level_anchors(self):
+        """[3][3][2] float32: the anchors of head s (s = 0 at stride 32)."""
+        return np.asarray([[self.anchors[i] for i in m] for m in self.masks], np.float32)
+
+    def validate(self, H=None, W=None):
+        """Raises ValueError naming the key that is refused."""
+        for key, v in (("height", self.height if H is None else H), ("width", self.width if W is None else W)):
+            if v % 32 or not 32 <= v <= 1024:
+                raise ValueError("%s=%d: canvas sides are multiples of 32 in 32..1024" % (key, v))
+        if not 1 <= self.classes <= YOLO_MAX_CLASSES:
+            raise ValueError("classes=%d: 1..%d classes are built" % (self.classes, YOLO_MAX_CLASSES))
+        if len(self.masks) != 3 or any(len(m) != 3 for m in self.masks):
+            raise ValueError("masks=%r: three [yolo] layers of three anchors each are built (A = 3)" % (self.masks,))
+        if any(not 0 <= i < len(self.anchors) for m in self.masks for i in m) or any(len(a) != 2 or a[0] <= 0 or a[1] <= 0 for a in self.anchors):
+            raise ValueError("anchors=%r: positive (w, h) pairs, every mask index inside the list" % (self.anchors,))
+        if not 1 <= self.pre_nms_top_n <= YOLO_MAX_TOP_N:
+            raise ValueError("pre_nms_top_n=%d: the selection kernels hold 1..%d per level" % (self.pre_nms_top_n, YOLO_MAX_TOP_N))
+        if not self.conf_thresh >= 0:
+            raise ValueError("conf_thresh=%r: a non-negative number" % (self.conf_thresh,))
+        if not self.nms_thresh > 0:
+            raise ValueError("nms_thresh=%r: a positive number" % (self.nms_thresh,))
+        if not self.min_wh >= 0:
+            raise ValueError("min_wh=%r: a non-negative number" % (self.min_wh,))
+        if self.nms_output_order not in ("score", "index"):
+            raise ValueError("nms_output_order=%r: score or index" % (self.nms_output_order,))
+        return self
+
+
+def yolo_grids(H, W):
+    """(h, w) of the three heads' grids on an (H, W) canvas, stride 32 first."""
+    return [(H // s, W // s) for s in YOLO_STRIDES]
+
+
+def yolov3_folded(sd, cfg=YoloV3Config()):
+    """{layer: (weight [Cout][R][S][Cin], scale or None, shift)}: BN folded with cfg.bn_eps, the predictors with their bias."""
+    out = {}
+    for name, bn, cout, cin, k in yolov3_layers(cfg.classes):
+        w = np.asarray(sd[name + ".weight"], np.float32)
+        if w.shape != (cout, cin, k, k):
+            raise ValueError("%s.weight: expected %s, got %s" % (name, (cout, cin, k, k), w.shape))
+        sc, sh = fold_batchnorm(sd, bn, cfg.bn_eps) if bn else (None, np.asarray(sd[name + ".bias"], np.float32))
+        out[name] = (to_krsc(w), sc, sh)
+    return out
+
+
+class YoloV3(Engine, DetectionBlock):
+    KIND = 5
+
+    def __init__(self, state_dict, H=None, W=None, cfg=YoloV3Config(), max_batch=8, device=0, fp16=False, graph=False):
+        if fp16:
+            raise ValueError("YoloV3: fp16=True is not built (fp32 only)")
+        if graph:
+            raise ValueError("YoloV3: graph=True (hipGraph capture) is not built")
+        H, W = int(cfg.height if H is None else H), int(cfg.width if W is None else W)
+        cfg.validate(H, W)
+        self.cfg, self.H, self.W, self.max_batch = cfg, H, W, max_batch
+        self.fp16 = False
+        self._create(device, max_batch, H, W)
+        for name, (w, sc, sh) in yolov3_folded(state_dict, cfg).items():
+            if name == "backbone._preconv.0":   # the 3-channel image runs as a zero-padded 32-channel copy
+                w = np.concatenate([w, np.zeros(w.shape[:3] + (32 - w.shape[3],), np.float32)], -1)
+            self._set_conv_krsc(name, w, sc, sh)
+        for i, v in enumerate(cfg.level_anchors().reshape(-1)):
+            self.set_param("yolo_anchor%d" % i, float(v))
+        self.configure(cfg)
+        self._d_in = _ffi.DeviceBuffer((max_batch, H, W, 3))
+
+    def configure(self, cfg):
+        """The tail's parameters from a config (live: the next forward uses them)."""
+        cfg.validate(self.H, self.W)
+        for k, v in (("yolo_conf_thresh", cfg.conf_thresh), ("yolo_nms_thresh", cfg.nms_thresh), ("yolo_pre_nms_top_n", cfg.pre_nms_top_n),
+                     ("yolo_multi_label", float(bool(cfg.multi_label))), ("yolo_min_wh", cfg.min_wh), ("detections_per_img", cfg.detections_per_img),
+                     ("detections_cap", cfg.detections_cap), ("nms_ge", cfg.nms_ge), ("nms_plus_one", cfg.nms_plus_one),
+                     ("nms_index_order", {"score": 0, "index": 1}[cfg.nms_output_order])):
+            self.set_param(k, float(v))
+        self.cfg = cfg
+
+    def rle_device(self, image_hw=None):
+        raise RuntimeError("rle_device: YoloV3 is a box detector: there are no masks to encode")
+
+    def upload(self, batch_nhwc3, slot=0):
+        """A letterboxed fp32 batch [n, H, W, 3] (RGB, x / 255)."""
+        x = np.ascontiguousarray(batch_nhwc3, np.float32)
+        assert x.ndim == 4 and x.shape[1:] == (self.H, self.W, 3) and x.shape[0] <= self.max_batch, x.shape
+        _ffi.check(_ffi.lib().isegmi_h2d(self.input_buffer(slot).ptr, x.ctypes.data_as(C.c_void_p), x.nbytes))
+        return x.shape[0]
+
+    def forward_device(self, n, slot=0):
+        _ffi.check(_ffi.lib().isegmi_yolov3_forward(self._h, self.input_buffer(slot).ptr, n))
+
+    def detections(self, n):
+        cnt, box, score, label = (self.fetch(k, n) for k in ("det.count", "det.box", "det.score", "det.label"))
+        return [dict(box=box[i, :cnt[i]].copy(), score=score[i, :cnt[i]].copy(), label=label[i, :cnt[i]].copy()) for i in range(n)]
+
+    def __call__(self, batch_nhwc3):
+        """-> per image dict(box [k, 4] xyxy in canvas coordinates, score [k], label [k] in 1..classes)."""
+        n = self.upload(batch_nhwc3)
+        self.forward_device(n)
+        self.sync()
+        return self.detections(n)
+
+    def heads(self, n):
+        """The raw head tensors of the last forward, stride 32 first: [n, H_s, W_s, 3 * (5 + classes)]."""
+        return [self.fetch("yolo.head%d" % s, n) for s in range(3)]
+
+    def candidate_counts(self, n):
+        """(kept [n, 3], before the top-n cut [n, 3]) per (image, level) of the last forward: kept < before means the cut truncated that level."""
+        return self.fetch("yolo.cand_cnt", n), self.fetch("yolo.cand_total", n)
+
+
+class YoloDetector:
+    """Images in, detections in original image coordinates out: letterbox on the host, YoloV3 on the device, the back mapping in numpy fp32."""
+
+    def __init__(self, state_dict, cfg=YoloV3Config(), max_batch=8, device=0):
+        self.cfg = cfg
+        self.net = YoloV3(state_dict, cfg.height, cfg.width, cfg, max_batch=max_batch, device=device)
+
+    def detect(self, images_bgr_u8):
+        """list of HxWx3 uint8 BGR images -> list of (boxes [k, 4] xyxy float32, scores [k], labels [k])."""
+        from .transforms import yolo_letterbox, yolo_unletterbox
+        out = []
+        B = self.net.max_batch
+        for i0 in range(0, len(images_bgr_u8), B):
+            ims = images_bgr_u8[i0:i0 + B]
+            lb = [yolo_letterbox(im, self.cfg.height, self.cfg.width) for im in ims]
+            dets = self.net(np.stack([x for x, _ in lb]))
+            for im, (_, geo), d in zip(ims, lb, dets):
+                out.append((yolo_unletterbox(d["box"], geo, im.shape[0], im.shape[1]), d["score"], d["label"]))
+        return out
+
+    def close(self):
+        self.net.close()
