@@ -486,6 +486,29 @@ int isegmi_op_yolo_select(int nl, int N, const float* const* d_heads, const int3
  * sizes <= 0 are refused before any launch. */
 int isegmi_op_concat_up2x(const float* d_coarse, int N, int Hc, int Wc, int Cc, const float* d_skip, int Cs, float* d_out, void* stream);
 
+/* ---- ViT operators (csrc/vit_ops.hip states every operation order, tests/vit_ref.py restates it).  fp32, finite inputs only: NaN and
+ * inf are outside these contracts.  Pointers 16-byte aligned.
+ * isegmi_op_attention: softmax(q k^T / 8) v per (image, head), head dimension 64.  d_qkv [N][T][3 * heads * 64] as the qkv projection wrote it: channel
+ * which * D + h * 64 + d (which 0 q, 1 k, 2 v; D = heads * 64) belongs to head h; d_out [N][T][D], head h at channels h * 64 ..  1 <= T <= 1024.
+ *   s_ij = (fmaf chain from +0 over d ascending of q_i[d] k_j[d]) * 0.125;  m_i = max_j s_ij;  e_ij = dm_exp(s_ij - m_i);
+ *   l_i = (c_0 + c_1) + (c_2 + c_3) with c_r the chain from +0 of e_ij over j = r, r + 4, ... ascending;  p_ij = e_ij / l_i (IEEE division);
+ *   o_i[d] = fmaf chain from +0 over j ascending of p_ij v_j[d].  Tokens past T are never read. */
+int isegmi_op_attention(const float* d_qkv, int N, int T, int heads, float* d_out, void* stream);
+/* LayerNorm over the last axis: row r = d_x + r * x_row_stride, D floats (D % 4 == 0, D <= 2048; strides in floats, multiples of 4);
+ * y = ((x - x[0]) - m) * rstd * gamma + beta with m / rstd from fp32 per-lane chains of the shifted data folded in fp64 (biased variance, clamped at 0);
+ * d_out may be d_x.  The same bits for the same row whatever the row count or the strides. */
+int isegmi_op_layer_norm(const float* d_x, int64_t rows, int D, int64_t x_row_stride, const float* d_gamma, const float* d_beta, float eps,
+                         float* d_out, int64_t out_row_stride, void* stream);
+/* GELU, elementwise, d_y may be d_x.  gelu_tanh 0: (0.5 x) * (1 + erf(x * fp32(1 / sqrt 2))), erf = Cephes erff / erfcf with every operation rounded on
+ * its own; 1: (0.5 x) * (1 + tanh(fp32(sqrt(2 / pi)) * (x + 0.044715 * ((x * x) * x)))). */
+int isegmi_op_gelu(const float* d_x, float* d_y, int64_t n, int gelu_tanh, void* stream);
+/* [N][H][W][3] -> [N][H / P][W / P][P * P * 3], element (py * P + px) * 3 + c of a patch = its pixel (py, px), channel c: the patch embedding then is a
+ * 1x1 convolution over P * P * 3 channels.  H and W multiples of P. */
+int isegmi_op_patchify(const float* d_in_nhwc3, int N, int H, int W, int P, float* d_out, void* stream);
+/* softmax of `rows` rows of n logits: e_j = dm_exp(x_j - max); lane l of 64 chains e_l + e_(l + 64) + ... from +0, the lane sums fold as the tree
+ * s[l] += s[l + off], off = 32 .. 1; prob_j = e_j / sum (IEEE division). */
+int isegmi_op_class_softmax(const float* d_logits, int rows, int n, float* d_prob, void* stream);
+
 /* ---- COCO run-length encoding on the device (the on-disk format behind inference() / tools/test_net.py,
  * README.md:344-347, annotation layout README.md:55-66; Yolact eval.py Detections.add_mask / dump, README.md:243-249) ----
  * pycocotools rleEncode + rleToString restated: for every valid slot (n, k), k < d_count[n], of the uint8 planes d_masks [N][K][plane_h][plane_w]
@@ -574,8 +597,8 @@ int isegmi_op_pose_scores(const float* d_scores_in, const int32_t* d_counts, int
  * state-dict names with BN already folded to (scale, shift) by the Python host; activations,
  * workspaces and outputs live in named device buffers owned by the engine. */
 typedef struct isegmi_engine isegmi_engine;
-/* model_kind: 1 = Yolact R50-FPN, 2 = Mask R-CNN R50/R101-FPN, 3 = Pose2Seg (H = W = 512), 4 = RetinaNet R50/R101-FPN, 5 = YOLOv3 (Darknet-53).  H, W = network
- * input size. */
+/* model_kind: 1 = Yolact R50-FPN, 2 = Mask R-CNN R50/R101-FPN, 3 = Pose2Seg (H = W = 512), 4 = RetinaNet R50/R101-FPN, 5 = YOLOv3 (Darknet-53),
+ * 7 = ViT classifier (6 is not assigned and is refused).  H, W = network input size. */
 int isegmi_engine_create(int model_kind, int max_batch, int H, int W, isegmi_engine** out);
 int isegmi_engine_destroy(isegmi_engine* e);
 int isegmi_engine_set_param(isegmi_engine* e, const char* name, float value);
@@ -622,6 +645,15 @@ int isegmi_retinanet_forward_canvas(isegmi_engine* e, const float* d_images_nhwc
  * yolo_pre_nms_top_n (1024, 1..1024), yolo_multi_label (1), yolo_min_wh (0), detections_per_img, detections_cap, nms_ge / nms_plus_one (0 here) /
  * nms_index_order.  fp32 only: "fp16" and "graph" are refused by name. */
 int isegmi_yolov3_forward(isegmi_engine* e, const float* d_images_nhwc3, int N);
+/* ViT classifier (model_kind 7; [UPSTREAM-RECALL] Dosovitskiy et al. in the timm layout, unverified): d_images NHWC3 fp32 [N][H][W][3],
+ * normalised.  patchify -> patch_embed.proj (1x1 over P * P * 3, + position embedding) -> depth pre-LN blocks (LayerNorm, qkv, isegmi_op_attention,
+ * proj + x, LayerNorm, fc1, GELU, fc2 + x) -> LayerNorm of the class tokens -> head -> isegmi_op_class_softmax -> isegmi_op_topk.  Layers by set_conv
+ * (bias as shift): patch_embed.proj, blocks.<i>.attn.qkv / .attn.proj / .mlp.fc1 / .mlp.fc2, head; tensors by set_tensor: blocks.<i>.norm1 / .norm2 and
+ * norm (.weight, .bias), vit.cls_row [D] = cls_token + pos_embed[0], vit.pos_rows [max_batch][T - 1][D] = pos_embed[1:] tiled.  Params: vit_dim,
+ * vit_depth, vit_heads (vit_dim = 64 vit_heads), vit_mlp_dim, vit_patch (16 or 32), vit_num_classes (2..8192), vit_ln_eps (1e-6), vit_gelu_tanh (0),
+ * vit_topk (5, 1..64).  Results: cls.logits / cls.prob [N][classes], cls.topk_val (probabilities) / cls.topk_idx [N][k]; vit.tokens, vit.qkv, vit.attn,
+ * vit.mlp hold the embedding and the last block's tensors.  fp32 only: "fp16" and "graph" are refused by name. */
+int isegmi_vit_forward(isegmi_engine* e, const float* d_images_nhwc3, int N);
 /* Masker paste of the last forward into (out_h,out_w) planes; boxes first scaled by h_ratios_wh [N][2] =
  * (out_w/w_i, out_h/h_i) like BoxList.resize -> det.masks u8 [N][cap][out_h][out_w], det.box_resized */
 int isegmi_maskrcnn_paste(isegmi_engine* e, const float* h_ratios_wh, int out_h, int out_w);

@@ -59,6 +59,56 @@ __device__ __forceinline__ float dm_tanh(float x) {
     return fmaf(t, x, x);
 }
 
+// erf: the Cephes single-precision erff / erfcf (ndtrf.c).  Unlike the functions above, every multiplication and addition here is rounded on its
+// own (no fmaf; the file is compiled with -ffp-contract=off): tests/vit_ref.py restates the sequence in numpy, which has no fused operation, and the
+// two agree bit for bit.  |x| <= 1: x * T(x^2).  |x| > 1: 1 - erfc(|x|) with erfc = exp(-x^2) * (1 / x) * P or R(1 / x^2), sign restored; past
+// x^2 > 88.7228 (Cephes' MAXLOGF) erfc is 0.  NaN in, NaN out.
+__device__ __forceinline__ float dm_erf(float x) {
+    const float a = fabsf(x);
+    if (!(a > 1.0f)) {
+        const float z = x * x;
+        float p = 7.853861353153693E-5f;
+        p = p * z + -8.010193625184903E-4f;
+        p = p * z + 5.188327685732524E-3f;
+        p = p * z + -2.685381193529856E-2f;
+        p = p * z + 1.128358514861418E-1f;
+        p = p * z + -3.761262582423300E-1f;
+        p = p * z + 1.128379165726710E+0f;
+        return x * p;
+    }
+    float y = 0.0f;
+    const float z = -(a * a);
+    if (!(z < -88.72283905206835f)) {
+        const float e = dm_exp(z);
+        const float q = dm_div(1.0f, a);
+        const float w = q * q;
+        float p;
+        if (a < 2.0f) {
+            p = 2.326819970068386E-2f;
+            p = p * w + -1.387039388740657E-1f;
+            p = p * w + 3.687424674597105E-1f;
+            p = p * w + -5.824733027278666E-1f;
+            p = p * w + 6.210004621745983E-1f;
+            p = p * w + -4.944515323274145E-1f;
+            p = p * w + 3.404879937665872E-1f;
+            p = p * w + -2.741127028184656E-1f;
+            p = p * w + 5.638259427386472E-1f;
+        } else {
+            p = -1.047766399936249E+1f;
+            p = p * w + 1.297719955372516E+1f;
+            p = p * w + -7.495518717768503E+0f;
+            p = p * w + 2.921019019210786E+0f;
+            p = p * w + -1.015265279202700E+0f;
+            p = p * w + 4.218463358204948E-1f;
+            p = p * w + -2.820767439740514E-1f;
+            p = p * w + 5.641895067754075E-1f;
+        }
+        y = (e * q) * p;
+    }
+    const float r = 1.0f - y;
+    return x < 0.0f ? -r : r;
+}
+
 // log2 of a positive normal float
 __device__ __forceinline__ float dm_log2(float x) {
     const unsigned b = __float_as_uint(x);

@@ -1,4 +1,4 @@
-// engine.h -- model engine: packed-weight registry, named activation buffers, per-model forward graphs (yolact.cpp, maskrcnn.cpp, pose2seg.cpp, retinanet.cpp, yolov3.cpp).
+// engine.h -- model engine: packed-weight registry, named activation buffers, per-model forward graphs (yolact.cpp, maskrcnn.cpp, pose2seg.cpp, retinanet.cpp, yolov3.cpp, vit.cpp).
 #pragma once
 #include "tail_launch.h"
 #include <stdarg.h>
@@ -52,7 +52,7 @@ struct StageTime {
 constexpr float STEP_OVERLAP_DEFAULT = 1.0f;
 
 struct Engine {
-    int kind = 0;  // 1 yolact, 2 maskrcnn, 3 pose2seg, 4 retinanet, 5 yolov3
+    int kind = 0;  // 1 yolact, 2 maskrcnn, 3 pose2seg, 4 retinanet, 5 yolov3, 7 vit (6 is refused)
     int max_batch = 0, H = 0, W = 0;       // H, W: the LARGEST network input (padded canvas) this engine serves
     int cur_H = 0, cur_W = 0;              // Mask R-CNN: padded canvas of the current forward (<= H, W; to_image_list pads each batch to its own size)
     int anchor_H = -1, anchor_W = -1;      // canvas the anchors.* buffers were generated for
@@ -140,6 +140,8 @@ struct Engine {
     // Yolact fp32 "lazy_coeffs": the forward runs only the loc|conf rows of the fused head and computes the mask coefficients of the kept detections on
     // the tail stream; columns [85 A, 117 A) of `headcat` then hold nothing until a fetch of that buffer asks for them (yolact_fill_coeff_columns).
     bool coeff_cols_valid = true;
+    // ViT (vit.cpp): the vit.tokens allocation whose class rows (row 0 of every image = vit.cls_row) are written; set_tensor clears it
+    const void* vit_cls_rows_in = nullptr;
     // timing
     bool timing = false;
     std::vector<StageTime> marks;
@@ -203,8 +205,9 @@ int eng_rpn_head_f16(Engine& e, const std::string& conv, const std::string& head
 int eng_stem_pool_f16(Engine& e, const std::string& layer, const Tensor& halo, int H, int W, const std::string& out_name, Tensor* out, bool* fused);
 int eng_conv_stem_f16(Engine& e, const std::string& layer, const Tensor& halo, int H, int W, const std::string& out_name, Tensor* out);
 // conv writing into a caller-provided strided destination (heads -> concatenated buffers, deconv parities)
+// (residual: contiguous [M][Cout], whatever the destination's strides)
 int eng_conv_into(Engine& e, const std::string& layer, const Tensor& in, int stride, int pad, int act, void* dst, int out_div,
-                  int64_t out_img_stride, int64_t out_pix_stride, bool out_f32 = false);
+                  int64_t out_img_stride, int64_t out_pix_stride, bool out_f32 = false, const float* residual = nullptr);
 void eng_mark(Engine& e, const char* name);
 // fork(k): side stream k waits for everything queued on the main stream so far; join(k): main waits for side k.
 int eng_fork(Engine& e, int k);
@@ -384,6 +387,13 @@ int yolact_coeff_index_launch(const int32_t* fin_idx, const int32_t* tk_idx, con
                               const CoeffLevels& lv, int32_t* rows, hipStream_t st);
 int yolact_coeff_rows_launch(const CoeffLevels& lv, int N, int Cin, int R, int S, int pad, const float* w_packed, const float* scale, const float* shift,
                              int A, int row0, int mask_dim, const int32_t* rows, const int32_t* count, int max_det, float* out, hipStream_t st);
+// csrc/vit_ops.hip (each header comment of include/isegmi.h states the contract)
+int vit_attention_launch(const float* qkv, int N, int T, int heads, float* out, hipStream_t st);
+int vit_layer_norm_launch(const float* x, int64_t rows, int D, int64_t x_stride, const float* gamma, const float* beta, float eps, float* out,
+                          int64_t out_stride, hipStream_t st);
+int vit_gelu_launch(const float* x, float* y, int64_t n, int gelu_tanh, hipStream_t st);
+int vit_patchify_launch(const float* in, int N, int H, int W, int P, float* out, hipStream_t st);
+int vit_softmax_launch(const float* x, int rows, int n, float* prob, hipStream_t st);
 int yolact_masks_launch(const float* proto, const float* coeffs, const float* boxes, const int* count, int N, int PH, int PW,
                         int mask_dim, int K, int h, int w, float* ws_lo, uint8_t* out_masks, int64_t* out_boxes, hipStream_t st,
                         const int* image_hw = nullptr, int* win = nullptr, bool clear = true, bool dense_lo = false);

@@ -169,6 +169,11 @@ SIGNATURES = {
     "isegmi_op_yolo_select_workspace": (L, [I, I, V, I, I, I]),
     "isegmi_op_yolo_select": (I, [I, I, V, V, V, V, I, I, I, F, I, F, I, I, V, L, V, V, V, V, V, V]),
     "isegmi_op_concat_up2x": (I, [V, I, I, I, I, V, I, V, V]),
+    "isegmi_op_attention": (I, [V, I, I, I, V, V]),
+    "isegmi_op_layer_norm": (I, [V, L, I, L, V, V, F, V, L, V]),
+    "isegmi_op_gelu": (I, [V, V, L, I, V]),
+    "isegmi_op_patchify": (I, [V, I, I, I, I, V, V]),
+    "isegmi_op_class_softmax": (I, [V, I, I, V, V]),
     "isegmi_rle_workspace": (I, [I, I, I, I, I, V, V, V, V, V, V]),
     "isegmi_op_rle_encode": (I, [V, V]),
     "isegmi_op_pose2seg_letterbox": (I, [V, V, I, I, V, V, I, I, V, V]),
@@ -191,6 +196,7 @@ SIGNATURES = {
     "isegmi_retinanet_forward": (I, [V, V, V, I]),
     "isegmi_retinanet_forward_canvas": (I, [V, V, V, I, I, I]),
     "isegmi_yolov3_forward": (I, [V, V, I]),
+    "isegmi_vit_forward": (I, [V, V, I]),
     "isegmi_maskrcnn_paste": (I, [V, V, I, I]),
     "isegmi_pose2seg_forward": (I, [V, V, V, V, V, I]),
     "isegmi_pose2seg_body": (I, [V, V, V, I]),

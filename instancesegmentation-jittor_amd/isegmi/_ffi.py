@@ -1178,3 +1178,59 @@ def coco_match(det_off, gt_off, iou_off, ious, det_area, gt_area, gt_crowd, gt_i
     for b in own:
         b.free()
     return out
+
+
+# ---- ViT operators (csrc/vit_ops.hip) on host arrays: tests and small inputs
+def attention(qkv, heads, pad_floats=0, pad_value=0.0):
+    """isegmi_op_attention of qkv [N, T, 3 * heads * 64] -> [N, T, heads * 64].  pad_floats: the device buffer is that much longer than the tensor and
+    the excess holds pad_value (a kernel that read past the last token would pick it up)."""
+    qkv = np.ascontiguousarray(qkv, np.float32)
+    N, T, C3 = qkv.shape
+    assert C3 == 3 * heads * 64, (qkv.shape, heads)
+    flat = np.concatenate([qkv.reshape(-1), np.full(int(pad_floats), pad_value, np.float32)])
+    dq = DeviceBuffer.from_numpy(flat); do = DeviceBuffer((N, T, heads * 64)).poison()
+    check(lib().isegmi_op_attention(dq.ptr, N, T, heads, do.ptr, None))
+    return do.numpy()
+
+
+def layer_norm(x, gamma, beta, eps=1e-6, inplace=False, rows=None, x_row_stride=None):
+    """isegmi_op_layer_norm of x [..., D].  rows / x_row_stride: only `rows` rows, x_row_stride floats apart, are normalised -> [rows, D] (the class-token
+    form; never in place)."""
+    x = np.ascontiguousarray(x, np.float32)
+    D = x.shape[-1]
+    dx = DeviceBuffer.from_numpy(x)
+    dg = DeviceBuffer.from_numpy(np.ascontiguousarray(gamma, np.float32)); db = DeviceBuffer.from_numpy(np.ascontiguousarray(beta, np.float32))
+    assert dg.shape == (D,) and db.shape == (D,), (dg.shape, db.shape, D)
+    if rows is None:
+        do = dx if inplace else DeviceBuffer(x.shape).poison()
+        check(lib().isegmi_op_layer_norm(dx.ptr, x.size // D, D, D, dg.ptr, db.ptr, float(eps), do.ptr, D, None))
+        return do.numpy()
+    assert (rows - 1) * x_row_stride + D <= x.size and not inplace
+    do = DeviceBuffer((rows, D)).poison()
+    check(lib().isegmi_op_layer_norm(dx.ptr, rows, D, int(x_row_stride), dg.ptr, db.ptr, float(eps), do.ptr, D, None))
+    return do.numpy()
+
+
+def gelu(x, gelu_tanh=False, inplace=False):
+    x = np.ascontiguousarray(x, np.float32)
+    dx = DeviceBuffer.from_numpy(x)
+    dy = dx if inplace else DeviceBuffer(x.shape).poison()
+    check(lib().isegmi_op_gelu(dx.ptr, dy.ptr, x.size, 1 if gelu_tanh else 0, None))
+    return dy.numpy()
+
+
+def patchify(x_nhwc3, P):
+    x = np.ascontiguousarray(x_nhwc3, np.float32)
+    N, H, W, c = x.shape
+    assert c == 3
+    dx = DeviceBuffer.from_numpy(x); do = DeviceBuffer((N, H // P, W // P, P * P * 3)).poison()
+    check(lib().isegmi_op_patchify(dx.ptr, N, H, W, P, do.ptr, None))
+    return do.numpy()
+
+
+def class_softmax(logits):
+    x = np.ascontiguousarray(logits, np.float32)
+    rows, n = x.shape
+    dx = DeviceBuffer.from_numpy(x); do = DeviceBuffer(x.shape).poison()
+    check(lib().isegmi_op_class_softmax(dx.ptr, rows, n, do.ptr, None))
+    return do.numpy()

@@ -6,6 +6,7 @@
   python -m isegmi.cli pose2seg_test --weights random --anno person_keypoints.json --image-root DIR [--output segm.json] [--batch-size 8]
   python -m isegmi.cli pose2seg_test --weights random --keypoint-config kp.yaml --keypoint-weights random|FILE --anno images.json --image-root DIR
   python -m isegmi.cli yolo_detect --cfg configs/yolov3.cfg --weights random|FILE.npz|FILE.weights --images DIR --output dets.json [--img-size 416]
+  python -m isegmi.cli vit_classify --model vit_b16 --weights random|FILE.npz --images DIR --topk 5 --output preds.json [--img-size 224] [--num-classes 1000]
   python -m isegmi.cli coco_eval --gt instances.json --dt results.json --iou-type segm|bbox|keypoints [--cat-ids ...] [--max-dets ...] [--out stats.json]
 
 eval, test_net, pose2seg_test and yolo_detect take an optional `--gt instances.json`: after writing their json they print the COCO AP / AR summary.
@@ -288,6 +289,42 @@ def cmd_yolo_detect(a):
     return results
 
 
+def vit_config(a):
+    """The ViTConfig of a vit_classify command line."""
+    from .vit import ViTConfig
+    return ViTConfig.named(a.model, num_classes=a.num_classes, topk=a.topk, gelu_tanh=bool(a.gelu_tanh), ln_eps=a.ln_eps).validate(a.img_size, a.img_size)
+
+
+def cmd_vit_classify(a):
+    """ViT classification over a directory of images -> json: one entry per image with its top-k labels and probabilities."""
+    from .vit import ViTClassifier
+    from .weights import vit_random_state_dict
+    _, world, local = _rank_world()
+    if world > 1:
+        raise SystemExit("vit_classify: WORLD_SIZE=%d: multi-rank inference (world > 1) is not built for ViT" % world)
+    cfg = vit_config(a)
+    if a.weights in ("", "random", None):
+        sd = vit_random_state_dict(cfg, 1234, a.img_size, a.img_size)
+    elif a.weights.endswith(".npz"):
+        sd = dict(np.load(a.weights))
+    else:
+        raise SystemExit("%s: --weights takes random or an .npz in the timm names (tools/import_pth.py --family %s writes one)" % (a.weights, a.model))
+    files = sorted(os.path.join(a.images, f) for f in os.listdir(a.images))
+    clf = ViTClassifier(sd, cfg, a.img_size, a.img_size, max_batch=a.batch_size, device=local)
+    results = []
+    try:
+        for i0 in range(0, len(files), a.batch_size):
+            chunk = files[i0:i0 + a.batch_size]
+            for f, (labels, probs) in zip(chunk, clf.classify([_load_image_bgr(f) for f in chunk])):
+                results.append({"file": os.path.basename(f), "labels": [int(v) for v in labels], "probabilities": [float(v) for v in probs]})
+    finally:
+        clf.close()
+    with open(a.output, "w") as f:
+        json.dump(results, f)
+    print("wrote the top-%d classes of %d images to %s" % (cfg.topk, len(files), a.output))
+    return results
+
+
 def _print_coco_summary(gt_path, results, iou_types, cat_ids=None, max_dets=None):
     """The COCO summary of a result list against an annotation file, as the reference's test commands print it."""
     from .cocoeval import evaluate_results
@@ -353,6 +390,17 @@ def build_parser():
     y.add_argument("--batch-size", dest="batch_size", type=int, default=8)
     for q in (e, t, p, y):
         q.add_argument("--gt", default=None, help="COCO annotation json: print the COCO AP / AR summary of the written results (isegmi.cocoeval)")
+    v = sub.add_parser("vit_classify", help="ViT classification over a directory of images -> json of top-k labels and probabilities")
+    v.add_argument("--model", default="vit_b16", choices=["vit_ti16", "vit_s16", "vit_b16", "vit_b32", "vit_l16"])
+    v.add_argument("--weights", default="random", help="random (seeded synthetic weights) or FILE.npz in the timm names")
+    v.add_argument("--images", required=True, help="directory of images, classified in sorted order")
+    v.add_argument("--topk", type=int, default=5)
+    v.add_argument("--num-classes", dest="num_classes", type=int, default=1000)
+    v.add_argument("--img-size", dest="img_size", type=int, default=224, help="canvas side: a multiple of the patch size; the position embedding is not interpolated")
+    v.add_argument("--gelu-tanh", dest="gelu_tanh", type=int, default=0, choices=[0, 1], help="1: the tanh GELU of the original JAX release")
+    v.add_argument("--ln-eps", dest="ln_eps", type=float, default=1e-6)
+    v.add_argument("--output", default="preds.json")
+    v.add_argument("--batch-size", dest="batch_size", type=int, default=8)
     c = sub.add_parser("coco_eval", help="COCO AP / AR of a result json against an annotation json (pycocotools COCOeval restated)")
     c.add_argument("--gt", required=True, help="COCO annotation json")
     c.add_argument("--dt", required=True, help="COCO result json")
@@ -366,7 +414,7 @@ def build_parser():
 def main(argv=None):
     a = build_parser().parse_args(argv)
     return {"eval": cmd_eval, "test_net": cmd_test_net, "pose2seg_test": cmd_pose2seg_test, "yolo_detect": cmd_yolo_detect,
-            "coco_eval": cmd_coco_eval}[a.cmd](a)
+            "vit_classify": cmd_vit_classify, "coco_eval": cmd_coco_eval}[a.cmd](a)
 
 
 if __name__ == "__main__":

@@ -579,3 +579,38 @@ def pose2seg_state_dict(seed=1234, cat_skeleton=True, width=64, blocks=(3, 4, 6,
     _conv_bias(rng, sd, "segnet.conv_out", 2, cin, 1, bias_std=0.1)
     sd["pose_templates"] = pose_templates()
     return sd
+
+
+def vit_random_state_dict(cfg, seed=1234, H=224, W=224):
+    """Seeded random ViT weights in the timm names (isegmi.vit.ViTConfig): linear layers N(0, 1 / fan_in) (the blocks' output projections damped so the
+    residual stream stays O(1) over the depth), LayerNorm weight U(0.5, 1.5) / bias N(0, 0.1), class token and position embedding N(0, 0.02^2) as
+    published, the head with a gain that spreads the class probabilities."""
+    rng = np.random.default_rng(seed)
+    D, T = cfg.dim, cfg.tokens(H, W)
+
+    def f(a):
+        return np.asarray(a, np.float32)
+
+    def linear(name, cout, cin, gain=1.0):
+        sd[name + ".weight"] = f(rng.standard_normal((cout, cin)) * (gain / np.sqrt(cin)))
+        sd[name + ".bias"] = f(rng.standard_normal(cout) * 0.02)
+
+    def norm(name):
+        sd[name + ".weight"] = f(rng.uniform(0.5, 1.5, D))
+        sd[name + ".bias"] = f(rng.standard_normal(D) * 0.1)
+
+    sd = {"cls_token": f(rng.standard_normal((1, 1, D)) * 0.02), "pos_embed": f(rng.standard_normal((1, T, D)) * 0.02)}
+    k = 3 * cfg.patch * cfg.patch
+    sd["patch_embed.proj.weight"] = f(rng.standard_normal((D, 3, cfg.patch, cfg.patch)) / np.sqrt(k))
+    sd["patch_embed.proj.bias"] = f(rng.standard_normal(D) * 0.02)
+    for i in range(cfg.depth):
+        b = "blocks.%d." % i
+        norm(b + "norm1")
+        linear(b + "attn.qkv", 3 * D, D, 2.0)   # q, k of unit-ish variance: scores that spread over a few units, a softmax that is not flat
+        linear(b + "attn.proj", D, D, 0.5)
+        norm(b + "norm2")
+        linear(b + "mlp.fc1", cfg.mlp_dim, D)
+        linear(b + "mlp.fc2", D, cfg.mlp_dim, 0.5)
+    norm("norm")
+    linear("head", cfg.num_classes, D, 2.0)
+    return sd

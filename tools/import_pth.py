@@ -4,7 +4,8 @@ upstream key names isegmi.yolact.Yolact / isegmi.maskrcnn.MaskRCNN consume.
     python tools/import_pth.py IN OUT.npz [--family maskrcnn_r50_fpn|maskrcnn_r101_fpn|maskrcnn_r50_c4|maskrcnn_r50_fpn_gn|yolact_resnet50|yolact_base|
                                                     yolact_im700|yolact_darknet53|yolact_plus_resnet50|yolact_plus_base|retinanet_r50_fpn|retinanet_r101_fpn|
                                                     fasterrcnn_r50_fpn|fasterrcnn_r101_fpn|fasterrcnn_r50_c4|fasterrcnn_r50_fpn_gn|
-                                                    keypointrcnn_r50_fpn|keypointrcnn_r101_fpn|maskrcnn_x101_fpn|fasterrcnn_x101_fpn|retinanet_x101_fpn]
+                                                    keypointrcnn_r50_fpn|keypointrcnn_r101_fpn|maskrcnn_x101_fpn|fasterrcnn_x101_fpn|retinanet_x101_fpn|
+                                                    vit_ti16|vit_s16|vit_b16|vit_b32|vit_l16]
 
 Accepted inputs (torch is used HERE only to unpickle -- a tool, not the product):
   * dbolya/yolact `.pth` (the tables at README.md:209-221): a flat state dict; `module.` prefixes, `num_batches_tracked`, the
@@ -35,13 +36,18 @@ sys.path[:0] = [os.path.join(ROOT, "instancesegmentation-jittor_amd")]
 FAMILIES = ("maskrcnn_r50_fpn", "maskrcnn_r101_fpn", "maskrcnn_r50_c4", "maskrcnn_r50_fpn_gn", "yolact_resnet50", "yolact_base", "yolact_im700",
             "yolact_darknet53", "yolact_plus_resnet50", "yolact_plus_base", "retinanet_r50_fpn", "retinanet_r101_fpn",
             "fasterrcnn_r50_fpn", "fasterrcnn_r101_fpn", "fasterrcnn_r50_c4", "fasterrcnn_r50_fpn_gn",
-            "keypointrcnn_r50_fpn", "keypointrcnn_r101_fpn", "maskrcnn_x101_fpn", "fasterrcnn_x101_fpn", "retinanet_x101_fpn")
+            "keypointrcnn_r50_fpn", "keypointrcnn_r101_fpn", "maskrcnn_x101_fpn", "fasterrcnn_x101_fpn", "retinanet_x101_fpn",
+            "vit_ti16", "vit_s16", "vit_b16", "vit_b32", "vit_l16")
 
 
 def expected_keys(family):
     """The complete state-dict key set (and shapes) of a model family, from the synthetic generators."""
     from isegmi import weights as W
     from isegmi.yolact import YolactConfig
+    if family.startswith("vit_"):
+        # [UPSTREAM-RECALL] a timm-layout ViT checkpoint at 224 x 224 with 1000 classes (DESIGN.md 18); the Google .npz key mapping is not built
+        from isegmi.vit import ViTConfig
+        return {k: v.shape for k, v in W.vit_random_state_dict(ViTConfig.named(family), 0).items()}
     if family.endswith("_x101_fpn"):
         # [UPSTREAM-RECALL] *_X_101_32x8d_FPN_1x (DESIGN.md 16): the R-101 key sets with ResNeXt widths -- conv2 [width, width / 32, 3, 3], width = 256 << stage
         x = dict(groups=32, width_per_group=8)
