@@ -196,6 +196,19 @@ int isegmi_op_keypoint_decode(const float* d_heat, const float* d_boxes, const i
  * convolution over R*S*C channels with the layer's KRSC weights.  C % 4 == 0. */
 int isegmi_op_deform_im2col(const float* d_x, int N, int H, int W, int C, const float* d_offset_mask,
                             int R, int S, int stride, int pad, int dil, float* d_out, void* stream);
+/* the DCNv1 form of isegmi_op_deform_im2col (the `dconv` models of maskrcnn-benchmark's dcn/ configs): d_offset [N][Ho][Wo][2*R*S] holds the offsets
+ * alone (channel 2k = dy_k, 2k+1 = dx_k) and no mask factor is applied.  Equal, bit for bit, to the modulated entry fed a saturated mask logit. */
+int isegmi_op_deform_im2col_v1(const float* d_x, int N, int H, int W, int C, const float* d_offset,
+                               int R, int S, int stride, int pad, int dil, float* d_out, void* stream);
+/* Fused 3x3 deformable convolution, fp32 NHWC: pad 1, dilation 1, stride 1 or 2; the columns of isegmi_op_deform_im2col are sampled
+ * straight into the MFMA operand tile and never written.  d_om [N][Ho][Wo][OC] is the raw output of the offset convolution: modulated 1 (DCNv2), OC = 27,
+ * channel 2k = dy_k, 2k+1 = dx_k, 18+k = mask logit; modulated 0 (DCNv1), OC = 18.  d_w is the isegmi_pack_conv_weights image of the 1x1 descriptor over
+ * 9*C input channels ([Cout][3][3][C] weights), d_scale / d_shift / d_res optional, act 0 or 1.  The result d_out [N][Ho][Wo][Cout] is bit-identical to
+ * isegmi_op_deform_im2col (or _v1) followed by isegmi_op_conv2d as that 1x1: one chain per output, taps outermost, the C channels of a tap ascending.
+ * C % 32 == 0, 32 <= C <= 512, Cout % 4 == 0; anything else is ISEGMI_ERR_ARG and launches nothing.  N*Ho*Wo == 0 is a successful no-op. */
+int isegmi_op_deform_conv2d(const float* d_x, int N, int H, int W, int C, const float* d_om, int OC, int modulated, int stride,
+                            const float* d_w, int Cout, const float* d_scale, const float* d_shift, const float* d_res, int act, float* d_out,
+                            void* stream);
 /* out = lateral + nearest2x(coarse) (M3) */
 int isegmi_op_upsample_nearest2x_add(const float* d_coarse, int N, int Hc, int Wc, int C,
                                      const float* d_lateral, int H, int W, float* d_out,

@@ -370,8 +370,11 @@ int nearest2x_add_launch(const float* coarse, int N, int Hc, int Wc, int C, cons
 int maskiou_conv1_launch(const float* lo, int NK, int PH, int PW, const float* w, const float* b, float* out, hipStream_t st);
 int maskiou_rescore_launch(const float* feat, int N, int K, int HW, int C, const int* cls, const float* score, const int* count,
                            float* out, hipStream_t st);
-int deform_im2col_launch(const float* x, int N, int H, int W, int C, const float* om, int R, int S, int stride, int pad, int dil,
+int deform_im2col_launch(const float* x, int N, int H, int W, int C, const float* om, int R, int S, int stride, int pad, int dil, int modulated,
                          float* out, hipStream_t st);
+// fused 3x3 deformable convolution (csrc/deform_conv.hip): `w` is the isegmi_pack_conv_weights image of the 1x1 / 9*C descriptor
+int deform_conv2d_launch(const float* x, int N, int H, int W, int C, const float* om, int OC, int modulated, int stride, const float* w, int Cout,
+                         const float* scale, const float* shift, const float* res, int act, float* out, hipStream_t st);
 int pad_c3_c4_launch(const float* in, int64_t npix, float* out, hipStream_t st);
 int preprocess_u8_launch(const uint8_t* in, int N, int Hin, int Win, float* out, int Hout, int Wout, int Hpad, int Wpad, int64_t out_img_stride,
                          const float* mean3, const float* std3, int swap_rb, hipStream_t st);

@@ -61,15 +61,41 @@ int resnet_stem(Engine& e, const std::string& layer, const float* d_images, int 
     return ISEGMI_OK;
 }
 
-// conv2 of a block as DCNv2 (YOLACT++ backbones): offsets + mask logits from a plain 3x3 -> the nine taps sampled into columns ->
-// the deformable conv proper as a 1x1 over 9*C channels (weights handed over in KRSC order, bias folded into BN)
+// conv2 of a block as a deformable 3x3 (YOLACT++ backbones: DCNv2; the dcn/ R-CNN models: DCNv1 or DCNv2, told apart by the offset layer's 18 or 27
+// channels): offsets (+ mask logits) from a plain 3x3, then the deformable conv proper over the layer's 1x1 / 9*C weights (KRSC order, bias folded into
+// BN).  "dcn_fused" 1: ONE launch that samples into the MFMA operand tile (csrc/deform_conv.hip), no column buffer; 0: the nine taps sampled into
+// columns -> a 1x1 over 9*C channels.  The two forms agree bit for bit.  The default is 0 in every engine and at every stage: at 800 x 1344 the fused
+// launch measures 1.3-2.3 x the time of the two launches it replaces (tools/deform_conv_bench.py), so it stays opt-in.
 static int dcn_conv2(Engine& e, const std::string& nm, const std::string& blk, const Tensor& t1, int stride, const std::string& out_name, Tensor* t2) {
-    if (t1.dt) { set_error("the DCNv2 backbones run in fp32 only"); return ISEGMI_ERR_STATE; }
+    if (t1.dt) { set_error("the deformable-convolution backbones run in fp32 only (" + nm + ".conv2)"); return ISEGMI_ERR_STATE; }
     Tensor om, col;
     TRY(eng_conv(e, nm + ".conv2.conv_offset_mask", t1, stride, 1, 0, nullptr, blk + ".om", &om));
-    TRY(eng_act(e, blk + ".col", t1.N, om.H, om.W, 9 * t1.C, &col));
-    TRY(deform_im2col_launch((const float*)t1.d, t1.N, t1.H, t1.W, t1.C, (const float*)om.d, 3, 3, stride, 1, 1, (float*)col.d, e.cur));
-    return eng_conv(e, nm + ".conv2", col, 1, 0, 1, nullptr, out_name, t2);
+    if (om.C != 27 && om.C != 18) {
+        set_error("deformable conv " + nm + ".conv2.conv_offset_mask has " + std::to_string(om.C) + " output channels: 27 (modulated) or 18 (offsets only)");
+        return ISEGMI_ERR_ARG;
+    }
+    const int modulated = om.C == 27 ? 1 : 0;
+    const bool fused = e.param("dcn_fused", 0.0f) != 0.0f;
+    if (!fused) {
+        TRY(eng_act(e, blk + ".col", t1.N, om.H, om.W, 9 * t1.C, &col));
+        TRY(deform_im2col_launch((const float*)t1.d, t1.N, t1.H, t1.W, t1.C, (const float*)om.d, 3, 3, stride, 1, 1, modulated, (float*)col.d, e.cur));
+        return eng_conv(e, nm + ".conv2", col, 1, 0, 1, nullptr, out_name, t2);
+    }
+    const auto it = e.convs.find(nm + ".conv2");
+    if (it == e.convs.end()) { set_error("conv layer not set: " + nm + ".conv2"); return ISEGMI_ERR_STATE; }
+    const ConvLayer& L = it->second;
+    if (L.f16 || L.groups != 1 || L.R != 1 || L.S != 1 || L.Cin != 9 * t1.C) {
+        set_error("deformable conv " + nm + ".conv2: the weights must be the fp32 1x1 layer over 9 * " + std::to_string(t1.C) + " channels");
+        return ISEGMI_ERR_ARG;
+    }
+    TRY(eng_act(e, out_name, t1.N, om.H, om.W, L.Cout, t2));
+    const int M = t1.N * om.H * om.W;
+    ConvScope cs(e);
+    cs.trace(nm + ".conv2", " (deform fused)", t1.N, t1.H, t1.W, t1.C, L.Cout, 3, stride, M, false);
+    TRY(deform_conv2d_launch((const float*)t1.d, t1.N, t1.H, t1.W, t1.C, (const float*)om.d, om.C, modulated, stride, L.d_w, L.Cout, L.d_scale, L.d_shift,
+                             nullptr, 1, (float*)t2->d, e.cur));
+    cs.done(2.0 * M * 9.0 * t1.C * L.Cout, "%s (deform fused) [M=%d K=%d Cout=%d 3x3/%d]", (nm + ".conv2").c_str(), M, 9 * t1.C, L.Cout, stride);
+    return ISEGMI_OK;
 }
 
 int resnet_stage(Engine& e, const ResStage& s, const Tensor& in, Tensor* out) {
@@ -134,6 +160,7 @@ int resnet_stage(Engine& e, const ResStage& s, const Tensor& in, Tensor* out) {
             if (gn) { set_error("grouped convolution " + nm + ".conv2 with GroupNorm weights: ResNeXt bodies with GroupNorm are not built"); return ISEGMI_ERR_STATE; }
             if (t1.dt) { set_error("grouped convolution " + nm + ".conv2 in an fp16 engine: fp16 ResNeXt is not built"); return ISEGMI_ERR_STATE; }
         }
+        if (gn && e.convs.count(nm + ".conv2.conv_offset_mask")) { set_error("deformable conv " + nm + ".conv2 with GroupNorm weights: DCN bodies with GroupNorm are not built"); return ISEGMI_ERR_STATE; }
         if (e.convs.count(nm + ".conv2.conv_offset_mask")) TRY(dcn_conv2(e, nm, blk, t1, st2, sg + ".t2", &t2));
         else TRY(eng_conv(e, nm + ".conv2", t1, st2, 1, act, nullptr, sg + ".t2", &t2, false, /*may_split=*/s.full));
         if (gn) TRY(eng_gn(e, nm + ".conv2", &t2, nullptr, true));

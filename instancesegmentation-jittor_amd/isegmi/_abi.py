@@ -133,6 +133,8 @@ SIGNATURES = {
     "isegmi_op_keypoint_heatmap": (I, [V, L, I, I, I, V, V]),
     "isegmi_op_keypoint_decode": (I, [V, V, V, I, I, I, I, V, V, V]),
     "isegmi_op_deform_im2col": (I, [V, I, I, I, I, V, I, I, I, I, I, V, V]),
+    "isegmi_op_deform_im2col_v1": (I, [V, I, I, I, I, V, I, I, I, I, I, V, V]),
+    "isegmi_op_deform_conv2d": (I, [V, I, I, I, I, V, I, I, I, V, I, V, V, V, I, V, V]),
     "isegmi_op_upsample_nearest2x_add": (I, [V, I, I, I, I, V, I, I, V, V]),
     "isegmi_op_group_norm_workspace_bytes": (L, [L, I, I, I, I]),
     "isegmi_op_group_norm": (I, [V, L, I, I, I, I, V, V, F, V, I, V, V, L, V]),

@@ -360,6 +360,39 @@ def deform_im2col(x, om, R=3, S=3, stride=1, pad=1, dil=1):
     return do.numpy()
 
 
+def deform_im2col_v1(x, off, R=3, S=3, stride=1, pad=1, dil=1):
+    """x [N,H,W,C], off [N,Ho,Wo,2*R*S] raw offset-conv output -> DCNv1 columns [N,Ho,Wo,R*S*C] (no mask factor)."""
+    x = np.ascontiguousarray(x, np.float32); off = np.ascontiguousarray(off, np.float32)
+    N, H, W, Cc = x.shape
+    Ho = (H + 2 * pad - dil * (R - 1) - 1) // stride + 1; Wo = (W + 2 * pad - dil * (S - 1) - 1) // stride + 1
+    assert off.shape == (N, Ho, Wo, 2 * R * S), off.shape
+    dx = DeviceBuffer.from_numpy(x); dm = DeviceBuffer.from_numpy(off); do = DeviceBuffer((N, Ho, Wo, R * S * Cc))
+    check(lib().isegmi_op_deform_im2col_v1(dx.ptr, N, H, W, Cc, dm.ptr, R, S, stride, pad, dil, do.ptr, None))
+    return do.numpy()
+
+
+def deform_conv2d(x, om, w_krsc, stride=1, scale=None, shift=None, residual=None, act=0, launches=1):
+    """isegmi_op_deform_conv2d, host -> device -> host: x [N,H,W,C], om [N,Ho,Wo,27] (DCNv2) or [N,Ho,Wo,18] (DCNv1), w [Cout,3,3,C].  The weights go in
+    as the packed image of the 1x1 / 9*C descriptor.  launches > 1: the same launch again into the same (re-poisoned) buffer; the last result returns."""
+    x = np.ascontiguousarray(x, np.float32); om = np.ascontiguousarray(om, np.float32)
+    N, H, W, Cc = x.shape
+    Cout = w_krsc.shape[0]
+    Ho, Wo = (H - 1) // stride + 1 if H else 0, (W - 1) // stride + 1 if W else 0
+    OC = om.shape[-1]
+    d = make_conv_desc(max(N, 1), max(Ho, 1), max(Wo, 1), 9 * Cc, Cout, 1, 1)
+    dw = DeviceBuffer.from_numpy(pack_conv_weights(d, np.ascontiguousarray(w_krsc, np.float32).reshape(Cout, 1, 1, 9 * Cc)))
+    dx = DeviceBuffer.from_numpy(x); dm = DeviceBuffer.from_numpy(om)
+    ds = None if scale is None else DeviceBuffer.from_numpy(np.asarray(scale, np.float32))
+    dh = None if shift is None else DeviceBuffer.from_numpy(np.asarray(shift, np.float32))
+    dr = None if residual is None else DeviceBuffer.from_numpy(np.asarray(residual, np.float32))
+    do = DeviceBuffer((N, Ho, Wo, Cout))
+    for _ in range(launches):
+        do.poison()
+        check(lib().isegmi_op_deform_conv2d(dx.ptr, N, H, W, Cc, dm.ptr, OC, int(OC == 27), stride, dw.ptr, Cout, _ptr(ds), _ptr(dh), _ptr(dr), act,
+                                            do.ptr, None))
+    return do.numpy()
+
+
 def upsample_nearest2x_add(coarse, lateral):
     coarse = np.ascontiguousarray(coarse, np.float32); lateral = np.ascontiguousarray(lateral, np.float32)
     N, Hc, Wc, Cc = coarse.shape

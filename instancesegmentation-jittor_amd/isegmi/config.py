@@ -78,7 +78,9 @@ def _defaults():
                   # [UPSTREAM-RECALL] maskrcnn-benchmark defaults.py
                   "GROUP_NORM": {"DIM_PER_GP": -1, "NUM_GROUPS": 32, "EPSILON": 1e-5},
                   "RESNETS": {"TRANS_FUNC": "BottleneckWithFixedBatchNorm", "STEM_FUNC": "StemWithFixedBatchNorm", "STRIDE_IN_1X1": True,
-                              "RES5_DILATION": 1, "NUM_GROUPS": 1, "WIDTH_PER_GROUP": 64, "RES2_OUT_CHANNELS": 256, "STEM_OUT_CHANNELS": 64},
+                              "RES5_DILATION": 1, "NUM_GROUPS": 1, "WIDTH_PER_GROUP": 64, "RES2_OUT_CHANNELS": 256, "STEM_OUT_CHANNELS": 64,
+                              # [UPSTREAM-RECALL] maskrcnn-benchmark defaults.py: deformable convolutions
+                              "STAGE_WITH_DCN": (False, False, False, False), "WITH_MODULATED_DCN": False, "DEFORMABLE_GROUPS": 1},
                   "FPN": {"USE_GN": False, "USE_RELU": False},
                   "ROI_BOX_HEAD": {"FEATURE_EXTRACTOR": "FPN2MLPFeatureExtractor", "USE_GN": False, "NUM_STACKED_CONVS": 4, "CONV_HEAD_DIM": 256,
                                    "MLP_HEAD_DIM": 1024, "DILATION": 1, "NUM_CLASSES": 81},
@@ -122,6 +124,33 @@ def _resnext_config(c, body, gn_key=None):
         if str(body).endswith("-C4"):
             raise ValueError("MODEL.RESNETS.NUM_GROUPS=%d with MODEL.BACKBONE.CONV_BODY=%r: ResNeXt is built on the FPN bodies" % (groups, body))
     return groups, width
+
+
+def dcn_stages(c):
+    """[UPSTREAM-RECALL] MODEL.RESNETS.STAGE_WITH_DCN -> a 4-tuple of bools (res2..res5); raises, naming the key, for anything else."""
+    v = c.MODEL.RESNETS.get("STAGE_WITH_DCN", (False, False, False, False))
+    if isinstance(v, (str, bytes)) or not hasattr(v, "__len__") or len(v) != 4:
+        raise ValueError("MODEL.RESNETS.STAGE_WITH_DCN=%r: four flags, one per stage res2..res5" % (v,))
+    return tuple(_bool(x) for x in v)
+
+
+def _dcn_config(c, body, use_gn, num_groups):
+    """[UPSTREAM-RECALL] MODEL.RESNETS.STAGE_WITH_DCN / WITH_MODULATED_DCN / DEFORMABLE_GROUPS -> MaskRCNNConfig fields.  Built: conv2 of
+    every bottleneck of the flagged stages as DCNv1 or DCNv2 on the FrozenBN R-50-FPN / R-101-FPN bodies; everything else raises and names its key."""
+    rn = c.MODEL.RESNETS
+    stages = dcn_stages(c)
+    if int(rn.get("DEFORMABLE_GROUPS", 1)) != 1:
+        raise ValueError("MODEL.RESNETS.DEFORMABLE_GROUPS=%s: deformable convolutions are built with one offset group" % rn.DEFORMABLE_GROUPS)
+    if not any(stages):
+        return {}   # WITH_MODULATED_DCN without a deformable stage changes nothing upstream either
+    if use_gn:
+        raise ValueError("MODEL.RESNETS.STAGE_WITH_DCN=%r with GroupNorm (%s): deformable convolutions are built on the FrozenBN bodies" % (stages, use_gn))
+    if num_groups > 1:
+        raise ValueError("MODEL.RESNETS.STAGE_WITH_DCN=%r with MODEL.RESNETS.NUM_GROUPS=%d: deformable ResNeXt is not built" % (stages, num_groups))
+    if body not in ("R-50-FPN", "R-101-FPN"):
+        raise ValueError("MODEL.RESNETS.STAGE_WITH_DCN=%r with MODEL.BACKBONE.CONV_BODY=%r: deformable convolutions are built on R-50-FPN and R-101-FPN" %
+                         (stages, body))
+    return dict(STAGE_WITH_DCN=stages, WITH_MODULATED_DCN=_bool(rn.get("WITH_MODULATED_DCN", False)))
 
 
 def _norm_config(c, body, mask_on=True):
@@ -198,6 +227,8 @@ def _two_stage_config(c):
     norm = _norm_config(c, body, mask_on)
     if body not in ("R-50-FPN", "R-101-FPN", "R-50-C4"):
         raise ValueError("built bodies: R-50-FPN, R-101-FPN, R-50-C4 (got %r)" % body)
+    gn_key = "MODEL.RESNETS.TRANS_FUNC=BottleneckWithGN" if norm.get("USE_GN") else None
+    dcn = _dcn_config(c, body, gn_key, int(norm.get("NUM_GROUPS", 1)))
     for key, on in (("MODEL.RPN_ONLY", c.MODEL.get("RPN_ONLY", False)), ("TEST.BBOX_AUG.ENABLED", c.TEST.get("BBOX_AUG", {}).get("ENABLED", False))):
         if _bool(on):
             raise ValueError("%s=True is not built (DESIGN.md 13: RPN-only models and test-time box augmentation are out of scope)" % key)
@@ -227,7 +258,7 @@ def _two_stage_config(c):
                           RPN_PRE_NMS_TOP_N_TEST=int(r.PRE_NMS_TOP_N_TEST), RPN_POST_NMS_TOP_N_TEST=int(r.POST_NMS_TOP_N_TEST),
                           RPN_FPN_POST_NMS_TOP_N_TEST=int(r.FPN_POST_NMS_TOP_N_TEST), RPN_NMS_THRESH=float(r.NMS_THRESH),
                           RPN_MIN_SIZE=float(r.MIN_SIZE), ROI_SCORE_THRESH=float(h.SCORE_THRESH), ROI_NMS=float(h.NMS),
-                          DETECTIONS_PER_IMG=int(h.DETECTIONS_PER_IMG), **heads, **norm)
+                          DETECTIONS_PER_IMG=int(h.DETECTIONS_PER_IMG), **heads, **norm, **dcn)
 
 
 def is_keypoint_rcnn(c):
@@ -249,6 +280,8 @@ def to_keypointrcnn_config(c):
     body = str(m.BACKBONE.CONV_BODY)
     if body not in ("R-50-FPN", "R-101-FPN"):
         raise ValueError("MODEL.BACKBONE.CONV_BODY=%r with MODEL.KEYPOINT_ON: the keypoint head is built on R-50-FPN and R-101-FPN (it reads P2..P5)" % body)
+    if any(dcn_stages(c)):
+        raise ValueError("MODEL.RESNETS.STAGE_WITH_DCN=%r with MODEL.KEYPOINT_ON: Keypoint R-CNN with deformable convolutions is not built" % (dcn_stages(c),))
     mc = _two_stage_config(c)
     if mc.NUM_GROUPS > 1:
         raise ValueError("MODEL.RESNETS.NUM_GROUPS=%d with MODEL.KEYPOINT_ON: Keypoint R-CNN on ResNeXt is not built" % mc.NUM_GROUPS)
@@ -307,6 +340,10 @@ def to_retinanet_config(c):
     if _bool(m.FPN.USE_RELU):
         raise ValueError("MODEL.FPN.USE_RELU=True is not built")
     num_groups, width_per_group = _resnext_config(c, body)
+    if any(dcn_stages(c)):
+        raise ValueError("MODEL.RESNETS.STAGE_WITH_DCN=%r with MODEL.RETINANET_ON: RetinaNet with deformable convolutions is not built" % (dcn_stages(c),))
+    if int(rn.get("DEFORMABLE_GROUPS", 1)) != 1:
+        raise ValueError("MODEL.RESNETS.DEFORMABLE_GROUPS=%s: deformable convolutions are not built for RetinaNet" % rn.DEFORMABLE_GROUPS)
     if not _bool(rn.STRIDE_IN_1X1) and num_groups == 1:
         raise ValueError("MODEL.RESNETS.STRIDE_IN_1X1=False is built for the GroupNorm Mask R-CNN only")
     resnext = dict(NUM_GROUPS=num_groups, WIDTH_PER_GROUP=width_per_group, STRIDE_IN_1X1=_bool(rn.STRIDE_IN_1X1)) if num_groups > 1 else {}

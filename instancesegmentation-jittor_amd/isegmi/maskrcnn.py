@@ -75,6 +75,10 @@ class MaskRCNNConfig:
     # bottleneck width is NUM_GROUPS * WIDTH_PER_GROUP * 2^stage.  FrozenBN FPN bodies, fp32, no keypoint head.
     NUM_GROUPS: int = 1          # MODEL.RESNETS.NUM_GROUPS
     WIDTH_PER_GROUP: int = 64    # MODEL.RESNETS.WIDTH_PER_GROUP
+    # [UPSTREAM-RECALL] DESIGN.md 19.  Deformable trunks (dcn/e2e_*_dconv_* and *_mdconv_*): conv2 of every bottleneck of the flagged stages (res2..res5) is a
+    # deformable 3x3 -- DCNv1 (18 offsets) or, with WITH_MODULATED_DCN, DCNv2 (18 offsets + 9 mask logits).  FrozenBN FPN bodies, fp32, one offset group.
+    STAGE_WITH_DCN: tuple = (False, False, False, False)   # MODEL.RESNETS.STAGE_WITH_DCN
+    WITH_MODULATED_DCN: bool = False                       # MODEL.RESNETS.WITH_MODULATED_DCN
 
     @staticmethod
     def c4():
@@ -124,6 +128,22 @@ def resnext_refusals(cfg, fp16):
                      (getattr(cfg, "KEYPOINT_ON", False), "MODEL.KEYPOINT_ON: Keypoint R-CNN on ResNeXt is not built")):
         if bad:
             raise ValueError("MODEL.RESNETS.NUM_GROUPS=%d together with %s" % (cfg.NUM_GROUPS, why))
+
+
+def dcn_refusals(cfg, fp16):
+    """What a deformable trunk (any of STAGE_WITH_DCN) is not built next to; ValueError naming the key."""
+    stages = tuple(bool(v) for v in getattr(cfg, "STAGE_WITH_DCN", ()))
+    if not any(stages):
+        return
+    if len(stages) != 4:
+        raise ValueError("MODEL.RESNETS.STAGE_WITH_DCN=%r: four flags, one per stage res2..res5" % (stages,))
+    for bad, why in ((fp16, "fp16=True: the deformable convolution kernels are fp32 only"),
+                     (cfg.is_c4, "the C4 body (MODEL.BACKBONE.CONV_BODY %s): deformable convolutions are built on the FPN bodies" % cfg.CONV_BODY),
+                     (getattr(cfg, "USE_GN", False), "GroupNorm (USE_GN): deformable convolutions are built on the FrozenBN bodies"),
+                     (getattr(cfg, "NUM_GROUPS", 1) > 1, "MODEL.RESNETS.NUM_GROUPS > 1: deformable ResNeXt is not built"),
+                     (getattr(cfg, "KEYPOINT_ON", False), "MODEL.KEYPOINT_ON: Keypoint R-CNN with deformable convolutions is not built")):
+        if bad:
+            raise ValueError("MODEL.RESNETS.STAGE_WITH_DCN=%r together with %s" % (stages, why))
 
 
 GN_TILE_CHANNELS = 64   # csrc/groupnorm.hip GN_TILE_C
@@ -319,6 +339,7 @@ class MaskRCNN(Engine):
         if not 2 <= int(cfg.NUM_CLASSES) <= 257:
             raise ValueError("MODEL.ROI_BOX_HEAD.NUM_CLASSES=%s: the box post-processing kernels hold 2..257 classes (background included)" % (cfg.NUM_CLASSES,))
         resnext_refusals(cfg, fp16)
+        dcn_refusals(cfg, fp16)
         if cfg.KEYPOINT_ON:   # what the keypoint head is built next to
             for bad, why in ((fp16, "fp16=True: the keypoint head is fp32 only"), (cfg.is_c4, "the C4 body (CONV_BODY %s): the keypoint head reads P2..P5" % cfg.CONV_BODY),
                              (cfg.USE_GN, "GroupNorm (USE_GN): the keypoint head is built on the FrozenBN bodies"),
@@ -450,6 +471,13 @@ class MaskRCNN(Engine):
         width = groups * width_per_group * 2^stage; ValueError naming the key otherwise -- and uploaded dense (groups 1) or grouped."""
         cfg = self.cfg
         groups, wpg = int(getattr(cfg, "NUM_GROUPS", 1)), int(getattr(cfg, "WIDTH_PER_GROUP", 64))
+        dcn = bool(tuple(getattr(cfg, "STAGE_WITH_DCN", ()) or (False,) * 4)[stage])
+        if dcn:
+            return self._set_dcn_conv2(sd, src, dst, stage)
+        for k in (".conv2.offset.weight", ".conv2.conv.weight"):
+            if src + k in sd:
+                raise ValueError("%s%s: a deformable convolution in res%d, which MODEL.RESNETS.STAGE_WITH_DCN=%r says is plain"
+                                 % (src, k, stage + 2, tuple(getattr(cfg, "STAGE_WITH_DCN", (False,) * 4))))
         key = src + ".conv2.weight"
         w = np.asarray(sd[key])
         width = (groups * wpg) << stage
@@ -463,6 +491,33 @@ class MaskRCNN(Engine):
         if groups == 1:
             return self._set_conv_krsc(dst + ".conv2", to_krsc(w), scale, shift)
         self._set_conv_grouped(dst + ".conv2", to_krsc(w), groups, scale, shift)   # [width, 3, 3, width / groups]
+
+    def _set_dcn_conv2(self, sd, src, dst, stage):
+        """[UPSTREAM-RECALL] maskrcnn-benchmark DFConv2d as conv2 of bottleneck `src`: <src>.conv2.offset.{weight, bias} (a plain 3x3 with 18 outputs, or 27
+        with WITH_MODULATED_DCN) goes in as the engine layer <dst>.conv2.conv_offset_mask with the bias as shift; <src>.conv2.conv.weight [width, width, 3, 3]
+        as the 1x1 layer <dst>.conv2 over 9 * width channels in KRSC order with bn2 folded (what the YOLACT++ loader does).  ValueError naming the key."""
+        cfg = self.cfg
+        width = 64 << stage
+        mod = bool(cfg.WITH_MODULATED_DCN)
+        if src + ".conv2.weight" in sd:
+            raise ValueError("%s.conv2.weight: a plain convolution in res%d, which MODEL.RESNETS.STAGE_WITH_DCN=%r says is deformable"
+                             % (src, stage + 2, tuple(cfg.STAGE_WITH_DCN)))
+        for k in (".conv2.offset.weight", ".conv2.offset.bias", ".conv2.conv.weight"):
+            if src + k not in sd:
+                raise ValueError("%s%s is missing: MODEL.RESNETS.STAGE_WITH_DCN=%r makes conv2 of res%d deformable" % (src, k, tuple(cfg.STAGE_WITH_DCN), stage + 2))
+        wo, bo, w = np.asarray(sd[src + ".conv2.offset.weight"]), np.asarray(sd[src + ".conv2.offset.bias"]), np.asarray(sd[src + ".conv2.conv.weight"])
+        oc = 27 if mod else 18
+        if wo.shape != (oc, width, 3, 3) or bo.shape != (oc,):
+            raise ValueError("%s.conv2.offset.weight %s / bias %s: MODEL.RESNETS.WITH_MODULATED_DCN=%s needs (%d, %d, 3, 3) and (%d,)"
+                             % (src, tuple(wo.shape), tuple(bo.shape), mod, oc, width, oc))
+        if w.shape != (width, width, 3, 3):
+            raise ValueError("%s.conv2.conv.weight %s: expected (%d, %d, 3, 3) in res%d (MODEL.RESNETS.DEFORMABLE_GROUPS 1, NUM_GROUPS 1)"
+                             % (src, tuple(w.shape), width, width, stage + 2))
+        if src + ".conv2.conv.bias" in sd:
+            raise ValueError("%s.conv2.conv.bias: the deformable conv2 of a bottleneck has no bias" % src)
+        scale, shift = fold_frozen_batchnorm(sd, src + ".bn2", cfg.FROZEN_BN_EPS)
+        self._set_conv_krsc(dst + ".conv2.conv_offset_mask", to_krsc(wo), None, bo)
+        self._set_conv_krsc(dst + ".conv2", to_krsc(w).reshape(width, 1, 1, 9 * width), scale, shift)
 
     def _load(self, sd):
         cfg = self.cfg

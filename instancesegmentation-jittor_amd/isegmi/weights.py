@@ -356,10 +356,19 @@ def maskrcnn_gn_state_dict(seed=1234, depth=50, stacked_convs=4, conv_head_dim=2
     return sd if mask else _drop_mask_head(sd)
 
 
-def maskrcnn_state_dict(seed=1234, depth=50, gn=False, mask=True, num_classes=81, cls_agnostic=False, groups=1, width_per_group=64):
+def maskrcnn_state_dict(seed=1234, depth=50, gn=False, mask=True, num_classes=81, cls_agnostic=False, groups=1, width_per_group=64,
+                        stage_with_dcn=(0, 0, 0, 0), modulated=False):
     """maskrcnn-benchmark e2e_mask_rcnn_R_50/101_FPN state-dict names; gn=True: the GroupNorm model (maskrcnn_gn_state_dict).
     mask=False: the e2e_faster_rcnn_* key set (no roi_heads.mask.*); num_classes / cls_agnostic size the predictors.
-    groups / width_per_group: the ResNeXt trunks (e2e_*_X_101_32x8d_FPN_1x: 32, 8); the defaults are the ResNet dicts, bit for bit."""
+    groups / width_per_group: the ResNeXt trunks (e2e_*_X_101_32x8d_FPN_1x: 32, 8); the defaults are the ResNet dicts, bit for bit.
+    stage_with_dcn / modulated: [UPSTREAM-RECALL] the dcn/ models (DFConv2d names): in the flagged stages res2..res5, <block>.conv2.weight becomes
+    <block>.conv2.conv.weight and <block>.conv2.offset.{weight, bias} (18 outputs, 27 when modulated) is added, drawn from a SEPARATE generator so that
+    every other tensor equals the plain dict's, bit for bit."""
+    dcn = tuple(bool(v) for v in stage_with_dcn)
+    if len(dcn) != 4:
+        raise ValueError("maskrcnn_state_dict: stage_with_dcn takes four flags (res2..res5)")
+    if any(dcn) and (gn or groups != 1):
+        raise ValueError("maskrcnn_state_dict: deformable stages with gn=True or groups > 1 are not built")
     if gn and groups != 1:
         raise ValueError("maskrcnn_state_dict: groups > 1 (ResNeXt) with gn=True is not built")
     if gn:
@@ -397,6 +406,19 @@ def maskrcnn_state_dict(seed=1234, depth=50, gn=False, mask=True, num_classes=81
     sd["roi_heads.mask.predictor.conv5_mask.weight"] = (rng.standard_normal((256, 256, 2, 2)) * np.sqrt(2.0 / 256)).astype(np.float32)
     sd["roi_heads.mask.predictor.conv5_mask.bias"] = (rng.standard_normal(256) * 0.01).astype(np.float32)
     _conv_bias(rng, sd, "roi_heads.mask.predictor.mask_fcn_logits", ncls, 256, 1, gain=MRCNN_MASK_LOGIT_GAIN)
+    if any(dcn):
+        drng = np.random.default_rng([int(seed), 0xDC2])   # the deformable layers' own stream: the draws above are the plain dict's
+        oc = 27 if modulated else 18
+        for li, nb in enumerate(blocks, 1):
+            if not dcn[li - 1]:
+                continue
+            planes = 64 << (li - 1)
+            for b in range(nb):
+                nm = "backbone.body.layer%d.%d.conv2" % (li, b)
+                sd[nm + ".conv.weight"] = sd.pop(nm + ".weight")
+                # conv1 outputs (post BN + ReLU) are O(1): offsets of about +-1 pixel, mask logits around 0 (as YOLACT_DCN_OFFSET_STD)
+                sd[nm + ".offset.weight"] = (drng.standard_normal((oc, planes, 3, 3)) * (YOLACT_DCN_OFFSET_STD / np.sqrt(9.0 * planes))).astype(np.float32)
+                sd[nm + ".offset.bias"] = (drng.standard_normal(oc) * 0.1).astype(np.float32)
     return sd if mask else _drop_mask_head(sd)
 
 
@@ -520,7 +542,8 @@ def random_maskrcnn_state_dict(cfg, seed=1234):
         return maskrcnn_c4_state_dict(seed, **kw)
     if cfg.USE_GN:
         return maskrcnn_gn_state_dict(seed, cfg.depth, cfg.BOX_HEAD_STACKED_CONVS, cfg.BOX_HEAD_CONV_DIM, cfg.BOX_HEAD_MLP_DIM, **kw)
-    return maskrcnn_state_dict(seed, cfg.depth, groups=int(getattr(cfg, "NUM_GROUPS", 1)), width_per_group=int(getattr(cfg, "WIDTH_PER_GROUP", 64)), **kw)
+    return maskrcnn_state_dict(seed, cfg.depth, groups=int(getattr(cfg, "NUM_GROUPS", 1)), width_per_group=int(getattr(cfg, "WIDTH_PER_GROUP", 64)),
+                               stage_with_dcn=tuple(getattr(cfg, "STAGE_WITH_DCN", (0, 0, 0, 0))), modulated=bool(getattr(cfg, "WITH_MODULATED_DCN", False)), **kw)
 
 
 # Synthetic pose templates in the 64 x 64 align frame, COCO keypoint order (nose, eyes, ears, shoulders, elbows, wrists, hips, knees,

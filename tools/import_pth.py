@@ -5,7 +5,8 @@ upstream key names isegmi.yolact.Yolact / isegmi.maskrcnn.MaskRCNN consume.
                                                     yolact_im700|yolact_darknet53|yolact_plus_resnet50|yolact_plus_base|retinanet_r50_fpn|retinanet_r101_fpn|
                                                     fasterrcnn_r50_fpn|fasterrcnn_r101_fpn|fasterrcnn_r50_c4|fasterrcnn_r50_fpn_gn|
                                                     keypointrcnn_r50_fpn|keypointrcnn_r101_fpn|maskrcnn_x101_fpn|fasterrcnn_x101_fpn|retinanet_x101_fpn|
-                                                    vit_ti16|vit_s16|vit_b16|vit_b32|vit_l16]
+                                                    vit_ti16|vit_s16|vit_b16|vit_b32|vit_l16|
+                                                    maskrcnn_dconv_r50_fpn|maskrcnn_mdconv_r50_fpn|fasterrcnn_dconv_r50_fpn|fasterrcnn_mdconv_r50_fpn]
 
 Accepted inputs (torch is used HERE only to unpickle -- a tool, not the product):
   * dbolya/yolact `.pth` (the tables at README.md:209-221): a flat state dict; `module.` prefixes, `num_batches_tracked`, the
@@ -37,7 +38,8 @@ FAMILIES = ("maskrcnn_r50_fpn", "maskrcnn_r101_fpn", "maskrcnn_r50_c4", "maskrcn
             "yolact_darknet53", "yolact_plus_resnet50", "yolact_plus_base", "retinanet_r50_fpn", "retinanet_r101_fpn",
             "fasterrcnn_r50_fpn", "fasterrcnn_r101_fpn", "fasterrcnn_r50_c4", "fasterrcnn_r50_fpn_gn",
             "keypointrcnn_r50_fpn", "keypointrcnn_r101_fpn", "maskrcnn_x101_fpn", "fasterrcnn_x101_fpn", "retinanet_x101_fpn",
-            "vit_ti16", "vit_s16", "vit_b16", "vit_b32", "vit_l16")
+            "vit_ti16", "vit_s16", "vit_b16", "vit_b32", "vit_l16",
+            "maskrcnn_dconv_r50_fpn", "maskrcnn_mdconv_r50_fpn", "fasterrcnn_dconv_r50_fpn", "fasterrcnn_mdconv_r50_fpn")
 
 
 def expected_keys(family):
@@ -48,7 +50,11 @@ def expected_keys(family):
         # [UPSTREAM-RECALL] a timm-layout ViT checkpoint at 224 x 224 with 1000 classes; the Google .npz key mapping is not built
         from isegmi.vit import ViTConfig
         return {k: v.shape for k, v in W.vit_random_state_dict(ViTConfig.named(family), 0).items()}
-    if family.endswith("_x101_fpn"):
+    if "dconv_" in family:
+        # [UPSTREAM-RECALL] dcn/e2e_{mask,faster}_rcnn_{dconv,mdconv}_R_50_FPN_1x: the R-50 key sets with conv2 of res3..res5 as DFConv2d --
+        # conv2.offset.{weight, bias} (18 outputs, 27 for mdconv) and conv2.conv.weight in place of conv2.weight
+        sd = W.maskrcnn_state_dict(0, 50, mask=family.startswith("maskrcnn_"), stage_with_dcn=(0, 1, 1, 1), modulated="_mdconv_" in family)
+    elif family.endswith("_x101_fpn"):
         # [UPSTREAM-RECALL] *_X_101_32x8d_FPN_1x: the R-101 key sets with ResNeXt widths -- conv2 [width, width / 32, 3, 3], width = 256 << stage
         x = dict(groups=32, width_per_group=8)
         sd = {"maskrcnn_x101_fpn": lambda: W.maskrcnn_state_dict(0, 101, **x), "fasterrcnn_x101_fpn": lambda: W.maskrcnn_state_dict(0, 101, mask=False, **x),
