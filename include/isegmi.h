@@ -284,6 +284,24 @@ typedef struct isegmi_yolact_detect_args {
     int32_t off_loc, off_conf, off_mask;
     int32_t second_threshold;   /* App. A.6 fork, fast_nms(second_threshold=True): a box must also have its class score > conf_thresh (a prior passes
                                    the pre-filter on its BEST class and is ranked in every class); 0 = the default detect() call */
+    /* suppression rule (every field from here on may stay zero: nms_mode 0 is the path above, launch for launch).
+     *   1  cross-class fast NMS (upstream cc_fast_nms): score = max_c prob[c], class = the lowest c attaining it, ONE top_k and one fast-NMS pass per image;
+     *      the survivors are cut to the best max_det.  Needs d_ws_cc_scores / d_ws_cc_class; d_ws_tk_* and d_ws_cand are used as [N][top_k].
+     *   2  traditional NMS (upstream traditional_nms + cython_nms): per class the priors with prob[c] > conf_thresh in (score desc, prior asc) order,
+     *      greedy, boxes * trad_scale, legacy +1 areas, suppress on ovr >= nms_thresh; at most trad_cap candidates per (image, class) are visited.
+     *      d_ws_tk_vals / d_ws_tk_idx are then [N][ncls-1][trad_cap] and d_ws_cand [N][ncls-1][128] (a class's first 128 survivors: no later one can
+     *      enter the cut, max_det <= 128); top_k is not used.  Needs d_ws_trad_list and d_ws_trad_prior.
+     * second_threshold != 0 next to nms_mode 1 or 2 is refused. */
+    int32_t nms_mode;
+    int32_t trad_cap;            /* mode 2: a multiple of 64 in [64, 2048]; 0 = 1024 */
+    float trad_scale;            /* mode 2: upstream's cfg.max_size (> 0) */
+    int32_t* d_out_nms_total;    /* [N], optional, every mode: survivors of the suppression pass before the cut to max_det */
+    int32_t* d_out_nms_overflow; /* [N], optional: 1 iff (mode 2) some class of the image held more than trad_cap candidates AND fewer than max_det of
+                                    its first trad_cap survived -- the only case in which the cap can change the result; 0 in modes 0 and 1 */
+    float* d_ws_cc_scores;       /* mode 1: [N][P] */
+    int32_t* d_ws_cc_class;      /* mode 1: [N][P] */
+    int32_t* d_ws_trad_list;     /* mode 2: [1 + N*(ncls-1)] */
+    int32_t* d_ws_trad_prior;    /* mode 2: [N][ncls-1][128] */
 } isegmi_yolact_detect_args;
 int isegmi_op_yolact_detect(const isegmi_yolact_detect_args* a, void* stream);
 
@@ -615,6 +633,9 @@ typedef struct isegmi_engine isegmi_engine;
 int isegmi_engine_create(int model_kind, int max_batch, int H, int W, isegmi_engine** out);
 int isegmi_engine_destroy(isegmi_engine* e);
 int isegmi_engine_set_param(isegmi_engine* e, const char* name, float value);
+/* The value isegmi_engine_set_param last gave `name` on this engine; *is_set = 1 then, else 0 and *value = default_value (the caller states the default it
+ * cares about: the engine's own defaults live where each parameter is read). */
+int isegmi_engine_get_param(isegmi_engine* e, const char* name, float default_value, float* value, int32_t* is_set);
 /* "graph" param != 0: a forward (yolact / maskrcnn) runs eagerly once, is captured into a hipGraph on the next call with the
  * same (batch, input pointer) and replayed afterwards (latency mode: ends joined on the main stream; any set_param /
  * set_conv / set_tensor drops the captured graphs).  Counters for tests and diagnostics: */

@@ -850,6 +850,14 @@ extern "C" int isegmi_engine_set_param(isegmi_engine* h, const char* name, float
     return ISEGMI_OK;
 }
 
+extern "C" int isegmi_engine_get_param(isegmi_engine* h, const char* name, float default_value, float* value, int32_t* is_set) {
+    ARG_CHECK(h && name && value, "null");
+    auto it = h->e.params.find(name);
+    *value = it == h->e.params.end() ? default_value : it->second;
+    if (is_set) *is_set = it == h->e.params.end() ? 0 : 1;
+    return ISEGMI_OK;
+}
+
 extern "C" int isegmi_engine_graph_stats(isegmi_engine* h, int64_t* captures, int64_t* replays, int64_t* failures) {
     ARG_CHECK(h, "null");
     if (captures) *captures = h->e.graph_captures;

@@ -384,6 +384,9 @@ int yolact_detect_launch(const isegmi_yolact_detect_args* a, hipStream_t st);
 // takes slot (n, q)'s coefficients from there instead of from d_mask.
 int yolact_detect_select_launch(const isegmi_yolact_detect_args* a, hipStream_t st);
 int yolact_detect_gather_launch(const isegmi_yolact_detect_args* a, const float* coeff_sel, hipStream_t st);
+// the index rows the final top-k's flat indices refer to in the block's nms_mode: prior = idx[n * nc * K + flat]
+int yolact_nms_status_launch(const int32_t* overflow, int N, int32_t* status, hipStream_t st);   // det.nms_overflow -> rle.status[3]
+void yolact_detect_index_view(const isegmi_yolact_detect_args* a, const int32_t** idx, int* nc, int* K);
 // yolact_coeff.hip: the coefficient rows of selected priors, bit-identical to the head convolution's outputs
 struct CoeffLevels { const float* feat[5]; int H[5], W[5]; int n = 0; };
 int yolact_coeff_index_launch(const int32_t* fin_idx, const int32_t* tk_idx, const int32_t* fin_cnt, int N, int nc, int top_k, int max_det, int A,

@@ -141,6 +141,9 @@ int eng_rle(Engine& e, const int32_t* h_image_hw) {
         // det.mask_window (bench.py), 0 here
         OpScope op(e, rs, "rle (7 prefix-sum launches: pack, scans, emit, lengths, chars)", 0.0);
         TRY(rle_encode_launch(&a, rs));
+        // Yolact's traditional NMS: the per-class capacity's flag travels in the reserved status word (0 in every other mode and engine)
+        if (e.kind == 1 && e.param("nms_mode", 0.0f) == 2.0f && e.bufs.count("det.nms_overflow"))
+            TRY(yolact_nms_status_launch((const int32_t*)e.bufs["det.nms_overflow"].d, N, a.d_out_status, rs));
     }
     if (rs == e.tail) HIP_TRY(hipEventRecord(e.tail_done, e.tail));  // reads det.masks / det.count: extend the WAR fence
     return ISEGMI_OK;

@@ -312,6 +312,14 @@ static int detect_args(Engine& e, int N, const HeadOut& h, isegmi_yolact_detect_
     a.conf_thresh = e.param("nms_conf_thresh", 0.05f);
     a.nms_thresh = e.param("nms_thresh", 0.5f);
     a.second_threshold = (int)e.param("nms_second_threshold", 0) ? 1 : 0;   // App. A.6 fork (fast_nms(second_threshold=...)): default off
+    // the suppression rule.  0 fast NMS (the default: nothing below changes), 1 cross-class fast NMS, 2 traditional per-class NMS
+    const float fmode = e.param("nms_mode", 0.0f), fcap = e.param("nms_trad_cap", 1024.0f);
+    if (fmode != 0.0f && fmode != 1.0f && fmode != 2.0f) { set_error("nms_mode must be 0 (fast), 1 (cross-class fast) or 2 (traditional)"); return ISEGMI_ERR_ARG; }
+    const int mode = (int)fmode, cap = (int)fcap;
+    if ((float)cap != fcap || cap < 64 || cap > 2048 || cap % 64 != 0) { set_error("nms_trad_cap must be a multiple of 64 in [64, 2048]"); return ISEGMI_ERR_ARG; }
+    if (mode != 0 && a.second_threshold) { set_error("nms_second_threshold is an argument of fast_nms only: not with nms_mode 1 or 2"); return ISEGMI_ERR_ARG; }
+    a.nms_mode = mode; a.trad_cap = cap; a.trad_scale = e.param("max_size", 550.0f);
+    const int tkw = mode == 2 ? cap : top_k;   // width of the per-class sorted rows
     if (h.fused) {
         a.d_conf = a.d_loc = a.d_mask = (const float*)h.headcat;
         a.A = A; a.pix_stride = h.CH; a.off_loc = 0; a.off_conf = A * 4; a.off_mask = A * 4 + A * ncls; a.mask_tanh = 1;
@@ -323,10 +331,22 @@ static int detect_args(Engine& e, int N, const HeadOut& h, isegmi_yolact_detect_
     TRY(eng_buf(e, "ws.scoresT", (int64_t)N * nc * Ptot * 4, &p)); a.d_ws_scoresT = (float*)p;
     TRY(eng_buf(e, "boxes_all", (int64_t)N * Ptot * 16, &p, 0, {N, Ptot, 4})); a.d_ws_boxes = (float*)p;
     TRY(eng_buf(e, "ws.counts", (int64_t)2 * N * 4, &p, 1)); a.d_ws_counts = (int32_t*)p;
-    TRY(eng_buf(e, "ws.tk_vals", (int64_t)N * nc * top_k * 4, &p)); a.d_ws_tk_vals = (float*)p;
-    TRY(eng_buf(e, "ws.tk_idx", (int64_t)N * nc * top_k * 4, &p, 1)); a.d_ws_tk_idx = (int32_t*)p;
+    TRY(eng_buf(e, "ws.tk_vals", (int64_t)N * nc * tkw * 4, &p)); a.d_ws_tk_vals = (float*)p;
+    TRY(eng_buf(e, "ws.tk_idx", (int64_t)N * nc * tkw * 4, &p, 1)); a.d_ws_tk_idx = (int32_t*)p;
     TRY(eng_buf(e, "ws.tk_cnt", (int64_t)N * nc * 4, &p, 1)); a.d_ws_tk_cnt = (int32_t*)p;
-    TRY(eng_buf(e, "ws.cand", (int64_t)N * nc * top_k * 4, &p)); a.d_ws_cand = (float*)p;
+    TRY(eng_buf(e, "ws.cand", (int64_t)N * nc * (mode == 2 ? 128 : top_k) * 4, &p)); a.d_ws_cand = (float*)p;
+    if (mode != 0) {   // the default mode allocates and launches exactly what it did before the modes existed
+        TRY(eng_buf(e, "det.nms_total", (int64_t)N * 4, &p, 1, {N})); a.d_out_nms_total = (int32_t*)p;
+        TRY(eng_buf(e, "det.nms_overflow", (int64_t)N * 4, &p, 1, {N})); a.d_out_nms_overflow = (int32_t*)p;
+    }
+    if (mode == 1) {
+        TRY(eng_buf(e, "ws.cc_scores", (int64_t)N * Ptot * 4, &p)); a.d_ws_cc_scores = (float*)p;
+        TRY(eng_buf(e, "ws.cc_class", (int64_t)N * Ptot * 4, &p, 1)); a.d_ws_cc_class = (int32_t*)p;
+    }
+    if (mode == 2) {
+        TRY(eng_buf(e, "ws.trad_list", (int64_t)(1 + N * nc) * 4, &p, 1)); a.d_ws_trad_list = (int32_t*)p;
+        TRY(eng_buf(e, "ws.trad_prior", (int64_t)N * nc * 128 * 4, &p, 1)); a.d_ws_trad_prior = (int32_t*)p;
+    }
     TRY(eng_buf(e, "ws.fin_vals", (int64_t)N * max_det * 4, &p)); a.d_ws_fin_vals = (float*)p;
     TRY(eng_buf(e, "ws.fin_idx", (int64_t)N * max_det * 4, &p, 1)); a.d_ws_fin_idx = (int32_t*)p;
     TRY(eng_buf(e, "ws.fin_cnt", (int64_t)N * 4, &p, 1)); a.d_ws_fin_cnt = (int32_t*)p;
@@ -408,7 +428,9 @@ int yolact_forward(Engine& e, const float* d_images, int N) {
             TRY(eng_buf(e, "ws.coeff_rows", (int64_t)N * a.max_det * 5 * 4, &rows, 1));
             TRY(eng_buf(e, "ws.coeff_sel", (int64_t)N * a.max_det * a.mask_dim * 4, &sel, 0, {N, a.max_det, a.mask_dim}));
             TRY(yolact_detect_select_launch(&a, ds));
-            TRY(yolact_coeff_index_launch(a.d_ws_fin_idx, a.d_ws_tk_idx, a.d_ws_fin_cnt, N, a.ncls - 1, a.top_k, a.max_det, head.A, lv, (int32_t*)rows, ds));
+            const int32_t* sel_idx; int sel_nc, sel_k;   // where the final top-k's flat indices point in this nms_mode
+            yolact_detect_index_view(&a, &sel_idx, &sel_nc, &sel_k);
+            TRY(yolact_coeff_index_launch(a.d_ws_fin_idx, sel_idx, a.d_ws_fin_cnt, N, sel_nc, sel_k, a.max_det, head.A, lv, (int32_t*)rows, ds));
             TRY(yolact_coeff_rows_launch(lv, N, Lc.Cin, Lc.R, Lc.S, 1, Lc.d_w, Lc.d_scale, Lc.d_shift, head.A, 0, a.mask_dim, (const int32_t*)rows,
                                          a.d_ws_fin_cnt, a.max_det, (float*)sel, ds));
             TRY(yolact_detect_gather_launch(&a, (const float*)sel, ds));

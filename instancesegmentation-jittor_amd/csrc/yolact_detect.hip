@@ -7,12 +7,16 @@
 //   fast_nms       : per (image, class): box j survives iff max_{i<j} IoU(i,j) <= thr over the
 //                    class's score-sorted top-k (IoU without +1, NaN drops the box); with
 //                    second_threshold also iff its class score > conf_thresh.
+//   cc collapse    : (nms_mode 1) per prior the best foreground score and its lowest class -> one row per image through top-k + fast_nms (nc = 1)
+//   trad_nms       : (nms_mode 2) upstream's traditional_nms / cython_nms per (image, class): greedy, +1 areas on boxes * max_size, >=; small pairs in
+//                    one wave, crowded pairs listed for a block-wide kernel; per-class capacity with an overflow flag
 //   gather         : final per-image top-100 -> boxes / scores / classes / 32 mask coefficients.
 //   proto masks    : m = sigmoid(fmaf-chain_k proto*coeff) cropped to the box (+1 px) in proto space,
 //                    then bilinear (align_corners=False) to (h,w), > 0.5 -> uint8.
 // Reference anchors: README.md:243-249 (eval.py --score_threshold/--top_k reach Detect+postprocess).
 #include "../../include/isegmi.h"
 #include "common.h"
+#include "detbox.h"
 #include "detmath.h"
 #include "tail_launch.h"
 
@@ -157,22 +161,189 @@ __global__ __launch_bounds__(1024) void yolact_fast_nms_kernel(const float* __re
     if (threadIdx.x == 0 && k) atomicAdd(&kept_count[n], k);
 }
 
+// ---- nms_mode 1 (upstream cc_fast_nms): scores.max(dim=0) over the foreground classes of every prior.  scoresT [N][nc][P] already holds -1 in every
+// class row of a prior the pre-filter excluded, so such a prior's maximum is -1 and the top-k (limited to the image's kept count) never takes it.
+// Ties go to the LOWEST class (strict >).  grid (ceil(P/256), N); the nc loads of a thread are P apart, the lanes' adjacent.
+__global__ __launch_bounds__(256) void yolact_cc_collapse_kernel(const float* __restrict__ scoresT, int P, int nc, float* __restrict__ cc_scores,
+                                                                  int* __restrict__ cc_class) {
+    const int n = blockIdx.y, p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= P) return;
+    const float* s = scoresT + (int64_t)n * nc * P + p;
+    float best = s[0];
+    int bc = 0;
+    for (int c = 1; c < nc; ++c) { const float v = s[(int64_t)c * P]; if (v > best) { best = v; bc = c; } }
+    cc_scores[(int64_t)n * P + p] = best;
+    cc_class[(int64_t)n * P + p] = bc;
+}
+
+// ---- nms_mode 2 (upstream traditional_nms + utils/cython_nms.pyx): greedy per-class NMS over the class's candidates in (score desc, prior asc) order, on the
+// boxes scaled by max_size, legacy +1 areas, suppress on ovr >= thr (detbox.h: one = 1, ge).  tk_vals / tk_idx [N][nc][cap] hold each class's sorted top cap;
+// its candidates are the prefix with score > conf_thresh.  Almost every (image, class) pair holds none or a few dozen, so the pair's own wave resolves up to
+// 64 of them at once (one diagonal word, one chunk resolve) and only the crowded pairs are listed for the block-wide kernel below.
+// Output per pair: the first TRAD_KW survivors in visiting order, compacted: cand [N][nc][TRAD_KW] scores (-1 past them), cand_prior their priors.  A
+// later survivor of the class scores no higher than those and max_det <= TRAD_KW, so it can never enter the final cut; kept_count[n] counts all survivors.
+constexpr int TRAD_KW = 128;
+constexpr int TRAD_MAX_CAP = 2048;
+constexpr int TRAD_CROWD_BLOCKS = 512;   // the crowded kernel's grid: two blocks per CU; more listed pairs are strided over
+
+__device__ __forceinline__ float4 trad_box(const float* __restrict__ boxes, int64_t n, int P, int prior, float scale) {
+    const float4 b = *(const float4*)(boxes + (n * P + prior) * 4);
+    return make_float4(b.x * scale, b.y * scale, b.z * scale, b.w * scale);
+}
+
+// The cap lemma's flag: called by a pair whose first `cap` entries are ALL candidates.  The class may then hold more; if it does and fewer than
+// max_det of the visited ones survived, an unvisited candidate could have entered the result.  All threads of the block call; NT = blockDim.x.
+template <int NT>
+__device__ __forceinline__ void trad_overflow_check(const float* __restrict__ row, int P, float conf_thresh, int cap, int kept, int max_det,
+                                                    int* __restrict__ overflow_n) {
+    if (overflow_n == nullptr || kept >= max_det) return;   // uniform
+    int over = 0;
+    if (NT == 64) {
+        int total = 0;
+        for (int p0 = 0; p0 < P && total <= cap; p0 += 64) { const int p = p0 + (int)threadIdx.x; total += __popcll(__ballot(p < P && row[p] > conf_thresh)); }
+        over = total > cap;
+    } else {
+        int total = 0;
+        for (int p0 = 0; p0 < P; p0 += NT) { const int p = p0 + (int)threadIdx.x; total += __syncthreads_count(p < P && row[p] > conf_thresh); }
+        over = total > cap;
+    }
+    if (threadIdx.x == 0 && over) *overflow_n = 1;   // every writer stores the same value
+}
+
+// grid (nc, N); block 64 (one wave)
+__global__ __launch_bounds__(64) void yolact_trad_nms_small_kernel(const float* __restrict__ boxes, const float* __restrict__ scoresT,
+                                                                   const float* __restrict__ tk_vals, const int* __restrict__ tk_idx,
+                                                                   const int* __restrict__ tk_cnt, int P, int nc, int cap, float thr, float conf_thresh,
+                                                                   float scale, int max_det, float* __restrict__ cand, int* __restrict__ cand_prior,
+                                                                   int* __restrict__ kept_count, int* __restrict__ crowd_list, int* __restrict__ overflow) {
+    __shared__ float4 cols[64];
+    const int c = blockIdx.x, n = blockIdx.y, lane = threadIdx.x;
+    const int pair = n * nc + c;
+    const int64_t base = (int64_t)pair * cap, ob = (int64_t)pair * TRAD_KW;
+    const int cnt = tk_cnt[pair];
+    int m = 0;   // sorted descending: the candidates are a prefix
+    for (int j0 = 0; j0 < cnt; j0 += 64) { const int j = j0 + lane; m += __popcll(__ballot(j < cnt && tk_vals[base + j] > conf_thresh)); }
+    if (m > 64) {   // crowded: the block-wide kernel writes this pair's rows
+        if (lane == 0) crowd_list[1 + atomicAdd(&crowd_list[0], 1)] = pair;
+        return;
+    }
+    unsigned long long alive = 0ull;
+    int prior = -1;
+    float score = -1.0f;
+    if (m > 0) {
+        float4 mine = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (lane < m) { prior = tk_idx[base + lane]; score = tk_vals[base + lane]; mine = trad_box(boxes, n, P, prior, scale); }
+        nms_stage_cols(cols, lane, mine);
+        const IouThr T = make_iou_thr(thr, 1);
+        const unsigned long long d = nms_tile_word(mine, cols, lane, 0, 1.0f, T, [m](int j, int) { return j < m; });
+        alive = nms_resolve_chunk(m == 64 ? ~0ull : ((1ull << m) - 1ull), d);
+    }
+    const int kept = __popcll(alive);
+    const bool keep = (alive >> lane) & 1ull;
+    const int pos = __popcll(alive & ((1ull << lane) - 1ull));
+    if (keep) { cand[ob + pos] = score; cand_prior[ob + pos] = prior; }
+    for (int q = kept + lane; q < TRAD_KW; q += 64) { cand[ob + q] = -1.0f; cand_prior[ob + q] = -1; }
+    if (lane == 0 && kept) atomicAdd(&kept_count[n], kept);
+    if (m == cap) trad_overflow_check<64>(scoresT + (int64_t)pair * P, P, conf_thresh, cap, kept, max_det, overflow ? overflow + n : nullptr);
+}
+
+// (not inlined: the 64-step readlane chain inside a loop of the 1024-thread kernel below pushed its scalar registers into scratch)
+__device__ __attribute__((noinline)) unsigned long long trad_resolve_chunk(unsigned long long alive, unsigned long long d) {
+    return nms_resolve_chunk(alive, d);
+}
+
+// One block per listed pair, the blocks striding over the list (grid min(nc * N, TRAD_CROWD_BLOCKS); a block past the list's length leaves at once).
+// The greedy scan does only the work the greedy rule needs:
+// chunk by chunk, wave 0 resolves the chunk from its diagonal word and the removed bits so far, then all waves test the chunk's KEPT boxes against the
+// not yet removed boxes of the later chunks (lane = later box, the kept boxes broadcast from LDS).  48.8 KB of static LDS whatever the pair holds.
+__global__ __launch_bounds__(1024) void yolact_trad_nms_crowd_kernel(const float* __restrict__ boxes, const float* __restrict__ scoresT,
+                                                                     const float* __restrict__ tk_vals, const int* __restrict__ tk_idx,
+                                                                     const int* __restrict__ tk_cnt, int P, int nc, int cap, float thr, float conf_thresh,
+                                                                     float scale, int max_det, float* __restrict__ cand, int* __restrict__ cand_prior,
+                                                                     int* __restrict__ kept_count, const int* __restrict__ crowd_list,
+                                                                     int* __restrict__ overflow) {
+    constexpr int NW = 16, MAXW = TRAD_MAX_CAP / 64;
+    __shared__ float4 sb[TRAD_MAX_CAP];
+    __shared__ unsigned long long diag[TRAD_MAX_CAP];
+    __shared__ unsigned long long rem[MAXW], keepw[MAXW];
+    const int listed = crowd_list[0];
+    for (int li = blockIdx.x; li < listed; li += gridDim.x) {   // (uniform; a block past the list's length leaves on this load)
+        const int pair = crowd_list[1 + li];
+        const int n = pair / nc;
+        const int64_t base = (int64_t)pair * cap, ob = (int64_t)pair * TRAD_KW;
+        const int cnt = tk_cnt[pair];   // <= cap <= TRAD_MAX_CAP
+        const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+        int m = 0;
+        for (int j0 = 0; j0 < cnt; j0 += 1024) { const int j = j0 + tid; m += __syncthreads_count(j < cnt && tk_vals[base + j] > conf_thresh); }
+        for (int j = tid; j < m; j += 1024) sb[j] = trad_box(boxes, n, P, tk_idx[base + j], scale);
+        if (tid < MAXW) { rem[tid] = 0ull; keepw[tid] = 0ull; }
+        __syncthreads();
+        const IouThr T = make_iou_thr(thr, 1);
+        const int nwords = (m + 63) >> 6;
+        for (int w = wave; w < nwords; w += NW) {
+            const int i = (w << 6) + lane;
+            // the columns are read in place; those past m are stale and not eligible
+            diag[i] = nms_tile_word(sb[i < m ? i : 0], sb + (w << 6), i, w, 1.0f, T, [m](int j, int) { return j < m; });
+        }
+        __syncthreads();
+        for (int c = 0; c < nwords; ++c) {
+            if (wave == 0) {
+                const int i = (c << 6) + lane;
+                const unsigned long long in = __ballot(i < m);
+                const unsigned long long alive = trad_resolve_chunk(~rem[c] & in, diag[i]);
+                if (lane == 0) keepw[c] = alive;
+            }
+            __syncthreads();
+            const unsigned long long keepm = keepw[c];
+            for (int w = c + 1 + wave; w < nwords; w += NW) {   // word w belongs to this wave alone in this round
+                const int j = (w << 6) + lane;
+                const unsigned long long gone = rem[w];
+                bool hit = false;
+                if (j < m && !((gone >> lane) & 1ull)) {
+                    const float4 mine = sb[j];
+                    for (unsigned long long km = keepm; km != 0ull && !hit; km &= km - 1ull)
+                        hit = iou_exceeds(sb[(c << 6) + __builtin_ctzll(km)], mine, 1.0f, T);
+                }
+                const unsigned long long h = __ballot(hit);
+                if (lane == 0 && h) rem[w] = gone | h;
+            }
+            __syncthreads();
+        }
+        int kept = 0;
+        for (int w = 0; w < nwords; ++w) kept += __popcll(keepw[w]);
+        for (int j = tid; j < m; j += 1024) {
+            const int w = j >> 6;
+            const unsigned long long kw = keepw[w];
+            if ((kw >> (j & 63)) & 1ull) {
+                int pos = __popcll(kw & ((1ull << (j & 63)) - 1ull));
+                for (int pw = 0; pw < w; ++pw) pos += __popcll(keepw[pw]);
+                if (pos < TRAD_KW) { cand[ob + pos] = tk_vals[base + j]; cand_prior[ob + pos] = tk_idx[base + j]; }
+            }
+        }
+        for (int slot = kept + tid; slot < TRAD_KW; slot += 1024) { cand[ob + slot] = -1.0f; cand_prior[ob + slot] = -1; }
+        if (tid == 0 && kept) atomicAdd(&kept_count[n], kept);
+        if (m == cap) trad_overflow_check<1024>(scoresT + (int64_t)pair * P, P, conf_thresh, cap, kept, max_det, overflow ? overflow + n : nullptr);
+        __syncthreads();   // the next listed pair reuses sb / diag / rem / keepw
+    }
+}
+
 // grid (N); block 128: one thread per output slot.
 __global__ void yolact_gather_kernel(const float* __restrict__ boxes, const float* __restrict__ mask, const int* __restrict__ tk_idx,
                                      const float* __restrict__ fin_vals, const int* __restrict__ fin_idx,
                                      const int* __restrict__ fin_cnt, int P, int nc, int top_k, int mask_dim, int max_det,
-                                     const HeadLayout L, const float* __restrict__ coeff_sel,
-                                     int* __restrict__ out_count, float* __restrict__ out_boxes, float* __restrict__ out_scores,
+                                     const HeadLayout L, const float* __restrict__ coeff_sel, const int* __restrict__ cls_row,
+                                     const int* __restrict__ nms_kept, int* __restrict__ out_nms_total, int* __restrict__ out_count, float* __restrict__ out_boxes, float* __restrict__ out_scores,
                                      int* __restrict__ out_classes, float* __restrict__ out_coeffs, int* __restrict__ out_prior) {
     const int n = blockIdx.x;
     const int cnt = fin_cnt[n];
     if (threadIdx.x == 0) out_count[n] = cnt;
+    if (threadIdx.x == 0 && out_nms_total) out_nms_total[n] = nms_kept[n];   // the suppression pass's survivors, before the cut to max_det
     for (int q = threadIdx.x; q < max_det; q += blockDim.x) {
         const int64_t o = (int64_t)n * max_det + q;
         if (q < cnt) {
             const int flat = fin_idx[o];
-            const int c = flat / top_k;
             const int prior = tk_idx[(int64_t)n * nc * top_k + flat];
+            const int c = cls_row ? cls_row[(int64_t)n * P + prior] : flat / top_k;   // cross-class mode: the collapsed maximum's class
             *(float4*)(out_boxes + o * 4) = *(const float4*)(boxes + ((int64_t)n * P + prior) * 4);
             out_scores[o] = fin_vals[o];
             out_classes[o] = c;
@@ -327,13 +498,39 @@ static HeadLayout head_layout(const isegmi_yolact_detect_args* a) {
     return L;
 }
 
+// nms_mode / trad_cap / second_threshold as the argument block may hold them; named refusals before any launch
+static int detect_mode_check(const isegmi_yolact_detect_args* a, int* cap_out) {
+    ARG_CHECK(a->nms_mode >= 0 && a->nms_mode <= 2, "nms_mode must be 0 (fast), 1 (cross-class fast) or 2 (traditional)");
+    ARG_CHECK(a->nms_mode == 0 || a->second_threshold == 0, "nms_second_threshold is an argument of fast_nms only: not with nms_mode 1 or 2");
+    const int cap = a->trad_cap > 0 ? a->trad_cap : 1024;
+    if (a->nms_mode == 1) ARG_CHECK(a->d_ws_cc_scores && a->d_ws_cc_class, "nms_mode 1 needs d_ws_cc_scores and d_ws_cc_class");
+    if (a->nms_mode == 2) {
+        ARG_CHECK(a->trad_cap >= 0 && cap >= 64 && cap <= TRAD_MAX_CAP && cap % 64 == 0, "nms_trad_cap (trad_cap) must be a multiple of 64 in [64, 2048]");
+        ARG_CHECK(a->trad_scale > 0.0f, "nms_mode 2 needs trad_scale (max_size) > 0");
+        ARG_CHECK(a->d_ws_trad_list && a->d_ws_trad_prior, "nms_mode 2 needs d_ws_trad_list and d_ws_trad_prior");
+    }
+    *cap_out = cap;
+    return ISEGMI_OK;
+}
+
+// The index layout the final top-k's flat indices refer to, whatever the mode: prior = idx[(n * nc + flat / K) * K + flat % K] = idx[n * nc * K + flat]
+void yolact_detect_index_view(const isegmi_yolact_detect_args* a, const int32_t** idx, int* nc, int* K) {
+    if (a->nms_mode == 1) { *idx = a->d_ws_tk_idx; *nc = 1; *K = a->top_k; }
+    else if (a->nms_mode == 2) { *idx = a->d_ws_trad_prior; *nc = a->ncls - 1; *K = TRAD_KW; }
+    else { *idx = a->d_ws_tk_idx; *nc = a->ncls - 1; *K = a->top_k; }
+}
+
 // Detect up to the final per-image top-k (ws.fin_vals / fin_idx / fin_cnt); the gather below turns those into the det.* rows
 int yolact_detect_select_launch(const isegmi_yolact_detect_args* a, hipStream_t st) {
     ARG_CHECK(a->N > 0 && a->P > 0 && a->ncls >= 2 && a->ncls <= 256, "detect sizes");
     ARG_CHECK(a->top_k > 0 && a->top_k <= 256 && a->max_det > 0 && a->max_det <= 128, "top_k<=256, max_det<=128");
     ARG_CHECK(a->mask_dim > 0, "mask_dim");
+    int cap = 0;
+    int rc = detect_mode_check(a, &cap);
+    if (rc) return rc;
     const int nc = a->ncls - 1;
     HIP_TRY(hipMemsetAsync(a->d_ws_counts, 0, sizeof(int) * 2 * (size_t)a->N, st));
+    if (a->d_out_nms_overflow) HIP_TRY(hipMemsetAsync(a->d_out_nms_overflow, 0, sizeof(int) * (size_t)a->N, st));
     int* keep_count = a->d_ws_counts;
     int* kept2 = a->d_ws_counts + a->N;
     const size_t lds = ((size_t)SM_ROWS * a->ncls + (size_t)(SM_PARTS + 1) * SM_ROWS) * sizeof(float);
@@ -342,8 +539,35 @@ int yolact_detect_select_launch(const isegmi_yolact_detect_args* a, hipStream_t 
     hipLaunchKernelGGL(yolact_softmax_decode_kernel, dim3(cdiv(a->P, SM_ROWS), a->N), dim3(SM_ROWS * SM_PARTS), lds, st, a->d_conf, a->d_loc,
                        a->d_priors, a->P, a->ncls, a->conf_thresh, L, a->d_ws_scoresT, a->d_ws_boxes, keep_count);
     HIP_TRY(hipGetLastError());
-    int rc = topk_launch(a->d_ws_scoresT, a->P, a->N * nc, a->P, a->top_k, keep_count, nc, a->d_ws_tk_vals, a->d_ws_tk_idx,
-                         a->d_ws_tk_cnt, st);
+    if (a->nms_mode == 1) {   // one collapsed score row per image, then the per-class pieces with a single "class"
+        hipLaunchKernelGGL(yolact_cc_collapse_kernel, dim3(cdiv(a->P, 256), a->N), dim3(256), 0, st, a->d_ws_scoresT, a->P, nc, a->d_ws_cc_scores,
+                           a->d_ws_cc_class);
+        HIP_TRY(hipGetLastError());
+        rc = topk_launch(a->d_ws_cc_scores, a->P, a->N, a->P, a->top_k, keep_count, 1, a->d_ws_tk_vals, a->d_ws_tk_idx, a->d_ws_tk_cnt, st);
+        if (rc) return rc;
+        hipLaunchKernelGGL(yolact_fast_nms_kernel, dim3(1, a->N), dim3(1024), 0, st, a->d_ws_boxes, a->d_ws_tk_vals, a->d_ws_tk_idx, a->d_ws_tk_cnt,
+                           a->P, 1, a->top_k, a->nms_thresh, 0, a->conf_thresh, a->d_ws_cand, kept2);
+        HIP_TRY(hipGetLastError());
+        return topk_launch(a->d_ws_cand, a->top_k, a->N, a->top_k, a->max_det, kept2, 1, a->d_ws_fin_vals, a->d_ws_fin_idx, a->d_ws_fin_cnt, st);
+    }
+    if (a->nms_mode == 2) {
+        HIP_TRY(hipMemsetAsync(a->d_ws_trad_list, 0, sizeof(int), st));
+        rc = topk_launch(a->d_ws_scoresT, a->P, a->N * nc, a->P, cap, keep_count, nc, a->d_ws_tk_vals, a->d_ws_tk_idx, a->d_ws_tk_cnt, st);
+        if (rc) return rc;
+        hipLaunchKernelGGL(yolact_trad_nms_small_kernel, dim3(nc, a->N), dim3(64), 0, st, a->d_ws_boxes, a->d_ws_scoresT, a->d_ws_tk_vals,
+                           a->d_ws_tk_idx, a->d_ws_tk_cnt, a->P, nc, cap, a->nms_thresh, a->conf_thresh, a->trad_scale, a->max_det, a->d_ws_cand,
+                           a->d_ws_trad_prior, kept2, a->d_ws_trad_list, a->d_out_nms_overflow);
+        HIP_TRY(hipGetLastError());
+        const int crowd_blocks = nc * a->N < TRAD_CROWD_BLOCKS ? nc * a->N : TRAD_CROWD_BLOCKS;
+        hipLaunchKernelGGL(yolact_trad_nms_crowd_kernel, dim3(crowd_blocks), dim3(1024), 0, st, a->d_ws_boxes, a->d_ws_scoresT, a->d_ws_tk_vals,
+                           a->d_ws_tk_idx, a->d_ws_tk_cnt, a->P, nc, cap, a->nms_thresh, a->conf_thresh, a->trad_scale, a->max_det, a->d_ws_cand,
+                           a->d_ws_trad_prior, kept2, a->d_ws_trad_list, a->d_out_nms_overflow);
+        HIP_TRY(hipGetLastError());
+        return topk_launch(a->d_ws_cand, (int64_t)nc * TRAD_KW, a->N, nc * TRAD_KW, a->max_det, kept2, 1, a->d_ws_fin_vals, a->d_ws_fin_idx,
+                           a->d_ws_fin_cnt, st);
+    }
+    rc = topk_launch(a->d_ws_scoresT, a->P, a->N * nc, a->P, a->top_k, keep_count, nc, a->d_ws_tk_vals, a->d_ws_tk_idx,
+                     a->d_ws_tk_cnt, st);
     if (rc) return rc;
     hipLaunchKernelGGL(yolact_fast_nms_kernel, dim3(nc, a->N), dim3(1024), 0, st, a->d_ws_boxes, a->d_ws_tk_vals, a->d_ws_tk_idx,
                        a->d_ws_tk_cnt, a->P, nc, a->top_k, a->nms_thresh, a->second_threshold, a->conf_thresh, a->d_ws_cand, kept2);
@@ -354,11 +578,26 @@ int yolact_detect_select_launch(const isegmi_yolact_detect_args* a, hipStream_t 
 }
 
 int yolact_detect_gather_launch(const isegmi_yolact_detect_args* a, const float* coeff_sel, hipStream_t st) {
-    const int nc = a->ncls - 1;
+    const int32_t* idx; int nc, K;
+    yolact_detect_index_view(a, &idx, &nc, &K);
     const HeadLayout L = head_layout(a);
-    hipLaunchKernelGGL(yolact_gather_kernel, dim3(a->N), dim3(128), 0, st, a->d_ws_boxes, a->d_mask, a->d_ws_tk_idx, a->d_ws_fin_vals,
-                       a->d_ws_fin_idx, a->d_ws_fin_cnt, a->P, nc, a->top_k, a->mask_dim, a->max_det, L, coeff_sel, a->d_out_count,
-                       a->d_out_boxes, a->d_out_scores, a->d_out_classes, a->d_out_coeffs, a->d_out_prior);
+    hipLaunchKernelGGL(yolact_gather_kernel, dim3(a->N), dim3(128), 0, st, a->d_ws_boxes, a->d_mask, idx, a->d_ws_fin_vals,
+                       a->d_ws_fin_idx, a->d_ws_fin_cnt, a->P, nc, K, a->mask_dim, a->max_det, L, coeff_sel,
+                       a->nms_mode == 1 ? (const int*)a->d_ws_cc_class : (const int*)nullptr, (const int*)(a->d_ws_counts + a->N), a->d_out_nms_total,
+                       a->d_out_count, a->d_out_boxes, a->d_out_scores, a->d_out_classes, a->d_out_coeffs, a->d_out_prior);
+    HIP_TRY(hipGetLastError());
+    return ISEGMI_OK;
+}
+
+// rle.status[3] (reserved: 0 after every RLE pass) = 1 iff traditional NMS flagged an image of the batch: the record block carries the status words, so the
+// record loop sees the flag with the step's records and redoes the step with a larger nms_trad_cap, as it does for an RLE capacity
+__global__ void yolact_nms_status_kernel(const int* __restrict__ overflow, int N, int* __restrict__ status3) {
+    int any = 0;
+    for (int n = 0; n < N; ++n) any |= overflow[n];
+    if (any) *status3 = 1;
+}
+int yolact_nms_status_launch(const int32_t* overflow, int N, int32_t* status, hipStream_t st) {
+    hipLaunchKernelGGL(yolact_nms_status_kernel, dim3(1), dim3(1), 0, st, overflow, N, status + 3);
     HIP_TRY(hipGetLastError());
     return ISEGMI_OK;
 }

@@ -38,7 +38,9 @@ class YolactDetectArgs(C.Structure):
         _ptr("d_conf", "d_loc", "d_mask", "d_priors", "d_ws_scoresT", "d_ws_boxes", "d_ws_counts", "d_ws_tk_vals", "d_ws_tk_idx", "d_ws_tk_cnt",
              "d_ws_cand", "d_ws_fin_vals", "d_ws_fin_idx", "d_ws_fin_cnt", "d_out_count", "d_out_boxes", "d_out_scores", "d_out_classes",
              "d_out_coeffs", "d_out_prior") + \
-        _i32("A", "mask_tanh") + [("pix_stride", C.c_int64)] + _i32("off_loc", "off_conf", "off_mask", "second_threshold")
+        _i32("A", "mask_tanh") + [("pix_stride", C.c_int64)] + _i32("off_loc", "off_conf", "off_mask", "second_threshold") + \
+        _i32("nms_mode", "trad_cap") + [("trad_scale", C.c_float)] + \
+        _ptr("d_out_nms_total", "d_out_nms_overflow", "d_ws_cc_scores", "d_ws_cc_class", "d_ws_trad_list", "d_ws_trad_prior")
 
 
 class BoxPostArgs(C.Structure):
@@ -188,6 +190,7 @@ SIGNATURES = {
     "isegmi_engine_create": (I, [I, I, I, I, V]),
     "isegmi_engine_destroy": (I, [V]),
     "isegmi_engine_set_param": (I, [V, S, F]),
+    "isegmi_engine_get_param": (I, [V, S, F, V, V]),
     "isegmi_engine_graph_stats": (I, [V, V, V, V]),
     "isegmi_engine_set_conv": (I, [V, S, I, I, I, I, V, V, V]),
     "isegmi_engine_set_conv_grouped": (I, [V, S, I, I, V, V, V]),

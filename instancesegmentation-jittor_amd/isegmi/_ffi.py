@@ -483,25 +483,61 @@ def topk(keys2d, k, limit=None, rows_per_limit=1, row_stride=None):
     return dv.numpy(), di.numpy(), dc.numpy()
 
 
-def yolact_detect(conf_logits, loc, mask, priors, conf_thresh=0.05, nms_thresh=0.5, top_k=200, max_det=100, second_threshold=0):
-    """Host convenience wrapper: conf_logits [N,P,ncls], loc [N,P,4], mask [N,P,md], priors [P,4]."""
+def yolact_detect_prepare(conf_logits, loc, mask, priors, conf_thresh=0.05, nms_thresh=0.5, top_k=200, max_det=100, second_threshold=0,
+                          nms_mode=0, trad_cap=1024, max_size=550, fused_A=0, return_nms=False):
+    """-> (args, bufs): the argument block of isegmi_op_yolact_detect with every buffer uploaded / allocated, for yolact_detect() below and for
+    tools that time repeated calls on the same buffers.  conf_logits [N,P,ncls], loc [N,P,4], mask [N,P,md], priors [P,4].
+    nms_mode 0 fast NMS, 1 cross-class fast NMS, 2 traditional per-class NMS (trad_cap candidates per class at most, boxes * max_size).
+    fused_A > 0: the three head outputs go to the device as ONE per-pixel row buffer [N][P/A][A*4 | A*ncls | A*md] (the engines' fused head layout).
+    return_nms: also return (nms_total [N], nms_overflow [N])."""
     conf_logits = np.ascontiguousarray(conf_logits, np.float32)
+    loc = np.ascontiguousarray(loc, np.float32); mask = np.ascontiguousarray(mask, np.float32)
     N, P, ncls = conf_logits.shape
     md = mask.shape[-1]
     nc = ncls - 1
+    tkw = int(trad_cap) if nms_mode == 2 else top_k
     bufs = dict(
-        d_conf=DeviceBuffer.from_numpy(conf_logits), d_loc=DeviceBuffer.from_numpy(np.asarray(loc, np.float32)),
-        d_mask=DeviceBuffer.from_numpy(np.asarray(mask, np.float32)), d_priors=DeviceBuffer.from_numpy(np.asarray(priors, np.float32)),
+        d_priors=DeviceBuffer.from_numpy(np.asarray(priors, np.float32)),
         d_ws_scoresT=DeviceBuffer((N, nc, P)), d_ws_boxes=DeviceBuffer((N, P, 4)), d_ws_counts=DeviceBuffer((2 * N,), np.int32),
-        d_ws_tk_vals=DeviceBuffer((N, nc, top_k)), d_ws_tk_idx=DeviceBuffer((N, nc, top_k), np.int32),
-        d_ws_tk_cnt=DeviceBuffer((N, nc), np.int32), d_ws_cand=DeviceBuffer((N, nc, top_k)),
+        d_ws_tk_vals=DeviceBuffer((N, nc, tkw)), d_ws_tk_idx=DeviceBuffer((N, nc, tkw), np.int32),
+        d_ws_tk_cnt=DeviceBuffer((N, nc), np.int32), d_ws_cand=DeviceBuffer((N, nc, max(tkw, 128))),
         d_ws_fin_vals=DeviceBuffer((N, max_det)), d_ws_fin_idx=DeviceBuffer((N, max_det), np.int32),
         d_ws_fin_cnt=DeviceBuffer((N,), np.int32), d_out_count=DeviceBuffer((N,), np.int32),
         d_out_boxes=DeviceBuffer((N, max_det, 4)), d_out_scores=DeviceBuffer((N, max_det)),
         d_out_classes=DeviceBuffer((N, max_det), np.int32), d_out_coeffs=DeviceBuffer((N, max_det, md)),
         d_out_prior=DeviceBuffer((N, max_det), np.int32))
-    a = YolactDetectArgs(N, P, ncls, md, top_k, max_det, conf_thresh, nms_thresh, *[bufs[n].ptr for n, _ in YolactDetectArgs._fields_[8:28]])
+    a = YolactDetectArgs()   # zero-initialised: every field not set below keeps the default behaviour
+    a.N, a.P, a.ncls, a.mask_dim, a.top_k, a.max_det = N, P, ncls, md, top_k, max_det
+    a.conf_thresh, a.nms_thresh = conf_thresh, nms_thresh
+    if fused_A:
+        A = int(fused_A)
+        assert P % A == 0
+        row = np.concatenate([loc.reshape(N, P // A, A * 4), conf_logits.reshape(N, P // A, A * ncls), mask.reshape(N, P // A, A * md)], -1)
+        bufs["d_head"] = DeviceBuffer.from_numpy(np.ascontiguousarray(row))
+        a.d_conf = a.d_loc = a.d_mask = bufs["d_head"].ptr
+        a.A, a.pix_stride, a.off_loc, a.off_conf, a.off_mask = A, row.shape[-1], 0, A * 4, A * 4 + A * ncls
+    else:
+        bufs.update(d_conf=DeviceBuffer.from_numpy(conf_logits), d_loc=DeviceBuffer.from_numpy(loc), d_mask=DeviceBuffer.from_numpy(mask))
+    if return_nms or nms_mode:
+        bufs.update(d_out_nms_total=DeviceBuffer((N,), np.int32), d_out_nms_overflow=DeviceBuffer((N,), np.int32))
+    if nms_mode == 1:
+        bufs.update(d_ws_cc_scores=DeviceBuffer((N, P)), d_ws_cc_class=DeviceBuffer((N, P), np.int32))
+    if nms_mode == 2:
+        bufs.update(d_ws_trad_list=DeviceBuffer((1 + N * nc,), np.int32), d_ws_trad_prior=DeviceBuffer((N, nc, 128), np.int32))
+    for name, b in bufs.items():
+        if name != "d_head":
+            setattr(a, name, b.ptr)
     a.second_threshold = int(second_threshold)
+    a.nms_mode, a.trad_cap, a.trad_scale = int(nms_mode), int(trad_cap), float(max_size)
+    return a, bufs
+
+
+def yolact_detect(conf_logits, loc, mask, priors, conf_thresh=0.05, nms_thresh=0.5, top_k=200, max_det=100, second_threshold=0,
+                  nms_mode=0, trad_cap=1024, max_size=550, fused_A=0, return_nms=False):
+    """Host convenience wrapper: conf_logits [N,P,ncls], loc [N,P,4], mask [N,P,md], priors [P,4]; the keywords are yolact_detect_prepare's."""
+    a, bufs = yolact_detect_prepare(conf_logits, loc, mask, priors, conf_thresh, nms_thresh, top_k, max_det, second_threshold, nms_mode, trad_cap,
+                                    max_size, fused_A, return_nms)
+    N = a.N
     check(lib().isegmi_op_yolact_detect(C.byref(a), None))
     cnt = bufs["d_out_count"].numpy()
     out = []
@@ -509,6 +545,8 @@ def yolact_detect(conf_logits, loc, mask, priors, conf_thresh=0.05, nms_thresh=0
     for n in range(N):
         c = int(cnt[n])
         out.append(dict(box=B[n, :c], score=S[n, :c], cls=Cl[n, :c], mask=M[n, :c], prior=Pr[n, :c]))
+    if return_nms:
+        return out, bufs["d_ws_boxes"].numpy(), bufs["d_out_nms_total"].numpy(), bufs["d_out_nms_overflow"].numpy()
     return out, bufs["d_ws_boxes"].numpy()
 
 

@@ -19,6 +19,7 @@ e.g. by `python -m torch.distributed.run --nproc-per-node N -m isegmi.cli ...`) 
 records are all-gathered with RCCL; rank 0 writes the COCO json.  Nothing here imports torch.
 """
 import argparse
+import dataclasses
 import json
 import os
 import sys
@@ -78,6 +79,21 @@ def _image_sizes(files):
     return sizes
 
 
+def str2bool(v):
+    """upstream eval.py's str2bool: the spelling of its boolean arguments (--fast_nms=False)"""
+    if v.lower() in ("yes", "true", "t", "y", "1"):
+        return True
+    if v.lower() in ("no", "false", "f", "n", "0"):
+        return False
+    raise argparse.ArgumentTypeError("Boolean value expected.")
+
+
+def eval_nms_options(a):
+    """the suppression-rule arguments of `eval` as YolactConfig fields; an argument not given is upstream's default (fast NMS, per class)"""
+    return dict(use_fast_nms=getattr(a, "fast_nms", True), use_cross_class_nms=getattr(a, "cross_class_nms", False),
+                nms_trad_cap=getattr(a, "nms_trad_cap", 1024))
+
+
 def cmd_eval(a):
     """Yolact eval.py: evalimage / evalimages (+ Detections.dump when --output_coco_json is given)."""
     from .coco import dump, rle_decode
@@ -87,6 +103,8 @@ def cmd_eval(a):
     cfg = {"yolact_resnet50_config": YolactConfig(), "yolact_base_config": YolactConfig.base(), "yolact_im700_config": YolactConfig.im700(),
            "yolact_plus_resnet50_config": YolactConfig.plus_resnet50(), "yolact_plus_base_config": YolactConfig.plus_base(),
            "yolact_darknet53_config": YolactConfig.darknet53()}[a.config]
+    # upstream eval.py --fast_nms / --cross_class_nms (set_cfg: cfg.use_fast_nms / cfg.use_cross_class_nms); --nms_trad_cap is this engine's
+    cfg = dataclasses.replace(cfg, **eval_nms_options(a))
     rank, world, local = _rank_world()
     jobs = []
     if a.image:
@@ -354,6 +372,9 @@ def build_parser():
     e.add_argument("--images", default=None, help="in_dir:out_dir")
     e.add_argument("--output_coco_json", default=None)
     e.add_argument("--batch_size", type=int, default=8, help="images per step and rank")
+    e.add_argument("--fast_nms", type=str2bool, default=argparse.SUPPRESS, help="(default True) False: traditional per-class NMS (upstream's cython_nms) instead of fast NMS")
+    e.add_argument("--cross_class_nms", type=str2bool, default=argparse.SUPPRESS, help="(default False) True: one fast-NMS pass over all classes together")
+    e.add_argument("--nms_trad_cap", type=int, default=argparse.SUPPRESS, help="(default 1024) traditional NMS: candidates visited per image and class (a multiple of 64 in [64, 2048])")
     t = sub.add_parser("test_net", help="detectron tools/test_net.py-style evaluation -> COCO json")
     t.add_argument("--config-file", dest="config_file", default="")
     t.add_argument("--images", default=None, help="directory of images (the COCO dataset catalog is out of scope)")

@@ -119,7 +119,7 @@ def unpack_coco_records(buf, n, K=K_DEFAULT, kind=2, has_mscore=False, cap_chars
     """One rank's block -> dict(status, box, count, score, label[, mscore], str_off, chars=bytes, overflow=None).  If the engine flagged an
     overflow of its RLE capacities (the strings are incomplete): strict raises CocoRecordError; otherwise the dict carries
     overflow = (bits, runs, characters) -- bit 1: runs over rle_cap_runs (`runs` = what the step needs; characters unknown then), bit 2:
-    characters over rle_cap_chars -- and no strings; isegmi.pipeline.run_record_loop raises the capacities and redoes the step."""
+    characters over rle_cap_chars, bit 4: Yolact's traditional NMS flagged its per-class capacity nms_trad_cap -- and no strings; isegmi.pipeline.run_record_loop raises the capacities and redoes the step."""
     buf = np.ascontiguousarray(buf, np.uint8).ravel()
     secs, coff, total = coco_record_layout(n, K, kind, has_mscore, cap_chars, box_only, keypoints)
     assert buf.size >= total, (buf.size, total)
@@ -127,6 +127,12 @@ def unpack_coco_records(buf, n, K=K_DEFAULT, kind=2, has_mscore=False, cap_chars
     st = out["status"]
     out["overflow"] = None
     if box_only:   # no strings, nothing that can overflow: dict(status, box, count, score, label[, kpt, kscore], overflow=None)
+        return out
+    if st[3] != 0:   # Yolact traditional NMS: a class held more candidates than nms_trad_cap in a way that can change the result
+        if strict:
+            raise CocoRecordError("traditional NMS overflowed its per-class capacity; raise nms_trad_cap")
+        out["overflow"] = (int(st[2]) | 4, int(st[0]), int(st[1]))
+        out["chars"] = b""
         return out
     if st[2] != 0:
         if strict:

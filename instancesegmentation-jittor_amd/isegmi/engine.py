@@ -31,6 +31,13 @@ class Engine:
     def set_param(self, name, value):
         _ffi.check(_ffi.lib().isegmi_engine_set_param(self._h, name.encode(), value))
 
+    def param(self, name, default=None):
+        """The value set_param last gave `name` on this engine (read back from the engine, isegmi_engine_get_param), else `default`: the engine's
+        own defaults live in the C++ code that reads each parameter, so the caller names the one it means."""
+        v, is_set = C.c_float(), C.c_int32()
+        _ffi.check(_ffi.lib().isegmi_engine_get_param(self._h, name.encode(), 0.0, C.byref(v), C.byref(is_set)))
+        return float(v.value) if is_set.value else default
+
     # -- weights -------------------------------------------------------------------------------
     def _set_conv_krsc(self, name, w, scale=None, shift=None):
         """One layer, natural [Cout][R][S][Cin] weights with the folded scale / shift [Cout] (None: 1 / 0)."""

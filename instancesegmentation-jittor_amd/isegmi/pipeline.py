@@ -149,9 +149,21 @@ def record_capacity(net):
     return int(net.cfg.max_num_detections if net.KIND == 1 else net.cfg.det_cap)
 
 
+def grow_nms_capacity(net):
+    """Yolact's traditional NMS flagged its per-class capacity (det.nms_overflow, overflow bit 4 of a record block): doubles nms_trad_cap."""
+    cap = int(net.nms_trad_cap)
+    if cap >= 2048:
+        raise CocoRecordError("traditional NMS still overflows its per-class capacity at nms_trad_cap = %d (the largest is 2048)" % cap)
+    net.set_param("nms_trad_cap", float(min(2048, 2 * cap)))
+
+
 def grow_rle_capacity(net, overflows, batch):
     """Raises the engine's RLE capacities after a step overflowed them.  `overflows`: the (bits, runs, characters) of every rank's block of
     that step -- all ranks see all of them (they are in the gathered blocks), so all ranks arrive at the same new capacities."""
+    if any(o[0] & 4 for o in overflows):
+        grow_nms_capacity(net)
+        if not any(o[0] & 3 for o in overflows):
+            return
     nb, co = net.coco_record_bytes(batch)
     runs, chars = max(o[1] for o in overflows), max(o[2] for o in overflows)
     new_chars = max(2 * (nb - co), int(chars * 1.25) + 4096, 3 * runs)   # ~1.5-2 characters per run; a second round settles it if not

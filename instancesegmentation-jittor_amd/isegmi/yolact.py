@@ -33,6 +33,10 @@ class YolactConfig:
     nms_top_k: int = 200
     max_num_detections: int = 100
     nms_second_threshold: int = 0  # SURVEY App. A.6 fork: Detect.fast_nms(second_threshold=True) -- a box must also have its own class score > nms_conf_thresh
+    # the suppression rule, upstream's names (Detect: cfg.use_fast_nms / cfg.use_cross_class_nms; eval.py --fast_nms / --cross_class_nms)
+    use_fast_nms: bool = True          # False: traditional per-class NMS (cython_nms), "--fast_nms=False"
+    use_cross_class_nms: bool = False  # True (with use_fast_nms): one fast-NMS pass over all classes together
+    nms_trad_cap: int = 1024           # traditional NMS visits at most this many candidates per (image, class); a multiple of 64 in [64, 2048]
     conv_split_k: int = 0          # opt-in latency numerics mode (see MaskRCNNConfig.CONV_SPLIT_K): fixed-tree split-K for the backbone's small-M / large-K convolutions
     depth: int = 50  # 50 = yolact_resnet50_config, 101 = yolact_base_config / yolact_im700_config
     # YOLACT++ (yolact_plus_*_config, the YOLACT++ rows of README.md:216-221): three scales per level x three aspect ratios,
@@ -43,6 +47,22 @@ class YolactConfig:
     dcn_interval: int = 1
     use_maskiou: bool = False
     backbone: str = "resnet"           # "darknet53": yolact_darknet53_config (DarkNetBackbone([1, 2, 8, 8, 4]), LeakyReLU(0.1))
+
+    def __post_init__(self):
+        for k in ("use_fast_nms", "use_cross_class_nms"):
+            if not isinstance(getattr(self, k), (bool, np.bool_)):
+                raise TypeError("YolactConfig.%s must be a bool, got %r" % (k, getattr(self, k)))
+        cap = self.nms_trad_cap
+        if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or cap < 64 or cap > 2048 or cap % 64:
+            raise ValueError("YolactConfig.nms_trad_cap must be a multiple of 64 in [64, 2048], got %r" % (cap,))
+        if self.nms_second_threshold and self.nms_mode != 0:
+            raise ValueError("YolactConfig.nms_second_threshold is an argument of fast_nms only: it cannot be combined with "
+                             "use_cross_class_nms=True or use_fast_nms=False")
+
+    @property
+    def nms_mode(self):
+        """The engine's `nms_mode`, chosen as upstream Detect.detect() chooses: 0 fast_nms, 1 cc_fast_nms, 2 traditional_nms."""
+        return nms_mode_of(self.use_fast_nms, self.use_cross_class_nms, warn=False)
 
     @property
     def num_priors(self):
@@ -79,6 +99,21 @@ class YolactConfig:
     def im700():
         """yolact_im700_config: ResNet101-FPN at 700, pred_scales = int(s / 550 * 700)."""
         return YolactConfig(max_size=700, pred_scales=tuple(int(s / 550 * 700) for s in (24, 48, 96, 192, 384)), depth=101)
+
+
+def nms_mode_of(use_fast_nms, use_cross_class_nms, warn=True):
+    """Upstream Detect.detect(): `if cfg.use_cross_class_nms: cc_fast_nms` / `elif cfg.use_fast_nms: fast_nms` / `else: traditional_nms`, where
+    traditional_nms asserts (here: warns, as eval.py's users see it) that a cross-class traditional NMS does not exist and runs per class."""
+    if use_fast_nms:
+        return 1 if use_cross_class_nms else 0
+    if use_cross_class_nms and warn:
+        import warnings
+        warnings.warn("cross-class traditional NMS is not implemented (upstream has none either): running traditional per-class NMS")
+    return 2
+
+
+class NmsCapOverflow(RuntimeError):
+    """Traditional NMS met a class with more candidates than nms_trad_cap in a way that can change the result: raise nms_trad_cap."""
 
 
 def make_priors(conv_h, conv_w, scales, max_size, ars, square=True):
@@ -149,9 +184,25 @@ class Yolact(Engine):
         self._load(state_dict)
         for k in ("nms_conf_thresh", "nms_thresh", "nms_top_k", "max_num_detections", "nms_second_threshold", "conv_split_k"):
             self.set_param(k, float(getattr(cfg, k)))
+        mode = nms_mode_of(cfg.use_fast_nms, cfg.use_cross_class_nms)
+        if mode:  # the default mode sets nothing: its parameter table is what it was
+            self.set_param("nms_mode", float(mode))
+            self.set_param("nms_trad_cap", float(cfg.nms_trad_cap))
+            self.set_param("max_size", float(cfg.max_size))   # traditional NMS runs on boxes * cfg.max_size, as upstream scales them
         self._d_in = _ffi.DeviceBuffer((max_batch, self.size, self.size, 3))
         self._forward_id = 0
         self._pp_key = None
+
+    @property
+    def nms_mode(self):
+        """the engine's current `nms_mode` parameter (0 fast, 1 cross-class fast, 2 traditional): read back from the engine, so a caller
+        who switches the mode with set_param is checked by check_nms_overflow as one who chose it in the config"""
+        return int(self.param("nms_mode", 0))
+
+    @property
+    def nms_trad_cap(self):
+        """the engine's current `nms_trad_cap` parameter (1024, the engine's default, while nothing has set it)"""
+        return int(self.param("nms_trad_cap", 1024))
 
     # -- weights -------------------------------------------------------------------------------
     def _set_conv(self, name, w_oihw, scale=None, shift=None, pad_cin_to=None):
@@ -309,6 +360,7 @@ class Yolact(Engine):
         self.forward_device(n)
         self.sync()
         cnt = self.fetch("det.count", n)
+        total = self.check_nms_overflow(n)
         box, score, cls, coeff, prior = (self.fetch(k, n) for k in ("det.box", "det.score", "det.class", "det.coeff", "det.prior"))
         proto = self.fetch("proto", n)
         out = []
@@ -317,7 +369,21 @@ class Yolact(Engine):
             det = None if c == 0 else dict(box=box[i, :c], mask=coeff[i, :c], score=score[i, :c], proto=proto[i],
                                            prior=prior[i, :c], **{"class": cls[i, :c]})
             out.append({"detection": det, "net": self, "_index": i, "_forward": self._forward_id})
+            if total is not None:  # survivors of the suppression pass before the cut to max_num_detections (cross-class / traditional NMS)
+                out[-1]["nms_total"] = int(total[i])
         return out
+
+    def check_nms_overflow(self, n):
+        """After a synchronised forward in nms_mode 1 / 2: det.nms_total [n], or NmsCapOverflow if the traditional mode's per-class capacity
+        may have changed an image's result (det.nms_overflow).  None in the default mode, which has neither buffer."""
+        if not self.nms_mode:
+            return None
+        over = self.fetch("det.nms_overflow", n)
+        if over.any():
+            raise NmsCapOverflow("traditional NMS: a class of image(s) %s holds more than nms_trad_cap = %d candidates and fewer than "
+                                 "max_num_detections of those survived; raise nms_trad_cap (at most 2048)"
+                                 % (np.nonzero(over)[0].tolist(), self.nms_trad_cap))
+        return self.fetch("det.nms_total", n)
 
 
 def postprocess(det_output, w, h, batch_idx=0, score_threshold=0.0):
