@@ -516,6 +516,15 @@ int isegmi_op_yolo_select(int nl, int N, const float* const* d_heads, const int3
 /* darknet's upsample + route: d_out [N][2 Hc][2 Wc][Cc + Cs] = [d_coarse[n][y / 2][x / 2] | d_skip[n][y][x]]; Cc, Cs multiples of 32.  NULL pointers and
  * sizes <= 0 are refused before any launch. */
 int isegmi_op_concat_up2x(const float* d_coarse, int N, int Hc, int Wc, int Cc, const float* d_skip, int Cs, float* d_out, void* stream);
+/* darknet's [maxpool] (csrc/yolo_pool.hip), NHWC fp32: d_out [N][(H - 1) / stride + 1][(W - 1) / stride + 1][C]; the window of output o
+ * starts at o * stride - (size - 1) / 2 (integer divisions: an even size pads on the bottom / right only).  zero_pad 0: taps outside the map are skipped
+ * (darknet); 1: each contributes +0.0f (ZeroPad2d + MaxPool2d of the PyTorch ports).  The maximum is isegmi_op_maxpool's (v > m ? v : m from -inf: the
+ * largest non-NaN tap, -inf where there is none); with zero_pad 0, stride 1 and an odd size the result is bit-identical to isegmi_op_maxpool(size, 1,
+ * size / 2).  C % 4 == 0, size 1..13, stride 1..2; NULL pointers and sizes outside these sets are refused before any launch. */
+int isegmi_op_maxpool_darknet(const float* d_in, int N, int H, int W, int C, int size, int stride, int zero_pad, float* d_out, void* stream);
+/* The SPP block of yolov3-spp as one launch: d_out [N][H][W][4 C] = [mp13 | mp9 | mp5 | d_in] (route layers = -1, -3, -5, -6), mpK =
+ * isegmi_op_maxpool_darknet(size K, stride 1, zero_pad) as values.  C % 32 == 0, H and W 1..32; anything else is refused before any launch. */
+int isegmi_op_spp_concat(const float* d_in, int N, int H, int W, int C, int zero_pad, float* d_out, void* stream);
 
 /* ---- ViT operators (csrc/vit_ops.hip states every operation order, tests/vit_ref.py restates it).  fp32, finite inputs only: NaN and
  * inf are outside these contracts.  Pointers 16-byte aligned.

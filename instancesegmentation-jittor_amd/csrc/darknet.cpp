@@ -36,4 +36,31 @@ int darknet_backbone(Engine& e, const std::string& prefix, const float* d_images
     return ISEGMI_OK;
 }
 
+// The trunk of yolov3-tiny: <prefix>conv0..6, 3x3 + BN + LeakyReLU(0.1) to 16 (stored as 32: the host pads conv0's rows and conv1's input
+// channels with zeros, as the image is padded), 32, 64, 128, 256, 512, 1024 channels; a darknet 2 / 2 max-pool after conv0..4, a 2 / 1 pool after conv5.
+// *skip = conv4's output (256 channels, stride 16), *top = conv6's (1024, stride 32).
+int darknet_tiny_backbone(Engine& e, const std::string& prefix, const float* d_images, int N, int zero_pad, Tensor* skip, Tensor* top) {
+    if (e.fp16) { set_error("the yolov3-tiny trunk runs in fp32 only"); return ISEGMI_ERR_STATE; }
+    Tensor x;
+    TRY(eng_act(e, "input32", N, e.H, e.W, 32, &x));
+    TRY(pad_c3_c32_launch(d_images, (int64_t)N * e.H * e.W, x.d, e.cur));
+    TRY(eng_input_consumed(e));
+    for (int i = 0; i < 7; ++i) {
+        const std::string nm = "conv" + std::to_string(i);
+        Tensor y;
+        TRY(eng_conv(e, prefix + nm, x, 1, 1, 3, nullptr, "trunk." + nm, &y));
+        if (i == 4) *skip = y;
+        x = y;
+        if (i < 6) {
+            const int stride = i < 5 ? 2 : 1;
+            TRY(eng_act(e, "trunk.pool" + std::to_string(i), N, (y.H - 1) / stride + 1, (y.W - 1) / stride + 1, y.C, &x));
+            OpScope op(e, e.cur, "maxpool_darknet", (double)(y.numel() + x.numel()) * 4);
+            TRY(maxpool_darknet_launch(y.d, N, y.H, y.W, y.C, 2, stride, zero_pad, x.d, e.cur));
+        }
+    }
+    *top = x;
+    eng_mark(e, "trunk");
+    return ISEGMI_OK;
+}
+
 }  // namespace isegmi

@@ -303,6 +303,8 @@ int eng_gn(Engine& e, const std::string& layer, Tensor* x, const Tensor* residua
 
 // darknet.cpp: the Darknet-53 trunk of yolact_darknet53_config and YOLOv3 -> C[0..2] at strides 8, 16, 32; before_c3: waited on before C[0] is overwritten
 int darknet_backbone(Engine& e, const std::string& prefix, const float* d_images, int N, Tensor* C, hipEvent_t before_c3);
+// the seven-convolution trunk of yolov3-tiny -> *skip (256 channels, stride 16), *top (1024, stride 32); zero_pad: the pad switch of its max-pools
+int darknet_tiny_backbone(Engine& e, const std::string& prefix, const float* d_images, int N, int zero_pad, Tensor* skip, Tensor* top);
 int yolact_forward(Engine& e, const float* d_images, int N);
 int yolact_postprocess(Engine& e, int h, int w, const int32_t* h_image_hw = nullptr);
 // "lazy_coeffs" (yolact.cpp): the two row-range views of the fused head, whether a forward of N images takes the lazy schedule, and the fill of headcat's

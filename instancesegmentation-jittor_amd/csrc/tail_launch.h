@@ -66,6 +66,10 @@ int yolo_select_launch(int nl, int N, const float* const* d_heads, const int* gr
                        float* d_out_scores, int* d_out_labels, int* d_out_cnt, int* d_out_total, hipStream_t st);
 int concat_up2x_launch(const float* coarse, int N, int Hc, int Wc, int Cc, const float* skip, int Cs, float* out, hipStream_t st);
 
+// ---- csrc/yolo_pool.hip
+int maxpool_darknet_launch(const float* in, int N, int H, int W, int C, int size, int stride, int zero_pad, float* out, hipStream_t st);
+int spp_concat_launch(const float* in, int N, int H, int W, int C, int zero_pad, float* out, hipStream_t st);
+
 // ---- csrc/keypoint_ops.hip
 int keypoint_heatmap_launch(const float* in, int64_t R, int Hi, int Wi, int K, float* out, hipStream_t st);
 int keypoint_decode_launch(const float* heat, const float* boxes, const int* count, int N, int cap, int S, int K, float* kpt, float* kscore, hipStream_t st);

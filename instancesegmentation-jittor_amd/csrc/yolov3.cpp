@@ -7,28 +7,43 @@
 //
 // Params: yolo_conf_thresh (0.5), yolo_nms_thresh (0.4), yolo_pre_nms_top_n (1024, 1..1024), yolo_multi_label (1), yolo_min_wh (0), detections_per_img (100),
 // detections_cap, nms_ge / nms_plus_one (the host sets 0: plain areas) / nms_index_order; yolo_anchor0..17 = the anchors [3][3][2] in pixels, stride 32 first.  fp16 and graph are refused.
+//
+// Variants ([UPSTREAM-RECALL] the public yolov3-spp.cfg / yolov3-tiny.cfg): yolo_variant 0 (default) the graph above; 1 yolov3-spp:
+// head 0 is conv0, conv1, conv2, spp_concat (2048 channels), head.0.spp (1x1 -> 512), conv3 .. conv6; 2 yolov3-tiny: darknet_tiny_backbone, head.0.conv0
+// (1x1 1024 -> 256, the branch), conv1 (3x3 -> 512), conv2 (predictor); head.1.route (1x1 -> 128), concat_up2x with the stride-16 map (384), head.1.conv0
+// (3x3 -> 256), conv1 (predictor): two levels, strides 32 and 16, yolo_anchor0..11.  yolo_pool_zero_pad (0): 1 lets the out-of-range taps of the variants'
+// max-pools count as 0 (csrc/yolo_pool.hip).  Both are read at every forward.
 #include <string.h>
 
 #include "engine.h"
 
 namespace isegmi {
 
-constexpr int YOLO_LEVELS = 3, YOLO_A = 3;
+constexpr int YOLO_LEVELS = 3, YOLO_A = 3;   // YOLO_LEVELS: the most a variant has
 
-static int yolov3_forward(Engine& e, const float* d_images, int N) {
-    e.cur = e.stream;
+// yolov3 (spp 0) and yolov3-spp (spp 1): Darknet-53 and three heads; spp puts spp_concat and head.0.spp (1x1 2048 -> 512) between conv2 and conv3 of head 0
+static int yolov3_heads(Engine& e, const float* d_images, int N, bool spp, int zero_pad, Tensor* head) {
     hipStream_t st = e.stream;
-    eng_mark(e, "start");
     Tensor C[3];
     TRY(darknet_backbone(e, "backbone.", d_images, N, C, nullptr));
 
-    Tensor head[YOLO_LEVELS], x = C[2];
+    Tensor x = C[2];
     for (int s = 0; s < YOLO_LEVELS; ++s) {
         const std::string hn = "head." + std::to_string(s);
         Tensor t = x, u;
         for (int i = 0; i < 5; ++i) {
             TRY(eng_conv(e, hn + ".conv" + std::to_string(i), t, 1, i & 1, 3, nullptr, hn + ".t" + std::to_string(i), &u));
             t = u;
+            if (spp && s == 0 && i == 2) {
+                Tensor cat;
+                TRY(eng_act(e, "head.0.spp_cat", N, t.H, t.W, 4 * t.C, &cat));
+                {
+                    OpScope op(e, st, "spp_concat (max-pool 5 / 9 / 13 + route)", 5.0 * (double)t.numel() * 4);
+                    TRY(spp_concat_launch(t.d, N, t.H, t.W, t.C, zero_pad, cat.d, st));
+                }
+                TRY(eng_conv(e, "head.0.spp", cat, 1, 0, 3, nullptr, "head.0.spp", &u));
+                t = u;
+            }
         }
         const Tensor branch = t;   // conv4's output: the predictor pair and the next head's route both read it
         TRY(eng_conv(e, hn + ".conv5", branch, 1, 1, 3, nullptr, hn + ".t5", &u));
@@ -44,21 +59,53 @@ static int yolov3_forward(Engine& e, const float* d_images, int N) {
             TRY(concat_up2x_launch(r.d, N, r.H, r.W, r.C, skip.d, skip.C, x.d, st));
         }
     }
+    return ISEGMI_OK;
+}
+
+// yolov3-tiny: the seven-convolution trunk (darknet.cpp) and two heads.  head.0.conv0 (1x1 -> 256) is the branch; head 1 reads
+// concat(up2x(head.1.route(branch)), the trunk's stride-16 map), the upsampled half first (route layers = -1, 8)
+static int yolov3_tiny_heads(Engine& e, const float* d_images, int N, int zero_pad, Tensor* head) {
+    hipStream_t st = e.stream;
+    Tensor skip, top, branch, u, r, x;
+    TRY(darknet_tiny_backbone(e, "backbone.", d_images, N, zero_pad, &skip, &top));
+    TRY(eng_conv(e, "head.0.conv0", top, 1, 0, 3, nullptr, "head.0.t0", &branch));
+    TRY(eng_conv(e, "head.0.conv1", branch, 1, 1, 3, nullptr, "head.0.t1", &u));
+    TRY(eng_conv(e, "head.0.conv2", u, 1, 0, 0, nullptr, "yolo.head0", &head[0]));
+    TRY(eng_conv(e, "head.1.route", branch, 1, 0, 3, nullptr, "head.1.route", &r));
+    if (skip.H != 2 * r.H || skip.W != 2 * r.W) { set_error("yolov3: the trunk map is not twice the routed map (canvas sides must be multiples of 32)"); return ISEGMI_ERR_STATE; }
+    TRY(eng_act(e, "head.1.cat", N, skip.H, skip.W, r.C + skip.C, &x));
+    {
+        OpScope op(e, st, "concat_up2x (upsample + route)", 2.0 * (double)x.numel() * 4);
+        TRY(concat_up2x_launch(r.d, N, r.H, r.W, r.C, skip.d, skip.C, x.d, st));
+    }
+    TRY(eng_conv(e, "head.1.conv0", x, 1, 1, 3, nullptr, "head.1.t0", &u));
+    TRY(eng_conv(e, "head.1.conv1", u, 1, 0, 0, nullptr, "yolo.head1", &head[1]));
+    return ISEGMI_OK;
+}
+
+static int yolov3_forward(Engine& e, const float* d_images, int N, int variant) {
+    e.cur = e.stream;
+    hipStream_t st = e.stream;
+    eng_mark(e, "start");
+    const int L = variant == 2 ? 2 : YOLO_LEVELS;
+    const int zero_pad = e.param("yolo_pool_zero_pad", 0.0f) != 0.0f ? 1 : 0;
+    Tensor head[YOLO_LEVELS];
+    if (variant == 2) TRY(yolov3_tiny_heads(e, d_images, N, zero_pad, head));
+    else TRY(yolov3_heads(e, d_images, N, variant == 1, zero_pad, head));
     eng_mark(e, "heads");
 
     // ---- the tail
-    if (head[0].C % YOLO_A || head[0].C / YOLO_A < 6 || head[1].C != head[0].C || head[2].C != head[0].C) {
-        set_error("yolov3: head.<s>.conv6 must have 3 * (5 + classes) output channels, the same on every head");
+    if (head[0].C % YOLO_A || head[0].C / YOLO_A < 6 || head[1].C != head[0].C || head[L - 1].C != head[0].C) {
+        set_error("yolov3: the predictors (head.<s>.conv6; tiny: head.0.conv2, head.1.conv1) must have 3 * (5 + classes) output channels, the same on every head");
         return ISEGMI_ERR_STATE;
     }
     const int nclass = head[0].C / YOLO_A - 5;
     const int top_n = (int)e.param("yolo_pre_nms_top_n", 1024.0f);
     const int dpi = (int)e.param("detections_per_img", 100), cap = maskrcnn_det_cap(e);
-    const int L = YOLO_LEVELS;
     int grid[YOLO_LEVELS * 2], grid_max[YOLO_LEVELS * 2], strides[YOLO_LEVELS] = {32, 16, 8};
     const float* heads[YOLO_LEVELS];
     float anchors[YOLO_LEVELS * YOLO_A * 2];
-    for (int i = 0; i < YOLO_LEVELS * YOLO_A * 2; ++i) {
+    for (int i = 0; i < L * YOLO_A * 2; ++i) {
         const std::string k = "yolo_anchor" + std::to_string(i);
         if (e.params.count(k) == 0 || !(e.params[k] > 0.0f)) { set_error("parameter not set (or not positive): " + k); return ISEGMI_ERR_STATE; }
         anchors[i] = e.params[k];
@@ -115,6 +162,13 @@ extern "C" int isegmi_yolov3_forward(isegmi_engine* h, const float* d_images, in
     Engine& e = h->e;
     ARG_CHECK(e.kind == 5, "engine is not a YOLOv3 engine");
     ARG_CHECK(N > 0 && N <= e.max_batch, "batch size");
+    const float variant = e.param("yolo_variant", 0.0f), zp = e.param("yolo_pool_zero_pad", 0.0f);
+    if (variant != 0.0f && variant != 1.0f && variant != 2.0f) { set_error("yolov3: yolo_variant must be 0 (yolov3), 1 (yolov3-spp) or 2 (yolov3-tiny)"); return ISEGMI_ERR_ARG; }
+    if (zp != 0.0f && zp != 1.0f) { set_error("yolov3: yolo_pool_zero_pad must be 0 (out-of-range taps ignored) or 1 (they count as 0)"); return ISEGMI_ERR_ARG; }
+    if (variant == 2.0f && e.params.count("yolo_anchor12")) {
+        set_error("yolov3: yolo_anchor12 is set, but yolo_variant 2 (yolov3-tiny) has two levels: its anchors are yolo_anchor0..11");
+        return ISEGMI_ERR_ARG;
+    }
     if (e.param("fp16", 0.0f) != 0.0f || e.fp16) { set_error("yolov3: fp16 is not supported (fp32 only)"); return ISEGMI_ERR_ARG; }
     if (e.param("graph", 0.0f) != 0.0f) { set_error("yolov3: graph capture is not supported (graph must be 0)"); return ISEGMI_ERR_ARG; }
     const int top_n = (int)e.param("yolo_pre_nms_top_n", 1024.0f);
@@ -124,7 +178,7 @@ extern "C" int isegmi_yolov3_forward(isegmi_engine* h, const float* d_images, in
     if (!(nt > 0.0f)) { set_error("yolov3: yolo_nms_thresh must be positive"); return ISEGMI_ERR_ARG; }
     if (!(mw >= 0.0f)) { set_error("yolov3: yolo_min_wh must be a non-negative number"); return ISEGMI_ERR_ARG; }
     TRY(eng_wait_upload(e, d_images, (int64_t)N * e.H * e.W * 3 * 4, e.stream));
-    const int rc = yolov3_forward(e, d_images, N);
+    const int rc = yolov3_forward(e, d_images, N, (int)variant);
     e.cur = e.stream;
     if (rc == ISEGMI_OK) e.last_N = N;
     return rc;

@@ -173,6 +173,8 @@ SIGNATURES = {
     "isegmi_op_yolo_select_workspace": (L, [I, I, V, I, I, I]),
     "isegmi_op_yolo_select": (I, [I, I, V, V, V, V, I, I, I, F, I, F, I, I, V, L, V, V, V, V, V, V]),
     "isegmi_op_concat_up2x": (I, [V, I, I, I, I, V, I, V, V]),
+    "isegmi_op_maxpool_darknet": (I, [V, I, I, I, I, I, I, I, V, V]),
+    "isegmi_op_spp_concat": (I, [V, I, I, I, I, I, V, V]),
     "isegmi_op_attention": (I, [V, I, I, I, V, V]),
     "isegmi_op_layer_norm": (I, [V, L, I, L, V, V, F, V, L, V]),
     "isegmi_op_gelu": (I, [V, V, L, I, V]),

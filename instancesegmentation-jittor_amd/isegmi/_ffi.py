@@ -897,6 +897,26 @@ def concat_up2x(coarse, skip):
     return out.numpy()
 
 
+def maxpool_darknet(x, size, stride, zero_pad=0):
+    """isegmi_op_maxpool_darknet: x [N,H,W,C] -> [N,(H-1)//stride+1,(W-1)//stride+1,C]; zero_pad 0: taps outside the map are skipped, 1: they are 0."""
+    x = np.ascontiguousarray(x, np.float32)
+    N, H, W, Cc = x.shape
+    dx = DeviceBuffer.from_numpy(x)
+    out = DeviceBuffer((N, (H - 1) // max(int(stride), 1) + 1, (W - 1) // max(int(stride), 1) + 1, Cc)).poison()
+    check(lib().isegmi_op_maxpool_darknet(dx.ptr, N, H, W, Cc, int(size), int(stride), int(zero_pad), out.ptr, None))
+    return out.numpy()
+
+
+def spp_concat(x, zero_pad=0):
+    """isegmi_op_spp_concat: x [N,H,W,C] -> [N,H,W,4C] = [mp13 | mp9 | mp5 | x]."""
+    x = np.ascontiguousarray(x, np.float32)
+    N, H, W, Cc = x.shape
+    dx = DeviceBuffer.from_numpy(x)
+    out = DeviceBuffer((N, H, W, 4 * Cc)).poison()
+    check(lib().isegmi_op_spp_concat(dx.ptr, N, H, W, Cc, int(zero_pad), out.ptr, None))
+    return out.numpy()
+
+
 # ---------------------------------------------------------------- fp16 conv (configs[4])
 def pack_conv_weights_f16(desc, w_krsc):
     w = np.ascontiguousarray(w_krsc, np.float32)

@@ -5,7 +5,7 @@
   python -m isegmi.cli test_net --config-file cfg.yaml [--images dir] [--output results.json]
   python -m isegmi.cli pose2seg_test --weights random --anno person_keypoints.json --image-root DIR [--output segm.json] [--batch-size 8]
   python -m isegmi.cli pose2seg_test --weights random --keypoint-config kp.yaml --keypoint-weights random|FILE --anno images.json --image-root DIR
-  python -m isegmi.cli yolo_detect --cfg configs/yolov3.cfg --weights random|FILE.npz|FILE.weights --images DIR --output dets.json [--img-size 416]
+  python -m isegmi.cli yolo_detect --cfg configs/yolov3[-spp|-tiny].cfg --weights random|FILE.npz|FILE.weights --images DIR --output dets.json [--img-size 416] [--pool-pad ignore|zero]
   python -m isegmi.cli vit_classify --model vit_b16 --weights random|FILE.npz --images DIR --topk 5 --output preds.json [--img-size 224] [--num-classes 1000]
   python -m isegmi.cli coco_eval --gt instances.json --dt results.json --iou-type segm|bbox|keypoints [--cat-ids ...] [--max-dets ...] [--out stats.json]
 
@@ -263,6 +263,8 @@ def yolo_config(a):
         kw["bn_eps"] = a.bn_eps
     if a.best_class:
         kw["multi_label"] = False
+    if a.pool_pad is not None:
+        kw["pool_pad"] = a.pool_pad
     with open(a.cfg) as f:
         ycfg = parse_darknet_cfg(f.read(), **kw)
     if a.img_size:
@@ -282,7 +284,7 @@ def cmd_yolo_detect(a):
         raise SystemExit("yolo_detect: WORLD_SIZE=%d: multi-rank inference (world > 1) is not built for YOLOv3" % world)
     ycfg = yolo_config(a)
     if a.weights in ("", "random", None):
-        sd = yolov3_state_dict(1234, ycfg.classes)
+        sd = yolov3_state_dict(1234, ycfg.classes, ycfg.variant)
     elif a.weights.endswith(".npz"):
         sd = dict(np.load(a.weights))
     elif a.weights.endswith(".weights"):
@@ -399,7 +401,7 @@ def build_parser():
     p.add_argument("--keypoint-threshold", dest="keypoint_threshold", type=float, default=argparse.SUPPRESS,
                    help="with --keypoint-config: a keypoint is visible where its logit > this")
     y = sub.add_parser("yolo_detect", help="YOLOv3 detection over a directory of images -> bbox-only COCO json")
-    y.add_argument("--cfg", default="configs/yolov3.cfg", help="darknet yolov3.cfg (only this topology is built)")
+    y.add_argument("--cfg", default="configs/yolov3.cfg", help="darknet yolov3.cfg, yolov3-spp.cfg or yolov3-tiny.cfg (these three topologies are built)")
     y.add_argument("--weights", default="random", help="random (seeded synthetic weights), FILE.npz in this engine's names, or a darknet FILE.weights")
     y.add_argument("--images", required=True, help="directory of images; image_id = index in sorted order")
     y.add_argument("--img-size", dest="img_size", type=int, nargs="+", default=None, help="canvas side, or height and width (multiples of 32 in 32..1024; default: the cfg's)")
@@ -407,6 +409,8 @@ def build_parser():
     y.add_argument("--nms-thres", dest="nms_thres", type=float, default=None, help="class-wise NMS IoU threshold (default 0.4)")
     y.add_argument("--bn-eps", dest="bn_eps", type=float, default=None, help="BatchNorm epsilon of the fold: 1e-5 (default) or darknet's 1e-6")
     y.add_argument("--best-class", dest="best_class", action="store_true", help="one candidate per anchor, its best class, instead of every class over the threshold")
+    y.add_argument("--pool-pad", dest="pool_pad", choices=["ignore", "zero"], default=None,
+                   help="yolov3-spp / -tiny max-pools: a tap outside the map is skipped (ignore: darknet, default) or counts as 0 (zero: the PyTorch ports)")
     y.add_argument("--output", default="dets.json")
     y.add_argument("--batch-size", dest="batch_size", type=int, default=8)
     for q in (e, t, p, y):

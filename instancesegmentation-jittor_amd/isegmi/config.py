@@ -371,28 +371,49 @@ _NET_KEYS = (("batch", 1), ("subdivisions", 1), ("channels", 3), ("momentum", 0.
              ("steps", "400000,450000"), ("scales", ".1,.1"))
 
 
+_YOLO_TOPOLOGY = {"yolov3": "YOLOv3", "spp": "YOLOv3-SPP", "tiny": "YOLOv3-tiny"}
+
+
 def yolov3_sections(ycfg):
-    """The section list of yolov3.cfg for a YoloV3Config, from the public layer list: [(section, {key: str value})], [net] first."""
+    """The section list of yolov3.cfg / yolov3-spp.cfg / yolov3-tiny.cfg (ycfg.variant) for a YoloV3Config, from the public layer lists:
+    [(section, {key: str value})], [net] first.  A [yolo] section past ycfg.masks has no mask key."""
     def conv(filters, size, stride=1, bn=True):
         d = {"batch_normalize": "1"} if bn else {}
         d.update(size=str(size), stride=str(stride), pad="1", filters=str(filters), activation="leaky" if bn else "linear")
         return ("convolutional", d)
+
+    def pool(size, stride):
+        return ("maxpool", {"size": str(size), "stride": str(stride)})
+    anchors = ", ".join("%d,%d" % tuple(a) for a in ycfg.anchors)
+
+    def predictor(s):
+        d = {"mask": ",".join(str(i) for i in ycfg.masks[s])} if s < len(ycfg.masks) else {}
+        d.update(anchors=anchors, classes=str(ycfg.classes), num=str(len(ycfg.anchors)), jitter=".3", ignore_thresh=".7", truth_thresh="1", random="1")
+        return [conv(3 * (5 + ycfg.classes), 1, bn=False), ("yolo", d)]
     out = [("net", dict([("batch", "1"), ("subdivisions", "1"), ("width", str(ycfg.width)), ("height", str(ycfg.height))] + [(k, str(v)) for k, v in _NET_KEYS[2:]]))]
+    if ycfg.variant == "tiny":
+        for i in range(7):
+            out.append(conv(16 << i, 3))
+            if i < 6:
+                out.append(pool(2, 2 if i < 5 else 1))
+        out += [conv(256, 1), conv(512, 3)] + predictor(0)
+        out += [("route", {"layers": "-4"}), conv(128, 1), ("upsample", {"stride": "2"}), ("route", {"layers": "-1, 8"}), conv(256, 3)] + predictor(1)
+        return out
     out.append(conv(32, 3))
     for li, nb in enumerate((1, 2, 8, 8, 4)):
         ch = 32 << li
         out.append(conv(ch * 2, 3, 2))
         for _ in range(nb):
             out += [conv(ch, 1), conv(ch * 2, 3), ("shortcut", {"from": "-3", "activation": "linear"})]
-    anchors = ", ".join("%d,%d" % tuple(a) for a in ycfg.anchors)
     for s, m in enumerate((512, 256, 128)):
         if s:
             out += [("route", {"layers": "-4"}), conv(m, 1), ("upsample", {"stride": "2"}), ("route", {"layers": "-1, %d" % (61, 36)[s - 1]})]
         for i in range(6):
             out.append(conv(2 * m if i & 1 else m, 3 if i & 1 else 1))
-        out.append(conv(3 * (5 + ycfg.classes), 1, bn=False))
-        out.append(("yolo", {"mask": ",".join(str(i) for i in ycfg.masks[s]), "anchors": anchors, "classes": str(ycfg.classes), "num": str(len(ycfg.anchors)),
-                             "jitter": ".3", "ignore_thresh": ".7", "truth_thresh": "1", "random": "1"}))
+            if ycfg.variant == "spp" and s == 0 and i == 2:   # the SPP block: three stride-1 pools of conv2's output, routed together with it
+                out += [pool(5, 1), ("route", {"layers": "-2"}), pool(9, 1), ("route", {"layers": "-4"}), pool(13, 1), ("route", {"layers": "-1,-3,-5,-6"}),
+                        conv(512, 1)]
+        out += predictor(s)
     return out
 
 
@@ -418,10 +439,30 @@ def _cfg_sections(text):
     return out
 
 
+_CFG_STRUCTURAL = {"convolutional": ("batch_normalize", "filters", "size", "stride", "pad", "activation"), "shortcut": ("from", "activation"),
+                   "route": ("layers",), "upsample": ("stride",), "maxpool": ("size", "stride"), "yolo": ("mask", "classes", "num")}
+
+
+def _cfg_first_difference(secs, want):
+    """-> (index into secs[1:] of the first section that differs from `want`, its message), (len, None) when every section of the file matches."""
+    topo = want[0]
+    for i, (s, d) in enumerate(secs[1:]):
+        if i >= len(want[1]):
+            return i, "cfg section %d [%s]: past the end of the %s topology (%d layers)" % (i, s, topo, len(want[1]))
+        ws, wd = want[1][i]
+        got = {k: d.get(k, "0" if k == "batch_normalize" else None) for k in _CFG_STRUCTURAL[s]}
+        exp = {k: wd.get(k, "0" if k == "batch_normalize" else None) for k in _CFG_STRUCTURAL.get(ws, ())}
+        norm = lambda m: {k: (v.replace(" ", "") if isinstance(v, str) else v) for k, v in m.items()}
+        if s != ws or norm(got) != norm(exp):
+            return i, "cfg section %d [%s] %s: the %s topology has [%s] %s here" % (i, s, norm(got), topo, ws, norm(exp))
+    return len(secs) - 1, None
+
+
 def parse_darknet_cfg(text, **overrides):
-    """A darknet yolov3.cfg -> YoloV3Config (canvas from [net], classes / anchors / masks from the [yolo] sections; `overrides` set the inference
-    keys a .cfg does not carry).  Only the YOLOv3 topology is accepted: Darknet-53, three heads, A = 3.  Any other layer list -- yolov3-tiny and -spp
-    with their [maxpool] sections, another filter count, a missing route -- raises ValueError naming the first section that differs."""
+    """A darknet yolov3.cfg, yolov3-spp.cfg or yolov3-tiny.cfg -> YoloV3Config (canvas from [net], classes / anchors / masks from the [yolo] sections, the
+    variant from the layer list; `overrides` set the inference keys a .cfg does not carry).  Exactly these three topologies are accepted (DESIGN.md 17,
+    21).  The file is held against the one whose section list shares the longest prefix with it (yolov3 on a tie); any other layer list -- another filter
+    count or pool size, a missing route -- raises ValueError naming the first section that differs from that topology."""
     from .yolov3 import YoloV3Config
     secs = _cfg_sections(text)
     if not secs or secs[0][0] not in ("net", "network"):
@@ -429,35 +470,37 @@ def parse_darknet_cfg(text, **overrides):
     net = secs[0][1]
     yolos = [d for s, d in secs if s == "yolo"]
     for i, (s, _) in enumerate(secs[1:]):
-        if s not in ("convolutional", "shortcut", "route", "upsample", "yolo"):
-            raise ValueError("cfg section %d [%s]: not part of the YOLOv3 topology (Darknet-53 and three heads; yolov3-tiny / -spp are not built)" % (i, s))
-    if len(yolos) != 3:
-        raise ValueError("cfg: %d [yolo] sections; the YOLOv3 topology has three" % len(yolos))
+        if s not in _CFG_STRUCTURAL:
+            raise ValueError("cfg section %d [%s]: not part of the YOLOv3, YOLOv3-SPP or YOLOv3-tiny topology" % (i, s))
+    if not yolos:
+        raise ValueError("cfg: 0 [yolo] sections; the YOLOv3 topology has three")
     try:
         nums = [int(v) for v in yolos[0]["anchors"].replace(" ", "").split(",")]
         masks = tuple(tuple(int(v) for v in y["mask"].replace(" ", "").split(",")) for y in yolos)
-        ycfg = YoloV3Config(height=int(net["height"]), width=int(net["width"]), classes=int(yolos[0]["classes"]),
-                            anchors=tuple(zip(nums[0::2], nums[1::2])), masks=masks, **overrides)
+        base = dict(height=int(net["height"]), width=int(net["width"]), classes=int(yolos[0]["classes"]), anchors=tuple(zip(nums[0::2], nums[1::2])), masks=masks)
     except KeyError as e:
         raise ValueError("cfg: missing key %s in [net] / [yolo]" % e)
+    # the topology: the one the file follows furthest (the comparison needs no valid config: classes, anchors and masks are the file's own)
+    best = None
+    for variant in ("yolov3", "spp", "tiny"):
+        probe = YoloV3Config(variant=variant, **base)
+        at, msg = _cfg_first_difference(secs, (_YOLO_TOPOLOGY[variant], yolov3_sections(probe)[1:]))
+        if best is None or at > best[0]:
+            best = (at, msg, variant, probe)
+    _, msg, variant, probe = best
+    topo, nyolo = _YOLO_TOPOLOGY[variant], len(probe.strides)
+    if len(yolos) != nyolo:
+        raise ValueError("cfg: %d [yolo] sections; the %s topology has %s" % (len(yolos), topo, ("two", "three")[nyolo - 2]))
     if any(len(m) != 3 for m in masks):
         raise ValueError("cfg [yolo] mask=%s: three anchors per head are built (A = 3)" % (",".join(map(str, next(m for m in masks if len(m) != 3)))))
     for y in yolos[1:]:
         if y.get("anchors", "").replace(" ", "") != yolos[0]["anchors"].replace(" ", "") or y.get("classes") != yolos[0]["classes"]:
-            raise ValueError("cfg [yolo]: the three sections must share anchors and classes")
+            raise ValueError("cfg [yolo]: the %s sections must share anchors and classes" % ("two", "three")[nyolo - 2])
+    ycfg = YoloV3Config(variant=variant, **dict(base, **overrides))
     ycfg.validate()
+    if msg:
+        raise ValueError(msg)
     want = yolov3_sections(ycfg)[1:]
-    structural = {"convolutional": ("batch_normalize", "filters", "size", "stride", "pad", "activation"), "shortcut": ("from", "activation"),
-                  "route": ("layers",), "upsample": ("stride",), "yolo": ("mask", "classes", "num")}
-    for i, (s, d) in enumerate(secs[1:]):
-        if i >= len(want):
-            raise ValueError("cfg section %d [%s]: past the end of the YOLOv3 topology (%d layers)" % (i, s, len(want)))
-        ws, wd = want[i]
-        got = {k: d.get(k, "0" if k == "batch_normalize" else None) for k in structural[s]}
-        exp = {k: wd.get(k, "0" if k == "batch_normalize" else None) for k in structural.get(ws, ())}
-        norm = lambda m: {k: (v.replace(" ", "") if isinstance(v, str) else v) for k, v in m.items()}
-        if s != ws or norm(got) != norm(exp):
-            raise ValueError("cfg section %d [%s] %s: the YOLOv3 topology has [%s] %s here" % (i, s, norm(got), ws, norm(exp)))
     if len(secs) - 1 != len(want):
-        raise ValueError("cfg: %d layers; the YOLOv3 topology has %d (it ends after section %d [%s])" % (len(secs) - 1, len(want), len(secs) - 2, secs[-1][0]))
+        raise ValueError("cfg: %d layers; the %s topology has %d (it ends after section %d [%s])" % (len(secs) - 1, topo, len(want), len(secs) - 2, secs[-1][0]))
     return ycfg

@@ -193,18 +193,67 @@ def yolov3_layers(classes=80):
     return out
 
 
-def yolov3_state_dict(seed=1234, classes=80):
+YOLO_VARIANTS = ("yolov3", "spp", "tiny")
+
+
+def yolov3_spp_layers(classes=80):
+    """The 76 convolutions of yolov3-spp.cfg in file order: yolov3's, with head.0.spp (1x1 2048 -> 512 on [mp13 | mp9 | mp5 | x]) between head.0.conv2 and
+    head.0.conv3."""
+    out = yolov3_layers(classes)
+    at = [l[0] for l in out].index("head.0.conv3")
+    out.insert(at, ("head.0.spp", "head.0.spp_bn", 512, 2048, 1))
+    assert len(out) == 76
+    return out
+
+
+def yolov3_tiny_layers(classes=80):
+    """The 13 convolutions of yolov3-tiny.cfg in file order: the trunk backbone.conv0..6 (3x3), head.0.conv0 (1x1 -> 256, the branch), conv1
+    (3x3 -> 512), conv2 (predictor); head.1.route (1x1 256 -> 128), head.1.conv0 (3x3 on concat(route 128 | trunk 256) -> 256), conv1 (predictor)."""
+    out, cin = [], 3
+    for i in range(7):
+        out.append(("backbone.conv%d" % i, "backbone.bn%d" % i, 16 << i, cin, 3))
+        cin = 16 << i
+    out += [("head.0.conv0", "head.0.bn0", 256, 1024, 1), ("head.0.conv1", "head.0.bn1", 512, 256, 3), ("head.0.conv2", None, 3 * (5 + classes), 512, 1),
+            ("head.1.route", "head.1.route_bn", 128, 256, 1), ("head.1.conv0", "head.1.bn0", 256, 384, 3), ("head.1.conv1", None, 3 * (5 + classes), 256, 1)]
+    assert len(out) == 13
+    return out
+
+
+def yolo_layers(variant="yolov3", classes=80):
+    """The convolutions of a variant's .cfg in file order, as yolov3_layers lists them."""
+    if variant not in YOLO_VARIANTS:
+        raise ValueError("variant=%r: yolov3, spp or tiny" % (variant,))
+    return {"yolov3": yolov3_layers, "spp": yolov3_spp_layers, "tiny": yolov3_tiny_layers}[variant](classes)
+
+
+# Recorded calibration of yolov3-tiny's random weights, as above (found with the CPU reference on seeded uniform images at 64 x 96, 96 x 64 and 32 x 32):
+# seven conv + BN layers without a shortcut neither grow nor damp the maps much, so only the heads' BN weights are scaled.
+YOLO_TINY_HEAD_BN_SCALE = (0.8, 0.8)
+
+
+def yolov3_state_dict(seed=1234, classes=80, variant="yolov3"):
     """Seeded random YOLOv3 weights: the trunk is darknet53_state_dict's, the heads are head.<s>.conv0..6 / head.<s>.bn0..5 and head.<s>.route /
-    head.<s>.route_bn (s = 1, 2).  The predictors carry the recorded gains / biases above."""
+    head.<s>.route_bn (s = 1, 2).  The predictors carry the recorded gains / biases above.  variant "spp" adds head.0.spp / head.0.spp_bn (drawn after
+    everything else, so the other layers are the yolov3 ones of the same seed); "tiny" draws yolov3_tiny_layers' names."""
     rng = np.random.default_rng(seed)
     sd = {}
-    darknet53_state_dict(rng, sd, "backbone.")
-    for name, bn, cout, cin, k in yolov3_layers(classes):
+    layers = yolo_layers(variant, classes)
+    if variant == "tiny":
+        head_scale = YOLO_TINY_HEAD_BN_SCALE
+    else:
+        head_scale = YOLO_HEAD_BN_SCALE
+        darknet53_state_dict(rng, sd, "backbone.")
+        layers = [l for l in layers if l[0] != "head.0.spp"] + [l for l in layers if l[0] == "head.0.spp"]
+    for name, bn, cout, cin, k in layers:
+        if name.startswith("backbone.") and variant != "tiny":
+            continue
         if name.startswith("backbone."):
+            sd[name + ".weight"] = _conv(rng, cout, cin, k)
+            _bn(rng, sd, bn, cout)
             continue
         if bn is not None:
             sd[name + ".weight"] = _conv(rng, cout, cin, k)
-            _bn(rng, sd, bn, cout, YOLO_HEAD_BN_SCALE[int(name.split('.')[1])])
+            _bn(rng, sd, bn, cout, head_scale[int(name.split('.')[1])])
             continue
         w = _conv(rng, cout, cin, k).reshape(3, 5 + classes, cin, k, k)
         b = (rng.standard_normal((3, 5 + classes)) * 0.1).astype(np.float32)
@@ -219,13 +268,14 @@ def yolov3_state_dict(seed=1234, classes=80):
 DARKNET_WEIGHTS_HEADER = (0, 2, 0)   # major, minor, revision: minor >= 2 means a 64-bit `seen` follows
 
 
-def save_darknet_weights(sd, path, classes=80, seen=0):
+def save_darknet_weights(sd, path, classes=80, seen=0, variant="yolov3"):
     """Write a state dict as a darknet .weights file: header (three int32, then int64 `seen`), then per convolution in cfg order bias (BN: beta), and
-    for a BN layer gamma, running mean, running var, then the weight [Cout][Cin][R][S]; all float32, little endian."""
+    for a BN layer gamma, running mean, running var, then the weight [Cout][Cin][R][S]; all float32, little endian.  variant: whose layer list
+    (yolo_layers) the file follows."""
     with open(path, "wb") as f:
         f.write(np.asarray(DARKNET_WEIGHTS_HEADER, "<i4").tobytes())
         f.write(np.asarray([seen], "<i8").tobytes())
-        for name, bn, cout, cin, k in yolov3_layers(classes):
+        for name, bn, cout, cin, k in yolo_layers(variant, classes):
             parts = [sd[bn + ".bias"], sd[bn + ".weight"], sd[bn + ".running_mean"], sd[bn + ".running_var"]] if bn else [sd[name + ".bias"]]
             w = np.asarray(sd[name + ".weight"], np.float32)
             if w.shape != (cout, cin, k, k) or any(np.asarray(p).shape != (cout,) for p in parts):
@@ -235,9 +285,11 @@ def save_darknet_weights(sd, path, classes=80, seen=0):
 
 
 def load_darknet_weights(path, cfg=None):
-    """Read a darknet yolov3 .weights file into this project's state-dict names (BN statistics unfolded: YoloV3 folds them with cfg.bn_eps).  The file must
-    hold exactly the 75 convolutions of the topology: one that ends early or has floats left over raises and names the layer."""
+    """Read a darknet yolov3 / yolov3-spp / yolov3-tiny .weights file (cfg.variant; yolov3 without a cfg) into this project's state-dict names (BN
+    statistics unfolded: YoloV3 folds them with cfg.bn_eps).  The file must hold exactly the convolutions of the topology (75 / 76 / 13): one that ends
+    early or has floats left over raises and names the layer."""
     classes = 80 if cfg is None else cfg.classes
+    layers = yolo_layers("yolov3" if cfg is None else cfg.variant, classes)
     raw = np.fromfile(path, np.uint8)
     if raw.size < 20:
         raise ValueError("%s: shorter than the 20-byte darknet header" % path)
@@ -257,7 +309,7 @@ def load_darknet_weights(path, cfg=None):
         a = data[off:off + n].astype(np.float32)
         off += n
         return a
-    for name, bn, cout, cin, k in yolov3_layers(classes):
+    for name, bn, cout, cin, k in layers:
         if bn:
             for key in (".bias", ".weight", ".running_mean", ".running_var"):
                 sd[bn + key] = take(cout, name + " (BN" + key + ")")
@@ -265,7 +317,7 @@ def load_darknet_weights(path, cfg=None):
             sd[name + ".bias"] = take(cout, name + " (bias)")
         sd[name + ".weight"] = take(cout * cin * k * k, name + " (weight)").reshape(cout, cin, k, k)
     if off != data.size:
-        raise ValueError("%s: file too long: %d floats left after the last layer head.2.conv6 (another topology or class count?)" % (path, data.size - off))
+        raise ValueError("%s: file too long: %d floats left after the last layer %s (another topology or class count?)" % (path, data.size - off, layers[-1][0]))
     return sd
 
 

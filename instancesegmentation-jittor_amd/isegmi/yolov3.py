@@ -1,7 +1,8 @@
 """YOLOv3 inference, host side ([UPSTREAM-RECALL] the public yolov3.cfg / COCO-80 model, unverified: the reference's yolo.jittor directory is
 empty).  `net = YoloV3(sd, H, W)`; `dets = net(batch)` -> per image boxes (canvas coordinates), scores, labels 1..C.  `YoloDetector(...).detect(images)`
 adds the letterbox front end and maps the boxes back to the original images.  All numerics run in libisegmi.so (engine kind 5); this module moves
-config, weights and results across the C ABI.  The device front end (preprocess_u8) is not built for this model: the letterbox runs on the host."""
+config, weights and results across the C ABI.  The device front end (preprocess_u8) is not built for this model: the letterbox runs on the host.
+YoloV3Config.variant selects yolov3, yolov3-spp or yolov3-tiny; pool_pad is the pad switch of the two variants' max-pools."""
 import ctypes as C
 from dataclasses import dataclass
 
@@ -9,20 +10,24 @@ import numpy as np
 
 from . import _ffi
 from .engine import DetectionBlock, Engine
-from .weights import fold_batchnorm, to_krsc, yolov3_layers
+from .weights import YOLO_VARIANTS, fold_batchnorm, to_krsc, yolo_layers
 
 YOLO_MAX_TOP_N = 1024    # csrc/yolo_ops.hip YOLO_KCAP
 YOLO_MAX_CLASSES = 255   # the class-wise NMS holds 256 labels with the background
 YOLO_STRIDES = (32, 16, 8)
 YOLO_ANCHORS = ((10, 13), (16, 30), (33, 23), (30, 61), (62, 45), (59, 119), (116, 90), (156, 198), (373, 326))
 YOLO_MASKS = ((6, 7, 8), (3, 4, 5), (0, 1, 2))
+YOLO_TINY_ANCHORS = ((10, 14), (23, 27), (37, 58), (81, 82), (135, 169), (344, 319))
+YOLO_TINY_MASKS = ((3, 4, 5), (0, 1, 2))   # this project's yolov3-tiny.cfg; pjreddie's original has 1,2,3 in the second
 
 
 @dataclass(frozen=True)
 class YoloV3Config:
     """yolov3.cfg inference constants.  anchors: the cfg's nine (w, h) pairs in pixels; masks: the anchors of the [yolo] layers in file order (stride 32
     first).  multi_label True: every class with objectness x class > conf_thresh is a candidate (darknet, ultralytics); False: the best class only
-    (the PyTorch-YOLOv3 ports).  bn_eps: 1e-5 (the PyTorch ports); darknet's own normaliser uses 1e-6."""
+    (the PyTorch-YOLOv3 ports).  bn_eps: 1e-5 (the PyTorch ports); darknet's own normaliser uses 1e-6.  variant: "yolov3", "spp"
+    (yolov3-spp.cfg) or "tiny" (yolov3-tiny.cfg: two [yolo] layers, strides 32 and 16; YoloV3Config.tiny() has its anchors and masks).  pool_pad: what a
+    tap outside the map is to the variants' max-pools -- "ignore" (darknet: skipped) or "zero" (the PyTorch ports' ZeroPad2d + MaxPool2d: a 0)."""
     height: int = 416
     width: int = 416
     classes: int = 80
@@ -39,13 +44,24 @@ class YoloV3Config:
     nms_plus_one: int = 0          # plain areas
     nms_output_order: str = "score"
     bn_eps: float = 1e-5
+    variant: str = "yolov3"
+    pool_pad: str = "ignore"
+
+    @classmethod
+    def tiny(cls, **kw):
+        return cls(**dict(dict(variant="tiny", anchors=YOLO_TINY_ANCHORS, masks=YOLO_TINY_MASKS), **kw))
 
     @property
     def det_cap(self):
         return max(self.detections_per_img, self.detections_cap)
 
+    @property
+    def strides(self):
+        """The strides of the [yolo] layers in file order."""
+        return YOLO_STRIDES[:2] if self.variant == "tiny" else YOLO_STRIDES
+
     def level_anchors(self):
-        """[3][3][2] float32: the anchors of head s (s = 0 at stride 32)."""
+        """[levels][3][2] float32: the anchors of head s (s = 0 at stride 32)."""
         return np.asarray([[self.anchors[i] for i in m] for m in self.masks], np.float32)
 
     def validate(self, H=None, W=None):
@@ -55,8 +71,13 @@ class YoloV3Config:
                 raise ValueError("%s=%d: canvas sides are multiples of 32 in 32..1024" % (key, v))
         if not 1 <= self.classes <= YOLO_MAX_CLASSES:
             raise ValueError("classes=%d: 1..%d classes are built" % (self.classes, YOLO_MAX_CLASSES))
-        if len(self.masks) != 3 or any(len(m) != 3 for m in self.masks):
-            raise ValueError("masks=%r: three [yolo] layers of three anchors each are built (A = 3)" % (self.masks,))
+        if self.variant not in YOLO_VARIANTS:
+            raise ValueError("variant=%r: yolov3, spp or tiny" % (self.variant,))
+        if self.pool_pad not in ("ignore", "zero"):
+            raise ValueError("pool_pad=%r: ignore or zero" % (self.pool_pad,))
+        if len(self.masks) != len(self.strides) or any(len(m) != 3 for m in self.masks):
+            raise ValueError("masks=%r: %s [yolo] layers of three anchors each are built (A = 3) for variant %s"
+                             % (self.masks, "two" if self.variant == "tiny" else "three", self.variant))
         if any(not 0 <= i < len(self.anchors) for m in self.masks for i in m) or any(len(a) != 2 or a[0] <= 0 or a[1] <= 0 for a in self.anchors):
             raise ValueError("anchors=%r: positive (w, h) pairs, every mask index inside the list" % (self.anchors,))
         if not 1 <= self.pre_nms_top_n <= YOLO_MAX_TOP_N:
@@ -72,15 +93,15 @@ class YoloV3Config:
         return self
 
 
-def yolo_grids(H, W):
-    """(h, w) of the three heads' grids on an (H, W) canvas, stride 32 first."""
-    return [(H // s, W // s) for s in YOLO_STRIDES]
+def yolo_grids(H, W, strides=YOLO_STRIDES):
+    """(h, w) of the heads' grids on an (H, W) canvas, stride 32 first."""
+    return [(H // s, W // s) for s in strides]
 
 
 def yolov3_folded(sd, cfg=YoloV3Config()):
     """{layer: (weight [Cout][R][S][Cin], scale or None, shift)}: BN folded with cfg.bn_eps, the predictors with their bias."""
     out = {}
-    for name, bn, cout, cin, k in yolov3_layers(cfg.classes):
+    for name, bn, cout, cin, k in yolo_layers(cfg.variant, cfg.classes):
         w = np.asarray(sd[name + ".weight"], np.float32)
         if w.shape != (cout, cin, k, k):
             raise ValueError("%s.weight: expected %s, got %s" % (name, (cout, cin, k, k), w.shape))
@@ -103,9 +124,13 @@ class YoloV3(Engine, DetectionBlock):
         self.fp16 = False
         self._create(device, max_batch, H, W)
         for name, (w, sc, sh) in yolov3_folded(state_dict, cfg).items():
-            if name == "backbone._preconv.0":   # the 3-channel image runs as a zero-padded 32-channel copy
+            if w.shape[3] % 32:   # the 3-channel image, and tiny's 16-channel first map, run as zero-padded 32-channel copies
                 w = np.concatenate([w, np.zeros(w.shape[:3] + (32 - w.shape[3],), np.float32)], -1)
+            if cfg.variant == "tiny" and name == "backbone.conv0":   # 16 -> 32 rows: output channels 16..31 are zero weights with scale 1 and shift 0 -> LeakyReLU(0) = 0
+                w = np.concatenate([w, np.zeros((16,) + w.shape[1:], np.float32)], 0)
+                sc, sh = np.concatenate([sc, np.ones(16, np.float32)]), np.concatenate([sh, np.zeros(16, np.float32)])
             self._set_conv_krsc(name, w, sc, sh)
+        self.set_param("yolo_variant", float(YOLO_VARIANTS.index(cfg.variant)))
         for i, v in enumerate(cfg.level_anchors().reshape(-1)):
             self.set_param("yolo_anchor%d" % i, float(v))
         self.configure(cfg)
@@ -114,7 +139,9 @@ class YoloV3(Engine, DetectionBlock):
     def configure(self, cfg):
         """The tail's parameters from a config (live: the next forward uses them)."""
         cfg.validate(self.H, self.W)
-        for k, v in (("yolo_conf_thresh", cfg.conf_thresh), ("yolo_nms_thresh", cfg.nms_thresh), ("yolo_pre_nms_top_n", cfg.pre_nms_top_n),
+        if cfg.variant != self.cfg.variant:
+            raise ValueError("variant=%r: the engine was built as %r (the graph and its weights are fixed at construction)" % (cfg.variant, self.cfg.variant))
+        for k, v in (("yolo_pool_zero_pad", cfg.pool_pad == "zero"), ("yolo_conf_thresh", cfg.conf_thresh), ("yolo_nms_thresh", cfg.nms_thresh), ("yolo_pre_nms_top_n", cfg.pre_nms_top_n),
                      ("yolo_multi_label", float(bool(cfg.multi_label))), ("yolo_min_wh", cfg.min_wh), ("detections_per_img", cfg.detections_per_img),
                      ("detections_cap", cfg.detections_cap), ("nms_ge", cfg.nms_ge), ("nms_plus_one", cfg.nms_plus_one),
                      ("nms_index_order", {"score": 0, "index": 1}[cfg.nms_output_order])):
@@ -147,10 +174,10 @@ class YoloV3(Engine, DetectionBlock):
 
     def heads(self, n):
         """The raw head tensors of the last forward, stride 32 first: [n, H_s, W_s, 3 * (5 + classes)]."""
-        return [self.fetch("yolo.head%d" % s, n) for s in range(3)]
+        return [self.fetch("yolo.head%d" % s, n) for s in range(len(self.cfg.strides))]
 
     def candidate_counts(self, n):
-        """(kept [n, 3], before the top-n cut [n, 3]) per (image, level) of the last forward: kept < before means the cut truncated that level."""
+        """(kept [n, levels], before the top-n cut [n, levels]) per (image, level) of the last forward: kept < before means the cut truncated that level."""
         return self.fetch("yolo.cand_cnt", n), self.fetch("yolo.cand_total", n)
 
 
