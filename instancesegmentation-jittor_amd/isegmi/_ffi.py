@@ -1284,21 +1284,29 @@ def attention(qkv, heads, pad_floats=0, pad_value=0.0):
     return do.numpy()
 
 
-def layer_norm(x, gamma, beta, eps=1e-6, inplace=False, rows=None, x_row_stride=None):
+def layer_norm(x, gamma, beta, eps=1e-6, inplace=False, rows=None, x_row_stride=None, out_row_stride=None):
     """isegmi_op_layer_norm of x [..., D].  rows / x_row_stride: only `rows` rows, x_row_stride floats apart, are normalised -> [rows, D] (the class-token
-    form; never in place)."""
+    form).  out_row_stride (with rows): the output rows are that many floats apart in a poisoned buffer -> the whole buffer [rows, out_row_stride], gaps
+    included.  D is gamma's length.  In place with rows: x is [rows, x_row_stride], out_row_stride is x_row_stride -> the whole buffer after the call."""
     x = np.ascontiguousarray(x, np.float32)
-    D = x.shape[-1]
-    dx = DeviceBuffer.from_numpy(x)
     dg = DeviceBuffer.from_numpy(np.ascontiguousarray(gamma, np.float32)); db = DeviceBuffer.from_numpy(np.ascontiguousarray(beta, np.float32))
+    D = dg.shape[0]
+    dx = DeviceBuffer.from_numpy(x)
     assert dg.shape == (D,) and db.shape == (D,), (dg.shape, db.shape, D)
     if rows is None:
+        assert x.shape[-1] == D and out_row_stride is None
         do = dx if inplace else DeviceBuffer(x.shape).poison()
         check(lib().isegmi_op_layer_norm(dx.ptr, x.size // D, D, D, dg.ptr, db.ptr, float(eps), do.ptr, D, None))
         return do.numpy()
-    assert (rows - 1) * x_row_stride + D <= x.size and not inplace
-    do = DeviceBuffer((rows, D)).poison()
-    check(lib().isegmi_op_layer_norm(dx.ptr, rows, D, int(x_row_stride), dg.ptr, db.ptr, float(eps), do.ptr, D, None))
+    xs = int(x_row_stride)
+    os_ = xs if inplace and out_row_stride is None else D if out_row_stride is None else int(out_row_stride)
+    assert rows == 0 or (rows - 1) * xs + D <= x.size
+    if inplace:
+        assert os_ == xs, (os_, xs)
+        do = dx
+    else:
+        do = DeviceBuffer((rows, max(os_, D))).poison()
+    check(lib().isegmi_op_layer_norm(dx.ptr, rows, D, xs, dg.ptr, db.ptr, float(eps), do.ptr, os_, None))
     return do.numpy()
 
 

@@ -9,8 +9,7 @@ import pytest
 import vit_ref as vr
 from vit_ref import erf_sweep
 
-U = 2.0 ** -24
-TINY = 2.0 ** -149
+U, TINY = vr.U, vr.TINY
 
 
 def test_dm_erf_against_math_erf():
@@ -50,63 +49,35 @@ def test_gelu_against_float64(gelu_tanh):
     assert (err <= bound).all()
 
 
-def ln_bound(x, gamma, beta, eps):
-    """tests/groupnorm_ref.py's derivation on one row: k = the longest per-lane chain (4 floats per slot, ceil(D / 256) slots)."""
-    x64 = np.asarray(x, np.float64)
-    D = x64.shape[1]
-    k = 4 * -(-(D // 4) // 64)
-    d = x64 - x64[:, :1]
-    md = d.mean(1, keepdims=True); mabs = np.abs(d).mean(1, keepdims=True); m2 = (d * d).mean(1, keepdims=True)
-    var = np.maximum(m2 - md * md, 0.0)
-    s = np.sqrt(var + float(np.float32(eps)))
-    A = (k + 1) * mabs + np.abs(md)
-    V = (k + 3) * m2 + 2 * np.abs(md) * (k + 1) * mabs
-    t = d - md
-    ga = np.abs(np.asarray(gamma, np.float64))
-    y0 = t / s * np.asarray(gamma, np.float64) + np.asarray(beta, np.float64)
-    return 1.05 * U * (ga / s * (np.abs(d) + A + np.abs(t)) + ga * np.abs(t) / s * (V / (2 * s * s) + 3) + 2 * np.abs(y0)) + TINY
-
-
-@pytest.mark.parametrize("D", [32, 192, 768, 1024])
+@pytest.mark.parametrize("D", [4, 8, 32, 192, 252, 256, 260, 768, 1024, 1280, 2044, 2048])
 def test_layer_norm_against_float64(D):
-    import torch
+    """The bound is vit_ref.ln_bound (shared with the GPU tests).  D = 4 and 8: one and two live lanes; 252 / 256 / 260: one slot either side of 64 slots;
+    1280: ViT-H; 2044 / 2048: the last partial and the last full set of 8 slots per lane."""
     rng = np.random.default_rng(D)
     x = rng.standard_normal((7, D)).astype(np.float32)
     x[1] += 1000.0                       # |mean| >> sigma: the shifted sums keep their digits
     x[2] = x[2] * 1e-3 + 5.0
     ga = rng.uniform(0.5, 1.5, D).astype(np.float32); be = (rng.standard_normal(D) * 0.1).astype(np.float32)
     got = vr.layer_norm(x, ga, be, 1e-6).astype(np.float64)
-    want = torch.nn.functional.layer_norm(torch.from_numpy(x.astype(np.float64)), (D,), torch.from_numpy(ga.astype(np.float64)),
-                                          torch.from_numpy(be.astype(np.float64)), float(np.float32(1e-6))).numpy()
-    err, bound = np.abs(got - want), ln_bound(x, ga, be, 1e-6)
+    want = vr.layer_norm_float64(x, ga, be, 1e-6)
+    err, bound = np.abs(got - want), vr.ln_bound(x, ga, be, 1e-6)
     print("layer_norm D=%d: max error / bound %.3f" % (D, (err / bound).max()))
     assert (err <= bound).all()
     const = np.full((1, D), 3.25, np.float32)     # a constant row: variance exactly 0, y = beta
     assert np.array_equal(vr.layer_norm(const, ga, be, 1e-6), be[None])
 
 
-@pytest.mark.parametrize("T", [1, 17, 197])
+@pytest.mark.parametrize("T", [1, 17, 197, 576, 577, 1024])
 def test_attention_against_float64(T):
-    """s: a 64-term fmaf chain, |ds| <= 64 u S with S = sum |q k| / 8.  e = exp(s - m): the subtraction u |s - m|, the argument error 2 * 64 u S through
-    exp (relative), dm_exp 2 u.  l: chains of T / 4 terms and two folds.  p = e / l: u.  o: a T-term chain over p v, |do| <= T u sum p |v|.  e's
-    relative error E = 128 u S + u R + 2 u (R = max |s - m|) enters p through the numerator and, with the other sign, through l: 2 E.  In all
-    |do| <= sum_j p_ij |v_jd| * u * (T + T / 4 + 2 + 1 + 2 * (128 S + R + 2)), times 1.05 for the second-order terms."""
-    import torch
+    """The bound and its derivation are vit_ref.attention_bound (shared with the GPU tests).  576 / 577: either side of the kernel's 4 -> 2 wavefront fork;
+    1024: its maximum."""
     rng = np.random.default_rng(T)
     heads = 2
     qkv = rng.standard_normal((1, T, 3 * heads * 64)).astype(np.float32)
     got = vr.attention(qkv, heads).astype(np.float64)
-    t = torch.from_numpy(qkv.astype(np.float64)).reshape(1, T, 3, heads, 64).permute(2, 0, 3, 1, 4)
-    q, k, v = t[0], t[1], t[2]
-    s = q @ k.transpose(-1, -2) / 8
-    p = torch.softmax(s, -1)
-    want = (p @ v).permute(0, 2, 1, 3).reshape(1, T, heads * 64).numpy()
-    S = (q.abs() @ k.abs().transpose(-1, -2) / 8).amax(-1, keepdim=True)
-    R = (s.amax(-1, keepdim=True) - s.amin(-1, keepdim=True))
-    bound = (p @ v.abs()) * U * (T + T / 4 + 3 + 2 * (128 * S + R + 2)) * 1.05
-    bound = bound.permute(0, 2, 1, 3).reshape(1, T, heads * 64).numpy() + TINY
+    want, bound = vr.attention_bound(qkv, heads)
     err = np.abs(got - want)
-    print("attention T=%d: max error / bound %.3f" % (T, (err / bound).max()))
+    print("attention T=%d: max error / bound %.4f" % (T, (err / bound).max()))
     assert (err <= bound).all()
     if T == 1:
         assert np.array_equal(vr.attention(qkv, heads), qkv[:, :, 2 * heads * 64:])      # one key: p = 1, o = v

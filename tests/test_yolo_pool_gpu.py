@@ -100,3 +100,49 @@ def test_spp_concat_refusals(ffi):
                         ("null", (x.ptr, 1, 4, 4, 32, 0, None)), ("zero_pad", (x.ptr, 1, 4, 4, 32, 2, out.ptr)), ("1..32", (x.ptr, 0, 4, 4, 32, 0, out.ptr))):
         with pytest.raises(ffi.IsegmiError, match=match):
             ffi.check(call(*args, None))
+
+
+# ---- past the launchers' forks: the capped grid of maxpool_darknet and the LDS fork of spp_concat
+POOL_CAP_QUADS = 2048 * 256   # pool_grid: at most 2048 blocks of 256 threads, one channel quad of one output pixel per thread and trip
+SPP_PLANE = 8192              # floats of one LDS plane of spp_concat_kernel: a 16-channel slab while H * W * 16 fits, an 8-channel slab past that
+SPP_FORK_MAPS = ((22, 23), (16, 32), (23, 23), (1, 32), (32, 1))
+
+
+@pytest.mark.parametrize("shape,pool", [((1, 130, 130, 128), (2, 1)), ((1, 259, 260, 128), (2, 2))])
+def test_maxpool_darknet_grid_stride(ffi, shape, pool):
+    """yolov3-tiny's two even pools on an output of 540 800 channel quads: 16 512 of them belong to the second trip of the grid-stride loop."""
+    size, stride = pool
+    N, H, W, Cc = shape
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    quads = N * Ho * Wo * (Cc // 4)
+    assert (Ho, Wo) == (130, 130) and POOL_CAP_QUADS < quads < 2 * POOL_CAP_QUADS
+    for kind in ("special", "negative"):
+        x = _data(kind, shape, H + len(kind))
+        for zp in (0, 1):
+            got, want = ffi.maxpool_darknet(x, size, stride, zp), vr.maxpool_darknet(x, size, stride, bool(zp))
+            assert got.shape == want.shape == (N, Ho, Wo, Cc)
+            bad = np.flatnonzero(_bits(got).reshape(-1) != _bits(want).reshape(-1))
+            assert bad.size == 0, "%s zero_pad %d: %d floats differ, first %d, last %d; %d of them past the first sweep (%d floats)" % (
+                kind, zp, bad.size, bad[0], bad[-1], (bad >= POOL_CAP_QUADS * 4).sum(), POOL_CAP_QUADS * 4)
+            if kind == "negative":   # the last output row's windows leave the map at the bottom: the pad modes differ there, inside the second trip
+                assert (want[0, -1] == 0).all() == bool(zp) and (want[0, 0, :-1] < 0).all()
+
+
+@pytest.mark.parametrize("hw", SPP_FORK_MAPS)
+def test_spp_concat_lds_fork(ffi, hw):
+    """Both sides of the slab fork at its boundary: 22 x 23 = 506 and 16 x 32 = 512 pixels (the last map on 16-channel slabs), 23 x 23 = 529 (the first on
+    8-channel slabs), and the two one-pixel-wide maps, whose row or column pass sees a single line."""
+    H, W = hw
+    sixteen = H * W * 16 <= SPP_PLANE
+    assert sixteen == (hw != (23, 23)) and (H * W * 16 == SPP_PLANE) == (hw == (16, 32)) and H * W * 8 <= SPP_PLANE
+    for Cc in (32, 96):
+        N = 2
+        x = _data("special" if Cc == 96 else "normal", (N, H, W, Cc), H * 1000 + W * 10 + Cc)
+        x[..., 1::2] = -np.abs(x[..., 1::2]) - F32(0.01)   # every other channel all negative (or NaN / inf): the pad modes differ there
+        for zp in (0, 1):
+            got, want = ffi.spp_concat(x, zp), vr.spp_concat(x, bool(zp))
+            assert got.shape == want.shape == (N, H, W, 4 * Cc)
+            assert np.array_equal(got, want, equal_nan=True), (Cc, zp)
+            assert np.array_equal(_bits(got), _bits(want)), (Cc, zp)
+            pools = np.concatenate([ffi.maxpool_darknet(x, k, 1, zp) for k in (13, 9, 5)], -1)
+            assert np.array_equal(_bits(got[..., :3 * Cc]), _bits(pools)), (Cc, zp)

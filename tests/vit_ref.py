@@ -104,6 +104,56 @@ def layer_norm(x, gamma, beta, eps=1e-6):
     return y
 
 
+U = 2.0 ** -24
+TINY = 2.0 ** -149
+
+
+def ln_bound(x, gamma, beta, eps):
+    """tests/groupnorm_ref.py's derivation on one row: k = the longest per-lane chain (4 floats per slot, ceil(D / 256) slots)."""
+    x64 = np.asarray(x, np.float64)
+    D = x64.shape[1]
+    k = 4 * -(-(D // 4) // 64)
+    d = x64 - x64[:, :1]
+    md = d.mean(1, keepdims=True); mabs = np.abs(d).mean(1, keepdims=True); m2 = (d * d).mean(1, keepdims=True)
+    var = np.maximum(m2 - md * md, 0.0)
+    s = np.sqrt(var + float(np.float32(eps)))
+    A = (k + 1) * mabs + np.abs(md)
+    V = (k + 3) * m2 + 2 * np.abs(md) * (k + 1) * mabs
+    t = d - md
+    ga = np.abs(np.asarray(gamma, np.float64))
+    y0 = t / s * np.asarray(gamma, np.float64) + np.asarray(beta, np.float64)
+    return 1.05 * U * (ga / s * (np.abs(d) + A + np.abs(t)) + ga * np.abs(t) / s * (V / (2 * s * s) + 3) + 2 * np.abs(y0)) + TINY
+
+
+def layer_norm_float64(x, gamma, beta, eps):
+    """torch's LayerNorm in float64 on the fp32 inputs (eps rounded to fp32 first, as the kernel receives it)."""
+    import torch
+    D = x.shape[-1]
+    return torch.nn.functional.layer_norm(torch.from_numpy(np.asarray(x, np.float64)), (D,), torch.from_numpy(np.asarray(gamma, np.float64)),
+                                          torch.from_numpy(np.asarray(beta, np.float64)), float(np.float32(eps))).numpy()
+
+
+def attention_bound(qkv, heads):
+    """qkv [N, T, 3 * heads * 64] -> (softmax(q k^T / 8) v in float64 [N, T, heads * 64], the bound on an fp32 result in the kernel's order).
+
+    s: a 64-term fmaf chain, |ds| <= 64 u S with S = sum |q k| / 8.  e = exp(s - m): the subtraction u |s - m|, the argument error 2 * 64 u S through
+    exp (relative), dm_exp 2 u.  l: chains of T / 4 terms and two folds.  p = e / l: u.  o: a T-term chain over p v, |do| <= T u sum p |v|.  e's
+    relative error E = 128 u S + u R + 2 u (R = max |s - m|) enters p through the numerator and, with the other sign, through l: 2 E.  In all
+    |do| <= sum_j p_ij |v_jd| * u * (T + T / 4 + 2 + 1 + 2 * (128 S + R + 2)), times 1.05 for the second-order terms."""
+    import torch
+    qkv = np.ascontiguousarray(qkv, np.float32)
+    N, T, _ = qkv.shape
+    t = torch.from_numpy(qkv.astype(np.float64)).reshape(N, T, 3, heads, 64).permute(2, 0, 3, 1, 4)
+    q, k, v = t[0], t[1], t[2]
+    s = q @ k.transpose(-1, -2) / 8
+    p = torch.softmax(s, -1)
+    want = (p @ v).permute(0, 2, 1, 3).reshape(N, T, heads * 64).numpy()
+    S = (q.abs() @ k.abs().transpose(-1, -2) / 8).amax(-1, keepdim=True)
+    R = (s.amax(-1, keepdim=True) - s.amin(-1, keepdim=True))
+    bound = (p @ v.abs()) * U * (T + T / 4 + 3 + 2 * (128 * S + R + 2)) * 1.05
+    return want, bound.permute(0, 2, 1, 3).reshape(N, T, heads * 64).numpy() + TINY
+
+
 def _pad32(a, axis):
     n = a.shape[axis]
     pad = [(0, 0)] * a.ndim
