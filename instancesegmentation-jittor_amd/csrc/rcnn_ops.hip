@@ -467,7 +467,8 @@ __global__ __launch_bounds__(256) void roi_align_kernel(const RoiLevels lv, cons
     const float bh = dm_div(rh, (float)PH), bw = dm_div(rw, (float)PW);
     // g > 0: fixed sampling grid; g <= 0: adaptive ceil(roi / pooled) (ROIAlign's sampling_ratio = 0, the C4 config)
     const int gh = GS > 0 ? GS : (g > 0 ? g : (int)ceilf(bh)), gw = GS > 0 ? GS : (g > 0 ? g : (int)ceilf(bw));
-    const float cnt = (float)(gh * gw);
+    // an empty grid (aligned, adaptive, x2 <= x1 or y2 <= y1) pools to +0, as ROIAlign(aligned=True)'s count = max(gh * gw, 1) does, not to 0 / 0
+    const float cnt = (float)(gh * gw > 1 ? gh * gw : 1);
     for (int j = start + threadIdx.x; j < end; j += 256) {
         const int bin = j / c4n, c4 = j - bin * c4n;
         const int ph = bin / PW, pw = bin - ph * PW;

@@ -526,6 +526,7 @@ int roi_align_f16_launch(const void* const* feats, const int* Hs, const int* Ws,
                          const int* counts, int N, int K, int C, int PH, int PW, int g, int k_min, void* out, hipStream_t st,
                          const int* order = nullptr, const void* tab = nullptr, int aligned = 0) {
     ARG_CHECK(nlevels >= 1 && nlevels <= 4 && C % 4 == 0, "roi_align levels/C");
+    ARG_CHECK(g > 0, "roi_align_f16: a fixed sampling grid only (no fp16 kernel has the adaptive grid of sampling <= 0)");
     RoiLevelsH lv;
     for (int i = 0; i < 4; ++i) {
         const int s = i < nlevels ? i : nlevels - 1;
@@ -577,7 +578,7 @@ extern "C" int isegmi_op_pad_c3_to_f16_halo(const float* d_in_nhwc3, int N, int 
 extern "C" int isegmi_op_roi_align_f16(const void* const* d_feats, const int32_t* Hs, const int32_t* Ws, const float* scales, int nlevels,
                                        const float* d_rois, const int32_t* d_counts, int N, int K, int C, int PH, int PW, int sampling, int aligned,
                                        int k_min, void* d_out, void* stream) {
-    ARG_CHECK(d_feats && Hs && Ws && scales && d_rois && d_counts && d_out && N > 0 && K > 0 && PH > 0 && PW > 0 && sampling > 0, "args");
+    ARG_CHECK(d_feats && Hs && Ws && scales && d_rois && d_counts && d_out && N > 0 && K > 0 && PH > 0 && PW > 0, "args");
     return isegmi::roi_align_f16_launch(d_feats, Hs, Ws, scales, nlevels, d_rois, d_counts, N, K, C, PH, PW, sampling, k_min, d_out,
                                         (hipStream_t)stream, nullptr, nullptr, aligned);
 }

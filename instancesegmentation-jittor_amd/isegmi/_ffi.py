@@ -612,7 +612,7 @@ def roi_align(feats, scales, rois, counts, PH, PW, sampling=2, k_min=2, fixed_le
     Hs = (C.c_int32 * len(fb))(*[f.shape[1] for f in feats]); Ws = (C.c_int32 * len(fb))(*[f.shape[2] for f in feats])
     sc = (C.c_float * len(fb))(*scales)
     dr = DeviceBuffer.from_numpy(np.ascontiguousarray(rois, np.float32)); dcnt = DeviceBuffer.from_numpy(np.ascontiguousarray(counts, np.int32))
-    do = DeviceBuffer((N * K, PH, PW, Cc)); dl = DeviceBuffer((N, K), np.int32); dl.zero()
+    do = DeviceBuffer((N * K, PH, PW, Cc)).poison(); dl = DeviceBuffer((N, K), np.int32); dl.zero()   # NaN where the launch wrote nothing
     check(lib().isegmi_op_roi_align(ptrs, Hs, Ws, sc, len(fb), dr.ptr, dcnt.ptr, N, K, Cc, PH, PW, sampling, aligned, k_min, fixed_level,
                                     do.ptr, dl.ptr, None))
     return do.numpy(), dl.numpy()
@@ -670,7 +670,7 @@ def roi_align_f16(feats, scales, rois, counts, PH, PW, sampling=2, k_min=2, alig
     Hs = (C.c_int32 * len(fb))(*[f.shape[1] for f in feats]); Ws = (C.c_int32 * len(fb))(*[f.shape[2] for f in feats])
     sc = (C.c_float * len(fb))(*scales)
     dr = DeviceBuffer.from_numpy(np.ascontiguousarray(rois, np.float32)); dcnt = DeviceBuffer.from_numpy(np.ascontiguousarray(counts, np.int32))
-    do = DeviceBuffer((N * K, PH, PW, Cc), np.float16)
+    do = DeviceBuffer((N * K, PH, PW, Cc), np.float16).poison()
     check(lib().isegmi_op_roi_align_f16(ptrs, Hs, Ws, sc, len(fb), dr.ptr, dcnt.ptr, N, K, Cc, PH, PW, sampling, aligned, k_min, do.ptr, None))
     return do.numpy()
 

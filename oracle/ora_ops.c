@@ -653,7 +653,8 @@ ORA_API void ora_roi_align2(const float* feat, int N, int H, int W, int C, const
          * the R-50-C4 config, whose yaml does not set POOLER_SAMPLING_RATIO) */
         const int gh = g > 0 ? g : (int)ceilf(rh / (float)PH);
         const int gw = g > 0 ? g : (int)ceilf(rw / (float)PW);
-        const float count = (float)(gh * gw);
+        /* count = max(gh * gw, 1), as in ROIAlign(aligned=True): an empty adaptive grid (x2 <= x1 or y2 <= y1) gives +0, not 0 / 0 */
+        const float count = (float)(gh * gw > 1 ? gh * gw : 1);
         for (int ph = 0; ph < PH; ++ph)
             for (int pw = 0; pw < PW; ++pw) {
                 float* o = out + (((size_t)r * PH + ph) * PW + pw) * C;

@@ -260,6 +260,22 @@ def test_roi_align_refuses_null_and_level_before_any_launch(case):
     assert b"roi_align args" in err and b"fixed_level < nlevels" in err, err
 
 
+@pytest.mark.parametrize("sampling", [0, -1])
+def test_roi_align_f16_refuses_an_adaptive_grid_before_any_launch(sampling):
+    """No fp16 kernel has the adaptive grid (their sample loops run iy < g): with sampling <= 0 every RoI would pool to 0 / 0.  Only this entry point used to
+    refuse it, inside its unnamed "args" check; now the launcher -- the entry the engines call -- does, and names the reason.  Device pointers are made-up
+    addresses that nothing dereferences."""
+    from isegmi import _ffi
+    lib = _ffi.lib()
+    fake = 0x10000
+    feats = (C.c_void_p * 1)(fake)
+    Hs, Ws, scales = (C.c_int32 * 1)(8), (C.c_int32 * 1)(8), (C.c_float * 1)(0.25)
+    rc = lib.isegmi_op_roi_align_f16(feats, Hs, Ws, scales, 1, fake, fake, 1, 4, 64, 7, 7, sampling, 1, 2, fake, None)
+    assert rc != 0
+    err = lib.isegmi_last_error()
+    assert b"roi_align_f16: a fixed sampling grid only" in err and b"g > 0" in err, err
+
+
 ENGINE_SHARED = ("_create", "set_param", "_set_conv_krsc", "_set_conv_grouped", "_set_tensor", "sync", "stream", "fetch", "timings", "memory",
                  "conv_stats", "_buffer_info", "input_buffer", "upload_async", "_u8_staging", "_preprocess_u8", "mark_step", "wait_mark", "step_times",
                  "rle_device", "coco_record_bytes", "pack_coco_records", "download_async", "download_fence", "download_wait", "close", "__del__")
