@@ -549,6 +549,19 @@ int isegmi_op_patchify(const float* d_in_nhwc3, int N, int H, int W, int P, floa
  * s[l] += s[l + off], off = 32 .. 1; prob_j = e_j / sum (IEEE division). */
 int isegmi_op_class_softmax(const float* d_logits, int rows, int n, float* d_prob, void* stream);
 
+/* ---- the painter (csrc/render.hip): mask tints, box outlines and keypoint dots of a draw list on a uint8 image, bit for bit what the
+ * host overlays do (COCODemo.overlay / overlay_keypoints, cli._overlay; the annotated image README.md:243-249 and the Detectron example end in) ----
+ * d_image / d_out [H][W][3] u8, dense, the caller's channel order; d_out == d_image paints in place.  d_masks [slots][ph][pw] u8 planes with the image in
+ * their top-left H x W (det.masks), a byte != 0 is set.  d_entries i32 [D][8] = {slot (-1: no mask), x1, y1, x2, y2, colour = c0 | c1 << 8 | c2 << 16,
+ * flags (bit 0: outline), 0}, D <= 1024; d_dots i32 [Q][4] = {x, y, colour, half}, Q <= 32768, half 0..8.  Every pixel (x, y), every channel byte:
+ *   for k = 0 .. D-1:  mask of entry k set here -> p = (p + c) >> 1;   outline flag and ((y1 <= y <= y2 and (x == x1 or x == x2)) or
+ *                      (x1 <= x <= x2 and (y == y1 or y == y2))) -> p = c;          then for j = 0 .. Q-1:  |x - xj| <= half and |y - yj| <= half -> p = c.
+ * Everything is a device pointer (a list may be NULL when its count is 0; d_masks NULL: box-only lists).  ISEGMI_ERR_ARG, with nothing launched or
+ * written: a null image, H or W < 1, masks with slots < 1 or ph < H or pw < W, a slot outside -1 .. slots-1 or naming a slot without masks, D or Q over
+ * its cap, half outside 0..8 (the lists are read back to the host and checked first: this entry point synchronises `stream`). */
+int isegmi_op_paint(const uint8_t* d_image, int H, int W, const uint8_t* d_masks, int slots, int ph, int pw, const int32_t* d_entries, int D,
+                    const int32_t* d_dots, int Q, uint8_t* d_out, void* stream);
+
 /* ---- COCO run-length encoding on the device (the on-disk format behind inference() / tools/test_net.py,
  * README.md:344-347, annotation layout README.md:55-66; Yolact eval.py Detections.add_mask / dump, README.md:243-249) ----
  * pycocotools rleEncode + rleToString restated: for every valid slot (n, k), k < d_count[n], of the uint8 planes d_masks [N][K][plane_h][plane_w]
@@ -789,6 +802,12 @@ int isegmi_engine_pack_box_records(isegmi_engine* e, const float* h_ratios_wh, v
  *   y = det.kpt * (ratio_w, ratio_h), one fp32 multiplication each, v copied; every section starts on a multiple of 8 bytes, unused slots are zero.
  * isegmi_engine_coco_record_bytes returns this block's size (chars_offset = the size) while the engine's "keypoint_on" is 1. */
 int isegmi_engine_pack_keypoint_records(isegmi_engine* e, const float* h_ratios_wh, void* d_dst, int64_t cap, int n_block, int64_t* bytes);
+/* isegmi_op_paint over the engine's det.masks rows of image `image_index` of the last paste / postprocess, on the stream that produced them and ordered
+ * behind it; the lists are HOST arrays (checked, then staged by the engine), d_image / d_out the caller's device buffers.  ISEGMI_ERR_STATE by name: a call
+ * before the first forward; an entry that names a slot while there is no det.masks of this batch (no paste / postprocess yet, a box-only engine, RetinaNet,
+ * YOLOv3: those paint with slot -1 only) or while "sparse_masks" leaves the planes incomplete. */
+int isegmi_engine_paint(isegmi_engine* e, int image_index, const uint8_t* d_image, int H, int W, const int32_t* h_entries, int D, const int32_t* h_dots,
+                        int Q, uint8_t* d_out);
 int isegmi_engine_download_async(isegmi_engine* e, int slot, void* h_dst_pinned, const void* d_src, int64_t bytes);
 int isegmi_engine_download_fence(isegmi_engine* e, int slot);
 int isegmi_engine_download_wait(isegmi_engine* e, int slot);

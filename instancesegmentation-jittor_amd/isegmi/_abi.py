@@ -180,6 +180,7 @@ SIGNATURES = {
     "isegmi_op_gelu": (I, [V, V, L, I, V]),
     "isegmi_op_patchify": (I, [V, I, I, I, I, V, V]),
     "isegmi_op_class_softmax": (I, [V, I, I, V, V]),
+    "isegmi_op_paint": (I, [V, I, I, V, I, I, I, V, I, V, I, V, V]),
     "isegmi_rle_workspace": (I, [I, I, I, I, I, V, V, V, V, V, V]),
     "isegmi_op_rle_encode": (I, [V, V]),
     "isegmi_op_pose2seg_letterbox": (I, [V, V, I, I, V, V, I, I, V, V]),
@@ -229,6 +230,7 @@ SIGNATURES = {
     "isegmi_engine_pack_coco_records": (I, [V, V, L, I, V]),
     "isegmi_engine_pack_box_records": (I, [V, V, V, L, I, V]),
     "isegmi_engine_pack_keypoint_records": (I, [V, V, V, L, I, V]),
+    "isegmi_engine_paint": (I, [V, I, V, I, I, V, I, V, I, V]),
     "isegmi_engine_download_async": (I, [V, I, V, V, L]),
     "isegmi_engine_download_fence": (I, [V, I]),
     "isegmi_engine_download_wait": (I, [V, I]),

@@ -1333,3 +1333,40 @@ def class_softmax(logits):
     dx = DeviceBuffer.from_numpy(x); do = DeviceBuffer(x.shape).poison()
     check(lib().isegmi_op_class_softmax(dx.ptr, rows, n, do.ptr, None))
     return do.numpy()
+
+
+# ---- the painter (csrc/render.hip) on host arrays: tests and tools
+def paint_lists(entries, dots):
+    """-> (entries int32 [D, 8], dots int32 [Q, 4]) as isegmi_op_paint / isegmi_engine_paint read them; None is an empty list."""
+    e = np.zeros((0, 8), np.int32) if entries is None else np.ascontiguousarray(entries, np.int32).reshape(-1, 8)
+    d = np.zeros((0, 4), np.int32) if dots is None else np.ascontiguousarray(dots, np.int32).reshape(-1, 4)
+    return e, d
+
+
+def paint(image_u8, masks=None, entries=None, dots=None, inplace=False, tail=0, sentinel=0xA5, offset=0):
+    """isegmi_op_paint of image [H, W, 3] uint8 with masks [slots, ph, pw] uint8 (None: no planes).  The output buffer is `tail` bytes longer than the
+    image and pre-filled with `sentinel`; `offset` shifts the image, the planes and the output that many bytes into their allocations (unaligned bases).
+    -> (rc, out bytes [H * W * 3 + tail], the input buffer's H * W * 3 bytes after the call); rc is returned, not raised: the refusals are results."""
+    img = np.ascontiguousarray(image_u8, np.uint8)
+    H, W = img.shape[:2]
+    n = img.size
+    e, d = paint_lists(entries, dots)
+    d_in = DeviceBuffer((offset + n + (tail if inplace else 0),), np.uint8)
+    d_in.upload(np.concatenate([np.zeros(offset, np.uint8), img.reshape(-1), np.full(tail if inplace else 0, sentinel, np.uint8)]))
+    d_out = d_in if inplace else DeviceBuffer((offset + n + tail,), np.uint8)
+    if not inplace:
+        d_out.upload(np.full(offset + n + tail, sentinel, np.uint8))
+    d_m, slots, ph, pw = None, 0, 0, 0
+    if masks is not None:
+        m = np.ascontiguousarray(masks, np.uint8)
+        slots, ph, pw = m.shape
+        d_m = DeviceBuffer.from_numpy(np.concatenate([np.zeros(offset, np.uint8), m.reshape(-1)]))
+    d_e = DeviceBuffer.from_numpy(e) if len(e) else None
+    d_d = DeviceBuffer.from_numpy(d) if len(d) else None
+    at = lambda b: None if b is None else C.c_void_p(b.ptr.value + offset)   # noqa: E731
+    rc = lib().isegmi_op_paint(at(d_in), H, W, at(d_m), slots, ph, pw, _ptr(d_e), len(e), _ptr(d_d), len(d), at(d_out), None)
+    check(lib().isegmi_sync())
+    out, src = d_out.numpy()[offset:], d_in.numpy()[offset:offset + n]
+    for b in {id(x): x for x in (d_in, d_out, d_m, d_e, d_d) if x is not None}.values():
+        b.free()
+    return rc, out, src

@@ -120,6 +120,11 @@ def cmd_eval(a):
     net = Yolact(_weights(a.trained_model, "yolact", cfg.depth, cfg), cfg, max_batch=a.batch_size, device=local)
     results = evaluate(net, lambda i: _load_image_bgr(files[i]), batch_size=a.batch_size, score_threshold=a.score_threshold, top_k=a.top_k,
                        rank=rank, world=world, sizes=sizes)
+    painted = {}
+    if getattr(a, "render", "host") == "device" and rank == 0:   # --render=device: the outputs are painted from the mask planes, on the device
+        from .yolact import render_images
+        todo = [i for i, (_, dst) in enumerate(jobs) if dst]
+        painted = dict(zip(todo, render_images(net, [_load_image_bgr(files[i]) for i in todo], a.score_threshold, a.top_k, a.batch_size)))
     net.close()
     if rank == 0:
         by_img = {}
@@ -128,7 +133,9 @@ def cmd_eval(a):
         for i, (src, dst) in enumerate(jobs):
             dets = by_img.get(i, [])
             print("%s: %d detections" % (src, len(dets)))
-            if dst and dets:  # overlay from the records themselves: RLE -> mask, xywh -> box
+            if i in painted:
+                _save_image_bgr(dst, painted[i])
+            elif dst and dets:  # overlay from the records themselves: RLE -> mask, xywh -> box
                 from .coco import COCO_CATEGORY_IDS
                 masks = np.stack([rle_decode(d["segmentation"]) for d in dets])
                 boxes = [[d["bbox"][0], d["bbox"][1], d["bbox"][0] + d["bbox"][2], d["bbox"][1] + d["bbox"][3]] for d in dets]
@@ -169,6 +176,12 @@ def cmd_test_net(a):
     stats = {}
     results = inference(demo, lambda i: _load_image_bgr(files[i]), batch_size=a.batch_size, group=a.group, rank=rank, world=world,
                         sizes=_image_sizes(files), stats=stats) if files else []
+    vis_dir = getattr(a, "vis_dir", None)
+    if vis_dir and rank == 0:   # the Detectron example's last line for every image: run_on_opencv_image -> an annotated file
+        os.makedirs(vis_dir, exist_ok=True)
+        demo.confidence_threshold, demo.render = getattr(a, "vis_threshold", 0.7), getattr(a, "render", "host")
+        for f in files:
+            _save_image_bgr(os.path.join(vis_dir, os.path.splitext(os.path.basename(f))[0] + ".png"), demo.run_on_opencv_image(_load_image_bgr(f)))
     demo.close()
     if rank == 0:
         with open(a.output, "w") as f:
@@ -374,6 +387,8 @@ def build_parser():
     e.add_argument("--images", default=None, help="in_dir:out_dir")
     e.add_argument("--output_coco_json", default=None)
     e.add_argument("--batch_size", type=int, default=8, help="images per step and rank")
+    e.add_argument("--render", default=argparse.SUPPRESS, choices=["host", "device"],
+                   help="(default host) the --image / --images outputs: host draws them from the decoded records, device paints them from the mask planes (isegmi.yolact.render_images)")
     e.add_argument("--fast_nms", type=str2bool, default=argparse.SUPPRESS, help="(default True) False: traditional per-class NMS (upstream's cython_nms) instead of fast NMS")
     e.add_argument("--cross_class_nms", type=str2bool, default=argparse.SUPPRESS, help="(default False) True: one fast-NMS pass over all classes together")
     e.add_argument("--nms_trad_cap", type=int, default=argparse.SUPPRESS, help="(default 1024) traditional NMS: candidates visited per image and class (a multiple of 64 in [64, 2048])")
@@ -384,6 +399,10 @@ def build_parser():
     t.add_argument("--batch_size", type=int, default=2, help="images per step and rank (TEST.IMS_PER_BATCH / ranks)")
     t.add_argument("--group", default="canvas", choices=["canvas", "aspect"],
                    help="canvas: batch only images with the same padded canvas (every result equals the single-image result); aspect: upstream's ASPECT_RATIO_GROUPING")
+    # like the detector flags of pose2seg_test, these leave no attribute behind unless given
+    t.add_argument("--vis-dir", dest="vis_dir", default=argparse.SUPPRESS, help="also write COCODemo.run_on_opencv_image of every image (masks, boxes, names) to this directory")
+    t.add_argument("--vis-threshold", dest="vis_threshold", type=float, default=argparse.SUPPRESS, help="(default 0.7) with --vis-dir: draw detections with score > this")
+    t.add_argument("--render", default=argparse.SUPPRESS, choices=["host", "device"], help="(default host) with --vis-dir: where the masks, boxes and dots are drawn (DESIGN.md 22)")
     t.add_argument("opts", nargs=argparse.REMAINDER, default=[])
     p = sub.add_parser("pose2seg_test", help="Pose2Seg test.py-style evaluation: images + COCO person keypoints -> COCO segmentation json")
     p.add_argument("--weights", default="random", help="random (seeded synthetic weights) or an .npz in this engine's names")

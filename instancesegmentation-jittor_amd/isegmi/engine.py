@@ -172,7 +172,34 @@ class Engine:
     def download_wait(self, slot):
         _ffi.check(_ffi.lib().isegmi_engine_download_wait(self._h, slot))
 
+    # -- the painter: the annotated image of a demo, drawn where the masks are ---------------------------------------
+    def paint_device(self, image_u8, entries, dots=None, index=0):
+        """isegmi_engine_paint: the draw list `entries` (int32 [D, 8], isegmi.render) and `dots` (int32 [Q, 4]) on image [H, W, 3] uint8,
+        masks = det.masks of image `index` of the last paste / postprocess.  H * W * 3 bytes go up and come back; the mask planes stay on the device.
+        -> the painted image (a new array)."""
+        img = np.ascontiguousarray(image_u8, np.uint8)
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise TypeError("paint_device takes an HxWx3 uint8 image")
+        H, W = img.shape[:2]
+        e, d = _ffi.paint_lists(entries, dots)
+        buf = getattr(self, "_paint_buf", None)
+        if buf is None or buf.nbytes < img.nbytes:
+            if buf is not None:
+                self.sync()
+                buf.free()
+            buf = self._paint_buf = _ffi.DeviceBuffer((img.nbytes,), np.uint8)
+        _ffi.check(_ffi.lib().isegmi_h2d(buf.ptr, _addr(img), img.nbytes))
+        _ffi.check(_ffi.lib().isegmi_engine_paint(self._h, int(index), buf.ptr, H, W, _addr(e) if len(e) else None, len(e),
+                                                  _addr(d) if len(d) else None, len(d), buf.ptr))
+        self.sync()
+        out = np.empty_like(img)
+        _ffi.check(_ffi.lib().isegmi_d2h(_addr(out), buf.ptr, out.nbytes))
+        return out
+
     def close(self):
+        buf, self._paint_buf = getattr(self, "_paint_buf", None), None
+        if buf is not None:
+            buf.free()
         if self._h:
             _ffi.lib().isegmi_engine_destroy(self._h)
             self._h = None

@@ -19,8 +19,11 @@ class COCODemo:
     CATEGORIES = ("__background",) + COCO_CLASSES
 
     def __init__(self, cfg=None, min_image_size=800, confidence_threshold=0.5, state_dict=None, max_image_size=1333, device=0, max_batch=2,
-                 fp16=False):
+                 fp16=False, render="host"):
         from .retinanet import RetinaNetConfig
+        if render not in ("host", "device"):
+            raise ValueError("render: 'host' (numpy overlay of the downloaded masks) or 'device' (isegmi_engine_paint; DESIGN.md 22)")
+        self.render = render
         if cfg is not None and not isinstance(cfg, (MaskRCNNConfig, RetinaNetConfig)):   # the yacs-shaped node of isegmi.config (README.md:313-324)
             from .config import is_keypoint_rcnn, is_retinanet, to_keypointrcnn_config, to_maskrcnn_config, to_retinanet_config
             retina = is_retinanet(cfg)
@@ -92,8 +95,30 @@ class COCODemo:
         return predictions[order]
 
     def run_on_opencv_image(self, image):
+        if self.render == "device":
+            return self._run_on_device(image)
         predictions = self.select_top_predictions(self.compute_prediction(image))
         return self.overlay(image.copy(), predictions)
+
+    def _run_on_device(self, image):
+        """run_on_opencv_image with the painting on the device (render="device"): forward and paste as compute_prediction, but det.masks stays where
+        the paste wrote it -- only the small detection arrays come back, the selection runs on them, and isegmi_engine_paint draws the selected
+        detections in their selected order from their rows of det.masks (`slot`: the row before selection).  The image goes up and comes back once;
+        the class names are written on the host, as overlay does.  Bit-identical to the host overlay."""
+        from .render import demo_entries, keypoint_dots
+        h, w = image.shape[:2]
+        resized = maskrcnn_resize_u8(image, self.min_image_size, self.max_image_size)
+        model = self.engine()
+        (pred,) = model([resized])
+        with_masks = not (self.is_retinanet or self.box_only)
+        if with_masks:
+            model.paste_device(h, w, [(w, h)])   # on the results stream; the painter is ordered behind it
+        pred = pred.resize((w, h))
+        pred.add_field("slot", np.arange(len(pred), dtype=np.int64))
+        predictions = self.select_top_predictions(pred)
+        dots = keypoint_dots(predictions, self.KP_THRESH) if predictions.has_field("keypoints") else None
+        out = model.paint_device(image, demo_entries(predictions, h, w, with_masks), dots)
+        return self.overlay_class_names(out, predictions)
 
     @staticmethod
     def compute_colors_for_labels(labels):

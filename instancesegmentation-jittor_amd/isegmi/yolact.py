@@ -418,6 +418,39 @@ def postprocess(det_output, w, h, batch_idx=0, score_threshold=0.0):
     return d["class"][keep], scores, net._pp_boxes[i, :c][keep], net._pp_masks[i, :c][keep]
 
 
+def render_images(net, images, score_threshold=0.0, top_k=None, batch_size=None):
+    """eval.py --image / --images with the drawing on the device: -> one annotated HxWx3 uint8 BGR array per image, bit-identical to
+    cli._overlay(image, masks, boxes, classes) of postprocess(net(batch), w, h, i, score_threshold) cut to its first top_k detections.
+    Per batch: the uint8 front end, the forward, then per image postprocess_device at the image's own (h, w) and isegmi_engine_paint over its rows of
+    det.masks.  The detection arrays (count, score, class, integer boxes) come back; the mask planes never leave the device."""
+    from .render import yolact_entries
+    images = [np.ascontiguousarray(im, np.uint8) for im in images]
+    bs = int(batch_size or net.max_batch)
+    assert 0 < bs <= net.max_batch
+    out = []
+    for j in range(0, len(images), bs):
+        batch = images[j:j + bs]
+        n = net.upload_u8(batch)
+        net.forward_device(n)
+        net.sync()
+        net.check_nms_overflow(n)
+        cnt, score, cls = net.fetch("det.count", n), net.fetch("det.score", n), net.fetch("det.class", n)
+        for i, im in enumerate(batch):
+            h, w = im.shape[:2]
+            c = int(cnt[i])
+            keep = np.nonzero(score[i, :c] > np.float32(score_threshold))[0]
+            if top_k is not None:
+                keep = keep[:top_k]
+            if not len(keep):
+                out.append(im.copy())
+                continue
+            net.postprocess_device(h, w)   # the whole batch at this image's size, as postprocess() does: rows of image i are the planes it returns
+            net.sync()
+            boxes = net.fetch("det.box_int", n)[i]
+            out.append(net.paint_device(im, yolact_entries(keep, boxes[keep], cls[i, keep], h, w), index=i))
+    return out
+
+
 def evaluate(net, images, image_ids=None, batch_size=None, score_threshold=0.0, top_k=None, rank=0, world=1, sizes=None, stats=None, force_gather=False):
     """eval.py's image evaluation as a data-set loop (README.md:243-249: --images / --output_coco_json): images -> COCO-format result list
     (Detections.add_bbox / add_mask records) -- the path the benchmark measures, end to end.  Batches of `batch_size` raw uint8 BGR
