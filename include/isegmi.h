@@ -171,6 +171,11 @@ int isegmi_get_f16_mfma_shape(int* shape);
  * ora_build_transform (oracle/ora_ops.c: the rounding sequence is stated there) and to the numpy transforms of isegmi/transforms.py */
 int isegmi_op_preprocess_u8(const uint8_t* d_in, int N, int Hin, int Win, float* d_out, int Hout, int Wout, int Hpad, int Wpad,
                             int64_t out_img_stride, const float* mean3, const float* std3, int swap_rb, void* stream);
+/* the same with one more argument (the mirrored views of TEST.BBOX_AUG): hflip != 0 preprocesses the image whose columns are reversed within
+ * Win (not within the canvas: the image keeps its top-left corner, the padding stays right and bottom) -- bit-identical to isegmi_op_preprocess_u8 on a
+ * host-flipped copy of the bytes, which therefore go up once for both views of a scale */
+int isegmi_op_preprocess_u8_flip(const uint8_t* d_in, int N, int Hin, int Win, float* d_out, int Hout, int Wout, int Hpad, int Wpad,
+                                 int64_t out_img_stride, const float* mean3, const float* std3, int swap_rb, int hflip, void* stream);
 
 /* max_pool2d(k,s,p), -inf padding (M2/Y2 stem; k=1,s=2 = LastLevelMaxPool M3) */
 int isegmi_op_maxpool(const float* d_in, int N, int H, int W, int C, int k, int s, int p,
@@ -497,6 +502,26 @@ typedef struct isegmi_retina_post_args {
 } isegmi_retina_post_args;
 int64_t isegmi_op_retina_postprocess_workspace(int N, int nseg, int seg_len);
 int isegmi_op_retina_postprocess(const isegmi_retina_post_args* a, void* stream);
+/* ---- test-time box augmentation ([UPSTREAM-RECALL] maskrcnn-benchmark engine/bbox_aug.py, unverified) ----
+ * isegmi_op_bbox_aug_candidates: one view's raw box-predictor output -> candidates of the per-image pool, in the first view's coordinates.  Inputs in
+ * isegmi_box_post_args' layout, passed flat.  For every proposal row r < d_prop_cnt[n] (rows at or past the count are never read) and class j = 1..ncls-1 with
+ * p = softmax(logits[r])[j] > score_thresh (strict; the bits of isegmi_op_box_postprocess' probability tensor): box = clip(decode(props[r], deltas[r, j])) as
+ * in isegmi_op_box_postprocess (BoxCoder(10, 10, 5, 5), legacy +1, log(1000/16) clamp, clip to (w - 1, h - 1) of d_image_hw; cls_agnostic: deltas 4..7 for
+ * every class); hflip: x1' = w - x2 - 1, x2' = w - x1 - 1 in fp32; then x *= d_ratios_wh[n][0], y *= d_ratios_wh[n][1] (one fp32 multiplication each).
+ * Candidates are appended to the pool in (proposal asc, class asc) order behind the d_pool_cnt[n] entries already there: slot s < cap gets
+ * d_pool_boxes[n][s], d_pool_scores[n][s] = p, d_pool_labels[n][s] = j; d_pool_cnt[n] advances to min(cap, old + found), d_pool_total[n] by found -- the
+ * pool holds the first cap candidates and total > cap is the overflow signal.  Two launches, no atomics, bitwise reproducible.  R <= 1024, ncls 2..256,
+ * cap 1..8192; bad sizes return ISEGMI_ERR_ARG before any launch.  The merge is isegmi_op_retina_postprocess with nseg 1, seg_len cap, d_seg_cnt d_pool_cnt. */
+int64_t isegmi_op_bbox_aug_workspace(int N, int R);   /* bytes of d_ws (-1: bad sizes) */
+int isegmi_op_bbox_aug_candidates(int N, int R, int ncls, int cls_agnostic, int hflip, int cap, float score_thresh,
+                                  const float* d_logits /* [N*R] rows of ncls */, int64_t logits_stride /* floats between consecutive rois */,
+                                  const float* d_regr /* [N*R] rows; class j deltas at 4j..4j+3 (cls_agnostic: 4..7) */, int64_t regr_stride,
+                                  const float* d_props /* [N][R][4] */, const int32_t* d_prop_cnt /* [N] */,
+                                  const int32_t* d_image_hw /* [N][2] the VIEW's unpadded (h, w) */,
+                                  const float* d_ratios_wh /* [N][2] (w0 / w_view, h0 / h_view) as float */, void* d_ws, int64_t ws_bytes,
+                                  float* d_pool_boxes /* [N][cap][4] */, float* d_pool_scores /* [N][cap] */, int32_t* d_pool_labels /* [N][cap] */,
+                                  int32_t* d_pool_cnt /* [N] read, then advanced */, int32_t* d_pool_total /* [N] the uncapped running count */,
+                                  void* stream);
 /* ---- YOLOv3 tail and route ([UPSTREAM-RECALL] the public yolov3.cfg, unverified) ----
  * isegmi_op_yolo_select: objectness x class selection, top-n cut and grid decode for nl <= 3 levels x N images in two launches, straight from the raw head
  * tensors.  d_heads[l] is [N][H_l][W_l][A * (5 + C)] as the convolution wrote it, channel a * (5 + C) + k, k = 0..4 = tx, ty, tw, th, to, then the class logits;
@@ -685,6 +710,18 @@ int isegmi_maskrcnn_forward(isegmi_engine* e, const float* d_images_nhwc3, const
  * per-level base anchors as tensors "anchor_base.<l>" [A][4] and the strides as params "anchor_stride<l>"; the grid is laid out on the
  * device for the current canvas (isegmi_op_grid_anchors). */
 int isegmi_maskrcnn_forward_canvas(isegmi_engine* e, const float* d_images_nhwc3, const int32_t* h_image_hw, int N, int H, int W);
+/* Test-time box augmentation (TEST.BBOX_AUG) on a box-only FPN engine: begin, one aug_view per view (the first one is view 0, whose
+ * coordinates the results are in), merge.  aug_begin zeroes the pool counters aug.pool_cnt / aug.pool_total [N] and sizes aug.pool_box / _score / _label
+ * for pool_cap (64..8192) slots per image.  aug_view runs the forward on that canvas up to and including the box predictor, then
+ * isegmi_op_bbox_aug_candidates on its output: h_image_hw the view's sizes, hflip whether its input was mirrored, h_ratios_wh [N][2] = (w0 / w_view,
+ * h0 / h_view) as float.  aug_merge runs isegmi_op_retina_postprocess over the pool into det.count / det.box / det.score / det.label (the plain forward's
+ * buffers and order), leaves aug.pool_total fetchable (> pool_cap: the pool overflowed, the caller must not use det.*) and makes view 0's image sizes
+ * current again.  fp32, mask_on 0, keypoint_on 0, no hipGraph, not the C4 body, at most 256 classes: everything else is refused by name.  A plain
+ * forward before or after such a sequence behaves as ever. */
+int isegmi_maskrcnn_aug_begin(isegmi_engine* e, int N, int pool_cap);
+int isegmi_maskrcnn_aug_view(isegmi_engine* e, const float* d_images_nhwc3, const int32_t* h_image_hw, int N, int H, int W, int hflip,
+                             const float* h_ratios_wh);
+int isegmi_maskrcnn_aug_merge(isegmi_engine* e);
 /* RetinaNet (model_kind 4; reached from tools/test_net.py with configs/retinanet_R-*-FPN_1x.yaml, README.md:344-347): the same calling form as
  * the Mask R-CNN pair -- d_images [N][H][W][3] zero-padded to a multiple of 32, h_image_hw [N][2] unpadded (h, w), one engine for every canvas up to its (H, W),
  * anchors ("anchor_base.<l>" [9][4], "anchor_stride<l>", l = 0..4 for P3..P7) laid out again when the canvas changes.  Results: det.count [N], det.box
@@ -755,6 +792,9 @@ int isegmi_engine_upload_async(isegmi_engine* e, void* d_dst, const void* h_src_
 /* isegmi_op_preprocess_u8 on the engine's main stream: behind any upload_async of the bytes, in front of the next forward */
 int isegmi_engine_preprocess_u8(isegmi_engine* e, const uint8_t* d_u8, int N, int Hin, int Win, float* d_out, int Hout, int Wout,
                                 int Hpad, int Wpad, int64_t out_img_stride, const float* mean3, const float* std3, int swap_rb);
+/* isegmi_op_preprocess_u8_flip the same way */
+int isegmi_engine_preprocess_u8_flip(isegmi_engine* e, const uint8_t* d_u8, int N, int Hin, int Win, float* d_out, int Hout, int Wout,
+                                     int Hpad, int Wpad, int64_t out_img_stride, const float* mean3, const float* std3, int swap_rb, int hflip);
 /* per-step completion marks on the results stream; step_times returns the intervals between consecutive marks (ms) */
 int isegmi_engine_mark_step(isegmi_engine* e);
 int isegmi_engine_step_times(isegmi_engine* e, float* ms, int cap, int* count);

@@ -1024,8 +1024,9 @@ extern "C" int isegmi_engine_upload_async(isegmi_engine* h, void* d_dst, const v
 // COPY stream, right behind that copy: batch i+1's transform then runs under forward i instead of sitting in the main stream in front of
 // it (where it would hold forward i back until upload i+1 has crossed PCIe), and the forward that takes d_out as its input waits for it
 // like for an upload.  Otherwise (synchronous isegmi_h2d of the bytes) it runs on the main stream, in front of the next forward.
-extern "C" int isegmi_engine_preprocess_u8(isegmi_engine* h, const uint8_t* d_u8, int N, int Hin, int Win, float* d_out, int Hout, int Wout,
-                                           int Hpad, int Wpad, int64_t out_img_stride, const float* mean3, const float* std3, int swap_rb) {
+// (hflip: the mirrored views of TEST.BBOX_AUG, isegmi_engine_preprocess_u8_flip; the scheduling is the same)
+static int engine_preprocess_u8(isegmi_engine* h, const uint8_t* d_u8, int N, int Hin, int Win, float* d_out, int Hout, int Wout, int Hpad, int Wpad,
+                                int64_t out_img_stride, const float* mean3, const float* std3, int swap_rb, int hflip) {
     ARG_CHECK(h && N > 0, "preprocess args");
     Engine& e = h->e;
     const int64_t src_bytes = (int64_t)N * Hin * Win * 3, dst_bytes = (int64_t)N * out_img_stride * 4;
@@ -1038,7 +1039,7 @@ extern "C" int isegmi_engine_preprocess_u8(isegmi_engine* h, const uint8_t* d_u8
         // d_out's previous reader is fenced by upload_async's wait on in_done, which precedes the copy in this stream
         {
             OpScope op(e, e.copy, "front end (uint8 -> resize / normalise / pad -> fp32 input)", (double)src_bytes + (double)dst_bytes);
-            TRY(preprocess_u8_launch(d_u8, N, Hin, Win, d_out, Hout, Wout, Hpad, Wpad, out_img_stride, mean3, std3, swap_rb, e.copy));
+            TRY(preprocess_u8_launch(d_u8, N, Hin, Win, d_out, Hout, Wout, Hpad, Wpad, out_img_stride, mean3, std3, swap_rb, e.copy, hflip));
         }
         // (The source's upload entry stays UNCONSUMED: a batch is several launches over one staging buffer -- one per image of a Mask R-CNN batch --
         // and every one of them must find it and stay on the copy stream; marking it consumed here sent image 2 of a batch to the main stream,
@@ -1048,11 +1049,20 @@ extern "C" int isegmi_engine_preprocess_u8(isegmi_engine* h, const uint8_t* d_u8
     TRY(eng_wait_upload(e, d_u8, src_bytes, e.stream));
     {
         OpScope op(e, e.stream, "front end (uint8 -> resize / normalise / pad -> fp32 input)", (double)src_bytes + (double)dst_bytes);
-        TRY(preprocess_u8_launch(d_u8, N, Hin, Win, d_out, Hout, Wout, Hpad, Wpad, out_img_stride, mean3, std3, swap_rb, e.stream));
+        TRY(preprocess_u8_launch(d_u8, N, Hin, Win, d_out, Hout, Wout, Hpad, Wpad, out_img_stride, mean3, std3, swap_rb, e.stream, hflip));
     }
     // two lanes: the forward that reads d_out may run on lane 1, which is not behind this (lane 0) main-stream launch -- it waits as for an upload
     if (e.lane_state == 1) return eng_note_upload(e, d_out, dst_bytes, e.stream, 1u);
     return ISEGMI_OK;
+}
+
+extern "C" int isegmi_engine_preprocess_u8(isegmi_engine* h, const uint8_t* d_u8, int N, int Hin, int Win, float* d_out, int Hout, int Wout,
+                                           int Hpad, int Wpad, int64_t out_img_stride, const float* mean3, const float* std3, int swap_rb) {
+    return engine_preprocess_u8(h, d_u8, N, Hin, Win, d_out, Hout, Wout, Hpad, Wpad, out_img_stride, mean3, std3, swap_rb, 0);
+}
+extern "C" int isegmi_engine_preprocess_u8_flip(isegmi_engine* h, const uint8_t* d_u8, int N, int Hin, int Win, float* d_out, int Hout, int Wout,
+                                                int Hpad, int Wpad, int64_t out_img_stride, const float* mean3, const float* std3, int swap_rb, int hflip) {
+    return engine_preprocess_u8(h, d_u8, N, Hin, Win, d_out, Hout, Wout, Hpad, Wpad, out_img_stride, mean3, std3, swap_rb, hflip);
 }
 
 // Records a completion mark for the step just enqueued on the stream its results finish on; isegmi_engine_step_times returns

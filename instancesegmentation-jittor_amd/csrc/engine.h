@@ -132,6 +132,10 @@ struct Engine {
     std::vector<float> last_ratios;
     const void* last_ratios_ptr = nullptr;
     int last_N = 0;
+    // test-time box augmentation: batch and pool slots of the sequence isegmi_maskrcnn_aug_begin opened (0: none open), the views it has
+    // taken, and view 0's image sizes, which aug_merge makes current again
+    int aug_N = 0, aug_cap = 0, aug_views = 0;
+    std::vector<int32_t> aug_hw0;
     // Pose2Seg in two halves: what isegmi_pose2seg_body leaves for isegmi_pose2seg_persons -- the batch's image sizes and P2 -- and, per
     // device keypoint buffer a producer stream fills, the event behind the last persons call that read it (isegmi_pose2seg_wait_persons)
     std::vector<int32_t> p2s_hw;
@@ -379,7 +383,7 @@ int deform_conv2d_launch(const float* x, int N, int H, int W, int C, const float
                          const float* scale, const float* shift, const float* res, int act, float* out, hipStream_t st);
 int pad_c3_c4_launch(const float* in, int64_t npix, float* out, hipStream_t st);
 int preprocess_u8_launch(const uint8_t* in, int N, int Hin, int Win, float* out, int Hout, int Wout, int Hpad, int Wpad, int64_t out_img_stride,
-                         const float* mean3, const float* std3, int swap_rb, hipStream_t st);
+                         const float* mean3, const float* std3, int swap_rb, hipStream_t st, int hflip = 0);
 int pad_c3_c32_launch(const float* in, int64_t npix, float* out, hipStream_t st);
 int yolact_detect_launch(const isegmi_yolact_detect_args* a, hipStream_t st);
 // Detect in two halves: everything up to the final per-image top-k, then the gather.  coeff_sel (optional, [N][max_det][mask_dim] pre-tanh): the gather

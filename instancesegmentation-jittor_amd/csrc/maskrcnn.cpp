@@ -595,10 +595,10 @@ static int mask_head(RcnnCtx& x) {
 
 static int maskrcnn_c4_forward(Engine& e, const float* d_images, int N);
 
-int maskrcnn_forward(Engine& e, const float* d_images, int N) {
-    TRY(keypoint_refusals(e));
-    if (e.param("arch_c4", 0.0f) != 0.0f) return maskrcnn_c4_forward(e, d_images, N);
-    RcnnCtx x{e, N, e.fp16 ? 1 : 0};
+// The FPN graph from the input to the box predictor's rows *cb, on the current canvas; leaves e.cur on the stream the RoI heads run on.  What the plain
+// forward and the views of test-time augmentation (maskrcnn_aug_view) share.
+static int fpn_to_predictor(RcnnCtx& x, const float* d_images, Tensor* cb) {
+    Engine& e = x.e;
     if (e.cur_H % 32 || e.cur_W % 32) { set_error("Mask R-CNN input must be padded to a multiple of 32"); return ISEGMI_ERR_ARG; }
     e.cur = e.stream;
     eng_mark(e, "start");
@@ -606,15 +606,22 @@ int maskrcnn_forward(Engine& e, const float* d_images, int N) {
     x.nms_flags = maskrcnn_nms_flags(e); x.roi_aligned = (int)e.param("roi_aligned", 0) ? 1 : 0;
     x.roi_table = (int)e.param("roi_table", x.dt ? 3.0f : 1.0f);
     rpn_config(x);
-    TRY(rcnn_trunk(e, d_images, N, true, x.C));
+    TRY(rcnn_trunk(e, d_images, x.N, true, x.C));
     TRY(x.grp ? fpn_topdown_grouped(x) : fpn_topdown_levels(x));
     eng_mark(e, "fpn_topdown");
     TRY(fpn_out_and_rpn(x));
     eng_mark(e, "fpn_out+rpn");
     TRY(merge_proposals(x));
     eng_mark(e, "proposals");
+    return box_head(x, cb);
+}
+
+int maskrcnn_forward(Engine& e, const float* d_images, int N) {
+    TRY(keypoint_refusals(e));
+    if (e.param("arch_c4", 0.0f) != 0.0f) return maskrcnn_c4_forward(e, d_images, N);
+    RcnnCtx x{e, N, e.fp16 ? 1 : 0};
     Tensor cb;
-    TRY(box_head(x, &cb));
+    TRY(fpn_to_predictor(x, d_images, &cb));
     TRY(box_tail(e, N, x.fpn_post, cb, x.props, x.prop_cnt, x.d_hw, x.nms_flags, &x.a));
     eng_mark(e, "box_head");
     // Faster R-CNN (neither head): det.* is the result; the tail's bookkeeping as behind a head
@@ -622,6 +629,119 @@ int maskrcnn_forward(Engine& e, const float* d_images, int N) {
     else if (maskrcnn_mask_on(e)) TRY(mask_head(x));
     TRY(eng_tail_end(e));
     e.cur = e.stream;
+    return ISEGMI_OK;
+}
+
+// ---- test-time box augmentation: begin / view / merge
+// What the augmented path is built for; everything else is refused by name.
+static int aug_refusals(Engine& e) {
+    const char* why = e.fp16 ? "fp16: test-time box augmentation is fp32 only"
+                      : e.param("arch_c4", 0.0f) != 0.0f ? "arch_c4 (the R-50-C4 body): test-time box augmentation is built on the FPN bodies"
+                      : e.param("graph", 0.0f) != 0.0f ? "graph 1: the views of test-time box augmentation change canvas and are not captured, set graph 0"
+                      : maskrcnn_mask_on(e) ? "mask_on 1 (MODEL.MASK_ON True): test-time box augmentation returns boxes only, set mask_on 0"
+                      : maskrcnn_keypoint_on(e) ? "keypoint_on 1 (MODEL.KEYPOINT_ON True): test-time box augmentation returns boxes only"
+                      : nullptr;
+    if (why) { set_error(std::string("bbox_aug (TEST.BBOX_AUG) with ") + why); return ISEGMI_ERR_STATE; }
+    const int nc = (int)e.param("num_classes", 81.0f);
+    if (nc < 2 || nc > 256) { set_error("bbox_aug (TEST.BBOX_AUG): num_classes (MODEL.ROI_BOX_HEAD.NUM_CLASSES) must be 2..256 (the merge sorts labels in one byte), got " + std::to_string(nc)); return ISEGMI_ERR_STATE; }
+    const int R = (int)e.param("rpn_fpn_post_nms_top_n", 1000);   // before any view's forward is enqueued: the candidate stage holds 1024 rows per image
+    if (R < 1 || R > 1024) { set_error("bbox_aug (TEST.BBOX_AUG): rpn_fpn_post_nms_top_n (MODEL.RPN.FPN_POST_NMS_TOP_N_TEST) must be 1..1024, got " + std::to_string(R)); return ISEGMI_ERR_STATE; }
+    return ISEGMI_OK;
+}
+
+struct AugPool { float *boxes, *scores; int *labels, *cnt, *total; };
+static int aug_pool(Engine& e, AugPool* p) {
+    const int64_t N = e.max_batch, cap = e.aug_cap;
+    void* q;
+    TRY(eng_buf(e, "aug.pool_box", N * cap * 16, &q, 0, {N, cap, 4})); p->boxes = (float*)q;
+    TRY(eng_buf(e, "aug.pool_score", N * cap * 4, &q, 0, {N, cap})); p->scores = (float*)q;
+    TRY(eng_buf(e, "aug.pool_label", N * cap * 4, &q, 1, {N, cap})); p->labels = (int*)q;
+    TRY(eng_buf(e, "aug.pool_cnt", N * 4, &q, 1, {N})); p->cnt = (int*)q;
+    TRY(eng_buf(e, "aug.pool_total", N * 4, &q, 1, {N})); p->total = (int*)q;
+    return ISEGMI_OK;
+}
+
+// The pool lives on the stream the RoI heads run on (the tail stream; the main stream without multi_stream): every launch that touches it goes there.
+static hipStream_t aug_stream(Engine& e) { return e.multi_stream ? e.tail : e.stream; }
+
+static int maskrcnn_aug_begin(Engine& e, int N, int pool_cap) {
+    TRY(aug_refusals(e));
+    ARG_CHECK(N > 0 && N <= e.max_batch, "batch size");
+    if (pool_cap < 64 || pool_cap > 8192) { set_error("bbox_aug: pool_cap (BBoxAugConfig.POOL_CAP) must be 64..8192 (the merge sorts 8192 slots in LDS), got " + std::to_string(pool_cap)); return ISEGMI_ERR_ARG; }
+    e.aug_N = N; e.aug_cap = pool_cap; e.aug_views = 0; e.aug_hw0.clear();
+    AugPool p;
+    TRY(aug_pool(e, &p));
+    hipStream_t st = aug_stream(e);   // in stream order behind the previous sequence's merge and whatever read det.* there
+    HIP_TRY(hipMemsetAsync(p.cnt, 0, (size_t)e.max_batch * 4, st));
+    HIP_TRY(hipMemsetAsync(p.total, 0, (size_t)e.max_batch * 4, st));
+    return ISEGMI_OK;
+}
+
+static int maskrcnn_aug_view(Engine& e, const float* d_images, const int32_t* h_image_hw, int N, int hflip, const float* h_ratios_wh) {
+    TRY(aug_refusals(e));
+    if (e.aug_N <= 0) { set_error("aug_view before aug_begin"); return ISEGMI_ERR_STATE; }
+    ARG_CHECK(N == e.aug_N, "aug_view: the batch size aug_begin was given");
+    if (e.aug_views == 0) e.aug_hw0.assign(h_image_hw, h_image_hw + 2 * N);
+    RcnnCtx x{e, N, 0};
+    Tensor cb;
+    TRY(fpn_to_predictor(x, d_images, &cb));
+    eng_mark(e, "box_head");
+    BBoxAugArgs a;
+    memset(&a, 0, sizeof(a));
+    TRY(box_predictor_shape(e, cb.C, &a.ncls, &a.cls_agnostic));
+    AugPool p;
+    TRY(aug_pool(e, &p));
+    void *rt, *ws;
+    TRY(eng_buf(e, "aug.ratios", (int64_t)e.max_batch * 8, &rt));
+    a.ws_bytes = bbox_aug_workspace_bytes(e.max_batch, 1024);
+    TRY(eng_buf(e, "aug.ws", a.ws_bytes, &ws, 1));
+    TRY(eng_stage_small(e, h_ratios_wh, (size_t)N * 8, rt, e.cur));   // behind the previous view's candidate stage, which read it on this stream
+    a.N = N; a.R = x.fpn_post; a.hflip = hflip ? 1 : 0; a.cap = e.aug_cap;
+    a.score_thresh = e.param("roi_score_thresh", 0.05f);
+    a.logits_stride = cb.C; a.regr_stride = cb.C;
+    a.d_logits = cb.d; a.d_regr = cb.d + a.ncls; a.d_props = x.props; a.d_prop_cnt = x.prop_cnt; a.d_image_hw = x.d_hw; a.d_ratios_wh = (const float*)rt;
+    a.d_ws = ws;
+    a.d_pool_boxes = p.boxes; a.d_pool_scores = p.scores; a.d_pool_labels = p.labels; a.d_pool_cnt = p.cnt; a.d_pool_total = p.total;
+    {
+        // logits + box regressions of every proposal once and the proposals in; at most the pool's slots out
+        OpScope op(e, e.cur, "bbox_aug_candidates (softmax + decode + unflip + rescale, one view)", (double)N * a.R * ((double)cb.C * 4 + 16) + (double)N * e.aug_cap * 24);
+        TRY(bbox_aug_candidates_launch(&a, e.cur));
+    }
+    eng_mark(e, "aug_candidates");
+    ++e.aug_views;
+    TRY(eng_tail_end(e));
+    e.cur = e.stream;
+    return ISEGMI_OK;
+}
+
+static int maskrcnn_aug_merge(Engine& e) {
+    TRY(aug_refusals(e));
+    if (e.aug_N <= 0 || e.aug_views <= 0) { set_error("aug_merge before aug_begin and at least one aug_view"); return ISEGMI_ERR_STATE; }
+    const int N = e.aug_N, dpi = (int)e.param("detections_per_img", 100), cap = maskrcnn_det_cap(e);
+    AugPool p;
+    TRY(aug_pool(e, &p));
+    isegmi_retina_post_args a;
+    memset(&a, 0, sizeof(a));
+    void* q;
+    a.N = N; a.nseg = 1; a.seg_len = e.aug_cap; a.ncls = (int)e.param("num_classes", 81.0f); a.det_per_img = dpi; a.cap = cap;
+    a.nms_flags = maskrcnn_nms_flags(e); a.nms_thresh = e.param("roi_nms_thresh", 0.5f);
+    a.d_boxes = p.boxes; a.d_scores = p.scores; a.d_labels = p.labels; a.d_seg_cnt = p.cnt;
+    a.ws_bytes = retina_post_workspace_bytes(e.max_batch, 1, e.aug_cap);
+    TRY(eng_buf(e, "aug.merge_ws", a.ws_bytes, &q, 1)); a.d_ws = q;
+    TRY(eng_buf(e, "det.count", (int64_t)N * 4, &q, 1, {N})); a.d_out_count = (int*)q;
+    TRY(eng_buf(e, "det.box", (int64_t)N * cap * 16, &q, 0, {N, cap, 4})); a.d_out_boxes = (float*)q;
+    TRY(eng_buf(e, "det.score", (int64_t)N * cap * 4, &q, 0, {N, cap})); a.d_out_scores = (float*)q;
+    TRY(eng_buf(e, "det.label", (int64_t)N * cap * 4, &q, 1, {N, cap})); a.d_out_labels = (int*)q;
+    hipStream_t st = aug_stream(e);
+    {
+        OpScope op(e, st, "bbox_aug_merge (class-wise NMS + detection cut over the pool)", (double)N * e.aug_cap * 24 + (double)N * cap * 24);
+        TRY(retina_postprocess_launch(&a, st));
+    }
+    TRY(eng_tail_end(e));
+    e.cur = e.stream;
+    TRY(maskrcnn_set_image_hw(e, e.aug_hw0.data(), N));   // the sizes the results are in: view 0's
+    e.last_N = N;
+    e.aug_N = 0; e.aug_views = 0;
     return ISEGMI_OK;
 }
 
@@ -808,6 +928,33 @@ extern "C" int isegmi_maskrcnn_forward_canvas(isegmi_engine* h, const float* d_i
     if (graph_on) { e.anchor_H = -1; e.anchor_W = -1; }  // a replay leaves ITS canvas's anchors behind, whatever the bookkeeping says
     e.cur = e.stream;
     if (rc == ISEGMI_OK) e.last_N = N;
+    return rc;
+}
+
+extern "C" int isegmi_maskrcnn_aug_begin(isegmi_engine* h, int N, int pool_cap) {
+    ARG_CHECK(h, "null");
+    ARG_CHECK(h->e.kind == 2, "engine is not a Mask R-CNN engine");
+    return maskrcnn_aug_begin(h->e, N, pool_cap);
+}
+
+extern "C" int isegmi_maskrcnn_aug_view(isegmi_engine* h, const float* d_images, const int32_t* h_image_hw, int N, int H, int W, int hflip,
+                                        const float* h_ratios_wh) {
+    ARG_CHECK(h && d_images && h_image_hw && h_ratios_wh, "null");
+    ARG_CHECK(h->e.kind == 2, "engine is not a Mask R-CNN engine");
+    Engine& e = h->e;
+    TRY(aug_refusals(e));
+    TRY(rcnn_canvas_check(e, N, H, W));
+    TRY(rcnn_begin_canvas(e, d_images, h_image_hw, N, H, W));
+    const int rc = maskrcnn_aug_view(e, d_images, h_image_hw, N, hflip, h_ratios_wh);
+    e.cur = e.stream;
+    return rc;
+}
+
+extern "C" int isegmi_maskrcnn_aug_merge(isegmi_engine* h) {
+    ARG_CHECK(h, "null");
+    ARG_CHECK(h->e.kind == 2, "engine is not a Mask R-CNN engine");
+    const int rc = maskrcnn_aug_merge(h->e);
+    h->e.cur = h->e.stream;
     return rc;
 }
 

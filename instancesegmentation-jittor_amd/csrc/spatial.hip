@@ -107,6 +107,7 @@ struct PreU8 {
     const uint8_t* in;
     float* out;
     int N, Hin, Win, Hout, Wout, Hpad, Wpad, swap;
+    int hflip;               // the source is the image mirrored within Win: taps x0, x1 read columns Win-1-x0, Win-1-x1
     int64_t out_img_stride;  // floats
     float sch, scw;          // np.float32(Hin / Hout), np.float32(Win / Wout)
     float mean[3], stdv[3];
@@ -128,10 +129,11 @@ __global__ void preprocess_u8_kernel(const PreU8 a) {
         const float ly1 = sy - (float)y0, lx1 = sx - (float)x0;
         const float ly0 = 1.0f - ly1, lx0 = 1.0f - lx1;
         const uint8_t* img = a.in + (int64_t)n * a.Hin * a.Win * 3;
-        const uint8_t* p00 = img + ((int64_t)y0 * a.Win + x0) * 3;
-        const uint8_t* p01 = img + ((int64_t)y0 * a.Win + x1) * 3;
-        const uint8_t* p10 = img + ((int64_t)y1 * a.Win + x0) * 3;
-        const uint8_t* p11 = img + ((int64_t)y1 * a.Win + x1) * 3;
+        const int c0 = a.hflip ? a.Win - 1 - x0 : x0, c1 = a.hflip ? a.Win - 1 - x1 : x1;
+        const uint8_t* p00 = img + ((int64_t)y0 * a.Win + c0) * 3;
+        const uint8_t* p01 = img + ((int64_t)y0 * a.Win + c1) * 3;
+        const uint8_t* p10 = img + ((int64_t)y1 * a.Win + c0) * 3;
+        const uint8_t* p11 = img + ((int64_t)y1 * a.Win + c1) * 3;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const float top = (float)p00[c] * lx0 + (float)p01[c] * lx1;
@@ -255,12 +257,13 @@ int pad_c3_c4_launch(const float* in, int64_t npix, float* out, hipStream_t st) 
 }
 
 int preprocess_u8_launch(const uint8_t* in, int N, int Hin, int Win, float* out, int Hout, int Wout, int Hpad, int Wpad, int64_t out_img_stride,
-                         const float* mean3, const float* std3, int swap_rb, hipStream_t st) {
+                         const float* mean3, const float* std3, int swap_rb, hipStream_t st, int hflip) {
     ARG_CHECK(in && out && mean3 && std3, "null");
     ARG_CHECK(N > 0 && Hin > 0 && Win > 0 && Hout > 0 && Wout > 0 && Hpad >= Hout && Wpad >= Wout, "preprocess geometry");
     ARG_CHECK(out_img_stride >= (int64_t)Hpad * Wpad * 3, "output image stride");
     PreU8 a;
     a.in = in; a.out = out; a.N = N; a.Hin = Hin; a.Win = Win; a.Hout = Hout; a.Wout = Wout; a.Hpad = Hpad; a.Wpad = Wpad; a.swap = swap_rb ? 1 : 0;
+    a.hflip = hflip ? 1 : 0;
     a.out_img_stride = out_img_stride;
     a.sch = (float)((double)Hin / (double)Hout);  // np.float32(i / o)
     a.scw = (float)((double)Win / (double)Wout);
@@ -276,7 +279,11 @@ using namespace isegmi;
 
 extern "C" int isegmi_op_preprocess_u8(const uint8_t* d_in, int N, int Hin, int Win, float* d_out, int Hout, int Wout, int Hpad, int Wpad,
                                        int64_t out_img_stride, const float* mean3, const float* std3, int swap_rb, void* stream) {
-    return preprocess_u8_launch(d_in, N, Hin, Win, d_out, Hout, Wout, Hpad, Wpad, out_img_stride, mean3, std3, swap_rb, (hipStream_t)stream);
+    return preprocess_u8_launch(d_in, N, Hin, Win, d_out, Hout, Wout, Hpad, Wpad, out_img_stride, mean3, std3, swap_rb, (hipStream_t)stream, 0);
+}
+extern "C" int isegmi_op_preprocess_u8_flip(const uint8_t* d_in, int N, int Hin, int Win, float* d_out, int Hout, int Wout, int Hpad, int Wpad,
+                                            int64_t out_img_stride, const float* mean3, const float* std3, int swap_rb, int hflip, void* stream) {
+    return preprocess_u8_launch(d_in, N, Hin, Win, d_out, Hout, Wout, Hpad, Wpad, out_img_stride, mean3, std3, swap_rb, (hipStream_t)stream, hflip);
 }
 extern "C" int isegmi_op_maxpool(const float* d_in, int N, int H, int W, int C, int k, int s, int p, float* d_out,
                                  void* stream) {

@@ -58,6 +58,20 @@ int retina_select_launch(const isegmi_retina_select_args* p, hipStream_t st);
 int64_t retina_post_workspace_bytes(int N, int nseg, int seg_len);
 int retina_postprocess_launch(const isegmi_retina_post_args* p, hipStream_t st);
 
+// ---- csrc/bbox_aug.hip
+int64_t bbox_aug_workspace_bytes(int N, int R);
+struct BBoxAugArgs {   // isegmi_op_bbox_aug_candidates' arguments (include/isegmi.h says what each one is)
+    int N, R, ncls, cls_agnostic, hflip, cap;
+    float score_thresh;
+    int64_t logits_stride, regr_stride, ws_bytes;
+    const float *d_logits, *d_regr, *d_props, *d_ratios_wh;
+    const int *d_prop_cnt, *d_image_hw;
+    void* d_ws;
+    float *d_pool_boxes, *d_pool_scores;
+    int *d_pool_labels, *d_pool_cnt, *d_pool_total;
+};
+int bbox_aug_candidates_launch(const BBoxAugArgs* p, hipStream_t st);
+
 // ---- csrc/yolo_ops.hip
 int yolo_slice_records(int C);   // anchor records per slice of yolo_select's first launch (-1: C outside 1..256)
 int64_t yolo_select_workspace_bytes(int nl, int N, const int* grid_hw, int A, int C, int top_n);

@@ -130,6 +130,7 @@ SIGNATURES = {
     "isegmi_set_f16_mfma_shape": (I, [I]),
     "isegmi_get_f16_mfma_shape": (I, [V]),
     "isegmi_op_preprocess_u8": (I, [V, I, I, I, V, I, I, I, I, L, V, V, I, V]),
+    "isegmi_op_preprocess_u8_flip": (I, [V, I, I, I, V, I, I, I, I, L, V, V, I, I, V]),
     "isegmi_op_maxpool": (I, [V, I, I, I, I, I, I, I, V, V]),
     "isegmi_op_resize_bilinear": (I, [V, I, I, I, I, I, I, V, I, V, V]),
     "isegmi_op_keypoint_heatmap": (I, [V, L, I, I, I, V, V]),
@@ -169,6 +170,8 @@ SIGNATURES = {
     "isegmi_op_retina_select": (I, [V, V]),
     "isegmi_op_retina_postprocess_workspace": (L, [I, I, I]),
     "isegmi_op_retina_postprocess": (I, [V, V]),
+    "isegmi_op_bbox_aug_workspace": (L, [I, I]),
+    "isegmi_op_bbox_aug_candidates": (I, [I, I, I, I, I, I, F, V, L, V, L, V, V, V, V, V, L, V, V, V, V, V, V]),
     "isegmi_op_yolo_slice_records": (I, [I]),
     "isegmi_op_yolo_select_workspace": (L, [I, I, V, I, I, I]),
     "isegmi_op_yolo_select": (I, [I, I, V, V, V, V, I, I, I, F, I, F, I, I, V, L, V, V, V, V, V, V]),
@@ -201,6 +204,9 @@ SIGNATURES = {
     "isegmi_yolact_forward": (I, [V, V, I]),
     "isegmi_maskrcnn_forward": (I, [V, V, V, I]),
     "isegmi_maskrcnn_forward_canvas": (I, [V, V, V, I, I, I]),
+    "isegmi_maskrcnn_aug_begin": (I, [V, I, I]),
+    "isegmi_maskrcnn_aug_view": (I, [V, V, V, I, I, I, I, V]),
+    "isegmi_maskrcnn_aug_merge": (I, [V]),
     "isegmi_retinanet_forward": (I, [V, V, V, I]),
     "isegmi_retinanet_forward_canvas": (I, [V, V, V, I, I, I]),
     "isegmi_yolov3_forward": (I, [V, V, I]),
@@ -217,6 +223,7 @@ SIGNATURES = {
     "isegmi_engine_stream": (I, [V, V]),
     "isegmi_engine_upload_async": (I, [V, V, V, L]),
     "isegmi_engine_preprocess_u8": (I, [V, V, I, I, I, V, I, I, I, I, L, V, V, I]),
+    "isegmi_engine_preprocess_u8_flip": (I, [V, V, I, I, I, V, I, I, I, I, L, V, V, I, I]),
     "isegmi_engine_mark_step": (I, [V]),
     "isegmi_engine_step_times": (I, [V, V, I, V]),
     "isegmi_engine_wait_mark": (I, [V, I]),

@@ -349,6 +349,18 @@ def preprocess_u8(images_u8, Hout, Wout, Hpad, Wpad, mean3, std3, swap_rb):
     return do.numpy()
 
 
+def preprocess_u8_flip(images_u8, Hout, Wout, Hpad, Wpad, mean3, std3, swap_rb, hflip):
+    """isegmi_op_preprocess_u8_flip: preprocess_u8 of the images mirrored within their own width, the bytes untouched."""
+    x = np.ascontiguousarray(images_u8)
+    if x.dtype != np.uint8 or x.ndim != 4 or x.shape[3] != 3:
+        raise TypeError("preprocess_u8_flip takes an [N, H, W, 3] uint8 batch")
+    N, H, W, _ = x.shape
+    dx = DeviceBuffer.from_numpy(x); do = DeviceBuffer((N, Hpad, Wpad, 3)).poison()
+    m = (C.c_float * 3)(*[float(v) for v in mean3]); sd = (C.c_float * 3)(*[float(v) for v in std3])
+    check(lib().isegmi_op_preprocess_u8_flip(dx.ptr, N, H, W, do.ptr, Hout, Wout, Hpad, Wpad, Hpad * Wpad * 3, m, sd, int(bool(swap_rb)), int(bool(hflip)), None))
+    return do.numpy()
+
+
 def deform_im2col(x, om, R=3, S=3, stride=1, pad=1, dil=1):
     """x [N,H,W,C], om [N,Ho,Wo,3*R*S] raw conv_offset_mask output -> DCNv2 columns [N,Ho,Wo,R*S*C]."""
     x = np.ascontiguousarray(x, np.float32); om = np.ascontiguousarray(om, np.float32)
@@ -841,6 +853,54 @@ def retina_postprocess(boxes, scores, labels, seg_cnt, ncls=81, nms_thr=0.4, det
     ws = DeviceBuffer((wsb,), np.uint8).poison()   # dirty on purpose: nothing may be read before it is written
     oc = DeviceBuffer((N,), np.int32).poison(); ob = DeviceBuffer((N, cap, 4)).poison(); os_ = DeviceBuffer((N, cap)).poison(); ol = DeviceBuffer((N, cap), np.int32).poison()
     a = RetinaPostArgs(N, nseg, seg_len, ncls, det_per_img, cap, nms_flags, nms_thr, db.ptr, ds.ptr, dl.ptr, dc.ptr, ws.ptr, wsb, oc.ptr, ob.ptr, os_.ptr, ol.ptr)
+    check(lib().isegmi_op_retina_postprocess(C.byref(a), None))
+    c = oc.numpy(); B = ob.numpy(); S = os_.numpy(); Lb = ol.numpy()
+    return [(B[i, : c[i]], S[i, : c[i]], Lb[i, : c[i]]) for i in range(N)]
+
+
+# ---------------------------------------------------------------- test-time box augmentation
+class BBoxAugPool:
+    """The per-image candidate pool of isegmi_op_bbox_aug_candidates on the device: boxes [N,cap,4], scores / labels [N,cap], cnt / total [N].  Created
+    poisoned (nothing may be read before it is written) with the counters at `cnt` / `total` (default 0)."""
+
+    def __init__(self, N, cap, cnt=None, total=None):
+        self.N, self.cap = int(N), int(cap)
+        self.boxes = DeviceBuffer((N, cap, 4)).poison(); self.scores = DeviceBuffer((N, cap)).poison(); self.labels = DeviceBuffer((N, cap), np.int32).poison()
+        c = np.zeros(N, np.int32) if cnt is None else np.ascontiguousarray(cnt, np.int32)
+        self.cnt = DeviceBuffer.from_numpy(c)
+        self.total = DeviceBuffer.from_numpy(c.copy() if total is None else np.ascontiguousarray(total, np.int32))
+
+    def numpy(self):
+        """-> (boxes, scores, labels, cnt, total) as they are on the device, slots past the counts included"""
+        return self.boxes.numpy(), self.scores.numpy(), self.labels.numpy(), self.cnt.numpy(), self.total.numpy()
+
+
+def bbox_aug_candidates(pool, logits, regr, props, prop_cnt, image_hw, hflip=0, ratios_wh=None, score_thr=0.05, cls_agnostic=0, R=None, ncls=None, cap=None):
+    """isegmi_op_bbox_aug_candidates of one view into `pool` (a BBoxAugPool): logits [N,R,ncls], regr [N,R,4*ncls] ([N,R,8] with cls_agnostic), props [N,R,4],
+    prop_cnt [N], image_hw [N,2], ratios_wh [N,2] (default 1).  R / ncls / cap override what the arrays say (refusal tests)."""
+    logits = np.ascontiguousarray(logits, np.float32); regr = np.ascontiguousarray(regr, np.float32)
+    N, R_, C_ = logits.shape
+    r = np.ones((N, 2), np.float32) if ratios_wh is None else np.ascontiguousarray(ratios_wh, np.float32).reshape(N, 2)
+    dl = DeviceBuffer.from_numpy(logits); dr = DeviceBuffer.from_numpy(regr); dp = DeviceBuffer.from_numpy(np.ascontiguousarray(props, np.float32))
+    dc = DeviceBuffer.from_numpy(np.ascontiguousarray(prop_cnt, np.int32)); dh = DeviceBuffer.from_numpy(np.ascontiguousarray(image_hw, np.int32))
+    drt = DeviceBuffer.from_numpy(r)
+    wsb = max(int(lib().isegmi_op_bbox_aug_workspace(N, R_)), 256)
+    ws = DeviceBuffer((wsb,), np.uint8).poison()
+    check(lib().isegmi_op_bbox_aug_candidates(N, R_ if R is None else R, C_ if ncls is None else ncls, int(bool(cls_agnostic)), int(bool(hflip)),
+                                              pool.cap if cap is None else cap, score_thr, dl.ptr, C_, dr.ptr, regr.shape[2], dp.ptr, dc.ptr, dh.ptr, drt.ptr, ws.ptr, wsb,
+                                              pool.boxes.ptr, pool.scores.ptr, pool.labels.ptr, pool.cnt.ptr, pool.total.ptr, None))
+    check(lib().isegmi_sync())
+
+
+def bbox_aug_merge(pool, ncls, nms_thr=0.5, det_per_img=100, cap=100, nms_flags=0):
+    """The merge of test-time box augmentation: isegmi_op_retina_postprocess over the pool with nseg 1, seg_len cap, d_seg_cnt the pool count."""
+    N = pool.N
+    wsb = lib().isegmi_op_retina_postprocess_workspace(N, 1, pool.cap)
+    ws = DeviceBuffer((wsb,), np.uint8).poison()
+    cap = max(det_per_img, cap)
+    oc = DeviceBuffer((N,), np.int32).poison(); ob = DeviceBuffer((N, cap, 4)).poison(); os_ = DeviceBuffer((N, cap)).poison(); ol = DeviceBuffer((N, cap), np.int32).poison()
+    a = RetinaPostArgs(N, 1, pool.cap, ncls, det_per_img, cap, nms_flags, nms_thr, pool.boxes.ptr, pool.scores.ptr, pool.labels.ptr, pool.cnt.ptr, ws.ptr, wsb,
+                       oc.ptr, ob.ptr, os_.ptr, ol.ptr)
     check(lib().isegmi_op_retina_postprocess(C.byref(a), None))
     c = oc.numpy(); B = ob.numpy(); S = os_.numpy(); Lb = ol.numpy()
     return [(B[i, : c[i]], S[i, : c[i]], Lb[i, : c[i]]) for i in range(N)]

@@ -152,15 +152,19 @@ def cmd_eval(a):
 
 def cmd_test_net(a):
     """tools/test_net.py: build the model from the yaml, run inference() over the images, write COCO-format json."""
-    from .config import cfg, is_keypoint_rcnn, is_retinanet, to_keypointrcnn_config, to_maskrcnn_config, to_retinanet_config
+    from .config import cfg, is_bbox_aug, is_keypoint_rcnn, is_retinanet, to_bbox_aug_config, to_keypointrcnn_config, to_maskrcnn_config, to_retinanet_config
     from .predictor import COCODemo, inference
     c = cfg.clone()
     if a.config_file:
         c.merge_from_file(a.config_file)
     c.merge_from_list(a.opts)
     retina = is_retinanet(c)   # MODEL.RETINANET_ON: the one-stage detector, bbox results only
+    # TEST.BBOX_AUG.ENABLED: multi-scale + flip inference of a box-only model (DESIGN.md 23); the other mappings refuse the key by name
+    bbox_aug = None
+    if is_bbox_aug(c) and not retina and not is_keypoint_rcnn(c):
+        mc_aug, bbox_aug = to_bbox_aug_config(c)
     # MODEL.KEYPOINT_ON: Keypoint R-CNN -- one json entry per detection with `keypoints`; --gt prints the bbox block and then the keypoints block (DESIGN.md 10, 14)
-    mc = to_retinanet_config(c) if retina else to_keypointrcnn_config(c) if is_keypoint_rcnn(c) else to_maskrcnn_config(c)
+    mc = mc_aug if bbox_aug is not None else to_retinanet_config(c) if retina else to_keypointrcnn_config(c) if is_keypoint_rcnn(c) else to_maskrcnn_config(c)
     rank, world, local = _rank_world()
     files = sorted(os.path.join(a.images, f) for f in os.listdir(a.images)) if a.images else []
     if retina:
@@ -172,7 +176,7 @@ def cmd_test_net(a):
         sd = _weights(c.MODEL.WEIGHT, "maskrcnn", mc.depth, gn=mc.USE_GN)
     box_only = retina or not mc.MASK_ON   # RetinaNet and Faster R-CNN (MODEL.MASK_ON False): bbox results only
     demo = COCODemo(mc, min_image_size=mc.MIN_SIZE_TEST, confidence_threshold=0.0, state_dict=sd,
-                    max_image_size=mc.MAX_SIZE_TEST, device=local, max_batch=a.batch_size)
+                    max_image_size=mc.MAX_SIZE_TEST, device=local, max_batch=a.batch_size, bbox_aug=bbox_aug)
     stats = {}
     results = inference(demo, lambda i: _load_image_bgr(files[i]), batch_size=a.batch_size, group=a.group, rank=rank, world=world,
                         sizes=_image_sizes(files), stats=stats) if files else []

@@ -13,7 +13,7 @@ import copy
 
 import yaml
 
-from .maskrcnn import MaskRCNNConfig, gn_groups, gn_model_layers, resnext_check
+from .maskrcnn import BBOX_AUG_MAX_POOL, BBoxAugConfig, MaskRCNNConfig, gn_groups, gn_model_layers, resnext_check
 
 
 def _literal(v):
@@ -70,7 +70,8 @@ def _defaults():
     c._merge({
         "INPUT": {"MIN_SIZE_TEST": 800, "MAX_SIZE_TEST": 1333, "PIXEL_MEAN": (102.9801, 115.9465, 122.7717), "TO_BGR255": True},
         "DATALOADER": {"SIZE_DIVISIBILITY": 32},
-        "TEST": {"DETECTIONS_PER_IMG": 100, "BBOX_AUG": {"ENABLED": False}},
+        "TEST": {"DETECTIONS_PER_IMG": 100, # [UPSTREAM-RECALL] maskrcnn-benchmark defaults.py, TEST.BBOX_AUG
+                 "BBOX_AUG": {"ENABLED": False, "H_FLIP": False, "SCALES": (), "MAX_SIZE": 4000, "SCALE_H_FLIP": False}},
         # MASK_ON: upstream's default is False; this project's is True -- the e2e_faster_rcnn_* yamls under configs/ spell it out
         "MODEL": {"META_ARCHITECTURE": "GeneralizedRCNN", "WEIGHT": "", "MASK_ON": True, "RETINANET_ON": False, "RPN_ONLY": False, "KEYPOINT_ON": False,
                   "CLS_AGNOSTIC_BBOX_REG": False,
@@ -219,7 +220,51 @@ def to_maskrcnn_config(c):
     return _two_stage_config(c)
 
 
-def _two_stage_config(c):
+def is_bbox_aug(c):
+    """True for a yaml-keyed node that asks for test-time box augmentation (TEST.BBOX_AUG.ENABLED)."""
+    return _bool(c.TEST.get("BBOX_AUG", {}).get("ENABLED", False))
+
+
+def to_bbox_aug_config(c):
+    """[UPSTREAM-RECALL] The yaml-keyed node of a Faster R-CNN config with TEST.BBOX_AUG.ENABLED -> (MaskRCNNConfig, BBoxAugConfig); raises, naming the
+    key, for everything the augmented path is not built for.  The model side goes through the two-stage mapping."""
+    m, a = c.MODEL, c.TEST.get("BBOX_AUG", {})
+    if not is_bbox_aug(c):
+        raise ValueError("TEST.BBOX_AUG.ENABLED=False: not a test-time augmentation config (to_maskrcnn_config maps the plain two-stage models)")
+    if is_retinanet(c):
+        raise ValueError("TEST.BBOX_AUG.ENABLED=True together with MODEL.RETINANET_ON: test-time box augmentation is built for the two-stage box head")
+    if is_keypoint_rcnn(c):
+        raise ValueError("TEST.BBOX_AUG.ENABLED=True together with MODEL.KEYPOINT_ON: the augmented path returns boxes only")
+    if _bool(m.MASK_ON):
+        raise ValueError("TEST.BBOX_AUG.ENABLED=True together with MODEL.MASK_ON=True: the augmented path returns boxes only (as upstream's), set MODEL.MASK_ON: False")
+    body = str(m.BACKBONE.CONV_BODY)
+    if body.endswith("-C4"):
+        raise ValueError("TEST.BBOX_AUG.ENABLED=True with MODEL.BACKBONE.CONV_BODY=%r: test-time box augmentation is built on the FPN bodies" % body)
+    ncls = int(m.ROI_BOX_HEAD.NUM_CLASSES)
+    if ncls > 256:
+        raise ValueError("MODEL.ROI_BOX_HEAD.NUM_CLASSES=%d with TEST.BBOX_AUG.ENABLED: the merge holds 2..256 classes (background included)" % ncls)
+    scales = a.get("SCALES", ())
+    if isinstance(scales, (str, bytes)) or not hasattr(scales, "__iter__"):
+        raise ValueError("TEST.BBOX_AUG.SCALES=%r: a tuple of positive integers" % (scales,))
+    scales = tuple(scales)
+    for s in scales:
+        if isinstance(s, bool) or not isinstance(s, int) or s <= 0:
+            raise ValueError("TEST.BBOX_AUG.SCALES=%r: every scale is a positive integer (got %r)" % (scales, s))
+    max_size = a.get("MAX_SIZE", 4000)
+    # merge_from_list parses lists and tuples only, so `test_net ... TEST.BBOX_AUG.MAX_SIZE 2000` leaves the text "2000" in the node (SCALES "(400, 600)"
+    # arrives as a tuple of integers already); the other integer keys take int(...) of such text too (INPUT.MIN_SIZE_TEST, MODEL.RPN.*_TOP_N_TEST)
+    if isinstance(max_size, str) and max_size.strip().isdigit():
+        max_size = int(max_size)
+    if isinstance(max_size, bool) or not isinstance(max_size, int) or max_size <= 0:
+        raise ValueError("TEST.BBOX_AUG.MAX_SIZE=%r: a positive integer" % (max_size,))
+    if scales and max_size < max(scales):
+        raise ValueError("TEST.BBOX_AUG.MAX_SIZE=%d is below TEST.BBOX_AUG.SCALES=%r: the long side cannot be shorter than the short side" % (max_size, scales))
+    mc = _two_stage_config(c, bbox_aug=True)
+    return mc, BBoxAugConfig(H_FLIP=_bool(a.get("H_FLIP", False)), SCALES=scales, MAX_SIZE=max_size, SCALE_H_FLIP=_bool(a.get("SCALE_H_FLIP", False)),
+                             POOL_CAP=BBOX_AUG_MAX_POOL)
+
+
+def _two_stage_config(c, bbox_aug=False):
     body = c.MODEL.BACKBONE.CONV_BODY
     r = c.MODEL.RPN
     h = c.MODEL.ROI_HEADS
@@ -229,9 +274,10 @@ def _two_stage_config(c):
         raise ValueError("built bodies: R-50-FPN, R-101-FPN, R-50-C4 (got %r)" % body)
     gn_key = "MODEL.RESNETS.TRANS_FUNC=BottleneckWithGN" if norm.get("USE_GN") else None
     dcn = _dcn_config(c, body, gn_key, int(norm.get("NUM_GROUPS", 1)))
-    for key, on in (("MODEL.RPN_ONLY", c.MODEL.get("RPN_ONLY", False)), ("TEST.BBOX_AUG.ENABLED", c.TEST.get("BBOX_AUG", {}).get("ENABLED", False))):
-        if _bool(on):
-            raise ValueError("%s=True is not built (DESIGN.md 13: RPN-only models and test-time box augmentation are out of scope)" % key)
+    if _bool(c.MODEL.get("RPN_ONLY", False)):
+        raise ValueError("MODEL.RPN_ONLY=True is not built (DESIGN.md 13: RPN-only models are out of scope)")
+    if is_bbox_aug(c) and not bbox_aug:
+        raise ValueError("TEST.BBOX_AUG.ENABLED=True: a test-time box augmentation config (DESIGN.md 23) -- to_bbox_aug_config maps it")
     # [UPSTREAM-RECALL] DESIGN.md 13: the three keys that shape the RoI heads
     ncls = int(c.MODEL.ROI_BOX_HEAD.NUM_CLASSES)
     if not 2 <= ncls <= 257:
@@ -250,7 +296,7 @@ def _two_stage_config(c):
                               DETECTIONS_PER_IMG=int(h.DETECTIONS_PER_IMG), **heads)
     for k in ("PRE_NMS_TOP_N_TEST", "POST_NMS_TOP_N_TEST", "FPN_POST_NMS_TOP_N_TEST"):
         if int(c.MODEL.RPN[k]) > 1024:
-            raise ValueError("MODEL.RPN.%s=%d: the per-level FPN selection kernels hold at most 1024 boxes" % (k, c.MODEL.RPN[k]))
+            raise ValueError("MODEL.RPN.%s=%d: the per-level FPN selection kernels hold at most 1024 boxes" % (k, int(c.MODEL.RPN[k])))
     return MaskRCNNConfig(depth=101 if "101" in body else 50, CONV_BODY=body, MIN_SIZE_TEST=int(c.INPUT.MIN_SIZE_TEST),
                           MAX_SIZE_TEST=int(c.INPUT.MAX_SIZE_TEST),
                           SIZE_DIVISIBILITY=int(c.DATALOADER.SIZE_DIVISIBILITY), ANCHOR_SIZES=tuple(r.ANCHOR_SIZES),
@@ -324,6 +370,8 @@ def to_retinanet_config(c):
         raise ValueError("MODEL.RETINANET_ON=False: not a RetinaNet config (to_maskrcnn_config maps the two-stage models)")
     if _bool(m.MASK_ON):
         raise ValueError("MODEL.MASK_ON=True together with MODEL.RETINANET_ON: RetinaMask is not built, set MODEL.MASK_ON: False")
+    if is_bbox_aug(c):
+        raise ValueError("TEST.BBOX_AUG.ENABLED=True together with MODEL.RETINANET_ON: test-time box augmentation is built for the two-stage box head (DESIGN.md 23)")
     body = str(m.BACKBONE.CONV_BODY)
     if body not in RETINANET_BODIES:
         raise ValueError("MODEL.BACKBONE.CONV_BODY=%r: built RetinaNet bodies are %s" % (body, ", ".join(RETINANET_BODIES)))

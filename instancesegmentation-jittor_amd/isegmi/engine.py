@@ -140,8 +140,12 @@ class Engine:
             st[slot] = _ffi.DeviceBuffer((int(nbytes),), np.uint8)
         return st[slot]
 
-    def _preprocess_u8(self, d_u8_ptr, n, hin, win, d_out_ptr, hout, wout, hpad, wpad, mean, std, swap_rb):
+    def _preprocess_u8(self, d_u8_ptr, n, hin, win, d_out_ptr, hout, wout, hpad, wpad, mean, std, swap_rb, hflip=False):
+        """hflip: the image mirrored within its own width (isegmi_engine_preprocess_u8_flip; the mirrored views of TEST.BBOX_AUG)"""
         m = (C.c_float * 3)(*[float(v) for v in mean]); sd = (C.c_float * 3)(*[float(v) for v in std])
+        if hflip:
+            return _ffi.check(_ffi.lib().isegmi_engine_preprocess_u8_flip(self._h, C.c_void_p(d_u8_ptr), n, hin, win, C.c_void_p(d_out_ptr), hout, wout, hpad,
+                                                                          wpad, hpad * wpad * 3, m, sd, 1 if swap_rb else 0, 1))
         _ffi.check(_ffi.lib().isegmi_engine_preprocess_u8(self._h, C.c_void_p(d_u8_ptr), n, hin, win, C.c_void_p(d_out_ptr), hout, wout, hpad, wpad,
                                                           hpad * wpad * 3, m, sd, 1 if swap_rb else 0))
 

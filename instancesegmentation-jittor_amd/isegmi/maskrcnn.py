@@ -96,6 +96,49 @@ class MaskRCNNConfig:
         return max(self.DETECTIONS_PER_IMG, self.DETECTIONS_CAP)
 
 
+BBOX_AUG_MAX_POOL = 8192   # candidate slots per image the merge (isegmi_op_retina_postprocess) sorts in LDS
+
+
+@dataclass(frozen=True)
+class BBoxAugConfig:
+    """[UPSTREAM-RECALL] TEST.BBOX_AUG of maskrcnn-benchmark's defaults.py: multi-scale + horizontal-flip inference of a box-only model.
+    POOL_CAP is this project's: candidate slots per image over all views; a pool that overflows raises BBoxAugOverflow, nothing is truncated."""
+    H_FLIP: bool = False
+    SCALES: tuple = ()
+    MAX_SIZE: int = 4000
+    SCALE_H_FLIP: bool = False
+    POOL_CAP: int = BBOX_AUG_MAX_POOL
+
+
+class BBoxAugOverflow(RuntimeError):
+    """The views of one image passed more candidates than BBoxAugConfig.POOL_CAP holds."""
+
+
+def bbox_aug_views(image_hw, cfg, aug, min_size=None, max_size=None):
+    """[UPSTREAM-RECALL] engine/bbox_aug.py: the views of one image of ORIGINAL size image_hw = (h, w), in upstream's order, as (oh, ow, hflip): the
+    identity view Resize(MIN_SIZE_TEST, MAX_SIZE_TEST) (min_size / max_size override the two, as COCODemo's arguments do), its mirror image with H_FLIP,
+    then for every scale s Resize(s, MAX_SIZE) and, with SCALE_H_FLIP, its mirror image."""
+    from .transforms import get_size
+    h, w = int(image_hw[0]), int(image_hw[1])
+    first = get_size(w, h, int(min_size or cfg.MIN_SIZE_TEST), int(max_size or cfg.MAX_SIZE_TEST))
+    views = [first + (False,)] + ([first + (True,)] if aug.H_FLIP else [])
+    for s in aug.SCALES:
+        sz = get_size(w, h, int(s), int(aug.MAX_SIZE))
+        views += [sz + (False,)] + ([sz + (True,)] if aug.SCALE_H_FLIP else [])
+    return views
+
+
+def bbox_aug_engine_side(cfg, aug, min_size=None, max_size=None):
+    """The long side an engine needs for every view the plain rule's aspect allows: min(MAX_SIZE, ceil(largest short side * max / min)), not below the plain
+    rule's own long side, rounded up to SIZE_DIVISIBILITY."""
+    mn, mx = int(min_size or cfg.MIN_SIZE_TEST), int(max_size or cfg.MAX_SIZE_TEST)
+    d = cfg.SIZE_DIVISIBILITY
+    long_side = max(mx, mn)
+    if aug.SCALES:
+        long_side = max(long_side, min(int(aug.MAX_SIZE), -(-max(tuple(aug.SCALES) + (mn,)) * mx // mn)))
+    return -(-long_side // d) * d
+
+
 GROUPED_CONV_WIDTHS = (8, 16, 32, 64)   # channels per group the grouped kernel takes (csrc/conv_grouped.hip)
 
 
@@ -733,6 +776,85 @@ class MaskRCNN(Engine):
     def forward_device(self, n, slot=0):
         H, W = self._canvas
         _ffi.check(_ffi.lib().isegmi_maskrcnn_forward_canvas(self._h, self.input_buffer(slot).ptr, self._hw.ctypes.data_as(C.c_void_p), n, H, W))
+
+    # -- test-time box augmentation (TEST.BBOX_AUG) ------------------------------------------------------------
+    def aug_enqueue(self, images_bgr_u8, aug, slot=0, min_size=None, max_size=None):
+        """The whole augmented pass of one batch of ORIGINAL images, enqueued: host resizes (PIL, one per distinct size rule), ONE upload of every
+        scale's bytes (a scale serves both of its views: the mirror image is made by the front end), then per view the front end, the forward up to
+        the box predictor and the candidate stage, and the merge into det.*.  Afterwards the engine's current image sizes are view 0's, so
+        set_output_sizes / pack_box_records work as behind a plain forward.  Call aug_check() before using det.*.  -> batch size."""
+        from .transforms import maskrcnn_resize_u8
+        cfg = self.cfg
+        n = len(images_bgr_u8)
+        assert 0 < n <= self.max_batch
+        if any(np.asarray(im).dtype != np.uint8 or np.asarray(im).ndim != 3 or np.asarray(im).shape[2] != 3 for im in images_bgr_u8):
+            raise TypeError("detect_aug takes the original HxWx3 uint8 BGR images")
+        rules = [(int(min_size or cfg.MIN_SIZE_TEST), int(max_size or cfg.MAX_SIZE_TEST), bool(aug.H_FLIP))] + \
+                [(int(s), int(aug.MAX_SIZE), bool(aug.SCALE_H_FLIP)) for s in aug.SCALES]
+        groups, chunks, off, kept = [], [], 0, self._canvas
+        for mn, mx, flip in rules:
+            ims = [maskrcnn_resize_u8(np.ascontiguousarray(im), mn, mx) for im in images_bgr_u8]
+            hw = np.array([im.shape[:2] for im in ims], np.int32)
+            canvas = padded_canvas(hw, cfg.SIZE_DIVISIBILITY)
+            try:                        # a view that does not fit the engine raises here, naming the sizes, before anything is enqueued;
+                self._set_canvas(*canvas)
+            finally:                    # the engine's own canvas and image sizes stay what the last upload made them until the pass is really enqueued
+                self._canvas = kept
+            offs = []
+            for im in ims:
+                offs.append(off)
+                chunks.append(im.reshape(-1))
+                off += im.size
+            groups.append((hw, canvas, offs, flip))
+        flat = np.concatenate(chunks)
+        self.sync()   # the staging buffer may still be read by the front end of an earlier pass
+        st = self._u8_staging(slot, flat.nbytes)
+        _ffi.check(_ffi.lib().isegmi_h2d(st.ptr, flat.ctypes.data_as(C.c_void_p), flat.nbytes))
+        lib = _ffi.lib()
+        _ffi.check(lib.isegmi_maskrcnn_aug_begin(self._h, n, int(aug.POOL_CAP)))
+        hw0 = groups[0][0]
+        d_out = self.input_buffer(slot).ptr.value
+        for hw, (H, W), offs, flip in groups:
+            # BoxList.resize back to view 0: float(w0 / w_view), float(h0 / h_view), computed in double like _resize_ratios
+            ratios = np.ascontiguousarray(np.stack([hw0[:, 1].astype(np.float64) / hw[:, 1], hw0[:, 0].astype(np.float64) / hw[:, 0]], 1).astype(np.float32))
+            hwc = np.ascontiguousarray(hw, np.int32)
+            for hflip in ((False, True) if flip else (False,)):
+                for i in range(n):
+                    h, w = int(hw[i, 0]), int(hw[i, 1])
+                    self._preprocess_u8(st.ptr.value + offs[i], 1, h, w, d_out + i * H * W * 3 * 4, h, w, H, W, PIXEL_MEAN, (1.0, 1.0, 1.0), False, hflip)
+                _ffi.check(lib.isegmi_maskrcnn_aug_view(self._h, C.c_void_p(d_out), hwc.ctypes.data_as(C.c_void_p), n, H, W, 1 if hflip else 0,
+                                                        ratios.ctypes.data_as(C.c_void_p)))
+        _ffi.check(lib.isegmi_maskrcnn_aug_merge(self._h))
+        self._hw = np.ascontiguousarray(hw0, np.int32)
+        self._canvas = groups[0][1]
+        self._aug_cap = int(aug.POOL_CAP)
+        return n
+
+    def aug_check(self):
+        """Synchronises and raises BBoxAugOverflow if any image's views passed more candidates than POOL_CAP (det.* must then not be used)."""
+        self.sync()
+        n = self._hw.shape[0]
+        total = self.fetch("aug.pool_total", n)
+        if (total > self._aug_cap).any():
+            i = int(np.argmax(total))
+            raise BBoxAugOverflow("TEST.BBOX_AUG: image %d of the batch has %d candidates over its views, POOL_CAP holds %d (at most %d): raise "
+                                  "MODEL.ROI_HEADS.SCORE_THRESH or use fewer views" % (i, int(total[i]), self._aug_cap, BBOX_AUG_MAX_POOL))
+        return total
+
+    def detect_aug(self, images_bgr_u8, aug, min_size=None, max_size=None):
+        """[UPSTREAM-RECALL] im_detect_bbox_aug: ORIGINAL HxWx3 uint8 BGR images in, one BoxList per image out -- boxes, scores, labels in view-0
+        coordinates (the identity view's resized image), filter_results run once over the candidates of every view."""
+        n = self.aug_enqueue(images_bgr_u8, aug, 0, min_size, max_size)
+        self.aug_check()
+        cnt = self.fetch("det.count", n)
+        box, score, label = (self.fetch(k, n) for k in ("det.box", "det.score", "det.label"))
+        out = []
+        for i in range(n):
+            c = int(cnt[i])
+            bl = BoxList(box[i, :c], (int(self._hw[i, 1]), int(self._hw[i, 0])))
+            bl.add_field("scores", score[i, :c]); bl.add_field("labels", label[i, :c].astype(np.int64))
+            out.append(bl)
+        return out
 
     def paste_device(self, out_h, out_w, orig_sizes_wh=None):
         """Masker paste into (out_h, out_w); orig_sizes_wh [N,2] are the sizes boxes are resized to (default: no resize)."""

@@ -19,15 +19,20 @@ class COCODemo:
     CATEGORIES = ("__background",) + COCO_CLASSES
 
     def __init__(self, cfg=None, min_image_size=800, confidence_threshold=0.5, state_dict=None, max_image_size=1333, device=0, max_batch=2,
-                 fp16=False, render="host"):
+                 fp16=False, render="host", bbox_aug=None, aug_canvas=None):
+        """bbox_aug: a BBoxAugConfig next to a MaskRCNNConfig (a yaml-keyed node carries its own TEST.BBOX_AUG); aug_canvas = (H, W): the engine's largest
+        canvas under augmentation instead of the one derived from the scales."""
         from .retinanet import RetinaNetConfig
         if render not in ("host", "device"):
             raise ValueError("render: 'host' (numpy overlay of the downloaded masks) or 'device' (isegmi_engine_paint; DESIGN.md 22)")
         self.render = render
         if cfg is not None and not isinstance(cfg, (MaskRCNNConfig, RetinaNetConfig)):   # the yacs-shaped node of isegmi.config (README.md:313-324)
-            from .config import is_keypoint_rcnn, is_retinanet, to_keypointrcnn_config, to_maskrcnn_config, to_retinanet_config
+            from .config import is_bbox_aug, is_keypoint_rcnn, is_retinanet, to_bbox_aug_config, to_keypointrcnn_config, to_maskrcnn_config, to_retinanet_config
             retina = is_retinanet(cfg)
             to_two_stage = to_keypointrcnn_config if is_keypoint_rcnn(cfg) else to_maskrcnn_config   # MODEL.KEYPOINT_ON (DESIGN.md 14)
+            if is_bbox_aug(cfg) and not retina and not is_keypoint_rcnn(cfg):   # TEST.BBOX_AUG.ENABLED (DESIGN.md 23); the other two mappings refuse the key by name
+                bbox_aug = to_bbox_aug_config(cfg)[1]
+                to_two_stage = lambda c: to_bbox_aug_config(c)[0]
             if state_dict is None and getattr(cfg.MODEL, "WEIGHT", ""):
                 w = cfg.MODEL.WEIGHT
                 from .weights import random_maskrcnn_state_dict, retinanet_state_dict
@@ -41,6 +46,9 @@ class COCODemo:
         self.cfg = cfg or MaskRCNNConfig()
         self.is_retinanet = isinstance(self.cfg, RetinaNetConfig)   # MODEL.RETINANET_ON: boxes, scores and labels; no masks
         self.box_only = not self.is_retinanet and not self.cfg.MASK_ON   # MODEL.MASK_ON False: Faster R-CNN, the same
+        self.bbox_aug, self.aug_canvas = bbox_aug, aug_canvas   # TEST.BBOX_AUG: every prediction is MaskRCNN.detect_aug's
+        if bbox_aug is not None and (self.is_retinanet or not self.box_only or self.cfg.KEYPOINT_ON or self.cfg.is_c4 or fp16):
+            raise ValueError("TEST.BBOX_AUG.ENABLED is built for the box-only fp32 FPN models (MODEL.MASK_ON False, MODEL.KEYPOINT_ON False, no C4 body, no RetinaNet)")
         if not self.is_retinanet and self.cfg.NUM_CLASSES != 81:      # labels of another class count have no COCO names
             self.CATEGORIES = ("__background",) + tuple("class %d" % i for i in range(1, self.cfg.NUM_CLASSES))
         if state_dict is None:
@@ -62,11 +70,17 @@ class COCODemo:
         if self._model is None:
             d = self.cfg.SIZE_DIVISIBILITY
             m = -(-max(self.max_image_size, self.min_image_size) // d) * d
+            mh = mw = m
+            if self.bbox_aug is not None:   # the largest view the plain rule's aspect allows, or the caller's canvas
+                from .maskrcnn import bbox_aug_engine_side
+                mh = mw = bbox_aug_engine_side(self.cfg, self.bbox_aug, self.min_image_size, self.max_image_size)
+                if self.aug_canvas is not None:
+                    mh, mw = (-(-int(v) // d) * d for v in self.aug_canvas)
             if self.is_retinanet:
                 from .retinanet import RetinaNet
                 self._model = RetinaNet(self.state_dict, m, m, cfg=self.cfg, max_batch=want, device=self.device, fp16=self.fp16)
             else:
-                self._model = MaskRCNN(self.state_dict, m, m, cfg=self.cfg, max_batch=want, device=self.device, fp16=self.fp16)
+                self._model = MaskRCNN(self.state_dict, mh, mw, cfg=self.cfg, max_batch=want, device=self.device, fp16=self.fp16)
             self.memory = self._model.reserve()  # (weight bytes, activation / workspace bytes): the predictor's peak device memory
         return self._model
 
@@ -74,8 +88,11 @@ class COCODemo:
         """-> BoxList in ORIGINAL image coordinates with scores, labels and mask [n,1,H,W] uint8 (Masker output); RetinaNet and Faster R-CNN
         (MODEL.MASK_ON False): no mask field.  Keypoint R-CNN (MODEL.KEYPOINT_ON): keypoints [n,17,3] in original-image coordinates and keypoint_logits [n,17]."""
         h, w = original_image.shape[:2]
-        resized = maskrcnn_resize_u8(original_image, self.min_image_size, self.max_image_size)
         model = self.engine()
+        if self.bbox_aug is not None:   # TEST.BBOX_AUG: the views are resized from the original inside detect_aug
+            (pred,) = model.detect_aug([original_image], self.bbox_aug, self.min_image_size, self.max_image_size)
+            return pred.resize((w, h))
+        resized = maskrcnn_resize_u8(original_image, self.min_image_size, self.max_image_size)
         (pred,) = model([resized])  # device front end: the bytes cross PCIe, mean subtraction + padding (to_image_list) run on the GPU
         if self.is_retinanet or self.box_only:
             return pred.resize((w, h))
@@ -107,9 +124,11 @@ class COCODemo:
         the class names are written on the host, as overlay does.  Bit-identical to the host overlay."""
         from .render import demo_entries, keypoint_dots
         h, w = image.shape[:2]
-        resized = maskrcnn_resize_u8(image, self.min_image_size, self.max_image_size)
         model = self.engine()
-        (pred,) = model([resized])
+        if self.bbox_aug is not None:
+            (pred,) = model.detect_aug([image], self.bbox_aug, self.min_image_size, self.max_image_size)
+        else:
+            (pred,) = model([maskrcnn_resize_u8(image, self.min_image_size, self.max_image_size)])
         with_masks = not (self.is_retinanet or self.box_only)
         if with_masks:
             model.paste_device(h, w, [(w, h)])   # on the results stream; the painter is ordered behind it
@@ -197,7 +216,11 @@ def inference(predictor, images, image_ids=None, batch_size=None, group="canvas"
     category_ids: the data set's json category id of labels 1, 2, ... (two-stage models; default: the COCO ids for 81 classes, the label itself for
             any other class count).
     A Faster R-CNN predictor (MODEL.MASK_ON False) takes the same loop with the box-only record block: no paste, no RLE, bbox-only results (xywh with
-    the legacy +1, no `segmentation` key)."""
+    the legacy +1, no `segmentation` key).  With TEST.BBOX_AUG (DESIGN.md 23) every step is MaskRCNN.aug_enqueue on the ORIGINAL images -- one rank;
+    "canvas" then groups by the canvases of ALL views, so that an image's result still equals its single-image result.  The augmented loop is NOT
+    pipelined across steps: every step ends in aug_check (a device synchronisation and the fetch of the pool counters, so that an overflow raises before
+    its records are packed); what still overlaps is the worker threads' loading of the next batch, and inside a step the views follow each other as
+    consecutive forwards do."""
     import time
     if getattr(predictor, "is_retinanet", False):
         return _inference_boxes(predictor, images, image_ids, batch_size, group, rank, world, sizes, stats, workers)
@@ -218,8 +241,15 @@ def inference(predictor, images, image_ids=None, batch_size=None, group="canvas"
     cfg = predictor.cfg
     categories = label_categories(getattr(cfg, "NUM_CLASSES", 81), category_ids)
     box_only = bool(getattr(model, "box_only", False))
+    aug = getattr(predictor, "bbox_aug", None)
+    if aug is not None and world > 1:
+        raise ValueError("inference(): world=%d with TEST.BBOX_AUG.ENABLED -- test-time box augmentation runs on one rank; multi-rank runs are not built for it" % world)
     rs = [get_size(w, h, predictor.min_image_size, predictor.max_image_size) for h, w in sizes]   # resized (h, w) per image
-    if group == "canvas":
+    if group == "canvas" and aug is not None:
+        from .maskrcnn import bbox_aug_views
+        keys = [tuple(padded_canvas([v[:2]], cfg.SIZE_DIVISIBILITY) for v in bbox_aug_views(hw, cfg, aug, predictor.min_image_size, predictor.max_image_size))
+                for hw in sizes]
+    elif group == "canvas":
         keys = [padded_canvas([r], cfg.SIZE_DIVISIBILITY) for r in rs]
     elif group == "aspect":
         keys = [int(h >= w) for h, w in sizes]
@@ -227,9 +257,14 @@ def inference(predictor, images, image_ids=None, batch_size=None, group="canvas"
         raise ValueError("group: 'canvas' or 'aspect'")
     batches = schedule_batches(keys, bs)
     K = record_capacity(model)
-    pin = [_ffi.PinnedBuffer((bs * model.H * model.W * 3,), np.uint8) for _ in range(2)]
+    if aug is not None:   # no pinned input buffers (aug_enqueue uploads the views' bytes itself); the staging holds EVERY size rule's images of a batch
+        from .maskrcnn import bbox_aug_views
+        area = [sum(v[0] * v[1] * 3 for v in bbox_aug_views(hw, cfg, aug, predictor.min_image_size, predictor.max_image_size) if not v[2]) for hw in sizes]
+        pin, stage_bytes = [], max([sum(area[i] for i in b) for b in batches] + [1])
+    else:
+        pin, stage_bytes = [_ffi.PinnedBuffer((bs * model.H * model.W * 3,), np.uint8) for _ in range(2)], bs * model.H * model.W * 3
     for slot in (0, 1):
-        model._u8_staging(slot, bs * model.H * model.W * 3)   # device staging at its final size: no sync + re-allocation on a larger batch
+        model._u8_staging(slot, stage_bytes)   # device staging at its final size: no sync + re-allocation on a larger batch
     per_image = [None] * n_img
 
     def consume(step, recs):
@@ -248,6 +283,8 @@ def inference(predictor, images, image_ids=None, batch_size=None, group="canvas"
                 per_image[i] = by_id.get(ids[i], [])
 
     def load(i):   # host: decode + PIL resize (outside the hot path)
+        if aug is not None:   # the views are resized from the original inside aug_enqueue
+            return get(i)
         return maskrcnn_resize_u8(get(i), predictor.min_image_size, predictor.max_image_size)
     pool = None
     if workers and workers > 0:
@@ -268,6 +305,11 @@ def inference(predictor, images, image_ids=None, batch_size=None, group="canvas"
         request(j + world)                   # the next batch of this rank resizes on the worker threads meanwhile
         futs = prefetch.pop(j, None)         # (a step that is redone after an RLE overflow loads its images again, inline)
         resized = [f.result() for f in futs] if futs else [load(i) for i in b]
+        if aug is not None:
+            model.aug_enqueue(resized, aug, slot, predictor.min_image_size, predictor.max_image_size)
+            model.aug_check()                # BBoxAugOverflow: nothing is truncated silently
+            model.set_output_sizes([(w, h) for h, w in (sizes[i] for i in b)])
+            return True
         off, hw = 0, []
         for im in resized:                   # into pinned memory, back to back
             pin[slot].array[off:off + im.size] = im.reshape(-1)
