@@ -177,6 +177,33 @@ int isegmi_op_preprocess_u8(const uint8_t* d_in, int N, int Hin, int Win, float*
 int isegmi_op_preprocess_u8_flip(const uint8_t* d_in, int N, int Hin, int Win, float* d_out, int Hout, int Wout, int Hpad, int Wpad,
                                  int64_t out_img_stride, const float* mean3, const float* std3, int swap_rb, int hflip, void* stream);
 
+/* ---- PIL-exact 8-bit bilinear resampling (csrc/resample.hip) ----
+ * The resize of the R-CNN front ends and of the YOLOv3 letterbox on the device, bit-identical to PIL's Image.resize(..., BILINEAR) on 8-bit images
+ * (Resample.c: integer arithmetic over 22-bit fixed-point coefficient tables; horizontal pass first, rounded to bytes, then the vertical pass).
+ *
+ * isegmi_resample_coeffs: the tables of one axis I -> O, host only (no GPU needed), computed in double without contraction exactly as PIL does:
+ * bounds [O][2] = (xmin, n), kk [O][ksize] (unused slots 0), *ksize = 2 ceil(max(I / O, 1)) + 1.  bounds = kk = NULL asks for *ksize alone.
+ * Refuses I, O < 1 and scales whose ksize exceeds ISEGMI_RESAMPLE_MAX_KSIZE (downscales beyond 512; the ten contract shapes go up to 300). */
+#define ISEGMI_RESAMPLE_MAX_KSIZE 1025
+int isegmi_resample_coeffs(int I, int O, int32_t* bounds, int32_t* kk, int* ksize);
+/* One image of a batch is one row of ISEGMI_RESAMPLE_ENTRY_WORDS int32 words in the image table:
+ *   0, 1  byte offset of its [Hin][Win][3] uint8 pixels in d_src (low, high word of an int64; any alignment)
+ *   2..5  Hin, Win, Hout, Wout            6, 7  dst_y, dst_x: where the resized image sits on the canvas (fp32 output only)
+ *   8, 9  word offsets in d_coeffs of the horizontal (Win -> Wout) and vertical (Hin -> Hout) tables, each laid out bounds [O][2] then kk [O][ksize]
+ *   10, 11 their ksize                    12  hflip: output column x shows column Wout - 1 - x of the RESIZED image
+ *   13    the canvas plane it is written to (fp32 output)      14, 15  byte offset of its tight [Hout][Wout][3] output in d_out_u8 (int64) */
+#define ISEGMI_RESAMPLE_ENTRY_WORDS 16
+/* One launch for the whole batch.  d_table is the DEVICE table; h_table the same rows on the host, which this call validates against src_bytes,
+ * coeff_words and the output before it launches (the kernel additionally clamps every table bound to its image).  Exactly one output:
+ *   d_out != NULL: planes fp32 NHWC3 canvases of Hpad x Wpad, out_img_stride floats apart: out[.., swap_rb ? 2 - c : c] = ((float)p - mean3[c]) / std3[c]
+ *                  inside the image, `fill` everywhere else on the canvas of every plane a row names (each canvas element written exactly once);
+ *   d_out_u8 != NULL: the resized bytes, tight, at each row's output offset (Hpad, Wpad, mean3, std3, swap_rb, fill unused). */
+int isegmi_op_resample_u8(const uint8_t* d_src, int64_t src_bytes, const int32_t* d_table, const int32_t* h_table, int N, const int32_t* d_coeffs,
+                          int64_t coeff_words, float* d_out, int planes, int Hpad, int Wpad, int64_t out_img_stride, const float* mean3,
+                          const float* std3, int swap_rb, float fill, uint8_t* d_out_u8, int64_t out_u8_bytes, void* stream);
+/* the kernel's output tile (rows, columns) and the source rows one LDS chunk holds: the sizes its tests straddle */
+int isegmi_op_resample_tile(int* tile_h, int* tile_w, int* chunk_rows);
+
 /* max_pool2d(k,s,p), -inf padding (M2/Y2 stem; k=1,s=2 = LastLevelMaxPool M3) */
 int isegmi_op_maxpool(const float* d_in, int N, int H, int W, int C, int k, int s, int p,
                       float* d_out, void* stream);
@@ -795,6 +822,12 @@ int isegmi_engine_preprocess_u8(isegmi_engine* e, const uint8_t* d_u8, int N, in
 /* isegmi_op_preprocess_u8_flip the same way */
 int isegmi_engine_preprocess_u8_flip(isegmi_engine* e, const uint8_t* d_u8, int N, int Hin, int Win, float* d_out, int Hout, int Wout,
                                      int Hpad, int Wpad, int64_t out_img_stride, const float* mean3, const float* std3, int swap_rb, int hflip);
+/* isegmi_op_resample_u8 (fp32 output) scheduled like isegmi_engine_preprocess_u8.  The image table, the coefficient tables and the original bytes
+ * sit in ONE device blob (one upload): the table at byte table_off, the coefficients at coeff_off (both multiples of 4), the pixels from src_off.
+ * When the blob is the destination of a pending upload_async the launch goes to the copy stream behind it, otherwise to the main stream. */
+int isegmi_engine_resample_u8(isegmi_engine* e, const uint8_t* d_blob, int64_t blob_bytes, int64_t table_off, const int32_t* h_table, int N,
+                              int64_t coeff_off, int64_t coeff_words, int64_t src_off, float* d_out, int planes, int Hpad, int Wpad,
+                              int64_t out_img_stride, const float* mean3, const float* std3, int swap_rb, float fill);
 /* per-step completion marks on the results stream; step_times returns the intervals between consecutive marks (ms) */
 int isegmi_engine_mark_step(isegmi_engine* e);
 int isegmi_engine_step_times(isegmi_engine* e, float* ms, int cap, int* count);

@@ -1065,6 +1065,44 @@ extern "C" int isegmi_engine_preprocess_u8_flip(isegmi_engine* h, const uint8_t*
     return engine_preprocess_u8(h, d_u8, N, Hin, Win, d_out, Hout, Wout, Hpad, Wpad, out_img_stride, mean3, std3, swap_rb, hflip);
 }
 
+// PIL-exact resize + normalise + pad from the ORIGINAL bytes (csrc/resample.hip), scheduled exactly as engine_preprocess_u8: the image
+// table, the coefficient tables and the pixels are one blob, so one upload entry decides the stream, and nothing here synchronises.
+extern "C" int isegmi_engine_resample_u8(isegmi_engine* h, const uint8_t* d_blob, int64_t blob_bytes, int64_t table_off, const int32_t* h_table, int N,
+                                         int64_t coeff_off, int64_t coeff_words, int64_t src_off, float* d_out, int planes, int Hpad, int Wpad,
+                                         int64_t out_img_stride, const float* mean3, const float* std3, int swap_rb, float fill) {
+    ARG_CHECK(h && d_blob && h_table && d_out && N > 0 && planes > 0, "resample args");
+    ARG_CHECK(table_off >= 0 && table_off % 4 == 0 && coeff_off >= 0 && coeff_off % 4 == 0 && coeff_words >= 0 && src_off >= 0 &&
+              table_off + (int64_t)N * ISEGMI_RESAMPLE_ENTRY_WORDS * 4 <= blob_bytes && coeff_off + coeff_words * 4 <= blob_bytes && src_off <= blob_bytes,
+              "resample blob layout (table, coefficients and pixels inside the blob; the two tables on 4-byte offsets)");
+    ARG_CHECK(((uintptr_t)d_blob & 3u) == 0, "resample blob alignment");
+    Engine& e = h->e;
+    const int64_t dst_bytes = (int64_t)planes * out_img_stride * 4;
+    bool on_copy = false;  // (the rule of engine_preprocess_u8)
+    for (auto& u : e.uploads) {
+        const char* p = (const char*)d_blob;
+        if (!(u.waited & 1u) && p < u.dst + u.bytes && u.dst < p + blob_bytes) on_copy = true;
+    }
+    const int32_t* d_table = (const int32_t*)(d_blob + table_off);
+    const int32_t* d_coeffs = (const int32_t*)(d_blob + coeff_off);
+    const char* what = "front end (original uint8 -> PIL-exact resize / normalise / pad -> fp32 input)";
+    if (on_copy) {
+        {
+            OpScope op(e, e.copy, what, (double)blob_bytes + (double)dst_bytes);
+            TRY(resample_u8_launch(d_blob + src_off, blob_bytes - src_off, d_table, h_table, N, d_coeffs, coeff_words, d_out, planes, Hpad, Wpad,
+                                   out_img_stride, mean3, std3, swap_rb, fill, nullptr, 0, e.copy));
+        }
+        return eng_note_upload(e, d_out, dst_bytes);
+    }
+    TRY(eng_wait_upload(e, d_blob, blob_bytes, e.stream));
+    {
+        OpScope op(e, e.stream, what, (double)blob_bytes + (double)dst_bytes);
+        TRY(resample_u8_launch(d_blob + src_off, blob_bytes - src_off, d_table, h_table, N, d_coeffs, coeff_words, d_out, planes, Hpad, Wpad,
+                               out_img_stride, mean3, std3, swap_rb, fill, nullptr, 0, e.stream));
+    }
+    if (e.lane_state == 1) return eng_note_upload(e, d_out, dst_bytes, e.stream, 1u);
+    return ISEGMI_OK;
+}
+
 // Records a completion mark for the step just enqueued on the stream its results finish on; isegmi_engine_step_times returns
 // the intervals between consecutive marks (ms) -- per-step latency samples of a pipelined run -- and clears them.
 extern "C" int isegmi_engine_mark_step(isegmi_engine* h) {

@@ -384,6 +384,10 @@ int deform_conv2d_launch(const float* x, int N, int H, int W, int C, const float
 int pad_c3_c4_launch(const float* in, int64_t npix, float* out, hipStream_t st);
 int preprocess_u8_launch(const uint8_t* in, int N, int Hin, int Win, float* out, int Hout, int Wout, int Hpad, int Wpad, int64_t out_img_stride,
                          const float* mean3, const float* std3, int swap_rb, hipStream_t st, int hflip = 0);
+// csrc/resample.hip: PIL-exact 8-bit bilinear resize of a batch in one launch (the arguments of isegmi_op_resample_u8)
+int resample_u8_launch(const uint8_t* d_src, int64_t src_bytes, const int32_t* d_table, const int32_t* h_table, int N, const int32_t* d_coeffs,
+                       int64_t coeff_words, float* d_out, int planes, int Hpad, int Wpad, int64_t out_img_stride, const float* mean3, const float* std3,
+                       int swap_rb, float fill, uint8_t* d_out_u8, int64_t out_u8_bytes, hipStream_t st);
 int pad_c3_c32_launch(const float* in, int64_t npix, float* out, hipStream_t st);
 int yolact_detect_launch(const isegmi_yolact_detect_args* a, hipStream_t st);
 // Detect in two halves: everything up to the final per-image top-k, then the gather.  coeff_sel (optional, [N][max_det][mask_dim] pre-tanh): the gather

@@ -131,6 +131,9 @@ SIGNATURES = {
     "isegmi_get_f16_mfma_shape": (I, [V]),
     "isegmi_op_preprocess_u8": (I, [V, I, I, I, V, I, I, I, I, L, V, V, I, V]),
     "isegmi_op_preprocess_u8_flip": (I, [V, I, I, I, V, I, I, I, I, L, V, V, I, I, V]),
+    "isegmi_resample_coeffs": (I, [I, I, V, V, V]),
+    "isegmi_op_resample_u8": (I, [V, L, V, V, I, V, L, V, I, I, I, L, V, V, I, F, V, L, V]),
+    "isegmi_op_resample_tile": (I, [V, V, V]),
     "isegmi_op_maxpool": (I, [V, I, I, I, I, I, I, I, V, V]),
     "isegmi_op_resize_bilinear": (I, [V, I, I, I, I, I, I, V, I, V, V]),
     "isegmi_op_keypoint_heatmap": (I, [V, L, I, I, I, V, V]),
@@ -224,6 +227,7 @@ SIGNATURES = {
     "isegmi_engine_upload_async": (I, [V, V, V, L]),
     "isegmi_engine_preprocess_u8": (I, [V, V, I, I, I, V, I, I, I, I, L, V, V, I]),
     "isegmi_engine_preprocess_u8_flip": (I, [V, V, I, I, I, V, I, I, I, I, L, V, V, I, I]),
+    "isegmi_engine_resample_u8": (I, [V, V, L, L, V, I, L, L, L, V, I, I, I, L, V, V, I, F]),
     "isegmi_engine_mark_step": (I, [V]),
     "isegmi_engine_step_times": (I, [V, V, I, V]),
     "isegmi_engine_wait_mark": (I, [V, I]),

@@ -361,6 +361,56 @@ def preprocess_u8_flip(images_u8, Hout, Wout, Hpad, Wpad, mean3, std3, swap_rb, 
     return do.numpy()
 
 
+def resample_tile():
+    """(tile rows, tile columns, source rows per LDS chunk) of isegmi_op_resample_u8's kernel."""
+    th, tw, rc = C.c_int(), C.c_int(), C.c_int()
+    check(lib().isegmi_op_resample_tile(C.byref(th), C.byref(tw), C.byref(rc)))
+    return th.value, tw.value, rc.value
+
+
+def resample_u8(images, entries, canvas=None, planes=None, mean3=(0, 0, 0), std3=(1, 1, 1), swap_rb=False, fill=0.0):
+    """isegmi_op_resample_u8, one launch: images = HxWx3 uint8 arrays, packed back to back in one blob behind their tables
+    (transforms.ResamplePlan); entries = (image, Hout, Wout, dst_y, dst_x, hflip, plane) per resized view.  canvas = (Hpad, Wpad): -> fp32
+    [planes, Hpad, Wpad, 3], every canvas element of every plane an entry names written (normalised pixel or `fill`); canvas None: -> the
+    resized uint8 images, tight.  Both outputs are poisoned (0xFF bytes: NaN / 255) before the launch."""
+    from .transforms import ResamplePlan
+    ims = [np.ascontiguousarray(im) for im in images]
+    plan = ResamplePlan([im.shape[:2] for im in ims], [entries])
+    blob = np.empty(plan.nbytes, np.uint8)
+    plan.write(blob, ims)
+    table = plan.header()[1][0].copy()
+    out_off, off = [], 0
+    for r in range(table.shape[0]):   # the byte outputs back to back (words 14, 15; all far below 2^31 here)
+        out_off.append(off)
+        table[r, 14] = off
+        off += int(table[r, 4]) * int(table[r, 5]) * 3
+    blob[:table.nbytes] = table.reshape(-1).view(np.uint8)
+    db = DeviceBuffer.from_numpy(blob)
+    base = db.ptr.value
+    m = (C.c_float * 3)(*[float(v) for v in mean3]); sd = (C.c_float * 3)(*[float(v) for v in std3])
+    try:
+        if canvas is not None:
+            Hp, Wp = canvas
+            P = int(planes if planes is not None else 1 + max(int(e[6]) for e in entries))
+            do = DeviceBuffer((P, Hp, Wp, 3)).poison()
+            args = (do.ptr, P, Hp, Wp, Hp * Wp * 3, m, sd, int(bool(swap_rb)), float(fill), None, 0)
+        else:
+            do = DeviceBuffer((max(off, 1),), np.uint8).poison()
+            args = (None, 0, 0, 0, 0, None, None, 0, 0.0, do.ptr, off)
+        try:
+            check(lib().isegmi_op_resample_u8(C.c_void_p(base + plan.src_off), plan.pixel_bytes, C.c_void_p(base), table.ctypes.data_as(C.c_void_p), table.shape[0],
+                                              C.c_void_p(base + plan.coeff_off), plan.coeff_words, *args, None))
+            check(lib().isegmi_sync())
+            out = do.numpy()
+        finally:
+            do.free()
+    finally:
+        db.free()
+    if canvas is not None:
+        return out
+    return [out[o:o + int(t[4]) * int(t[5]) * 3].reshape(int(t[4]), int(t[5]), 3).copy() for o, t in zip(out_off, table)]
+
+
 def deform_im2col(x, om, R=3, S=3, stride=1, pad=1, dil=1):
     """x [N,H,W,C], om [N,Ho,Wo,3*R*S] raw conv_offset_mask output -> DCNv2 columns [N,Ho,Wo,R*S*C]."""
     x = np.ascontiguousarray(x, np.float32); om = np.ascontiguousarray(om, np.float32)

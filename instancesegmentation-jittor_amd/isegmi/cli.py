@@ -98,6 +98,7 @@ def cmd_eval(a):
     """Yolact eval.py: evalimage / evalimages (+ Detections.dump when --output_coco_json is given)."""
     from .coco import dump, rle_decode
     from .yolact import Yolact, YolactConfig, evaluate
+    refuse_device_resize(a, "Yolact", "isegmi_op_preprocess_u8 resizes to the square canvas on the device")
     # upstream eval.py --config: yolact_resnet50_config (default here), yolact_base_config (R101), yolact_im700_config, and the
     # YOLACT++ pair yolact_plus_resnet50_config / yolact_plus_base_config (DCNv2 backbones, 9 anchors, mask re-scoring)
     cfg = {"yolact_resnet50_config": YolactConfig(), "yolact_base_config": YolactConfig.base(), "yolact_im700_config": YolactConfig.im700(),
@@ -150,6 +151,12 @@ def cmd_eval(a):
     return results
 
 
+def refuse_device_resize(a, model, why):
+    """--resize device on a command whose model keeps its own front end: refused by name."""
+    if getattr(a, "resize", "host") == "device":
+        raise SystemExit("--resize device: %s keeps its own front end (%s); the PIL-exact device resize is built for the R-CNN family, RetinaNet and YOLOv3" % (model, why))
+
+
 def cmd_test_net(a):
     """tools/test_net.py: build the model from the yaml, run inference() over the images, write COCO-format json."""
     from .config import cfg, is_bbox_aug, is_keypoint_rcnn, is_retinanet, to_bbox_aug_config, to_keypointrcnn_config, to_maskrcnn_config, to_retinanet_config
@@ -176,7 +183,7 @@ def cmd_test_net(a):
         sd = _weights(c.MODEL.WEIGHT, "maskrcnn", mc.depth, gn=mc.USE_GN)
     box_only = retina or not mc.MASK_ON   # RetinaNet and Faster R-CNN (MODEL.MASK_ON False): bbox results only
     demo = COCODemo(mc, min_image_size=mc.MIN_SIZE_TEST, confidence_threshold=0.0, state_dict=sd,
-                    max_image_size=mc.MAX_SIZE_TEST, device=local, max_batch=a.batch_size, bbox_aug=bbox_aug)
+                    max_image_size=mc.MAX_SIZE_TEST, device=local, max_batch=a.batch_size, bbox_aug=bbox_aug, resize=getattr(a, "resize", "host"))
     stats = {}
     results = inference(demo, lambda i: _load_image_bgr(files[i]), batch_size=a.batch_size, group=a.group, rank=rank, world=world,
                         sizes=_image_sizes(files), stats=stats) if files else []
@@ -200,6 +207,7 @@ def cmd_test_net(a):
 def cmd_pose2seg_test(a):
     """Pose2Seg test.py (README section 2.2): images + COCO person keypoints -> COCO segmentation json (category 1, score 1.0)."""
     from .pose2seg import Pose2Seg, Pose2SegConfig, read_person_keypoints, test
+    refuse_device_resize(a, "Pose2Seg", "its affine letterbox, isegmi_op_pose2seg_letterbox, already runs on the device")
     from .weights import pose2seg_state_dict
     if a.weights in ("", "random", None):
         sd = pose2seg_state_dict(1234)
@@ -310,7 +318,7 @@ def cmd_yolo_detect(a):
         raise SystemExit("%s: --weights takes random, an .npz in this engine's names or a darknet .weights file" % a.weights)
     files = sorted(os.path.join(a.images, f) for f in os.listdir(a.images))
     cats = label_categories(ycfg.classes + 1)
-    det = YoloDetector(sd, ycfg, max_batch=a.batch_size, device=local)
+    det = YoloDetector(sd, ycfg, max_batch=a.batch_size, device=local, resize=getattr(a, "resize", "host"))
     results = []
     try:
         for i0 in range(0, len(files), a.batch_size):
@@ -335,6 +343,7 @@ def vit_config(a):
 def cmd_vit_classify(a):
     """ViT classification over a directory of images -> json: one entry per image with its top-k labels and probabilities."""
     from .vit import ViTClassifier
+    refuse_device_resize(a, "ViT", "isegmi_op_preprocess_u8 resizes to the square canvas on the device")
     from .weights import vit_random_state_dict
     _, world, local = _rank_world()
     if world > 1:
@@ -393,6 +402,7 @@ def build_parser():
     e.add_argument("--batch_size", type=int, default=8, help="images per step and rank")
     e.add_argument("--render", default=argparse.SUPPRESS, choices=["host", "device"],
                    help="(default host) the --image / --images outputs: host draws them from the decoded records, device paints them from the mask planes (isegmi.yolact.render_images)")
+    e.add_argument("--resize", default=argparse.SUPPRESS, choices=["host", "device"], help="refused for Yolact: its front end already resizes on the device")
     e.add_argument("--fast_nms", type=str2bool, default=argparse.SUPPRESS, help="(default True) False: traditional per-class NMS (upstream's cython_nms) instead of fast NMS")
     e.add_argument("--cross_class_nms", type=str2bool, default=argparse.SUPPRESS, help="(default False) True: one fast-NMS pass over all classes together")
     e.add_argument("--nms_trad_cap", type=int, default=argparse.SUPPRESS, help="(default 1024) traditional NMS: candidates visited per image and class (a multiple of 64 in [64, 2048])")
@@ -407,6 +417,8 @@ def build_parser():
     t.add_argument("--vis-dir", dest="vis_dir", default=argparse.SUPPRESS, help="also write COCODemo.run_on_opencv_image of every image (masks, boxes, names) to this directory")
     t.add_argument("--vis-threshold", dest="vis_threshold", type=float, default=argparse.SUPPRESS, help="(default 0.7) with --vis-dir: draw detections with score > this")
     t.add_argument("--render", default=argparse.SUPPRESS, choices=["host", "device"], help="(default host) with --vis-dir: where the masks, boxes and dots are drawn (DESIGN.md 22)")
+    t.add_argument("--resize", default=argparse.SUPPRESS, choices=["host", "device"],
+                   help="(default host) where the test-time resize runs: host = PIL on worker threads, device = the original bytes go up and one kernel resizes them, bit-identical (DESIGN.md 24)")
     t.add_argument("opts", nargs=argparse.REMAINDER, default=[])
     p = sub.add_parser("pose2seg_test", help="Pose2Seg test.py-style evaluation: images + COCO person keypoints -> COCO segmentation json")
     p.add_argument("--weights", default="random", help="random (seeded synthetic weights) or an .npz in this engine's names")
@@ -414,6 +426,7 @@ def build_parser():
     p.add_argument("--image-root", dest="image_root", required=True)
     p.add_argument("--output", default="segm.json")
     p.add_argument("--batch-size", dest="batch_size", type=int, default=8)
+    p.add_argument("--resize", default=argparse.SUPPRESS, choices=["host", "device"], help="refused for Pose2Seg: its letterbox already runs on the device")
     p.add_argument("--max-instances", dest="max_instances", type=int, default=32)
     # the detector flags leave no attribute behind unless given: without them the command is the one it was
     p.add_argument("--keypoint-config", dest="keypoint_config", default=argparse.SUPPRESS,
@@ -434,6 +447,8 @@ def build_parser():
     y.add_argument("--best-class", dest="best_class", action="store_true", help="one candidate per anchor, its best class, instead of every class over the threshold")
     y.add_argument("--pool-pad", dest="pool_pad", choices=["ignore", "zero"], default=None,
                    help="yolov3-spp / -tiny max-pools: a tap outside the map is skipped (ignore: darknet, default) or counts as 0 (zero: the PyTorch ports)")
+    y.add_argument("--resize", default=argparse.SUPPRESS, choices=["host", "device"],
+                   help="(default host) where the letterbox runs: host = PIL, device = the original bytes go up and one kernel makes the canvas, bit-identical (DESIGN.md 24)")
     y.add_argument("--output", default="dets.json")
     y.add_argument("--batch-size", dest="batch_size", type=int, default=8)
     for q in (e, t, p, y):
@@ -447,6 +462,7 @@ def build_parser():
     v.add_argument("--img-size", dest="img_size", type=int, default=224, help="canvas side: a multiple of the patch size; the position embedding is not interpolated")
     v.add_argument("--gelu-tanh", dest="gelu_tanh", type=int, default=0, choices=[0, 1], help="1: the tanh GELU of the original JAX release")
     v.add_argument("--ln-eps", dest="ln_eps", type=float, default=1e-6)
+    v.add_argument("--resize", default=argparse.SUPPRESS, choices=["host", "device"], help="refused for ViT: its front end already resizes on the device")
     v.add_argument("--output", default="preds.json")
     v.add_argument("--batch-size", dest="batch_size", type=int, default=8)
     c = sub.add_parser("coco_eval", help="COCO AP / AR of a result json against an annotation json (pycocotools COCOeval restated)")

@@ -149,6 +149,16 @@ class Engine:
         _ffi.check(_ffi.lib().isegmi_engine_preprocess_u8(self._h, C.c_void_p(d_u8_ptr), n, hin, win, C.c_void_p(d_out_ptr), hout, wout, hpad, wpad,
                                                           hpad * wpad * 3, m, sd, 1 if swap_rb else 0))
 
+    def _resample_u8(self, st, plan, view, d_out_ptr, planes, hpad, wpad, mean, std, swap_rb, fill=0.0):
+        """isegmi_engine_resample_u8: launch `view` of a transforms.ResamplePlan whose blob sits in staging buffer `st` -> `planes` fp32
+        canvases of hpad x wpad at d_out_ptr: PIL-exact resize, normalisation, padding, one launch for the view's images."""
+        _, tables = plan.header()
+        t = tables[view]
+        m = (C.c_float * 3)(*[float(v) for v in mean]); sd = (C.c_float * 3)(*[float(v) for v in std])
+        _ffi.check(_ffi.lib().isegmi_engine_resample_u8(self._h, st.ptr, plan.nbytes, plan.table_off[view], _addr(t), t.shape[0], plan.coeff_off,
+                                                       plan.coeff_words, plan.src_off, C.c_void_p(d_out_ptr), planes, hpad, wpad, hpad * wpad * 3, m, sd,
+                                                       1 if swap_rb else 0, float(fill)))
+
     # -- device-side COCO output: RLE of the masks, one fixed-size record block per batch, asynchronous download slots --------
     def rle_device(self, image_hw=None):
         """pycocotools RLE (counts + compressed strings) of det.masks of the last postprocess / paste, on the results stream; image_hw

@@ -128,6 +128,15 @@ def bbox_aug_views(image_hw, cfg, aug, min_size=None, max_size=None):
     return views
 
 
+def bbox_aug_plan(sizes_hw, cfg, aug, min_size=None, max_size=None):
+    """The device-resize blob of one augmented batch: every original once, one launch per view of bbox_aug_views -- its rows name every
+    image of the batch, each on its own canvas plane.  -> (transforms.ResamplePlan, [hw [n, 2] int32 per view])"""
+    from .transforms import ResamplePlan
+    per_image = [bbox_aug_views(hw, cfg, aug, min_size, max_size) for hw in sizes_hw]
+    views = [[(i, v[k][0], v[k][1], 0, 0, 1 if v[k][2] else 0, i) for i, v in enumerate(per_image)] for k in range(len(per_image[0]))]
+    return ResamplePlan(sizes_hw, views), [np.array([(e[1], e[2]) for e in view], np.int32) for view in views]
+
+
 def bbox_aug_engine_side(cfg, aug, min_size=None, max_size=None):
     """The long side an engine needs for every view the plain rule's aspect allows: min(MAX_SIZE, ceil(largest short side * max / min)), not below the plain
     rule's own long side, rounded up to SIZE_DIVISIBILITY."""
@@ -773,17 +782,59 @@ class MaskRCNN(Engine):
         _ffi.check(_ffi.lib().isegmi_engine_upload_async(self._h, st.ptr, pinned_u8.ptr, nbytes))
         self._front_end(st, hw, slot)
 
+    # -- the resize on the device: the ORIGINAL bytes go up, one launch makes the batch's input ----------------------------
+    def original_plan(self, image_hw, min_size=None, max_size=None):
+        """The blob layout (transforms.ResamplePlan) of a batch of originals of sizes image_hw [(h, w)] under the resize rule (default: the config's
+        MIN_SIZE_TEST / MAX_SIZE_TEST): what upload_original_u8_async takes next to pinned memory that plan.write() filled.  -> (plan, resized hw)"""
+        from .transforms import maskrcnn_resize_plan
+        cfg = self.cfg
+        return maskrcnn_resize_plan(image_hw, int(min_size or cfg.MIN_SIZE_TEST), int(max_size or cfg.MAX_SIZE_TEST))
+
+    def upload_original_u8(self, images_bgr_u8, slot=0, min_size=None, max_size=None, canvas=None):
+        """upload_u8(maskrcnn_resize_u8(im) for im in images) with the resize on the device: the original HxWx3 uint8 BGR images go up once (with their
+        tables, one copy) and ONE launch writes the mean-subtracted, zero-padded batch -- bit-identical to the host path's input buffer."""
+        assert 0 < len(images_bgr_u8) <= self.max_batch
+        ims = [np.ascontiguousarray(im) for im in images_bgr_u8]
+        if any(im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3 for im in ims):
+            raise TypeError("upload_original_u8 takes HxWx3 uint8 images")
+        plan, hw = self.original_plan([im.shape[:2] for im in ims], min_size, max_size)
+        self._set_canvas(*(canvas or padded_canvas(hw, self.cfg.SIZE_DIVISIBILITY)))
+        flat = np.empty(plan.nbytes, np.uint8)
+        plan.write(flat, ims)
+        st = self._u8_staging(slot, plan.nbytes)
+        _ffi.check(_ffi.lib().isegmi_h2d(st.ptr, flat.ctypes.data_as(C.c_void_p), plan.nbytes))
+        self._resize_front_end(st, plan, hw, slot)
+        return len(ims)
+
+    def upload_original_u8_async(self, pinned_u8, plan, hw, slot=0, canvas=None):
+        """upload_original_u8 from a uint8 _ffi.PinnedBuffer that plan.write() filled ((plan, hw) = original_plan(sizes)), on the engine's copy stream."""
+        assert pinned_u8.nbytes >= plan.nbytes and hw.shape[0] <= self.max_batch
+        self._set_canvas(*(canvas or padded_canvas(hw, self.cfg.SIZE_DIVISIBILITY)))
+        st = self._u8_staging(slot, plan.nbytes)
+        _ffi.check(_ffi.lib().isegmi_engine_upload_async(self._h, st.ptr, pinned_u8.ptr, plan.nbytes))
+        self._resize_front_end(st, plan, hw, slot)
+
+    def _resize_front_end(self, st, plan, hw, slot):
+        H, W = self._canvas
+        assert hw[:, 0].max() <= H and hw[:, 1].max() <= W, "image larger than the padded canvas"
+        self._resample_u8(st, plan, 0, self.input_buffer(slot).ptr.value, hw.shape[0], H, W, PIXEL_MEAN, (1.0, 1.0, 1.0), False, 0.0)
+        self._hw = np.ascontiguousarray(hw, np.int32)
+
     def forward_device(self, n, slot=0):
         H, W = self._canvas
         _ffi.check(_ffi.lib().isegmi_maskrcnn_forward_canvas(self._h, self.input_buffer(slot).ptr, self._hw.ctypes.data_as(C.c_void_p), n, H, W))
 
     # -- test-time box augmentation (TEST.BBOX_AUG; DESIGN.md 23) ------------------------------------------------------------
-    def aug_enqueue(self, images_bgr_u8, aug, slot=0, min_size=None, max_size=None):
+    def aug_enqueue(self, images_bgr_u8, aug, slot=0, min_size=None, max_size=None, resize="host"):
         """The whole augmented pass of one batch of ORIGINAL images, enqueued: host resizes (PIL, one per distinct size rule), ONE upload of every
         scale's bytes (a scale serves both of its views: the mirror image is made by the front end), then per view the front end, the forward up to
         the box predictor and the candidate stage, and the merge into det.*.  Afterwards the engine's current image sizes are view 0's, so
-        set_output_sizes / pack_box_records work as behind a plain forward.  Call aug_check() before using det.*.  -> batch size."""
-        from .transforms import maskrcnn_resize_u8
+        set_output_sizes / pack_box_records work as behind a plain forward.  Call aug_check() before using det.*.  -> batch size.
+        resize="device" (DESIGN.md 24): no host resize at all -- each ORIGINAL goes up once, and every size rule's view and its mirror are made from those
+        bytes by one isegmi_engine_resample_u8 launch per view, bit-identical to the host path's input."""
+        from .transforms import get_size, maskrcnn_resize_u8
+        if resize not in ("host", "device"):
+            raise ValueError("resize: 'host' (PIL) or 'device' (isegmi_engine_resample_u8; DESIGN.md 24)")
         cfg = self.cfg
         n = len(images_bgr_u8)
         assert 0 < n <= self.max_batch
@@ -793,8 +844,12 @@ class MaskRCNN(Engine):
                 [(int(s), int(aug.MAX_SIZE), bool(aug.SCALE_H_FLIP)) for s in aug.SCALES]
         groups, chunks, off, kept = [], [], 0, self._canvas
         for mn, mx, flip in rules:
-            ims = [maskrcnn_resize_u8(np.ascontiguousarray(im), mn, mx) for im in images_bgr_u8]
-            hw = np.array([im.shape[:2] for im in ims], np.int32)
+            if resize == "device":
+                ims = []
+                hw = np.array([get_size(np.asarray(im).shape[1], np.asarray(im).shape[0], mn, mx) for im in images_bgr_u8], np.int32)
+            else:
+                ims = [maskrcnn_resize_u8(np.ascontiguousarray(im), mn, mx) for im in images_bgr_u8]
+                hw = np.array([im.shape[:2] for im in ims], np.int32)
             canvas = padded_canvas(hw, cfg.SIZE_DIVISIBILITY)
             try:                        # a view that does not fit the engine raises here, naming the sizes, before anything is enqueued;
                 self._set_canvas(*canvas)
@@ -806,7 +861,13 @@ class MaskRCNN(Engine):
                 chunks.append(im.reshape(-1))
                 off += im.size
             groups.append((hw, canvas, offs, flip))
-        flat = np.concatenate(chunks)
+        plan = None
+        if resize == "device":   # one launch per (size rule, mirror): its table rows name every image of the batch
+            plan, _ = bbox_aug_plan([np.asarray(im).shape[:2] for im in images_bgr_u8], cfg, aug, min_size, max_size)
+            flat = np.empty(plan.nbytes, np.uint8)
+            plan.write(flat, [np.ascontiguousarray(im) for im in images_bgr_u8])
+        else:
+            flat = np.concatenate(chunks)
         self.sync()   # the staging buffer may still be read by the front end of an earlier pass
         st = self._u8_staging(slot, flat.nbytes)
         _ffi.check(_ffi.lib().isegmi_h2d(st.ptr, flat.ctypes.data_as(C.c_void_p), flat.nbytes))
@@ -814,12 +875,16 @@ class MaskRCNN(Engine):
         _ffi.check(lib.isegmi_maskrcnn_aug_begin(self._h, n, int(aug.POOL_CAP)))
         hw0 = groups[0][0]
         d_out = self.input_buffer(slot).ptr.value
+        view = 0
         for hw, (H, W), offs, flip in groups:
             # BoxList.resize back to view 0: float(w0 / w_view), float(h0 / h_view), computed in double like _resize_ratios
             ratios = np.ascontiguousarray(np.stack([hw0[:, 1].astype(np.float64) / hw[:, 1], hw0[:, 0].astype(np.float64) / hw[:, 0]], 1).astype(np.float32))
             hwc = np.ascontiguousarray(hw, np.int32)
             for hflip in ((False, True) if flip else (False,)):
-                for i in range(n):
+                if plan is not None:
+                    self._resample_u8(st, plan, view, d_out, n, H, W, PIXEL_MEAN, (1.0, 1.0, 1.0), False, 0.0)
+                    view += 1
+                for i in range(n if plan is None else 0):
                     h, w = int(hw[i, 0]), int(hw[i, 1])
                     self._preprocess_u8(st.ptr.value + offs[i], 1, h, w, d_out + i * H * W * 3 * 4, h, w, H, W, PIXEL_MEAN, (1.0, 1.0, 1.0), False, hflip)
                 _ffi.check(lib.isegmi_maskrcnn_aug_view(self._h, C.c_void_p(d_out), hwc.ctypes.data_as(C.c_void_p), n, H, W, 1 if hflip else 0,
@@ -841,10 +906,10 @@ class MaskRCNN(Engine):
                                   "MODEL.ROI_HEADS.SCORE_THRESH or use fewer views" % (i, int(total[i]), self._aug_cap, BBOX_AUG_MAX_POOL))
         return total
 
-    def detect_aug(self, images_bgr_u8, aug, min_size=None, max_size=None):
+    def detect_aug(self, images_bgr_u8, aug, min_size=None, max_size=None, resize="host"):
         """[UPSTREAM-RECALL] im_detect_bbox_aug: ORIGINAL HxWx3 uint8 BGR images in, one BoxList per image out -- boxes, scores, labels in view-0
         coordinates (the identity view's resized image), filter_results run once over the candidates of every view."""
-        n = self.aug_enqueue(images_bgr_u8, aug, 0, min_size, max_size)
+        n = self.aug_enqueue(images_bgr_u8, aug, 0, min_size, max_size, resize)
         self.aug_check()
         cnt = self.fetch("det.count", n)
         box, score, label = (self.fetch(k, n) for k in ("det.box", "det.score", "det.label"))
@@ -916,6 +981,14 @@ class MaskRCNN(Engine):
         (14x14 for the C4 predictor; no mask field from a box-only engine; a keypoint engine adds keypoints [n,17,3] and keypoint_logits [n,17]).  With image_hw = None the first argument is a list of already-resized uint8 BGR images and goes
         through the device front end (upload_u8: mean subtraction and padding on the GPU)."""
         n = self.upload_u8(batch_nhwc3) if image_hw is None else self.upload(batch_nhwc3, image_hw)
+        return self._detect(n)
+
+    def detect_original(self, images_bgr_u8, min_size=None, max_size=None):
+        """__call__ on ORIGINAL uint8 BGR images: the resize rule runs on the device (upload_original_u8).  Same results as
+        self([maskrcnn_resize_u8(im, min_size, max_size) for im in images])."""
+        return self._detect(self.upload_original_u8(images_bgr_u8, 0, min_size, max_size))
+
+    def _detect(self, n):
         self.forward_device(n)
         self.sync()
         cnt = self.fetch("det.count", n)

@@ -19,13 +19,16 @@ class COCODemo:
     CATEGORIES = ("__background",) + COCO_CLASSES
 
     def __init__(self, cfg=None, min_image_size=800, confidence_threshold=0.5, state_dict=None, max_image_size=1333, device=0, max_batch=2,
-                 fp16=False, render="host", bbox_aug=None, aug_canvas=None):
-        """bbox_aug: a BBoxAugConfig next to a MaskRCNNConfig (a yaml-keyed node carries its own TEST.BBOX_AUG); aug_canvas = (H, W): the engine's largest
+                 fp16=False, render="host", bbox_aug=None, aug_canvas=None, resize="host"):
+        """resize: "host" -- PIL resizes every image before its bytes go up; "device" -- the original bytes go up and isegmi_engine_resample_u8 resizes
+        them, bit-identical to PIL.  bbox_aug: a BBoxAugConfig next to a MaskRCNNConfig (a yaml-keyed node carries its own TEST.BBOX_AUG); aug_canvas = (H, W): the engine's largest
         canvas under augmentation instead of the one derived from the scales."""
         from .retinanet import RetinaNetConfig
         if render not in ("host", "device"):
             raise ValueError("render: 'host' (numpy overlay of the downloaded masks) or 'device' (isegmi_engine_paint; DESIGN.md 22)")
-        self.render = render
+        if resize not in ("host", "device"):
+            raise ValueError("resize: 'host' (PIL on the host) or 'device' (isegmi_engine_resample_u8; DESIGN.md 24)")
+        self.render, self.resize = render, resize
         if cfg is not None and not isinstance(cfg, (MaskRCNNConfig, RetinaNetConfig)):   # the yacs-shaped node of isegmi.config (README.md:313-324)
             from .config import is_bbox_aug, is_keypoint_rcnn, is_retinanet, to_bbox_aug_config, to_keypointrcnn_config, to_maskrcnn_config, to_retinanet_config
             retina = is_retinanet(cfg)
@@ -90,10 +93,9 @@ class COCODemo:
         h, w = original_image.shape[:2]
         model = self.engine()
         if self.bbox_aug is not None:   # TEST.BBOX_AUG: the views are resized from the original inside detect_aug
-            (pred,) = model.detect_aug([original_image], self.bbox_aug, self.min_image_size, self.max_image_size)
+            (pred,) = model.detect_aug([original_image], self.bbox_aug, self.min_image_size, self.max_image_size, self.resize)
             return pred.resize((w, h))
-        resized = maskrcnn_resize_u8(original_image, self.min_image_size, self.max_image_size)
-        (pred,) = model([resized])  # device front end: the bytes cross PCIe, mean subtraction + padding (to_image_list) run on the GPU
+        (pred,) = self._forward_one(model, original_image)
         if self.is_retinanet or self.box_only:
             return pred.resize((w, h))
         model.paste_device(h, w, [(w, h)])
@@ -103,6 +105,13 @@ class COCODemo:
         out = pred.resize((w, h))
         out.add_field("mask", masks[:, None])
         return out
+
+    def _forward_one(self, model, image):
+        """One image through the front end and the forward.  resize="host": PIL, then the bytes cross PCIe and mean subtraction + padding (to_image_list)
+        run on the GPU; "device": the original bytes cross and the resize runs there too."""
+        if self.resize == "device":
+            return model.detect_original([image], self.min_image_size, self.max_image_size)
+        return model([maskrcnn_resize_u8(image, self.min_image_size, self.max_image_size)])
 
     def select_top_predictions(self, predictions):
         scores = predictions.get_field("scores")
@@ -126,9 +135,9 @@ class COCODemo:
         h, w = image.shape[:2]
         model = self.engine()
         if self.bbox_aug is not None:
-            (pred,) = model.detect_aug([image], self.bbox_aug, self.min_image_size, self.max_image_size)
+            (pred,) = model.detect_aug([image], self.bbox_aug, self.min_image_size, self.max_image_size, self.resize)
         else:
-            (pred,) = model([maskrcnn_resize_u8(image, self.min_image_size, self.max_image_size)])
+            (pred,) = self._forward_one(model, image)
         with_masks = not (self.is_retinanet or self.box_only)
         if with_masks:
             model.paste_device(h, w, [(w, h)])   # on the results stream; the painter is ordered behind it
@@ -197,7 +206,7 @@ class COCODemo:
 
 
 def inference(predictor, images, image_ids=None, batch_size=None, group="canvas", rank=0, world=1, sizes=None, stats=None, force_gather=False,
-              workers=4, category_ids=None):
+              workers=4, category_ids=None, resize=None):
     """engine/inference.py-shaped evaluation (README.md:344-347): images -> COCO-format result list (bbox + segm) ready for json.dump.
 
     The path the benchmark measures, end to end: batches of `batch_size` resized uint8 images go up through pinned memory (double-buffered),
@@ -220,10 +229,16 @@ def inference(predictor, images, image_ids=None, batch_size=None, group="canvas"
     "canvas" then groups by the canvases of ALL views, so that an image's result still equals its single-image result.  The augmented loop is NOT
     pipelined across steps: every step ends in aug_check (a device synchronisation and the fetch of the pool counters, so that an overflow raises before
     its records are packed); what still overlaps is the worker threads' loading of the next batch, and inside a step the views follow each other as
-    consecutive forwards do."""
+    consecutive forwards do.
+    resize: "host" -- the worker threads resize with PIL and the resized bytes go up; "device" -- the ORIGINAL bytes go up (pinned and staging buffers
+            sized by the largest batch's originals) and isegmi_engine_resample_u8 resizes them behind the copy, bit-identical; None: the
+            predictor's own setting.  Grouping, canvases and results are the same in both modes."""
     import time
+    resize = resize or getattr(predictor, "resize", "host")
+    if resize not in ("host", "device"):
+        raise ValueError("resize: 'host' or 'device'")
     if getattr(predictor, "is_retinanet", False):
-        return _inference_boxes(predictor, images, image_ids, batch_size, group, rank, world, sizes, stats, workers)
+        return _inference_boxes(predictor, images, image_ids, batch_size, group, rank, world, sizes, stats, workers, resize)
     from .coco import label_categories, results_from_records
     from .pipeline import record_capacity, run_record_loop, schedule_batches
     from .transforms import get_size
@@ -239,6 +254,7 @@ def inference(predictor, images, image_ids=None, batch_size=None, group="canvas"
     bs = int(batch_size or predictor.max_batch)
     model = predictor.engine(bs)
     cfg = predictor.cfg
+    device_resize = resize == "device"
     categories = label_categories(getattr(cfg, "NUM_CLASSES", 81), category_ids)
     box_only = bool(getattr(model, "box_only", False))
     aug = getattr(predictor, "bbox_aug", None)
@@ -261,6 +277,12 @@ def inference(predictor, images, image_ids=None, batch_size=None, group="canvas"
         from .maskrcnn import bbox_aug_views
         area = [sum(v[0] * v[1] * 3 for v in bbox_aug_views(hw, cfg, aug, predictor.min_image_size, predictor.max_image_size) if not v[2]) for hw in sizes]
         pin, stage_bytes = [], max([sum(area[i] for i in b) for b in batches] + [1])
+        if device_resize:   # the originals and the tables of every view
+            from .maskrcnn import bbox_aug_plan
+            stage_bytes = max([bbox_aug_plan([sizes[i] for i in b], cfg, aug, predictor.min_image_size, predictor.max_image_size)[0].nbytes for b in batches] + [1])
+    elif device_resize:   # pinned and staging buffers hold the largest batch's ORIGINAL bytes and their tables
+        stage_bytes = max([model.original_plan([sizes[i] for i in b], predictor.min_image_size, predictor.max_image_size)[0].nbytes for b in batches] + [1])
+        pin = [_ffi.PinnedBuffer((stage_bytes,), np.uint8) for _ in range(2)]
     else:
         pin, stage_bytes = [_ffi.PinnedBuffer((bs * model.H * model.W * 3,), np.uint8) for _ in range(2)], bs * model.H * model.W * 3
     for slot in (0, 1):
@@ -283,7 +305,7 @@ def inference(predictor, images, image_ids=None, batch_size=None, group="canvas"
                 per_image[i] = by_id.get(ids[i], [])
 
     def load(i):   # host: decode + PIL resize (outside the hot path)
-        if aug is not None:   # the views are resized from the original inside aug_enqueue
+        if aug is not None or device_resize:   # the views are resized from the original inside aug_enqueue / on the device
             return get(i)
         return maskrcnn_resize_u8(get(i), predictor.min_image_size, predictor.max_image_size)
     pool = None
@@ -306,16 +328,21 @@ def inference(predictor, images, image_ids=None, batch_size=None, group="canvas"
         futs = prefetch.pop(j, None)         # (a step that is redone after an RLE overflow loads its images again, inline)
         resized = [f.result() for f in futs] if futs else [load(i) for i in b]
         if aug is not None:
-            model.aug_enqueue(resized, aug, slot, predictor.min_image_size, predictor.max_image_size)
+            model.aug_enqueue(resized, aug, slot, predictor.min_image_size, predictor.max_image_size, resize)
             model.aug_check()                # BBoxAugOverflow: nothing is truncated silently
             model.set_output_sizes([(w, h) for h, w in (sizes[i] for i in b)])
             return True
-        off, hw = 0, []
-        for im in resized:                   # into pinned memory, back to back
-            pin[slot].array[off:off + im.size] = im.reshape(-1)
-            off += im.size
-            hw.append(im.shape[:2])
-        model.upload_u8_async(pin[slot], hw, slot)
+        if device_resize:                    # the originals and their tables into pinned memory: one copy, one launch
+            plan, hw = model.original_plan([im.shape[:2] for im in resized], predictor.min_image_size, predictor.max_image_size)
+            plan.write(pin[slot].array, resized)
+            model.upload_original_u8_async(pin[slot], plan, hw, slot)
+        else:
+            off, hw = 0, []
+            for im in resized:               # into pinned memory, back to back
+                pin[slot].array[off:off + im.size] = im.reshape(-1)
+                off += im.size
+                hw.append(im.shape[:2])
+            model.upload_u8_async(pin[slot], hw, slot)
         model.forward_device(len(b), slot)
         oh = [sizes[i] for i in b]
         if box_only:   # the record block's one launch scales the boxes to the original sizes
@@ -343,7 +370,7 @@ def inference(predictor, images, image_ids=None, batch_size=None, group="canvas"
     return [d for r in per_image if r for d in r]
 
 
-def _inference_boxes(predictor, images, image_ids, batch_size, group, rank, world, sizes, stats, workers):
+def _inference_boxes(predictor, images, image_ids, batch_size, group, rank, world, sizes, stats, workers, resize="host"):
     """inference() for a detector without masks (RetinaNet): bbox-only COCO results -- xywh with the legacy +1, no `segmentation` key.  Per step the four
     fixed-size detection buffers come back through the engine's two asynchronous download slots into pinned memory; step t's download and step t + 1's
     upload + forward are enqueued before step t's results are unpacked, so the host work hides under the device's."""
@@ -373,13 +400,19 @@ def _inference_boxes(predictor, images, image_ids, batch_size, group, rank, worl
     else:
         raise ValueError("group: 'canvas' or 'aspect'")
     batches = schedule_batches(keys, bs)
-    pin = [_ffi.PinnedBuffer((bs * model.H * model.W * 3,), np.uint8) for _ in range(2)]
+    device_resize = resize == "device"
+    in_bytes = bs * model.H * model.W * 3
+    if device_resize:   # the largest batch's ORIGINAL bytes and their tables
+        in_bytes = max([model.original_plan([sizes[i] for i in b], predictor.min_image_size, predictor.max_image_size)[0].nbytes for b in batches] + [1])
+    pin = [_ffi.PinnedBuffer((in_bytes,), np.uint8) for _ in range(2)]
     out_pin = [_ffi.PinnedBuffer((model.detection_bytes(bs),), np.uint8) for _ in range(2)]
     for slot in (0, 1):
-        model._u8_staging(slot, bs * model.H * model.W * 3)
+        model._u8_staging(slot, in_bytes)
     per_image = [None] * n_img
 
     def load(i):
+        if device_resize:
+            return get(i)
         return maskrcnn_resize_u8(get(i), predictor.min_image_size, predictor.max_image_size)
     pool = None
     if workers and workers > 0:
@@ -397,12 +430,17 @@ def _inference_boxes(predictor, images, image_ids, batch_size, group, rank, worl
         request(j + 1)
         futs = prefetch.pop(j, None)
         resized = [f.result() for f in futs] if futs else [load(i) for i in b]
-        off, hw = 0, []
-        for im in resized:
-            pin[slot].array[off:off + im.size] = im.reshape(-1)
-            off += im.size
-            hw.append(im.shape[:2])
-        model.upload_u8_async(pin[slot], hw, slot)
+        if device_resize:
+            plan, hw = model.original_plan([im.shape[:2] for im in resized], predictor.min_image_size, predictor.max_image_size)
+            plan.write(pin[slot].array, resized)
+            model.upload_original_u8_async(pin[slot], plan, hw, slot)
+        else:
+            off, hw = 0, []
+            for im in resized:
+                pin[slot].array[off:off + im.size] = im.reshape(-1)
+                off += im.size
+                hw.append(im.shape[:2])
+            model.upload_u8_async(pin[slot], hw, slot)
         model.forward_device(len(b), slot)
         model.download_detections_async(slot, out_pin[slot], bs)
         return hw

@@ -145,7 +145,9 @@ class RetinaNet(MaskRCNN, DetectionBlock):
     def __call__(self, batch_nhwc3, image_hw=None):
         """-> list of BoxList (one per image, network-input coordinates) with scores and labels 1..80.  image_hw None: a list of already-resized uint8
         BGR images through the device front end."""
-        n = self.upload_u8(batch_nhwc3) if image_hw is None else self.upload(batch_nhwc3, image_hw)
+        return self._detect(self.upload_u8(batch_nhwc3) if image_hw is None else self.upload(batch_nhwc3, image_hw))
+
+    def _detect(self, n):
         self.forward_device(n)
         self.sync()
         return self.boxlists(n, *(self.fetch(k, n) for k in ("det.count", "det.box", "det.score", "det.label")))

@@ -94,3 +94,113 @@ def yolo_unletterbox(boxes_xyxy, geometry, h, w):
     out[:, 0::2] = np.clip(out[:, 0::2], np.float32(0), np.float32(w))
     out[:, 1::2] = np.clip(out[:, 1::2], np.float32(0), np.float32(h))
     return out.astype(np.float32)
+
+
+# -- PIL-exact resize on the device: the tables and the one-upload blob of isegmi_op_resample_u8 ---------------------------
+RESAMPLE_MAX_KSIZE = 1025     # ISEGMI_RESAMPLE_MAX_KSIZE
+RESAMPLE_ENTRY_WORDS = 16     # ISEGMI_RESAMPLE_ENTRY_WORDS
+_TABLES = {}
+
+
+def resample_ksize(I, O):
+    """Taps per output sample of PIL's bilinear filter on an axis I -> O: 2 ceil(max(I / O, 1)) + 1."""
+    import math
+    return 2 * int(math.ceil(max(I / O, 1.0))) + 1
+
+
+def resample_tables(I, O):
+    """PIL's 8-bit bilinear coefficient tables of one axis I -> O (isegmi_resample_coeffs, host only): (bounds [O, 2] = (xmin, n), kk [O, ksize]) int32,
+    read-only and cached by (I, O).  Raises for I, O < 1 and for downscales beyond the kernel's cap (ksize > RESAMPLE_MAX_KSIZE)."""
+    import ctypes as C
+    from . import _ffi
+    key = (int(I), int(O))
+    t = _TABLES.get(key)
+    if t is None:
+        ks = C.c_int()
+        _ffi.check(_ffi.lib().isegmi_resample_coeffs(key[0], key[1], None, None, C.byref(ks)))
+        bounds, kk = np.zeros((key[1], 2), np.int32), np.zeros((key[1], ks.value), np.int32)
+        _ffi.check(_ffi.lib().isegmi_resample_coeffs(key[0], key[1], bounds.ctypes.data_as(C.c_void_p), kk.ctypes.data_as(C.c_void_p), C.byref(ks)))
+        bounds.setflags(write=False); kk.setflags(write=False)
+        if len(_TABLES) >= 1024:
+            _TABLES.clear()
+        t = _TABLES[key] = (bounds, kk)
+    return t
+
+
+class ResamplePlan:
+    """The layout of one blob [image tables of every view][coefficient tables][original pixels, back to back] that a batch's resizes need, from sizes alone.
+
+    sizes_hw: (h, w) of every original, in the order their pixels are packed.  views: one list per launch of (image, Hout, Wout, dst_y, dst_x, hflip,
+    plane) -- image indexes sizes_hw, the resized image sits at (dst_y, dst_x) of canvas plane `plane`.  The layout (offsets, nbytes) needs no table
+    values; header() computes them (cached per (I, O)) and write() fills a uint8 buffer -- pinned memory or a numpy array -- for the single upload."""
+
+    def __init__(self, sizes_hw, views):
+        self.sizes = [(int(h), int(w)) for h, w in sizes_hw]
+        self.views = [[tuple(int(v) for v in e) for e in view] for view in views]
+        self.table_off, off = [], 0
+        for view in self.views:
+            self.table_off.append(off)
+            off += len(view) * RESAMPLE_ENTRY_WORDS * 4
+        self.coeff_off = off
+        self._axes, words = {}, 0
+        for view in self.views:
+            for i, ho, wo, *_ in view:
+                h, w = self.sizes[i]
+                for I, O in ((w, wo), (h, ho)):
+                    if (I, O) not in self._axes:
+                        ks = resample_ksize(I, O)
+                        if I < 1 or O < 1 or ks > RESAMPLE_MAX_KSIZE:
+                            raise ValueError("resize %d -> %d: sizes are positive and a downscale stays within 512 (at most %d taps per sample)" % (I, O, RESAMPLE_MAX_KSIZE))
+                        self._axes[(I, O)] = (words, ks)
+                        words += O * (2 + ks)
+        self.coeff_words = words
+        self.src_off = self.coeff_off + words * 4
+        self.image_off, off = [], 0
+        for h, w in self.sizes:
+            self.image_off.append(off)
+            off += h * w * 3
+        self.pixel_bytes = off
+        self.nbytes = self.src_off + off
+        self._header = None
+
+    def header(self):
+        """-> (uint8 [src_off] header bytes, [int32 [n, 16] table per view])"""
+        if self._header is None:
+            coeffs = np.zeros(self.coeff_words, np.int32)
+            for (I, O), (off, ks) in self._axes.items():
+                bounds, kk = resample_tables(I, O)
+                assert kk.shape == (O, ks)
+                coeffs[off:off + 2 * O] = bounds.reshape(-1)
+                coeffs[off + 2 * O:off + O * (2 + ks)] = kk.reshape(-1)
+            tables = []
+            for view in self.views:
+                t = np.zeros((len(view), RESAMPLE_ENTRY_WORDS), np.int32)
+                for r, (i, ho, wo, dy, dx, flip, plane) in enumerate(view):
+                    h, w = self.sizes[i]
+                    (ch, ksh), (cv, ksv) = self._axes[(w, wo)], self._axes[(h, ho)]
+                    so = self.image_off[i]
+                    lo = so & 0xFFFFFFFF   # the int64 offset as two int32 words
+                    t[r] = (lo - (1 << 32) if lo >= 1 << 31 else lo, so >> 32, h, w, ho, wo, dy, dx, ch, cv, ksh, ksv, 1 if flip else 0, plane, 0, 0)
+                tables.append(t)
+            head = np.concatenate([t.reshape(-1) for t in tables] + [coeffs]).view(np.uint8)
+            assert head.nbytes == self.src_off
+            self._header = (head, tables)
+        return self._header
+
+    def write(self, buf_u8, images):
+        """Header and pixels into buf_u8 (a flat uint8 array of at least nbytes)."""
+        head, _ = self.header()
+        assert len(images) == len(self.sizes) and buf_u8.size >= self.nbytes
+        buf_u8[:self.src_off] = head
+        for im, off, (h, w) in zip(images, self.image_off, self.sizes):
+            im = np.asarray(im)
+            if im.dtype != np.uint8 or im.shape != (h, w, 3):
+                raise TypeError("an original image is HxWx3 uint8 of the size the plan was made for")
+            buf_u8[self.src_off + off:self.src_off + off + im.size] = im.reshape(-1)
+        return self.nbytes
+
+
+def maskrcnn_resize_plan(sizes_hw, min_size=800, max_size=1333):
+    """One view: every original resized by get_size, top-left on its own canvas plane (to_image_list).  -> (plan, resized hw [n, 2] int32)"""
+    hw = np.array([get_size(w, h, min_size, max_size) for h, w in sizes_hw], np.int32).reshape(-1, 2)
+    return ResamplePlan(sizes_hw, [[(i, hw[i, 0], hw[i, 1], 0, 0, 0, i) for i in range(len(sizes_hw))]]), hw

@@ -1,7 +1,8 @@
 """YOLOv3 inference, host side ([UPSTREAM-RECALL] the public yolov3.cfg / COCO-80 model, unverified: the reference's yolo.jittor directory is
 empty).  `net = YoloV3(sd, H, W)`; `dets = net(batch)` -> per image boxes (canvas coordinates), scores, labels 1..C.  `YoloDetector(...).detect(images)`
 adds the letterbox front end and maps the boxes back to the original images.  All numerics run in libisegmi.so (engine kind 5); this module moves
-config, weights and results across the C ABI.  The device front end (preprocess_u8) is not built for this model: the letterbox runs on the host.
+config, weights and results across the C ABI.  The letterbox runs on the host by default (PIL); YoloDetector(..., resize="device") uploads the original
+bytes and runs it on the device (isegmi_engine_resample_u8: PIL-exact resize, x / 255, RGB, 0.5 border), bit-identical.
 YoloV3Config.variant selects yolov3, yolov3-spp or yolov3-tiny; pool_pad is the pad switch of the two variants' max-pools."""
 import ctypes as C
 from dataclasses import dataclass
@@ -158,6 +159,24 @@ class YoloV3(Engine, DetectionBlock):
         _ffi.check(_ffi.lib().isegmi_h2d(self.input_buffer(slot).ptr, x.ctypes.data_as(C.c_void_p), x.nbytes))
         return x.shape[0]
 
+    def upload_original_u8(self, images_bgr_u8, slot=0):
+        """The letterbox on the device: ORIGINAL HxWx3 uint8 BGR images -> the canvas batch yolo_letterbox makes on the host, bit for bit:
+        one upload of the bytes and their tables, one launch (resize to the letterbox size at (pad_y, pad_x), x / 255, RGB, 0.5 elsewhere).
+        -> (n, [(gain, pad_x, pad_y)])"""
+        from .transforms import ResamplePlan, letterbox_geometry
+        ims = [np.ascontiguousarray(im) for im in images_bgr_u8]
+        assert 0 < len(ims) <= self.max_batch
+        if any(im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3 for im in ims):
+            raise TypeError("upload_original_u8 takes HxWx3 uint8 images")
+        geo = [letterbox_geometry(im.shape[0], im.shape[1], self.H, self.W) for im in ims]
+        plan = ResamplePlan([im.shape[:2] for im in ims], [[(i, nh, nw, py, px, 0, i) for i, (_, nh, nw, px, py) in enumerate(geo)]])
+        flat = np.empty(plan.nbytes, np.uint8)
+        plan.write(flat, ims)
+        st = self._u8_staging(slot, plan.nbytes)
+        _ffi.check(_ffi.lib().isegmi_h2d(st.ptr, flat.ctypes.data_as(C.c_void_p), plan.nbytes))
+        self._resample_u8(st, plan, 0, self.input_buffer(slot).ptr.value, len(ims), self.H, self.W, (0.0, 0.0, 0.0), (255.0, 255.0, 255.0), True, 0.5)
+        return len(ims), [(g, px, py) for g, _, _, px, py in geo]
+
     def forward_device(self, n, slot=0):
         _ffi.check(_ffi.lib().isegmi_yolov3_forward(self._h, self.input_buffer(slot).ptr, n))
 
@@ -182,10 +201,13 @@ class YoloV3(Engine, DetectionBlock):
 
 
 class YoloDetector:
-    """Images in, detections in original image coordinates out: letterbox on the host, YoloV3 on the device, the back mapping in numpy fp32."""
+    """Images in, detections in original image coordinates out: letterbox on the host (resize="host", PIL) or on the device (resize="device": the original
+    bytes go up, YoloV3.upload_original_u8), YoloV3 on the device, the back mapping in numpy fp32.  Both modes give identical detections."""
 
-    def __init__(self, state_dict, cfg=YoloV3Config(), max_batch=8, device=0):
-        self.cfg = cfg
+    def __init__(self, state_dict, cfg=YoloV3Config(), max_batch=8, device=0, resize="host"):
+        if resize not in ("host", "device"):
+            raise ValueError("resize: 'host' (PIL letterbox) or 'device' (isegmi_engine_resample_u8; DESIGN.md 24)")
+        self.cfg, self.resize = cfg, resize
         self.net = YoloV3(state_dict, cfg.height, cfg.width, cfg, max_batch=max_batch, device=device)
 
     def detect(self, images_bgr_u8):
@@ -195,6 +217,13 @@ class YoloDetector:
         B = self.net.max_batch
         for i0 in range(0, len(images_bgr_u8), B):
             ims = images_bgr_u8[i0:i0 + B]
+            if self.resize == "device":
+                n, geos = self.net.upload_original_u8(ims)
+                self.net.forward_device(n)
+                self.net.sync()
+                for im, geo, d in zip(ims, geos, self.net.detections(n)):
+                    out.append((yolo_unletterbox(d["box"], geo, im.shape[0], im.shape[1]), d["score"], d["label"]))
+                continue
             lb = [yolo_letterbox(im, self.cfg.height, self.cfg.width) for im in ims]
             dets = self.net(np.stack([x for x, _ in lb]))
             for im, (_, geo), d in zip(ims, lb, dets):
