@@ -358,6 +358,21 @@ int isegmi_op_yolact_masks(const float* d_proto, const float* d_coeffs, const fl
                            const int32_t* d_count, int N, int PH, int PW, int mask_dim, int K, int h,
                            int w, float* d_ws_lo, uint8_t* d_out_masks, int64_t* d_out_boxes,
                            void* stream);
+/* The same stage with the forks the engines take (parity-test entry).  d_image_hw [N][2] (may be NULL): image n is assembled at its own (h_n, w_n)
+ * in the top-left corner of the common h x w plane.  d_win [N][K][4] (may be NULL) receives, for every slot below the count, a window
+ * (x0, y0, x1, y1) that holds every set pixel of the slot; slots past the count are not written.  clear = 0: the planes are not zeroed first and only
+ * the bytes inside each window are written (a reader goes through the windows).  dense_lo = 1: d_ws_lo receives the complete zero-padded
+ * proto-resolution masks of the slots below the count, not only their crop windows' pixels. */
+int isegmi_op_yolact_masks_win(const float* d_proto, const float* d_coeffs, const float* d_boxes, const int32_t* d_count, int N, int PH, int PW,
+                               int mask_dim, int K, int h, int w, float* d_ws_lo, uint8_t* d_out_masks, int64_t* d_out_boxes,
+                               const int32_t* d_image_hw, int32_t* d_win, int clear, int dense_lo, void* stream);
+/* YOLACT++ mask re-scoring, first layer (parity-test entry): d_lo [NK][PH][PW] -> d_out [NK][Ho][Wo][32], Ho = (PH - 3) / 2 + 1, Wo = (PW - 3) / 2 + 1:
+ * channels 0..7 = relu(3x3 stride-2 conv with d_w [8][9], d_b [8]; nine chained fmaf, then the bias), channels 8..31 = 0.  PH, PW >= 3. */
+int isegmi_op_maskiou_conv1(const float* d_lo, int NK, int PH, int PW, const float* d_w, const float* d_b, float* d_out, void* stream);
+/* YOLACT++ mask re-scoring, last step (parity-test entry): d_feat [N*K][HW][C], d_cls / d_score [N][K], d_count [N] ->
+ * d_out [n][d] = d_score[n][d] * max over HW of d_feat[n*K + d][.][d_cls[n][d]] for d < d_count[n], else 0. */
+int isegmi_op_maskiou_rescore(const float* d_feat, int N, int K, int HW, int C, const int32_t* d_cls, const float* d_score, const int32_t* d_count,
+                              float* d_out, void* stream);
 
 /* ---- Mask R-CNN RoI ops (M6 M7 M9 M10 M11 M12; App. A.4-A.8; all reached from README.md:331) ---- */
 /* Semantic forks of the NMS (which of them detectron.jittor takes is unknown -- the reference tree holds no code -- so every one is a
@@ -455,6 +470,12 @@ int isegmi_op_mask_logits_select_f16(const void* d_feat, int R, int HW, int C, c
 /* Masker(threshold, padding=1) paste (A.8): masks [N][K][M][M], boxes [N][K][4] -> u8 [N][K][im_h][im_w] */
 int isegmi_op_paste_masks(const float* d_masks, const float* d_boxes, const int32_t* d_counts, int N,
                           int K, int M, int im_h, int im_w, float thr, uint8_t* d_out, void* stream);
+/* The same paste with the forks the engines take (parity-test entry).  d_win [N][K][4] (may be NULL) receives, for every slot below the count, the
+ * window (x0, y0, x1, y1) of the padded box clamped to the image: every set pixel lies inside it (x1 <= x0 or y1 <= y0: none is set); slots past
+ * the count are not written.  clear = 0: the planes are not zeroed first; every byte inside a window is written, and outside it at most the three
+ * bytes that share a 4-byte word with a window row's end (as zeros). */
+int isegmi_op_paste_masks_win(const float* d_masks, const float* d_boxes, const int32_t* d_counts, int N, int K, int M, int im_h, int im_w,
+                              float thr, uint8_t* d_out, int32_t* d_win, int clear, void* stream);
 /* AnchorGenerator.grid_anchors (M5, A.3): d_out [(y*grid_w + x)*A + a][4] = d_base[a] + (x, y, x, y) * stride */
 int isegmi_op_grid_anchors(const float* d_base, int A, int stride, int grid_h, int grid_w, float* d_out, void* stream);
 /* one RPN level (A.4) for N images: fused head [N][HW][A*5] (A logits then A*4 deltas per pixel) */

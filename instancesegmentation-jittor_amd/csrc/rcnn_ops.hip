@@ -1389,6 +1389,13 @@ extern "C" int isegmi_op_paste_masks(const float* d_masks, const float* d_boxes,
                                      int im_h, int im_w, float thr, uint8_t* d_out, void* stream) {
     return paste_masks_launch(d_masks, d_boxes, d_counts, N, K, M, im_h, im_w, thr, d_out, (hipStream_t)stream, nullptr, true);
 }
+// the same launcher with its two product-path forks exposed: the box windows (d_win, may be NULL) and the planes left uncleared (clear = 0)
+extern "C" int isegmi_op_paste_masks_win(const float* d_masks, const float* d_boxes, const int32_t* d_counts, int N, int K, int M,
+                                         int im_h, int im_w, float thr, uint8_t* d_out, int32_t* d_win, int clear, void* stream) {
+    ARG_CHECK(d_masks && d_boxes && d_counts && d_out, "paste_masks_win: null pointer");
+    ARG_CHECK(N > 0 && K > 0 && M > 0 && im_h > 0 && im_w > 0 && (int64_t)im_h * im_w < (1ll << 31), "paste_masks_win sizes");
+    return paste_masks_launch(d_masks, d_boxes, d_counts, N, K, M, im_h, im_w, thr, d_out, (hipStream_t)stream, d_win, clear != 0);
+}
 
 // One RPN level for N images (parity-test entry; the engine calls the same launchers):
 // head [N][HW][A*5] -> boxes/scores [N][post_nms] (+count).  Workspaces: prob [N][HWA], tk_* [N][pre_nms]; d_ws_nms: optional

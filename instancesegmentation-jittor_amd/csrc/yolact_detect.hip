@@ -684,6 +684,7 @@ int yolact_masks_launch(const float* proto, const float* coeffs, const float* bo
                         const int* image_hw, int* win, bool clear, bool dense_lo) {
     ARG_CHECK(mask_dim == MD, "mask_dim must be 32");
     ARG_CHECK(N > 0 && K > 0 && K <= 128 && h > 0 && w > 0, "mask sizes");
+    ARG_CHECK((int64_t)h * w < (1ll << 31), "h * w must stay below 2^31");
     const size_t lds = (size_t)K * (MD + 4) * sizeof(float);
     // dense_lo: ws_lo receives the complete zero-padded proto-resolution masks (a consumer other than the upsampling below reads them)
     if (dense_lo)
@@ -693,7 +694,6 @@ int yolact_masks_launch(const float* proto, const float* coeffs, const float* bo
         hipLaunchKernelGGL(yolact_proto_masks_kernel<false>, dim3(cdiv(PH * PW, 256), N, cdiv(K, PROTO_DG)), dim3(256), lds, st, proto, coeffs, boxes, count,
                            PH, PW, K, ws_lo);
     HIP_TRY(hipGetLastError());
-    ARG_CHECK((int64_t)h * w < (1ll << 31), "h * w must stay below 2^31");
     if (clear) HIP_TRY(hipMemsetAsync(out_masks, 0, (size_t)N * K * h * w, st));  // skipped when the planes are read through their windows only
     // chunks per detection: a full-image window is h*w pixels; 256 threads x ~8 pixels per thread and chunk
     int chunks = (int)cdiv64((int64_t)h * w, 2048);
@@ -721,4 +721,29 @@ extern "C" int isegmi_op_yolact_masks(const float* d_proto, const float* d_coeff
                                       uint8_t* d_out_masks, int64_t* d_out_boxes, void* stream) {
     return yolact_masks_launch(d_proto, d_coeffs, d_boxes, d_count, N, PH, PW, mask_dim, K, h, w, d_ws_lo, d_out_masks, d_out_boxes,
                                (hipStream_t)stream, nullptr, nullptr, true, false);
+}
+// the same launcher with its product-path forks exposed: per-image sizes inside the common plane (d_image_hw), the box windows (d_win), the planes
+// left uncleared (clear = 0) and the complete zero-padded proto-resolution masks in d_ws_lo (dense_lo = 1)
+extern "C" int isegmi_op_yolact_masks_win(const float* d_proto, const float* d_coeffs, const float* d_boxes, const int* d_count,
+                                          int N, int PH, int PW, int mask_dim, int K, int h, int w, float* d_ws_lo,
+                                          uint8_t* d_out_masks, int64_t* d_out_boxes, const int32_t* d_image_hw, int32_t* d_win, int clear,
+                                          int dense_lo, void* stream) {
+    ARG_CHECK(d_proto && d_coeffs && d_boxes && d_count && d_ws_lo && d_out_masks, "yolact_masks_win: null pointer");
+    ARG_CHECK(PH > 0 && PW > 0, "yolact_masks_win: prototype size");
+    return yolact_masks_launch(d_proto, d_coeffs, d_boxes, d_count, N, PH, PW, mask_dim, K, h, w, d_ws_lo, d_out_masks, d_out_boxes,
+                               (hipStream_t)stream, d_image_hw, d_win, clear != 0, dense_lo != 0);
+}
+// YOLACT++ mask re-scoring ends (the engine calls the same launchers).  d_lo [NK][PH][PW]; d_w [8][9]; d_b [8]; d_out [NK][Ho][Wo][32] with
+// Ho = (PH - 3) / 2 + 1, Wo = (PW - 3) / 2 + 1
+extern "C" int isegmi_op_maskiou_conv1(const float* d_lo, int NK, int PH, int PW, const float* d_w, const float* d_b, float* d_out, void* stream) {
+    ARG_CHECK(d_lo && d_w && d_b && d_out, "maskiou_conv1: null pointer");
+    ARG_CHECK(NK > 0 && PH >= 3 && PW >= 3, "maskiou_conv1 sizes (input at least 3x3)");
+    return maskiou_conv1_launch(d_lo, NK, PH, PW, d_w, d_b, d_out, (hipStream_t)stream);
+}
+// d_feat [N*K][HW][C]; d_cls, d_score [N][K]; d_count [N]; d_out [N][K] = score * max over HW of feat[..][cls] (0 past the count)
+extern "C" int isegmi_op_maskiou_rescore(const float* d_feat, int N, int K, int HW, int C, const int32_t* d_cls, const float* d_score,
+                                         const int32_t* d_count, float* d_out, void* stream) {
+    ARG_CHECK(d_feat && d_cls && d_score && d_count && d_out, "maskiou_rescore: null pointer");
+    ARG_CHECK(N > 0 && K > 0 && HW > 0 && C > 0, "maskiou_rescore sizes");
+    return maskiou_rescore_launch(d_feat, N, K, HW, C, d_cls, d_score, d_count, d_out, (hipStream_t)stream);
 }

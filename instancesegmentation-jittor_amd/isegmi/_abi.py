@@ -153,6 +153,9 @@ SIGNATURES = {
     "isegmi_op_yolact_detect": (I, [V, V]),
     "isegmi_op_yolact_coeff_rows": (I, [I, V, V, V, I, I, I, I, I, V, V, V, I, I, V, V, I, V, V]),
     "isegmi_op_yolact_masks": (I, [V, V, V, V, I, I, I, I, I, I, I, V, V, V, V]),
+    "isegmi_op_yolact_masks_win": (I, [V, V, V, V, I, I, I, I, I, I, I, V, V, V, V, V, I, I, V]),
+    "isegmi_op_maskiou_conv1": (I, [V, I, I, I, V, V, V, V]),
+    "isegmi_op_maskiou_rescore": (I, [V, I, I, I, I, V, V, V, V, V]),
     "isegmi_op_nms": (I, [V, V, I, I, F, I, I, I, V, V, V]),
     "isegmi_op_roi_align": (I, [V, V, V, V, I, V, V, I, I, I, I, I, I, I, I, I, V, V, V]),
     "isegmi_op_avgpool_full": (I, [V, L, I, I, V, V]),
@@ -165,6 +168,7 @@ SIGNATURES = {
     "isegmi_op_mask_logits_select": (I, [V, I, I, I, V, V, V, V, V]),
     "isegmi_op_mask_logits_select_f16": (I, [V, I, I, I, V, V, V, V, V]),
     "isegmi_op_paste_masks": (I, [V, V, V, I, I, I, I, I, F, V, V]),
+    "isegmi_op_paste_masks_win": (I, [V, V, V, I, I, I, I, I, F, V, V, I, V]),
     "isegmi_op_grid_anchors": (I, [V, I, I, I, I, V, V]),
     "isegmi_op_rpn_level": (I, [V, V, V, I, I, I, I, I, F, F, I, V, V, V, V, V, V, V, V, V]),
     "isegmi_op_rpn_levels_workspace": (I, [I, I, V, I, I, V, V]),

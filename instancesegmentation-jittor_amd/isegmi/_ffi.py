@@ -650,6 +650,61 @@ def yolact_masks(proto, coeffs, boxes, counts, h, w):
     return dm.numpy(), dob.numpy()
 
 
+def _initial(init, shape, dtype, fill):
+    """caller-supplied initial contents of an output buffer (a poison, or what a previous launch left), or `fill` everywhere"""
+    if init is None:
+        return np.full(shape, fill, dtype)
+    a = np.ascontiguousarray(init, dtype)
+    assert a.shape == tuple(shape), (a.shape, shape)
+    return a
+
+
+def yolact_masks_win(proto, coeffs, boxes, counts, h, w, image_hw=None, clear=False, dense_lo=False, planes=None, windows=None, ws_lo=None,
+                     want_windows=True):
+    """isegmi_op_yolact_masks_win: the mask assembly with the engines' forks.  planes [N,K,h,w] u8, windows [N,K,4] i32 and ws_lo [N,K,PH,PW] f32 are
+    the buffers' contents BEFORE the launch (default: 0xA5 bytes, -1, NaN) -> (planes, windows or None, ws_lo, boxes i64) after it."""
+    proto = np.ascontiguousarray(proto, np.float32)
+    N, PH, PW, md = proto.shape
+    K = coeffs.shape[1]
+    dp = DeviceBuffer.from_numpy(proto); dc = DeviceBuffer.from_numpy(np.asarray(coeffs, np.float32))
+    db = DeviceBuffer.from_numpy(np.asarray(boxes, np.float32)); dn = DeviceBuffer.from_numpy(np.asarray(counts, np.int32))
+    dlo = DeviceBuffer.from_numpy(_initial(ws_lo, (N, K, PH, PW), np.float32, np.nan))
+    dm = DeviceBuffer.from_numpy(_initial(planes, (N, K, h, w), np.uint8, 0xA5))
+    dwin = DeviceBuffer.from_numpy(_initial(windows, (N, K, 4), np.int32, -1)) if want_windows else None
+    dh = None if image_hw is None else DeviceBuffer.from_numpy(np.ascontiguousarray(image_hw, np.int32).reshape(N, 2))
+    dob = DeviceBuffer((N, K, 4), np.int64)
+    check(lib().isegmi_op_yolact_masks_win(dp.ptr, dc.ptr, db.ptr, dn.ptr, N, PH, PW, md, K, h, w, dlo.ptr, dm.ptr, dob.ptr, _ptr(dh), _ptr(dwin),
+                                           int(bool(clear)), int(bool(dense_lo)), None))
+    sync()
+    return dm.numpy(), (dwin.numpy() if want_windows else None), dlo.numpy(), dob.numpy()
+
+
+def maskiou_conv1(lo, w, b, out=None):
+    """lo [NK,PH,PW]; w [8,9]; b [8] -> [NK,Ho,Wo,32] (isegmi_op_maskiou_conv1); `out`: the output buffer's contents before the launch (default NaN)"""
+    lo = np.ascontiguousarray(lo, np.float32)
+    NK, PH, PW = lo.shape
+    Ho, Wo = (PH - 3) // 2 + 1, (PW - 3) // 2 + 1
+    dl = DeviceBuffer.from_numpy(lo); dw = DeviceBuffer.from_numpy(np.ascontiguousarray(w, np.float32).reshape(8, 9))
+    db = DeviceBuffer.from_numpy(np.ascontiguousarray(b, np.float32).reshape(8))
+    do = DeviceBuffer.from_numpy(_initial(out, (NK, Ho, Wo, 32), np.float32, np.nan))
+    check(lib().isegmi_op_maskiou_conv1(dl.ptr, NK, PH, PW, dw.ptr, db.ptr, do.ptr, None))
+    sync()
+    return do.numpy()
+
+
+def maskiou_rescore(feat, cls, score, count):
+    """feat [N,K,HW,C]; cls i32 / score f32 [N,K]; count [N] -> [N,K] (isegmi_op_maskiou_rescore); the output buffer starts as NaN"""
+    feat = np.ascontiguousarray(feat, np.float32)
+    N, K, HW, Cc = feat.shape
+    df = DeviceBuffer.from_numpy(feat); dc = DeviceBuffer.from_numpy(np.ascontiguousarray(cls, np.int32).reshape(N, K))
+    ds = DeviceBuffer.from_numpy(np.ascontiguousarray(score, np.float32).reshape(N, K))
+    dn = DeviceBuffer.from_numpy(np.ascontiguousarray(count, np.int32).reshape(N))
+    do = DeviceBuffer.from_numpy(np.full((N, K), np.nan, np.float32))
+    check(lib().isegmi_op_maskiou_rescore(df.ptr, N, K, HW, Cc, dc.ptr, ds.ptr, dn.ptr, do.ptr, None))
+    sync()
+    return do.numpy()
+
+
 # ---------------------------------------------------------------- Mask R-CNN op wrappers (tests / small inputs)
 NMS_GE, NMS_NO_PLUS_ONE, NMS_INDEX_ORDER = 1, 2, 4   # ISEGMI_NMS_* of include/isegmi.h (SURVEY App. A.6 forks)
 
@@ -805,6 +860,20 @@ def paste_masks(masks, boxes, counts, im_h, im_w, thr=0.5):
     dc = DeviceBuffer.from_numpy(np.ascontiguousarray(counts, np.int32)); do = DeviceBuffer((N, K, im_h, im_w), np.uint8)
     check(lib().isegmi_op_paste_masks(dm.ptr, db.ptr, dc.ptr, N, K, M, im_h, im_w, thr, do.ptr, None))
     return do.numpy()
+
+
+def paste_masks_win(masks, boxes, counts, im_h, im_w, thr=0.5, clear=False, planes=None, windows=None, want_windows=True):
+    """isegmi_op_paste_masks_win: the paste with the engines' forks.  planes [N,K,im_h,im_w] u8 and windows [N,K,4] i32 are the buffers' contents
+    BEFORE the launch (default: 0xA5 bytes, -1) -> (planes, windows or None) after it."""
+    masks = np.ascontiguousarray(masks, np.float32)
+    N, K, M, _ = masks.shape
+    dm = DeviceBuffer.from_numpy(masks); db = DeviceBuffer.from_numpy(np.ascontiguousarray(boxes, np.float32))
+    dc = DeviceBuffer.from_numpy(np.ascontiguousarray(counts, np.int32))
+    do = DeviceBuffer.from_numpy(_initial(planes, (N, K, im_h, im_w), np.uint8, 0xA5))
+    dwin = DeviceBuffer.from_numpy(_initial(windows, (N, K, 4), np.int32, -1)) if want_windows else None
+    check(lib().isegmi_op_paste_masks_win(dm.ptr, db.ptr, dc.ptr, N, K, M, im_h, im_w, thr, do.ptr, _ptr(dwin), int(bool(clear)), None))
+    sync()
+    return do.numpy(), (dwin.numpy() if want_windows else None)
 
 
 def rpn_level(head, anchors, image_hw, A, pre_nms, post_nms, nms_thr=0.7, min_size=0.0, nms_flags=0, chip_wide=True):

@@ -131,3 +131,34 @@ def test_rle_reads_only_the_windows(ffi):
             m = n * K + k
             ref = ora.rle_encode(clean[n, k, :hw[n, 0], :hw[n, 1]])
             assert np.array_equal(cn[ro[m]:ro[m + 1]], ref), (n, k)
+
+
+@pytest.mark.parametrize("M", [1025, 2100])
+def test_rle_more_than_1024_slots(ffi, M):
+    """rle_maskscan walks the slots 1024 at a time with a carried sum: the second (and third) trip, with slots without runs on both sides of the seam"""
+    rng = np.random.default_rng(M)
+    masks = (rng.uniform(0, 1, (M, 1, 8, 8)) < rng.uniform(0.1, 0.9, (M, 1, 1, 1))).astype(np.uint8)
+    masks[::7] = 0; masks[3::11] = 1                         # empty and full planes among them: one run, two runs
+    count = (rng.uniform(0, 1, M) < 0.8).astype(np.int32)    # N = M images of K = 1 slot: any slot can be without runs
+    count[[1023, 1024]] = 0
+    count[[1022, 1025 % M]] = 1
+    if M > 2048:
+        count[[2047, 2048]] = [1, 0]
+    _check(ffi, masks, count)
+    _check(ffi, masks.reshape(5, M // 5, 8, 8), np.array([M // 5, 0, M // 5 - 3, 1, M // 5], np.int32))   # K = 205 / 420 slots per image: ragged counts
+    hw = np.stack([rng.integers(1, 9, M), rng.integers(1, 9, M)], 1).astype(np.int32)
+    _check(ffi, masks, count, hw)
+
+
+def test_rle_more_than_1024_tiles(ffi):
+    """rle_tilescan walks the 1024-run tiles 1024 at a time with a carried sum: two 1024 x 1024 checkerboards hold more than 2^20 runs (2047 tiles);
+    counts and string bytes compared in bulk"""
+    board = (np.add.outer(np.arange(1024), np.arange(1024)) % 2).astype(np.uint8)
+    masks = np.stack([board, 1 - board])[None]
+    ro, cn, so, ch, st = ffi.rle_encode(masks)
+    refs = [ora.rle_encode(masks[0, k]) for k in range(2)]
+    strs = [ora.rle_to_string(r).encode("ascii") for r in refs]
+    assert st[2] == 0 and st[0] == len(refs[0]) + len(refs[1]) > 1024 * 1024
+    assert list(ro) == [0, len(refs[0]), st[0]] and list(so) == [0, len(strs[0]), len(strs[0]) + len(strs[1])] and st[1] == so[2]
+    assert np.array_equal(cn[:st[0]], np.concatenate(refs))
+    assert ch[:so[2]] == strs[0] + strs[1]
