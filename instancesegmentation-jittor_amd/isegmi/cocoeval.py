@@ -35,7 +35,8 @@ def _kpt_extent(kp):
 
 
 def _seg_counts(seg, h, w):
-    """A COCO `segmentation` field -> (run counts, (h, w)).  Polygons: the union of the parts (rleFrPoly + rleMerge)."""
+    """A COCO `segmentation` field -> (run counts, (h, w)).  Polygons: the union of the parts (rleFrPoly + rleMerge).
+    An RLE's counts are taken as they are: non-negative and adding up to h * w, zero-length runs included -- they cover no pixel."""
     if isinstance(seg, dict):
         sh, sw = (int(v) for v in seg["size"])
         c = seg["counts"]

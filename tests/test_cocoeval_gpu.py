@@ -222,3 +222,40 @@ def test_cli_coco_eval(ffi, tmp_path, capsys):
     e = cocoeval.COCOeval(gt, res, "bbox"); e.params.catIds = [1, 2]
     e.evaluate(); e.accumulate(); e.summarize()
     assert np.array_equal(only, e.stats)
+
+
+@pytest.mark.parametrize("as_string", [False, True])
+def test_zero_length_runs_leave_every_number_of_the_evaluation_alone(ffi, as_string):
+    """a zero-length run covers no pixel.  Every RLE of a data set -- gts and results -- rewritten with zero-length runs (runs split as
+    (a, 0, b), pairs of zeros put in anywhere, the front and the end included), as count lists or as compressed strings: IoUs, matches, areas, precision,
+    recall and the twelve numbers are those of the canonical encodings."""
+    import copy
+
+    import fuzz_cases as fc
+    from isegmi import cocoeval
+    gt, res = data.make_dataset(41, n_images=40)
+    rng = np.random.default_rng(41)
+    gt2, res2 = copy.deepcopy(gt), copy.deepcopy(res)
+    n = 0
+    for a in gt2["annotations"] + res2:
+        seg = a.get("segmentation")
+        if isinstance(seg, dict):
+            c = seg["counts"]
+            z = fc.same_mask_with_zero_runs(rng, coco.rle_from_string(c) if isinstance(c, str) else c)
+            assert 0 in z[1:] and np.array_equal(ref.dense(z, *seg["size"]), ref.seg_dense(seg, 0, 0))
+            seg["counts"] = coco.rle_to_string(z) if as_string else z
+            n += 1
+    assert n > 100
+    runs = []
+    for g, r in ((gt, res), (gt2, res2)):
+        e = cocoeval.COCOeval(cocoeval.COCOGt(g), r, "segm")
+        e.evaluate(); e.accumulate(); e.summarize()
+        runs.append(e)
+    plain, zeros = runs
+    assert sorted(plain.evalImgs) == sorted(zeros.evalImgs) and len(plain.evalImgs) > 40
+    for key, w in plain.evalImgs.items():
+        for name in ("dtScores", "dtMatches", "dtIgnore", "gtMatches", "gtIgnore", "ious"):
+            assert np.array_equal(zeros.evalImgs[key][name], w[name]), (key, name)
+    for name in ("precision", "recall", "scores"):
+        assert np.array_equal(zeros.eval[name], plain.eval[name]), name
+    assert np.array_equal(zeros.stats, plain.stats) and (plain.stats[:3] > 0).all()
